@@ -3,7 +3,7 @@
 2048 x 2048 k-mesh (BASELINE.json configs[2], the configuration the metric is
 quoted on), fp64, one process per GPU.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
 
 One "step" = one pass of the hot path over the mesh: H(k) assembly + Hermitian
 eigen-solve for every mesh point (eigenvectors written to the device-resident
@@ -12,12 +12,13 @@ over all plaquettes and its deterministic sum.  Inputs (model tables) are reside
 in HBM before the timed region; nothing crosses PCIe inside it.
 
 `value` = k-points of the K timed steps / wall time (max over ranks), exactly as the
-driver's contract asks.  Order on every rank: W warm-up steps | the K-step burst on the still-idle chip
+driver's contract asks.  Order on every rank: W warm-up steps | (--full only) the K-step burst on the still-idle chip
 (`cold_burst`, reported, not the value) | `--preheat-s` seconds (default 0.5) of the same step, untimed | barrier |
 the K timed steps | barrier.  An MI355X that has been idle needs more than 35 ms of work before its clocks
 are up (profiles/burst_vs_warmup.sh: the burst costs 73-77 us per step after 5 or 500 warm-up steps, 67 us
-after 3000); W = 5 steps are 0.4 ms.  Beside it, on ONE GPU, the same JSON line carries (all
-outside the timed region):
+after 3000); W = 5 steps are 0.4 ms.  A plain run stops there: it prints the line (value, ms_per_step and the
+per-kernel brackets sampled inside the timed steps, with their roofline).  With --full, on ONE GPU, the same JSON
+line also carries (all outside the timed region):
   roofline        dominant kernel: algorithmic bytes / average launch duration from HIP events on the
                   kernels' stream (the RAW bracket, event overhead included: conservative); valu_frac = VALU
                   issue-slot use at the fp64 rate from rocprofv3 instruction counts (profiles/valu.json);
@@ -30,6 +31,13 @@ outside the timed region):
                   flux + Wilson loops) and configs[4] (cubic16 256^3: solve + Berry phase), each with
                   HBM and VALU fractions
   cpu_baseline    the oracle's per-k Python loop on 1 host core and on all of them (os.cpu_count())
+  empty_bracket_ms  the cost of one empty HIP-event bracket (null in a plain run)
+
+--dump-outputs DIR writes what the timed path computed in its last step, as the caller of wf.solve_on_grid();
+wf.berry_flux([0]) receives it: DIR/min_gaps.npy and DIR/berry_flux.npy (float64; with N > 1 this rank's slab,
+names prefixed rank<r>_), and DIR/wfs_sample.npy, the eigenvectors of DUMP_POINTS mesh points drawn with a fixed
+seed (row-major point indices, sorted), as float64 (point, state, component, re/im).  The inputs are fixed, so two
+builds can be compared output for output.
 
 N > 1 (weak scaling): the global mesh is (2048*N + 1) x 2049; rank r owns the slab
 of 2048 plaquette rows starting at global row 2048*r and recomputes its one halo
@@ -63,6 +71,8 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 MESH = 2048                      # plaquette rows per rank and plaquettes per row
 N_STA = 2                        # Haldane: two orbitals
+DUMP_POINTS = 65536              # --dump-outputs: eigenvectors of this many mesh points (4 MB)
+DUMP_SEED = 0
 HBM_PEAK_GBS = 8000.0            # MI355X_MICROARCH.md: 8 TB/s spec
 FP64_VALU_PEAK_TFLOPS = 78.6     # vector fp64 peak: 256 CUs x 4 SIMDs x 16 lanes x 2 flop x 2.4 GHz
 VALU_SLOTS_PER_S = 256 * 4 * 2.4e9 / 4.0   # wave64 VALU instructions the chip can issue per second at the fp64 rate
@@ -182,6 +192,23 @@ def cpu_baseline(sample_mesh=257):
 
 
 # ---------------------------------------------------------------- helpers around the C ABI
+def wfs_sample(grid, npoints=DUMP_POINTS, seed=DUMP_SEED):
+    """Eigenvectors of a fixed, seeded sample of the slab's mesh points (row-major indices, sorted), downloaded from the
+    device-resident array: float64 (point, state, component, re/im)."""
+    total = int(np.prod(grid.mesh))
+    idx = np.sort(np.random.default_rng(seed).choice(total, size=min(npoints, total), replace=False)).astype(np.int64)
+    buf = np.zeros((len(idx), grid.n, grid.n), dtype=complex)
+    grid._lib.check(grid.lib.tbk_wfs_download_points(grid.h, idx.ctypes.data_as(C.POINTER(C.c_int64)), len(idx),
+                                                     grid._lib.dptr(buf.view(float))))
+    return np.ascontiguousarray(buf.view(float).reshape(len(idx), grid.n, grid.n, 2))
+
+
+def dump_outputs(d, prefix, arrays):
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(d, prefix + name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def Grid(*a, **k):
     """One rank's slab of the headline workload: the library's own slab driver (pythtb_amd/multi.py::GridSlab)."""
     from pythtb_amd import multi
@@ -524,12 +551,17 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also run every measurement beside the headline (CPU baseline, cold burst, "
+                    "sustained rate, per-kernel legs, fused extension, Python-API call, the other configs, empty-bracket cost); "
+                    "a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step to DIR/<name>.npy (float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--preheat-s", type=float, default=0.5,
                     help="seconds of the same step run back to back, untimed, between the W warm-up steps and the K timed ones: "
                          "an idle MI355X needs > 35 ms of work before its clocks are up (profiles/burst_vs_warmup.sh); "
-                         "0 = none.  The K-step burst WITHOUT it is in the line as cold_burst")
-    ap.add_argument("--headline-only", action="store_true", help="skip the sustained / python-API / other-config legs")
+                         "0 = none.  With --full the K-step burst WITHOUT it is in the line as cold_burst")
+    ap.add_argument("--headline-only", action="store_true", help="with --full: skip the sustained / python-API / other-config legs")
     ap.add_argument("--no-check", action="store_true", help="diagnostics: skip the Chern-number assertion")
     ap.add_argument("--two-calls", action="store_true", help=argparse.SUPPRESS)   # (kept for old command lines: now the default)
     ap.add_argument("--fused-headline", action="store_true", help="diagnostics: time the fused extension (tbk_wfs_solve_grid_flux_async) "
@@ -547,7 +579,7 @@ def main():
     args.gpus = world
 
     cpu = None
-    if world == 1 and not args.no_cpu_baseline and not args.stub:
+    if world == 1 and args.full and not args.no_cpu_baseline and not args.stub:
         cpu = cpu_baseline()                        # forks workers: must precede every GPU call of this process
 
     dist = None
@@ -617,25 +649,27 @@ def main():
 
     for _ in range(args.warmup):
         step()
-    # ---- the chip has been idle until now and W steps are ~0.4 ms of work: the same K-step burst here (kept in the line as
-    # cold_burst) runs ~10 % slower than any later one.  Then `--preheat-s` seconds of the same step, untimed.
+    # ---- the chip has been idle until now and W steps are ~0.4 ms of work: the same K-step burst here (--full: kept in the
+    # line as cold_burst) runs ~10 % slower than any later one.  Then `--preheat-s` seconds of the same step, untimed.
     preheat = None
     if args.preheat_s > 0 and not args.stub:
         barrier()
-        c0 = time.perf_counter()
-        for _ in range(args.steps):
-            step()
-        ctx.sync()
-        c1 = time.perf_counter()
+        preheat = {}
+        if args.full:
+            c0 = time.perf_counter()
+            for _ in range(args.steps):
+                step()
+            ctx.sync()
+            c1 = time.perf_counter()
+            preheat["cold_burst"] = {"steps": args.steps, "ms_per_step": 1e3 * (c1 - c0) / args.steps, "when": "right after the W warm-up steps"}
         n_pre, p0 = 0, time.perf_counter()
         while time.perf_counter() - p0 < args.preheat_s:
             for _ in range(200):
                 step()
             ctx.sync()
             n_pre += 200
-        preheat = {"cold_burst": {"steps": args.steps, "ms_per_step": 1e3 * (c1 - c0) / args.steps, "when": "right after the W warm-up steps"},
-                   "preheat": {"steps": n_pre, "seconds": time.perf_counter() - p0,
-                               "what": "the same step back to back, untimed, before the K timed steps (--preheat-s)"}}
+        preheat["preheat"] = {"steps": n_pre, "seconds": time.perf_counter() - p0,
+                              "what": "the same step back to back, untimed, before the K timed steps (--preheat-s)"}
     # HIP-event brackets on the kernels' own stream, inside the timed region.  A bracket
     # costs ~3 us of stream time (3 kernels x 2 events = 20% of a step), so every 7th
     # launch is bracketed: coprime with the 3 launches per step, every kernel is sampled
@@ -652,14 +686,20 @@ def main():
     ctx.prof_enable(False)
     elapsed = t1 - t0
     prof = ctx.prof_report()
-    ev_ms = ctx.prof_calibrate(50)                  # empty-bracket overhead, measured now (reported, not subtracted)
+    # empty-bracket overhead, measured now (reported, not subtracted)
+    ev_ms = ctx.prof_calibrate(50) if args.full else None
 
     # results of the last step (outside the timed region)
     gaps = grid.gaps()
     tot = grid.flux_total()
+    if args.dump_outputs:
+        arrays = {"min_gaps": gaps, "berry_flux": tot}
+        if not args.stub:
+            arrays["wfs_sample"] = wfs_sample(grid)
+        dump_outputs(args.dump_outputs, "rank%d_" % rank if world > 1 else "", arrays)
 
     extras = dict(preheat or {})
-    if world == 1 and not args.headline_only and not args.stub:
+    if world == 1 and args.full and not args.headline_only and not args.stub:
         # ---- sustained: at least one second of back-to-back steps (the K-step burst above is ~1.6 ms)
         n_sus = max(args.steps, int(math.ceil(1.2 / max(elapsed / args.steps, 1e-6))))
         ctx.sync()
@@ -765,7 +805,7 @@ def main():
             "value": nk_step * args.steps / t_max, "unit": "k-points/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": 1e3 * t_max / args.steps, "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+            "vs_baseline": None, "dtype": "f64", "data": "synthetic", "full": bool(args.full),
             "config": {"workload": "Haldane (2 orb, 9 hops) wf_array solve_on_grid + berry_flux([0]), "
                                    "%d x %d k-mesh per GPU (BASELINE.json configs[2])" % (MESH, MESH),
                        "step": "one fused pass (tbk_wfs_solve_grid_flux_async: eigenvectors written once, plaquette phases from registers)"

@@ -8,7 +8,8 @@ travels: only model tables (inputs) and the numbers the reference computes from
 them (expected outputs).  `--full` additionally runs the reference at the
 BASELINE.json config sizes C and D (about 20 minutes of CPU) and stores the
 scalars / small arrays in full_size.npz; `--full-E` does the same for configs[4]
-at 16^3 (full_size_E.npz).
+at 16^3 (full_size_E.npz).  `--live` writes live_reference.npz, the reference's
+outputs that test_oracle_live_against_imported_reference checks the oracle against.
 
 Models are built here through the reference's own public API, following the
 example scripts cited next to each builder.
@@ -433,7 +434,34 @@ def visualize_artists():
     print("visualize_artists.npz", len(out))
 
 
+def live_case():
+    """What test_oracle_live_against_imported_reference compares the oracle with: a 2-spin honeycomb model with seeded
+    random complex hoppings, its H(k) and eigenvalues at 9 random k, and a 9 x 8 wf_array's eigenvectors, gaps, plaquette
+    phases and Berry phases for every occupation / direction / contin / berry_evals combination."""
+    rng = np.random.default_rng(5)
+    m = quiet(ref.tb_model, 2, 2, LAT, ORB, nspin=2)
+    m.set_onsite([[0.3, 0.1, 0.2, -0.4], [-0.2, 0.0, 0.1, 0.3]])
+    for (i, j, R) in ((0, 1, [0, 0]), (0, 1, [1, -1]), (1, 1, [1, 0]), (0, 0, [0, 1]), (1, 0, [2, 1])):
+        m.set_hop(rng.standard_normal((2, 2)) + 1j * rng.standard_normal((2, 2)), i, j, R)
+    k = rng.uniform(-1, 1, size=(9, 2))
+    out = tables(m)
+    out.update(k=k, ham=np.array([m._gen_ham(kk) for kk in k]), evals=m.solve_all(k))
+    w = ref.wf_array(m, [9, 8])
+    out["min_gaps"] = w.solve_on_grid([0.1, 0.2])
+    out["wfs"] = np.array(w._wfs)
+    for io_, occ in enumerate(([0], [0, 1], [0, 1, 2, 3])):
+        out["plaq_occ%d" % io_] = w.berry_flux(occ, individual_phases=True)
+        for d in (0, 1):
+            for contin in (True, False):
+                for be in (True, False):
+                    out["phase_occ%d_dir%d_c%d_e%d" % (io_, d, contin, be)] = w.berry_phase(occ, d, contin=contin, berry_evals=be)
+    save("live_reference", **out)
+
+
 if __name__ == "__main__":
+    if "--live" in sys.argv:
+        live_case()
+        sys.exit(0)
     if "--visualize" in sys.argv:
         visualize_artists()
         sys.exit(0)

@@ -7,6 +7,7 @@ import subprocess
 import sys
 import time
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -87,6 +88,27 @@ def test_bench_starts_its_own_ranks(world):
     assert out["config"]["gather"] == "stub_allgather" and out["config"]["global_mesh"] == [2048 * world, 2048]
     assert abs(out["check"]["chern"] + 1.0) < 1e-12 and out["check"]["min_gap"] == 1.5
     assert abs(out["value"] - 2048 * 2048 * world * 4 / (out["ms_per_step"] * 4e-3)) < 1e-6 * out["value"]
+
+
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """A plain run (no --full) times the headline only and says so; --dump-outputs DIR writes every rank's last-step
+    results as float64 .npy files, the same from run to run."""
+    outs = []
+    for run in ("a", "b"):
+        d = tmp_path / run
+        res, lines = _bench(["--gpus", "2", "--steps", "3", "--warmup", "1", "--stub", "--dump-outputs", str(d)])
+        assert res.returncode == 0, res.stderr[-3000:]
+        out = json.loads(lines[0])
+        assert out["full"] is False and out["steps"] == 3 and out["ms_per_step"] > 0
+        for leg in ("cpu_baseline", "sustained", "fused_extension", "python_api", "configs", "cold_burst"):
+            assert leg not in out, leg
+        names = sorted(os.listdir(str(d)))
+        assert names == ["rank%d_%s.npy" % (r, n) for r in (0, 1) for n in ("berry_flux", "min_gaps")], names
+        arrs = {n: np.load(str(d / n)) for n in names}
+        assert all(a.dtype == np.float64 for a in arrs.values())
+        outs.append(arrs)
+    assert all(np.array_equal(outs[0][n], outs[1][n]) for n in outs[0])
+    assert abs(outs[0]["rank0_berry_flux.npy"][0] + outs[0]["rank1_berry_flux.npy"][0] + 2 * np.pi) < 1e-12
 
 
 def test_bench_multi_rank_control_flow_needs_no_torch(tmp_path):
