@@ -265,6 +265,25 @@ int tbk_solve_mesh(tbk_model* model, const int32_t* mesh, double* eval, double* 
 int tbk_dos_mesh(tbk_model* model, const int32_t* mesh, int nbins, const double* edges,
                  int64_t* counts, double* band_min, double* band_max);
 
+/* ---- Berry curvature by the Kubo formula ----------
+ * k in reduced coordinates, H the convention-II matrix of tbk_gen_ham.  No reference counterpart (PythTB 1.8 has only the
+ * link products of berry_flux); the quantities PythTB 2 and Wannier-interpolation codes call the Berry curvature.
+ * d_dir H(k) = sum_t amp 2 pi i (R + tau_j - tau_i)_dir exp(2 pi i k.(R + tau_j - tau_i)) for nk points:
+ * out[nk][nsta][nsta] c128, the layout of tbk_gen_ham.  dir in [0, dim_k).                                        */
+int tbk_gen_dham(tbk_model* model, const double* k, int64_t nk, int dir, double* out);
+/* Omega on a k list k[nk][dim_k], dirs (dir0, dir1) distinct in [0, dim_k), dim_k >= 2.
+ * occ == NULL: per band, out[nsta][nk], Omega_n = -2 Im sum_{m != n} V^a_nm V^b_mn / (E_n - E_m)^2 (pairs closer than
+ *              1e-9 max(1, |E_n|, |E_m|) left out);
+ * otherwise:   the manifold of the bands occ[nocc] (distinct, in [0, nsta)), out[nk], the sum over n in occ, m not in occ. */
+int tbk_berry_curv_list(tbk_model* model, const double* k, int64_t nk, int dir0, int dir1,
+                        const int32_t* occ, int nocc, double* out);
+/* Plane means of Omega over k_uniform_mesh(mesh) (dim_k 2 or 3), generated on the device: per band out[nsta] (occ NULL,
+ * nmu 0), manifold out[1] (occ given), or the T = 0 Fermi scan out[nmu], I(mu) = mean_k sum_{n: E_n(k) <= mu} Omega_n(k)
+ * for nmu (1..8192) levels mu[] in any order (occ NULL).  A 3-D mesh gains a trailing axis over the remaining mesh
+ * direction: out[..][N_rest].  Fixed-shape reductions: bit-reproducible.                                           */
+int tbk_berry_curv_mesh(tbk_model* model, const int32_t* mesh, int dir0, int dir1, const int32_t* occ,
+                        int nocc, int nmu, const double* mu, double* out);
+
 /* ---- multi-GPU: one process per GPU, k-points sharded, one gather ------
  * Thin RCCL wrappers (librccl is dlopen'ed on first use).  The 128-byte id is
  * created on rank 0 and distributed by the launcher (any out-of-band channel). */

@@ -424,6 +424,105 @@ class tb_model(object):
                                          counts.ctypes.data_as(_lib.C.POINTER(_lib.C.c_int64)), None, None))
         return (counts if per_band else counts.sum(axis=0)), edges
 
+    # ------------------------------------------------------------------ Berry curvature (extensions)
+    def _gen_dham(self, k_input, dir):
+        """Extension: dH/dk_dir for one k in reduced coordinates, with the shapes of `_gen_ham`
+        (`(norb, 2, norb, 2)` for spinful models): sum t 2 pi i (R + tau_j - tau_i)_dir e^{2 pi i k.(R + tau_j - tau_i)}."""
+        if self._dim_k < 1:
+            raise Exception("\n\n_gen_dham needs a model with dim_k >= 1")
+        if not _is_int(dir) or dir < 0 or dir >= self._dim_k:
+            raise Exception("\n\n_gen_dham: dir must be an axis in [0, dim_k)")
+        kp = np.array(k_input, dtype=float)
+        if kp.ndim == 0:
+            kp = kp.reshape(1)
+        if kp.shape != (self._dim_k,):
+            raise Exception("\n\nk-vector of wrong shape!")
+        k = np.ascontiguousarray(kp.reshape(1, -1))
+        n = self._nsta
+        out = np.zeros((1, n, n), dtype=complex)
+        _lib.check(_lib.lib.tbk_gen_dham(self._device_model(), _lib.dptr(k), 1, int(dir), _lib.dptr(out.view(float))))
+        if self._nspin == 1:
+            return out[0]
+        return out[0].reshape(self._norb, 2, self._norb, 2)
+
+    def _curv_args(self, occ, dirs):
+        """Checked (occ as int32 indices or None, dir0, dir1) of the curvature calls."""
+        if self._dim_k < 2:
+            raise Exception("\n\nThe Berry curvature needs a model with dim_k >= 2.")
+        dirs = list(dirs)
+        if len(dirs) != 2 or not all(_is_int(d) for d in dirs):
+            raise Exception("\n\ndirs must be two integer axes.")
+        if dirs[0] == dirs[1]:
+            raise Exception("\n\nNeed to specify two different directions for the Berry curvature.")
+        if min(dirs) < 0 or max(dirs) >= self._dim_k:
+            raise Exception("\n\nDirection for the Berry curvature out of bounds.")
+        if occ is None:
+            return None, int(dirs[0]), int(dirs[1])
+        sel = np.arange(self._nsta)[occ]                 # a NumPy fancy index, as wf_array.berry_flux reads it (IndexError)
+        sel = np.atleast_1d(sel).ravel()
+        if sel.size == 0:
+            raise Exception("\n\nocc selects no band.")
+        if np.unique(sel).size != sel.size:
+            raise Exception("\n\nocc lists a band twice.")
+        return np.ascontiguousarray(sel, dtype=np.int32), int(dirs[0]), int(dirs[1])
+
+    def berry_curvature(self, k_list, occ=None, dirs=(0, 1)):
+        """Extension: the Berry curvature by the Kubo formula at every k of `k_list` (reduced coordinates, as solve_all).
+
+        occ=None: per band, float64 `(nsta, nk)` (the layout of solve_all's eigenvalues),
+            Omega_n(k) = -2 Im sum_{m != n} <n|dH_a|m><m|dH_b|n> / (E_n - E_m)^2,  (a, b) = dirs;
+            a pair with |E_n - E_m| <= 1e-9 max(1, |E_n|, |E_m|) contributes to neither band.
+        occ given (a NumPy index of bands): the gauge-invariant curvature of that band set, `(nk,)`,
+            -2 Im sum_{n in occ, m not in occ} (same terms) -- what berry_flux(occ, dirs) measures per plaquette.  It is not
+            finite (or huge) where a band of occ touches one outside it, as berry_flux is meaningless there.
+        Reduced units: the mean over a uniform (a, b) mesh divided by 2 pi is the Chern number.  The Cartesian curvature of a
+        2-D cell of area A (dirs spanning it) is Omega_xy = Omega A / (2 pi)^2, in the length unit of the lattice vectors."""
+        sel, d0, d1 = self._curv_args(occ, dirs)
+        k = self._k_array(k_list)
+        nk = k.shape[0]
+        n = self._nsta
+        out = np.zeros(nk if sel is not None else (n, nk), dtype=float)
+        if nk == 0:
+            return out
+        _lib.check(_lib.lib.tbk_berry_curv_list(self._device_model(), _lib.dptr(k), nk, d0, d1, _lib.iptr(sel),
+                                                0 if sel is None else len(sel), _lib.dptr(out)))
+        return out
+
+    def berry_curvature_mesh(self, mesh_size, occ=None, dirs=(0, 1), fermi_levels=None):
+        """Extension: means of the Berry curvature over `k_uniform_mesh(mesh_size)` (generated on the device), i.e. BZ
+        integrals in reduced units -- divided by 2 pi, the Chern number of a gapped set.
+
+        2-D mesh: occ given -> a float (the band set's integral); occ=None -> per band `(nsta,)`;
+            fermi_levels (1-D, at most 8192 values, any order) -> `(nmu,)` in input order,
+            I(mu) = mean_k sum_{n: E_n(k) <= mu} Omega_n(k), the T = 0 anomalous-Hall integral (sigma_xy = -(e^2/h) I / 2 pi
+            per layer).
+        3-D mesh: every result gains a trailing axis over the mesh direction that is not in dirs, one (dirs) plane per slice.
+        Curvatures as in `berry_curvature`; the reductions have a fixed order, so two calls give the same bits."""
+        sel, d0, d1 = self._curv_args(occ, dirs)
+        mesh, nk = self._mesh_arg(mesh_size)
+        if self._dim_k not in (2, 3):
+            raise Exception("\n\nberry_curvature_mesh needs a 2-D or 3-D mesh.")
+        mu = None
+        if fermi_levels is not None:
+            if sel is not None:
+                raise Exception("\n\nGive either occ or fermi_levels, not both.")
+            mu = np.ascontiguousarray(np.array(fermi_levels, dtype=float))
+            if mu.ndim != 1 or mu.size < 1 or mu.size > 8192:
+                raise Exception("\n\nfermi_levels must be a 1-D array of 1..8192 levels.")
+            if not np.all(np.isfinite(mu)):
+                raise Exception("\n\nfermi_levels must be finite.")
+        n = self._nsta
+        nch = mu.size if mu is not None else (1 if sel is not None else n)
+        nslice = 1 if self._dim_k == 2 else int(mesh[3 - d0 - d1])
+        out = np.zeros((nch, nslice), dtype=float)
+        _lib.check(_lib.lib.tbk_berry_curv_mesh(self._device_model(), _lib.iptr(mesh), d0, d1, _lib.iptr(sel),
+                                                0 if sel is None else len(sel), 0 if mu is None else mu.size,
+                                                _lib.dptr(mu), _lib.dptr(out)))
+        if self._dim_k == 2:
+            out = out[:, 0]
+            return float(out[0]) if sel is not None else out
+        return out[0] if sel is not None else out
+
     # ------------------------------------------------------------------ position operator
     def ignore_position_operator_offdiagonal(self):
         self._assume_position_operator_diagonal = True
