@@ -284,6 +284,19 @@ int tbk_berry_curv_list(tbk_model* model, const double* k, int64_t nk, int dir0,
 int tbk_berry_curv_mesh(tbk_model* model, const int32_t* mesh, int dir0, int dir1, const int32_t* occ,
                         int nocc, int nmu, const double* mu, double* out);
 
+/* ---- interband optical conductivity by the Kubo formula ----------
+ * k reduced, H the convention-II matrix of tbk_gen_ham, V^a = d_a H (tbk_gen_dham), E_n, |n> the eigenpairs of the solver,
+ * f_n = [E_n <= mu] for kT = 0, else 1 / (1 + exp((E_n - mu) / kT)); the mean over k_uniform_mesh(mesh) (dim_k 1..3, N_k points):
+ *   S_ab(w) = (i / N_k) sum_k sum_{n != m} [(f_m - f_n) / (E_m - E_n)] V^a_nm V^b_mn / (E_m - E_n - w - i eta)
+ * pairs with |E_m - E_n| <= 1e-9 max(1, |E_n|, |E_m|) left out (interband only), time dependence e^{-i w t}, no spin factor.
+ * Reduced units: sigma = A^T S A / ((2 pi)^2 V_c) in e^2/hbar x length^(2 - dim_k), A the periodic lattice vectors as rows,
+ * V_c = sqrt(det(A A^T)); at w -> 0 the antisymmetric part Re (S_ab - S_ba) / 2 is minus the Fermi scan of tbk_berry_curv_mesh.
+ * nomega (1..65536) finite frequencies omega[] in any order, eta > 0, kT >= 0, all finite.  dir0 = dir1 = -1: the full tensor,
+ * out[nomega][dim_k][dim_k] c128; otherwise the one component S_{dir0 dir1}, out[nomega] c128 (dir0 == dir1 allowed).
+ * Fixed partitions, no atomics: bit-reproducible.                                                                          */
+int tbk_optical_cond_mesh(tbk_model* model, const int32_t* mesh, int nomega, const double* omega, double eta, double mu,
+                          double kT, int dir0, int dir1, double* out);
+
 /* ---- multi-GPU: one process per GPU, k-points sharded, one gather ------
  * Thin RCCL wrappers (librccl is dlopen'ed on first use).  The 128-byte id is
  * created on rank 0 and distributed by the launcher (any out-of-band channel). */

@@ -1,0 +1,522 @@
+// tbk_optics.hip -- interband optical conductivity on uniform meshes by the Kubo formula.
+//
+// k in reduced coordinates, H the convention-II matrix of tbk_gen_ham, V^d = d_d H (tbk_gen_dham), E_n and |n> the eigenpairs of
+// the solver, f_n = [E_n <= mu] (kT = 0) or 1 / (1 + exp((E_n - mu) / kT)):
+//   S_ab(w) = (i / N_k) sum_k sum_{n != m} [(f_m - f_n) / (E_m - E_n)] V^a_nm V^b_mn / (E_m - E_n - w - i eta)
+// pairs with |E_m - E_n| <= 1e-9 max(1, |E_n|, |E_m|) left out (the rule of tbk_curv.hip: interband only).
+// Per unordered pair n < m, eps = E_m - E_n >= 0, c = (f_m - f_n) / eps and P_ab = V^a_nm V^b_mn (P_ba = conj P_ab):
+//   S_ab += i c Re(P_ab) G+ - c Im(P_ab) G-,   g+- = 1 / (+-eps - w - i eta),  G+ = g+ + g-,  G- = g+ - g-
+// so a pair is a RECORD of 1 + ns + na doubles: eps (-1: the pair adds nothing), the symmetric weights A = c Re P_ab (a <= b) and
+// the antisymmetric ones B = c Im P_ab (a < b) of the components asked for.
+//
+// Pipeline, in chunks of a fixed number of points (kOptChunkBytes of eigenvectors, kOptRecBytes of records): the device k generator,
+// the eigen-solver with vectors, then the PAIR stage writes the chunk's records at a fixed stride of n (n - 1) / 2 per point
+//   n <= 32    k_opt_pairs: U, d_d H for every direction asked for, and V^d = conj(U) d_d H U^T of several points in LDS
+//   n > 32     k_opt_wsp (W^d = d_d H U^T from the sparse slots), k_opt_vprod (V^d = conj(U) W^d, LDS tiles), k_opt_pairs_wide
+// and the FREQUENCY stage k_opt_omega (two frequencies per lane, the records read as wave-uniform values) adds each k-group's sums
+// into part[G][row]; k_opt_rows sums the G groups in a fixed order.  Every partition depends on the mesh, n, dim_k, n_omega and the
+// components alone, and nothing uses atomics: two calls give the same bits on any machine.
+#include <math.h>
+#include <string.h>
+#include <algorithm>
+#include <cmath>
+#include <vector>
+#include "tbk_dham.h"
+
+static const size_t kOptChunkBytes = (size_t)32 << 20;   // eigenvectors per chunk (the budget of section 11)
+static const size_t kOptRecBytes = (size_t)256 << 20;    // pair records per chunk
+static const int kOptTile = 512;                         // frequencies per workgroup of k_opt_omega (two per lane)
+static const int64_t kOptPartCap = (int64_t)1 << 24;     // doubles of part[G][rows]: G shrinks as the frequencies grow
+static const int kOptGroupsMax = 1024;                   // k-groups G at most
+#define OPT_LDS_CD 5120                                  // c128 of LDS per workgroup of k_opt_pairs at most (80 KiB)
+
+// The components of one call: the velocity matrices of nd directions dir[] are formed; record field f < ns is A of the direction
+// pair (dir[fa[f]], dir[fb[f]]), field ns + f is B of (dir[fa[ns + f]], dir[fb[ns + f]]).
+struct OptFields {
+    int nd;
+    int dir[3];
+    int ns, na;
+    int fa[9], fb[9];
+};
+
+// the pair (i, j), i < j, of index q in the row-major order of the strict upper triangle of n x n
+__device__ __forceinline__ void opt_pair_of(const int n, const int64_t q, int& i, int& j) {
+    const double t = 2.0 * n - 1.0;
+    int r = (int)((t - sqrt(fmax(t * t - 8.0 * (double)q, 0.0))) * 0.5);
+    r = max(0, min(r, n - 2));
+    while (r > 0 && (int64_t)r * (2 * n - r - 1) / 2 > q) --r;
+    while (r < n - 2 && (int64_t)(r + 1) * (2 * n - r - 2) / 2 <= q) ++r;
+    i = r;
+    j = (int)(q - (int64_t)r * (2 * n - r - 1) / 2) + r + 1;
+}
+
+// c = (f_m - f_n) / eps for E_m = E_n + eps, eps > 0.  kT > 0: with h = eps / 2kT and u = ((E_n + E_m) / 2 - mu) / kT,
+// f_m - f_n = -sinh h / (cosh h + cosh u), evaluated as exp(h - M) expm1(-2h) / (e^{h-M} + e^{-h-M} + e^{|u|-M} + e^{-|u|-M}),
+// M = max(h, |u|): no cancellation for close levels, no overflow far from mu.
+__device__ __forceinline__ double opt_weight(const double en, const double em, const double eps, const double mu, const double kT) {
+    if (kT == 0.0) return (en <= mu && !(em <= mu)) ? -1.0 / eps : 0.0;
+    const double h = 0.5 * eps / kT, u = fabs((0.5 * (en + em) - mu) / kT), M = fmax(h, u);
+    const double den = exp(h - M) + exp(-h - M) + exp(u - M) + exp(-u - M);
+    return exp(h - M) * expm1(-2.0 * h) / den / eps;
+}
+
+// one record at r: vel(d, 0) = V^{dir[d]}_nm, vel(d, 1) = V^{dir[d]}_mn
+template <class Vel>
+__device__ __forceinline__ void opt_record(double* __restrict__ r, const OptFields& F, const double en, const double em, const double mu,
+                                           const double kT, const Vel& vel) {
+    const double eps = em - en;
+    const bool keep = eps > 1e-9 * fmax(1.0, fmax(fabs(en), fabs(em)));
+    const double c = keep ? opt_weight(en, em, eps, mu, kT) : 0.0;
+    const int nf = F.ns + F.na;
+    if (c == 0.0) {
+        r[0] = -1.0;
+        for (int f = 0; f < nf; ++f) r[1 + f] = 0.0;
+        return;
+    }
+    r[0] = eps;
+    for (int f = 0; f < nf; ++f) {
+        const cd p = cmul(vel(F.fa[f], 0), vel(F.fb[f], 1));   // V^a_nm V^b_mn
+        r[1 + f] = c * (f < F.ns ? p.x : p.y);
+    }
+}
+
+// ---------------------------------------------------------------- pair stage, 1 .. 32 states
+// P points per workgroup; per point U (its eigenvectors, read once from HBM) and nd + 1 matrices in LDS.  For direction d, buffer d
+// takes d_d H (from the non-empty slots), buffer d + 1 takes T = d_d H U^T, then buffer d := V^d = conj(U) T; after the last
+// direction buffers 0 .. nd - 1 hold V^0 .. V^{nd-1}.  One lane per (point, pair) then writes the records.
+static inline int opt_lds_points(int n, int nd) { return std::max(1, std::min(64, OPT_LDS_CD / ((nd + 2) * n * n))); }
+__global__ __launch_bounds__(256) void k_opt_pairs(const ModelView mv, const double* __restrict__ k, const cd* __restrict__ evec,
+                                                   const double* __restrict__ eval, const int64_t nk, const OptFields F, const int P,
+                                                   const double mu, const double kT, double* __restrict__ rec) {
+    extern __shared__ cd L[];
+    const int n = mv.nsta, nn = n * n, nd = F.nd;
+    const int64_t ik0 = (int64_t)blockIdx.x * P;
+    const int np = (int)std::min<int64_t>(P, nk - ik0);
+    cd* U = L;
+    cd* Bf = L + P * nn;                                           // buffer j at Bf + j P nn, j = 0 .. nd
+    for (int e = threadIdx.x; e < np * nn; e += 256) {
+        const int p = e / nn, r = e - p * nn, b = r / n, i = r - b * n;
+        U[e] = evec[((int64_t)b * nk + ik0 + p) * n + i];
+    }
+    for (int d = 0; d < nd; ++d) {
+        cd* S = Bf + d * P * nn;
+        cd* T = Bf + (d + 1) * P * nn;
+        for (int e = threadIdx.x; e < np * nn; e += 256) S[e] = cd{0.0, 0.0};
+        __syncthreads();
+        for (int e = threadIdx.x; e < np * mv.nnz; e += 256) {
+            const int p = e / mv.nnz;
+            const int4 z4 = mv.nz[e - p * mv.nnz];
+            const int a = z4.x & 0xffff, b = z4.x >> 16;
+            double kk[4];
+            cd z[4];
+            k_phases(mv, k, ik0 + p, kk, z);
+            cd h, v0, v1;
+            dham_terms(mv, a, b, z4.y, z4.z, kk, z, F.dir[d], F.dir[d], h, v0, v1);
+            S[p * nn + a * n + b] = v0;
+            S[p * nn + b * n + a] = cconj(v0);
+        }
+        __syncthreads();
+        for (int e = threadIdx.x; e < np * nn; e += 256) {        // T = d_d H U^T
+            const int p = e / nn, r = e - p * nn, i = r / n, mm = r - i * n;
+            const cd* dr = S + p * nn + i * n;
+            const cd* um = U + p * nn + mm * n;
+            cd acc{0.0, 0.0};
+            for (int j = 0; j < n; ++j) cfma(acc, dr[j], um[j]);
+            T[e] = acc;
+        }
+        __syncthreads();
+        for (int e = threadIdx.x; e < np * nn; e += 256) {        // S := V^d = conj(U) T
+            const int p = e / nn, r = e - p * nn, b = r / n, mm = r - b * n;
+            const cd* ub = U + p * nn + b * n;
+            const cd* tc = T + p * nn + mm;
+            cd acc{0.0, 0.0};
+            for (int i = 0; i < n; ++i) cfmac(acc, ub[i], tc[i * n]);
+            S[e] = acc;
+        }
+        __syncthreads();
+    }
+    const int npair = n * (n - 1) / 2, R = 1 + F.ns + F.na;
+    for (int e = threadIdx.x; e < np * npair; e += 256) {
+        const int p = e / npair, q = e - p * npair;
+        int i, j;
+        opt_pair_of(n, q, i, j);
+        const int64_t ik = ik0 + p;
+        const double ei = eval[(int64_t)i * nk + ik], ej = eval[(int64_t)j * nk + ik];
+        const bool sw = ej < ei;                                   // (n, m) of the formula: E_m >= E_n
+        const int a = sw ? j : i, b = sw ? i : j;
+        const cd* V = Bf + p * nn;
+        opt_record(rec + (ik * npair + q) * R, F, sw ? ej : ei, sw ? ei : ej, mu, kT, [&](const int d, const int mn) {
+            return mn ? V[d * P * nn + b * n + a] : V[d * P * nn + a * n + b];
+        });
+    }
+}
+
+// ---------------------------------------------------------------- pair stage, 33 .. 2048 states
+// W^d[ik][i][m] = sum_j d_d H_ij u_m[j] of the nd directions from the non-empty slots (the form of k_curv_wsp): workgroup (point, block
+// of 256 columns), lane m owns column m of every W^d; the slot values are computed once per point and staged in LDS.  wt[ik][d][n][n].
+__global__ __launch_bounds__(256) void k_opt_wsp(const ModelView mv, const double* __restrict__ k, const cd* __restrict__ evec,
+                                                 const int64_t nk, const OptFields F, cd* __restrict__ wt) {
+    __shared__ int sab[256];
+    __shared__ cd sv[3][256];
+    const int n = mv.nsta, nd = F.nd;
+    const int64_t ik = blockIdx.x, nn = (int64_t)n * n;
+    const int m = blockIdx.y * 256 + threadIdx.x;
+    const bool live = m < n;
+    cd* w = wt + ik * nd * nn;
+    if (live)
+        for (int d = 0; d < nd; ++d)
+            for (int i = 0; i < n; ++i) w[d * nn + (int64_t)i * n + m] = cd{0.0, 0.0};
+    double kk[4];
+    cd z[4];
+    k_phases(mv, k, ik, kk, z);
+    const cd* u = evec + ((int64_t)(live ? m : 0) * nk + ik) * n;
+    for (int q0 = 0; q0 < mv.nnz; q0 += 256) {
+        __syncthreads();
+        if (q0 + (int)threadIdx.x < mv.nnz) {
+            const int4 z4 = mv.nz[q0 + threadIdx.x];
+            for (int d = 0; d < nd; d += 2) {
+                cd h, v0, v1;
+                const int d1 = d + 1 < nd ? d + 1 : d;
+                dham_terms(mv, z4.x & 0xffff, z4.x >> 16, z4.y, z4.z, kk, z, F.dir[d], F.dir[d1], h, v0, v1);
+                sv[d][threadIdx.x] = v0;
+                if (d + 1 < nd) sv[d + 1][threadIdx.x] = v1;
+            }
+            sab[threadIdx.x] = z4.x;
+        }
+        __syncthreads();
+        const int cnt = min(256, mv.nnz - q0);
+        if (!live) continue;
+        for (int q = 0; q < cnt; ++q) {
+            const int a = sab[q] & 0xffff, b = sab[q] >> 16;
+            const cd ub = u[b], ua = u[a];
+            for (int d = 0; d < nd; ++d) {
+                const cd v = sv[d][q];
+                cd* pa = w + d * nn + (int64_t)a * n + m;
+                cd t = *pa;
+                cfma(t, v, ub);
+                *pa = t;
+                if (a != b) {
+                    cd* pb = w + d * nn + (int64_t)b * n + m;
+                    cd s = *pb;
+                    cfma(s, cconj(v), ua);
+                    *pb = s;
+                }
+            }
+        }
+    }
+}
+
+// V^d = conj(U) W^d for every (point, direction) z = ik nd + d (blockIdx.z): 16 x 16 output tiles, the 16-wide slices of conj(U) and
+// W^d staged in LDS.  vt[ik][d][n][n], V^d[b][m] = <b| d_d H |m>.
+__global__ __launch_bounds__(256) void k_opt_vprod(const cd* __restrict__ evec, const cd* __restrict__ wt, const int64_t nk, const int n,
+                                                   const int nd, cd* __restrict__ vt) {
+    __shared__ cd Ut[16][17], Wt[16][17];
+    const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
+    const int64_t zi = blockIdx.z, nn = (int64_t)n * n;
+    const int64_t ik = zi / nd;
+    const int row = blockIdx.y * 16 + ty, col = blockIdx.x * 16 + tx;
+    const cd* w = wt + zi * nn;
+    cd acc{0.0, 0.0};
+    for (int k0 = 0; k0 < n; k0 += 16) {
+        const int uc = k0 + tx, wr = k0 + ty;
+        Ut[ty][tx] = (row < n && uc < n) ? evec[((int64_t)row * nk + ik) * n + uc] : cd{0.0, 0.0};
+        Wt[ty][tx] = (wr < n && col < n) ? w[(int64_t)wr * n + col] : cd{0.0, 0.0};
+        __syncthreads();
+#pragma unroll
+        for (int q = 0; q < 16; ++q) cfmac(acc, Ut[ty][q], Wt[q][tx]);
+        __syncthreads();
+    }
+    if (row < n && col < n) vt[zi * nn + (int64_t)row * n + col] = acc;
+}
+
+// one lane per (point, pair): the records from vt
+__global__ __launch_bounds__(256) void k_opt_pairs_wide(const double* __restrict__ eval, const cd* __restrict__ vt, const int64_t nk,
+                                                        const int n, const OptFields F, const double mu, const double kT,
+                                                        double* __restrict__ rec) {
+    const int64_t npair = (int64_t)n * (n - 1) / 2, nn = (int64_t)n * n;
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= nk * npair) return;
+    const int64_t ik = idx / npair, q = idx - ik * npair;
+    int i, j;
+    opt_pair_of(n, q, i, j);
+    const double ei = eval[(int64_t)i * nk + ik], ej = eval[(int64_t)j * nk + ik];
+    const bool sw = ej < ei;
+    const int a = sw ? j : i, b = sw ? i : j;
+    const cd* V = vt + ik * F.nd * nn;
+    opt_record(rec + idx * (1 + F.ns + F.na), F, sw ? ej : ei, sw ? ei : ej, mu, kT, [&](const int d, const int mn) {
+        return mn ? V[d * nn + (int64_t)b * n + a] : V[d * nn + (int64_t)a * n + b];
+    });
+}
+
+// ---------------------------------------------------------------- frequency stage
+// 1 / x by v_rcp_f64 and two Newton steps (x > 0, normal)
+__device__ __forceinline__ double opt_rcp(const double x) {
+    double r = __builtin_amdgcn_rcp(x);
+    double e = fma(-x, r, 1.0);
+    r = fma(r, e, r);
+    e = fma(-x, r, 1.0);
+    return fma(r, e, r);
+}
+
+// Workgroup (tile of kOptTile frequencies, k-group g): lane t takes w[tile + t] and w[tile + 256 + t] and walks the records of the
+// points [g nk / G, (g + 1) nk / G) of the chunk in order.  Per lane and frequency the sums
+//   x_f = sum A_f G+.x (f < NS) or B_f G-.x,   y_f = sum A_f (r+ + r-) or B_f (r+ - r-)     (G+-.y = eta (r+ +- r-))
+// go to part[g][row], row = (2 f + {0: x, 1: y}) nw + w: written by the first chunk, added to by the later ones (stream order).
+template <int NS, int NA>
+__global__ __launch_bounds__(256) void k_opt_omega(const double* __restrict__ rec, const int64_t nk, const int64_t npair, const int G,
+                                                   const double* __restrict__ omega, const int nw, const double eta,
+                                                   const int accumulate, double* __restrict__ part) {
+    constexpr int NF = NS + NA, R = 1 + NF;
+    const int base = blockIdx.x * kOptTile;
+    if (base + (int)(threadIdx.x & ~63u) >= nw) return;            // a wavefront without a frequency (uniform)
+    const int g = blockIdx.y;
+    int wi[2];
+    double om[2];
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+        wi[s] = base + s * 256 + threadIdx.x;
+        om[s] = wi[s] < nw ? omega[wi[s]] : 0.0;
+    }
+    double sx[2][NF], sy[2][NF];
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+#pragma unroll
+        for (int f = 0; f < NF; ++f) sx[s][f] = sy[s][f] = 0.0;
+    const double eta2 = eta * eta;
+    const int64_t r0 = (int64_t)g * nk / G * npair, r1 = (int64_t)(g + 1) * nk / G * npair;
+    const double* __restrict__ p = rec + r0 * R;
+    for (int64_t r = r0; r < r1; ++r, p += R) {
+        double v[R];
+#pragma unroll
+        for (int f = 0; f < R; ++f) v[f] = p[f];
+        if (v[0] < 0.0) continue;                                  // c = 0 or a degenerate pair (uniform branch)
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            const double xp = v[0] - om[s], xm = -v[0] - om[s];
+            const double rp = opt_rcp(fma(xp, xp, eta2)), rm = opt_rcp(fma(xm, xm, eta2));
+            const double gp = xp * rp, gm = xm * rm;
+            const double Gpx = gp + gm, Gmx = gp - gm, Gpy = rp + rm, Gmy = rp - rm;
+#pragma unroll
+            for (int f = 0; f < NS; ++f) {
+                sx[s][f] = fma(v[1 + f], Gpx, sx[s][f]);
+                sy[s][f] = fma(v[1 + f], Gpy, sy[s][f]);
+            }
+#pragma unroll
+            for (int f = NS; f < NF; ++f) {
+                sx[s][f] = fma(v[1 + f], Gmx, sx[s][f]);
+                sy[s][f] = fma(v[1 + f], Gmy, sy[s][f]);
+            }
+        }
+    }
+    double* out = part + (int64_t)g * 2 * NF * nw;
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+        if (wi[s] >= nw) continue;
+#pragma unroll
+        for (int f = 0; f < NF; ++f) {
+            double* px = out + (int64_t)(2 * f) * nw + wi[s];
+            double* py = px + nw;
+            *px = accumulate ? *px + sx[s][f] : sx[s][f];
+            *py = accumulate ? *py + sy[s][f] : sy[s][f];
+        }
+    }
+}
+
+// sum over the 256 threads of a workgroup in a fixed order (shuffle tree in each wavefront, then the four in order); thread 0 has it
+__device__ __forceinline__ double opt_block_sum(double v, double* red) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// rows[r] = inv sum_g part[g][r] in a fixed order (one workgroup per row)
+__global__ __launch_bounds__(256) void k_opt_rows(const double* __restrict__ part, const int G, const int64_t nrows, const double inv,
+                                                  double* __restrict__ rows) {
+    __shared__ double red[4];
+    double acc = 0.0;
+    for (int g = threadIdx.x; g < G; g += 256) acc += part[(int64_t)g * nrows + blockIdx.x];
+    const double t = opt_block_sum(acc, red);
+    if (threadIdx.x == 0) rows[blockIdx.x] = t * inv;
+}
+
+// ---------------------------------------------------------------- host side
+static inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
+static inline unsigned nblk(int64_t threads) { return (unsigned)((threads + 255) / 256); }
+
+template <int NS, int NA>
+static int opt_omega_launch(tbk_ctx* ctx, dim3 grid, const double* rec, int64_t cnt, int64_t npair, int G, const double* om, int nw,
+                            double eta, int accumulate, double* part) {
+    hipLaunchKernelGGL((k_opt_omega<NS, NA>), grid, dim3(256), 0, ctx->stream, rec, cnt, npair, G, om, nw, eta, accumulate, part);
+    TBK_HIP(hipGetLastError());
+    return TBK_OK;
+}
+
+extern "C" int tbk_optical_cond_mesh(tbk_model* m, const int32_t* mesh, int nomega, const double* omega, double eta, double mu,
+                                     double kT, int dir0, int dir1, double* out) {
+    TBK_REQUIRE(m && mesh && omega && out, TBK_EINVAL, "tbk_optical_cond_mesh: null argument");
+    const int dk = m->dim_k;
+    TBK_REQUIRE(dk >= 1 && dk <= 3, TBK_EINVAL, "tbk_optical_cond_mesh: dim_k=%d (meshes of 1, 2 or 3 dimensions)", dk);
+    TBK_REQUIRE(nomega >= 1 && nomega <= 65536, TBK_EINVAL, "tbk_optical_cond_mesh: nomega=%d (1..65536 frequencies)", nomega);
+    for (int j = 0; j < nomega; ++j)
+        TBK_REQUIRE(std::isfinite(omega[j]), TBK_EINVAL, "tbk_optical_cond_mesh: frequency %d is not finite", j);
+    TBK_REQUIRE(std::isfinite(eta) && eta > 0.0, TBK_EINVAL, "tbk_optical_cond_mesh: eta must be finite and > 0");
+    TBK_REQUIRE(std::isfinite(kT) && kT >= 0.0, TBK_EINVAL, "tbk_optical_cond_mesh: kT must be finite and >= 0");
+    TBK_REQUIRE(std::isfinite(mu), TBK_EINVAL, "tbk_optical_cond_mesh: the Fermi level must be finite");
+    const bool full = dir0 == -1 && dir1 == -1;
+    TBK_REQUIRE(full || (dir0 >= 0 && dir0 < dk && dir1 >= 0 && dir1 < dk), TBK_EINVAL,
+                "tbk_optical_cond_mesh: dirs (%d, %d) must be axes in [0, %d), or both -1 for the full tensor", dir0, dir1, dk);
+    int64_t npts = 1;
+    for (int d = 0; d < dk; ++d) {
+        TBK_REQUIRE(mesh[d] >= 1, TBK_EINVAL, "tbk_optical_cond_mesh: mesh[%d]=%d", d, mesh[d]);
+        npts *= mesh[d];
+    }
+    const int n = m->nsta;
+    const int64_t npair = (int64_t)n * (n - 1) / 2;
+    const int64_t nout = full ? (int64_t)nomega * dk * dk : (int64_t)nomega;   // complex values
+    if (npair == 0) {
+        std::fill(out, out + 2 * nout, 0.0);
+        return TBK_OK;
+    }
+    // the components: full tensor -> A of every a <= b, B of every a < b; one component -> A (and B when a != b)
+    OptFields F{};
+    if (full) {
+        F.nd = dk;
+        for (int d = 0; d < dk; ++d) F.dir[d] = d;
+        for (int a = 0; a < dk; ++a)
+            for (int b = a; b < dk; ++b) F.fa[F.ns] = a, F.fb[F.ns] = b, ++F.ns;
+        for (int a = 0; a < dk; ++a)
+            for (int b = a + 1; b < dk; ++b) F.fa[F.ns + F.na] = a, F.fb[F.ns + F.na] = b, ++F.na;
+    } else if (dir0 == dir1) {
+        F.nd = 1;
+        F.dir[0] = dir0;
+        F.ns = 1;
+        F.fa[0] = F.fb[0] = 0;
+    } else {
+        F.nd = 2;
+        F.dir[0] = dir0;
+        F.dir[1] = dir1;
+        F.ns = F.na = 1;
+        F.fa[0] = F.fa[1] = 0;
+        F.fb[0] = F.fb[1] = 1;
+    }
+    const int nf = F.ns + F.na, R = 1 + nf;
+    // chunk, k-groups and tiles: functions of (mesh, n, dim_k, nomega, components) only
+    const size_t vb = (size_t)n * n * sizeof(cd), rb = (size_t)npair * R * sizeof(double);
+    int64_t chunk = std::max<int64_t>(1, std::min<int64_t>((int64_t)(kOptChunkBytes / vb), (int64_t)(kOptRecBytes / rb)));
+    chunk = std::min<int64_t>(chunk, npts);
+    const int64_t nrows = 2 * (int64_t)nf * nomega;
+    const int G = (int)std::max<int64_t>(1, std::min<int64_t>({kOptPartCap / nrows, (int64_t)kOptGroupsMax, chunk}));
+    const unsigned ntile = (unsigned)((nomega + kOptTile - 1) / kOptTile);
+    const bool wide = n > 32;
+    const size_t omb = al256((size_t)nomega * sizeof(double)), partb = al256((size_t)G * nrows * sizeof(double)),
+                 rowb = al256((size_t)nrows * sizeof(double)), kb = al256((size_t)chunk * dk * sizeof(double)),
+                 eb = al256((size_t)chunk * n * sizeof(double)), ub = al256((size_t)chunk * vb), recb = al256((size_t)chunk * rb),
+                 wb = wide ? al256((size_t)chunk * F.nd * vb) : 0;
+    tbk_ctx* ctx = m->ctx;
+    TBK_HIP(hipSetDevice(ctx->device));
+    void* base = nullptr;
+    int rc = tbk_ctx_scratch(ctx, 256 + omb + partb + rowb + kb + eb + ub + recb + 2 * wb, &base);
+    if (rc) return rc;
+    unsigned char* p = (unsigned char*)base + 256;
+    double* om_dev = (double*)p;
+    p += omb;
+    double* part = (double*)p;
+    p += partb;
+    double* rows = (double*)p;
+    p += rowb;
+    double* kc = (double*)p;
+    p += kb;
+    double* ec = (double*)p;
+    p += eb;
+    cd* vc = (cd*)p;
+    p += ub;
+    double* rec = (double*)p;
+    p += recb;
+    cd* wt = (cd*)p;
+    cd* vt = (cd*)(p + wb);
+    TBK_HIP(hipMemcpyAsync(om_dev, omega, (size_t)nomega * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    const int P = opt_lds_points(n, F.nd);
+    const size_t lds = (size_t)(F.nd + 2) * P * n * n * sizeof(cd);
+    if (!wide && lds > 64 * 1024)
+        TBK_HIP(hipFuncSetAttribute((const void*)k_opt_pairs, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    for (int64_t first = 0; first < npts; first += chunk) {
+        const int64_t cnt = std::min<int64_t>(chunk, npts - first);
+        rc = tbk_k_uniform_mesh_range_dev(ctx, dk, mesh, first, cnt, kc);
+        if (rc) return rc;
+        rc = tbk_solve_list_dev_checked(m, kc, cnt, ec, (double*)vc);
+        if (rc) return rc;
+        if (!wide) {
+            ProfScope ps(ctx, "opt_pairs");
+            hipLaunchKernelGGL(k_opt_pairs, dim3((unsigned)((cnt + P - 1) / P)), dim3(256), lds, ctx->stream, m->view,
+                               (const double*)kc, (const cd*)vc, (const double*)ec, cnt, F, P, mu, kT, rec);
+            TBK_HIP(hipGetLastError());
+        } else {
+            {
+                ProfScope ps(ctx, "opt_wide");
+                hipLaunchKernelGGL(k_opt_wsp, dim3((unsigned)cnt, (unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, m->view,
+                                   (const double*)kc, (const cd*)vc, cnt, F, wt);
+                TBK_HIP(hipGetLastError());
+            }
+            {
+                // cnt nd <= 3 kOptChunkBytes / (33^2 16 B) < 65536 (the grid's z limit)
+                ProfScope ps(ctx, "opt_wide");
+                const unsigned t = (unsigned)((n + 15) / 16);
+                hipLaunchKernelGGL(k_opt_vprod, dim3(t, t, (unsigned)(cnt * F.nd)), dim3(256), 0, ctx->stream, (const cd*)vc,
+                                   (const cd*)wt, cnt, n, F.nd, vt);
+                TBK_HIP(hipGetLastError());
+            }
+            ProfScope ps(ctx, "opt_pairs");
+            hipLaunchKernelGGL(k_opt_pairs_wide, dim3(nblk(cnt * npair)), dim3(256), 0, ctx->stream, (const double*)ec, (const cd*)vt,
+                               cnt, n, F, mu, kT, rec);
+            TBK_HIP(hipGetLastError());
+        }
+        ProfScope ps(ctx, "opt_omega");
+        const dim3 grid(ntile, (unsigned)G);
+        const int acc = first > 0 ? 1 : 0;
+        if (F.ns == 1 && F.na == 0) rc = opt_omega_launch<1, 0>(ctx, grid, rec, cnt, npair, G, om_dev, nomega, eta, acc, part);
+        else if (F.ns == 1 && F.na == 1) rc = opt_omega_launch<1, 1>(ctx, grid, rec, cnt, npair, G, om_dev, nomega, eta, acc, part);
+        else if (F.ns == 3) rc = opt_omega_launch<3, 1>(ctx, grid, rec, cnt, npair, G, om_dev, nomega, eta, acc, part);
+        else rc = opt_omega_launch<6, 3>(ctx, grid, rec, cnt, npair, G, om_dev, nomega, eta, acc, part);
+        if (rc) return rc;
+    }
+    {
+        ProfScope ps(ctx, "opt_rows");
+        hipLaunchKernelGGL(k_opt_rows, dim3((unsigned)nrows), dim3(256), 0, ctx->stream, (const double*)part, G, nrows,
+                           1.0 / (double)npts, rows);
+        TBK_HIP(hipGetLastError());
+    }
+    std::vector<double> sums((size_t)nrows);
+    TBK_HIP(hipMemcpyAsync(sums.data(), rows, (size_t)nrows * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    TBK_HIP(hipStreamSynchronize(ctx->stream));
+    // S_ab = i SA - SB, S_ba = i SA + SB with SA = (x_A, eta y_A), SB = (x_B, eta y_B) of the pair (a, b), a < b; S_aa = i SA
+    auto X = [&](int f, int w) { return sums[(size_t)(2 * f) * nomega + w]; };
+    auto Y = [&](int f, int w) { return eta * sums[(size_t)(2 * f + 1) * nomega + w]; };
+    auto B_of = [&](int a, int b) {   // the B field of (a, b), a < b, or -1
+        for (int f = F.ns; f < nf; ++f)
+            if (F.fa[f] == a && F.fb[f] == b) return f;
+        return -1;
+    };
+    for (int w = 0; w < nomega; ++w) {
+        for (int f = 0; f < F.ns; ++f) {
+            const int a = F.fa[f], b = F.fb[f];
+            const int fb = a == b ? -1 : B_of(a, b);
+            const double bx = fb >= 0 ? X(fb, w) : 0.0, by = fb >= 0 ? Y(fb, w) : 0.0;
+            const double re = -Y(f, w), im = X(f, w);
+            if (!full) {
+                out[2 * w] = re - bx;
+                out[2 * w + 1] = im - by;
+                continue;
+            }
+            double* o = out + (size_t)w * 2 * dk * dk;
+            o[2 * (a * dk + b)] = re - bx;
+            o[2 * (a * dk + b) + 1] = im - by;
+            if (a != b) {
+                o[2 * (b * dk + a)] = re + bx;
+                o[2 * (b * dk + a) + 1] = im + by;
+            }
+        }
+    }
+    return TBK_OK;
+}

@@ -523,6 +523,63 @@ class tb_model(object):
             return float(out[0]) if sel is not None else out
         return out[0] if sel is not None else out
 
+    def optical_conductivity_mesh(self, mesh_size, omega, eta, fermi_level=0.0, kT=0.0, dirs=None, cartesian=False):
+        """Extension: the interband optical conductivity tensor by the Kubo formula, averaged over the whole
+        `k_uniform_mesh(mesh_size)` (1-, 2- or 3-D, generated on the device):
+
+            S_ab(w) = (i / N_k) sum_k sum_{n != m} [(f_m - f_n) / (E_m - E_n)] V^a_nm V^b_mn / (E_m - E_n - w - i eta)
+
+        k reduced, H the matrix of `_gen_ham`, V^a = dH/dk_a (`_gen_dham`), E_n and |n> the eigenpairs of `solve_all`,
+        f_n = [E_n <= fermi_level] for kT = 0, else 1 / (1 + exp((E_n - fermi_level) / kT)).  Pairs with
+        |E_m - E_n| <= 1e-9 max(1, |E_n|, |E_m|) are left out (interband only, no Drude term); eta > 0 is a constant
+        Lorentzian half-width; time dependence e^{-i w t}; no spin-degeneracy factor.
+
+        omega: 1-D, 1..65536 finite frequencies in any order.  dirs=None -> complex `(nw, dim_k, dim_k)`; dirs=(a, b)
+        (a == b allowed) -> `(nw,)`, the component S_ab.  Re S_aa >= 0 (passive), S(-w) = conj S(w), and S_ab = S_ba with
+        time reversal.  DC limit: at w = 0, eta -> 0, Re (S_ab - S_ba) / 2 = -I(mu) of `berry_curvature_mesh(mesh,
+        dirs=(a, b), fermi_levels=[mu])` (the slice mean for a 3-D mesh); the error shrinks as eta^2.
+        cartesian=True (dirs=None only) returns sigma = A^T S A / ((2 pi)^2 V_c), `(nw, dim_r, dim_r)`, in units of
+        e^2/hbar x length^(2 - dim_k), A = the periodic lattice vectors as rows, V_c = sqrt(det(A A^T)); spinless graphene
+        gives Re sigma_xx -> 1/8 at small w.  A one-state model, or kT = 0 with the Fermi level below or above every
+        level, gives exact zeros.  Fixed reduction order: two calls give the same bits."""
+        if self._dim_k not in (1, 2, 3):
+            raise Exception("\n\noptical_conductivity_mesh needs a model with dim_k 1, 2 or 3.")
+        mesh, nk = self._mesh_arg(mesh_size)
+        w = np.array(omega, dtype=float)
+        if w.ndim != 1 or w.size < 1 or w.size > 65536:
+            raise Exception("\n\nomega must be a 1-D array of 1..65536 frequencies.")
+        if not np.all(np.isfinite(w)):
+            raise Exception("\n\nomega must be finite.")
+        w = np.ascontiguousarray(w)
+        if not np.isfinite(eta) or not eta > 0.0:
+            raise Exception("\n\neta must be finite and > 0.")
+        if not np.isfinite(kT) or not kT >= 0.0:
+            raise Exception("\n\nkT must be finite and >= 0.")
+        if not np.isfinite(fermi_level):
+            raise Exception("\n\nfermi_level must be finite.")
+        if dirs is None:
+            d0 = d1 = -1
+        else:
+            dirs = list(dirs)
+            if len(dirs) != 2 or not all(_is_int(d) for d in dirs):
+                raise Exception("\n\ndirs must be two integer axes.")
+            if min(dirs) < 0 or max(dirs) >= self._dim_k:
+                raise Exception("\n\nDirection for the optical conductivity out of bounds.")
+            if cartesian:
+                raise Exception("\n\ncartesian=True returns the whole tensor: give dirs=None.")
+            d0, d1 = int(dirs[0]), int(dirs[1])
+        dk = self._dim_k
+        out = np.zeros((w.size, dk, dk) if d0 < 0 else (w.size,), dtype=complex)
+        if self._nsta > 1:
+            _lib.check(_lib.lib.tbk_optical_cond_mesh(self._device_model(), _lib.iptr(mesh), int(w.size), _lib.dptr(w),
+                                                      float(eta), float(fermi_level), float(kT), d0, d1,
+                                                      _lib.dptr(out.view(float))))
+        if not cartesian:
+            return out
+        a = np.array(self._lat, dtype=float)[self._per]               # (dim_k, dim_r)
+        vc = np.sqrt(np.linalg.det(a @ a.T))
+        return np.einsum("ia,wij,jb->wab", a, out, a) / ((2.0 * np.pi) ** 2 * vc)
+
     # ------------------------------------------------------------------ position operator
     def ignore_position_operator_offdiagonal(self):
         self._assume_position_operator_diagonal = True

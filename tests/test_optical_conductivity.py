@@ -1,0 +1,261 @@
+"""Interband optical conductivity by the Kubo formula (tb_model.optical_conductivity_mesh) against the NumPy restatement in
+optics_ref.py, and its DC limit against berry_curvature_mesh's Fermi scan."""
+import os
+
+import numpy as np
+import pytest
+
+import curv_ref as cr
+import helpers as hp
+import optics_ref as opr
+from conftest import ROOT
+from helpers import quiet
+from oracle import tb_oracle as orc
+
+import pythtb_amd as tb
+from pythtb_amd import w90
+
+SILICON = os.path.join(ROOT, "tests", "golden", "w90_silicon")
+OMEGA = np.array([-1.3, -0.2, 0.0, 0.35, 1.1, 2.7])
+ETA = 0.05
+
+
+def haldane(delta=0.2):
+    return hp.haldane(tb.tb_model, delta=delta)
+
+
+def supercell(m, s):
+    return quiet(m.make_supercell, [[s, 0], [0, s]])
+
+
+def ribbon(cells):
+    return quiet(haldane().cut_piece, cells, 1)
+
+
+def silicon():
+    return quiet(w90(SILICON, "silicon").model)
+
+
+def stacked_haldane(delta=0.2, t=-1.0, t2abs=0.15, tz=0.1):
+    """Haldane layers along a third axis with a weak interlayer hop."""
+    lat = [[1.0, 0.0, 0.0], [0.5, np.sqrt(3.0) / 2.0, 0.0], [0.0, 0.0, 1.0]]
+    orb = [[1.0 / 3.0, 1.0 / 3.0, 0.0], [2.0 / 3.0, 2.0 / 3.0, 0.0]]
+    m = quiet(tb.tb_model, 3, 3, lat, orb)
+    t2 = t2abs * np.exp(1j * np.pi / 2.0)
+    m.set_onsite([-delta, delta])
+    for amp, i, j, R in [(t, 0, 1, [0, 0, 0]), (t, 1, 0, [1, 0, 0]), (t, 1, 0, [0, 1, 0]), (t2, 0, 0, [1, 0, 0]),
+                         (t2, 1, 1, [1, -1, 0]), (t2, 1, 1, [0, 1, 0]), (np.conj(t2), 1, 1, [1, 0, 0]),
+                         (np.conj(t2), 0, 0, [1, -1, 0]), (np.conj(t2), 0, 0, [0, 1, 0]), (tz, 0, 0, [0, 0, 1]),
+                         (tz, 1, 1, [0, 0, 1])]:
+        m.set_hop(amp, i, j, R)
+    return m
+
+
+def levels(m, mesh):
+    """Every eigenvalue on the mesh, (nsta, nk), in NumPy."""
+    return np.linalg.eigvalsh(orc.ham_batch(m, m.k_uniform_mesh(mesh))).T
+
+
+def safe_mu(ev, target):
+    """The midpoint of the two levels around `target`: at least 1e-6 from every level on the mesh."""
+    s = np.unique(ev.ravel())
+    j = int(np.searchsorted(s, target))
+    if j == 0:
+        return s[0] - 1.0
+    if j == len(s):
+        return s[-1] + 1.0
+    mu = 0.5 * (s[j - 1] + s[j])
+    assert s[j] - s[j - 1] >= 2e-6
+    return mu
+
+
+def close(got, want, rel=1e-10):
+    scale = np.max(np.abs(want))
+    if scale == 0.0:                                         # (kT = 0, mu outside the spectrum)
+        assert np.all(got == 0.0)
+        return
+    assert np.max(np.abs(got - want)) <= rel * scale, np.max(np.abs(got - want)) / scale
+
+
+# ---------------------------------------------------------------- CPU: argument errors, the reference's properties
+def test_argument_errors_without_gpu():
+    m = haldane()
+    flat = quiet(tb.tb_model, 0, 2, hp.LAT, hp.ORB)
+    with pytest.raises(Exception, match="dim_k"):
+        flat.optical_conductivity_mesh([4], [0.1], 0.1)
+    for bad in ([8], [8, 0], [8, 8, 8]):
+        with pytest.raises(Exception):
+            m.optical_conductivity_mesh(bad, [0.1], 0.1)
+    for w in ([], [[0.1, 0.2]], [0.1, np.nan], [np.inf], np.zeros(65537)):
+        with pytest.raises(Exception, match="omega"):
+            m.optical_conductivity_mesh([8, 8], w, 0.1)
+    for eta in (0.0, -0.1, np.inf, np.nan):
+        with pytest.raises(Exception, match="eta"):
+            m.optical_conductivity_mesh([8, 8], [0.1], eta)
+    for kT in (-1e-3, np.inf):
+        with pytest.raises(Exception, match="kT"):
+            m.optical_conductivity_mesh([8, 8], [0.1], 0.1, kT=kT)
+    with pytest.raises(Exception, match="fermi_level"):
+        m.optical_conductivity_mesh([8, 8], [0.1], 0.1, fermi_level=np.nan)
+    for bad in [(0, 2), (-1, 0), (0,), (0, 1, 1)]:
+        with pytest.raises(Exception):
+            m.optical_conductivity_mesh([8, 8], [0.1], 0.1, dirs=bad)
+    with pytest.raises(Exception, match="cartesian"):
+        m.optical_conductivity_mesh([8, 8], [0.1], 0.1, dirs=(0, 1), cartesian=True)
+
+
+def test_numpy_reference_dc_limit():
+    """Property 1 of the reference: Re (S_01 - S_10) / 2 at w = 0, eta = 1e-6 is minus the Fermi scan of curv_ref."""
+    m = haldane()
+    mesh = [24, 24]
+    ev = levels(m, mesh)
+    for target in (0.5 * (ev[0].max() + ev[1].min()), 0.5 * (ev[0].min() + ev[0].max())):
+        mu = safe_mu(ev, target)
+        s = opr.conductivity(m, mesh, [0.0], 1e-6, mu=mu)[0]
+        want = -opr.fermi_curvature_integral(m, mesh, mu)
+        assert abs(0.5 * (s[0, 1] - s[1, 0]).real - want) <= 1e-9 * max(1.0, abs(want))
+
+
+def test_numpy_reference_passive_and_real():
+    m = hp.kane_mele(tb.tb_model)
+    mesh = [10, 10]
+    w = np.linspace(-4.0, 4.0, 17)
+    for kT in (0.0, 0.1):
+        s = opr.conductivity(m, mesh, w, 0.1, mu=0.3, kT=kT)
+        scale = np.max(np.abs(s))
+        assert scale > 0.0
+        assert np.min(np.diagonal(s, axis1=1, axis2=2).real) >= -1e-14 * scale
+        assert np.max(np.abs(s[::-1] - np.conj(s))) <= 1e-13 * scale
+
+
+def test_numpy_fermi_difference_is_stable():
+    """-sinh h / (cosh h + cosh u) keeps its relative accuracy for close levels and stays finite far from mu."""
+    e = np.array([0.3, -0.2, 0.45])
+    for kT in (0.05, 0.5):
+        for d in (1e-9, 1e-3, 0.7):
+            de = (e + d) - e                                  # the gap the function sees
+            h, u = 0.5 * de / kT, (0.5 * (e + (e + d)) - 0.1) / kT
+            want = -np.sinh(h) / (np.cosh(h) + np.cosh(u))
+            got = opr.fermi_diff(e, e + d, 0.1, kT)
+            assert np.max(np.abs(got - want) / np.abs(want)) <= 1e-12
+    far = opr.fermi_diff([-1e6, 0.0, 3.0], [1e6, 1e5, 3.0 + 1e-12], 0.0, 1e-3)
+    assert np.all(np.isfinite(far)) and np.all(far <= 0.0) and far[0] == -1.0
+
+
+# ---------------------------------------------------------------- GPU: against the NumPy form
+def check_model(m, mesh, mus, kTs=(0.0,), dirs=None):
+    ev = levels(m, mesh)
+    for target in mus:
+        mu = safe_mu(ev, target)
+        for kT in kTs:
+            want = opr.conductivity(m, mesh, OMEGA, ETA, mu=mu, kT=kT)
+            got = m.optical_conductivity_mesh(mesh, OMEGA, ETA, fermi_level=mu, kT=kT)
+            assert got.shape == want.shape == (len(OMEGA), m._dim_k, m._dim_k)
+            close(got, want)
+            for a, b in dirs or [(m._dim_k - 1, 0), (0, 0)]:
+                one = m.optical_conductivity_mesh(mesh, OMEGA, ETA, fermi_level=mu, kT=kT, dirs=(a, b))
+                assert one.shape == (len(OMEGA),)
+                ref = np.max(np.abs(want[:, a, b]))
+                close(one, want[:, a, b], 1e-10 * np.max(np.abs(want)) / ref if ref > 0.0 else 1e-10)
+
+
+@pytest.mark.gpu
+def test_haldane_two_states():
+    m = haldane()
+    mesh = [24, 24]
+    ev = levels(m, mesh)
+    gap = 0.5 * (ev[0].max() + ev[1].min())
+    lower = 0.5 * (ev[0].min() + ev[0].max())
+    check_model(m, mesh, [gap, lower, ev.max() + 0.5], kTs=(0.0, 0.05))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["kane_mele", "silicon", "cubic16", "haldane_4x4", "haldane_5x5", "ribbon_20", "ribbon_100"])
+def test_models(name):
+    if name == "kane_mele":
+        m, mesh = hp.kane_mele(tb.tb_model), [20, 20]
+    elif name == "silicon":
+        m, mesh = silicon(), [6, 6, 6]
+    elif name == "cubic16":
+        m, mesh = hp.cubic16(tb.tb_model), [6, 6, 6]
+    elif name == "haldane_4x4":
+        m, mesh = supercell(haldane(), 4), [48, 48]         # 2304 points: two chunks of 32-state eigenvectors
+    elif name == "haldane_5x5":
+        m, mesh = supercell(haldane(), 5), [8, 8]
+    else:
+        m, mesh = ribbon(int(name.split("_")[1])), [64]
+    ev = levels(m, mesh)
+    n = m._nsta
+    mid = 0.5 * (ev[n // 2 - 1].max() + ev[n // 2].min())
+    if name == "silicon":
+        mid = 0.5 * (ev[3].max() + ev[4].min())
+    dirs = [(0, 0)] if m._dim_k == 1 else [(m._dim_k - 1, 0), (1, 1)]
+    check_model(m, mesh, [mid], dirs=dirs)
+
+
+# ---------------------------------------------------------------- GPU: properties
+@pytest.mark.gpu
+def test_dc_limit_is_the_fermi_scan():
+    m = haldane()
+    mesh = [128, 128]
+    e = m.solve_all_mesh(mesh)
+    for target in (0.5 * (e[0].max() + e[1].min()), 0.5 * (e[0].min() + e[0].max())):
+        mu = safe_mu(e, target)
+        s = m.optical_conductivity_mesh(mesh, [0.0], 1e-6, fermi_level=mu)[0]
+        want = -m.berry_curvature_mesh(mesh, fermi_levels=[mu])[0]
+        assert abs(0.5 * (s[0, 1] - s[1, 0]).real - want) <= 1e-9 * max(1.0, abs(want))
+    st = stacked_haldane()
+    mesh = [32, 32, 5]
+    e = st.solve_all_mesh(mesh)
+    for target in (0.5 * (e[0].max() + e[1].min()), 0.5 * (e[0].min() + e[0].max())):
+        mu = safe_mu(e, target)
+        s = st.optical_conductivity_mesh(mesh, [0.0], 1e-6, fermi_level=mu)[0]
+        want = -st.berry_curvature_mesh(mesh, fermi_levels=[mu])[0].mean()
+        assert abs(0.5 * (s[0, 1] - s[1, 0]).real - want) <= 1e-9 * max(1.0, abs(want))
+
+
+@pytest.mark.gpu
+def test_graphene_universal_absorption():
+    m = hp.graphene(tb.tb_model)
+    sig = m.optical_conductivity_mesh([512, 512], [0.2], 0.02, cartesian=True)[0]
+    assert sig.shape == (2, 2)
+    assert 0.99 <= 8.0 * sig[0, 0].real <= 1.02
+    assert abs(sig[0, 0] - sig[1, 1]) <= 1e-10 * abs(sig[0, 0])
+    assert abs(sig[0, 1]) <= 1e-12 * abs(sig[0, 0]) and abs(sig[1, 0]) <= 1e-12 * abs(sig[0, 0])
+
+
+@pytest.mark.gpu
+def test_onsager_passive_real():
+    m = hp.kane_mele(tb.tb_model)
+    mesh = [24, 24]
+    w = np.linspace(-5.0, 5.0, 41)
+    assert w[20] == 0.0
+    for kT in (0.0, 0.1):
+        s = m.optical_conductivity_mesh(mesh, w, 0.1, fermi_level=0.31, kT=kT)
+        scale = np.max(np.abs(s))
+        assert scale > 0.0
+        assert np.max(np.abs(s - np.transpose(s, (0, 2, 1)))) <= 1e-10 * scale
+        assert np.min(np.diagonal(s, axis1=1, axis2=2).real) >= -1e-14 * scale
+        assert np.max(np.abs(s[::-1] - np.conj(s))) <= 1e-13 * scale
+
+
+@pytest.mark.gpu
+def test_repeat_components_and_zeros():
+    m = haldane()
+    mesh = [40, 40]
+    w = np.linspace(-3.0, 3.0, 700)                          # two frequency tiles
+    s = m.optical_conductivity_mesh(mesh, w, ETA, fermi_level=-0.4, kT=0.02)
+    np.testing.assert_array_equal(s, m.optical_conductivity_mesh(mesh, w, ETA, fermi_level=-0.4, kT=0.02))
+    scale = np.max(np.abs(s))
+    for a, b in [(0, 1), (1, 0), (1, 1)]:
+        one = m.optical_conductivity_mesh(mesh, w, ETA, fermi_level=-0.4, kT=0.02, dirs=(a, b))
+        assert np.max(np.abs(one - s[:, a, b])) <= 1e-13 * scale
+    e = m.solve_all_mesh(mesh)
+    for mu in (e.min() - 1.0, e.max() + 1.0):
+        z = m.optical_conductivity_mesh(mesh, w, ETA, fermi_level=mu)
+        assert np.all(z == 0.0)
+    one = quiet(tb.tb_model, 2, 2, hp.LAT, [[0.0, 0.0]])
+    one.set_onsite([0.3])
+    one.set_hop(-1.0, 0, 0, [1, 0])
+    z = one.optical_conductivity_mesh([8, 8], w[:5], ETA, fermi_level=0.3)
+    assert z.shape == (5, 2, 2) and np.all(z == 0.0)
