@@ -297,6 +297,26 @@ int tbk_berry_curv_mesh(tbk_model* model, const int32_t* mesh, int dir0, int dir
 int tbk_optical_cond_mesh(tbk_model* model, const int32_t* mesh, int nomega, const double* omega, double eta, double mu,
                           double kT, int dir0, int dir1, double* out);
 
+/* ---- orbital moments and orbital magnetization by the Kubo formula ----------
+ * k reduced, V^d = d_d H (tbk_gen_dham), E_n, |n> the eigenpairs of the solver, (a, b) = (dir0, dir1) distinct in [0, dim_k),
+ * dim_k >= 2, P_nm = Im V^a_nm V^b_mn, Delta_nm = E_n - E_m.
+ * On a k list k[nk][dim_k]:
+ *   occ == NULL: per band, out[nsta][nk], m_n = sum_{m != n} P_nm / (E_m - E_n) (pairs closer than 1e-9 max(1, |E_n|, |E_m|)
+ *                left out, as tbk_berry_curv_list);
+ *   otherwise:   out[nk] = LC + IC of the bands occ[nocc], LC = sum_{n in occ, m not in occ} P_nm E_m / Delta^2,
+ *                IC = (same) P_nm E_n / Delta^2.                                                                          */
+int tbk_orb_moment_list(tbk_model* model, const double* k, int64_t nk, int dir0, int dir1, const int32_t* occ, int nocc,
+                        double* out);
+/* Plane means over k_uniform_mesh(mesh) (dim_k 2 or 3), generated on the device; exactly one of occ and mu[nmu]:
+ *   occ given:  out[3] = (LC, IC, Omega_occ), Omega_occ = -2 sum_{n in occ, m not in occ} P_nm / Delta^2 (kT must be 0);
+ *   nmu levels (1..8192, finite, any order): out[nmu], M(mu) = mean_k sum_n [f_n m_n + g_n Omega_n] with Omega_n the
+ *   per-band curvature of tbk_berry_curv_list; kT = 0: f = [E_n <= mu], g = (mu - E_n) f; kT > 0: f = 1 / (1 + e^x),
+ *   g = kT ln(1 + e^-x), x = (E_n - mu) / kT.
+ * M_z = -(q / hbar) M / (2 pi)^2 per area for dirs (0, 1) of a 2-D cell with a1 x a2 along +z.  A 3-D mesh gains a trailing
+ * axis over the remaining mesh direction: out[..][N_rest].  Fixed-shape reductions, no atomics: bit-reproducible.      */
+int tbk_orb_mag_mesh(tbk_model* model, const int32_t* mesh, int dir0, int dir1, const int32_t* occ, int nocc, int nmu,
+                     const double* mu, double kT, double* out);
+
 /* ---- multi-GPU: one process per GPU, k-points sharded, one gather ------
  * Thin RCCL wrappers (librccl is dlopen'ed on first use).  The 128-byte id is
  * created on rank 0 and distributed by the launcher (any out-of-band channel). */

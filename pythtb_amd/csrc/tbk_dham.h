@@ -1,5 +1,5 @@
-// tbk_dham.h -- the gradient form of the model's slot sums, shared by the Kubo-formula translation units (tbk_curv.hip,
-// tbk_optics.hip; DESIGN.md sections 11 and 12).
+// tbk_dham.h -- the gradient form of the model's slot sums, the n = 2 closed form and the mesh-plane geometry, shared by the
+// Kubo-formula translation units (tbk_curv.hip, tbk_optics.hip, tbk_orbmag.hip; DESIGN.md sections 11 to 13).
 #pragma once
 #include "tbk_solve_dev.h"
 
@@ -51,3 +51,65 @@ __device__ __forceinline__ void k_phases(const ModelView& mv, const double* __re
         z[d] = d < mv.dim_k ? expi2pi(kk[d]) : cd{1.0, 0.0};
     }
 }
+
+// ---------------------------------------------------------------- n = 2: closed form in registers
+struct Curv2 {
+    double e0, e1, om;   // eigenvalues (ascending) and Omega_0 without the degeneracy rule (Omega_1 = -om)
+    bool degenerate;     // the pair falls under the rule of (1)
+};
+__device__ __forceinline__ Curv2 curv2_point(const ModelView& mv, const double (&kk)[4], const int d0, const int d1) {
+    cd z[4];
+#pragma unroll
+    for (int d = 0; d < 4; ++d) z[d] = d < mv.dim_k ? expi2pi(kk[d]) : cd{1.0, 0.0};
+    cd h[3], va[3], vb[3];
+#pragma unroll
+    for (int s = 0; s < 3; ++s) {
+        const int a = s == 2 ? 1 : 0, b = s == 0 ? 0 : 1;   // slots (0,0) (0,1) (1,1)
+        dham_terms(mv, a, b, mv.slot_ptr[s], mv.slot_ptr[s + 1], kk, z, d0, d1, h[s], va[s], vb[s]);
+    }
+    // H = d0 + dx sx + dy sy + dz sz:  H_01 = dx - i dy,  H_00 - H_11 = 2 dz
+    const double dx = h[1].x, dy = -h[1].y, dz = 0.5 * (h[0].x - h[2].x);
+    const double ax = va[1].x, ay = -va[1].y, az = 0.5 * (va[0].x - va[2].x);
+    const double bx = vb[1].x, by = -vb[1].y, bz = 0.5 * (vb[0].x - vb[2].x);
+    const double cx = ay * bz - az * by, cy = az * bx - ax * bz, cz = ax * by - ay * bx;
+    const double d2 = dx * dx + dy * dy + dz * dz, dn = sqrt(d2);
+    const double mid = 0.5 * (h[0].x + h[2].x);
+    Curv2 r;
+    r.e0 = mid - dn;
+    r.e1 = mid + dn;
+    r.om = (dx * cx + dy * cy + dz * cz) / (2.0 * d2 * dn);
+    r.degenerate = !(r.e1 - r.e0 > 1e-9 * fmax(1.0, fmax(fabs(r.e0), fabs(r.e1))));
+    return r;
+}
+
+// ---------------------------------------------------------------- mesh planes
+// The (da, db) planes of k_uniform_mesh(N): slice s runs along the remaining axis (dc < 0: one slice); plane point p = ia N[db] + ib.
+struct PlaneArgs {
+    int N[3];
+    int da, db, dc;
+    int64_t nplane;
+    int64_t npts;
+    int nslice;
+};
+__device__ __forceinline__ int64_t plane_point(const PlaneArgs& P, const int s, const int64_t p, int (&ii)[3]) {
+    ii[0] = ii[1] = ii[2] = 0;
+    const int64_t ia = p / P.N[P.db];
+    ii[P.da] = (int)ia;
+    ii[P.db] = (int)(p - ia * P.N[P.db]);
+    if (P.dc >= 0) ii[P.dc] = s;
+    return ((int64_t)ii[0] * P.N[1] + ii[1]) * P.N[2] + ii[2];
+}
+
+// sum over the 256 threads of a workgroup in a fixed order (shuffle tree in each wavefront, then the four in order); thread 0 has it
+__device__ __forceinline__ double block_sum(double v, double* red) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// 33..2048 states: W^d = d_d H U^T of a chunk from the non-empty slots, wt[ik][2][n][n] (defined in tbk_curv.hip; launched
+// by tbk_orbmag.hip as well)
+__global__ void k_curv_wsp(const ModelView mv, const double* __restrict__ k, const cd* __restrict__ evec, const int64_t nk,
+                           const int d0, const int d1, cd* __restrict__ wt);

@@ -445,17 +445,17 @@ class tb_model(object):
             return out[0]
         return out[0].reshape(self._norb, 2, self._norb, 2)
 
-    def _curv_args(self, occ, dirs):
-        """Checked (occ as int32 indices or None, dir0, dir1) of the curvature calls."""
+    def _curv_args(self, occ, dirs, what="Berry curvature"):
+        """Checked (occ as int32 indices or None, dir0, dir1) of the curvature and orbital-moment calls."""
         if self._dim_k < 2:
-            raise Exception("\n\nThe Berry curvature needs a model with dim_k >= 2.")
+            raise Exception("\n\nThe %s needs a model with dim_k >= 2." % what)
         dirs = list(dirs)
         if len(dirs) != 2 or not all(_is_int(d) for d in dirs):
             raise Exception("\n\ndirs must be two integer axes.")
         if dirs[0] == dirs[1]:
-            raise Exception("\n\nNeed to specify two different directions for the Berry curvature.")
+            raise Exception("\n\nNeed to specify two different directions for the %s." % what)
         if min(dirs) < 0 or max(dirs) >= self._dim_k:
-            raise Exception("\n\nDirection for the Berry curvature out of bounds.")
+            raise Exception("\n\nDirection for the %s out of bounds." % what)
         if occ is None:
             return None, int(dirs[0]), int(dirs[1])
         sel = np.arange(self._nsta)[occ]                 # a NumPy fancy index, as wf_array.berry_flux reads it (IndexError)
@@ -579,6 +579,72 @@ class tb_model(object):
         a = np.array(self._lat, dtype=float)[self._per]               # (dim_k, dim_r)
         vc = np.sqrt(np.linalg.det(a @ a.T))
         return np.einsum("ia,wij,jb->wab", a, out, a) / ((2.0 * np.pi) ** 2 * vc)
+
+    # ------------------------------------------------------------------ orbital magnetization (extensions)
+    def orbital_moment(self, k_list, occ=None, dirs=(0, 1)):
+        """Extension: the orbital moment by the Kubo formula at every k of `k_list` (reduced coordinates, as solve_all).
+
+        (a, b) = dirs, V^d = dH/dk_d (`_gen_dham`), E_n and |n> the eigenpairs of `solve_all`, P_nm = Im V^a_nm V^b_mn.
+        occ=None: per band, float64 `(nsta, nk)`, m_n(k) = sum_{m != n} P_nm / (E_m - E_n); a pair with
+            |E_n - E_m| <= 1e-9 max(1, |E_n|, |E_m|) contributes to neither band (the rule of `berry_curvature`).  A two-state
+            model has m_0 = m_1 = (E_0 - E_1) Omega_0 / 2, Omega_0 of `berry_curvature`.
+        occ given (a NumPy index of bands): the gauge-invariant sum of that band set, `(nk,)`, LC(k) + IC(k) with
+            LC = sum_{n in occ, m not in occ} P_nm E_m / (E_n - E_m)^2 and IC = (same) P_nm E_n / (E_n - E_m)^2 (no
+            degeneracy rule).  Its mean over a mesh is the band-set part of `orbital_magnetization_mesh`.
+        Reduced units (energy x the reduced curvature); `orbital_magnetization_mesh` gives the conversion."""
+        sel, d0, d1 = self._curv_args(occ, dirs, "orbital moment")
+        k = self._k_array(k_list)
+        nk = k.shape[0]
+        out = np.zeros(nk if sel is not None else (self._nsta, nk), dtype=float)
+        if nk == 0:
+            return out
+        _lib.check(_lib.lib.tbk_orb_moment_list(self._device_model(), _lib.dptr(k), nk, d0, d1, _lib.iptr(sel),
+                                                0 if sel is None else len(sel), _lib.dptr(out)))
+        return out
+
+    def orbital_magnetization_mesh(self, mesh_size, occ=None, fermi_levels=None, kT=0.0, dirs=(0, 1)):
+        """Extension: the orbital magnetization by the Kubo formula, as means over `k_uniform_mesh(mesh_size)` (2-D or 3-D,
+        generated on the device).  Give exactly one of occ and fermi_levels.
+
+        occ given: float64 `(3,)` = (mean LC, mean IC, mean Omega_occ) of `orbital_moment(occ=...)`'s terms, with
+            Omega_occ = -2 sum_{n in occ, m not in occ} P_nm / (E_n - E_m)^2 (`berry_curvature_mesh(occ)`).  For mu in the gap
+            above the set, M(mu) = LC + IC + mu Omega_occ, so dM/dmu = 2 pi C (the Streda formula).
+        fermi_levels (1-D, 1..8192 finite values, any order): M(mu), `(nmu,)` in input order,
+            kT = 0:  M(mu) = mean_k sum_{n: E_n <= mu} [m_n + (mu - E_n) Omega_n] = A(mu) + mu I(mu), m_n of `orbital_moment`,
+                     Omega_n of `berry_curvature`, I(mu) of `berry_curvature_mesh(fermi_levels=...)`.  Pairs of occupied bands
+                     cancel only in exact arithmetic, so near-degenerate occupied pairs cost precision, as in that scan.
+            kT > 0:  M(mu, T) = mean_k sum_n [f_n m_n + g_n Omega_n], f_n = 1 / (1 + e^x), g_n = kT ln(1 + e^-x),
+                     x = (E_n - mu) / kT (Xiao et al., PRL 97, 026603); it tends to the kT = 0 form as kT -> 0.
+        3-D mesh: every result gains a trailing axis over the mesh direction that is not in dirs, one plane per slice (a sheet
+        value per slice).
+        Units and sign: for dirs = (0, 1) of a 2-D cell with a1 x a2 along +z, the orbital magnetization per area of particles
+        of charge q is M_z = -(q / hbar) M / (2 pi)^2, with M in the model's energy unit.  The reductions have a fixed order,
+        so two calls give the same bits."""
+        sel, d0, d1 = self._curv_args(occ, dirs, "orbital magnetization")
+        mesh, nk = self._mesh_arg(mesh_size)
+        if self._dim_k not in (2, 3):
+            raise Exception("\n\norbital_magnetization_mesh needs a 2-D or 3-D mesh.")
+        kT = float(kT)
+        if not np.isfinite(kT) or not kT >= 0.0:
+            raise Exception("\n\nkT must be finite and >= 0.")
+        if (sel is None) == (fermi_levels is None):
+            raise Exception("\n\nGive exactly one of occ and fermi_levels.")
+        if kT > 0.0 and fermi_levels is None:
+            raise Exception("\n\nkT > 0 needs fermi_levels.")
+        mu = None
+        if fermi_levels is not None:
+            mu = np.ascontiguousarray(np.array(fermi_levels, dtype=float))
+            if mu.ndim != 1 or mu.size < 1 or mu.size > 8192:
+                raise Exception("\n\nfermi_levels must be a 1-D array of 1..8192 levels.")
+            if not np.all(np.isfinite(mu)):
+                raise Exception("\n\nfermi_levels must be finite.")
+        nch = 3 if sel is not None else mu.size
+        nslice = 1 if self._dim_k == 2 else int(mesh[3 - d0 - d1])
+        out = np.zeros((nch, nslice), dtype=float)
+        _lib.check(_lib.lib.tbk_orb_mag_mesh(self._device_model(), _lib.iptr(mesh), d0, d1, _lib.iptr(sel),
+                                             0 if sel is None else len(sel), 0 if mu is None else mu.size, _lib.dptr(mu), kT,
+                                             _lib.dptr(out)))
+        return out[:, 0] if self._dim_k == 2 else out
 
     # ------------------------------------------------------------------ position operator
     def ignore_position_operator_offdiagonal(self):

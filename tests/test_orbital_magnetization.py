@@ -1,0 +1,325 @@
+"""Orbital moments and orbital magnetization by the Kubo formula (tb_model.orbital_moment, orbital_magnetization_mesh)
+against the NumPy restatement in orbmag_ref.py, the Streda formula, time reversal and a finite-flake sign anchor."""
+import numpy as np
+import pytest
+
+import curv_ref as cr
+import helpers as hp
+import orbmag_ref as omr
+from helpers import quiet
+from test_berry_curvature import CURV_MODELS, silicon, supercell
+
+import pythtb_amd as tb
+
+TWO_PI = 2.0 * np.pi
+
+
+def haldane(delta=0.2):
+    return hp.haldane(tb.tb_model, delta=delta)
+
+
+def close(got, want, scale, rel=1e-9):
+    err = np.max(np.abs(np.asarray(got) - np.asarray(want)))
+    assert err <= rel * scale, (err, scale)
+
+
+def safe_levels(e, targets):
+    """For each target, the midpoint of the two mesh levels around it (or 1 below / above the spectrum)."""
+    s = np.unique(e.ravel())
+    out = []
+    for t in targets:
+        j = int(np.searchsorted(s, t))
+        out.append(s[0] - 1.0 if j == 0 else (s[-1] + 1.0 if j == len(s) else 0.5 * (s[j - 1] + s[j])))
+    return np.array(out)
+
+
+def one_state():
+    m = quiet(tb.tb_model, 2, 2, hp.LAT, [[0.0, 0.0]])
+    m.set_onsite([0.3])
+    m.set_hop(-0.7, 0, 0, [1, 0])
+    m.set_hop(0.2j, 0, 0, [0, 1])
+    return m
+
+
+# ---------------------------------------------------------------- CPU: argument errors, the reference's properties
+def test_argument_errors_without_gpu():
+    m = haldane()
+    chain = hp.chain3(tb.tb_model, -1.0, 0.5, 0.1)
+    with pytest.raises(Exception, match="dim_k >= 2"):
+        chain.orbital_moment([[0.1]])
+    with pytest.raises(Exception, match="dim_k >= 2"):
+        chain.orbital_magnetization_mesh([8], fermi_levels=[0.0])
+    for bad in [(0, 0), (1, 1), (0, 2), (-1, 0), (0,)]:
+        with pytest.raises(Exception):
+            m.orbital_moment([[0.1, 0.2]], dirs=bad)
+        with pytest.raises(Exception):
+            m.orbital_magnetization_mesh([8, 8], occ=[0], dirs=bad)
+    with pytest.raises(IndexError):
+        m.orbital_moment([[0.1, 0.2]], occ=[2])
+    with pytest.raises(Exception, match="twice"):
+        m.orbital_magnetization_mesh([8, 8], occ=[0, -2])
+    with pytest.raises(Exception, match="wrong shape"):
+        m.orbital_moment([[0.1, 0.2, 0.3]])
+    with pytest.raises(Exception, match="exactly one"):
+        m.orbital_magnetization_mesh([8, 8])
+    with pytest.raises(Exception, match="exactly one"):
+        m.orbital_magnetization_mesh([8, 8], occ=[0], fermi_levels=[0.0])
+    for kT in (-1e-3, np.inf, np.nan):
+        with pytest.raises(Exception, match="kT"):
+            m.orbital_magnetization_mesh([8, 8], fermi_levels=[0.0], kT=kT)
+    with pytest.raises(Exception, match="kT > 0 needs fermi_levels"):
+        m.orbital_magnetization_mesh([8, 8], occ=[0], kT=0.1)
+    for mu in ([[0.0, 1.0]], [], np.zeros(8193)):
+        with pytest.raises(Exception, match="1-D"):
+            m.orbital_magnetization_mesh([8, 8], fermi_levels=mu)
+    with pytest.raises(Exception, match="finite"):
+        m.orbital_magnetization_mesh([8, 8], fermi_levels=[0.0, np.nan])
+    for bad in ([8], [8, 0], [8, 8, 8]):
+        with pytest.raises(Exception):
+            m.orbital_magnetization_mesh(bad, occ=[0])
+
+
+def test_numpy_prefix_form_equals_crossing_pairs():
+    """(3): the per-band prefix sums, where occupied pairs cancel, equal the sum over the pairs that cross mu alone."""
+    for m, mesh in [(haldane(), [16, 16]), (hp.kane_mele(tb.tb_model), [12, 12])]:
+        kk = m.k_uniform_mesh(mesh)
+        e, mom, om = omr.moments(m, kk)
+        levels = safe_levels(e, np.linspace(e.min() - 0.2, e.max() + 0.2, 9))
+        prefix = omr.scan_t0(e, mom, om, levels)
+        cross = omr.scan_t0_crossing(m, kk, levels)
+        close(prefix, cross, np.max(np.abs(mom)) + np.max(np.abs(om)) * np.max(np.abs(levels) + np.abs(e).max()), 1e-12)
+
+
+def test_numpy_streda_slope_in_the_haldane_gap():
+    m = haldane()
+    mesh = [48, 48]
+    kk = m.k_uniform_mesh(mesh)
+    e, mom, om = omr.moments(m, kk)
+    lo, hi = e[0].max(), e[1].min()
+    mus = np.array([lo + 0.2 * (hi - lo), lo + 0.8 * (hi - lo)])
+    scan = omr.scan_t0(e, mom, om, mus).mean(axis=1)
+    assert abs((scan[1] - scan[0]) / (mus[1] - mus[0]) + TWO_PI) < 1e-8
+    lc, ic, oc = (v.mean() for v in omr.band_set(m, kk, [0]))
+    assert abs(oc + TWO_PI) < 1e-8
+    for mu, s in zip(mus, scan):
+        assert abs(lc + ic + mu * oc - s) < 1e-10
+
+
+def test_numpy_two_state_identity():
+    """m_0 = m_1 = (E_0 - E_1) Omega_0 / 2 = -d.(d_a d x d_b d) / (2 |d|^2) for H = d_0 + d.sigma, on random k."""
+    m = haldane()
+    k = np.random.default_rng(2).random((64, 2))
+    e, mom, om = omr.moments(m, k)
+    scale = np.max(np.abs(mom))
+    close(mom[0], 0.5 * (e[0] - e[1]) * om[0], scale, 1e-12)
+    close(mom[1], mom[0], scale, 1e-12)
+    from oracle import tb_oracle as orc
+    h, ha, hb = orc.ham_batch(m, k), cr.dham_batch(m, k, 0), cr.dham_batch(m, k, 1)
+    vec = lambda x: np.stack([x[:, 0, 1].real, -x[:, 0, 1].imag, 0.5 * (x[:, 0, 0] - x[:, 1, 1]).real], axis=1)  # noqa: E731
+    d, da, db = vec(h), vec(ha), vec(hb)
+    closed = -np.einsum("ki,ki->k", d, np.cross(da, db)) / (2.0 * np.einsum("ki,ki->k", d, d))
+    close(mom[0], closed, scale, 1e-12)
+
+
+def test_numpy_finite_temperature_tends_to_t0():
+    m = haldane()
+    kk = m.k_uniform_mesh([32, 32])
+    e, mom, om = omr.moments(m, kk)
+    mu = 0.5 * (e[0].max() + e[1].min())
+    t0 = omr.scan_t0(e, mom, om, [mu]).mean()
+    kt = omr.scan_kt(e, mom, om, [mu], 1e-4).mean()
+    assert abs(kt - t0) <= 1e-12 * max(1.0, abs(t0))
+
+
+def test_numpy_flake_sign_anchor():
+    """Haldane (delta 0.2, t -1, t2 0.15i) at mu = 0.3: the bulk -M/(2 pi)^2 = +0.0477 (= 0.3 / 2 pi) and a 20 x 20 flake's
+    (1/2A) sum_{E <= mu} <x v_y - y v_x> (charge +1) = 0.0418 have the same sign and agree within 15 %."""
+    m = haldane()
+    kk = m.k_uniform_mesh([64, 64])
+    e, mom, om = omr.moments(m, kk)
+    bulk = -omr.scan_t0(e, mom, om, [0.3]).mean() / TWO_PI ** 2
+    assert abs(bulk - 0.3 / TWO_PI) < 1e-6
+    L = 20
+    flake = quiet(quiet(m.cut_piece, L, 0).cut_piece, L, 1)
+    area = L * L * abs(np.linalg.det(np.array(hp.LAT)))
+    fl = omr.flake_magnetization(flake, 0.3, area)
+    assert np.sign(fl) == np.sign(bulk)
+    assert abs(fl - bulk) <= 0.15 * abs(bulk)
+
+
+# ---------------------------------------------------------------- GPU
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", list(CURV_MODELS))
+def test_moment_on_random_k(name):
+    make, occ = CURV_MODELS[name]
+    m = make()
+    k = np.random.default_rng(7).random((64, m._dim_k))
+    for dirs in ([(0, 1), (2, 0)] if m._dim_k == 3 else [(0, 1), (1, 0)]):
+        _, mom, _ = omr.moments(m, k, dirs)
+        got = m.orbital_moment(k, dirs=dirs)
+        assert got.shape == mom.shape
+        ok = cr.smallest_gap(m, k) >= 1e-3
+        assert ok.sum() >= 16
+        close(got[:, ok], mom[:, ok], np.max(np.abs(mom[:, ok])))
+        lc, ic, _ = omr.band_set(m, k, occ, dirs)
+        got = m.orbital_moment(k, occ=occ, dirs=dirs)
+        assert got.shape == (64,)
+        ok = cr.smallest_gap(m, k, occ=occ) >= 1e-3
+        assert ok.sum() >= 16
+        close(got[ok], (lc + ic)[ok], np.max(np.abs(lc[ok])) + np.max(np.abs(ic[ok])))
+
+
+@pytest.mark.gpu
+def test_one_state_model_gives_zeros():
+    m = one_state()
+    k = np.random.default_rng(1).random((9, 2))
+    assert np.all(m.orbital_moment(k) == np.zeros((1, 9)))
+    assert np.all(m.orbital_moment(k, occ=[0]) == 0.0)
+    assert m.orbital_moment(np.zeros((0, 2))).shape == (1, 0)
+    assert np.all(m.orbital_magnetization_mesh([8, 8], occ=[0]) == 0.0)
+    assert np.all(m.orbital_magnetization_mesh([8, 8], fermi_levels=[-1.0, 0.3, 2.0]) == 0.0)
+    assert np.all(m.orbital_magnetization_mesh([8, 8], fermi_levels=[0.3], kT=0.1) == 0.0)
+
+
+@pytest.mark.gpu
+def test_two_state_identity_against_berry_curvature():
+    m = haldane()
+    k = np.random.default_rng(3).random((256, 2))
+    mom = m.orbital_moment(k)
+    om = m.berry_curvature(k)
+    e = m.solve_all(k)
+    want = 0.5 * (e[0] - e[1]) * om[0]
+    scale = np.max(np.abs(want))
+    close(mom[0], want, scale, 1e-12)
+    close(mom[1], want, scale, 1e-12)
+
+
+MESH_CASES = {
+    "haldane": (haldane, [24, 24], [0]),
+    "kane_mele": (lambda: hp.kane_mele(tb.tb_model), [16, 16], [0, 1]),
+    "cubic16": (lambda: hp.cubic16(tb.tb_model), [6, 6, 5], list(range(8))),
+    "silicon": (silicon, [6, 6, 6], [0, 1, 2, 3]),
+}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", list(MESH_CASES))
+def test_mesh_forms_against_numpy(name):
+    make, mesh, occ = MESH_CASES[name]
+    m = make()
+    kk = m.k_uniform_mesh(mesh)
+    lc, ic, oc = omr.band_set(m, kk, occ)
+    got = m.orbital_magnetization_mesh(mesh, occ=occ)
+    want = np.array([omr.plane_means(v, mesh) for v in (lc, ic, oc)])
+    assert got.shape == want.shape
+    close(got, want, np.max(np.abs(lc)) + np.max(np.abs(ic)) + np.max(np.abs(oc)))
+    np.testing.assert_array_equal(got[2], m.berry_curvature_mesh(mesh, occ=occ))
+    if name == "kane_mele":
+        return
+    e, mom, om = omr.moments(m, kk)
+    levels = safe_levels(e, np.linspace(e.min() - 0.3, e.max() + 0.3, 7))
+    scale = np.max(np.abs(mom)) + np.max(np.abs(om)) * (np.max(np.abs(levels)) + np.max(np.abs(e)))
+    t0 = m.orbital_magnetization_mesh(mesh, fermi_levels=levels)
+    want = omr.plane_means(omr.scan_t0(e, mom, om, levels), mesh)
+    assert t0.shape == want.shape
+    close(t0, want, scale)
+    kt = m.orbital_magnetization_mesh(mesh, fermi_levels=levels, kT=0.05)
+    close(kt, omr.plane_means(omr.scan_kt(e, mom, om, levels, 0.05), mesh), scale)
+    if len(mesh) == 3:                                          # another plane orientation: slices along axis 1
+        got = m.orbital_magnetization_mesh(mesh, fermi_levels=levels[2:4], dirs=(2, 0))
+        e, mom, om = omr.moments(m, kk, (2, 0))
+        assert got.shape == (2, mesh[1])
+        close(got, omr.plane_means(omr.scan_t0(e, mom, om, levels[2:4]), mesh, (2, 0)), scale)
+
+
+@pytest.mark.gpu
+def test_streda_in_the_haldane_gap():
+    m = haldane()
+    mesh = [64, 64]
+    e = m.solve_all_mesh(mesh)
+    lo, hi = e[0].max(), e[1].min()
+    mus = np.array([lo + 0.2 * (hi - lo), lo + 0.8 * (hi - lo)])
+    scan = m.orbital_magnetization_mesh(mesh, fermi_levels=mus)
+    lc, ic, oc = m.orbital_magnetization_mesh(mesh, occ=[0])
+    i_mu = m.berry_curvature_mesh(mesh, fermi_levels=mus)
+    assert abs(oc / TWO_PI + 1.0) < 1e-9
+    assert np.max(np.abs(i_mu - oc)) < 1e-10
+    assert abs((scan[1] - scan[0]) - (mus[1] - mus[0]) * oc) < 1e-10
+    for mu, s in zip(mus, scan):
+        assert abs(lc + ic + mu * oc - s) < 1e-10
+    kt = m.orbital_magnetization_mesh(mesh, fermi_levels=mus, kT=1e-4)
+    assert np.max(np.abs(kt - scan)) < 1e-10
+
+
+@pytest.mark.gpu
+def test_time_reversal_graphene_and_silicon():
+    g = hp.graphene(tb.tb_model, delta=0.2)
+    mom = g.orbital_moment([[2.0 / 3.0, 1.0 / 3.0], [1.0 / 3.0, 2.0 / 3.0]])
+    assert abs(mom[0, 0] + 85.473) < 1e-3 and abs(mom[0, 1] - 85.473) < 1e-3
+    assert abs(mom[0, 0] + mom[0, 1]) <= 1e-10 * abs(mom[0, 0])
+    mesh = [48, 48]
+    e, mm, om = omr.moments(g, g.k_uniform_mesh(mesh))
+    scale = np.max(np.abs(mm)) + np.max(np.abs(om)) * np.max(np.abs(e))
+    mu = 0.5 * (e[0].max() + e[1].min())
+    assert np.max(np.abs(g.orbital_magnetization_mesh(mesh, fermi_levels=[mu, e.max() + 1.0]))) <= 1e-12 * scale
+    assert abs(g.orbital_magnetization_mesh(mesh, fermi_levels=[mu], kT=0.05)[0]) <= 1e-12 * scale
+    assert np.max(np.abs(g.orbital_magnetization_mesh(mesh, occ=[0])[:2].sum())) <= 1e-12 * scale
+    si = silicon()
+    mesh = [8, 8, 8]
+    kk = si.k_uniform_mesh(mesh)
+    e, mm, om = omr.moments(si, kk)
+    scale = np.max(np.abs(mm)) + np.max(np.abs(om)) * np.max(np.abs(e))
+    gap = 0.5 * (e[3].max() + e[4].min())
+    levels = safe_levels(e, [e.min() - 1.0, gap, e.max() + 1.0])
+    scan = si.orbital_magnetization_mesh(mesh, fermi_levels=levels)
+    assert scan.shape == (3, 8)
+    assert np.all(scan[0] == 0.0)
+    # The Wannier data split degenerate levels by ~1e-5, so single bands carry terms of ~1e13 that cancel in the sum: M(mu)
+    # vanishes to their round-off.  The gapped valence set is well conditioned; its slice means vanish up to the data's own
+    # small breaking of the symmetries (a fraction of a percent of its per-point terms, as in NumPy).
+    assert np.max(np.abs(scan)) <= 1e-14 * scale
+    lc, ic, oc = omr.band_set(si, kk, [0, 1, 2, 3])
+    pscale = np.max(np.abs(lc)) + np.max(np.abs(ic)) + np.max(np.abs(oc))
+    st = si.orbital_magnetization_mesh(mesh, occ=[0, 1, 2, 3])
+    close(st, np.array([omr.plane_means(v, mesh) for v in (lc, ic, oc)]), pscale)
+    assert np.max(np.abs(st)) <= 1e-2 * pscale
+    assert np.max(np.abs(st[0] + st[1] + levels[1] * st[2] - scan[1])) <= 1e-14 * scale
+
+
+@pytest.mark.gpu
+def test_list_and_mesh_agree_and_repeat():
+    for m, mesh, occ in [(haldane(), [64, 64], [0]), (hp.kane_mele(tb.tb_model), [32, 32], [0, 1]),
+                         (supercell(haldane(), 3), [16, 16], list(range(9)))]:
+        kk = m.k_uniform_mesh(mesh)
+        lst = m.orbital_moment(kk, occ=occ)
+        st = m.orbital_magnetization_mesh(mesh, occ=occ)
+        assert abs(lst.mean() - (st[0] + st[1])) <= 1e-12 * max(1.0, np.max(np.abs(lst)))
+        np.testing.assert_array_equal(st, m.orbital_magnetization_mesh(mesh, occ=occ))
+        e = m.solve_all_mesh(mesh)
+        levels = np.linspace(e.min(), e.max(), 11)
+        for kT in (0.0, 0.05):
+            a = m.orbital_magnetization_mesh(mesh, fermi_levels=levels, kT=kT)
+            np.testing.assert_array_equal(a, m.orbital_magnetization_mesh(mesh, fermi_levels=levels, kT=kT))
+        perm = np.random.default_rng(3).permutation(len(levels))
+        np.testing.assert_array_equal(m.orbital_magnetization_mesh(mesh, fermi_levels=levels[perm]),
+                                      m.orbital_magnetization_mesh(mesh, fermi_levels=levels)[perm])
+
+
+@pytest.mark.gpu
+def test_chunks_of_a_16_state_mesh():
+    """cubic16 on 24 x 24 x 16 = 9216 points: two chunks of the n != 2 path (8192 points of 16 x 16 eigenvectors each)."""
+    m = hp.cubic16(tb.tb_model)
+    mesh = [24, 24, 16]
+    kk = m.k_uniform_mesh(mesh)
+    e, mom, om = omr.moments(m, kk)
+    levels = safe_levels(e, [-2.5, -1.0, 0.0, 1.5])
+    scale = np.max(np.abs(mom)) + np.max(np.abs(om)) * (np.max(np.abs(levels)) + np.max(np.abs(e)))
+    got = m.orbital_magnetization_mesh(mesh, fermi_levels=levels)
+    assert got.shape == (4, 16)
+    close(got, omr.plane_means(omr.scan_t0(e, mom, om, levels), mesh), scale)
+    got = m.orbital_magnetization_mesh(mesh, fermi_levels=levels, kT=0.05)
+    close(got, omr.plane_means(omr.scan_kt(e, mom, om, levels, 0.05), mesh), scale)
+    lc, ic, oc = omr.band_set(m, kk, list(range(8)))
+    got = m.orbital_magnetization_mesh(mesh, occ=list(range(8)))
+    close(got, np.array([omr.plane_means(v, mesh) for v in (lc, ic, oc)]),
+          np.max(np.abs(lc)) + np.max(np.abs(ic)) + np.max(np.abs(oc)))
