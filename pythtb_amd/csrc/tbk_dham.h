@@ -1,5 +1,6 @@
-// tbk_dham.h -- the gradient form of the model's slot sums, the n = 2 closed form and the mesh-plane geometry, shared by the
-// Kubo-formula translation units (tbk_curv.hip, tbk_optics.hip, tbk_orbmag.hip; DESIGN.md sections 11 to 13).
+// tbk_dham.h -- the gradient form of the model's slot sums, the degeneracy rule, the n = 2 closed form and the mesh-plane geometry of
+// the Kubo-formula translation units (tbk_curv.hip, tbk_optics.hip, tbk_orbmag.hip; DESIGN.md sections 11 to 13).  The kernels and the
+// host pipeline they share are in tbk_kubo.h, which includes this file.
 #pragma once
 #include "tbk_solve_dev.h"
 
@@ -52,6 +53,11 @@ __device__ __forceinline__ void k_phases(const ModelView& mv, const double* __re
     }
 }
 
+// the degeneracy rule of the interband sums: the pair (E_n, E_m), de = E_n - E_m of either sign, contributes nothing (NaN: nothing)
+__device__ __forceinline__ bool kubo_degenerate(const double de, const double en, const double em) {
+    return !(fabs(de) > 1e-9 * fmax(1.0, fmax(fabs(en), fabs(em))));
+}
+
 // ---------------------------------------------------------------- n = 2: closed form in registers
 struct Curv2 {
     double e0, e1, om;   // eigenvalues (ascending) and Omega_0 without the degeneracy rule (Omega_1 = -om)
@@ -78,7 +84,7 @@ __device__ __forceinline__ Curv2 curv2_point(const ModelView& mv, const double (
     r.e0 = mid - dn;
     r.e1 = mid + dn;
     r.om = (dx * cx + dy * cy + dz * cz) / (2.0 * d2 * dn);
-    r.degenerate = !(r.e1 - r.e0 > 1e-9 * fmax(1.0, fmax(fabs(r.e0), fabs(r.e1))));
+    r.degenerate = kubo_degenerate(r.e1 - r.e0, r.e0, r.e1);
     return r;
 }
 
@@ -108,8 +114,3 @@ __device__ __forceinline__ double block_sum(double v, double* red) {
     __syncthreads();
     return (red[0] + red[1]) + (red[2] + red[3]);
 }
-
-// 33..2048 states: W^d = d_d H U^T of a chunk from the non-empty slots, wt[ik][2][n][n] (defined in tbk_curv.hip; launched
-// by tbk_orbmag.hip as well)
-__global__ void k_curv_wsp(const ModelView mv, const double* __restrict__ k, const cd* __restrict__ evec, const int64_t nk,
-                           const int d0, const int d1, cd* __restrict__ wt);

@@ -1,0 +1,488 @@
+// tbk_kubo.h -- what the Kubo-formula translation units share beyond the d H formula of tbk_dham.h (DESIGN.md sections 11 to 14):
+//   device   the contraction of the solver's eigenvectors with d_a H, d_b H (k_kubo_lds up to 32 states; k_kubo_wsp, k_kubo_contract and
+//            k_kubo_occ_sum from 33), templates over a policy Q that says what a (point, band) lane keeps of a pair; the n = 2 mesh
+//            source; the T = 0 Fermi scan k_kubo_fermi and the row sum k_kubo_rows
+//   host     the argument checks, the mesh planes, the sort of the Fermi levels and the chunk pipeline (KuboChunks, kubo_for_chunks)
+// tbk_curv.hip and tbk_orbmag.hip use all of it, tbk_optics.hip the chunk pipeline.  The library is built without relocatable device
+// code, so every kernel here is a template or static: each unit that launches one holds its own definition and host stub.
+#pragma once
+#include <algorithm>
+#include <cmath>
+#include <numeric>
+#include <vector>
+#include "tbk_dham.h"
+
+static inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
+static inline unsigned nblk(int64_t threads) { return (unsigned)((threads + 255) / 256); }
+
+// ---------------------------------------------------------------- n = 2 on a mesh: the closed form at plane point ii
+struct Kubo2Src {
+    ModelView mv;
+    int d0, d1, occ_sign;   // occ_sign: the band set {0} (+1) or {1} (-1); 0 per band
+    __device__ __forceinline__ Curv2 at(const PlaneArgs& P, const int (&ii)[3]) const {
+        double kk[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+        for (int d = 0; d < 3; ++d)
+            if (d < mv.dim_k) kk[d] = (double)ii[d] / (double)P.N[d];   // k_uniform_mesh's point, bit for bit
+        return curv2_point(mv, kk, d0, d1);
+    }
+};
+
+// ---------------------------------------------------------------- reductions
+// T = 0 Fermi scan: every (point, band) item of slice s adds its NQ quantities (Src::band) to the bins of the first sorted level
+// mu_j >= E_n.  A tile of 256 items is staged in LDS as (bin, quantities); each lane owns a fixed range of the window's bins and adds
+// the tile's items in item order.  blockIdx.x = g of gx (tiles g, g + gx, ...), blockIdx.y = slice (and every gridDim.y after it),
+// blockIdx.z = window of 4096 / NQ levels (32 KiB of bins).  part[s][j][NQ][gx]
+static const int kFermiBins = 4096;
+template <class Src, int NQ>
+__global__ __launch_bounds__(256) void k_kubo_fermi(const Src src, const PlaneArgs P, const int nb, const double* __restrict__ mu,
+                                                    const int nmu, double* __restrict__ part) {
+    constexpr int WIN = kFermiBins / NQ;
+    __shared__ double bins[NQ][WIN];
+    __shared__ double tw[NQ][256];
+    __shared__ int tb[256];
+    for (int s = blockIdx.y; s < P.nslice; s += gridDim.y) {   // (slices beyond the grid's y limit: the next pass)
+        const int w0 = blockIdx.z * WIN, wn = min(WIN, nmu - w0);
+        for (int j = threadIdx.x; j < WIN; j += 256)
+#pragma unroll
+            for (int c = 0; c < NQ; ++c) bins[c][j] = 0.0;
+        const int per = (wn + 255) / 256;
+        const int lo = threadIdx.x * per, hi = min(wn, lo + per);
+        const int64_t total = P.nplane * nb;
+        for (int64_t t0 = (int64_t)blockIdx.x * 256; t0 < total; t0 += (int64_t)gridDim.x * 256) {
+            const int64_t it = t0 + threadIdx.x;
+            int bin = -1;
+            double w[NQ];
+#pragma unroll
+            for (int c = 0; c < NQ; ++c) w[c] = 0.0;
+            if (it < total) {
+                const int64_t p = it / nb;
+                const int band = (int)(it - p * nb);
+                int ii[3];
+                const int64_t idx = plane_point(P, s, p, ii);
+                double e;
+                src.band(P, ii, idx, band, e, w);
+                int l = 0, r = nmu;                  // first j with mu[j] >= e (nmu: above every level; NaN: nowhere)
+                while (l < r) {
+                    const int m = (l + r) >> 1;
+                    if (mu[m] < e) l = m + 1;
+                    else r = m;
+                }
+                bin = e == e ? l - w0 : -1;
+            }
+            __syncthreads();                         // the previous tile's items are consumed
+            tb[threadIdx.x] = bin;
+#pragma unroll
+            for (int c = 0; c < NQ; ++c) tw[c][threadIdx.x] = w[c];
+            __syncthreads();
+            for (int q = 0; q < 256; ++q) {
+                const int b = tb[q];
+                if (b >= lo && b < hi)
+#pragma unroll
+                    for (int c = 0; c < NQ; ++c) bins[c][b] += tw[c][q];
+            }
+        }
+        __syncthreads();
+        for (int j = threadIdx.x; j < wn; j += 256)
+#pragma unroll
+            for (int c = 0; c < NQ; ++c) part[(((int64_t)s * nmu + w0 + j) * NQ + c) * gridDim.x + blockIdx.x] = bins[c][j];
+        __syncthreads();                                           // (bins are reused by the next slice)
+    }
+}
+
+template <int NQ, class Src>
+static int kubo_fermi_launch(tbk_ctx* ctx, const Src& src, const PlaneArgs& P, int n, const double* mu_dev, int nmu, int gx, double* part) {
+    const unsigned nwin = (unsigned)((nmu + kFermiBins / NQ - 1) / (kFermiBins / NQ));
+    hipLaunchKernelGGL((k_kubo_fermi<Src, NQ>), dim3(gx, (unsigned)std::min(P.nslice, 65535), nwin), dim3(256), 0, ctx->stream, src, P, n,
+                       mu_dev, nmu, part);
+    TBK_HIP(hipGetLastError());
+    return TBK_OK;
+}
+
+// out[r] = sum_g part[r][g] in a fixed order (one workgroup per row)
+static __global__ __launch_bounds__(256) void k_kubo_rows(const double* __restrict__ part, const int gx, double* __restrict__ out) {
+    __shared__ double red[4];
+    const double* p = part + (int64_t)blockIdx.x * gx;
+    double acc = 0.0;
+    for (int g = threadIdx.x; g < gx; g += 256) acc += p[g];
+    const double t = block_sum(acc, red);
+    if (threadIdx.x == 0) out[blockIdx.x] = t;
+}
+
+// ---------------------------------------------------------------- n != 2: contraction of the solver's eigenvectors
+// A policy Q is what a (point, band b) lane keeps of its pairs (b, m), P_bm = Im V^a_bm V^b_mb and Delta = E_b - E_m:
+//   pair()    adds one pair (set: the call sums a band set -- b in occ, m outside, no degeneracy rule)
+//   band()    stores the lane's per-band result at i = b nfull + first + ik
+//   share()   stores the lane's NSET doubles of a band set's sums; set() stores a point's sums over b of them at i = first + ik
+//   kLabel    the ProfScope labels of k_kubo_lds, k_kubo_wsp, k_kubo_contract, k_kubo_occ_sum
+// CurvQ (tbk_curv.hip): Omega.  OrbQ (tbk_orbmag.hip): m and Omega, or (LC, IC, Omega_occ).
+//
+// Up to 32 states: ONE kernel, P = min(64, 4096 / (4 n^2)) points per workgroup, everything of a point in LDS (64 KiB):
+// U (its eigenvectors, read once from HBM), D = d_{d0} H and X = d_{d1} H (built from the non-empty slots), T = D U^T, then
+// D := V^{d0} = conj(U) T, T := X U^T, and one lane per (point, band) forms V^{d1} from T on the fly and feeds Q.
+// Nothing but Q's results is written.
+#define KUBO_LDS_CD 4096
+static inline int kubo_lds_points(int n) { return std::max(1, std::min(64, KUBO_LDS_CD / (4 * n * n))); }
+template <class Q>
+__global__ __launch_bounds__(256) void k_kubo_lds(const ModelView mv, const double* __restrict__ k, const cd* __restrict__ evec,
+                                                  const double* __restrict__ eval, const int64_t nk, const int d0, const int d1,
+                                                  const int P, const int* __restrict__ occ, const int64_t first, const int64_t nfull,
+                                                  const typename Q::Out out) {
+    __shared__ cd L[KUBO_LDS_CD];
+    const int n = mv.nsta, nn = n * n;
+    const int64_t ik0 = (int64_t)blockIdx.x * P;
+    const int np = (int)std::min<int64_t>(P, nk - ik0);
+    cd* U = L;
+    cd* D = L + P * nn;
+    cd* T = L + 2 * P * nn;
+    cd* X = L + 3 * P * nn;
+    for (int e = threadIdx.x; e < np * nn; e += 256) {
+        const int p = e / nn, r = e - p * nn, b = r / n, i = r - b * n;
+        U[e] = evec[((int64_t)b * nk + ik0 + p) * n + i];
+        D[e] = cd{0.0, 0.0};
+        X[e] = cd{0.0, 0.0};
+    }
+    __syncthreads();
+    for (int e = threadIdx.x; e < np * mv.nnz; e += 256) {
+        const int p = e / mv.nnz;
+        const int4 z4 = mv.nz[e - p * mv.nnz];
+        const int a = z4.x & 0xffff, b = z4.x >> 16;
+        double kk[4];
+        cd z[4];
+        k_phases(mv, k, ik0 + p, kk, z);
+        cd h, v0, v1;
+        dham_terms(mv, a, b, z4.y, z4.z, kk, z, d0, d1, h, v0, v1);
+        D[p * nn + a * n + b] = v0;
+        D[p * nn + b * n + a] = cconj(v0);
+        X[p * nn + a * n + b] = v1;
+        X[p * nn + b * n + a] = cconj(v1);
+    }
+    __syncthreads();
+    for (int e = threadIdx.x; e < np * nn; e += 256) {            // T = D U^T
+        const int p = e / nn, r = e - p * nn, i = r / n, mm = r - i * n;
+        const cd* dr = D + p * nn + i * n;
+        const cd* um = U + p * nn + mm * n;
+        cd acc{0.0, 0.0};
+        for (int j = 0; j < n; ++j) cfma(acc, dr[j], um[j]);
+        T[e] = acc;
+    }
+    __syncthreads();
+    for (int e = threadIdx.x; e < np * nn; e += 256) {            // D := V^{d0} = conj(U) T   (reads U, T only)
+        const int p = e / nn, r = e - p * nn, b = r / n, mm = r - b * n;
+        const cd* ub = U + p * nn + b * n;
+        const cd* tc = T + p * nn + mm;
+        cd acc{0.0, 0.0};
+        for (int i = 0; i < n; ++i) cfmac(acc, ub[i], tc[i * n]);
+        D[e] = acc;
+    }
+    __syncthreads();
+    for (int e = threadIdx.x; e < np * nn; e += 256) {            // T := X U^T
+        const int p = e / nn, r = e - p * nn, i = r / n, mm = r - i * n;
+        const cd* xr = X + p * nn + i * n;
+        const cd* um = U + p * nn + mm * n;
+        cd acc{0.0, 0.0};
+        for (int j = 0; j < n; ++j) cfma(acc, xr[j], um[j]);
+        T[e] = acc;
+    }
+    __syncthreads();
+    double* share = (double*)X;                                    // (X is dead: the band shares, NSET np n <= 2 P n^2 doubles)
+    for (int e = threadIdx.x; e < np * n; e += 256) {
+        const int p = e / n, b = e - p * n;
+        const int64_t ik = ik0 + p;
+        const double eb = eval[(int64_t)b * nk + ik];
+        const cd* ub = U + p * nn + b * n;
+        const cd* va = D + p * nn + b * n;
+        const cd* tp = T + p * nn;
+        Q q;
+        if (!occ || occ[b]) {
+            for (int mm = 0; mm < n; ++mm) {
+                if (mm == b) continue;
+                const double em = eval[(int64_t)mm * nk + ik];
+                const double de = eb - em;
+                if (occ ? occ[mm] != 0 : kubo_degenerate(de, eb, em)) continue;
+                cd vb{0.0, 0.0};
+                for (int i = 0; i < n; ++i) cfmac(vb, ub[i], tp[i * n + mm]);
+                const cd a = va[mm];
+                q.pair(a.y * vb.x - a.x * vb.y, de, eb, em, occ != nullptr);   // Im V^a_bm V^b_mb = Im V^a_bm conj(V^b_bm)
+            }
+        }
+        if (occ) q.share(share + Q::NSET * e, eb);
+        else q.band(out, (int64_t)b * nfull + first + ik, eb);
+    }
+    if (occ) {
+        __syncthreads();
+        for (int p = threadIdx.x; p < np; p += 256) {
+            double s[Q::NSET];
+#pragma unroll
+            for (int c = 0; c < Q::NSET; ++c) s[c] = 0.0;
+            for (int b = 0; b < n; ++b)
+#pragma unroll
+                for (int c = 0; c < Q::NSET; ++c) s[c] += share[Q::NSET * (p * n + b) + c];
+            Q::set(out, first + ik0 + p, nfull, s);
+        }
+    }
+}
+
+// 33..2048 states: W^d[ik][i][m] = sum_j d_d H_ij u_m[j] from the non-empty slots only (ModelView.nz; no dense d_d H), wt[ik][2][n][n].
+// Workgroup (point, block of 256 columns); lane m owns column m of both W^d -- every slot adds to two entries of each, and no other
+// lane touches them: no atomics, a fixed order.  The slot values (both directions) are computed once per point and staged in LDS.
+static __global__ __launch_bounds__(256) void k_kubo_wsp(const ModelView mv, const double* __restrict__ k, const cd* __restrict__ evec,
+                                                         const int64_t nk, const int d0, const int d1, cd* __restrict__ wt) {
+    __shared__ int sab[256];
+    __shared__ cd sv0[256], sv1[256];
+    const int n = mv.nsta;
+    const int64_t ik = blockIdx.x, nn = (int64_t)n * n;
+    const int m = blockIdx.y * 256 + threadIdx.x;
+    const bool live = m < n;
+    cd* w0 = wt + 2 * ik * nn;
+    cd* w1 = w0 + nn;
+    if (live)
+        for (int i = 0; i < n; ++i) {
+            w0[(int64_t)i * n + m] = cd{0.0, 0.0};
+            w1[(int64_t)i * n + m] = cd{0.0, 0.0};
+        }
+    double kk[4];
+    cd z[4];
+    k_phases(mv, k, ik, kk, z);
+    const cd* u = evec + ((int64_t)(live ? m : 0) * nk + ik) * n;
+    for (int q0 = 0; q0 < mv.nnz; q0 += 256) {
+        __syncthreads();
+        if (q0 + (int)threadIdx.x < mv.nnz) {
+            const int4 z4 = mv.nz[q0 + threadIdx.x];
+            cd h;
+            dham_terms(mv, z4.x & 0xffff, z4.x >> 16, z4.y, z4.z, kk, z, d0, d1, h, sv0[threadIdx.x], sv1[threadIdx.x]);
+            sab[threadIdx.x] = z4.x;
+        }
+        __syncthreads();
+        const int cnt = min(256, mv.nnz - q0);
+        if (!live) continue;
+        for (int q = 0; q < cnt; ++q) {
+            const int a = sab[q] & 0xffff, b = sab[q] >> 16;
+            const cd v0 = sv0[q], v1 = sv1[q], ub = u[b];
+            cd* pa0 = w0 + (int64_t)a * n + m;
+            cd* pa1 = w1 + (int64_t)a * n + m;
+            cd t0 = *pa0, t1 = *pa1;
+            cfma(t0, v0, ub);
+            cfma(t1, v1, ub);
+            *pa0 = t0;
+            *pa1 = t1;
+            if (a != b) {
+                const cd ua = u[a];
+                cd* pb0 = w0 + (int64_t)b * n + m;
+                cd* pb1 = w1 + (int64_t)b * n + m;
+                cd s0 = *pb0, s1 = *pb1;
+                cfma(s0, cconj(v0), ua);
+                cfma(s1, cconj(v1), ua);
+                *pb0 = s0;
+                *pb1 = s1;
+            }
+        }
+    }
+}
+
+// 33..2048 states, one lane per (ik, band b) on k_kubo_wsp's W^d: V^d_{b,m} = sum_i conj(u_b[i]) W^d[i][m], fed to Q as in k_kubo_lds.
+// A band set's shares go to tmp[ik][b][NSET], summed per point by k_kubo_occ_sum.
+template <class Q>
+__global__ __launch_bounds__(256) void k_kubo_contract(const cd* __restrict__ evec, const double* __restrict__ eval,
+                                                       const cd* __restrict__ wt, const int64_t nk, const int n,
+                                                       const int* __restrict__ occ, const int64_t first, const int64_t nfull,
+                                                       const typename Q::Out out, double* __restrict__ tmp) {
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= nk * n) return;
+    const int64_t ik = idx / n;
+    const int b = (int)(idx - ik * n);
+    const int64_t nn = (int64_t)n * n;
+    const cd* u = evec + ((int64_t)b * nk + ik) * n;
+    const cd* w0 = wt + (2 * ik) * nn;
+    const cd* w1 = w0 + nn;
+    const double eb = eval[(int64_t)b * nk + ik];
+    Q q;
+    if (!occ || occ[b]) {
+        for (int m = 0; m < n; ++m) {
+            if (m == b) continue;
+            const double em = eval[(int64_t)m * nk + ik];
+            const double de = eb - em;
+            if (occ ? occ[m] != 0 : kubo_degenerate(de, eb, em)) continue;
+            cd va{0.0, 0.0}, vb{0.0, 0.0};
+            for (int i = 0; i < n; ++i) {
+                cfmac(va, u[i], w0[(int64_t)i * n + m]);
+                cfmac(vb, u[i], w1[(int64_t)i * n + m]);
+            }
+            q.pair(va.y * vb.x - va.x * vb.y, de, eb, em, occ != nullptr);   // Im V^a_bm V^b_mb = Im V^a_bm conj(V^b_bm)
+        }
+    }
+    if (occ) q.share(tmp + Q::NSET * idx, eb);
+    else q.band(out, (int64_t)b * nfull + first + ik, eb);
+}
+
+template <class Q>
+__global__ __launch_bounds__(256) void k_kubo_occ_sum(const double* __restrict__ tmp, const int64_t nk, const int n, const int64_t first,
+                                                      const int64_t nfull, const typename Q::Out out) {
+    const int64_t ik = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (ik >= nk) return;
+    double s[Q::NSET];
+#pragma unroll
+    for (int c = 0; c < Q::NSET; ++c) s[c] = 0.0;
+    for (int b = 0; b < n; ++b)
+#pragma unroll
+        for (int c = 0; c < Q::NSET; ++c) s[c] += tmp[Q::NSET * (ik * n + b) + c];
+    Q::set(out, first + ik, nfull, s);
+}
+
+// ---------------------------------------------------------------- host side: checks and mesh set-up
+// the argument checks of a (dir0, dir1) quantity `what`; mask (n entries) = 1 for the bands of occ, empty without occ
+static int kubo_check(const char* fn, const char* what, tbk_model* m, int dir0, int dir1, const int32_t* occ, int nocc,
+                      std::vector<int>& mask) {
+    TBK_REQUIRE(m, TBK_EINVAL, "%s: null model", fn);
+    TBK_REQUIRE(m->dim_k >= 2, TBK_EINVAL, "%s: the %s needs dim_k >= 2 (the model has %d)", fn, what, m->dim_k);
+    TBK_REQUIRE(dir0 >= 0 && dir0 < m->dim_k && dir1 >= 0 && dir1 < m->dim_k && dir0 != dir1, TBK_EINVAL,
+                "%s: dirs (%d, %d) must be two different axes in [0, %d)", fn, dir0, dir1, m->dim_k);
+    const int n = m->nsta;
+    mask.clear();
+    if (occ) {
+        TBK_REQUIRE(nocc >= 1 && nocc <= n, TBK_EINVAL, "%s: nocc=%d (1..%d)", fn, nocc, n);
+        mask.assign(n, 0);
+        for (int i = 0; i < nocc; ++i) {
+            TBK_REQUIRE(occ[i] >= 0 && occ[i] < n, TBK_EINVAL, "%s: occ[%d]=%d outside [0, %d)", fn, i, occ[i], n);
+            TBK_REQUIRE(!mask[occ[i]], TBK_EINVAL, "%s: band %d appears twice in occ", fn, occ[i]);
+            mask[occ[i]] = 1;
+        }
+    } else {
+        TBK_REQUIRE(nocc == 0, TBK_EINVAL, "%s: nocc=%d without occ", fn, nocc);
+    }
+    return TBK_OK;
+}
+
+// the (dir0, dir1) planes of a mesh of dim_k = 2 or 3 dimensions (checked by the caller)
+static int kubo_planes(const char* fn, const int32_t* mesh, int dir0, int dir1, int dk, PlaneArgs& P) {
+    P = PlaneArgs{};
+    P.npts = 1;
+    for (int d = 0; d < 3; ++d) {
+        if (d < dk) TBK_REQUIRE(mesh[d] >= 1, TBK_EINVAL, "%s: mesh[%d]=%d", fn, d, mesh[d]);
+        P.N[d] = d < dk ? mesh[d] : 1;
+        P.npts *= P.N[d];
+    }
+    P.da = dir0;
+    P.db = dir1;
+    P.dc = dk == 3 ? 3 - dir0 - dir1 : -1;
+    P.nplane = (int64_t)P.N[dir0] * P.N[dir1];
+    P.nslice = P.dc >= 0 ? P.N[P.dc] : 1;
+    return TBK_OK;
+}
+
+// mus = the levels in the order ord: ascending (ties by index) when `sorted`, else as given
+static void kubo_levels(const double* mu, int nmu, bool sorted, std::vector<int>& ord, std::vector<double>& mus) {
+    ord.resize(nmu);
+    std::iota(ord.begin(), ord.end(), 0);
+    if (sorted) std::stable_sort(ord.begin(), ord.end(), [&](int x, int y) { return mu[x] < mu[y]; });
+    mus.resize(nmu);
+    for (int j = 0; j < nmu; ++j) mus[j] = mu[ord[j]];
+}
+
+// workgroups per row of the plane sums and per (slice, level, quantity) of the Fermi scan: functions of the mesh shape, n, nmu, nq alone
+static inline int kubo_plane_gx(const PlaneArgs& P) {
+    return (int)std::max<int64_t>(1, std::min<int64_t>((P.nplane + 2047) / 2048, 1024));
+}
+static inline int kubo_fermi_gx(const PlaneArgs& P, int n, int nmu, int nq) {
+    const int64_t tiles = (P.nplane * n + 255) / 256;
+    const int64_t cap = std::max<int64_t>(1, ((int64_t)1 << 22) / ((int64_t)P.nslice * nmu * nq));
+    return (int)std::max<int64_t>(1, std::min<int64_t>({(tiles + 7) / 8, 512, cap}));
+}
+
+// ---------------------------------------------------------------- host side: the chunk pipeline
+// The points [0, nk) of a k list or a mesh go through the solver in chunks of a fixed length, so that the chunking -- and with it
+// every result -- does not depend on the machine: at most kKuboChunkBytes of eigenvectors (a caller may shorten it further).
+// KuboChunks describes a chunk's workspace: k, eigenvalues and eigenvectors of `chunk` points, then up to three buffers of the caller
+// (x0, x1, x2 bytes); bytes() of scratch at `base`.
+static const size_t kKuboChunkBytes = (size_t)32 << 20;
+static inline int64_t kubo_chunk_len(int n, int64_t nk) {
+    const int64_t chunk = std::max<int64_t>(1, (int64_t)(kKuboChunkBytes / ((size_t)n * n * sizeof(cd))));
+    return std::min<int64_t>(chunk, std::max<int64_t>(nk, 1));
+}
+struct KuboChunks {
+    int64_t chunk = 0;
+    size_t off[7] = {0, 0, 0, 0, 0, 0, 0};   // of k, eigenvalues, eigenvectors, the three extra buffers, the end
+    unsigned char* base = nullptr;
+    KuboChunks() {}
+    KuboChunks(int n, int dk, int64_t chunk_, size_t x0, size_t x1, size_t x2) : chunk(chunk_) {
+        const size_t b[6] = {(size_t)chunk * dk * sizeof(double), (size_t)chunk * n * sizeof(double),
+                             (size_t)chunk * n * n * sizeof(cd), x0, x1, x2};
+        for (int i = 0; i < 6; ++i) off[i + 1] = off[i] + al256(b[i]);
+    }
+    size_t bytes() const { return off[6]; }
+    template <class T>
+    T* extra(int i) const { return (T*)(base + off[3 + i]); }
+};
+
+// body(first, cnt, k, eval, evec) for every chunk [first, first + cnt): k from k_all_dev (list) or generated from `mesh`, eval[n][cnt]
+// and evec[n][cnt][n] from tbk_solve_list_dev_checked, all on the device and valid until the next chunk
+template <class Body>
+static int kubo_for_chunks(tbk_model* m, const KuboChunks& w, const double* k_all_dev, const int32_t* mesh, int64_t nk, Body&& body) {
+    double* kc = (double*)(w.base + w.off[0]);
+    double* ec = (double*)(w.base + w.off[1]);
+    cd* vc = (cd*)(w.base + w.off[2]);
+    for (int64_t first = 0; first < nk; first += w.chunk) {
+        const int64_t cnt = std::min<int64_t>(w.chunk, nk - first);
+        const double* kp = kc;
+        if (mesh) {
+            int rc = tbk_k_uniform_mesh_range_dev(m->ctx, m->dim_k, mesh, first, cnt, kc);
+            if (rc) return rc;
+        } else {
+            kp = k_all_dev + first * m->dim_k;
+        }
+        int rc = tbk_solve_list_dev_checked(m, kp, cnt, ec, (double*)vc);
+        if (rc) return rc;
+        rc = body(first, cnt, kp, (const double*)ec, (const cd*)vc);
+        if (rc) return rc;
+    }
+    return TBK_OK;
+}
+
+// The n != 2 contraction over points [0, nk) with policy Q: its workspace (W^d from 33 states, the occ mask, the band-set shares of
+// the wide form) and the pipeline.  Per band Q::band's arrays at stride nk, band set (mask not empty) Q::set's.
+static KuboChunks kubo_contract_chunks(int n, int dk, int64_t nk, bool manifold, int nset) {
+    const int64_t chunk = kubo_chunk_len(n, nk);
+    const bool wide = n > 32;
+    return KuboChunks(n, dk, chunk, wide ? 2 * (size_t)chunk * n * n * sizeof(cd) : 0, (size_t)n * sizeof(int),
+                      wide && manifold ? (size_t)nset * chunk * n * sizeof(double) : 0);
+}
+template <class Q>
+static int kubo_contract(tbk_model* m, const double* k_all_dev, const int32_t* mesh, int64_t nk, int d0, int d1,
+                         const std::vector<int>& mask, const KuboChunks& w, const typename Q::Out out) {
+    tbk_ctx* ctx = m->ctx;
+    const int n = m->nsta;
+    cd* wt = w.extra<cd>(0);
+    int* occ_dev = w.extra<int>(1);
+    double* tmp = w.extra<double>(2);
+    const bool manifold = !mask.empty();
+    const int* occ = manifold ? (const int*)occ_dev : (const int*)nullptr;
+    if (manifold) TBK_HIP(hipMemcpyAsync(occ_dev, mask.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    return kubo_for_chunks(m, w, k_all_dev, mesh, nk, [&](int64_t first, int64_t cnt, const double* kp, const double* ec, const cd* vc) -> int {
+        if (n <= 32) {
+            const int P = kubo_lds_points(n);
+            ProfScope ps(ctx, Q::kLabel[0]);
+            hipLaunchKernelGGL(k_kubo_lds<Q>, dim3((unsigned)((cnt + P - 1) / P)), dim3(256), 0, ctx->stream, m->view, kp, vc, ec, cnt, d0,
+                               d1, P, occ, first, nk, out);
+            TBK_HIP(hipGetLastError());
+            return TBK_OK;
+        }
+        {
+            ProfScope ps(ctx, Q::kLabel[1]);
+            hipLaunchKernelGGL(k_kubo_wsp, dim3((unsigned)cnt, (unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, m->view, kp, vc, cnt,
+                               d0, d1, wt);
+            TBK_HIP(hipGetLastError());
+        }
+        {
+            ProfScope ps(ctx, Q::kLabel[2]);
+            hipLaunchKernelGGL(k_kubo_contract<Q>, dim3(nblk(cnt * n)), dim3(256), 0, ctx->stream, vc, ec, (const cd*)wt, cnt, n, occ, first,
+                               nk, out, tmp);
+            TBK_HIP(hipGetLastError());
+        }
+        if (manifold) {
+            ProfScope ps(ctx, Q::kLabel[3]);
+            hipLaunchKernelGGL(k_kubo_occ_sum<Q>, dim3(nblk(cnt)), dim3(256), 0, ctx->stream, (const double*)tmp, cnt, n, first, nk, out);
+            TBK_HIP(hipGetLastError());
+        }
+        return TBK_OK;
+    });
+}

@@ -9,8 +9,8 @@
 // so a pair is a RECORD of 1 + ns + na doubles: eps (-1: the pair adds nothing), the symmetric weights A = c Re P_ab (a <= b) and
 // the antisymmetric ones B = c Im P_ab (a < b) of the components asked for.
 //
-// Pipeline, in chunks of a fixed number of points (kOptChunkBytes of eigenvectors, kOptRecBytes of records): the device k generator,
-// the eigen-solver with vectors, then the PAIR stage writes the chunk's records at a fixed stride of n (n - 1) / 2 per point
+// Pipeline, in chunks of a fixed number of points (tbk_kubo.h's chunk pipeline: kKuboChunkBytes of eigenvectors, here also
+// kOptRecBytes of records): the device k generator, the eigen-solver with vectors, then the PAIR stage writes the chunk's records at a fixed stride of n (n - 1) / 2 per point
 //   n <= 32    k_opt_pairs: U, d_d H for every direction asked for, and V^d = conj(U) d_d H U^T of several points in LDS
 //   n > 32     k_opt_wsp (W^d = d_d H U^T from the sparse slots), k_opt_vprod (V^d = conj(U) W^d, LDS tiles), k_opt_pairs_wide
 // and the FREQUENCY stage k_opt_omega (two frequencies per lane, the records read as wave-uniform values) adds each k-group's sums
@@ -18,12 +18,8 @@
 // components alone, and nothing uses atomics: two calls give the same bits on any machine.
 #include <math.h>
 #include <string.h>
-#include <algorithm>
-#include <cmath>
-#include <vector>
-#include "tbk_dham.h"
+#include "tbk_kubo.h"
 
-static const size_t kOptChunkBytes = (size_t)32 << 20;   // eigenvectors per chunk (the budget of section 11)
 static const size_t kOptRecBytes = (size_t)256 << 20;    // pair records per chunk
 static const int kOptTile = 512;                         // frequencies per workgroup of k_opt_omega (two per lane)
 static const int64_t kOptPartCap = (int64_t)1 << 24;     // doubles of part[G][rows]: G shrinks as the frequencies grow
@@ -65,8 +61,7 @@ template <class Vel>
 __device__ __forceinline__ void opt_record(double* __restrict__ r, const OptFields& F, const double en, const double em, const double mu,
                                            const double kT, const Vel& vel) {
     const double eps = em - en;
-    const bool keep = eps > 1e-9 * fmax(1.0, fmax(fabs(en), fabs(em)));
-    const double c = keep ? opt_weight(en, em, eps, mu, kT) : 0.0;
+    const double c = kubo_degenerate(eps, en, em) ? 0.0 : opt_weight(en, em, eps, mu, kT);
     const int nf = F.ns + F.na;
     if (c == 0.0) {
         r[0] = -1.0;
@@ -322,29 +317,17 @@ __global__ __launch_bounds__(256) void k_opt_omega(const double* __restrict__ re
     }
 }
 
-// sum over the 256 threads of a workgroup in a fixed order (shuffle tree in each wavefront, then the four in order); thread 0 has it
-__device__ __forceinline__ double opt_block_sum(double v, double* red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
-}
-
 // rows[r] = inv sum_g part[g][r] in a fixed order (one workgroup per row)
 __global__ __launch_bounds__(256) void k_opt_rows(const double* __restrict__ part, const int G, const int64_t nrows, const double inv,
                                                   double* __restrict__ rows) {
     __shared__ double red[4];
     double acc = 0.0;
     for (int g = threadIdx.x; g < G; g += 256) acc += part[(int64_t)g * nrows + blockIdx.x];
-    const double t = opt_block_sum(acc, red);
+    const double t = block_sum(acc, red);
     if (threadIdx.x == 0) rows[blockIdx.x] = t * inv;
 }
 
 // ---------------------------------------------------------------- host side
-static inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
-static inline unsigned nblk(int64_t threads) { return (unsigned)((threads + 255) / 256); }
-
 template <int NS, int NA>
 static int opt_omega_launch(tbk_ctx* ctx, dim3 grid, const double* rec, int64_t cnt, int64_t npair, int G, const double* om, int nw,
                             double eta, int accumulate, double* part) {
@@ -404,20 +387,18 @@ extern "C" int tbk_optical_cond_mesh(tbk_model* m, const int32_t* mesh, int nome
     const int nf = F.ns + F.na, R = 1 + nf;
     // chunk, k-groups and tiles: functions of (mesh, n, dim_k, nomega, components) only
     const size_t vb = (size_t)n * n * sizeof(cd), rb = (size_t)npair * R * sizeof(double);
-    int64_t chunk = std::max<int64_t>(1, std::min<int64_t>((int64_t)(kOptChunkBytes / vb), (int64_t)(kOptRecBytes / rb)));
-    chunk = std::min<int64_t>(chunk, npts);
+    const int64_t chunk = std::min<int64_t>(kubo_chunk_len(n, npts), std::max<int64_t>(1, (int64_t)(kOptRecBytes / rb)));
     const int64_t nrows = 2 * (int64_t)nf * nomega;
     const int G = (int)std::max<int64_t>(1, std::min<int64_t>({kOptPartCap / nrows, (int64_t)kOptGroupsMax, chunk}));
     const unsigned ntile = (unsigned)((nomega + kOptTile - 1) / kOptTile);
     const bool wide = n > 32;
     const size_t omb = al256((size_t)nomega * sizeof(double)), partb = al256((size_t)G * nrows * sizeof(double)),
-                 rowb = al256((size_t)nrows * sizeof(double)), kb = al256((size_t)chunk * dk * sizeof(double)),
-                 eb = al256((size_t)chunk * n * sizeof(double)), ub = al256((size_t)chunk * vb), recb = al256((size_t)chunk * rb),
-                 wb = wide ? al256((size_t)chunk * F.nd * vb) : 0;
+                 rowb = al256((size_t)nrows * sizeof(double)), wb = wide ? (size_t)chunk * F.nd * vb : 0;
+    KuboChunks cw(n, dk, chunk, (size_t)chunk * rb, wb, wb);   // the records, then W^d and V^d of the wide form
     tbk_ctx* ctx = m->ctx;
     TBK_HIP(hipSetDevice(ctx->device));
     void* base = nullptr;
-    int rc = tbk_ctx_scratch(ctx, 256 + omb + partb + rowb + kb + eb + ub + recb + 2 * wb, &base);
+    int rc = tbk_ctx_scratch(ctx, 256 + omb + partb + rowb + cw.bytes(), &base);
     if (rc) return rc;
     unsigned char* p = (unsigned char*)base + 256;
     double* om_dev = (double*)p;
@@ -425,62 +406,50 @@ extern "C" int tbk_optical_cond_mesh(tbk_model* m, const int32_t* mesh, int nome
     double* part = (double*)p;
     p += partb;
     double* rows = (double*)p;
-    p += rowb;
-    double* kc = (double*)p;
-    p += kb;
-    double* ec = (double*)p;
-    p += eb;
-    cd* vc = (cd*)p;
-    p += ub;
-    double* rec = (double*)p;
-    p += recb;
-    cd* wt = (cd*)p;
-    cd* vt = (cd*)(p + wb);
+    cw.base = p + rowb;
+    double* rec = cw.extra<double>(0);
+    cd* wt = cw.extra<cd>(1);
+    cd* vt = cw.extra<cd>(2);
     TBK_HIP(hipMemcpyAsync(om_dev, omega, (size_t)nomega * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     const int P = opt_lds_points(n, F.nd);
     const size_t lds = (size_t)(F.nd + 2) * P * n * n * sizeof(cd);
     if (!wide && lds > 64 * 1024)
         TBK_HIP(hipFuncSetAttribute((const void*)k_opt_pairs, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    for (int64_t first = 0; first < npts; first += chunk) {
-        const int64_t cnt = std::min<int64_t>(chunk, npts - first);
-        rc = tbk_k_uniform_mesh_range_dev(ctx, dk, mesh, first, cnt, kc);
-        if (rc) return rc;
-        rc = tbk_solve_list_dev_checked(m, kc, cnt, ec, (double*)vc);
-        if (rc) return rc;
+    rc = kubo_for_chunks(m, cw, nullptr, mesh, npts, [&](int64_t first, int64_t cnt, const double* kc, const double* ec, const cd* vc) -> int {
         if (!wide) {
             ProfScope ps(ctx, "opt_pairs");
             hipLaunchKernelGGL(k_opt_pairs, dim3((unsigned)((cnt + P - 1) / P)), dim3(256), lds, ctx->stream, m->view,
-                               (const double*)kc, (const cd*)vc, (const double*)ec, cnt, F, P, mu, kT, rec);
+                               kc, vc, ec, cnt, F, P, mu, kT, rec);
             TBK_HIP(hipGetLastError());
         } else {
             {
                 ProfScope ps(ctx, "opt_wide");
                 hipLaunchKernelGGL(k_opt_wsp, dim3((unsigned)cnt, (unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, m->view,
-                                   (const double*)kc, (const cd*)vc, cnt, F, wt);
+                                   kc, vc, cnt, F, wt);
                 TBK_HIP(hipGetLastError());
             }
             {
-                // cnt nd <= 3 kOptChunkBytes / (33^2 16 B) < 65536 (the grid's z limit)
+                // cnt nd <= 3 kKuboChunkBytes / (33^2 16 B) < 65536 (the grid's z limit)
                 ProfScope ps(ctx, "opt_wide");
                 const unsigned t = (unsigned)((n + 15) / 16);
-                hipLaunchKernelGGL(k_opt_vprod, dim3(t, t, (unsigned)(cnt * F.nd)), dim3(256), 0, ctx->stream, (const cd*)vc,
+                hipLaunchKernelGGL(k_opt_vprod, dim3(t, t, (unsigned)(cnt * F.nd)), dim3(256), 0, ctx->stream, vc,
                                    (const cd*)wt, cnt, n, F.nd, vt);
                 TBK_HIP(hipGetLastError());
             }
             ProfScope ps(ctx, "opt_pairs");
-            hipLaunchKernelGGL(k_opt_pairs_wide, dim3(nblk(cnt * npair)), dim3(256), 0, ctx->stream, (const double*)ec, (const cd*)vt,
+            hipLaunchKernelGGL(k_opt_pairs_wide, dim3(nblk(cnt * npair)), dim3(256), 0, ctx->stream, ec, (const cd*)vt,
                                cnt, n, F, mu, kT, rec);
             TBK_HIP(hipGetLastError());
         }
         ProfScope ps(ctx, "opt_omega");
         const dim3 grid(ntile, (unsigned)G);
         const int acc = first > 0 ? 1 : 0;
-        if (F.ns == 1 && F.na == 0) rc = opt_omega_launch<1, 0>(ctx, grid, rec, cnt, npair, G, om_dev, nomega, eta, acc, part);
-        else if (F.ns == 1 && F.na == 1) rc = opt_omega_launch<1, 1>(ctx, grid, rec, cnt, npair, G, om_dev, nomega, eta, acc, part);
-        else if (F.ns == 3) rc = opt_omega_launch<3, 1>(ctx, grid, rec, cnt, npair, G, om_dev, nomega, eta, acc, part);
-        else rc = opt_omega_launch<6, 3>(ctx, grid, rec, cnt, npair, G, om_dev, nomega, eta, acc, part);
-        if (rc) return rc;
-    }
+        if (F.ns == 1 && F.na == 0) return opt_omega_launch<1, 0>(ctx, grid, rec, cnt, npair, G, om_dev, nomega, eta, acc, part);
+        if (F.ns == 1 && F.na == 1) return opt_omega_launch<1, 1>(ctx, grid, rec, cnt, npair, G, om_dev, nomega, eta, acc, part);
+        if (F.ns == 3) return opt_omega_launch<3, 1>(ctx, grid, rec, cnt, npair, G, om_dev, nomega, eta, acc, part);
+        return opt_omega_launch<6, 3>(ctx, grid, rec, cnt, npair, G, om_dev, nomega, eta, acc, part);
+    });
+    if (rc) return rc;
     {
         ProfScope ps(ctx, "opt_rows");
         hipLaunchKernelGGL(k_opt_rows, dim3((unsigned)nrows), dim3(256), 0, ctx->stream, (const double*)part, G, nrows,
