@@ -284,6 +284,20 @@ int tbk_berry_curv_list(tbk_model* model, const double* k, int64_t nk, int dir0,
 int tbk_berry_curv_mesh(tbk_model* model, const int32_t* mesh, int dir0, int dir1, const int32_t* occ,
                         int nocc, int nmu, const double* mu, double* out);
 
+/* ---- spin Berry curvature and spin Hall conductivity by the Kubo formula ----------
+ * For a model with nspin = 2 (state = 2 orbital + spin).  Sigma_s = 1_orb (x) (s.sigma) for the real vector spin[3] (used as
+ * given, not normalised; every result is linear in it), J^{s,a} = (Sigma_s d_a H + d_a H Sigma_s) / 2 the spin current:
+ *   Omega^s_n = -2 Im sum_{m != n} J^{s,a}_nm V^b_mn / (E_n - E_m)^2,   (a, b) = (dir0, dir1),
+ * with the degeneracy rule, the band-set form, the Fermi scan, the shapes and the argument rules of tbk_berry_curv_list and
+ * tbk_berry_curv_mesh.  With spin hbar sigma / 2, sigma^s_ab = (e / 4 pi) I^s / (2 pi) per layer for the mesh mean I^s; an
+ * S_z-conserving model has I^s / (2 pi) = C_up - C_down.  A model with nspin = 1 or a non-finite spin[] is TBK_EINVAL.
+ * tbk_gen_jham: J^{s,dir}(k) for nk points, out[nk][nsta][nsta] c128 (the layout of tbk_gen_dham).                  */
+int tbk_gen_jham(tbk_model* model, const double* k, int64_t nk, int dir, const double spin[3], double* out);
+int tbk_spin_curv_list(tbk_model* model, const double* k, int64_t nk, int dir0, int dir1,
+                       const int32_t* occ, int nocc, const double spin[3], double* out);
+int tbk_spin_curv_mesh(tbk_model* model, const int32_t* mesh, int dir0, int dir1, const int32_t* occ,
+                       int nocc, int nmu, const double* mu, const double spin[3], double* out);
+
 /* ---- interband optical conductivity by the Kubo formula ----------
  * k reduced, H the convention-II matrix of tbk_gen_ham, V^a = d_a H (tbk_gen_dham), E_n, |n> the eigenpairs of the solver,
  * f_n = [E_n <= mu] for kT = 0, else 1 / (1 + exp((E_n - mu) / kT)); the mean over k_uniform_mesh(mesh) (dim_k 1..3, N_k points):

@@ -12,6 +12,9 @@
 //   n != 2    the chunk pipeline and the contraction kernels of tbk_kubo.h with the policy CurvQ: up to 32 states ONE kernel with
 //             several points' U, d H and products in LDS (k_kubo_lds); from 33 states W^d = d_d H U^T from the sparse slots
 //             (k_kubo_wsp) and a lane per (k, band) contraction (k_kubo_contract).
+// Spin form (section 15): Omega^s_n with the first velocity replaced by the spin current J^{s,a} = (Sigma_s d_a H + d_a H Sigma_s) / 2,
+// Sigma_s = 1_orb (x) s.sigma, for spinful models.  The policy SpinQ (CurvQ's sums, kSpin) takes the same kernels at every n -- the n = 2
+// closed form is for two velocities and is not used; the mesh reductions are those of the charge form.
 // Reductions are fixed-shape trees (per-workgroup partials in a grid-stride order that depends on the mesh shape alone, then one
 // workgroup per output): two calls on the same input give the same bits.  No floating-point atomics anywhere.
 #include <math.h>
@@ -40,6 +43,17 @@ __global__ __launch_bounds__(256) void k_curv_dham(const ModelView mv, const int
         o1[a * n + b] = v1;
         o1[b * n + a] = cconj(v1);
     }
+}
+
+// J = (Sigma_s D + D Sigma_s) / 2 of nk dense n x n matrices D (k_curv_dham's), one lane per entry
+__global__ __launch_bounds__(256) void k_curv_jham(const int n, const int64_t total, const SpinVec sv, const cd* __restrict__ dh,
+                                                   cd* __restrict__ out) {
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= total) return;
+    const int64_t nn = (int64_t)n * n, ik = idx / nn;
+    const int r = (int)(idx - ik * nn), i = r / n, j = r - i * n;
+    const cd* dp = dh + ik * nn;
+    out[idx] = spin_apply(sv, i, j, dp[r], dp[(i ^ 1) * n + j], dp[i * n + (j ^ 1)]);
 }
 
 // ---------------------------------------------------------------- n = 2: closed form in registers (curv2_point, tbk_dham.h)
@@ -126,22 +140,49 @@ struct CurvQ {
     static __device__ __forceinline__ void set(const Out& o, const int64_t i, int64_t, const double (&s)[1]) { o.om[i] = s[0]; }
 };
 
+// the spin form: CurvQ's sums of Im J_bm V^b_mb; the kernels that form the first operator read Out::spin (kubo_spin, tbk_kubo.h)
+struct SpinQ : CurvQ {
+    static constexpr bool kSpin = true;
+    static constexpr const char* kLabel[4] = {"spin_curv_lds", "spin_curv_wsp", "spin_curv_contract", "spin_curv_occ_sum"};
+    using Contract = CurvQ;
+    struct Out : CurvQ::Out {
+        SpinVec spin;
+    };
+};
+
 // ---------------------------------------------------------------- host side
-extern "C" int tbk_gen_dham(tbk_model* m, const double* k, int64_t nk, int dir, double* out) {
-    TBK_REQUIRE(m && out && nk >= 0, TBK_EINVAL, "tbk_gen_dham: bad argument");
-    TBK_REQUIRE(m->dim_k >= 1 && dir >= 0 && dir < m->dim_k, TBK_EINVAL, "tbk_gen_dham: dir=%d outside [0, dim_k=%d)", dir,
-                m->dim_k);
-    TBK_REQUIRE(k || nk == 0, TBK_EINVAL, "tbk_gen_dham: null k");
+// the checks of a spin direction: a spinful model and three finite components
+static int spin_check(const char* fn, tbk_model* m, const double* spin, SpinVec& sv) {
+    TBK_REQUIRE(m && spin, TBK_EINVAL, "%s: null argument", fn);
+    TBK_REQUIRE(m->nspin == 2, TBK_EINVAL, "%s: the spin current needs a model with nspin = 2 (the model has %d)", fn, m->nspin);
+    for (int c = 0; c < 3; ++c) {
+        TBK_REQUIRE(std::isfinite(spin[c]), TBK_EINVAL, "%s: spin[%d] is not finite", fn, c);
+        sv.s[c] = spin[c];
+    }
+    return TBK_OK;
+}
+
+// tbk_gen_dham (spin null) and tbk_gen_jham
+static int gen_dham(const char* fn, tbk_model* m, const double* k, int64_t nk, int dir, const double* spin, double* out) {
+    TBK_REQUIRE(m && out && nk >= 0, TBK_EINVAL, "%s: bad argument", fn);
+    TBK_REQUIRE(m->dim_k >= 1 && dir >= 0 && dir < m->dim_k, TBK_EINVAL, "%s: dir=%d outside [0, dim_k=%d)", fn, dir, m->dim_k);
+    TBK_REQUIRE(k || nk == 0, TBK_EINVAL, "%s: null k", fn);
+    SpinVec sv{};
+    if (spin) {
+        int rc = spin_check(fn, m, spin, sv);
+        if (rc) return rc;
+    }
     if (nk == 0) return TBK_OK;
     tbk_ctx* ctx = m->ctx;
     TBK_HIP(hipSetDevice(ctx->device));
     const int n = m->nsta;
     const size_t kb = (size_t)nk * m->dim_k * sizeof(double), hb = (size_t)nk * n * n * sizeof(cd);
     void* base = nullptr;
-    int rc = tbk_ctx_scratch(ctx, 256 + al256(kb) + al256(hb), &base);
+    int rc = tbk_ctx_scratch(ctx, 256 + al256(kb) + (spin ? 2 : 1) * al256(hb), &base);
     if (rc) return rc;
     double* k_dev = (double*)((unsigned char*)base + 256);
     cd* h_dev = (cd*)((unsigned char*)k_dev + al256(kb));
+    cd* j_dev = spin ? (cd*)((unsigned char*)h_dev + al256(hb)) : h_dev;
     TBK_HIP(hipMemcpyAsync(k_dev, k, kb, hipMemcpyHostToDevice, ctx->stream));
     TBK_HIP(hipMemsetAsync(h_dev, 0, hb, ctx->stream));
     if (m->view.nnz > 0) {
@@ -150,17 +191,35 @@ extern "C" int tbk_gen_dham(tbk_model* m, const double* k, int64_t nk, int dir, 
                            (int64_t)n * n, h_dev, (cd*)nullptr);
         TBK_HIP(hipGetLastError());
     }
-    TBK_HIP(hipMemcpyAsync(out, h_dev, hb, hipMemcpyDeviceToHost, ctx->stream));
+    if (spin) {
+        ProfScope ps(ctx, "gen_jham");
+        hipLaunchKernelGGL(k_curv_jham, dim3(nblk(nk * n * n)), dim3(256), 0, ctx->stream, n, nk * n * n, sv, (const cd*)h_dev, j_dev);
+        TBK_HIP(hipGetLastError());
+    }
+    TBK_HIP(hipMemcpyAsync(out, j_dev, hb, hipMemcpyDeviceToHost, ctx->stream));
     TBK_HIP(hipStreamSynchronize(ctx->stream));
     return TBK_OK;
 }
+extern "C" int tbk_gen_dham(tbk_model* m, const double* k, int64_t nk, int dir, double* out) {
+    return gen_dham("tbk_gen_dham", m, k, nk, dir, nullptr, out);
+}
+extern "C" int tbk_gen_jham(tbk_model* m, const double* k, int64_t nk, int dir, const double* spin, double* out) {
+    TBK_REQUIRE(spin, TBK_EINVAL, "tbk_gen_jham: null spin");
+    return gen_dham("tbk_gen_jham", m, k, nk, dir, spin, out);
+}
 
-extern "C" int tbk_berry_curv_list(tbk_model* m, const double* k, int64_t nk, int dir0, int dir1, const int32_t* occ, int nocc,
-                                   double* out) {
+// tbk_berry_curv_list (spin null) and tbk_spin_curv_list
+static int curv_list(const char* fn, tbk_model* m, const double* k, int64_t nk, int dir0, int dir1, const int32_t* occ, int nocc,
+                     const double* spin, double* out) {
     std::vector<int> mask;
-    int rc = kubo_check("tbk_berry_curv_list", "curvature", m, dir0, dir1, occ, nocc, mask);
+    int rc = kubo_check(fn, spin ? "spin curvature" : "curvature", m, dir0, dir1, occ, nocc, mask);
     if (rc) return rc;
-    TBK_REQUIRE(nk >= 0 && out && (k || nk == 0), TBK_EINVAL, "tbk_berry_curv_list: bad k list or output");
+    SpinVec sv{};
+    if (spin) {
+        rc = spin_check(fn, m, spin, sv);
+        if (rc) return rc;
+    }
+    TBK_REQUIRE(nk >= 0 && out && (k || nk == 0), TBK_EINVAL, "%s: bad k list or output", fn);
     const int n = m->nsta, dk = m->dim_k;
     const bool manifold = occ != nullptr;
     const int64_t nout = manifold ? nk : (int64_t)n * nk;
@@ -172,7 +231,8 @@ extern "C" int tbk_berry_curv_list(tbk_model* m, const double* k, int64_t nk, in
     tbk_ctx* ctx = m->ctx;
     TBK_HIP(hipSetDevice(ctx->device));
     const size_t kb = al256((size_t)nk * dk * sizeof(double)), ob = al256((size_t)nout * sizeof(double));
-    KuboChunks cw = n == 2 ? KuboChunks() : kubo_contract_chunks(n, dk, nk, manifold, CurvQ::NSET);
+    const bool general = n != 2 || spin;   // (the n = 2 closed form is for two velocities)
+    KuboChunks cw = general ? kubo_contract_chunks(n, dk, nk, manifold, CurvQ::NSET) : KuboChunks();
     void* base = nullptr;
     rc = tbk_ctx_scratch(ctx, 256 + kb + ob + cw.bytes(), &base);
     if (rc) return rc;
@@ -180,7 +240,7 @@ extern "C" int tbk_berry_curv_list(tbk_model* m, const double* k, int64_t nk, in
     double* k_dev = (double*)p;
     double* o_dev = (double*)(p + kb);
     TBK_HIP(hipMemcpyAsync(k_dev, k, (size_t)nk * dk * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    if (n == 2) {
+    if (!general) {
         ProfScope ps(ctx, "curv2_list");
         const int sign = manifold ? (mask[0] ? 1 : -1) : 0;
         hipLaunchKernelGGL(k_curv2_list, dim3(nblk(nk)), dim3(256), 0, ctx->stream, m->view, nk, (const double*)k_dev, dir0, dir1,
@@ -188,28 +248,44 @@ extern "C" int tbk_berry_curv_list(tbk_model* m, const double* k, int64_t nk, in
         TBK_HIP(hipGetLastError());
     } else {
         cw.base = p + kb + ob;
-        rc = kubo_contract<CurvQ>(m, k_dev, nullptr, nk, dir0, dir1, mask, cw, CurvQ::Out{o_dev, nullptr});
+        if (spin) rc = kubo_contract<SpinQ>(m, k_dev, nullptr, nk, dir0, dir1, mask, cw, SpinQ::Out{{o_dev, nullptr}, sv});
+        else rc = kubo_contract<CurvQ>(m, k_dev, nullptr, nk, dir0, dir1, mask, cw, CurvQ::Out{o_dev, nullptr});
         if (rc) return rc;
     }
     TBK_HIP(hipMemcpyAsync(out, o_dev, (size_t)nout * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     TBK_HIP(hipStreamSynchronize(ctx->stream));
     return TBK_OK;
 }
+extern "C" int tbk_berry_curv_list(tbk_model* m, const double* k, int64_t nk, int dir0, int dir1, const int32_t* occ, int nocc,
+                                   double* out) {
+    return curv_list("tbk_berry_curv_list", m, k, nk, dir0, dir1, occ, nocc, nullptr, out);
+}
+extern "C" int tbk_spin_curv_list(tbk_model* m, const double* k, int64_t nk, int dir0, int dir1, const int32_t* occ, int nocc,
+                                  const double* spin, double* out) {
+    TBK_REQUIRE(spin, TBK_EINVAL, "tbk_spin_curv_list: null spin");
+    return curv_list("tbk_spin_curv_list", m, k, nk, dir0, dir1, occ, nocc, spin, out);
+}
 
-extern "C" int tbk_berry_curv_mesh(tbk_model* m, const int32_t* mesh, int dir0, int dir1, const int32_t* occ, int nocc, int nmu,
-                                   const double* mu, double* out) {
+// tbk_berry_curv_mesh (spin null) and tbk_spin_curv_mesh
+static int curv_mesh(const char* fn, tbk_model* m, const int32_t* mesh, int dir0, int dir1, const int32_t* occ, int nocc, int nmu,
+                     const double* mu, const double* spin, double* out) {
     std::vector<int> mask;
-    int rc = kubo_check("tbk_berry_curv_mesh", "curvature", m, dir0, dir1, occ, nocc, mask);
+    int rc = kubo_check(fn, spin ? "spin curvature" : "curvature", m, dir0, dir1, occ, nocc, mask);
     if (rc) return rc;
-    TBK_REQUIRE(mesh && out, TBK_EINVAL, "tbk_berry_curv_mesh: null argument");
-    TBK_REQUIRE(m->dim_k == 2 || m->dim_k == 3, TBK_EINVAL, "tbk_berry_curv_mesh: dim_k=%d (meshes of 2 or 3 dimensions)", m->dim_k);
-    TBK_REQUIRE(nmu >= 0 && nmu <= 8192 && (nmu == 0 || mu), TBK_EINVAL, "tbk_berry_curv_mesh: nmu=%d (0..8192 levels)", nmu);
-    TBK_REQUIRE(!(nmu > 0 && occ), TBK_EINVAL, "tbk_berry_curv_mesh: a band set and a Fermi scan are exclusive");
+    SpinVec sv{};
+    if (spin) {
+        rc = spin_check(fn, m, spin, sv);
+        if (rc) return rc;
+    }
+    TBK_REQUIRE(mesh && out, TBK_EINVAL, "%s: null argument", fn);
+    TBK_REQUIRE(m->dim_k == 2 || m->dim_k == 3, TBK_EINVAL, "%s: dim_k=%d (meshes of 2 or 3 dimensions)", fn, m->dim_k);
+    TBK_REQUIRE(nmu >= 0 && nmu <= 8192 && (nmu == 0 || mu), TBK_EINVAL, "%s: nmu=%d (0..8192 levels)", fn, nmu);
+    TBK_REQUIRE(!(nmu > 0 && occ), TBK_EINVAL, "%s: a band set and a Fermi scan are exclusive", fn);
     for (int j = 0; j < nmu; ++j)
-        TBK_REQUIRE(std::isfinite(mu[j]), TBK_EINVAL, "tbk_berry_curv_mesh: Fermi level %d is not finite", j);
+        TBK_REQUIRE(std::isfinite(mu[j]), TBK_EINVAL, "%s: Fermi level %d is not finite", fn, j);
     const int n = m->nsta, dk = m->dim_k;
     PlaneArgs P;
-    rc = kubo_planes("tbk_berry_curv_mesh", mesh, dir0, dir1, dk, P);
+    rc = kubo_planes(fn, mesh, dir0, dir1, dk, P);
     if (rc) return rc;
     const int64_t npts = P.npts;
     const int nslice = P.nslice;
@@ -227,12 +303,12 @@ extern "C" int tbk_berry_curv_mesh(tbk_model* m, const int32_t* mesh, int dir0, 
     std::vector<double> mus;
     kubo_levels(mu, nmu, true, ord, mus);
     // partial layout and counts: the grid-stride shapes depend on the mesh shape alone
-    const int nplane_ch = (!fermi && !manifold && n == 2) ? 1 : nch;   // n = 2 per band: band 1 is -band 0, bit for bit
+    const bool general = n != 2 || spin;                                // (the n = 2 closed form is for two velocities)
+    const int nplane_ch = (!fermi && !manifold && !general) ? 1 : nch;   // n = 2 per band: band 1 is -band 0, bit for bit
     const int gx = fermi ? kubo_fermi_gx(P, n, nmu, 1) : kubo_plane_gx(P);
     const int64_t nrows = (int64_t)nslice * nplane_ch;
     const size_t partb = al256((size_t)nrows * gx * sizeof(double)), rowb = al256((size_t)nrows * sizeof(double));
     const size_t mub = al256((size_t)std::max(nmu, 1) * sizeof(double));
-    const bool general = n != 2;
     const size_t omb = general ? al256((size_t)(manifold ? 1 : n) * npts * sizeof(double)) : 0;
     const size_t evb = general && fermi ? al256((size_t)n * npts * sizeof(double)) : 0;
     KuboChunks cw = general ? kubo_contract_chunks(n, dk, npts, manifold, CurvQ::NSET) : KuboChunks();
@@ -249,11 +325,11 @@ extern "C" int tbk_berry_curv_mesh(tbk_model* m, const int32_t* mesh, int dir0, 
     if (fermi) TBK_HIP(hipMemcpyAsync(mu_dev, mus.data(), (size_t)nmu * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     auto reduce = [&](auto src) -> int {
         if (fermi) {
-            ProfScope ps(ctx, n == 2 ? "curv2_fermi" : "curv_fermi");
+            ProfScope ps(ctx, general ? "curv_fermi" : "curv2_fermi");
             int rc = kubo_fermi_launch<1>(ctx, src, P, n, mu_dev, nmu, gx, part);
             if (rc) return rc;
         } else {
-            ProfScope ps(ctx, n == 2 ? "curv2_plane" : "curv_plane");
+            ProfScope ps(ctx, general ? "curv_plane" : "curv2_plane");
             hipLaunchKernelGGL(k_curv_plane<decltype(src)>, dim3(gx, (unsigned)std::min<int64_t>(nrows, 65535)), dim3(256), 0, ctx->stream, src,
                                P, manifold ? 1 : 0, nplane_ch, nrows, part);
             TBK_HIP(hipGetLastError());
@@ -264,7 +340,8 @@ extern "C" int tbk_berry_curv_mesh(tbk_model* m, const int32_t* mesh, int dir0, 
         return TBK_OK;
     };
     if (general) {
-        rc = kubo_contract<CurvQ>(m, nullptr, mesh, npts, dir0, dir1, mask, cw, CurvQ::Out{om_dev, ev_dev});
+        if (spin) rc = kubo_contract<SpinQ>(m, nullptr, mesh, npts, dir0, dir1, mask, cw, SpinQ::Out{{om_dev, ev_dev}, sv});
+        else rc = kubo_contract<CurvQ>(m, nullptr, mesh, npts, dir0, dir1, mask, cw, CurvQ::Out{om_dev, ev_dev});
         if (rc) return rc;
         rc = reduce(ArraySrc{om_dev, ev_dev});
     } else {
@@ -292,4 +369,13 @@ extern "C" int tbk_berry_curv_mesh(tbk_model* m, const int32_t* mesh, int dir0, 
         }
     }
     return TBK_OK;
+}
+extern "C" int tbk_berry_curv_mesh(tbk_model* m, const int32_t* mesh, int dir0, int dir1, const int32_t* occ, int nocc, int nmu,
+                                   const double* mu, double* out) {
+    return curv_mesh("tbk_berry_curv_mesh", m, mesh, dir0, dir1, occ, nocc, nmu, mu, nullptr, out);
+}
+extern "C" int tbk_spin_curv_mesh(tbk_model* m, const int32_t* mesh, int dir0, int dir1, const int32_t* occ, int nocc, int nmu,
+                                  const double* mu, const double* spin, double* out) {
+    TBK_REQUIRE(spin, TBK_EINVAL, "tbk_spin_curv_mesh: null spin");
+    return curv_mesh("tbk_spin_curv_mesh", m, mesh, dir0, dir1, occ, nocc, nmu, mu, spin, out);
 }

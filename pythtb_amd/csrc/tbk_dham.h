@@ -1,5 +1,6 @@
-// tbk_dham.h -- the gradient form of the model's slot sums, the degeneracy rule, the n = 2 closed form and the mesh-plane geometry of
-// the Kubo-formula translation units (tbk_curv.hip, tbk_optics.hip, tbk_orbmag.hip; DESIGN.md sections 11 to 13).  The kernels and the
+// tbk_dham.h -- the gradient form of the model's slot sums, the degeneracy rule, the 2 x 2 spin action of the spin current, the n = 2
+// closed form and the mesh-plane geometry of the Kubo-formula translation units (tbk_curv.hip, tbk_optics.hip, tbk_orbmag.hip;
+// DESIGN.md sections 11 to 13 and 15).  The kernels and the
 // host pipeline they share are in tbk_kubo.h, which includes this file.
 #pragma once
 #include "tbk_solve_dev.h"
@@ -56,6 +57,32 @@ __device__ __forceinline__ void k_phases(const ModelView& mv, const double* __re
 // the degeneracy rule of the interband sums: the pair (E_n, E_m), de = E_n - E_m of either sign, contributes nothing (NaN: nothing)
 __device__ __forceinline__ bool kubo_degenerate(const double de, const double en, const double em) {
     return !(fabs(de) > 1e-9 * fmax(1.0, fmax(fabs(en), fabs(em))));
+}
+
+// ---------------------------------------------------------------- spin current
+// Sigma_s = 1_orb (x) s.sigma acts on the 2 x 2 spin blocks of a spinful model (state = 2 orbital + spin).  The one copy of its
+// action: the LDS pass of k_kubo_lds, the wide build k_kubo_wsp_spin and the parity hook k_curv_jham all call these.
+struct SpinVec {
+    double s[3];
+};
+// (s.sigma)[al][be]
+__device__ __forceinline__ cd spin_elem(const SpinVec& sv, const int al, const int be) {
+    return al == be ? cd{al ? -sv.s[2] : sv.s[2], 0.0} : cd{sv.s[0], al ? sv.s[1] : -sv.s[1]};
+}
+// (Sigma_s u)[b] of a state vector u
+__device__ __forceinline__ cd spin_vec(const SpinVec& sv, const cd* __restrict__ u, const int b) {
+    const int be = b & 1;
+    cd r = cscale(u[b], be ? -sv.s[2] : sv.s[2]);
+    cfma(r, spin_elem(sv, be, be ^ 1), u[b ^ 1]);
+    return r;
+}
+// J_ab = (Sigma_s D + D Sigma_s)_ab / 2 from dab = D_ab, dxb = D_{a^1, b} and dax = D_{a, b^1}
+__device__ __forceinline__ cd spin_apply(const SpinVec& sv, const int a, const int b, const cd dab, const cd dxb, const cd dax) {
+    const int al = a & 1, be = b & 1;
+    cd r = cscale(dab, (al ? -sv.s[2] : sv.s[2]) + (be ? -sv.s[2] : sv.s[2]));
+    cfma(r, spin_elem(sv, al, al ^ 1), dxb);
+    cfma(r, dax, spin_elem(sv, be ^ 1, be));
+    return cscale(r, 0.5);
 }
 
 // ---------------------------------------------------------------- n = 2: closed form in registers

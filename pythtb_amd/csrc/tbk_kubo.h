@@ -9,6 +9,7 @@
 #include <algorithm>
 #include <cmath>
 #include <numeric>
+#include <type_traits>
 #include <vector>
 #include "tbk_dham.h"
 
@@ -116,6 +117,22 @@ static __global__ __launch_bounds__(256) void k_kubo_rows(const double* __restri
 //   share()   stores the lane's NSET doubles of a band set's sums; set() stores a point's sums over b of them at i = first + ik
 //   kLabel    the ProfScope labels of k_kubo_lds, k_kubo_wsp, k_kubo_contract, k_kubo_occ_sum
 // CurvQ (tbk_curv.hip): Omega.  OrbQ (tbk_orbmag.hip): m and Omega, or (LC, IC, Omega_occ).
+// A policy with kSpin = true (SpinQ, tbk_curv.hip; section 15) replaces the first operator d_{d0} H by the spin current
+// J = (Sigma_s d_{d0} H + d_{d0} H Sigma_s) / 2: its Out carries the SpinVec `spin`, and its member type Contract names the policy
+// whose k_kubo_contract / k_kubo_occ_sum serve it (they see matrix elements only).  The choice is made at compile time
+// (kubo_spin<Q>): a policy without the member compiles to what it was.
+template <class Q, class = void>
+struct kubo_spin : std::false_type {};
+template <class Q>
+struct kubo_spin<Q, std::void_t<decltype(Q::kSpin)>> : std::bool_constant<Q::kSpin> {};
+template <class Q, class = void>
+struct kubo_contract_policy {
+    using type = Q;
+};
+template <class Q>
+struct kubo_contract_policy<Q, std::void_t<typename Q::Contract>> {
+    using type = typename Q::Contract;
+};
 //
 // Up to 32 states: ONE kernel, P = min(64, 4096 / (4 n^2)) points per workgroup, everything of a point in LDS (64 KiB):
 // U (its eigenvectors, read once from HBM), D = d_{d0} H and X = d_{d1} H (built from the non-empty slots), T = D U^T, then
@@ -158,6 +175,17 @@ __global__ __launch_bounds__(256) void k_kubo_lds(const ModelView mv, const doub
         X[p * nn + b * n + a] = cconj(v1);
     }
     __syncthreads();
+    if constexpr (kubo_spin<Q>::value) {                           // J = (Sigma_s D + D Sigma_s) / 2 into the still-free T; the two
+        for (int e = threadIdx.x; e < np * nn; e += 256) {         // regions then swap roles: one barrier, no copy back
+            const int p = e / nn, r = e - p * nn, i = r / n, j = r - i * n;
+            const cd* dp = D + p * nn;
+            T[e] = spin_apply(out.spin, i, j, dp[r], dp[(i ^ 1) * n + j], dp[i * n + (j ^ 1)]);
+        }
+        cd* t = D;
+        D = T;
+        T = t;
+        __syncthreads();
+    }
     for (int e = threadIdx.x; e < np * nn; e += 256) {            // T = D U^T
         const int p = e / nn, r = e - p * nn, i = r / n, mm = r - i * n;
         const cd* dr = D + p * nn + i * n;
@@ -226,8 +254,14 @@ __global__ __launch_bounds__(256) void k_kubo_lds(const ModelView mv, const doub
 // 33..2048 states: W^d[ik][i][m] = sum_j d_d H_ij u_m[j] from the non-empty slots only (ModelView.nz; no dense d_d H), wt[ik][2][n][n].
 // Workgroup (point, block of 256 columns); lane m owns column m of both W^d -- every slot adds to two entries of each, and no other
 // lane touches them: no atomics, a fixed order.  The slot values (both directions) are computed once per point and staged in LDS.
-static __global__ __launch_bounds__(256) void k_kubo_wsp(const ModelView mv, const double* __restrict__ k, const cd* __restrict__ evec,
-                                                         const int64_t nk, const int d0, const int d1, cd* __restrict__ wt) {
+//
+// SPIN (section 15): the first direction's matrix is W^J = (Sigma_s (d_{d0} H U^T) + d_{d0} H (Sigma_s U^T)) / 2.  Sigma_s mixes only rows
+// 2o and 2o + 1 of the lane's own column, so a slot (a, b) adds v0 ((Sigma_s u)[b] + Sigma_aa u[b]) / 2 to row a and
+// Sigma_{a^1,a} v0 u[b] / 2 to row a^1 (and likewise for its conjugate half): still one lane per column, one read-modify-write after
+// the other in slot order -- no third buffer, no atomics, the same bits every call.
+template <bool SPIN>
+__device__ __forceinline__ void kubo_wsp_body(const ModelView& mv, const double* __restrict__ k, const cd* __restrict__ evec,
+                                              const int64_t nk, const int d0, const int d1, cd* __restrict__ wt, const SpinVec& sv) {
     __shared__ int sab[256];
     __shared__ cd sv0[256], sv1[256];
     const int n = mv.nsta;
@@ -262,22 +296,47 @@ static __global__ __launch_bounds__(256) void k_kubo_wsp(const ModelView mv, con
             cd* pa0 = w0 + (int64_t)a * n + m;
             cd* pa1 = w1 + (int64_t)a * n + m;
             cd t0 = *pa0, t1 = *pa1;
-            cfma(t0, v0, ub);
+            if constexpr (SPIN) cfma(t0, v0, cscale(cadd(spin_vec(sv, u, b), cmul(spin_elem(sv, a & 1, a & 1), ub)), 0.5));
+            else cfma(t0, v0, ub);
             cfma(t1, v1, ub);
             *pa0 = t0;
             *pa1 = t1;
+            if constexpr (SPIN) {
+                cd* px = w0 + (int64_t)(a ^ 1) * n + m;
+                cd x = *px;
+                cfma(x, cmul(spin_elem(sv, (a & 1) ^ 1, a & 1), v0), cscale(ub, 0.5));
+                *px = x;
+            }
             if (a != b) {
                 const cd ua = u[a];
                 cd* pb0 = w0 + (int64_t)b * n + m;
                 cd* pb1 = w1 + (int64_t)b * n + m;
                 cd s0 = *pb0, s1 = *pb1;
-                cfma(s0, cconj(v0), ua);
+                if constexpr (SPIN) cfma(s0, cconj(v0), cscale(cadd(spin_vec(sv, u, a), cmul(spin_elem(sv, b & 1, b & 1), ua)), 0.5));
+                else cfma(s0, cconj(v0), ua);
                 cfma(s1, cconj(v1), ua);
                 *pb0 = s0;
                 *pb1 = s1;
+                if constexpr (SPIN) {
+                    cd* px = w0 + (int64_t)(b ^ 1) * n + m;
+                    cd x = *px;
+                    cfma(x, cmul(spin_elem(sv, (b & 1) ^ 1, b & 1), cconj(v0)), cscale(ua, 0.5));
+                    *px = x;
+                }
             }
         }
     }
+}
+static __global__ __launch_bounds__(256) void k_kubo_wsp(const ModelView mv, const double* __restrict__ k, const cd* __restrict__ evec,
+                                                         const int64_t nk, const int d0, const int d1, cd* __restrict__ wt) {
+    kubo_wsp_body<false>(mv, k, evec, nk, d0, d1, wt, SpinVec{});
+}
+// (a template so that only a unit that launches it holds a copy)
+template <class Q>
+__global__ __launch_bounds__(256) void k_kubo_wsp_spin(const ModelView mv, const double* __restrict__ k, const cd* __restrict__ evec,
+                                                       const int64_t nk, const int d0, const int d1, cd* __restrict__ wt,
+                                                       const SpinVec sv) {
+    kubo_wsp_body<true>(mv, k, evec, nk, d0, d1, wt, sv);
 }
 
 // 33..2048 states, one lane per (ik, band b) on k_kubo_wsp's W^d: V^d_{b,m} = sum_i conj(u_b[i]) W^d[i][m], fed to Q as in k_kubo_lds.
@@ -468,19 +527,24 @@ static int kubo_contract(tbk_model* m, const double* k_all_dev, const int32_t* m
         }
         {
             ProfScope ps(ctx, Q::kLabel[1]);
-            hipLaunchKernelGGL(k_kubo_wsp, dim3((unsigned)cnt, (unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, m->view, kp, vc, cnt,
-                               d0, d1, wt);
+            const dim3 grid((unsigned)cnt, (unsigned)((n + 255) / 256));
+            if constexpr (kubo_spin<Q>::value)
+                hipLaunchKernelGGL(k_kubo_wsp_spin<Q>, grid, dim3(256), 0, ctx->stream, m->view, kp, vc, cnt, d0, d1, wt, out.spin);
+            else
+                hipLaunchKernelGGL(k_kubo_wsp, grid, dim3(256), 0, ctx->stream, m->view, kp, vc, cnt, d0, d1, wt);
             TBK_HIP(hipGetLastError());
         }
+        using C = typename kubo_contract_policy<Q>::type;   // (Q itself unless Q names another policy's kernels)
+        const typename C::Out cout = out;
         {
             ProfScope ps(ctx, Q::kLabel[2]);
-            hipLaunchKernelGGL(k_kubo_contract<Q>, dim3(nblk(cnt * n)), dim3(256), 0, ctx->stream, vc, ec, (const cd*)wt, cnt, n, occ, first,
-                               nk, out, tmp);
+            hipLaunchKernelGGL(k_kubo_contract<C>, dim3(nblk(cnt * n)), dim3(256), 0, ctx->stream, vc, ec, (const cd*)wt, cnt, n, occ, first,
+                               nk, cout, tmp);
             TBK_HIP(hipGetLastError());
         }
         if (manifold) {
             ProfScope ps(ctx, Q::kLabel[3]);
-            hipLaunchKernelGGL(k_kubo_occ_sum<Q>, dim3(nblk(cnt)), dim3(256), 0, ctx->stream, (const double*)tmp, cnt, n, first, nk, out);
+            hipLaunchKernelGGL(k_kubo_occ_sum<C>, dim3(nblk(cnt)), dim3(256), 0, ctx->stream, (const double*)tmp, cnt, n, first, nk, cout);
             TBK_HIP(hipGetLastError());
         }
         return TBK_OK;

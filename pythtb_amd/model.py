@@ -466,6 +466,20 @@ class tb_model(object):
             raise Exception("\n\nocc lists a band twice.")
         return np.ascontiguousarray(sel, dtype=np.int32), int(dirs[0]), int(dirs[1])
 
+    @staticmethod
+    def _fermi_levels_arg(sel, fermi_levels):
+        """Checked Fermi levels of a curvature scan as a float64 array, or None (sel: the band set, exclusive with them)."""
+        if fermi_levels is None:
+            return None
+        if sel is not None:
+            raise Exception("\n\nGive either occ or fermi_levels, not both.")
+        mu = np.ascontiguousarray(np.array(fermi_levels, dtype=float))
+        if mu.ndim != 1 or mu.size < 1 or mu.size > 8192:
+            raise Exception("\n\nfermi_levels must be a 1-D array of 1..8192 levels.")
+        if not np.all(np.isfinite(mu)):
+            raise Exception("\n\nfermi_levels must be finite.")
+        return mu
+
     def berry_curvature(self, k_list, occ=None, dirs=(0, 1)):
         """Extension: the Berry curvature by the Kubo formula at every k of `k_list` (reduced coordinates, as solve_all).
 
@@ -502,15 +516,7 @@ class tb_model(object):
         mesh, nk = self._mesh_arg(mesh_size)
         if self._dim_k not in (2, 3):
             raise Exception("\n\nberry_curvature_mesh needs a 2-D or 3-D mesh.")
-        mu = None
-        if fermi_levels is not None:
-            if sel is not None:
-                raise Exception("\n\nGive either occ or fermi_levels, not both.")
-            mu = np.ascontiguousarray(np.array(fermi_levels, dtype=float))
-            if mu.ndim != 1 or mu.size < 1 or mu.size > 8192:
-                raise Exception("\n\nfermi_levels must be a 1-D array of 1..8192 levels.")
-            if not np.all(np.isfinite(mu)):
-                raise Exception("\n\nfermi_levels must be finite.")
+        mu = self._fermi_levels_arg(sel, fermi_levels)
         n = self._nsta
         nch = mu.size if mu is not None else (1 if sel is not None else n)
         nslice = 1 if self._dim_k == 2 else int(mesh[3 - d0 - d1])
@@ -518,6 +524,94 @@ class tb_model(object):
         _lib.check(_lib.lib.tbk_berry_curv_mesh(self._device_model(), _lib.iptr(mesh), d0, d1, _lib.iptr(sel),
                                                 0 if sel is None else len(sel), 0 if mu is None else mu.size,
                                                 _lib.dptr(mu), _lib.dptr(out)))
+        if self._dim_k == 2:
+            out = out[:, 0]
+            return float(out[0]) if sel is not None else out
+        return out[0] if sel is not None else out
+
+    # ------------------------------------------------------------------ spin Berry curvature (extensions)
+    def _spin_arg(self, spin, what):
+        """Checked spin direction of the spin-current calls as a float64 3-vector: 0, 1 or 2 (sigma_x, sigma_y, sigma_z) or a
+        finite real 3-vector, used as given."""
+        if self._nspin != 2:
+            raise Exception("\n\nThe %s needs a spinful model (nspin = 2)." % what)
+        if _is_int(spin):
+            if spin not in (0, 1, 2):
+                raise Exception("\n\nspin must be 0, 1 or 2 (sigma_x, sigma_y, sigma_z) or a real 3-vector.")
+            vec = np.zeros(3, dtype=float)
+            vec[int(spin)] = 1.0
+            return vec
+        try:
+            if np.iscomplexobj(spin):
+                raise TypeError
+            vec = np.array(spin, dtype=float)
+        except (TypeError, ValueError):
+            raise Exception("\n\nspin must be 0, 1 or 2 (sigma_x, sigma_y, sigma_z) or a real 3-vector.")
+        if vec.shape != (3,) or not np.all(np.isfinite(vec)):
+            raise Exception("\n\nspin must be 0, 1 or 2 (sigma_x, sigma_y, sigma_z) or a finite real 3-vector.")
+        return np.ascontiguousarray(vec)
+
+    def _gen_jham(self, k_input, dir, spin=2):
+        """Extension: the spin current J = (S dH/dk_dir + dH/dk_dir S) / 2, S = 1_orb (x) s.sigma, for one k in reduced
+        coordinates, in `_gen_ham`'s `(norb, 2, norb, 2)` shape (computed on the device; the twin of `_gen_dham`)."""
+        vec = self._spin_arg(spin, "spin current")
+        if self._dim_k < 1:
+            raise Exception("\n\n_gen_jham needs a model with dim_k >= 1")
+        if not _is_int(dir) or dir < 0 or dir >= self._dim_k:
+            raise Exception("\n\n_gen_jham: dir must be an axis in [0, dim_k)")
+        kp = np.array(k_input, dtype=float)
+        if kp.ndim == 0:
+            kp = kp.reshape(1)
+        if kp.shape != (self._dim_k,):
+            raise Exception("\n\nk-vector of wrong shape!")
+        k = np.ascontiguousarray(kp.reshape(1, -1))
+        n = self._nsta
+        out = np.zeros((1, n, n), dtype=complex)
+        _lib.check(_lib.lib.tbk_gen_jham(self._device_model(), _lib.dptr(k), 1, int(dir), _lib.dptr(vec),
+                                         _lib.dptr(out.view(float))))
+        return out[0].reshape(self._norb, 2, self._norb, 2)
+
+    def spin_berry_curvature(self, k_list, spin=2, occ=None, dirs=(0, 1)):
+        """Extension: the spin Berry curvature of a spinful model by the Kubo formula at every k of `k_list` -- `berry_curvature`
+        with the first velocity replaced by the spin current J^a = (S dH_a + dH_a S) / 2, S = 1_orb (x) s.sigma:
+
+            Omega^s_n(k) = -2 Im sum_{m != n} <n|J^a|m><m|dH_b|n> / (E_n - E_m)^2,  (a, b) = dirs.
+
+        `spin`: 0, 1 or 2 for sigma_x, sigma_y, sigma_z, or a finite real 3-vector s (used as given, not normalised; the result
+        is linear in it).  Shapes, `occ` and the degeneracy rule as in `berry_curvature`: `(nsta, nk)` per band, `(nk,)` for a
+        band set (pairs inside the set cancel, as for the charge curvature)."""
+        vec = self._spin_arg(spin, "spin Berry curvature")
+        sel, d0, d1 = self._curv_args(occ, dirs, "spin Berry curvature")
+        k = self._k_array(k_list)
+        nk = k.shape[0]
+        out = np.zeros(nk if sel is not None else (self._nsta, nk), dtype=float)
+        if nk == 0:
+            return out
+        _lib.check(_lib.lib.tbk_spin_curv_list(self._device_model(), _lib.dptr(k), nk, d0, d1, _lib.iptr(sel),
+                                               0 if sel is None else len(sel), _lib.dptr(vec), _lib.dptr(out)))
+        return out
+
+    def spin_hall_conductivity_mesh(self, mesh_size, spin=2, occ=None, dirs=(0, 1), fermi_levels=None):
+        """Extension: means of `spin_berry_curvature` over `k_uniform_mesh(mesh_size)` (generated on the device), with every
+        rule of `berry_curvature_mesh`: a float for a band set, `(nsta,)` per band, `(nmu,)` for `fermi_levels`
+        (I^s(mu) = mean_k sum_{n: E_n(k) <= mu} Omega^s_n(k), 1..8192 finite levels in any order, returned in input order;
+        either occ or fermi_levels, not both), and a trailing slice axis for 3-D meshes.
+
+        Units: with spin hbar sigma / 2 and the sign convention of `berry_curvature_mesh`, the spin Hall conductivity is
+        sigma^s_ab = (e / 4 pi) I^s / (2 pi) per layer; for a model that conserves S_z, I^s / (2 pi) = C_up - C_down.
+        `spin` as in `spin_berry_curvature`.  Fixed-order reductions: two calls give the same bits."""
+        vec = self._spin_arg(spin, "spin Hall conductivity")
+        sel, d0, d1 = self._curv_args(occ, dirs, "spin Hall conductivity")
+        mesh, nk = self._mesh_arg(mesh_size)
+        if self._dim_k not in (2, 3):
+            raise Exception("\n\nspin_hall_conductivity_mesh needs a 2-D or 3-D mesh.")
+        mu = self._fermi_levels_arg(sel, fermi_levels)
+        nch = mu.size if mu is not None else (1 if sel is not None else self._nsta)
+        nslice = 1 if self._dim_k == 2 else int(mesh[3 - d0 - d1])
+        out = np.zeros((nch, nslice), dtype=float)
+        _lib.check(_lib.lib.tbk_spin_curv_mesh(self._device_model(), _lib.iptr(mesh), d0, d1, _lib.iptr(sel),
+                                               0 if sel is None else len(sel), 0 if mu is None else mu.size,
+                                               _lib.dptr(mu), _lib.dptr(vec), _lib.dptr(out)))
         if self._dim_k == 2:
             out = out[:, 0]
             return float(out[0]) if sel is not None else out
