@@ -331,6 +331,26 @@ int tbk_orb_moment_list(tbk_model* model, const double* k, int64_t nk, int dir0,
 int tbk_orb_mag_mesh(tbk_model* model, const int32_t* mesh, int dir0, int dir1, const int32_t* occ, int nocc, int nmu,
                      const double* mu, double kT, double* out);
 
+/* ---- Fermi-surface transport ----------
+ * k reduced, V^c = d_c H (tbk_gen_dham), E_n, |n> the eigenpairs of the solver, dim_k 1..3.  A group G at a k point is a maximal
+ * run of consecutive sorted levels, each within 1e-9 max(1, |E|, |E'|) of its predecessor (the pair rule of tbk_berry_curv_list).
+ * For band n in G: vbar^c_n = mean over m in G of <m|V^c|m>, w^{cd}_n = sum_{m in G} Re <n|V^c|m><m|V^d|n>; both group sums are
+ * independent of the solver's choice of eigenvectors inside G.  x = (E_n - mu) / kT, f = 1 / (1 + e^x), -f' = -df/dE,
+ * s = -f ln f - (1 - f) ln(1 - f).
+ * Band velocities on a k list k[nk][dim_k]: the raw diagonal elements v^c_n = <n|V^c|n> (the derivative of an isolated band's
+ * eigenvalue; inside a group only the group's trace is defined).  dir = -1: out[dim_k][nsta][nk]; dir in [0, dim_k): out[nsta][nk]. */
+int tbk_band_velocity_list(tbk_model* model, const double* k, int64_t nk, int dir, double* out);
+/* Plane means over k_uniform_mesh(mesh) (dim_k 2 or 3), (dir0, dir1) distinct, nmu (1..8192) finite levels in any order, kT > 0:
+ *   out[2 + dim_k][nmu] = hall, nernst, dipole_0 .. dipole_{dim_k - 1}:  mean_k sum_n f_n Omega_n,  mean_k sum_n s_n Omega_n,
+ *   mean_k sum_n (-f')_n Omega_n vbar^c_n, with Omega_n the per-band curvature of tbk_berry_curv_list(dir0, dir1).
+ * A 3-D mesh gains a trailing axis over the remaining mesh direction: out[..][nmu][N_rest].                             */
+int tbk_anom_transport_mesh(tbk_model* model, const int32_t* mesh, int dir0, int dir1, int nmu, const double* mu, double kT,
+                            double* out);
+/* The Drude weight, the mean over the whole k_uniform_mesh(mesh) (dim_k 1..3): out[nmu][dim_k (dim_k + 1) / 2],
+ * D_cd = mean_k sum_n (-f')_n w^{cd}_n for c <= d row by row: the intraband pairs that tbk_optical_cond_mesh leaves out.
+ * Both mesh calls: fixed partitions, no atomics on floating-point data: bit-reproducible.                               */
+int tbk_drude_mesh(tbk_model* model, const int32_t* mesh, int nmu, const double* mu, double kT, double* out);
+
 /* ---- multi-GPU: one process per GPU, k-points sharded, one gather ------
  * Thin RCCL wrappers (librccl is dlopen'ed on first use).  The 128-byte id is
  * created on rank 0 and distributed by the launcher (any out-of-band channel). */

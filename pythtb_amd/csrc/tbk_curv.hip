@@ -123,23 +123,7 @@ __global__ __launch_bounds__(256) void k_curv_plane(const Src src, const PlaneAr
 }
 
 // ---------------------------------------------------------------- n != 2: what a (point, band) lane of tbk_kubo.h's contraction keeps
-struct CurvQ {
-    static constexpr int NSET = 1;
-    static constexpr const char* kLabel[4] = {"curv_lds", "curv_wsp", "curv_contract", "curv_occ_sum"};
-    struct Out {
-        double* om;   // per band [n][nfull], manifold [nfull]
-        double* ev;   // per band [n][nfull], nullable
-    };
-    double acc = 0.0;
-    __device__ __forceinline__ void pair(const double pr, const double de, double, double, bool) { acc += pr / (de * de); }
-    __device__ __forceinline__ void band(const Out& o, const int64_t i, const double eb) const {
-        o.om[i] = -2.0 * acc;
-        if (o.ev) o.ev[i] = eb;
-    }
-    __device__ __forceinline__ void share(double* s, double) const { s[0] = -2.0 * acc; }
-    static __device__ __forceinline__ void set(const Out& o, const int64_t i, int64_t, const double (&s)[1]) { o.om[i] = s[0]; }
-};
-
+// (CurvQ, the policy of the charge curvature, is in tbk_kubo.h: tbk_transport.hip sums with it too)
 // the spin form: CurvQ's sums of Im J_bm V^b_mb; the kernels that form the first operator read Out::spin (kubo_spin, tbk_kubo.h)
 struct SpinQ : CurvQ {
     static constexpr bool kSpin = true;

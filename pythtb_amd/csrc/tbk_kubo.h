@@ -116,11 +116,28 @@ static __global__ __launch_bounds__(256) void k_kubo_rows(const double* __restri
 //   band()    stores the lane's per-band result at i = b nfull + first + ik
 //   share()   stores the lane's NSET doubles of a band set's sums; set() stores a point's sums over b of them at i = first + ik
 //   kLabel    the ProfScope labels of k_kubo_lds, k_kubo_wsp, k_kubo_contract, k_kubo_occ_sum
-// CurvQ (tbk_curv.hip): Omega.  OrbQ (tbk_orbmag.hip): m and Omega, or (LC, IC, Omega_occ).
+// CurvQ (below; tbk_curv.hip and tbk_transport.hip): Omega.  OrbQ (tbk_orbmag.hip): m and Omega, or (LC, IC, Omega_occ).
 // A policy with kSpin = true (SpinQ, tbk_curv.hip; section 15) replaces the first operator d_{d0} H by the spin current
 // J = (Sigma_s d_{d0} H + d_{d0} H Sigma_s) / 2: its Out carries the SpinVec `spin`, and its member type Contract names the policy
 // whose k_kubo_contract / k_kubo_occ_sum serve it (they see matrix elements only).  The choice is made at compile time
 // (kubo_spin<Q>): a policy without the member compiles to what it was.
+struct CurvQ {
+    static constexpr int NSET = 1;
+    static constexpr const char* kLabel[4] = {"curv_lds", "curv_wsp", "curv_contract", "curv_occ_sum"};
+    struct Out {
+        double* om;   // per band [n][nfull], manifold [nfull]
+        double* ev;   // per band [n][nfull], nullable
+    };
+    double acc = 0.0;
+    __device__ __forceinline__ void pair(const double pr, const double de, double, double, bool) { acc += pr / (de * de); }
+    __device__ __forceinline__ void band(const Out& o, const int64_t i, const double eb) const {
+        o.om[i] = -2.0 * acc;
+        if (o.ev) o.ev[i] = eb;
+    }
+    __device__ __forceinline__ void share(double* s, double) const { s[0] = -2.0 * acc; }
+    static __device__ __forceinline__ void set(const Out& o, const int64_t i, int64_t, const double (&s)[1]) { o.om[i] = s[0]; }
+};
+
 template <class Q, class = void>
 struct kubo_spin : std::false_type {};
 template <class Q>
@@ -505,9 +522,10 @@ static KuboChunks kubo_contract_chunks(int n, int dk, int64_t nk, bool manifold,
     return KuboChunks(n, dk, chunk, wide ? 2 * (size_t)chunk * n * n * sizeof(cd) : 0, (size_t)n * sizeof(int),
                       wide && manifold ? (size_t)nset * chunk * n * sizeof(double) : 0);
 }
-template <class Q>
+// `after(first, cnt, k, eval, evec)` runs in the same chunk body, behind the contraction, while the chunk's eigenpairs are valid.
+template <class Q, class After>
 static int kubo_contract(tbk_model* m, const double* k_all_dev, const int32_t* mesh, int64_t nk, int d0, int d1,
-                         const std::vector<int>& mask, const KuboChunks& w, const typename Q::Out out) {
+                         const std::vector<int>& mask, const KuboChunks& w, const typename Q::Out out, After&& after) {
     tbk_ctx* ctx = m->ctx;
     const int n = m->nsta;
     cd* wt = w.extra<cd>(0);
@@ -519,11 +537,13 @@ static int kubo_contract(tbk_model* m, const double* k_all_dev, const int32_t* m
     return kubo_for_chunks(m, w, k_all_dev, mesh, nk, [&](int64_t first, int64_t cnt, const double* kp, const double* ec, const cd* vc) -> int {
         if (n <= 32) {
             const int P = kubo_lds_points(n);
-            ProfScope ps(ctx, Q::kLabel[0]);
-            hipLaunchKernelGGL(k_kubo_lds<Q>, dim3((unsigned)((cnt + P - 1) / P)), dim3(256), 0, ctx->stream, m->view, kp, vc, ec, cnt, d0,
-                               d1, P, occ, first, nk, out);
-            TBK_HIP(hipGetLastError());
-            return TBK_OK;
+            {
+                ProfScope ps(ctx, Q::kLabel[0]);
+                hipLaunchKernelGGL(k_kubo_lds<Q>, dim3((unsigned)((cnt + P - 1) / P)), dim3(256), 0, ctx->stream, m->view, kp, vc, ec, cnt,
+                                   d0, d1, P, occ, first, nk, out);
+                TBK_HIP(hipGetLastError());
+            }
+            return after(first, cnt, kp, ec, vc);
         }
         {
             ProfScope ps(ctx, Q::kLabel[1]);
@@ -547,6 +567,12 @@ static int kubo_contract(tbk_model* m, const double* k_all_dev, const int32_t* m
             hipLaunchKernelGGL(k_kubo_occ_sum<C>, dim3(nblk(cnt)), dim3(256), 0, ctx->stream, (const double*)tmp, cnt, n, first, nk, cout);
             TBK_HIP(hipGetLastError());
         }
-        return TBK_OK;
+        return after(first, cnt, kp, ec, vc);
     });
+}
+template <class Q>
+static int kubo_contract(tbk_model* m, const double* k_all_dev, const int32_t* mesh, int64_t nk, int d0, int d1,
+                         const std::vector<int>& mask, const KuboChunks& w, const typename Q::Out out) {
+    return kubo_contract<Q>(m, k_all_dev, mesh, nk, d0, d1, mask, w, out,
+                            [](int64_t, int64_t, const double*, const double*, const cd*) -> int { return TBK_OK; });
 }

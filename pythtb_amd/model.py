@@ -635,7 +635,8 @@ class tb_model(object):
         cartesian=True (dirs=None only) returns sigma = A^T S A / ((2 pi)^2 V_c), `(nw, dim_r, dim_r)`, in units of
         e^2/hbar x length^(2 - dim_k), A = the periodic lattice vectors as rows, V_c = sqrt(det(A A^T)); spinless graphene
         gives Re sigma_xx -> 1/8 at small w.  A one-state model, or kT = 0 with the Fermi level below or above every
-        level, gives exact zeros.  Fixed reduction order: two calls give the same bits."""
+        level, gives exact zeros.  Fixed reduction order: two calls give the same bits.  The pairs left out here -- the
+        intraband (Drude) weight of a metal at kT > 0 -- are `drude_weight_mesh`."""
         if self._dim_k not in (1, 2, 3):
             raise Exception("\n\noptical_conductivity_mesh needs a model with dim_k 1, 2 or 3.")
         mesh, nk = self._mesh_arg(mesh_size)
@@ -739,6 +740,114 @@ class tb_model(object):
                                              0 if sel is None else len(sel), 0 if mu is None else mu.size, _lib.dptr(mu), kT,
                                              _lib.dptr(out)))
         return out[:, 0] if self._dim_k == 2 else out
+
+    # ------------------------------------------------------------------ Fermi-surface transport (extensions)
+    @staticmethod
+    def _thermal_args(fermi_levels, kT):
+        """Checked (levels as a float64 array, kT) of the thermal scans: 1..8192 finite levels in any order, kT finite and > 0."""
+        try:
+            kT = float(kT)
+        except (TypeError, ValueError):
+            raise Exception("\n\nkT must be finite and > 0.")
+        if not np.isfinite(kT) or not kT > 0.0:
+            raise Exception("\n\nkT must be finite and > 0.")
+        mu = np.array(fermi_levels, dtype=float)
+        if mu.ndim != 1 or mu.size < 1 or mu.size > 8192:
+            raise Exception("\n\nfermi_levels must be a 1-D array of 1..8192 levels.")
+        if not np.all(np.isfinite(mu)):
+            raise Exception("\n\nfermi_levels must be finite.")
+        return np.ascontiguousarray(mu), kT
+
+    def band_velocity(self, k_list, dirs=None):
+        """Extension: the band velocities v^c_n(k) = <n|dH/dk_c|n> at every k of `k_list` (reduced coordinates, as solve_all;
+        dim_k >= 1), |n> the eigenvectors of `solve_all` and dH/dk_c of `_gen_dham`.
+
+        dirs=None: every axis, float64 `(dim_k, nsta, nk)`; dirs an integer axis: `(nsta, nk)`.
+        For an isolated band this is the derivative of `solve_all`'s eigenvalue with respect to the reduced k_c
+        (Hellmann-Feynman).  It is the raw diagonal element: inside a group of degenerate levels (the pair rule of
+        `berry_curvature` applied to neighbouring levels) the eigenvectors are the solver's choice, and only the sum of the
+        group's velocities is defined -- `anomalous_transport_mesh` and `drude_weight_mesh` use the group forms.
+        Cartesian velocities are v A / (2 pi) with A the periodic lattice vectors as rows."""
+        if self._dim_k < 1:
+            raise Exception("\n\nThe band velocity needs a model with dim_k >= 1.")
+        if dirs is not None and (not _is_int(dirs) or dirs < 0 or dirs >= self._dim_k):
+            raise Exception("\n\ndirs must be None (every axis) or one integer axis in [0, dim_k).")
+        k = self._k_array(k_list)
+        nk = k.shape[0]
+        n, dk = self._nsta, self._dim_k
+        out = np.zeros((dk, n, nk) if dirs is None else (n, nk), dtype=float)
+        if nk == 0:
+            return out
+        _lib.check(_lib.lib.tbk_band_velocity_list(self._device_model(), _lib.dptr(k), nk, -1 if dirs is None else int(dirs),
+                                                   _lib.dptr(out)))
+        return out
+
+    def anomalous_transport_mesh(self, mesh_size, fermi_levels, kT, dirs=(0, 1)):
+        """Extension: the thermal anomalous-Hall and Nernst integrals and the Berry curvature dipole, as means over
+        `k_uniform_mesh(mesh_size)` (2-D or 3-D, generated on the device), for many Fermi levels at once.
+
+        fermi_levels: 1-D, 1..8192 finite values in any order; kT finite and > 0.  With x = (E_n - mu) / kT,
+        f = 1 / (1 + e^x), s = -f ln f - (1 - f) ln(1 - f) and Omega_n of `berry_curvature(dirs=dirs)`, the tuple
+        (hall, nernst, dipole), each in input order of the levels:
+            hall `(nmu,)`           = mean_k sum_n f_n Omega_n
+            nernst `(nmu,)`         = mean_k sum_n s_n Omega_n
+            dipole `(dim_k, nmu)`   = mean_k sum_n (-df/dE)_n Omega_n vbar^c_n,  c = 0 .. dim_k - 1,
+        vbar^c_n the mean of <m|dH/dk_c|m> over the group of levels degenerate with n (`band_velocity` for an isolated band): a
+        group's sum does not depend on the solver's eigenvectors, e.g. at the Kramers points of a time-reversal-symmetric model.
+        3-D mesh: every result gains a trailing axis over the mesh direction that is not in dirs, one plane per slice.
+        Identities: dipole[c] = mean_k sum_n f_n dOmega_n/dk_c (integration by parts), d nernst / d mu = d hall / d kT, and
+        hall -> `berry_curvature_mesh(fermi_levels=...)` as kT -> 0 (nernst and dipole -> 0 in a gap).  A time-reversal-symmetric
+        model has hall = nernst = 0 and, without inversion, a dipole; a C3-symmetric 2-D model has no dipole.
+        Units, in the sign convention of `berry_curvature_mesh`: sigma_xy = -(e^2/h) hall / (2 pi) per layer; the anomalous
+        Nernst (Peltier) coefficient alpha_xy = -(k_B e / h) nernst / (2 pi), i.e. alpha_xy / sigma_xy = (k_B / e) nernst / hall
+        (Xiao et al., PRL 97, 026603); the Cartesian dipole of a 2-D cell with dirs
+        spanning it is D_x = dipole A / (2 pi)^2 (a length), A the periodic lattice vectors as rows.
+        Fixed-order reductions: two calls give the same bits."""
+        _, d0, d1 = self._curv_args(None, dirs, "anomalous transport")
+        mesh, nk = self._mesh_arg(mesh_size)
+        if self._dim_k not in (2, 3):
+            raise Exception("\n\nanomalous_transport_mesh needs a 2-D or 3-D mesh.")
+        mu, kT = self._thermal_args(fermi_levels, kT)
+        dk = self._dim_k
+        nslice = 1 if dk == 2 else int(mesh[3 - d0 - d1])
+        out = np.zeros((2 + dk, mu.size, nslice), dtype=float)
+        _lib.check(_lib.lib.tbk_anom_transport_mesh(self._device_model(), _lib.iptr(mesh), d0, d1, int(mu.size), _lib.dptr(mu), kT,
+                                                    _lib.dptr(out)))
+        if dk == 2:
+            out = out[:, :, 0]
+        return out[0], out[1], out[2:]
+
+    def drude_weight_mesh(self, mesh_size, fermi_levels, kT, cartesian=False):
+        """Extension: the Drude weight tensor, the mean over the whole `k_uniform_mesh(mesh_size)` (1-, 2- or 3-D, generated on
+        the device), for many Fermi levels at once: float64 `(nmu, dim_k, dim_k)` in input order of the levels,
+
+            D_cd(mu) = mean_k sum_n (-df/dE)_n w^{cd}_n,   w^{cd}_n = sum_{m in G(n)} Re <n|dH/dk_c|m><m|dH/dk_d|n>,
+
+        G(n) the group of levels degenerate with n (w = v^c_n v^d_n of `band_velocity` for an isolated band), f the Fermi
+        function at kT > 0 (finite); fermi_levels 1-D, 1..8192 finite values in any order.  The pairs inside a group are
+        exactly the ones `optical_conductivity_mesh` leaves out, so D is its intraband complement: real, symmetric, with a
+        non-negative diagonal, and D_cd = mean_k sum_n f_n d^2 E_n / dk_c dk_d for non-degenerate bands.
+        cartesian=True returns A^T D A / ((2 pi)^2 V_c), `(nmu, dim_r, dim_r)`, with the A and V_c of
+        `optical_conductivity_mesh`: the weight of sigma(w) = i D / (w + i 0) in e^2/hbar x length^(2 - dim_k).
+        Fixed-order reductions: two calls give the same bits."""
+        if self._dim_k not in (1, 2, 3):
+            raise Exception("\n\ndrude_weight_mesh needs a model with dim_k 1, 2 or 3.")
+        if not isinstance(cartesian, (bool, np.bool_)):
+            raise Exception("\n\ncartesian must be True or False.")
+        mesh, nk = self._mesh_arg(mesh_size)
+        mu, kT = self._thermal_args(fermi_levels, kT)
+        dk = self._dim_k
+        tri = np.zeros((mu.size, dk * (dk + 1) // 2), dtype=float)
+        _lib.check(_lib.lib.tbk_drude_mesh(self._device_model(), _lib.iptr(mesh), int(mu.size), _lib.dptr(mu), kT, _lib.dptr(tri)))
+        out = np.zeros((mu.size, dk, dk), dtype=float)
+        iu = np.triu_indices(dk)
+        out[:, iu[0], iu[1]] = tri
+        out[:, iu[1], iu[0]] = tri
+        if not cartesian:
+            return out
+        a = np.array(self._lat, dtype=float)[self._per]               # (dim_k, dim_r)
+        vc = np.sqrt(np.linalg.det(a @ a.T))
+        return np.einsum("ia,wij,jb->wab", a, out, a) / ((2.0 * np.pi) ** 2 * vc)
 
     # ------------------------------------------------------------------ position operator
     def ignore_position_operator_offdiagonal(self):
