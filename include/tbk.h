@@ -351,6 +351,35 @@ int tbk_anom_transport_mesh(tbk_model* model, const int32_t* mesh, int dir0, int
  * Both mesh calls: fixed partitions, no atomics on floating-point data: bit-reproducible.                               */
 int tbk_drude_mesh(tbk_model* model, const int32_t* mesh, int nmu, const double* mu, double kT, double* out);
 
+/* ---- shift and injection photocurrents: the interband second-order response ----------
+ * k reduced, V^a = d_a H (tbk_gen_dham), W^{ab} = d_a d_b H (tbk_gen_ddham), E_n, |n> the eigenpairs of the solver, E_nm = E_n - E_m,
+ * G(n) the group of band n (the rule of the transport block above), f as in tbk_optical_cond_mesh.  For G(n) != G(m):
+ *   r^b_nm   = -i V^b_nm / E_nm   (0 inside a group)
+ *   r^b_nm;a = (i / E_nm) [T^{ba}_nm / E_nm - W^{ba}_nm + sum_{p not in G(n) u G(m)} (V^b_np V^a_pm / E_pm - V^a_np V^b_pm / E_np)]
+ *   T^{ba}_nm = sum_{p in G(n)} (V^a_np V^b_pm + V^b_np V^a_pm) - sum_{p in G(m)} (V^b_np V^a_pm + V^a_np V^b_pm)
+ *   X^{abc}_nm = r^b_mn r^c_nm;a + r^c_mn r^b_nm;a
+ *   Y^{abc}_nm = sum_{m' in G(m)} V^a_mm' r^c_m'n r^b_nm - sum_{n' in G(n)} r^c_mn V^a_nn' r^b_n'm
+ * (groups of one: T^{ba}_nm = V^b_nm D^a_nm + V^a_nm D^b_nm and Y^{abc}_nm = D^a_mn r^b_nm r^c_mn, D^a_nm = V^a_nn - V^a_mm).  The sums
+ * over (n in G1, m in G2) do not depend on the solver's choice of eigenvectors inside a group; nothing beyond that has been validated
+ * for models whose in-group velocity blocks are not multiples of the identity.
+ * tbk_gen_ddham: d_dir0 d_dir1 H(k) = sum_t amp (2 pi i)^2 (R + tau_j - tau_i)_dir0 (R + tau_j - tau_i)_dir1 exp(2 pi i k.(R + tau_j -
+ * tau_i)) for nk points, out[nk][nsta][nsta] c128 (the layout of tbk_gen_dham); dir0 == dir1 allowed.                            */
+int tbk_gen_ddham(tbk_model* model, const double* k, int64_t nk, int dir0, int dir1, double* out);
+/* The k-resolved shift transition strength on a k list k[nk][dim_k] (dim_k 1..3): out[nk] = sum_{n in occ, m not in occ,
+ * G(n) != G(m)} Im X^{abc}_nm for the bands occ[nocc] (distinct, in [0, nsta)); a, b, c axes in [0, dim_k), repeats allowed.     */
+int tbk_shift_list(tbk_model* model, const double* k, int64_t nk, int a, int b, int c, const int32_t* occ, int nocc, double* out);
+/* Means over k_uniform_mesh(mesh) (dim_k 1..3), generated on the device, with D(eps, w) = (eta / pi) [1 / ((eps - w)^2 + eta^2) +
+ * 1 / ((eps + w)^2 + eta^2)]:
+ *   kind 0 (shift):      K_abc(w) = mean_k sum_{E_m > E_n, G(n) != G(m)} (f_n - f_m) Im X^{abc}_nm D(E_m - E_n, w), real, K_abc = K_acb
+ *   kind 1 (injection):  N_abc(w) = the same sum of Y^{abc}_nm, complex, N_acb = conj N_abc
+ * Cartesian shift conductivity: sigma^{xyz} = (pi / 2) sum_abc A_ax A_by A_cz K_abc / ((2 pi)^3 V_c) in e^3/hbar^2 x length^(3 - dim_k),
+ * A and V_c as in tbk_optical_cond_mesh.  nomega (1..65536) finite frequencies in any order, eta > 0, kT >= 0, all finite.
+ * a = b = c = -1: the full tensor, out[nomega][dim_k][dim_k][dim_k] (doubles for kind 0, c128 for kind 1); otherwise the one
+ * component, out[nomega].  One state, or kT = 0 with mu outside the spectrum: exact zeros.  Fixed partitions, no atomics:
+ * bit-reproducible.                                                                                                            */
+int tbk_photocurrent_mesh(tbk_model* model, const int32_t* mesh, int kind /*0 shift, 1 injection*/, int nomega, const double* omega,
+                          double eta, double mu, double kT, int a, int b, int c /* all -1: full tensor */, double* out);
+
 /* ---- multi-GPU: one process per GPU, k-points sharded, one gather ------
  * Thin RCCL wrappers (librccl is dlopen'ed on first use).  The 128-byte id is
  * created on rank 0 and distributed by the launcher (any out-of-band channel). */

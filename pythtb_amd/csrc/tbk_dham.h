@@ -1,7 +1,7 @@
-// tbk_dham.h -- the gradient form of the model's slot sums, the degeneracy rule, the 2 x 2 spin action of the spin current, the n = 2
-// closed form and the mesh-plane geometry of the Kubo-formula translation units (tbk_curv.hip, tbk_optics.hip, tbk_orbmag.hip;
-// DESIGN.md sections 11 to 13 and 15).  The kernels and the
-// host pipeline they share are in tbk_kubo.h, which includes this file.
+// tbk_dham.h -- the gradient form of the model's slot sums and its second derivative, the degeneracy rule and the groups of levels it
+// defines, the 2 x 2 spin action of the spin current, the n = 2 closed form and the mesh-plane geometry of the Kubo-formula translation
+// units (tbk_curv.hip, tbk_optics.hip, tbk_orbmag.hip, tbk_transport.hip, tbk_shift.hip; DESIGN.md sections 11 to 13 and 15 to 17).
+// The kernels and the host pipeline they share are in tbk_kubo.h, which includes this file.
 #pragma once
 #include "tbk_solve_dev.h"
 
@@ -45,6 +45,32 @@ __device__ __forceinline__ void dham_terms(const ModelView& mv, const int a, con
     v1 = cd{-tp * pq1.y, tp * pq1.x};
 }
 
+// The second derivative of the same slot sum: with G_de = sum amp R_d R_e e^{2 pi i k.R} and
+// dt = tau_b - tau_a,  d_d d_e h = (2 pi i)^2 p (G_de + dt_d G_e + dt_e G_d + dt_d dt_e S); real on a diagonal slot, like the first
+// derivative.  The one copy of this formula: the parity hook k_sh_ddham and the W matrices of tbk_shift.hip call it.
+__device__ __forceinline__ cd ddham_terms(const ModelView& mv, const int a, const int b, const int t0, const int t1,
+                                          const double (&kk)[4], const cd (&z)[4], const int d, const int e) {
+    cd s{0.0, 0.0}, gd{0.0, 0.0}, ge{0.0, 0.0}, gde{0.0, 0.0};
+    for (int t = t0; t < t1; ++t) {
+        const int4 R = mv.term_R[t];
+        const cd x = cmul(mv.term_amp[t], phase_of_R(z, R));
+        const double rd = (double)comp4i(R, d), re = (double)comp4i(R, e);
+        s = cadd(s, x);
+        gd = cadd(gd, cscale(x, rd));
+        ge = cadd(ge, cscale(x, re));
+        gde = cadd(gde, cscale(x, rd * re));
+    }
+    const double c = -4.0 * M_PI * M_PI;
+    if (a == b) return cd{c * gde.x, 0.0};
+    const double4 oa = mv.orb[a], ob = mv.orb[b];
+    const cd p = cmulc(expi2pi(kdot(kk, oa)), expi2pi(kdot(kk, ob)));   // conj(e_a) e_b, as dham_terms
+    const double td = comp4(ob, d) - comp4(oa, d), te = comp4(ob, e) - comp4(oa, e);
+    cd q = cadd(gde, cscale(ge, td));
+    q = cadd(q, cscale(gd, te));
+    q = cadd(q, cscale(s, td * te));
+    return cscale(cmul(p, q), c);
+}
+
 __device__ __forceinline__ void k_phases(const ModelView& mv, const double* __restrict__ k, const int64_t ik, double (&kk)[4],
                                          cd (&z)[4]) {
 #pragma unroll
@@ -57,6 +83,28 @@ __device__ __forceinline__ void k_phases(const ModelView& mv, const double* __re
 // the degeneracy rule of the interband sums: the pair (E_n, E_m), de = E_n - E_m of either sign, contributes nothing (NaN: nothing)
 __device__ __forceinline__ bool kubo_degenerate(const double de, const double en, const double em) {
     return !(fabs(de) > 1e-9 * fmax(1.0, fmax(fabs(en), fabs(em))));
+}
+
+// the group [g0, g1) of band b at point ik (eval[n][nk]): a maximal run of consecutive levels, each degenerate with its predecessor
+// (tbk_transport.hip and tbk_shift.hip)
+__device__ __forceinline__ void band_group(const double* __restrict__ eval, const int64_t nk, const int64_t ik, const int n, const int b,
+                                           int& g0, int& g1) {
+    g0 = b;
+    g1 = b + 1;
+    double hi = eval[(int64_t)b * nk + ik];
+    while (g0 > 0) {
+        const double lo = eval[(int64_t)(g0 - 1) * nk + ik];
+        if (!kubo_degenerate(hi - lo, hi, lo)) break;
+        hi = lo;
+        --g0;
+    }
+    double lo = eval[(int64_t)b * nk + ik];
+    while (g1 < n) {
+        const double up = eval[(int64_t)g1 * nk + ik];
+        if (!kubo_degenerate(up - lo, up, lo)) break;
+        lo = up;
+        ++g1;
+    }
 }
 
 // ---------------------------------------------------------------- spin current

@@ -1,0 +1,688 @@
+// tbk_shift.hip -- shift and injection photocurrents: the interband second-order optical response.
+//
+// k reduced, H the convention-II matrix of tbk_gen_ham, V^a = d_a H (tbk_gen_dham), W^{ab} = d_a d_b H (tbk_gen_ddham), E_n and |n> the
+// eigenpairs of the solver, E_nm = E_n - E_m, G(n) the group of band n (band_group, tbk_dham.h).  For G(n) != G(m):
+//   r^b_nm   = -i V^b_nm / E_nm                                                  (0 inside a group)
+//   r^b_nm;a = (i / E_nm) [ T^{ba}_nm / E_nm - W^{ba}_nm + sum_{p not in G(n) u G(m)} (V^b_np V^a_pm / E_pm - V^a_np V^b_pm / E_np) ]
+//   T^{ba}_nm = sum_{p in G(n)} (V^a_np V^b_pm + V^b_np V^a_pm) - sum_{p in G(m)} (V^b_np V^a_pm + V^a_np V^b_pm)
+//   X^{abc}_nm = r^b_mn r^c_nm;a + r^c_mn r^b_nm;a
+//   Y^{abc}_nm = sum_{m' in G(m)} V^a_mm' r^c_m'n r^b_nm - sum_{n' in G(n)} r^c_mn V^a_nn' r^b_n'm
+//   K_abc(w) = mean_k sum_{E_m > E_n, G(n) != G(m)} (f_n - f_m) Im X^{abc}_nm D(E_m - E_n, w)        (shift, real)
+//   N_abc(w) = the same sum of Y^{abc}_nm                                                             (injection, complex)
+//   D(eps, w) = (eta / pi) [1 / ((eps - w)^2 + eta^2) + 1 / ((eps + w)^2 + eta^2)]
+// The sums over (n in G1, m in G2) do not change when the solver's eigenvectors are rotated inside a group.
+//
+// Pipeline (tbk_kubo.h's chunk loop): the device k generator, the eigen-solver with vectors, then per current direction a one PASS:
+// the PAIR stage writes a record (eps, fields...) per (point, pair i < j) -- eps = -1 for a pair that adds nothing, which is decided
+// before the walk over p -- and the FREQUENCY stage k_sh_omega adds each k-group's sums into part[G][row]; k_opt_rows sums the groups.
+//   n <= 32    k_sh_pairs: U, the V^d and W^{da} of the pass and one scratch matrix of several points in LDS
+//   n > 32     k_sh_wsp (d H U^T and d d H U^T from the sparse slots), k_opt_vprod (conj(U) times it), k_sh_pairs_wide
+// A pass of the full tensor holds at most 3 V + 3 W: at 32 states 8 matrices of 16 KiB with U and the scratch, 128 KiB of the CU's 160.
+// Every partition depends on the mesh, n, dim_k, n_omega and the components alone, and nothing uses atomics: two calls give the same bits.
+#include <math.h>
+#include <string.h>
+#include "tbk_pairs.h"
+
+static const size_t kShRecBytes = (size_t)256 << 20;     // pair records per chunk
+static const int kShTile = 512;                          // frequencies per workgroup of k_sh_omega (two per lane)
+static const int64_t kShPartCap = (int64_t)1 << 24;      // doubles of part[G][rows]
+static const int kShGroupsMax = 1024;                    // k-groups G at most
+#define SH_LDS_CD 4096                                   // c128 of LDS per workgroup of k_sh_pairs while more than one point fits
+
+// One pass: the current direction a and the light directions bdir[nb].  Operator j < nv is V^{vdir[j]}; operator nv + j (shift only) is
+// W^{bdir[j] a}.  Field f is the light pair (bdir[f1[f]], bdir[f2[f]]): one double (Im X, shift) or two (Re Y, Im Y; injection).
+// The small index lists are packed two bits per entry (sh_get, sh_set), so that no kernel indexes an argument array with a loop
+// variable: the pass stays in scalar registers.
+struct ShiftPass {
+    int kind;   // 0 shift, 1 injection
+    int a, ia;  // V^a is operator ia
+    int nv, nb, nfld;
+    unsigned vdir, bdir, ib, f1, f2;
+    __host__ __device__ int nops() const { return kind == 0 ? nv + nb : nv; }
+    __host__ __device__ int nf() const { return kind == 0 ? nfld : 2 * nfld; }
+};
+
+__host__ __device__ __forceinline__ int sh_get(const unsigned pk, const int i) { return (int)((pk >> (2 * i)) & 3u); }
+static inline void sh_set(unsigned& pk, const int i, const int v) { pk = (pk & ~(3u << (2 * i))) | ((unsigned)v << (2 * i)); }
+
+// the weight of the pair (i, j), E_j >= E_i: f_i - f_j on a mesh; with a band set, +1 for i in occ and j outside, -1 the other way
+__device__ __forceinline__ double sh_weight(const double en, const double em, const double mu, const double kT,
+                                            const int* __restrict__ occ, const int i, const int j) {
+    if (occ) return occ[i] ? (occ[j] ? 0.0 : 1.0) : (occ[j] ? -1.0 : 0.0);
+    if (kT == 0.0) return (en <= mu && !(em <= mu)) ? 1.0 : 0.0;
+    const double eps = em - en;
+    return -opt_weight(en, em, eps, mu, kT) * eps;
+}
+
+// v[i] of three without a dynamic index: the three values are read first, so that the choice is between registers, not addresses
+__device__ __forceinline__ cd sh_pick(const cd (&v)[3], const int i) {
+    const cd v0 = v[0], v1 = v[1], v2 = v[2];
+    return i == 0 ? v0 : (i == 1 ? v1 : v2);
+}
+
+// One record at r for the pair (i, j), i < j, of a point: M(op, row, col) the operators in the eigenbasis, E(b) the levels.
+// Every lane walks p upwards, so the members of a group sum in the same order.
+template <int KIND, class Mat, class Eig>
+__device__ __forceinline__ void sh_record(double* __restrict__ r, const ShiftPass& S, const int n, const int i, const int j,
+                                          const int gi0, const int gi1, const int gj0, const int gj1, const double wgt, const Mat& M,
+                                          const Eig& E) {
+    const int nf = S.nf();
+    const double en = E(i), em = E(j), enm = en - em;
+    if (wgt == 0.0 || j < gi1 || !(enm < 0.0)) {                   // no weight, one group, or not a number
+        r[0] = -1.0;
+        for (int f = 0; f < nf; ++f) r[1 + f] = 0.0;
+        return;
+    }
+    const double inv = 1.0 / enm;
+    r[0] = -enm;
+    cd rmn[3], q[3];                                               // r^b_ji; r^b_ij;a (shift) or the two group sums' difference
+    if constexpr (KIND == 0) {
+        cd T[3], Ps[3];
+#pragma unroll
+        for (int b = 0; b < 3; ++b) T[b] = Ps[b] = cd{0.0, 0.0};
+        for (int p = 0; p < n; ++p) {
+            const bool in_n = p >= gi0 && p < gi1, in_m = p >= gj0 && p < gj1;
+            const cd va_ip = M(S.ia, i, p), va_pj = M(S.ia, p, j);
+            double ipm = 0.0, inp = 0.0;
+            if (!in_n && !in_m) {
+                const double ep = E(p);
+                ipm = 1.0 / (ep - em);
+                inp = 1.0 / (en - ep);
+            }
+#pragma unroll
+            for (int b = 0; b < 3; ++b) {
+                if (b >= S.nb) continue;
+                const cd vb_ip = M(sh_get(S.ib, b), i, p), vb_pj = M(sh_get(S.ib, b), p, j);
+                const cd t1 = cmul(vb_ip, va_pj), t2 = cmul(va_ip, vb_pj);
+                if (in_n) T[b] = cadd(T[b], cadd(t1, t2));
+                else if (in_m) T[b] = csub(T[b], cadd(t1, t2));
+                else Ps[b] = cadd(Ps[b], csub(cscale(t1, ipm), cscale(t2, inp)));
+            }
+        }
+#pragma unroll
+        for (int b = 0; b < 3; ++b) {
+            if (b >= S.nb) continue;
+            const cd x = cadd(csub(cscale(T[b], inv), M(S.nv + b, i, j)), Ps[b]);
+            q[b] = cd{-x.y * inv, x.x * inv};                      // r^b_ij;a = (i / E_ij) x
+            const cd v = M(sh_get(S.ib, b), j, i);
+            rmn[b] = cd{-v.y * inv, v.x * inv};                    // r^b_ji = -i V^b_ji / E_ji = i V^b_ji / E_ij
+        }
+        for (int f = 0; f < S.nfld; ++f) {
+            const int b = sh_get(S.f1, f), c = sh_get(S.f2, f);
+            const cd x = cadd(cmul(sh_pick(rmn, b), sh_pick(q, c)), cmul(sh_pick(rmn, c), sh_pick(q, b)));
+            r[1 + f] = wgt * x.y;
+        }
+    } else {
+        cd A[3], B[3], rnm[3];
+#pragma unroll
+        for (int b = 0; b < 3; ++b) A[b] = B[b] = cd{0.0, 0.0};
+        for (int p = gi0; p < gi1; ++p) {                          // B_b = sum_{n' in G(i)} V^a_in' r^b_n'j
+            const cd va = M(S.ia, i, p);
+            const double ie = 1.0 / (E(p) - em);
+#pragma unroll
+            for (int b = 0; b < 3; ++b) {
+                if (b >= S.nb) continue;
+                const cd v = M(sh_get(S.ib, b), p, j);
+                B[b] = cadd(B[b], cmul(va, cd{v.y * ie, -v.x * ie}));
+            }
+        }
+        for (int p = gj0; p < gj1; ++p) {                          // A_c = sum_{m' in G(j)} V^a_jm' r^c_m'i
+            const cd va = M(S.ia, j, p);
+            const double ie = 1.0 / (E(p) - en);
+#pragma unroll
+            for (int b = 0; b < 3; ++b) {
+                if (b >= S.nb) continue;
+                const cd v = M(sh_get(S.ib, b), p, i);
+                A[b] = cadd(A[b], cmul(va, cd{v.y * ie, -v.x * ie}));
+            }
+        }
+#pragma unroll
+        for (int b = 0; b < 3; ++b) {
+            if (b >= S.nb) continue;
+            const cd v = M(sh_get(S.ib, b), i, j), u = M(sh_get(S.ib, b), j, i);
+            rnm[b] = cd{v.y * inv, -v.x * inv};                    // r^b_ij = -i V^b_ij / E_ij
+            rmn[b] = cd{-u.y * inv, u.x * inv};
+        }
+        for (int f = 0; f < S.nfld; ++f) {
+            const int b = sh_get(S.f1, f), c = sh_get(S.f2, f);
+            const cd y = csub(cmul(sh_pick(A, c), sh_pick(rnm, b)), cmul(sh_pick(rmn, c), sh_pick(B, b)));
+            r[1 + 2 * f] = wgt * y.x;
+            r[2 + 2 * f] = wgt * y.y;
+        }
+    }
+}
+
+// the slot value of operator op of the pass: d_{vdir[op]} H_ab, or d_{bdir[op - nv]} d_a H_ab
+__device__ __forceinline__ cd sh_slot(const ModelView& mv, const ShiftPass& S, const int op, const int4 z4, const double (&kk)[4],
+                                      const cd (&z)[4]) {
+    const int a = z4.x & 0xffff, b = z4.x >> 16;
+    if (op < S.nv) {
+        cd h, v0, v1;
+        dham_terms(mv, a, b, z4.y, z4.z, kk, z, sh_get(S.vdir, op), sh_get(S.vdir, op), h, v0, v1);
+        return v0;
+    }
+    return ddham_terms(mv, a, b, z4.y, z4.z, kk, z, sh_get(S.bdir, op - S.nv), S.a);
+}
+
+// ---------------------------------------------------------------- pair stage, 1 .. 32 states
+// P points per workgroup; per point U and nops + 1 matrices in LDS, as k_opt_pairs: buffer j takes operator j from the non-empty
+// slots, buffer j + 1 takes T = (operator) U^T, then buffer j := conj(U) T.  One lane per (point, pair) then walks p once.
+static inline int sh_lds_points(int n, int nops) { return std::max(1, std::min(64, SH_LDS_CD / ((nops + 2) * n * n))); }
+template <int KIND>
+__global__ __launch_bounds__(256) void k_sh_pairs(const ModelView mv, const double* __restrict__ k, const cd* __restrict__ evec,
+                                                  const double* __restrict__ eval, const int64_t nk, const ShiftPass S, const int P,
+                                                  const double mu, const double kT, const int* __restrict__ occ,
+                                                  double* __restrict__ rec) {
+    extern __shared__ cd L[];
+    const int n = mv.nsta, nn = n * n, nops = S.nops();
+    const int64_t ik0 = (int64_t)blockIdx.x * P;
+    const int np = (int)std::min<int64_t>(P, nk - ik0);
+    cd* U = L;
+    cd* Bf = L + P * nn;                                           // buffer j at Bf + j P nn, j = 0 .. nops
+    for (int e = threadIdx.x; e < np * nn; e += 256) {
+        const int p = e / nn, r = e - p * nn, b = r / n, i = r - b * n;
+        U[e] = evec[((int64_t)b * nk + ik0 + p) * n + i];
+    }
+    for (int op = 0; op < nops; ++op) {
+        cd* Sm = Bf + op * P * nn;
+        cd* T = Bf + (op + 1) * P * nn;
+        for (int e = threadIdx.x; e < np * nn; e += 256) Sm[e] = cd{0.0, 0.0};
+        __syncthreads();
+        for (int e = threadIdx.x; e < np * mv.nnz; e += 256) {
+            const int p = e / mv.nnz;
+            const int4 z4 = mv.nz[e - p * mv.nnz];
+            const int a = z4.x & 0xffff, b = z4.x >> 16;
+            double kk[4];
+            cd z[4];
+            k_phases(mv, k, ik0 + p, kk, z);
+            const cd v = sh_slot(mv, S, op, z4, kk, z);
+            Sm[p * nn + a * n + b] = v;
+            Sm[p * nn + b * n + a] = cconj(v);
+        }
+        __syncthreads();
+        for (int e = threadIdx.x; e < np * nn; e += 256) {        // T = (operator) U^T
+            const int p = e / nn, r = e - p * nn, i = r / n, mm = r - i * n;
+            const cd* dr = Sm + p * nn + i * n;
+            const cd* um = U + p * nn + mm * n;
+            cd acc{0.0, 0.0};
+            for (int j = 0; j < n; ++j) cfma(acc, dr[j], um[j]);
+            T[e] = acc;
+        }
+        __syncthreads();
+        for (int e = threadIdx.x; e < np * nn; e += 256) {        // buffer := conj(U) T
+            const int p = e / nn, r = e - p * nn, b = r / n, mm = r - b * n;
+            const cd* ub = U + p * nn + b * n;
+            const cd* tc = T + p * nn + mm;
+            cd acc{0.0, 0.0};
+            for (int i = 0; i < n; ++i) cfmac(acc, ub[i], tc[i * n]);
+            Sm[e] = acc;
+        }
+        __syncthreads();
+    }
+    const int npair = n * (n - 1) / 2, R = 1 + S.nf();
+    for (int e = threadIdx.x; e < np * npair; e += 256) {
+        const int p = e / npair, q = e - p * npair;
+        int i, j;
+        opt_pair_of(n, q, i, j);
+        const int64_t ik = ik0 + p;
+        const double* ev = eval + ik;
+        int gi0, gi1, gj0, gj1;
+        band_group(eval, nk, ik, n, i, gi0, gi1);
+        band_group(eval, nk, ik, n, j, gj0, gj1);
+        const double wgt = sh_weight(ev[(int64_t)i * nk], ev[(int64_t)j * nk], mu, kT, occ, i, j);
+        const cd* V = Bf + p * nn;
+        sh_record<KIND>(
+            rec + (ik * npair + q) * R, S, n, i, j, gi0, gi1, gj0, gj1, wgt,
+            [&](const int op, const int row, const int col) __attribute__((always_inline)) { return V[op * P * nn + row * n + col]; },
+            [&](const int b) __attribute__((always_inline)) { return ev[(int64_t)b * nk]; });
+    }
+}
+
+// ---------------------------------------------------------------- pair stage, 33 .. 2048 states
+// (operator) U^T of the pass's operators from the non-empty slots, the form of k_opt_wsp: workgroup (point, block of 256 columns), lane m
+// owns column m of every product; the slot values are computed once per point and staged in LDS.  wt[ik][op][n][n].
+__global__ __launch_bounds__(256) void k_sh_wsp(const ModelView mv, const double* __restrict__ k, const cd* __restrict__ evec,
+                                                const int64_t nk, const ShiftPass S, cd* __restrict__ wt) {
+    __shared__ int sab[256];
+    __shared__ cd sv[6][256];
+    const int n = mv.nsta, nops = S.nops();
+    const int64_t ik = blockIdx.x, nn = (int64_t)n * n;
+    const int m = blockIdx.y * 256 + threadIdx.x;
+    const bool live = m < n;
+    cd* w = wt + ik * nops * nn;
+    if (live)
+        for (int d = 0; d < nops; ++d)
+            for (int i = 0; i < n; ++i) w[d * nn + (int64_t)i * n + m] = cd{0.0, 0.0};
+    double kk[4];
+    cd z[4];
+    k_phases(mv, k, ik, kk, z);
+    const cd* u = evec + ((int64_t)(live ? m : 0) * nk + ik) * n;
+    for (int q0 = 0; q0 < mv.nnz; q0 += 256) {
+        __syncthreads();
+        if (q0 + (int)threadIdx.x < mv.nnz) {
+            const int4 z4 = mv.nz[q0 + threadIdx.x];
+            for (int d = 0; d < nops; ++d) sv[d][threadIdx.x] = sh_slot(mv, S, d, z4, kk, z);
+            sab[threadIdx.x] = z4.x;
+        }
+        __syncthreads();
+        const int cnt = min(256, mv.nnz - q0);
+        if (!live) continue;
+        for (int q = 0; q < cnt; ++q) {
+            const int a = sab[q] & 0xffff, b = sab[q] >> 16;
+            const cd ub = u[b], ua = u[a];
+            for (int d = 0; d < nops; ++d) {
+                const cd v = sv[d][q];
+                cd* pa = w + d * nn + (int64_t)a * n + m;
+                cd t = *pa;
+                cfma(t, v, ub);
+                *pa = t;
+                if (a != b) {
+                    cd* pb = w + d * nn + (int64_t)b * n + m;
+                    cd s = *pb;
+                    cfma(s, cconj(v), ua);
+                    *pb = s;
+                }
+            }
+        }
+    }
+}
+
+// one lane per (point, pair): the records from vt[ik][op][n][n] (k_opt_vprod's).  Neighbouring lanes hold neighbouring columns j, so
+// the walk down column j is coalesced and row i is shared by most of a wavefront.
+template <int KIND>
+__global__ __launch_bounds__(256) void k_sh_pairs_wide(const double* __restrict__ eval, const cd* __restrict__ vt, const int64_t nk,
+                                                       const int n, const ShiftPass S, const double mu, const double kT,
+                                                       const int* __restrict__ occ, double* __restrict__ rec) {
+    const int64_t npair = (int64_t)n * (n - 1) / 2, nn = (int64_t)n * n;
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= nk * npair) return;
+    const int64_t ik = idx / npair, q = idx - ik * npair;
+    int i, j;
+    opt_pair_of(n, q, i, j);
+    const double* ev = eval + ik;
+    int gi0, gi1, gj0, gj1;
+    band_group(eval, nk, ik, n, i, gi0, gi1);
+    band_group(eval, nk, ik, n, j, gj0, gj1);
+    const double wgt = sh_weight(ev[(int64_t)i * nk], ev[(int64_t)j * nk], mu, kT, occ, i, j);
+    const cd* V = vt + ik * S.nops() * nn;
+    sh_record<KIND>(
+        rec + idx * (1 + S.nf()), S, n, i, j, gi0, gi1, gj0, gj1, wgt,
+        [&](const int op, const int row, const int col) __attribute__((always_inline)) { return V[op * nn + (int64_t)row * n + col]; },
+        [&](const int b) __attribute__((always_inline)) { return ev[(int64_t)b * nk]; });
+}
+
+// ---------------------------------------------------------------- frequency stage
+// k_opt_omega's pattern for the one sum that is needed: workgroup (tile of kShTile frequencies, k-group g), lane t takes w[tile + t] and
+// w[tile + 256 + t] and walks the records of the points [g nk / G, (g + 1) nk / G) of the chunk in order; per lane and frequency
+//   y_f = sum field_f [1 / ((eps - w)^2 + eta^2) + 1 / ((eps + w)^2 + eta^2)]
+// for the NF fields f0 .. f0 + NF - 1 of records of R doubles goes to part[g][(row0 + f) nw + w]: written by the first chunk, added to by
+// the later ones (stream order).  A pass with more than 6 fields takes several launches.
+template <int NF>
+__global__ __launch_bounds__(256) void k_sh_omega(const double* __restrict__ rec, const int64_t nk, const int64_t npair, const int R,
+                                                  const int f0, const int G, const double* __restrict__ omega, const int nw,
+                                                  const double eta, const int accumulate, const int64_t nrows, const int row0,
+                                                  double* __restrict__ part) {
+    const int base = blockIdx.x * kShTile;
+    if (base + (int)(threadIdx.x & ~63u) >= nw) return;            // a wavefront without a frequency (uniform)
+    const int g = blockIdx.y;
+    int wi[2];
+    double om[2];
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+        wi[s] = base + s * 256 + threadIdx.x;
+        om[s] = wi[s] < nw ? omega[wi[s]] : 0.0;
+    }
+    double sy[2][NF];
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+#pragma unroll
+        for (int f = 0; f < NF; ++f) sy[s][f] = 0.0;
+    const double eta2 = eta * eta;
+    const int64_t r0 = (int64_t)g * nk / G * npair, r1 = (int64_t)(g + 1) * nk / G * npair;
+    const double* __restrict__ p = rec + r0 * R;
+    for (int64_t r = r0; r < r1; ++r, p += R) {
+        const double eps = p[0];
+        if (eps < 0.0) continue;                                   // a pair that adds nothing (uniform branch)
+        double v[NF];
+#pragma unroll
+        for (int f = 0; f < NF; ++f) v[f] = p[1 + f0 + f];
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            const double xp = eps - om[s], xm = -eps - om[s];
+            const double d = opt_rcp(fma(xp, xp, eta2)) + opt_rcp(fma(xm, xm, eta2));
+#pragma unroll
+            for (int f = 0; f < NF; ++f) sy[s][f] = fma(v[f], d, sy[s][f]);
+        }
+    }
+    double* out = part + (int64_t)g * nrows + (int64_t)row0 * nw;
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+        if (wi[s] >= nw) continue;
+#pragma unroll
+        for (int f = 0; f < NF; ++f) {
+            double* py = out + (int64_t)f * nw + wi[s];
+            *py = accumulate ? *py + sy[s][f] : sy[s][f];
+        }
+    }
+}
+
+// out[first + ik] = the sum of the one-field records of point ik in pair order (the k-list call)
+__global__ __launch_bounds__(256) void k_sh_list_sum(const double* __restrict__ rec, const int64_t nk, const int64_t npair,
+                                                     const int64_t first, double* __restrict__ out) {
+    const int64_t ik = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (ik >= nk) return;
+    const double* p = rec + ik * npair * 2;
+    double acc = 0.0;
+    for (int64_t q = 0; q < npair; ++q) acc += p[2 * q + 1];
+    out[first + ik] = acc;
+}
+
+// dense d_{d0} d_{d1} H of nk points from the non-empty slots (out zeroed by the caller): the parity hook
+__global__ __launch_bounds__(256) void k_sh_ddham(const ModelView mv, const int64_t nk, const double* __restrict__ k, const int d0,
+                                                  const int d1, cd* __restrict__ out) {
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= nk * mv.nnz) return;
+    const int64_t ik = idx / mv.nnz;
+    const int4 e = mv.nz[(int)(idx - ik * mv.nnz)];
+    const int a = e.x & 0xffff, b = e.x >> 16, n = mv.nsta;
+    double kk[4];
+    cd z[4];
+    k_phases(mv, k, ik, kk, z);
+    const cd w = ddham_terms(mv, a, b, e.y, e.z, kk, z, d0, d1);
+    cd* o = out + ik * (int64_t)n * n;
+    o[a * n + b] = w;
+    o[b * n + a] = cconj(w);
+}
+
+// ---------------------------------------------------------------- host side
+// the pass of current direction a with the light directions b[nb] (distinct) and the fields (f1, f2) given as indices into b[]
+static ShiftPass sh_pass(int kind, int a, int nb, const int* b) {
+    ShiftPass S{};
+    S.kind = kind;
+    S.a = a;
+    S.nb = nb;
+    S.ia = -1;
+    for (int j = 0; j < nb; ++j) {
+        sh_set(S.bdir, j, b[j]);
+        sh_set(S.ib, j, S.nv);
+        sh_set(S.vdir, S.nv++, b[j]);
+        if (b[j] == a) S.ia = sh_get(S.ib, j);
+    }
+    if (S.ia < 0) {                                                // (nb = 3 spans every direction: a is among them)
+        S.ia = S.nv;
+        sh_set(S.vdir, S.nv++, a);
+    }
+    return S;
+}
+static ShiftPass sh_pass_full(int kind, int a, int dk) {
+    const int b[3] = {0, 1, 2};
+    ShiftPass S = sh_pass(kind, a, dk, b);
+    for (int x = 0; x < dk; ++x)
+        for (int y = kind == 0 ? x : 0; y < dk; ++y) sh_set(S.f1, S.nfld, x), sh_set(S.f2, S.nfld, y), ++S.nfld;
+    return S;
+}
+static ShiftPass sh_pass_one(int kind, int a, int b, int c) {
+    const int bb[2] = {b, c};
+    ShiftPass S = sh_pass(kind, a, b == c ? 1 : 2, bb);
+    S.nfld = 1;
+    sh_set(S.f1, 0, 0);
+    sh_set(S.f2, 0, b == c ? 0 : 1);
+    return S;
+}
+
+template <int KIND>
+static int sh_lds_attr(size_t lds) {
+    if (lds > 64 * 1024)
+        TBK_HIP(hipFuncSetAttribute((const void*)k_sh_pairs<KIND>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    return TBK_OK;
+}
+
+// the pair stage of one pass over a chunk: records of 1 + S.nf() doubles at rec
+static int sh_pair_stage(tbk_model* m, const ShiftPass& S, int64_t cnt, const double* kc, const double* ec, const cd* vc, double mu,
+                         double kT, const int* occ, cd* wt, cd* vt, double* rec) {
+    tbk_ctx* ctx = m->ctx;
+    const int n = m->nsta, nops = S.nops();
+    const int64_t npair = (int64_t)n * (n - 1) / 2;
+    if (n <= 32) {
+        const int P = sh_lds_points(n, nops);
+        const size_t lds = (size_t)(nops + 2) * P * n * n * sizeof(cd);
+        int rc = S.kind == 0 ? sh_lds_attr<0>(lds) : sh_lds_attr<1>(lds);
+        if (rc) return rc;
+        ProfScope ps(ctx, "shift_pairs");
+        const dim3 grid((unsigned)((cnt + P - 1) / P));
+        if (S.kind == 0)
+            hipLaunchKernelGGL(k_sh_pairs<0>, grid, dim3(256), lds, ctx->stream, m->view, kc, vc, ec, cnt, S, P, mu, kT, occ, rec);
+        else
+            hipLaunchKernelGGL(k_sh_pairs<1>, grid, dim3(256), lds, ctx->stream, m->view, kc, vc, ec, cnt, S, P, mu, kT, occ, rec);
+        TBK_HIP(hipGetLastError());
+        return TBK_OK;
+    }
+    {
+        ProfScope ps(ctx, "shift_wide");
+        hipLaunchKernelGGL(k_sh_wsp, dim3((unsigned)cnt, (unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, m->view, kc, vc, cnt, S,
+                           wt);
+        TBK_HIP(hipGetLastError());
+    }
+    {
+        // cnt nops <= 6 kKuboChunkBytes / (33^2 16 B) < 65536 (the grid's z limit)
+        ProfScope ps(ctx, "shift_wide");
+        const unsigned t = (unsigned)((n + 15) / 16);
+        hipLaunchKernelGGL(k_opt_vprod, dim3(t, t, (unsigned)(cnt * nops)), dim3(256), 0, ctx->stream, vc, (const cd*)wt, cnt, n, nops, vt);
+        TBK_HIP(hipGetLastError());
+    }
+    ProfScope ps(ctx, "shift_pairs");
+    if (S.kind == 0)
+        hipLaunchKernelGGL(k_sh_pairs_wide<0>, dim3(nblk(cnt * npair)), dim3(256), 0, ctx->stream, ec, (const cd*)vt, cnt, n, S, mu, kT, occ,
+                           rec);
+    else
+        hipLaunchKernelGGL(k_sh_pairs_wide<1>, dim3(nblk(cnt * npair)), dim3(256), 0, ctx->stream, ec, (const cd*)vt, cnt, n, S, mu, kT, occ,
+                           rec);
+    TBK_HIP(hipGetLastError());
+    return TBK_OK;
+}
+
+template <int NF>
+static int sh_omega_launch(tbk_ctx* ctx, dim3 grid, const double* rec, int64_t cnt, int64_t npair, int R, int f0, int G, const double* om,
+                           int nw, double eta, int accumulate, int64_t nrows, int row0, double* part) {
+    hipLaunchKernelGGL((k_sh_omega<NF>), grid, dim3(256), 0, ctx->stream, rec, cnt, npair, R, f0, G, om, nw, eta, accumulate, nrows, row0,
+                       part);
+    TBK_HIP(hipGetLastError());
+    return TBK_OK;
+}
+
+extern "C" int tbk_gen_ddham(tbk_model* m, const double* k, int64_t nk, int dir0, int dir1, double* out) {
+    TBK_REQUIRE(m && out && nk >= 0, TBK_EINVAL, "tbk_gen_ddham: bad argument");
+    TBK_REQUIRE(m->dim_k >= 1 && dir0 >= 0 && dir0 < m->dim_k && dir1 >= 0 && dir1 < m->dim_k, TBK_EINVAL,
+                "tbk_gen_ddham: dirs (%d, %d) outside [0, dim_k=%d)", dir0, dir1, m->dim_k);
+    TBK_REQUIRE(k || nk == 0, TBK_EINVAL, "tbk_gen_ddham: null k");
+    if (nk == 0) return TBK_OK;
+    tbk_ctx* ctx = m->ctx;
+    TBK_HIP(hipSetDevice(ctx->device));
+    const int n = m->nsta;
+    const size_t kb = (size_t)nk * m->dim_k * sizeof(double), hb = (size_t)nk * n * n * sizeof(cd);
+    void* base = nullptr;
+    int rc = tbk_ctx_scratch(ctx, 256 + al256(kb) + al256(hb), &base);
+    if (rc) return rc;
+    double* k_dev = (double*)((unsigned char*)base + 256);
+    cd* h_dev = (cd*)((unsigned char*)k_dev + al256(kb));
+    TBK_HIP(hipMemcpyAsync(k_dev, k, kb, hipMemcpyHostToDevice, ctx->stream));
+    TBK_HIP(hipMemsetAsync(h_dev, 0, hb, ctx->stream));
+    if (m->view.nnz > 0) {
+        ProfScope ps(ctx, "gen_ddham");
+        hipLaunchKernelGGL(k_sh_ddham, dim3(nblk(nk * m->view.nnz)), dim3(256), 0, ctx->stream, m->view, nk, (const double*)k_dev, dir0,
+                           dir1, h_dev);
+        TBK_HIP(hipGetLastError());
+    }
+    TBK_HIP(hipMemcpyAsync(out, h_dev, hb, hipMemcpyDeviceToHost, ctx->stream));
+    TBK_HIP(hipStreamSynchronize(ctx->stream));
+    return TBK_OK;
+}
+
+extern "C" int tbk_shift_list(tbk_model* m, const double* k, int64_t nk, int a, int b, int c, const int32_t* occ, int nocc,
+                              double* out) {
+    TBK_REQUIRE(m && out && occ && nk >= 0 && (k || nk == 0), TBK_EINVAL, "tbk_shift_list: null argument");
+    const int dk = m->dim_k, n = m->nsta;
+    TBK_REQUIRE(dk >= 1 && dk <= 3, TBK_EINVAL, "tbk_shift_list: dim_k=%d (1, 2 or 3)", dk);
+    TBK_REQUIRE(a >= 0 && a < dk && b >= 0 && b < dk && c >= 0 && c < dk, TBK_EINVAL,
+                "tbk_shift_list: dirs (%d, %d, %d) must be axes in [0, %d)", a, b, c, dk);
+    TBK_REQUIRE(nocc >= 1 && nocc <= n, TBK_EINVAL, "tbk_shift_list: nocc=%d (1..%d)", nocc, n);
+    std::vector<int> mask((size_t)n, 0);
+    for (int i = 0; i < nocc; ++i) {
+        TBK_REQUIRE(occ[i] >= 0 && occ[i] < n, TBK_EINVAL, "tbk_shift_list: occ[%d]=%d outside [0, %d)", i, occ[i], n);
+        TBK_REQUIRE(!mask[occ[i]], TBK_EINVAL, "tbk_shift_list: band %d appears twice in occ", occ[i]);
+        mask[occ[i]] = 1;
+    }
+    if (nk == 0) return TBK_OK;
+    if (nocc == n) {                       // the complement is empty: nothing to sum
+        std::fill(out, out + nk, 0.0);
+        return TBK_OK;
+    }
+    const ShiftPass S = sh_pass_one(0, a, b, c);
+    const int64_t npair = (int64_t)n * (n - 1) / 2;
+    const size_t vb = (size_t)n * n * sizeof(cd), rb = (size_t)npair * 2 * sizeof(double);
+    const int64_t chunk = std::min<int64_t>(kubo_chunk_len(n, nk), std::max<int64_t>(1, (int64_t)(kShRecBytes / rb)));
+    const size_t wb = n > 32 ? (size_t)chunk * S.nops() * vb : 0;
+    KuboChunks cw(n, dk, chunk, (size_t)chunk * rb, wb, wb);
+    tbk_ctx* ctx = m->ctx;
+    TBK_HIP(hipSetDevice(ctx->device));
+    const size_t kb = al256((size_t)nk * dk * sizeof(double)), ob = al256((size_t)nk * sizeof(double)), mb = al256((size_t)n * sizeof(int));
+    void* base = nullptr;
+    int rc = tbk_ctx_scratch(ctx, 256 + kb + ob + mb + cw.bytes(), &base);
+    if (rc) return rc;
+    unsigned char* p = (unsigned char*)base + 256;
+    double* k_dev = (double*)p;
+    double* o_dev = (double*)(p + kb);
+    int* occ_dev = (int*)(p + kb + ob);
+    cw.base = p + kb + ob + mb;
+    TBK_HIP(hipMemcpyAsync(k_dev, k, (size_t)nk * dk * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    TBK_HIP(hipMemcpyAsync(occ_dev, mask.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    double* rec = cw.extra<double>(0);
+    rc = kubo_for_chunks(m, cw, k_dev, nullptr, nk, [&](int64_t first, int64_t cnt, const double* kc, const double* ec, const cd* vc) -> int {
+        int r2 = sh_pair_stage(m, S, cnt, kc, ec, vc, 0.0, 0.0, occ_dev, cw.extra<cd>(1), cw.extra<cd>(2), rec);
+        if (r2) return r2;
+        ProfScope ps(ctx, "shift_list_sum");
+        hipLaunchKernelGGL(k_sh_list_sum, dim3(nblk(cnt)), dim3(256), 0, ctx->stream, (const double*)rec, cnt, npair, first, o_dev);
+        TBK_HIP(hipGetLastError());
+        return TBK_OK;
+    });
+    if (rc) return rc;
+    TBK_HIP(hipMemcpyAsync(out, o_dev, (size_t)nk * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    TBK_HIP(hipStreamSynchronize(ctx->stream));
+    return TBK_OK;
+}
+
+extern "C" int tbk_photocurrent_mesh(tbk_model* m, const int32_t* mesh, int kind, int nomega, const double* omega, double eta, double mu,
+                                     double kT, int a, int b, int c, double* out) {
+    TBK_REQUIRE(m && mesh && omega && out, TBK_EINVAL, "tbk_photocurrent_mesh: null argument");
+    const int dk = m->dim_k;
+    TBK_REQUIRE(kind == 0 || kind == 1, TBK_EINVAL, "tbk_photocurrent_mesh: kind=%d (0 shift, 1 injection)", kind);
+    TBK_REQUIRE(dk >= 1 && dk <= 3, TBK_EINVAL, "tbk_photocurrent_mesh: dim_k=%d (meshes of 1, 2 or 3 dimensions)", dk);
+    TBK_REQUIRE(nomega >= 1 && nomega <= 65536, TBK_EINVAL, "tbk_photocurrent_mesh: nomega=%d (1..65536 frequencies)", nomega);
+    for (int j = 0; j < nomega; ++j)
+        TBK_REQUIRE(std::isfinite(omega[j]), TBK_EINVAL, "tbk_photocurrent_mesh: frequency %d is not finite", j);
+    TBK_REQUIRE(std::isfinite(eta) && eta > 0.0, TBK_EINVAL, "tbk_photocurrent_mesh: eta must be finite and > 0");
+    TBK_REQUIRE(std::isfinite(kT) && kT >= 0.0, TBK_EINVAL, "tbk_photocurrent_mesh: kT must be finite and >= 0");
+    TBK_REQUIRE(std::isfinite(mu), TBK_EINVAL, "tbk_photocurrent_mesh: the Fermi level must be finite");
+    const bool full = a == -1 && b == -1 && c == -1;
+    TBK_REQUIRE(full || (a >= 0 && a < dk && b >= 0 && b < dk && c >= 0 && c < dk), TBK_EINVAL,
+                "tbk_photocurrent_mesh: dirs (%d, %d, %d) must be axes in [0, %d), or all -1 for the full tensor", a, b, c, dk);
+    int64_t npts = 1;
+    for (int d = 0; d < dk; ++d) {
+        TBK_REQUIRE(mesh[d] >= 1, TBK_EINVAL, "tbk_photocurrent_mesh: mesh[%d]=%d", d, mesh[d]);
+        npts *= mesh[d];
+    }
+    const int n = m->nsta, cplx = kind == 1 ? 2 : 1;
+    const int64_t npair = (int64_t)n * (n - 1) / 2;
+    const int64_t nout = (full ? (int64_t)nomega * dk * dk * dk : (int64_t)nomega) * cplx;   // doubles
+    std::fill(out, out + nout, 0.0);
+    if (npair == 0) return TBK_OK;
+    ShiftPass pass[3];
+    int npass = 0, row0[4] = {0, 0, 0, 0}, rmax = 0;
+    if (full)
+        for (int d = 0; d < dk; ++d) pass[npass++] = sh_pass_full(kind, d, dk);
+    else
+        pass[npass++] = sh_pass_one(kind, a, b, c);
+    for (int s = 0; s < npass; ++s) {
+        row0[s + 1] = row0[s] + pass[s].nf();
+        rmax = std::max(rmax, 1 + pass[s].nf());
+    }
+    const int nft = row0[npass], nopmax = pass[0].nops();          // (every pass of a call has as many operators)
+    // chunk, k-groups and tiles: functions of (mesh, n, dim_k, nomega, components) only
+    const size_t vb = (size_t)n * n * sizeof(cd), rb = (size_t)npair * rmax * sizeof(double);
+    const int64_t chunk = std::min<int64_t>(kubo_chunk_len(n, npts), std::max<int64_t>(1, (int64_t)(kShRecBytes / rb)));
+    const int64_t nrows = (int64_t)nft * nomega;
+    const int G = (int)std::max<int64_t>(1, std::min<int64_t>({kShPartCap / nrows, (int64_t)kShGroupsMax, chunk}));
+    const unsigned ntile = (unsigned)((nomega + kShTile - 1) / kShTile);
+    const bool wide = n > 32;
+    const size_t omb = al256((size_t)nomega * sizeof(double)), partb = al256((size_t)G * nrows * sizeof(double)),
+                 rowb = al256((size_t)nrows * sizeof(double)), wb = wide ? (size_t)chunk * nopmax * vb : 0;
+    KuboChunks cw(n, dk, chunk, (size_t)chunk * rb, wb, wb);       // the records, then the two dense stages of the wide form
+    tbk_ctx* ctx = m->ctx;
+    TBK_HIP(hipSetDevice(ctx->device));
+    void* base = nullptr;
+    int rc = tbk_ctx_scratch(ctx, 256 + omb + partb + rowb + cw.bytes(), &base);
+    if (rc) return rc;
+    unsigned char* p = (unsigned char*)base + 256;
+    double* om_dev = (double*)p;
+    p += omb;
+    double* part = (double*)p;
+    p += partb;
+    double* rows = (double*)p;
+    cw.base = p + rowb;
+    double* rec = cw.extra<double>(0);
+    TBK_HIP(hipMemcpyAsync(om_dev, omega, (size_t)nomega * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    rc = kubo_for_chunks(m, cw, nullptr, mesh, npts, [&](int64_t first, int64_t cnt, const double* kc, const double* ec, const cd* vc) -> int {
+        const dim3 grid(ntile, (unsigned)G);
+        const int acc = first > 0 ? 1 : 0;
+        for (int s = 0; s < npass; ++s) {
+            const ShiftPass& S = pass[s];
+            int r2 = sh_pair_stage(m, S, cnt, kc, ec, vc, mu, kT, nullptr, cw.extra<cd>(1), cw.extra<cd>(2), rec);
+            if (r2) return r2;
+            ProfScope ps(ctx, "shift_omega");
+            const int nf = S.nf(), R = 1 + nf;
+            for (int f0 = 0; f0 < nf;) {
+                const int left = nf - f0, w = left >= 6 ? 6 : (left >= 3 ? 3 : (left >= 2 ? 2 : 1));
+                auto go = w == 6 ? sh_omega_launch<6> : (w == 3 ? sh_omega_launch<3> : (w == 2 ? sh_omega_launch<2> : sh_omega_launch<1>));
+                r2 = go(ctx, grid, rec, cnt, npair, R, f0, G, om_dev, nomega, eta, acc, nrows, row0[s] + f0, part);
+                if (r2) return r2;
+                f0 += w;
+            }
+        }
+        return TBK_OK;
+    });
+    if (rc) return rc;
+    {
+        ProfScope ps(ctx, "shift_rows");
+        hipLaunchKernelGGL(k_opt_rows, dim3((unsigned)nrows), dim3(256), 0, ctx->stream, (const double*)part, G, nrows,
+                           1.0 / (double)npts, rows);
+        TBK_HIP(hipGetLastError());
+    }
+    std::vector<double> sums((size_t)nrows);
+    TBK_HIP(hipMemcpyAsync(sums.data(), rows, (size_t)nrows * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    TBK_HIP(hipStreamSynchronize(ctx->stream));
+    const double pref = eta / M_PI;
+    for (int w = 0; w < nomega; ++w)
+        for (int s = 0; s < npass; ++s) {
+            const ShiftPass& S = pass[s];
+            for (int f = 0; f < S.nfld; ++f) {
+                const int x = sh_get(S.bdir, sh_get(S.f1, f)), y = sh_get(S.bdir, sh_get(S.f2, f));
+                if (kind == 0) {
+                    const double v = pref * sums[(size_t)(row0[s] + f) * nomega + w];
+                    if (!full) {
+                        out[w] = v;
+                        continue;
+                    }
+                    double* o = out + (size_t)w * dk * dk * dk + (size_t)S.a * dk * dk;
+                    o[x * dk + y] = v;
+                    o[y * dk + x] = v;
+                } else {
+                    const double re = pref * sums[(size_t)(row0[s] + 2 * f) * nomega + w];
+                    const double im = pref * sums[(size_t)(row0[s] + 2 * f + 1) * nomega + w];
+                    double* o = full ? out + 2 * ((size_t)w * dk * dk * dk + (size_t)S.a * dk * dk + x * dk + y) : out + 2 * (size_t)w;
+                    o[0] = re;
+                    o[1] = im;
+                }
+            }
+        }
+    return TBK_OK;
+}

@@ -61,27 +61,6 @@ __device__ __forceinline__ void slot_add(cd (&e)[3], const int dk, const int a, 
     }
 }
 
-// the group [g0, g1) of band b at point ik (eval[n][nk])
-__device__ __forceinline__ void band_group(const double* __restrict__ eval, const int64_t nk, const int64_t ik, const int n, const int b,
-                                           int& g0, int& g1) {
-    g0 = b;
-    g1 = b + 1;
-    double hi = eval[(int64_t)b * nk + ik];
-    while (g0 > 0) {
-        const double lo = eval[(int64_t)(g0 - 1) * nk + ik];
-        if (!kubo_degenerate(hi - lo, hi, lo)) break;
-        hi = lo;
-        --g0;
-    }
-    double lo = eval[(int64_t)b * nk + ik];
-    while (g1 < n) {
-        const double up = eval[(int64_t)g1 * nk + ik];
-        if (!kubo_degenerate(up - lo, up, lo)) break;
-        lo = up;
-        ++g1;
-    }
-}
-
 // w6 += Re x_c conj(x_d) for c <= d, in the row-by-row order of three directions (00 01 02 11 12 22; a direction the model
 // does not have contributes zeros); w_pick: entry q of the dk-direction order (dk = 2: 00 01 11)
 __device__ __forceinline__ void w_add(double (&w)[6], const cd (&x)[3]) {

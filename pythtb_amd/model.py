@@ -675,6 +675,153 @@ class tb_model(object):
         vc = np.sqrt(np.linalg.det(a @ a.T))
         return np.einsum("ia,wij,jb->wab", a, out, a) / ((2.0 * np.pi) ** 2 * vc)
 
+    # ------------------------------------------------------------------ shift and injection photocurrents (extensions)
+    def _gen_ddham(self, k_input, dir0, dir1):
+        """Extension: d^2 H / dk_dir0 dk_dir1 for one k in reduced coordinates, with the shapes of `_gen_ham` (`(norb, 2, norb, 2)`
+        for spinful models): sum t (2 pi i)^2 (R + tau_j - tau_i)_dir0 (R + tau_j - tau_i)_dir1 e^{2 pi i k.(R + tau_j - tau_i)}.
+        The twin of `_gen_dham`; dir0 == dir1 is allowed."""
+        if self._dim_k < 1:
+            raise Exception("\n\n_gen_ddham needs a model with dim_k >= 1")
+        for d in (dir0, dir1):
+            if not _is_int(d) or d < 0 or d >= self._dim_k:
+                raise Exception("\n\n_gen_ddham: dir0 and dir1 must be axes in [0, dim_k)")
+        kp = np.array(k_input, dtype=float)
+        if kp.ndim == 0:
+            kp = kp.reshape(1)
+        if kp.shape != (self._dim_k,):
+            raise Exception("\n\nk-vector of wrong shape!")
+        k = np.ascontiguousarray(kp.reshape(1, -1))
+        n = self._nsta
+        out = np.zeros((1, n, n), dtype=complex)
+        _lib.check(_lib.lib.tbk_gen_ddham(self._device_model(), _lib.dptr(k), 1, int(dir0), int(dir1),
+                                          _lib.dptr(out.view(float))))
+        if self._nspin == 1:
+            return out[0]
+        return out[0].reshape(self._norb, 2, self._norb, 2)
+
+    def _dirs3_arg(self, dirs, what):
+        """Checked (a, b, c) of the photocurrent calls: three integer axes in [0, dim_k), repeats allowed."""
+        dirs = list(dirs)
+        if len(dirs) != 3 or not all(_is_int(d) for d in dirs):
+            raise Exception("\n\ndirs must be three integer axes.")
+        if min(dirs) < 0 or max(dirs) >= self._dim_k:
+            raise Exception("\n\nDirection for the %s out of bounds." % what)
+        return int(dirs[0]), int(dirs[1]), int(dirs[2])
+
+    def shift_current(self, k_list, occ, dirs):
+        """Extension: the k-resolved shift-current transition strength at every k of `k_list` (reduced coordinates, as
+        solve_all), float64 `(nk,)`:
+
+            sum_{n in occ, m not in occ, G(n) != G(m)} Im X^{abc}_nm,   X^{abc}_nm = r^b_mn r^c_nm;a + r^c_mn r^b_nm;a,
+
+        (a, b, c) = dirs (axes may repeat), `occ` a NumPy index of bands as in `berry_curvature`.  r^b_nm = -i V^b_nm / E_nm
+        is the interband connection and r^b_nm;a its generalized derivative by the sum rule of `shift_current_mesh`, with
+        the same groups G.  Needs dim_k >= 1."""
+        if self._dim_k < 1:
+            raise Exception("\n\nThe shift current needs a model with dim_k >= 1.")
+        a, b, c = self._dirs3_arg(dirs, "shift current")
+        sel = np.atleast_1d(np.arange(self._nsta)[occ]).ravel()
+        if sel.size == 0:
+            raise Exception("\n\nocc selects no band.")
+        if np.unique(sel).size != sel.size:
+            raise Exception("\n\nocc lists a band twice.")
+        sel = np.ascontiguousarray(sel, dtype=np.int32)
+        k = self._k_array(k_list)
+        nk = k.shape[0]
+        out = np.zeros(nk, dtype=float)
+        if nk == 0 or self._nsta == 1:
+            return out
+        _lib.check(_lib.lib.tbk_shift_list(self._device_model(), _lib.dptr(k), nk, a, b, c, _lib.iptr(sel), len(sel),
+                                           _lib.dptr(out)))
+        return out
+
+    def _photocurrent_mesh(self, kind, what, mesh_size, omega, eta, fermi_level, kT, dirs, cartesian):
+        if self._dim_k not in (1, 2, 3):
+            raise Exception("\n\n%s needs a model with dim_k 1, 2 or 3." % what)
+        mesh, nk = self._mesh_arg(mesh_size)
+        w = np.array(omega, dtype=float)
+        if w.ndim != 1 or w.size < 1 or w.size > 65536:
+            raise Exception("\n\nomega must be a 1-D array of 1..65536 frequencies.")
+        if not np.all(np.isfinite(w)):
+            raise Exception("\n\nomega must be finite.")
+        w = np.ascontiguousarray(w)
+        if not np.isfinite(eta) or not eta > 0.0:
+            raise Exception("\n\neta must be finite and > 0.")
+        if not np.isfinite(kT) or not kT >= 0.0:
+            raise Exception("\n\nkT must be finite and >= 0.")
+        if not np.isfinite(fermi_level):
+            raise Exception("\n\nfermi_level must be finite.")
+        if dirs is None:
+            a = b = c = -1
+        else:
+            a, b, c = self._dirs3_arg(dirs, "photocurrent")
+            if cartesian:
+                raise Exception("\n\ncartesian=True returns the whole tensor: give dirs=None.")
+        dk = self._dim_k
+        out = np.zeros((w.size, dk, dk, dk) if a < 0 else (w.size,), dtype=complex if kind else float)
+        if self._nsta > 1:
+            _lib.check(_lib.lib.tbk_photocurrent_mesh(self._device_model(), _lib.iptr(mesh), int(kind), int(w.size),
+                                                      _lib.dptr(w), float(eta), float(fermi_level), float(kT), a, b, c,
+                                                      _lib.dptr(out.view(float))))
+        if not cartesian:
+            return out
+        lat = np.array(self._lat, dtype=float)[self._per]             # (dim_k, dim_r)
+        vc = np.sqrt(np.linalg.det(lat @ lat.T))
+        pref = (0.5 * np.pi if kind == 0 else 1.0) / ((2.0 * np.pi) ** 3 * vc)
+        return pref * np.einsum("ax,by,cz,wabc->wxyz", lat, lat, lat, out)
+
+    def shift_current_mesh(self, mesh_size, omega, eta, fermi_level=0.0, kT=0.0, dirs=None, cartesian=False):
+        """Extension: the shift-current response -- the interband second-order (bulk photovoltaic) response to linearly
+        polarised light -- averaged over the whole `k_uniform_mesh(mesh_size)` (1-, 2- or 3-D, generated on the device):
+
+            K_abc(w) = mean_k sum_{E_m > E_n, G(n) != G(m)} (f_n - f_m) Im X^{abc}_nm D(E_m - E_n, w)
+            X^{abc}_nm = r^b_mn r^c_nm;a + r^c_mn r^b_nm;a
+            D(eps, w) = (eta / pi) [1 / ((eps - w)^2 + eta^2) + 1 / ((eps + w)^2 + eta^2)]
+
+        k reduced, H the matrix of `_gen_ham`, V^a = dH/dk_a (`_gen_dham`), W^{ab} = d^2H/dk_a dk_b (`_gen_ddham`), E_n and
+        |n> the eigenpairs of `solve_all`, E_nm = E_n - E_m, f as in `optical_conductivity_mesh`.  G(n) is the group of band
+        n: a maximal run of consecutive levels, each within 1e-9 max(1, |E|, |E'|) of its predecessor (the rule of
+        `anomalous_transport_mesh`).  r^b_nm = -i V^b_nm / E_nm for G(n) != G(m) and 0 inside a group, and the generalized
+        derivative follows from the sum rule
+
+            r^b_nm;a = (i / E_nm) [T^{ba}_nm / E_nm - W^{ba}_nm + sum_{p not in G(n) u G(m)} (V^b_np V^a_pm / E_pm - V^a_np V^b_pm / E_np)]
+            T^{ba}_nm = sum_{p in G(n)} (V^a_np V^b_pm + V^b_np V^a_pm) - sum_{p in G(m)} (V^b_np V^a_pm + V^a_np V^b_pm)
+
+        (groups of one: T^{ba}_nm = V^b_nm D^a_nm + V^a_nm D^b_nm, D^a_nm = V^a_nn - V^a_mm, the sum rule of Sipe and
+        Shkrebtii, Phys. Rev. B 61, 5337 (2000)).  The sums over (n in G1, m in G2) do not depend on the solver's choice of
+        eigenvectors inside a group -- Kramers points, spin-doubled models.  For a model whose in-group velocity blocks are
+        not multiples of the identity at every k (PT-symmetric antiferromagnets with spin-orbit coupling), nothing beyond
+        that independence has been validated.
+
+        omega, eta, fermi_level, kT: the rules of `optical_conductivity_mesh`.  dirs=None -> real `(nw, dim_k, dim_k, dim_k)`;
+        dirs=(a, b, c) (axes may repeat) -> `(nw,)`.  K is symmetric in b <-> c and even in w, and vanishes with inversion
+        symmetry.  cartesian=True (dirs=None only) returns
+        sigma^{xyz} = (pi / 2) sum_abc A_ax A_by A_cz K_abc / ((2 pi)^3 V_c), `(nw, dim_r, dim_r, dim_r)`, in units of
+        e^3/hbar^2 x length^(3 - dim_k), A and V_c as in `optical_conductivity_mesh`; for b = c this is the standard
+        sigma^{abb} = (pi e^3 / hbar^2) int [dk] sum f_nm Im[r^b_mn r^b_nm;a] delta(w_mn - w).  No spin-degeneracy factor.  A
+        one-state model, or kT = 0 with the Fermi level below or above every level, gives exact zeros.  Fixed reduction
+        order: two calls give the same bits."""
+        return self._photocurrent_mesh(0, "shift_current_mesh", mesh_size, omega, eta, fermi_level, kT, dirs, cartesian)
+
+    def injection_current_mesh(self, mesh_size, omega, eta, fermi_level=0.0, kT=0.0, dirs=None, cartesian=False):
+        """Extension: the injection-current response, with the signature, the conventions and the groups G of
+        `shift_current_mesh`:
+
+            N_abc(w) = mean_k sum_{E_m > E_n, G(n) != G(m)} (f_n - f_m) Y^{abc}_nm D(E_m - E_n, w)
+            Y^{abc}_nm = sum_{m' in G(m)} V^a_mm' r^c_m'n r^b_nm - sum_{n' in G(n)} r^c_mn V^a_nn' r^b_n'm
+
+        (groups of one: Y^{abc}_nm = (V^a_mm - V^a_nn) r^b_nm r^c_mn).  Complex, `(nw, dim_k, dim_k, dim_k)` or `(nw,)`;
+        N_acb = conj N_abc.  Re N is the linear (magnetic) injection, which vanishes with time reversal; Im N is the
+        circular injection, which needs broken inversion.  Physical prefactor: the injection rate of the current is
+        d j^a / dt = eta^{abc}(w) E_b(w) E_c(-w) with eta^{abc} = (pi e^3 / 2 hbar^2) int [dk] sum_{nm} f_nm D^a_mn r^c_mn r^b_nm
+        delta(w_mn - w), D^a_mn = V^a_mm - V^a_nn: the product form of Sipe and Shkrebtii, Phys. Rev. B 61, 5337 (2000),
+        eq. (57), whose commutator [r^c_mn, r^b_nm] keeps the part antisymmetric in b <-> c (2i Im N, the circular
+        injection); the symmetric part is the magnetic injection.  So eta^{abc} = (pi e^3 / 2 hbar^2) N_abc after the
+        reduced-to-Cartesian transform.  cartesian=True (dirs=None only)
+        applies the rank-3 transform of `shift_current_mesh` without the pi / 2:
+        sum_abc A_ax A_by A_cz N_abc / ((2 pi)^3 V_c).  The same documented limit for in-group velocity blocks applies."""
+        return self._photocurrent_mesh(1, "injection_current_mesh", mesh_size, omega, eta, fermi_level, kT, dirs, cartesian)
+
     # ------------------------------------------------------------------ orbital magnetization (extensions)
     def orbital_moment(self, k_list, occ=None, dirs=(0, 1)):
         """Extension: the orbital moment by the Kubo formula at every k of `k_list` (reduced coordinates, as solve_all).
