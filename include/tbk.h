@@ -380,6 +380,31 @@ int tbk_shift_list(tbk_model* model, const double* k, int64_t nk, int a, int b, 
 int tbk_photocurrent_mesh(tbk_model* model, const int32_t* mesh, int kind /*0 shift, 1 injection*/, int nomega, const double* omega,
                           double eta, double mu, double kT, int a, int b, int c /* all -1: full tensor */, double* out);
 
+/* ---- surface Green's functions by iterative decimation ----------
+ * No reference counterpart (the reference's route to an edge spectrum is cut_piece + solve_all on a ribbon).  `cut` is the uploaded
+ * cut_piece(2 L, fin_dir) of the model, L = max(1, max |R_fin_dir|): 2 nlayer states, nlayer = L ncell the principal layer, ncell the
+ * states of one unit cell; its dim_k (0..3) is the dimension of the surface zone and k[nk][dim_k] its reduced coordinates (dim_k = 0:
+ * k ignored, nk = 1).  H00(k), H01(k): the top-left and top-right nlayer x nlayer blocks of that model's H(k) (tbk_gen_ham).
+ * tbk_surface_blocks: h00[nk][nlayer][nlayer], h01[nk][nlayer][nlayer] c128.                                                    */
+int tbk_surface_blocks(tbk_model* cut, int nlayer, const double* k, int64_t nk, double* h00, double* h01);
+/* z = omega + i eta.  With es = et = e = H00, al = H01, be = H01^+ one step is g = (z - e)^-1, es += al g be, et += be g al,
+ * e += al g be + be g al, al <- al g al, be <- be g be; after i steps G_0 = (z - es)^-1 (side 0: the crystal fills cells >= 0, cell 0
+ * exposed), G_1 = (z - et)^-1 (side 1: cells <= 0, the last cell of the layer exposed), G_b = (z - e)^-1 (side 2: bulk).  A point
+ * (k, omega) stops at the first i >= 0 with max(|al|_max, |be|_max) <= tol max(|H00|_max, |H01|_max); tol = 0: exactly max_iter steps.
+ * TBK_ENOCONV (the message counts the points) when a point misses a non-zero tol after max_iter (0..64) steps.
+ * nomega (1..65536) finite frequencies in any order, eta > 0, tol >= 0, all finite; nlayer <= 128 (TBK_EUNSUPPORTED beyond).
+ *   mode 0: out[nk][nomega][nlayer][nlayer] c128, the Green's function of `side` (0, 1, 2)
+ *   mode 1: out[3][nk][nomega], A = -(1 / pi) Im sum_s G_ss over the states of the exposed unit cell (cell 0; the last cell for side 1)
+ *   mode 2: out[3][nk][nomega][ncell], that diagonal itself
+ * info (nullable): [nk][nomega] steps taken.  The value at a point does not depend on the rest of the call: same bits alone, in any
+ * batch, at any position.                                                                                                       */
+int tbk_surface_green_list(tbk_model* cut, int nlayer, int ncell, const double* k, int64_t nk, int nomega, const double* omega,
+                           double eta, double tol, int max_iter, int mode, int side, double* out, int32_t* info);
+/* the mean of modes 1 (per_state = 0: out[3][nomega]) and 2 (out[3][nomega][ncell]) over k_uniform_mesh(mesh) of the surface zone
+ * (dim_k 1..3), generated on the device; fixed-order sums, no atomics on floating-point data: bit-reproducible.                */
+int tbk_surface_dos_mesh(tbk_model* cut, int nlayer, int ncell, const int32_t* mesh, int nomega, const double* omega, double eta,
+                         double tol, int max_iter, int per_state, double* out);
+
 /* ---- multi-GPU: one process per GPU, k-points sharded, one gather ------
  * Thin RCCL wrappers (librccl is dlopen'ed on first use).  The 128-byte id is
  * created on rank 0 and distributed by the launcher (any out-of-band channel). */

@@ -85,6 +85,7 @@ class tb_model(object):
         self._hoppings = []
         self._tbk_epoch = 0        # bumped whenever the tables change
         self._tbk_cache = None     # (epoch, device handle)
+        self._tbk_surface = {}     # fin_dir -> (fingerprint, cut_piece(2 L, fin_dir)) of the surface Green's functions
 
     # ------------------------------------------------------------------ tables
     def _val_to_block(self, val):
@@ -232,6 +233,7 @@ class tb_model(object):
     def __getstate__(self):                      # deepcopy / pickle: drop the device handle
         st = dict(self.__dict__)
         st["_tbk_cache"] = None
+        st["_tbk_surface"] = {}
         return st
 
     def __del__(self):
@@ -1080,6 +1082,159 @@ class tb_model(object):
             raise Exception("\n\nBasis must be either 'wavefunction', 'bloch', or 'orbital'")
         _, hwfc, hwf = self._position_call(evec, dir, False, True, True, orbital, _wfs)
         return (hwfc, hwf)
+
+    # ------------------------------------------------------------------ surface Green's functions (extensions)
+    def _surface_dir(self, fin_dir):
+        """Checked fin_dir of the surface calls: a periodic lattice direction, as `cut_piece` takes it."""
+        if self._dim_k == 0:
+            raise Exception("\n\nSurface Green's functions need a model with dim_k >= 1.")
+        if not _is_int(fin_dir) or fin_dir < 0 or fin_dir >= self._dim_r:
+            raise Exception("\n\nfin_dir must be a lattice direction in [0, dim_r).")
+        if list(self._per).count(fin_dir) != 1:
+            raise Exception("\n\nCan not make model finite along this direction!")
+        return int(fin_dir)
+
+    def principal_layer(self, fin_dir):
+        """Extension: L = max(1, max |R_fin_dir| over the hoppings), the number of unit cells along `fin_dir` in one
+        principal layer: layers of L cells couple to their nearest neighbours only."""
+        d = self._surface_dir(fin_dir)
+        return max([1] + [abs(int(h[3][d])) for h in self._hoppings])
+
+    def _surface_cut(self, fin_dir):
+        """(device handle of cut_piece(2 L, fin_dir), L, N = L nsta); the cut model is built once per state of the tables."""
+        d = self._surface_dir(fin_dir)
+        L = self.principal_layer(d)
+        N = L * self._nsta
+        if N > 128:
+            raise _lib.TbkError("\n\nA principal layer of %d states (L = %d cells of %d): the decimation kernels of this "
+                                "build take at most 128." % (N, L, self._nsta))
+        mark = (self._tbk_epoch, len(self._hoppings), self._orb.tobytes(), np.asarray(self._site_energies).tobytes())
+        c = self._tbk_surface.get(d)
+        if c is None or c[0] != mark:
+            import contextlib
+            import io
+            with contextlib.redirect_stdout(io.StringIO()):
+                cut = self.cut_piece(2 * L, d)
+            c = (mark, cut)
+            self._tbk_surface[d] = c
+        return c[1], L, N
+
+    def _surface_k(self, k_list, one=False):
+        """k list of the surface zone, `(nk, dim_k - 1)`; a model with dim_k == 1 has no k and one point."""
+        dk = self._dim_k - 1
+        if dk == 0:
+            if k_list is not None and np.asarray(k_list, dtype=float).size != 0:
+                raise Exception("\n\nk-vector of wrong shape!")
+            return None, 1
+        if k_list is None:
+            raise Exception("\n\nHave to provide a k-vector!")
+        k = np.array(k_list, dtype=float)
+        if one:
+            if k.ndim == 0:
+                k = k.reshape(1)
+            if k.shape != (dk,):
+                raise Exception("\n\nk-vector of wrong shape!")
+            k = k.reshape(1, dk)
+        elif dk == 1 and k.ndim == 1:
+            k = k.reshape(-1, 1)
+        if k.ndim != 2 or k.shape[1] != dk or k.shape[0] < 1:
+            raise Exception("\n\nk-vector of wrong shape!")
+        if not np.all(np.isfinite(k)):
+            raise Exception("\n\nk must be finite.")
+        return np.ascontiguousarray(k), k.shape[0]
+
+    @staticmethod
+    def _surface_args(omega, eta, tol, max_iter):
+        w = np.array(omega, dtype=float)
+        if w.ndim != 1 or w.size < 1 or w.size > 65536:
+            raise Exception("\n\nomega must be a 1-D array of 1..65536 frequencies.")
+        if not np.all(np.isfinite(w)):
+            raise Exception("\n\nomega must be finite.")
+        if not np.isfinite(eta) or not eta > 0.0:
+            raise Exception("\n\neta must be finite and > 0.")
+        if not np.isfinite(tol) or not tol >= 0.0:
+            raise Exception("\n\ntol must be finite and >= 0.")
+        if not _is_int(max_iter) or max_iter < 0 or max_iter > 64:
+            raise Exception("\n\nmax_iter must be an integer in 0..64.")
+        return np.ascontiguousarray(w)
+
+    def _gen_layer_blocks(self, k_point, fin_dir):
+        """Extension: `(H00, H01)`, each complex `(N, N)`, N = L nsta: the top-left and top-right blocks of
+        `cut_piece(2 L, fin_dir)._gen_ham(k_point)`, built on the device.  H00 is the Hamiltonian of one principal layer
+        (state `cell * nsta + state`, spin innermost), H01 couples it to the next layer toward +fin_dir; `k_point` holds the
+        reduced coordinates of the remaining periodic directions (None for dim_k == 1)."""
+        cut, L, N = self._surface_cut(fin_dir)
+        k, _ = self._surface_k(k_point, one=True)
+        h00 = np.zeros((1, N, N), dtype=complex)
+        h01 = np.zeros((1, N, N), dtype=complex)
+        _lib.check(_lib.lib.tbk_surface_blocks(cut._device_model(), N, _lib.dptr(k), 1, _lib.dptr(h00.view(float)),
+                                               _lib.dptr(h01.view(float))))
+        return h00[0], h01[0]
+
+    def surface_green(self, k_list, omega, eta, fin_dir, side, tol=1e-12, max_iter=50):
+        """Extension: the retarded Green's function of the semi-infinite crystal by iterative decimation (Lopez Sancho,
+        Lopez Sancho and Rubio 1985) on the principal layer of `_gen_layer_blocks`, z = omega + i eta:
+
+            side 0   the crystal fills cells >= 0 along fin_dir, cell 0 exposed:  G = [z - H00 - H01 G H01^+]^-1
+            side 1   the crystal fills cells <= 0, the last cell of the layer exposed:  G = [z - H00 - H01^+ G H01]^-1
+            side 2   bulk:  G = [z - H00 - H01 G_0 H01^+ - H01^+ G_1 H01]^-1
+
+        Returns complex `(nk, nw, N, N)`; meant for a few points (whole matrices).  k_list: points of the surface zone,
+        `(nk, dim_k - 1)`, the coordinates `cut_piece(., fin_dir)`'s model takes (None for dim_k == 1: one point).
+        omega: 1-D, 1..65536 finite values in any order; eta > 0.  A point stops at the first step count i (0 included)
+        with max(|alpha|_max, |beta|_max) <= tol max(|H00|_max, |H01|_max); tol=0 takes exactly max_iter (0..64) steps, after
+        which G is a diagonal block of the resolvent of the slab of L 2^i cells (L (2^(i+1) - 1) for the bulk).  Raises when
+        a point misses a non-zero tol.  The value at a point does not depend on the rest of the call (same bits)."""
+        if side not in (0, 1, 2) or not _is_int(side):
+            raise Exception("\n\nside must be 0, 1 or 2 (bulk).")
+        cut, L, N = self._surface_cut(fin_dir)
+        k, nk = self._surface_k(k_list)
+        w = self._surface_args(omega, eta, tol, max_iter)
+        out = np.zeros((nk, w.size, N, N), dtype=complex)
+        _lib.check(_lib.lib.tbk_surface_green_list(cut._device_model(), N, self._nsta, _lib.dptr(k), nk, int(w.size), _lib.dptr(w),
+                                                   float(eta), float(tol), int(max_iter), 0, int(side),
+                                                   _lib.dptr(out.view(float)), None))
+        return out
+
+    def surface_spectral(self, k_list, omega, eta, fin_dir, per_state=False, tol=1e-12, max_iter=50, return_info=False):
+        """Extension: the spectral functions A = -(1 / pi) Im sum_s G_ss of the two surfaces and the bulk, float
+        `(3, nk, nw)` with rows side 0, side 1, bulk of `surface_green`; the sum runs over the states of the exposed unit
+        cell (cell 0 of the layer; the last cell for side 1).  per_state=True: `(3, nk, nw, nsta)`, the diagonal itself.
+        return_info=True: `(A, steps)` with steps int32 `(nk, nw)`, the decimation steps each point took.  Arguments and
+        stopping rule as `surface_green`.  Each side and the bulk come out separately and without a finite-size gap, at the
+        cost of matrices of one principal layer per (k, omega): what a ribbon of `cut_piece` cells diagonalised at every k
+        approximates."""
+        cut, L, N = self._surface_cut(fin_dir)
+        k, nk = self._surface_k(k_list)
+        w = self._surface_args(omega, eta, tol, max_iter)
+        ns = self._nsta
+        out = np.zeros((3, nk, w.size, ns) if per_state else (3, nk, w.size), dtype=float)
+        info = np.zeros((nk, w.size), dtype=np.int32) if return_info else None
+        _lib.check(_lib.lib.tbk_surface_green_list(cut._device_model(), N, ns, _lib.dptr(k), nk, int(w.size), _lib.dptr(w),
+                                                   float(eta), float(tol), int(max_iter), 2 if per_state else 1, 0,
+                                                   _lib.dptr(out), _lib.iptr(info)))
+        return (out, info) if return_info else out
+
+    def surface_dos_mesh(self, mesh_size, omega, eta, fin_dir, per_state=False, tol=1e-12, max_iter=50):
+        """Extension: the mean of `surface_spectral` over the uniform mesh of the surface zone -- the `k_uniform_mesh`
+        points of `cut_piece(., fin_dir)`'s model, generated on the device: `(3, nw)`, or `(3, nw, nsta)` with
+        per_state=True.  Needs dim_k >= 2.  Fixed-order sums on the device: two calls give the same bits."""
+        d = self._surface_dir(fin_dir)
+        if self._dim_k < 2:
+            raise Exception("\n\nsurface_dos_mesh needs a model with dim_k >= 2.")
+        mesh = np.array(list(map(round, mesh_size)), dtype=np.int32)
+        if mesh.shape != (self._dim_k - 1,):
+            raise Exception("\n\nIncorrect size of the specified k-mesh!")
+        if np.min(mesh) <= 0:
+            raise Exception("\n\nMesh must have positive non-zero number of elements.")
+        w = self._surface_args(omega, eta, tol, max_iter)
+        cut, L, N = self._surface_cut(d)
+        ns = self._nsta
+        out = np.zeros((3, w.size, ns) if per_state else (3, w.size), dtype=float)
+        _lib.check(_lib.lib.tbk_surface_dos_mesh(cut._device_model(), N, ns, _lib.iptr(np.ascontiguousarray(mesh)), int(w.size),
+                                                 _lib.dptr(w), float(eta), float(tol), int(max_iter), 1 if per_state else 0,
+                                                 _lib.dptr(out)))
+        return out
 
     # ------------------------------------------------------------------ k generators (host)
     def k_uniform_mesh(self, mesh_size):
