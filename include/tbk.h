@@ -405,6 +405,31 @@ int tbk_surface_green_list(tbk_model* cut, int nlayer, int ncell, const double* 
 int tbk_surface_dos_mesh(tbk_model* cut, int nlayer, int ncell, const int32_t* mesh, int nomega, const double* omega, double eta,
                          double tol, int max_iter, int per_state, double* out);
 
+/* ---- Landauer transmission through a scattering region between two leads of the crystal ----------
+ * No reference counterpart.  `cut`, nlayer, k, omega, eta, tol, max_iter and the decimation as in the surface calls above.  The left
+ * lead fills the layers <= 0 and the right one the layers >= nlayers + 1; with G_0 = (z - es)^-1, G_1 = (z - et)^-1 of that decimation
+ *   Sigma_R = H01 G_0 H01^+ (side 0, on layer nlayers),   Sigma_L = H01^+ G_1 H01 (side 1, on layer 1),   Gamma = i (Sigma - Sigma^+).
+ * `dev` is the uploaded device: a model of nlayers nlayer states (1..1024 layers) with the dim_k and the context of `cut`, whose H(k)
+ * is block-tridiagonal in layers of nlayer states, D_i (i = 1..nlayers) on the diagonal and U_i = H_{i,i+1} above it; slots that join
+ * layers further apart are ignored (the Python layer rejects such a device).
+ * tbk_landauer_blocks: d[nk][nlayers][nlayer][nlayer], u[nk][nlayers - 1][nlayer][nlayer] c128 (u nullable for one layer).        */
+int tbk_landauer_blocks(tbk_model* dev, int nlayer, int nlayers, const double* k, int64_t nk, double* d, double* u);
+/* out[nk][nomega][nlayer][nlayer] c128: Sigma_R (side 0) or Sigma_L (side 1); info (nullable): [nk][nomega] decimation steps.   */
+int tbk_lead_self_energy_list(tbk_model* cut, int nlayer, const double* k, int64_t nk, int nomega, const double* omega,
+                              double eta, double tol, int max_iter, int side, double* out, int32_t* info);
+/* T = Re Tr[Gamma_R P Gamma_L P^+], P = G_{nlayers,1} of (z - H_dev - Sigma_L (+) Sigma_R)^-1 by the forward sweep A_1 = z - D_1 -
+ * Sigma_L, A_i = z - D_i - U_{i-1}^+ A_{i-1}^-1 U_{i-1}, A_nlayers additionally - Sigma_R, P_1 = A_1^-1, P_i = A_i^-1 U_{i-1}^+ P_{i-1};
+ * the same eta in the leads and in the device.  out[nk][nomega] doubles, info as above.  dev = null: one pristine layer (nlayers = 1,
+ * D_1 = H00).  TBK_ENOCONV as the surface calls; TBK_EUNSUPPORTED (the message says what to split) when the buffers of a call would
+ * pass 4 GiB.  The value at a point does not depend on the rest of the call: same bits alone, in any batch, at any position.         */
+int tbk_transmission_list(tbk_model* cut, tbk_model* dev /* null: one pristine layer */, int nlayer, int nlayers,
+                          const double* k, int64_t nk, int nomega, const double* omega, double eta, double tol,
+                          int max_iter, double* out, int32_t* info);
+/* out[nomega]: the mean of T over k_uniform_mesh(mesh) of the surface zone (dim_k 1..3), generated on the device; fixed-order sums,
+ * no atomics on floating-point data: bit-reproducible.                                                                           */
+int tbk_transmission_mesh(tbk_model* cut, tbk_model* dev, int nlayer, int nlayers, const int32_t* mesh, int nomega,
+                          const double* omega, double eta, double tol, int max_iter, double* out);
+
 /* ---- multi-GPU: one process per GPU, k-points sharded, one gather ------
  * Thin RCCL wrappers (librccl is dlopen'ed on first use).  The 128-byte id is
  * created on rank 0 and distributed by the launcher (any out-of-band channel). */

@@ -112,7 +112,11 @@ SIGNATURES = {
     "tbk_surface_blocks": (_i, [_p, _i, _dp, _i64, _dp, _dp]),
     "tbk_surface_green_list": (_i, [_p, _i, _i, _dp, _i64, _i, _dp, C.c_double, C.c_double, _i, _i, _i, _dp, _ip]),
     "tbk_surface_dos_mesh": (_i, [_p, _i, _i, _ip, _i, _dp, C.c_double, C.c_double, _i, _i, _dp]),
-    "tbk_comm_unique_id": (_i, [C.POINTER(C.c_ubyte)]),
+    "tbk_landauer_blocks": (_i, [_p, _i, _i, _dp, _i64, _dp, _dp]),
+    "tbk_lead_self_energy_list": (_i, [_p, _i, _dp, _i64, _i, _dp, C.c_double, C.c_double, _i, _i, _dp, _ip]),
+    "tbk_transmission_list": (_i, [_p, _p, _i, _i, _dp, _i64, _i, _dp, C.c_double, C.c_double, _i, _dp, _ip]),
+    "tbk_transmission_mesh": (_i, [_p, _p, _i, _i, _ip, _i, _dp, C.c_double, C.c_double, _i, _dp]),
+    "tbk_comm_unique_id":(_i, [C.POINTER(C.c_ubyte)]),
     "tbk_comm_init": (_i, [_p, C.POINTER(C.c_ubyte), _i, _i]),
     "tbk_comm_destroy": (_i, [_p]),
     "tbk_comm_allgather_f64": (_i, [_p, _p, _p, _i64]),

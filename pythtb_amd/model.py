@@ -1236,6 +1236,111 @@ class tb_model(object):
                                                  _lib.dptr(out)))
         return out
 
+    # ------------------------------------------------------------------ Landauer transmission (extensions)
+    def lead_self_energy(self, k_list, omega, eta, fin_dir, side, tol=1e-12, max_iter=50):
+        """Extension: the self-energy a pristine semi-infinite lead of this crystal puts on the layer it touches, from the
+        decimation of `surface_green` (same arguments, stopping rule and sides):
+
+            side 0   Sigma_R = H01 G_0 H01^+   the lead fills the layers toward +fin_dir, its first layer exposed
+            side 1   Sigma_L = H01^+ G_1 H01   the lead fills the layers toward -fin_dir, its last layer exposed
+
+        Returns complex `(nk, nw, N, N)`; whole matrices, meant for a few points."""
+        if side not in (0, 1) or not _is_int(side):
+            raise Exception("\n\nside must be 0 or 1.")
+        cut, L, N = self._surface_cut(fin_dir)
+        k, nk = self._surface_k(k_list)
+        w = self._surface_args(omega, eta, tol, max_iter)
+        out = np.zeros((nk, w.size, N, N), dtype=complex)
+        _lib.check(_lib.lib.tbk_lead_self_energy_list(cut._device_model(), N, _lib.dptr(k), nk, int(w.size), _lib.dptr(w),
+                                                      float(eta), float(tol), int(max_iter), int(side),
+                                                      _lib.dptr(out.view(float)), None))
+        return out
+
+    def _landauer_device(self, device, fin_dir):
+        """Checked `device` of the transmission calls: the number M of principal layers it holds (host checks only)."""
+        d = self._surface_dir(fin_dir)
+        L = self.principal_layer(d)
+        if not isinstance(device, tb_model):
+            raise Exception("\n\ndevice must be a tb_model.")
+        if (device._dim_r != self._dim_r or device._nspin != self._nspin or device._lat.shape != self._lat.shape
+                or not np.array_equal(device._lat, self._lat)):
+            raise Exception("\n\ndevice must share the lattice and nspin of the model.")
+        if list(device._per) != [p for p in self._per if p != d]:
+            raise Exception("\n\ndevice must be finite along fin_dir and periodic along the other periodic directions.")
+        nl = L * self._norb
+        M = device._norb // nl
+        if device._norb % nl != 0 or M < 1 or M > 1024:
+            raise Exception("\n\ndevice must hold 1..1024 principal layers of %d orbitals." % nl)
+        want = np.tile(self._orb, (M * L, 1))                  # the orbitals of cut_piece(M L, fin_dir), by its own arithmetic
+        want[:, d] += np.repeat(np.arange(M * L, dtype=float), self._norb)
+        if not np.abs(device._orb - want).max() <= 1e-12:
+            raise Exception("\n\ndevice orbitals must be those of cut_piece(%d, fin_dir)." % (M * L))
+        for h in device._hoppings:
+            la, lb = sorted((h[1] // nl, h[2] // nl))
+            if lb - la > 1:
+                raise Exception("\n\ndevice couples layers %d and %d: only neighbouring principal layers may couple."
+                                % (la + 1, lb + 1))
+        return M
+
+    def _gen_device_blocks(self, k_point, fin_dir, device):
+        """Extension: `(D, U)`, complex `(M, N, N)` and `(M - 1, N, N)`: the diagonal blocks D_i and the upper blocks
+        U_i = H_{i,i+1} of `device._gen_ham(k_point)` in layers of N = L nsta states, built on the device; the counterpart
+        of `_gen_layer_blocks` for the scattering region of `transmission`."""
+        cut, L, N = self._surface_cut(fin_dir)
+        M = self._landauer_device(device, fin_dir)
+        k, _ = self._surface_k(k_point, one=True)
+        D = np.zeros((1, M, N, N), dtype=complex)
+        U = np.zeros((1, max(M - 1, 0), N, N), dtype=complex)
+        _lib.check(_lib.lib.tbk_landauer_blocks(device._device_model(), N, M, _lib.dptr(k), 1, _lib.dptr(D.view(float)),
+                                                _lib.dptr(U.view(float)) if M > 1 else None))
+        return D[0], U[0]
+
+    def transmission(self, k_list, omega, eta, fin_dir, device=None, tol=1e-12, max_iter=50, return_info=False):
+        """Extension: the Landauer transmission T(k, omega) = Tr[Gamma_R G Gamma_L G^+] (Caroli / Fisher-Lee) of a scattering
+        region between two pristine semi-infinite leads of this crystal, float `(nk, nw)`; the conductance is e^2 / h times
+        T (per spin channel kept in the model).  Gamma = i (Sigma - Sigma^+) with the self-energies of `lead_self_energy`,
+        G the retarded Green's function of the region with both self-energies, z = omega + i eta in the leads and in the
+        region alike.
+
+        device: a `tb_model` with the geometry of `self.cut_piece(M * L, fin_dir)`, L = `principal_layer(fin_dir)`,
+        M = 1..1024, which the caller has edited (on-site shifts, changed or added hoppings); it may couple neighbouring
+        principal layers only.  The left lead continues it below layer 1, the right lead above layer M, both with the
+        crystal's own H01.  device=None: one pristine principal layer.  The work per point is a recursive Green's function
+        sweep over the M layers on matrices of one layer (N <= 128).  k_list, omega, eta, tol, max_iter as `surface_green`;
+        return_info=True: `(T, steps)` with steps int32 `(nk, nw)`, the decimation steps of the leads.  The value at a point
+        does not depend on the rest of the call (same bits)."""
+        cut, L, N = self._surface_cut(fin_dir)
+        M = 1 if device is None else self._landauer_device(device, fin_dir)
+        k, nk = self._surface_k(k_list)
+        w = self._surface_args(omega, eta, tol, max_iter)
+        out = np.zeros((nk, w.size), dtype=float)
+        info = np.zeros((nk, w.size), dtype=np.int32) if return_info else None
+        _lib.check(_lib.lib.tbk_transmission_list(cut._device_model(), None if device is None else device._device_model(), N, M,
+                                                  _lib.dptr(k), nk, int(w.size), _lib.dptr(w), float(eta), float(tol),
+                                                  int(max_iter), _lib.dptr(out), _lib.iptr(info)))
+        return (out, info) if return_info else out
+
+    def conductance_mesh(self, mesh_size, omega, eta, fin_dir, device=None, tol=1e-12, max_iter=50):
+        """Extension: the mean of `transmission` over the uniform mesh of the surface zone -- the `k_uniform_mesh` points of
+        `cut_piece(., fin_dir)`'s model, generated on the device: float `(nw,)`, the conductance per transverse cell in
+        units of e^2 / h.  Needs dim_k >= 2.  Fixed-order sums on the device: two calls give the same bits."""
+        d = self._surface_dir(fin_dir)
+        if self._dim_k < 2:
+            raise Exception("\n\nconductance_mesh needs a model with dim_k >= 2.")
+        mesh = np.array(list(map(round, mesh_size)), dtype=np.int32)
+        if mesh.shape != (self._dim_k - 1,):
+            raise Exception("\n\nIncorrect size of the specified k-mesh!")
+        if np.min(mesh) <= 0:
+            raise Exception("\n\nMesh must have positive non-zero number of elements.")
+        w = self._surface_args(omega, eta, tol, max_iter)
+        cut, L, N = self._surface_cut(d)
+        M = 1 if device is None else self._landauer_device(device, d)
+        out = np.zeros(w.size, dtype=float)
+        _lib.check(_lib.lib.tbk_transmission_mesh(cut._device_model(), None if device is None else device._device_model(), N, M,
+                                                  _lib.iptr(np.ascontiguousarray(mesh)), int(w.size), _lib.dptr(w), float(eta),
+                                                  float(tol), int(max_iter), _lib.dptr(out)))
+        return out
+
     # ------------------------------------------------------------------ k generators (host)
     def k_uniform_mesh(self, mesh_size):
         """Gamma-containing uniform mesh, last index fastest (pythtb.py:1792-1861)."""
