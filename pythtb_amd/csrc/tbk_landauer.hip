@@ -13,36 +13,31 @@
 //   P_i = X_a   (P_M = G_{M,1}),      T = Re Tr[Gamma_R P_M Gamma_L P_M^+]
 //
 // Kernels: k_land_blocks (D, U of every k of a chunk, once) and the three storage regimes of tbk_surface.hip, each kernel the
-// decimation loop, the two self-energies, the sweep and the trace in one:
+// decimation (sgf_decimate_n2 / sgf_decimate_wg of tbk_sgf.h, the calls tbk_surface.hip makes), then this unit's own part: the two
+// self-energies, the sweep and the trace:
 //   N = 2        k_land_n2: a lane per problem, the matrices in registers, 2 x 2 inverses by the adjugate
 //   N <= 32      k_land_wg<false>: the seven N x (N + 1) slots per problem in LDS (Sigma_L, Sigma_R, A, X_a, X_b, U^+ P, one spare)
 //   N <= 128     k_land_wg<true>: the same code on the global workspace
 // mode 1 of the same kernels stops after the self-energies and writes one of them whole.  A problem's arithmetic depends on its own
 // (k, w) alone; the trace is summed over the problem's own threads in a fixed order (shuffle tree, then the `red` array): a point's
-// bits do not depend on the batch, its position in it or the chunk.  No floating-point atomics.
+// bits do not depend on the batch, its position in it or the chunk.  No floating-point atomics.  The host side is the launcher, the
+// argument checks and the chunk driver of tbk_sgf.h around this unit's kernels, block table and downloads.
 #include <math.h>
 #include <string.h>
 #include "tbk_sgf.h"
 
 static const int kLandMaxLayers = 1024;
 
-struct LandArgs {
-    const cd* blk;        // [nk][2][N][N]: H00, H01 of the chunk's k points
+struct LandArgs : SgfCommon {
     const cd* dblk;       // [nk][2 M - 1][N][N]: D_1 .. D_M, U_1 .. U_{M-1} of the device; null: M = 1 and D_1 = H00
-    const double* omega;  // [nw]
-    int nw, N, M;         // frequencies, layer size, layers of the device
-    double eta, tol;
-    int max_iter;
+    int M;                // layers of the device
     int mode;             // 0: T, out[p] double; 1: the self-energy of `side` (0: Sigma_R, 1: Sigma_L), out[p][N][N] c128
     int side;
-    int64_t nprob;        // nk nw, problem p = ik nw + iw
     double* out;
-    int* info;            // [nprob] decimation steps taken, or null
-    unsigned long long* fail;   // count of problems that missed a non-zero tol
 };
 
 // ---------------------------------------------------------------- D, U
-// one thread per (k, non-empty slot (a, b), a <= b) of the device model, H_ab as k_sgf_blocks forms it: both states in layer i -> D_i,
+// one thread per (k, non-empty slot (a, b), a <= b) of the device model, H_ab by sgf_hab: both states in layer i -> D_i,
 // b in the next layer -> U_i.  (Slots further apart do not exist: the caller has rejected such a device.)
 __global__ __launch_bounds__(256) void k_land_blocks(const ModelView mv, const double* __restrict__ k, const int64_t nk, const int N,
                                                      const int M, cd* __restrict__ dblk) {
@@ -53,21 +48,13 @@ __global__ __launch_bounds__(256) void k_land_blocks(const ModelView mv, const d
     const int a = z4.x & 0xffff, b = z4.x >> 16;
     const int la = a / N, lb = b / N;
     if (a > b || lb >= M || lb - la > 1) return;
-    double kk[4];
-    cd z[4];
-    k_phases(mv, k, ik, kk, z);
-    cd s{0.0, 0.0};
-    for (int t = z4.y; t < z4.z; ++t) cfma(s, mv.term_amp[t], phase_of_R(z, mv.term_R[t]));
+    const cd v = sgf_hab(mv, k, ik, z4);
     const int64_t NN = (int64_t)N * N;
     cd* d = dblk + (ik * (2 * M - 1) + la) * NN;
     const int ra = a - la * N, rb = b - lb * N;
     if (a == b) {
-        d[ra * N + ra] = cd{s.x, 0.0};
-        return;
-    }
-    const cd ea = expi2pi(kdot(kk, mv.orb[a])), eb = expi2pi(kdot(kk, mv.orb[b]));
-    const cd v = cmul(cmulc(ea, eb), s);
-    if (la == lb) {
+        d[ra * N + ra] = v;
+    } else if (la == lb) {
         d[ra * N + rb] = v;
         d[rb * N + ra] = cconj(v);
     } else {
@@ -76,8 +63,6 @@ __global__ __launch_bounds__(256) void k_land_blocks(const ModelView mv, const d
 }
 
 // ---------------------------------------------------------------- N = 2: a lane per problem
-__device__ __forceinline__ M2 m2load(const cd* h) { return M2{h[0], h[1], h[2], h[3]}; }
-__device__ __forceinline__ M2 m2dag(const M2& x) { return M2{cconj(x.a), cconj(x.c), cconj(x.b), cconj(x.d)}; }
 // i (x - conj(y))
 __device__ __forceinline__ cd land_gamma(const cd x, const cd y) { return cd{-(x.y + y.y), x.x - y.x}; }
 __device__ __forceinline__ M2 m2gamma(const M2& s) {
@@ -88,39 +73,12 @@ __device__ __forceinline__ double land_re(const double acc, const cd g, const cd
 __global__ __launch_bounds__(256) void k_land_n2(const LandArgs A) {
     const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (p >= A.nprob) return;
-    const int64_t ik = p / A.nw;
-    const int iw = (int)(p - ik * A.nw);
-    const cd* h = A.blk + ik * 8;
-    const M2 h0{h[0], h[1], h[2], h[3]};
-    M2 al{h[4], h[5], h[6], h[7]};
-    M2 be{cconj(al.a), cconj(al.c), cconj(al.b), cconj(al.d)};
-    M2 es = h0, et = h0;
-    const cd z{A.omega[iw], A.eta};
-    const double scale = sqrt(fmax(m2max(h0), m2max(al)));
-    double cur = sqrt(m2max(al));
-    int steps = 0;
-    bool conv = false;
-    for (;;) {
-        if (A.tol > 0.0 && cur <= A.tol * scale) {
-            conv = true;
-            break;
-        }
-        if (steps == A.max_iter) break;
-        const M2 g = m2resolvent(z, m2bulk(es, et, h0));
-        const M2 xa = m2mul(g, al), xb = m2mul(g, be);
-        m2acc(es, m2mul(al, xb));
-        m2acc(et, m2mul(be, xa));
-        const M2 na = m2mul(al, xa), nb = m2mul(be, xb);
-        al = na;
-        be = nb;
-        cur = sqrt(fmax(m2max(al), m2max(be)));
-        ++steps;
-    }
-    if (A.tol > 0.0 && !conv) atomicAdd(A.fail, 1ull);
-    if (A.info) A.info[p] = steps;
+    const Sgf2 D = sgf_decimate_n2(A, p);
+    const cd* h = D.h;
+    const cd z = D.z;
     const M2 h1 = m2load(h + 4), h1d = m2dag(h1);
-    const M2 sl = m2mul(h1d, m2mul(m2resolvent(z, et), h1));
-    const M2 sr = m2mul(h1, m2mul(m2resolvent(z, es), h1d));
+    const M2 sl = m2mul(h1d, m2mul(m2resolvent(z, D.et), h1));
+    const M2 sr = m2mul(h1, m2mul(m2resolvent(z, D.es), h1d));
     if (A.mode == 1) {
         cd* o = (cd*)A.out + p * 4;
         if (A.side == 0) o[0] = sr.a, o[1] = sr.b, o[2] = sr.c, o[3] = sr.d;
@@ -128,7 +86,7 @@ __global__ __launch_bounds__(256) void k_land_n2(const LandArgs A) {
         return;
     }
     const int M = A.M;
-    const cd* d = A.dblk ? A.dblk + ik * (2 * M - 1) * 4 : h;
+    const cd* d = A.dblk ? A.dblk + D.ik * (2 * M - 1) * 4 : h;
     const cd* u = d + (int64_t)M * 4;
     M2 e = m2load(d);
     m2acc(e, sl);
@@ -168,106 +126,21 @@ template <bool GLOBAL>
 __global__ __launch_bounds__(256) void k_land_wg(const LandArgs A, const int P, const int tp_log, const int ld, cd* ws) {
     extern __shared__ cd sgf_lds[];
     __shared__ double red[8];
-    const int N = A.N, TP = 1 << tp_log, NN = N * N, msz = N * ld, M = A.M;
-    const int sub = threadIdx.x >> tp_log, t = threadIdx.x & (TP - 1);
-    cd* B;
-    if constexpr (GLOBAL) B = ws + (int64_t)blockIdx.x * 7 * msz;
-    else B = sgf_lds + sub * 7 * msz;
+    const int N = A.N, TP = 1 << tp_log, NN = N * N, M = A.M;
+    cd* const mem = GLOBAL ? ws + (int64_t)blockIdx.x * 7 * N * ld : sgf_lds;
     const int64_t ngroups = (A.nprob + P - 1) / P;
     for (int64_t g = blockIdx.x; g < ngroups; g += gridDim.x) {
-        cd *es = B, *et = B + msz, *al = B + 2 * msz, *be = B + 3 * msz, *wm = B + 4 * msz, *xa = B + 5 * msz, *xb = B + 6 * msz;
-        const int64_t p = g * P + sub;
-        const bool live = p < A.nprob;
-        const int64_t ik = live ? p / A.nw : 0;
-        const int iw = live ? (int)(p - ik * A.nw) : 0;
-        const cd* h00 = A.blk + ik * 2 * NN;
-        const cd* h01 = h00 + NN;
-        const cd z{A.omega[iw], A.eta};
-        __syncthreads();                                   // the previous group's last reads
-        double m0 = 0.0, m1 = 0.0;
-        if (live)
-            for (int e = t; e < NN; e += TP) {
-                const int i = e / N, j = e - i * N;
-                const cd a0 = h00[e], a1 = h01[e];
-                es[i * ld + j] = a0;
-                et[i * ld + j] = a0;
-                al[i * ld + j] = a1;
-                be[i * ld + j] = cconj(h01[j * N + i]);
-                m0 = fmax(m0, cabs2(a0));
-                m1 = fmax(m1, cabs2(a1));
-            }
-        sgf_group_max(m0, m1, tp_log, red);
-        const double scale = sqrt(fmax(m0, m1));
-        double cur = sqrt(m1);
-        int steps = 0;
-        bool conv = false, active = live;
-        for (;;) {                                         // the decimation loop of k_sgf_wg
-            if (active) {
-                if (A.tol > 0.0 && cur <= A.tol * scale) conv = true, active = false;
-                else if (steps == A.max_iter) active = false;
-            }
-            if (!__syncthreads_or(active ? 1 : 0)) break;
-            if (active)
-                for (int e = t; e < NN; e += TP) {
-                    const int i = e / N, j = e - i * N, q = i * ld + j;
-                    const cd eb = cadd(es[q], csub(et[q], h00[e]));
-                    wm[q] = i == j ? csub(z, eb) : cd{-eb.x, -eb.y};
-                    xa[q] = al[q];
-                    xb[q] = be[q];
-                }
-            __syncthreads();
-            sgf_solve(wm, xa, xb, N, ld, 3 * N, t, tp_log, active);
-            double ma = 0.0, mb = 0.0;
-            if (active)
-                for (int e = t; e < NN; e += TP) {
-                    const int i = e / N, j = e - i * N, q = i * ld + j;
-                    cd s0{0.0, 0.0}, s1{0.0, 0.0}, na{0.0, 0.0};
-                    for (int k = 0; k < N; ++k) {
-                        const cd a = al[i * ld + k], b = be[i * ld + k], ya = xa[k * ld + j], yb = xb[k * ld + j];
-                        cfma_x(s0, a, yb);
-                        cfma_x(s1, b, ya);
-                        cfma_x(na, a, ya);
-                    }
-                    es[q] = cadd(es[q], s0);
-                    et[q] = cadd(et[q], s1);
-                    wm[q] = na;
-                    ma = fmax(ma, cabs2(na));
-                }
-            __syncthreads();
-            if (active)
-                for (int e = t; e < NN; e += TP) {
-                    const int i = e / N, j = e - i * N;
-                    cd nb{0.0, 0.0};
-                    for (int k = 0; k < N; ++k) cfma_x(nb, be[i * ld + k], xb[k * ld + j]);
-                    al[i * ld + j] = nb;
-                    mb = fmax(mb, cabs2(nb));
-                }
-            __syncthreads();
-            if (active) {
-                cd* const o = al;
-                al = wm;
-                wm = be;
-                be = o;
-                ++steps;
-            }
-            sgf_group_max(ma, mb, tp_log, red);
-            if (active) cur = sqrt(fmax(ma, mb));
-        }
-        if (live && t == 0) {
-            if (A.tol > 0.0 && !conv) atomicAdd(A.fail, 1ull);
-            if (A.info) A.info[p] = steps;
-        }
+        SgfSlots S;
+        const SgfProb Q = sgf_problem(A, P, tp_log, ld, mem, g, S);
+        const int t = Q.t;
+        const bool live = Q.live;
+        const cd *h00 = Q.h00, *h01 = Q.h01;
+        const cd z = Q.z;
+        sgf_decimate_wg(A, Q, S, red);
         // the self-energies: two eliminations with right-hand sides H01 and H01^+, two products; al and be are free and take them
-        cd *sl = al, *sr = be;
-        if (live)
-            for (int e = t; e < NN; e += TP) {
-                const int i = e / N, j = e - i * N, q = i * ld + j;
-                const cd ev = et[q];
-                wm[q] = i == j ? csub(z, ev) : cd{-ev.x, -ev.y};
-                xa[q] = h01[e];
-            }
-        __syncthreads();
-        sgf_solve(wm, xa, xb, N, ld, 2 * N, t, tp_log, live);             // xa = G_1 H01
+        cd *sl = S.al, *sr = S.be, *wm = S.wm, *xa = S.xa, *xb = S.xb;
+        sgf_resolve(                                       // xa = G_1 H01
+            Q, S, [&](int, int q) { return S.et[q]; }, [&](int, int, int e) { return h01[e]; });
         if (live)
             for (int e = t; e < NN; e += TP) {
                 const int i = e / N, j = e - i * N, q = i * ld + j;
@@ -276,15 +149,8 @@ __global__ __launch_bounds__(256) void k_land_wg(const LandArgs A, const int P, 
                 sl[q] = s;
             }
         __syncthreads();
-        if (live)
-            for (int e = t; e < NN; e += TP) {
-                const int i = e / N, j = e - i * N, q = i * ld + j;
-                const cd ev = es[q];
-                wm[q] = i == j ? csub(z, ev) : cd{-ev.x, -ev.y};
-                xa[q] = cconj(h01[j * N + i]);
-            }
-        __syncthreads();
-        sgf_solve(wm, xa, xb, N, ld, 2 * N, t, tp_log, live);             // xa = G_0 H01^+
+        sgf_resolve(                                       // xa = G_0 H01^+
+            Q, S, [&](int, int q) { return S.es[q]; }, [&](int i, int j, int) { return cconj(h01[j * N + i]); });
         if (live)
             for (int e = t; e < NN; e += TP) {
                 const int i = e / N, j = e - i * N, q = i * ld + j;
@@ -296,7 +162,7 @@ __global__ __launch_bounds__(256) void k_land_wg(const LandArgs A, const int P, 
         if (A.mode == 1) {
             if (live) {
                 const cd* s = A.side == 0 ? sr : sl;
-                cd* o = (cd*)A.out + p * NN;
+                cd* o = (cd*)A.out + Q.p * NN;
                 for (int e = t; e < NN; e += TP) {
                     const int i = e / N;
                     o[e] = s[i * ld + (e - i * N)];
@@ -305,8 +171,8 @@ __global__ __launch_bounds__(256) void k_land_wg(const LandArgs A, const int P, 
             continue;
         }
         // the sweep over the layers; es is free and takes the product U^+ P, et is spare
-        cd* up = es;
-        const cd* D = A.dblk ? A.dblk + ik * (2 * M - 1) * NN : h00;
+        cd* up = S.es;
+        const cd* D = A.dblk ? A.dblk + Q.ik * (2 * M - 1) * NN : h00;
         const cd* U = D + (int64_t)M * NN;
         for (int l = 0; l < M; ++l) {
             const bool last = l == M - 1;
@@ -370,39 +236,11 @@ __global__ __launch_bounds__(256) void k_land_wg(const LandArgs A, const int P, 
                 tr = land_re(tr, land_gamma(sr[i * ld + j], sr[j * ld + i]), up[j * ld + i]);
             }
         tr = land_group_sum(tr, tp_log, red);
-        if (live && t == 0) A.out[p] = tr;
+        if (live && t == 0) A.out[Q.p] = tr;
     }
 }
 
 // ---------------------------------------------------------------- host side
-static int land_launch(tbk_ctx* ctx, const LandArgs& A, cd* ws, int ws_groups) {
-    if (A.N == 2) {
-        ProfScope ps(ctx, "land_n2");
-        hipLaunchKernelGGL(k_land_n2, dim3(nblk(A.nprob)), dim3(256), 0, ctx->stream, A);
-        TBK_HIP(hipGetLastError());
-        return TBK_OK;
-    }
-    const SgfShape S = sgf_shape(A.N);
-    if (S.global) {
-        ProfScope ps(ctx, "land_wg_global");
-        const unsigned grid = (unsigned)std::min<int64_t>(A.nprob, ws_groups);
-        hipLaunchKernelGGL(k_land_wg<true>, dim3(grid), dim3(256), 0, ctx->stream, A, 1, S.tp_log, S.ld, ws);
-        TBK_HIP(hipGetLastError());
-        return TBK_OK;
-    }
-    ProfScope ps(ctx, "land_wg_lds");
-    static bool big_lds = false;                           // the attribute belongs to the function: set once per process
-    if (S.lds > 64 * 1024 && !big_lds) {
-        TBK_HIP(hipFuncSetAttribute((const void*)k_land_wg<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-        big_lds = true;
-    }
-    const int64_t ngroups = (A.nprob + S.P - 1) / S.P;
-    const unsigned grid = (unsigned)std::min<int64_t>(ngroups, (int64_t)std::max(ctx->cus, 1) * 32);
-    hipLaunchKernelGGL(k_land_wg<false>, dim3(grid), dim3(256), S.lds, ctx->stream, A, S.P, S.tp_log, S.ld, (cd*)nullptr);
-    TBK_HIP(hipGetLastError());
-    return TBK_OK;
-}
-
 static int land_blocks_launch(tbk_model* dev, const double* k_dev, int64_t nk, int N, int M, cd* dblk) {
     tbk_ctx* ctx = dev->ctx;
     TBK_HIP(hipMemsetAsync(dblk, 0, (size_t)nk * (2 * M - 1) * N * N * sizeof(cd), ctx->stream));
@@ -465,123 +303,44 @@ extern "C" int tbk_landauer_blocks(tbk_model* dev, int nlayer, int nlayers, cons
 }
 
 // the list forms (mesh == null: k[nk][dim_k] from the host) and the mesh mean of T (mesh given: k_uniform_mesh(mesh) generated per
-// chunk); the structure of sgf_run
+// chunk), through the chunk driver of tbk_sgf.h; the device's blocks are the driver's extra table
 static int land_run(const char* who, tbk_model* cut, tbk_model* dev, int N, int M, const double* k, int64_t nk, const int32_t* mesh,
                     int nw, const double* omega, double eta, double tol, int max_iter, int mode, int side, double* out, int32_t* info) {
-    TBK_REQUIRE(omega && out, TBK_EINVAL, "%s: null argument", who);
-    TBK_REQUIRE(nw >= 1 && nw <= 65536, TBK_EINVAL, "%s: nomega=%d (1..65536 frequencies)", who, nw);
-    for (int j = 0; j < nw; ++j) TBK_REQUIRE(std::isfinite(omega[j]), TBK_EINVAL, "%s: frequency %d is not finite", who, j);
-    TBK_REQUIRE(std::isfinite(eta) && eta > 0.0, TBK_EINVAL, "%s: eta must be finite and > 0", who);
-    TBK_REQUIRE(std::isfinite(tol) && tol >= 0.0, TBK_EINVAL, "%s: tol must be finite and >= 0", who);
-    TBK_REQUIRE(max_iter >= 0 && max_iter <= 64, TBK_EINVAL, "%s: max_iter=%d (0..64)", who, max_iter);
+    int rc = sgf_check_call(who, nw, omega, eta, tol, max_iter, out);
+    if (rc) return rc;
     TBK_REQUIRE(mode >= 0 && mode <= 1 && side >= 0 && side <= 1, TBK_EINVAL, "%s: mode %d, side %d", who, mode, side);
-    TBK_REQUIRE(nk >= 1, TBK_EINVAL, "%s: no k point", who);
-    tbk_ctx* ctx = cut->ctx;
-    TBK_HIP(hipSetDevice(ctx->device));
-    const int dk = cut->dim_k;
-    const size_t mb = (size_t)N * N * sizeof(cd), dper = dev ? (size_t)(2 * M - 1) * mb : 0;
-    const size_t perk = 2 * mb + dper + (size_t)nw * sizeof(int) + (mode == 1 ? (size_t)nw * mb : (size_t)nw * sizeof(double));
-    const int64_t chunk = std::max<int64_t>(
-        1, std::min<int64_t>(nk, std::min<int64_t>((int64_t)(kSgfChunkBytes / perk), kSgfChunkProblems / nw)));
-    const int64_t nchunk = (nk + chunk - 1) / chunk;
-    const int64_t rows = nw;                               // values per k point of the mesh mean
-    const SgfShape S = sgf_shape(N);
-    const int ws_groups = (int)std::min<int64_t>(std::max(ctx->cus, 1), chunk * nw);   // the grid of the workspace regime
-    const size_t omb = al256((size_t)nw * sizeof(double));
-    const size_t kb = al256((size_t)(mesh ? chunk : nk) * std::max(dk, 1) * sizeof(double));
-    const size_t bb = al256((size_t)chunk * 2 * mb);
-    const size_t db = al256((size_t)chunk * dper);
-    const size_t ob = al256(mode == 1 ? (size_t)chunk * nw * mb : (size_t)chunk * nw * sizeof(double));
-    const size_t ib = al256((size_t)chunk * nw * sizeof(int));
-    const size_t cb = mesh ? al256((size_t)(nchunk + 1) * rows * sizeof(double)) : 0;
-    const size_t wb = S.global && N != 2 ? (size_t)ws_groups * 7 * N * S.ld * sizeof(cd) : 0;
-    const size_t total = 512 + omb + kb + bb + db + ob + ib + cb + wb;
-    TBK_REQUIRE(total <= kSgfMaxBytes, TBK_EUNSUPPORTED,
+    const size_t mb = (size_t)N * N * sizeof(cd);
+    SgfPlan P;
+    rc = sgf_plan(who, cut, N, nk, mesh, nw, dev ? (size_t)(2 * M - 1) * mb : 0, mode == 1 ? (size_t)nw * mb : (size_t)nw * sizeof(double), nw,
+                  P);
+    if (rc) return rc;
+    TBK_REQUIRE(P.total <= kSgfMaxBytes, TBK_EUNSUPPORTED,
                 "%s: %lld k points x %d frequencies of %d layers of %d states need %zu bytes on the device (at most %zu per call): split "
                 "omega, or the k list",
-                who, (long long)nk, nw, M, N, total, kSgfMaxBytes);
-    void* base = nullptr;
-    int rc = tbk_ctx_scratch(ctx, total, &base);
-    if (rc) return rc;
-    unsigned char* q = (unsigned char*)base + 256;
-    unsigned long long* fail_dev = (unsigned long long*)q;
-    q += 256;
-    double* om_dev = (double*)q;
-    q += omb;
-    double* k_dev = (double*)q;
-    q += kb;
-    cd* blk = (cd*)q;
-    q += bb;
-    cd* dblk = (cd*)q;
-    q += db;
-    double* out_dev = (double*)q;
-    q += ob;
-    int* info_dev = (int*)q;
-    q += ib;
-    double* csum = (double*)q;                             // [nchunk][rows] chunk sums, then [rows] the mean
-    q += cb;
-    cd* ws = (cd*)q;
-    TBK_HIP(hipMemsetAsync(fail_dev, 0, sizeof(unsigned long long), ctx->stream));
-    TBK_HIP(hipMemcpyAsync(om_dev, omega, (size_t)nw * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    if (!mesh && dk > 0) TBK_HIP(hipMemcpyAsync(k_dev, k, (size_t)nk * dk * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    for (int64_t c = 0; c < nchunk; ++c) {
-        const int64_t first = c * chunk, cnt = std::min(chunk, nk - first);
-        const double* kc = k_dev + (mesh ? 0 : first * dk);
-        if (mesh) {
-            rc = tbk_k_uniform_mesh_range_dev(ctx, dk, mesh, first, cnt, k_dev);
-            if (rc) return rc;
-        }
-        rc = sgf_blocks_launch(cut, kc, cnt, N, blk);
-        if (rc) return rc;
-        if (dev) {
-            rc = land_blocks_launch(dev, kc, cnt, N, M, dblk);
-            if (rc) return rc;
-        }
-        LandArgs A{};
-        A.blk = blk;
-        A.dblk = dev ? dblk : nullptr;
-        A.omega = om_dev;
-        A.nw = nw;
-        A.N = N;
-        A.M = M;
-        A.eta = eta;
-        A.tol = tol;
-        A.max_iter = max_iter;
-        A.mode = mode;
-        A.side = side;
-        A.nprob = cnt * nw;
-        A.out = out_dev;
-        A.info = info ? info_dev : nullptr;
-        A.fail = fail_dev;
-        rc = land_launch(ctx, A, ws, ws_groups);
-        if (rc) return rc;
-        if (mesh) {
-            ProfScope ps(ctx, "land_rows");
-            hipLaunchKernelGGL(k_opt_rows, dim3((unsigned)rows), dim3(256), 0, ctx->stream, (const double*)out_dev, (int)cnt, rows, 1.0,
-                               csum + c * rows);
-            TBK_HIP(hipGetLastError());
-        } else if (mode == 1) {
-            TBK_HIP(hipMemcpyAsync(out + first * nw * 2 * N * N, out_dev, (size_t)cnt * nw * mb, hipMemcpyDeviceToHost, ctx->stream));
-        } else {
-            TBK_HIP(hipMemcpyAsync(out + first * nw, out_dev, (size_t)cnt * nw * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-        }
-        if (info)
-            TBK_HIP(hipMemcpyAsync(info + first * nw, info_dev, (size_t)cnt * nw * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-        if (nchunk > 1) TBK_HIP(hipStreamSynchronize(ctx->stream));   // the next chunk reuses the buffers the copies read
-    }
-    if (mesh) {
-        ProfScope ps(ctx, "land_rows");
-        hipLaunchKernelGGL(k_opt_rows, dim3((unsigned)rows), dim3(256), 0, ctx->stream, (const double*)csum, (int)nchunk, rows,
-                           1.0 / (double)nk, csum + nchunk * rows);
-        TBK_HIP(hipGetLastError());
-        TBK_HIP(hipMemcpyAsync(out, csum + nchunk * rows, (size_t)rows * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    }
-    unsigned long long nfail = 0;
-    TBK_HIP(hipMemcpyAsync(&nfail, fail_dev, sizeof(nfail), hipMemcpyDeviceToHost, ctx->stream));
-    TBK_HIP(hipStreamSynchronize(ctx->stream));
-    TBK_REQUIRE(nfail == 0, TBK_ENOCONV, "%s: %llu of %lld (k, omega) points did not reach tol=%g within max_iter=%d decimation steps", who,
-                nfail, (long long)(nk * nw), tol, max_iter);
-    return TBK_OK;
+                who, (long long)nk, nw, M, N, P.total, kSgfMaxBytes);
+    static const char* const names[3] = {"land_n2", "land_wg_lds", "land_wg_global"};
+    return sgf_drive(
+        who, cut, P, k, omega, eta, tol, max_iter, out, info, "land_rows",
+        [&](const SgfChunk& C) {
+            if (dev) {
+                const int rb = land_blocks_launch(dev, C.k, C.cnt, N, M, C.extra);
+                if (rb) return rb;
+            }
+            LandArgs A{};
+            static_cast<SgfCommon&>(A) = C.args;
+            A.dblk = dev ? C.extra : nullptr;
+            A.M = M;
+            A.mode = mode;
+            A.side = side;
+            A.out = C.out;
+            return sgf_launch<LandArgs, k_land_n2, k_land_wg<false>, k_land_wg<true>>(cut->ctx, A, C.ws, P.ws_groups, names);
+        },
+        [&](const SgfChunk& C) -> int {
+            const size_t perw = mode == 1 ? mb : sizeof(double);   // bytes per (k, w): a whole Sigma, or T
+            TBK_HIP(hipMemcpyAsync((char*)out + C.first * nw * perw, C.out, (size_t)C.cnt * nw * perw, hipMemcpyDeviceToHost,
+                                   cut->ctx->stream));
+            return TBK_OK;
+        });
 }
 
 extern "C" int tbk_lead_self_energy_list(tbk_model* cut, int nlayer, const double* k, int64_t nk, int nomega, const double* omega,

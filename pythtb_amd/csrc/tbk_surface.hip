@@ -16,69 +16,34 @@
 //   N = 2        k_sgf_n2: a lane per problem, the matrices in registers, the 2 x 2 inverse in closed form
 //   N <= 32      k_sgf_wg<false>: seven N x (N + 1) matrices per problem in LDS, P problems of TP threads per 256-thread workgroup
 //   N <= 128     k_sgf_wg<true>: the same code, the seven matrices in a global workspace sized by the number of workgroups
-// The last stage of the same kernels inverts z - es, z - et, z - e and writes whole matrices, exposed-cell diagonals or their traces.
-// A problem's arithmetic depends on its own (k, w) alone -- a finished problem is masked off and only keeps its neighbours company at
-// the barriers -- so its bits do not depend on the batch, its position in it or the chunk.  The mesh mean sums per-k rows with the
-// fixed-order k_opt_rows of tbk_pairs.h.  No floating-point atomics anywhere.  (k_sgf_blocks, the elimination, the 2 x 2 helpers and
-// the launch shape are in tbk_sgf.h, which tbk_landauer.hip shares.)
+// The decimation itself is in tbk_sgf.h (sgf_decimate_n2, sgf_decimate_wg), which tbk_landauer.hip shares, with k_sgf_blocks, the
+// elimination, the launcher of the three regimes, the argument checks and the chunk driver.  This unit holds what follows the loop:
+// the last stage of the same kernels inverts z - es, z - et, z - e and writes whole matrices, exposed-cell diagonals or their
+// traces.  k_sgf_wg alone keeps the text of the shared workgroup functions in its body, for its speed (see the kernel).  A problem's arithmetic depends on its own (k, w) alone -- a finished problem is masked off and only keeps its
+// neighbours company at the barriers -- so its bits do not depend on the batch, its position in it or the chunk.  The mesh mean sums
+// per-k rows with the fixed-order k_opt_rows of tbk_pairs.h.  No floating-point atomics anywhere.
 #include <math.h>
 #include <string.h>
 #include "tbk_sgf.h"
 
-struct SgfArgs {
-    const cd* blk;        // [nk][2][N][N]: H00, H01 of the chunk's k points
-    const double* omega;  // [nw]
-    int nw, N, ns;        // frequencies, layer size, states of one unit cell
-    double eta, tol;
-    int max_iter;
+struct SgfArgs : SgfCommon {
+    int ns;               // states of one unit cell
     int mode;             // 0: G of `side`, out[p][N][N] c128; 1: traces, 2: diagonals of the exposed cell, all three sides
     int side;
-    int64_t nprob;        // nk nw, problem p = ik nw + iw
     double* out;
     int64_t s_side, s_k, s_w;   // modes 1, 2: value (side, ik, iw, q) at side s_side + ik s_k + iw s_w + q
-    int* info;            // [nprob] steps taken, or null
-    unsigned long long* fail;   // count of problems that missed a non-zero tol
 };
 
 // ---------------------------------------------------------------- N = 2: a lane per problem
 __global__ __launch_bounds__(256) void k_sgf_n2(const SgfArgs A) {
     const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (p >= A.nprob) return;
-    const int64_t ik = p / A.nw;
-    const int iw = (int)(p - ik * A.nw);
-    const cd* h = A.blk + ik * 8;
-    const M2 h0{h[0], h[1], h[2], h[3]};
-    M2 al{h[4], h[5], h[6], h[7]};
-    M2 be{cconj(al.a), cconj(al.c), cconj(al.b), cconj(al.d)};
-    M2 es = h0, et = h0;
-    const cd z{A.omega[iw], A.eta};
-    const double scale = sqrt(fmax(m2max(h0), m2max(al)));
-    double cur = sqrt(m2max(al));
-    int steps = 0;
-    bool conv = false;
-    for (;;) {
-        if (A.tol > 0.0 && cur <= A.tol * scale) {
-            conv = true;
-            break;
-        }
-        if (steps == A.max_iter) break;
-        const M2 g = m2resolvent(z, m2bulk(es, et, h0));
-        const M2 xa = m2mul(g, al), xb = m2mul(g, be);
-        m2acc(es, m2mul(al, xb));
-        m2acc(et, m2mul(be, xa));
-        const M2 na = m2mul(al, xa), nb = m2mul(be, xb);
-        al = na;
-        be = nb;
-        cur = sqrt(fmax(m2max(al), m2max(be)));
-        ++steps;
-    }
-    if (A.tol > 0.0 && !conv) atomicAdd(A.fail, 1ull);
-    if (A.info) A.info[p] = steps;
+    const Sgf2 D = sgf_decimate_n2(A, p);
     const double mpi = -1.0 / M_PI;
 #pragma unroll
     for (int s = 0; s < 3; ++s) {
         if (A.mode == 0 && s != A.side) continue;
-        const M2 G = m2resolvent(z, s == 0 ? es : (s == 1 ? et : m2bulk(es, et, h0)));
+        const M2 G = m2resolvent(D.z, s == 0 ? D.es : (s == 1 ? D.et : m2bulk(D.es, D.et, D.h0)));
         if (A.mode == 0) {
             cd* o = (cd*)A.out + p * 4;
             o[0] = G.a;
@@ -87,7 +52,7 @@ __global__ __launch_bounds__(256) void k_sgf_n2(const SgfArgs A) {
             o[3] = G.d;
             continue;
         }
-        double* o = A.out + s * A.s_side + ik * A.s_k + iw * A.s_w;
+        double* o = A.out + s * A.s_side + D.ik * A.s_k + D.iw * A.s_w;
         // the exposed cell: ns = 2 the whole layer; ns = 1 (L = 2) state 0, or state 1 on side 1
         const double d0 = mpi * G.a.y, d1 = mpi * G.d.y;
         if (A.ns == 2) {
@@ -100,6 +65,9 @@ __global__ __launch_bounds__(256) void k_sgf_n2(const SgfArgs A) {
 }
 
 // ---------------------------------------------------------------- N != 2: TP threads per problem, matrices in LDS or in a workspace
+// This kernel keeps the text of sgf_problem, sgf_decimate_wg and sgf_resolve (tbk_sgf.h) instead of calling them: built from the calls
+// the LDS regime measured 0.4 .. 1.2 % slower.  The loop must stay that of sgf_decimate_wg, statement for
+// statement; tests/test_landauer.py compares the step counts of the two.
 template <bool GLOBAL>
 __global__ __launch_bounds__(256) void k_sgf_wg(const SgfArgs A, const int P, const int tp_log, const int ld, cd* ws) {
     extern __shared__ cd sgf_lds[];
@@ -230,34 +198,6 @@ __global__ __launch_bounds__(256) void k_sgf_wg(const SgfArgs A, const int P, co
 }
 
 // ---------------------------------------------------------------- host side
-static int sgf_launch(tbk_ctx* ctx, const SgfArgs& A, cd* ws, int ws_groups) {
-    if (A.N == 2) {
-        ProfScope ps(ctx, "sgf_n2");
-        hipLaunchKernelGGL(k_sgf_n2, dim3(nblk(A.nprob)), dim3(256), 0, ctx->stream, A);
-        TBK_HIP(hipGetLastError());
-        return TBK_OK;
-    }
-    const SgfShape S = sgf_shape(A.N);
-    if (S.global) {
-        ProfScope ps(ctx, "sgf_wg_global");
-        const unsigned grid = (unsigned)std::min<int64_t>(A.nprob, ws_groups);
-        hipLaunchKernelGGL(k_sgf_wg<true>, dim3(grid), dim3(256), 0, ctx->stream, A, 1, S.tp_log, S.ld, ws);
-        TBK_HIP(hipGetLastError());
-        return TBK_OK;
-    }
-    ProfScope ps(ctx, "sgf_wg_lds");
-    static bool big_lds = false;                           // the attribute belongs to the function: set once per process
-    if (S.lds > 64 * 1024 && !big_lds) {
-        TBK_HIP(hipFuncSetAttribute((const void*)k_sgf_wg<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-        big_lds = true;
-    }
-    const int64_t ngroups = (A.nprob + S.P - 1) / S.P;
-    const unsigned grid = (unsigned)std::min<int64_t>(ngroups, (int64_t)std::max(ctx->cus, 1) * 32);
-    hipLaunchKernelGGL(k_sgf_wg<false>, dim3(grid), dim3(256), S.lds, ctx->stream, A, S.P, S.tp_log, S.ld, (cd*)nullptr);
-    TBK_HIP(hipGetLastError());
-    return TBK_OK;
-}
-
 extern "C" int tbk_surface_blocks(tbk_model* cut, int nlayer, const double* k, int64_t nk, double* h00, double* h01) {
     int rc = sgf_check_model("tbk_surface_blocks", cut, nlayer, nlayer);
     if (rc) return rc;
@@ -282,124 +222,47 @@ extern "C" int tbk_surface_blocks(tbk_model* cut, int nlayer, const double* k, i
     return TBK_OK;
 }
 
-// k points per chunk: a function of (N, nk, nw, mode, cell) alone
-static int64_t sgf_chunk_len(int N, int64_t nk, int nw, int mode, int ns) {
-    const size_t perk = (size_t)2 * N * N * sizeof(cd) + (size_t)nw * sizeof(int) +
-                        (mode == 0 ? (size_t)nw * N * N * sizeof(cd) : (size_t)3 * nw * (mode == 2 ? ns : 1) * sizeof(double));
-    const int64_t c = std::min<int64_t>((int64_t)(kSgfChunkBytes / perk), kSgfChunkProblems / nw);
-    return std::max<int64_t>(1, std::min<int64_t>(nk, c));
-}
-
 // the list forms (mesh == null: k[nk][dim_k] from the host) and the mesh mean (mesh given: k_uniform_mesh(mesh) generated per chunk)
 static int sgf_run(const char* who, tbk_model* cut, int N, int ns, const double* k, int64_t nk, const int32_t* mesh, int nw,
                    const double* omega, double eta, double tol, int max_iter, int mode, int side, double* out, int32_t* info) {
-    TBK_REQUIRE(omega && out, TBK_EINVAL, "%s: null argument", who);
-    TBK_REQUIRE(nw >= 1 && nw <= 65536, TBK_EINVAL, "%s: nomega=%d (1..65536 frequencies)", who, nw);
-    for (int j = 0; j < nw; ++j) TBK_REQUIRE(std::isfinite(omega[j]), TBK_EINVAL, "%s: frequency %d is not finite", who, j);
-    TBK_REQUIRE(std::isfinite(eta) && eta > 0.0, TBK_EINVAL, "%s: eta must be finite and > 0", who);
-    TBK_REQUIRE(std::isfinite(tol) && tol >= 0.0, TBK_EINVAL, "%s: tol must be finite and >= 0", who);
-    TBK_REQUIRE(max_iter >= 0 && max_iter <= 64, TBK_EINVAL, "%s: max_iter=%d (0..64)", who, max_iter);
-    TBK_REQUIRE(mode >= 0 && mode <= 2 && side >= 0 && side <= 2, TBK_EINVAL, "%s: mode %d, side %d", who, mode, side);
-    TBK_REQUIRE(nk >= 1, TBK_EINVAL, "%s: no k point", who);
-    tbk_ctx* ctx = cut->ctx;
-    TBK_HIP(hipSetDevice(ctx->device));
-    const int dk = cut->dim_k, nv = mode == 2 ? ns : 1;
-    const int64_t chunk = sgf_chunk_len(N, nk, nw, mode, ns), nchunk = (nk + chunk - 1) / chunk;
-    const int64_t rows = (int64_t)3 * nw * nv;             // values per k point of modes 1, 2
-    const SgfShape S = sgf_shape(N);
-    const int ws_groups = (int)std::min<int64_t>(std::max(ctx->cus, 1), chunk * nw);   // the grid of the workspace regime
-    const size_t omb = al256((size_t)nw * sizeof(double));
-    const size_t kb = al256((size_t)(mesh ? chunk : nk) * std::max(dk, 1) * sizeof(double));
-    const size_t bb = al256((size_t)chunk * 2 * N * N * sizeof(cd));
-    const size_t ob = al256(mode == 0 ? (size_t)chunk * nw * N * N * sizeof(cd) : (size_t)chunk * rows * sizeof(double));
-    const size_t ib = al256((size_t)chunk * nw * sizeof(int));
-    const size_t cb = mesh ? al256((size_t)(nchunk + 1) * rows * sizeof(double)) : 0;
-    const size_t wb = S.global && N != 2 ? (size_t)ws_groups * 7 * N * S.ld * sizeof(cd) : 0;
-    const size_t total = 512 + omb + kb + bb + ob + ib + cb + wb;
-    TBK_REQUIRE(total <= kSgfMaxBytes, TBK_EUNSUPPORTED,
-                "%s: %d frequencies of a layer of %d states need %zu bytes of results per k point (at most %zu per call): split omega", who,
-                nw, N, ob / (size_t)chunk, kSgfMaxBytes);
-    void* base = nullptr;
-    int rc = tbk_ctx_scratch(ctx, total, &base);
+    int rc = sgf_check_call(who, nw, omega, eta, tol, max_iter, out);
     if (rc) return rc;
-    unsigned char* q = (unsigned char*)base + 256;
-    unsigned long long* fail_dev = (unsigned long long*)q;
-    q += 256;
-    double* om_dev = (double*)q;
-    q += omb;
-    double* k_dev = (double*)q;
-    q += kb;
-    cd* blk = (cd*)q;
-    q += bb;
-    double* out_dev = (double*)q;
-    q += ob;
-    int* info_dev = (int*)q;
-    q += ib;
-    double* csum = (double*)q;                             // [nchunk][rows] chunk sums, then [rows] the mean
-    q += cb;
-    cd* ws = (cd*)q;
-    TBK_HIP(hipMemsetAsync(fail_dev, 0, sizeof(unsigned long long), ctx->stream));
-    TBK_HIP(hipMemcpyAsync(om_dev, omega, (size_t)nw * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    if (!mesh && dk > 0) TBK_HIP(hipMemcpyAsync(k_dev, k, (size_t)nk * dk * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    for (int64_t c = 0; c < nchunk; ++c) {
-        const int64_t first = c * chunk, cnt = std::min(chunk, nk - first);
-        const double* kc = k_dev + (mesh ? 0 : first * dk);
-        if (mesh) {
-            rc = tbk_k_uniform_mesh_range_dev(ctx, dk, mesh, first, cnt, k_dev);
-            if (rc) return rc;
-        }
-        rc = sgf_blocks_launch(cut, kc, cnt, N, blk);
-        if (rc) return rc;
-        SgfArgs A{};
-        A.blk = blk;
-        A.omega = om_dev;
-        A.nw = nw;
-        A.N = N;
-        A.ns = ns;
-        A.eta = eta;
-        A.tol = tol;
-        A.max_iter = max_iter;
-        A.mode = mode;
-        A.side = side;
-        A.nprob = cnt * nw;
-        A.out = out_dev;
-        A.s_w = nv;
-        if (mesh) A.s_k = rows, A.s_side = (int64_t)nw * nv;      // part[k][side][w][q]
-        else A.s_k = (int64_t)nw * nv, A.s_side = cnt * nw * nv;  // [side][k][w][q] of the chunk
-        A.info = info ? info_dev : nullptr;
-        A.fail = fail_dev;
-        rc = sgf_launch(ctx, A, ws, ws_groups);
-        if (rc) return rc;
-        if (mesh) {
-            ProfScope ps(ctx, "sgf_rows");
-            hipLaunchKernelGGL(k_opt_rows, dim3((unsigned)rows), dim3(256), 0, ctx->stream, (const double*)out_dev, (int)cnt, rows, 1.0,
-                               csum + c * rows);
-            TBK_HIP(hipGetLastError());
-        } else if (mode == 0) {
-            TBK_HIP(hipMemcpyAsync(out + first * nw * 2 * N * N, out_dev, (size_t)cnt * nw * N * N * sizeof(cd), hipMemcpyDeviceToHost,
-                                   ctx->stream));
-        } else {
+    TBK_REQUIRE(mode >= 0 && mode <= 2 && side >= 0 && side <= 2, TBK_EINVAL, "%s: mode %d, side %d", who, mode, side);
+    const int nv = mode == 2 ? ns : 1;
+    const int64_t rows = (int64_t)3 * nw * nv;             // values per k point of modes 1, 2
+    SgfPlan P;
+    rc = sgf_plan(who, cut, N, nk, mesh, nw, 0, mode == 0 ? (size_t)nw * N * N * sizeof(cd) : (size_t)rows * sizeof(double), rows, P);
+    if (rc) return rc;
+    TBK_REQUIRE(P.total <= kSgfMaxBytes, TBK_EUNSUPPORTED,
+                "%s: %d frequencies of a layer of %d states need %zu bytes of results per k point (at most %zu per call): split omega", who,
+                nw, N, P.ob / (size_t)P.chunk, kSgfMaxBytes);
+    static const char* const names[3] = {"sgf_n2", "sgf_wg_lds", "sgf_wg_global"};
+    return sgf_drive(
+        who, cut, P, k, omega, eta, tol, max_iter, out, info, "sgf_rows",
+        [&](const SgfChunk& C) {
+            SgfArgs A{};
+            static_cast<SgfCommon&>(A) = C.args;
+            A.ns = ns;
+            A.mode = mode;
+            A.side = side;
+            A.out = C.out;
+            A.s_w = nv;
+            if (mesh) A.s_k = rows, A.s_side = (int64_t)nw * nv;        // part[k][side][w][q]
+            else A.s_k = (int64_t)nw * nv, A.s_side = C.cnt * nw * nv;  // [side][k][w][q] of the chunk
+            return sgf_launch<SgfArgs, k_sgf_n2, k_sgf_wg<false>, k_sgf_wg<true>>(cut->ctx, A, C.ws, P.ws_groups, names);
+        },
+        [&](const SgfChunk& C) -> int {
+            hipStream_t st = cut->ctx->stream;
+            if (mode == 0) {
+                TBK_HIP(hipMemcpyAsync(out + C.first * nw * 2 * N * N, C.out, (size_t)C.cnt * nw * N * N * sizeof(cd), hipMemcpyDeviceToHost,
+                                       st));
+                return TBK_OK;
+            }
             for (int s = 0; s < 3; ++s)
-                TBK_HIP(hipMemcpyAsync(out + (s * nk + first) * nw * nv, out_dev + s * A.s_side, (size_t)cnt * nw * nv * sizeof(double),
-                                       hipMemcpyDeviceToHost, ctx->stream));
-        }
-        if (info)
-            TBK_HIP(hipMemcpyAsync(info + first * nw, info_dev, (size_t)cnt * nw * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-        if (nchunk > 1) TBK_HIP(hipStreamSynchronize(ctx->stream));   // the next chunk reuses the buffers the copies read
-    }
-    if (mesh) {
-        ProfScope ps(ctx, "sgf_rows");
-        hipLaunchKernelGGL(k_opt_rows, dim3((unsigned)rows), dim3(256), 0, ctx->stream, (const double*)csum, (int)nchunk, rows,
-                           1.0 / (double)nk, csum + nchunk * rows);
-        TBK_HIP(hipGetLastError());
-        TBK_HIP(hipMemcpyAsync(out, csum + nchunk * rows, (size_t)rows * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    }
-    unsigned long long nfail = 0;
-    TBK_HIP(hipMemcpyAsync(&nfail, fail_dev, sizeof(nfail), hipMemcpyDeviceToHost, ctx->stream));
-    TBK_HIP(hipStreamSynchronize(ctx->stream));
-    TBK_REQUIRE(nfail == 0, TBK_ENOCONV, "%s: %llu of %lld (k, omega) points did not reach tol=%g within max_iter=%d decimation steps", who,
-                nfail, (long long)(nk * nw), tol, max_iter);
-    return TBK_OK;
+                TBK_HIP(hipMemcpyAsync(out + (s * nk + C.first) * nw * nv, C.out + s * C.cnt * nw * nv, (size_t)C.cnt * nw * nv * sizeof(double),
+                                       hipMemcpyDeviceToHost, st));
+            return TBK_OK;
+        });
 }
 
 extern "C" int tbk_surface_green_list(tbk_model* cut, int nlayer, int ncell, const double* k, int64_t nk, int nomega,

@@ -454,6 +454,25 @@ def test_a_point_does_not_depend_on_its_batch(gpu_ctx, name):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("name", ["haldane0", "kane_mele", "rand2d_spin", "cubic16", "n36"])
+@pytest.mark.parametrize("stop", [{}, dict(tol=0.0, max_iter=3)])
+def test_leads_and_surface_run_one_decimation(gpu_ctx, name, stop):
+    """The surface unit and this one must decimate alike (the surface unit's workgroup kernel holds a copy of the shared loop): the
+    step counts of the two are the same integers at every point, in every storage regime (a lane per problem, P = 16, P = 4, 256
+    threads per problem, the workspace).  It guards against the two drifting apart later; it holds before the code was shared too."""
+    m, fd = model(name)
+    k, om, eta = kpts(name, 7), OMEGA13, eta_of(name)
+    _, surface = m.surface_spectral(k, om, eta, fd, return_info=True, **stop)
+    _, leads = m.transmission(k, om, eta, fd, return_info=True, **stop)
+    assert surface.shape == leads.shape == (7, 13) and surface.dtype == leads.dtype == np.int32
+    assert np.array_equal(surface, leads)
+    if stop:
+        assert np.all(leads == 3)
+    else:
+        assert leads.min() >= 1 and leads.max() < 50
+
+
+@pytest.mark.gpu
 def test_a_point_across_the_chunk_boundary(gpu_ctx):
     """A chunk holds at most 2^20 (k, omega) problems: 17 k x 65 536 omega of the Haldane model are two chunks (16 k + 1 k)."""
     m, fd = model("haldane0")
