@@ -284,6 +284,17 @@ int tbk_berry_curv_list(tbk_model* model, const double* k, int64_t nk, int dir0,
 int tbk_berry_curv_mesh(tbk_model* model, const int32_t* mesh, int dir0, int dir1, const int32_t* occ,
                         int nocc, int nmu, const double* mu, double* out);
 
+/* ---- quantum geometric tensor and quantum metric by the Kubo formula ----------
+ * Q_ab = g_ab - i Omega_ab / 2 over ALL axes a, b in [0, dim_k), dim_k 1..3: the real part of the sum whose imaginary part is
+ * tbk_berry_curv_list's.  occ == NULL: per band, Q^n_ab = sum_{m != n} V^a_nm V^b_mn / (E_n - E_m)^2 with the degeneracy rule of
+ * tbk_berry_curv_list; otherwise the band set occ[nocc] (distinct, in [0, nsta)), the sum over n in occ, m not in occ.
+ * A (band or set, point) result is dim_k^2 doubles: g_ab for a <= b in row-major upper-triangle order, then Omega_ab for a < b
+ * in the same order.  tbk_qgt_list: out[nsta][nk][dim_k^2] per band, out[nk][dim_k^2] for a set.
+ * tbk_qgt_mesh: the means over the whole k_uniform_mesh(mesh) (mesh[d] >= 1, generated on the device), out[nsta][dim_k^2] or
+ * out[dim_k^2].  Fixed-shape reductions: bit-reproducible.                                                         */
+int tbk_qgt_list(tbk_model* model, const double* k, int64_t nk, const int32_t* occ, int nocc, double* out);
+int tbk_qgt_mesh(tbk_model* model, const int32_t* mesh, const int32_t* occ, int nocc, double* out);
+
 /* ---- spin Berry curvature and spin Hall conductivity by the Kubo formula ----------
  * For a model with nspin = 2 (state = 2 orbital + spin).  Sigma_s = 1_orb (x) (s.sigma) for the real vector spin[3] (used as
  * given, not normalised; every result is linear in it), J^{s,a} = (Sigma_s d_a H + d_a H Sigma_s) / 2 the spin current:

@@ -97,6 +97,8 @@ SIGNATURES = {
     "tbk_gen_dham": (_i, [_p, _dp, _i64, _i, _dp]),
     "tbk_berry_curv_list": (_i, [_p, _dp, _i64, _i, _i, _ip, _i, _dp]),
     "tbk_berry_curv_mesh": (_i, [_p, _ip, _i, _i, _ip, _i, _i, _dp, _dp]),
+    "tbk_qgt_list": (_i, [_p, _dp, _i64, _ip, _i, _dp]),
+    "tbk_qgt_mesh": (_i, [_p, _ip, _ip, _i, _dp]),
     "tbk_gen_jham": (_i, [_p, _dp, _i64, _i, _dp, _dp]),
     "tbk_spin_curv_list": (_i, [_p, _dp, _i64, _i, _i, _ip, _i, _dp, _dp]),
     "tbk_spin_curv_mesh": (_i, [_p, _ip, _i, _i, _ip, _i, _i, _dp, _dp, _dp]),

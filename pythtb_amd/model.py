@@ -531,6 +531,85 @@ class tb_model(object):
             return float(out[0]) if sel is not None else out
         return out[0] if sel is not None else out
 
+    # ------------------------------------------------------------------ quantum geometric tensor (extensions)
+    def _qgt_args(self, occ):
+        """Checked band set of the quantum-geometry calls (int32 indices or None); `occ` is read as `_curv_args` reads it."""
+        if self._dim_k not in (1, 2, 3):
+            raise Exception("\n\nThe quantum geometric tensor needs a model with dim_k 1, 2 or 3.")
+        if occ is None:
+            return None
+        sel = np.arange(self._nsta)[occ]                 # a NumPy fancy index (IndexError)
+        sel = np.atleast_1d(sel).ravel()
+        if sel.size == 0:
+            raise Exception("\n\nocc selects no band.")
+        if np.unique(sel).size != sel.size:
+            raise Exception("\n\nocc lists a band twice.")
+        return np.ascontiguousarray(sel, dtype=np.int32)
+
+    def _qgt_assemble(self, raw):
+        """Hermitian Q = g - i Omega / 2, `(..., dk, dk)` complex, from the library's `(..., dk^2)` doubles: g_ab for a <= b in
+        `np.triu_indices(dk)` order, then Omega_ab for a < b in the same order."""
+        dk = self._dim_k
+        iu = np.triu_indices(dk)
+        io = np.triu_indices(dk, 1)
+        ng = len(iu[0])
+        q = np.zeros(raw.shape[:-1] + (dk, dk), dtype=complex)
+        q[..., iu[0], iu[1]] = raw[..., :ng]
+        q[..., iu[1], iu[0]] = raw[..., :ng]
+        q[..., io[0], io[1]] -= 0.5j * raw[..., ng:]
+        q[..., io[1], io[0]] += 0.5j * raw[..., ng:]
+        return q
+
+    def quantum_geometric_tensor(self, k_list, occ=None):
+        """Extension: the quantum geometric tensor by the Kubo formula at every k of `k_list` (reduced coordinates, as
+        solve_all), over all dk = dim_k axes (1, 2 or 3) at once, complex128.
+
+        occ=None: per band, `(nsta, nk, dk, dk)`,
+            Q^n_ab(k) = sum_{m != n} <n|dH_a|m><m|dH_b|n> / (E_n - E_m)^2;
+            a pair with |E_n - E_m| <= 1e-9 max(1, |E_n|, |E_m|) contributes to neither band (the rule of `berry_curvature`).
+        occ given (a NumPy index of bands): the band set's tensor `(nk, dk, dk)`, the sum over n in occ and m not in occ of the
+            same terms (no degeneracy rule) = Tr[P d_aP d_bP]: gauge invariant inside the set, and not finite where the set
+            touches a band outside it.
+        Q is Hermitian and positive semidefinite, Q = g - i Omega / 2: g_ab = Re Q_ab is the quantum metric (`quantum_metric`) and
+        Omega_ab = -2 Im Q_ab is `berry_curvature(..., dirs=(a, b))`.
+        There is no Fermi-level scan, on purpose: sum_{n in occ} Q^n is NOT Q^occ for the real part -- the pairs of two
+        occupied bands cancel in Omega but count twice in g -- so a scan built from per-band sums would be wrong."""
+        sel = self._qgt_args(occ)
+        k = self._k_array(k_list)
+        nk, n, dk = k.shape[0], self._nsta, self._dim_k
+        raw = np.zeros((nk, dk * dk) if sel is not None else (n, nk, dk * dk), dtype=float)
+        if nk > 0:
+            _lib.check(_lib.lib.tbk_qgt_list(self._device_model(), _lib.dptr(k), nk, _lib.iptr(sel),
+                                             0 if sel is None else len(sel), _lib.dptr(raw)))
+        return self._qgt_assemble(raw)
+
+    def quantum_metric(self, k_list, occ=None):
+        """Extension: the quantum metric g_ab = Re Q_ab of `quantum_geometric_tensor(k_list, occ)` as float64, same shapes:
+        `(nsta, nk, dk, dk)` per band or `(nk, dk, dk)` for a band set.  No Fermi-level scan (see there)."""
+        return np.ascontiguousarray(self.quantum_geometric_tensor(k_list, occ).real)
+
+    def quantum_geometric_tensor_mesh(self, mesh_size, occ=None, cartesian=False):
+        """Extension: the mean of `quantum_geometric_tensor` over the whole `k_uniform_mesh(mesh_size)` (1-, 2- or 3-D, generated
+        on the device): complex `(nsta, dk, dk)` per band, `(dk, dk)` for a band set.  -2 Im of its (a, b) entry is the mean
+        curvature (2 pi times the Chern number of a gapped set in 2-D).
+        cartesian=True returns A^T Q A / (2 pi)^2, `(..., dim_r, dim_r)`, with the A of `drude_weight_mesh` (the periodic
+        lattice vectors as rows): its real trace is the band set's gauge-invariant Wannier spread Omega_I per cell, in the
+        squared length unit of the lattice vectors.  Fixed-order reductions: two calls give the same bits.  No Fermi-level
+        scan (see `quantum_geometric_tensor`)."""
+        sel = self._qgt_args(occ)
+        if not isinstance(cartesian, (bool, np.bool_)):
+            raise Exception("\n\ncartesian must be True or False.")
+        mesh, nk = self._mesh_arg(mesh_size)
+        n, dk = self._nsta, self._dim_k
+        raw = np.zeros((dk * dk,) if sel is not None else (n, dk * dk), dtype=float)
+        _lib.check(_lib.lib.tbk_qgt_mesh(self._device_model(), _lib.iptr(mesh), _lib.iptr(sel), 0 if sel is None else len(sel),
+                                         _lib.dptr(raw)))
+        q = self._qgt_assemble(raw)
+        if not cartesian:
+            return q
+        a = np.array(self._lat, dtype=float)[self._per]               # (dim_k, dim_r)
+        return np.einsum("ia,...ij,jb->...ab", a, q, a) / (2.0 * np.pi) ** 2
+
     # ------------------------------------------------------------------ spin Berry curvature (extensions)
     def _spin_arg(self, spin, what):
         """Checked spin direction of the spin-current calls as a float64 3-vector: 0, 1 or 2 (sigma_x, sigma_y, sigma_z) or a
