@@ -441,6 +441,35 @@ int tbk_transmission_list(tbk_model* cut, tbk_model* dev /* null: one pristine l
 int tbk_transmission_mesh(tbk_model* cut, tbk_model* dev, int nlayer, int nlayers, const int32_t* mesh, int nomega,
                           const double* omega, double eta, double tol, int max_iter, double* out);
 
+/* ---- kernel polynomial method: Chebyshev moments of the sparse H(k), any number of states ----------
+ * No reference counterpart.  The tables are those of tbk_model_upload; the operator is CSR over the states (nsta = norb nspin rows, no
+ * TBK_MAX_NSTA limit): the on-site blocks, every hop and its Hermitian conjugate, spin blocks expanded to scalar entries, entries with
+ * the same (row, col, R) summed, exact zeros dropped, (col, R) ascending within a row.  The value of an entry at k is
+ * amp exp(2 pi i k.(R + orb_col - orb_row)) (_gen_ham, pythtb.py:874-925).  The Gershgorin interval [min_i (d_i - r_i),
+ * max_i (d_i + r_i)], d_i the real R = 0 diagonal entry and r_i the sum of the moduli of the other entries of row i, contains the
+ * spectrum at every k.
+ * tbk_sparse_flatten_host: host only (no device call).  *nnz = number of entries (call with cap = 0 to size); with cap >= *nnz,
+ * row_ptr[nsta + 1], col[nnz], ent_R[nnz][4] (zero-padded beyond dim_k), ent_amp[nnz] c128; gershgorin[2] (nullable).          */
+typedef struct tbk_sparse tbk_sparse;
+int tbk_sparse_flatten_host(int dim_k, int norb, int nspin, const double* orb, const double* onsite, int64_t nhop,
+                            const int32_t* hop_i, const int32_t* hop_j, const int32_t* hop_R, const double* hop_amp, int64_t cap,
+                            int64_t* nnz, int64_t* row_ptr, int32_t* col, int32_t* ent_R, double* ent_amp, double* gershgorin);
+int tbk_sparse_upload(tbk_ctx* ctx, int dim_k, int norb, int nspin, const double* orb, const double* onsite, int64_t nhop,
+                      const int32_t* hop_i, const int32_t* hop_j, const int32_t* hop_R, const double* hop_amp, tbk_sparse** out);
+int tbk_sparse_free(tbk_sparse* sp);
+int tbk_sparse_info(tbk_sparse* sp, int* dim_k, int* nsta, int64_t* nnz, double* gershgorin);
+/* Random-phase vectors number first .. first + count - 1 of `seed`: out[count][nsta] c128, element i of vector g = e^{i phi}, phi a pure
+ * function of (seed, g, i) (a counter-based generator: independent of the launch and of how many vectors a call asks for).       */
+int tbk_kpm_vectors(tbk_sparse* sp, uint64_t seed, int64_t first, int64_t count, double* out);
+/* mu[nk][nvec][n_moments] = <v|T_m(H~(k))|v> / <v|v>, H~ = (H - b) / a with a = (emax - emin) / 2, b = (emax + emin) / 2, by the
+ * recursion alpha_m+1 = 2 H~ alpha_m - alpha_m-1 and the identities mu_2m = 2 <alpha_m|alpha_m> - mu_0, mu_2m+1 = 2 <alpha_m+1|alpha_m>
+ * - mu_1: n_moments / 2 sparse products per block of 8 vectors.  k[nk][dim_k] (dim_k = 0: ignored, nk = 1).  Start vectors:
+ * vectors[nvec][nsta] c128, or the unit vectors at states[nvec], or (both null) the random-phase vectors number q nvec + v of `seed`
+ * for the k-point with index q.  TBK_EINVAL, naming the bounds, when a moment is not finite or exceeds 1 + 1e-6 in modulus: (emin,
+ * emax) does not contain the spectrum.  Fixed-order sums, no atomics on floating-point data: bit-reproducible.                  */
+int tbk_kpm_moments(tbk_sparse* sp, const double* k, int64_t nk, int n_moments, double emin, double emax, int nvec,
+                    const double* vectors, const int32_t* states, uint64_t seed, double* mu);
+
 /* ---- multi-GPU: one process per GPU, k-points sharded, one gather ------
  * Thin RCCL wrappers (librccl is dlopen'ed on first use).  The 128-byte id is
  * created on rank 0 and distributed by the launcher (any out-of-band channel). */

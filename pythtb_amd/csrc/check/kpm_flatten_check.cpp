@@ -1,0 +1,135 @@
+// Stand-alone host check of tbk_sparse_flatten_host (no device call): built with the host code of tbk_kpm.hip under
+// AddressSanitizer + UBSan by `make -C pythtb_amd/csrc kpm-check` and run as an ordinary program.  Two tables: the spinless
+// Haldane cell (dim_k = 2) and a spinful three-orbital molecule (dim_k = 0) with a repeated hop, an R = 0 self-pair and an
+// isolated zero-energy orbital.  It expands the CSR table to a dense matrix, compares with the matrix built from the definition
+// (ham[i,s,j,t] += amp e^{2 pi i k.(R + tau_j - tau_i)}, plus the Hermitian conjugate), and checks the structure.
+#include <complex>
+#include <cstdarg>
+#include <cstdio>
+#include <cstdlib>
+#include <vector>
+#include "../tbk_internal.h"
+
+// what tbk_kpm.hip takes from tbk_core.hip (this program links the one translation unit alone)
+static char g_err[512];
+void tbk_set_error(const char* fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(g_err, sizeof g_err, fmt, ap);
+    va_end(ap);
+}
+int tbk_ctx_scratch(tbk_ctx*, size_t, void**) { return TBK_EHIP; }
+ProfScope::ProfScope(tbk_ctx* c, const char* n) : ctx(c), name(n) {}
+ProfScope::~ProfScope() {}
+
+typedef std::complex<double> cplx;
+
+struct Table {
+    int dim_k, norb, nspin;
+    std::vector<double> orb, onsite, hop_amp;
+    std::vector<int32_t> hop_i, hop_j, hop_R;
+};
+
+static int check(const Table& t, const double* k, const char* name) {
+    const int ns = t.nspin, n = t.norb * ns, dk = t.dim_k;
+    const int64_t nhop = (int64_t)t.hop_i.size();
+    int64_t nnz = -1;
+    double gersh[2] = {0.0, 0.0};
+    int rc = tbk_sparse_flatten_host(dk, t.norb, ns, t.orb.data(), t.onsite.data(), nhop, t.hop_i.data(), t.hop_j.data(),
+                                     t.hop_R.data(), t.hop_amp.data(), 0, &nnz, nullptr, nullptr, nullptr, nullptr, gersh);
+    if (rc || nnz < 0) return printf("%s: sizing call failed: %s\n", name, g_err), 1;
+    std::vector<int64_t> row_ptr(n + 1, -1);
+    std::vector<int32_t> col(nnz, -1), R(4 * nnz, 99);
+    std::vector<double> amp(2 * nnz, 0.0);
+    rc = tbk_sparse_flatten_host(dk, t.norb, ns, t.orb.data(), t.onsite.data(), nhop, t.hop_i.data(), t.hop_j.data(), t.hop_R.data(),
+                                 t.hop_amp.data(), nnz, &nnz, row_ptr.data(), col.data(), R.data(), amp.data(), gersh);
+    if (rc) return printf("%s: %s\n", name, g_err), 1;
+    auto phase = [&](int a, int b, const int32_t* Rv, int sign) {
+        double x = 0.0;
+        for (int d = 0; d < dk; ++d) x += k[d] * (sign * Rv[d] + t.orb[(b / ns) * dk + d] - t.orb[(a / ns) * dk + d]);
+        return std::polar(1.0, 2.0 * M_PI * x);
+    };
+    std::vector<cplx> ref((size_t)n * n), got((size_t)n * n);
+    for (int o = 0; o < t.norb; ++o)
+        for (int s = 0; s < ns; ++s)
+            for (int u = 0; u < ns; ++u) {
+                const double* p = &t.onsite[2 * ((o * ns + s) * ns + u)];
+                ref[(size_t)(o * ns + s) * n + o * ns + u] += cplx(p[0], p[1]);
+            }
+    for (int64_t h = 0; h < nhop; ++h)
+        for (int s = 0; s < ns; ++s)
+            for (int u = 0; u < ns; ++u) {
+                const double* p = &t.hop_amp[2 * ((h * ns + s) * ns + u)];
+                const int a = t.hop_i[h] * ns + s, b = t.hop_j[h] * ns + u;
+                const int32_t* Rv = dk ? &t.hop_R[h * dk] : nullptr;
+                ref[(size_t)a * n + b] += cplx(p[0], p[1]) * phase(a, b, Rv, 1);
+                ref[(size_t)b * n + a] += cplx(p[0], -p[1]) * phase(b, a, Rv, -1);
+            }
+    int bad = 0;
+    if (row_ptr[0] != 0 || row_ptr[n] != nnz) bad++;
+    for (int a = 0; a < n; ++a) {
+        if (row_ptr[a + 1] < row_ptr[a]) bad++;
+        for (int64_t e = row_ptr[a]; e < row_ptr[a + 1]; ++e) {
+            if (col[e] < 0 || col[e] >= n) {
+                bad++;
+                continue;
+            }
+            if (e > row_ptr[a]) {      // (col, R) strictly ascending
+                int c = col[e - 1] < col[e] ? -1 : (col[e - 1] > col[e] ? 1 : 0);
+                for (int d = 0; d < 4 && c == 0; ++d) c = R[4 * (e - 1) + d] < R[4 * e + d] ? -1 : (R[4 * (e - 1) + d] > R[4 * e + d] ? 1 : 0);
+                if (c >= 0) bad++;
+            }
+            got[(size_t)a * n + col[e]] += cplx(amp[2 * e], amp[2 * e + 1]) * phase(a, col[e], &R[4 * e], 1);
+        }
+    }
+    double err = 0.0, big = 0.0;
+    for (size_t i = 0; i < ref.size(); ++i) {
+        err = std::max(err, std::abs(ref[i] - got[i]));
+        big = std::max(big, std::abs(ref[i]));
+    }
+    printf("%s: n = %d, nnz = %lld, Gershgorin (%g, %g), |csr - dense| = %.2e of %.2e, structure faults %d\n", name, n, (long long)nnz,
+           gersh[0], gersh[1], err, big, bad);
+    return (bad || !(err <= 1e-14 * big) || !(gersh[0] < gersh[1])) ? 1 : 0;
+}
+
+int main() {
+    int fail = 0;
+    {
+        Table t{2, 2, 1, {1.0 / 3, 1.0 / 3, 2.0 / 3, 2.0 / 3}, {-0.2, 0.0, 0.2, 0.0}, {}, {}, {}, {}};
+        const double t2[2] = {0.0, 0.15};
+        const int hops[9][4] = {{0, 1, 0, 0}, {1, 0, 1, 0}, {1, 0, 0, 1}, {0, 0, 1, 0}, {1, 1, 1, -1}, {1, 1, 0, 1}, {1, 1, 1, 0}, {0, 0, 1, -1}, {0, 0, 0, 1}};
+        for (int h = 0; h < 9; ++h) {
+            t.hop_i.push_back(hops[h][0]);
+            t.hop_j.push_back(hops[h][1]);
+            t.hop_R.push_back(hops[h][2]);
+            t.hop_R.push_back(hops[h][3]);
+            t.hop_amp.push_back(h < 3 ? -1.0 : t2[0]);
+            t.hop_amp.push_back(h < 3 ? 0.0 : (h < 6 ? t2[1] : -t2[1]));
+        }
+        const double k[2] = {0.137, 0.731};
+        fail += check(t, k, "haldane");
+    }
+    {
+        Table t{0, 3, 2, {}, {}, {}, {}, {}, {}};
+        const double on[3][8] = {{0.5, 0, 0.1, -0.2, 0.1, 0.2, -0.3, 0}, {-0.4, 0, 0, 0, 0, 0, 0.7, 0}, {0, 0, 0, 0, 0, 0, 0, 0}};
+        for (auto& o : on) t.onsite.insert(t.onsite.end(), o, o + 8);
+        const int hops[3][2] = {{0, 1}, {0, 1}, {1, 1}};     // a repeated hop and an R = 0 self-pair; orbital 2 is isolated
+        const double amps[3][8] = {{1, 0.5, 0.2, 0, -0.3, 0.1, 0.9, -0.4}, {1, 0.5, 0.2, 0, -0.3, 0.1, 0.9, -0.4}, {0.3, 0.2, 0.1, 0.6, -0.2, 0.4, 0.05, -0.1}};
+        for (int h = 0; h < 3; ++h) {
+            t.hop_i.push_back(hops[h][0]);
+            t.hop_j.push_back(hops[h][1]);
+            t.hop_amp.insert(t.hop_amp.end(), amps[h], amps[h] + 8);
+        }
+        fail += check(t, nullptr, "molecule");
+    }
+    // argument errors come back as codes
+    int64_t nnz = 0;
+    const double on1[2] = {0.0, 0.0};
+    const int32_t bad_i[1] = {3}, ok_j[1] = {0};
+    const double amp1[2] = {1.0, 0.0};
+    if (tbk_sparse_flatten_host(0, 1, 1, nullptr, on1, 1, bad_i, ok_j, nullptr, amp1, 0, &nnz, nullptr, nullptr, nullptr, nullptr, nullptr) !=
+        TBK_EINVAL)
+        fail += printf("orbital index out of range not refused\n");
+    printf(fail ? "FAILED\n" : "kpm_flatten_check ok\n");
+    return fail ? 1 : 0;
+}

@@ -12,11 +12,49 @@ import numpy as np
 
 from . import _lib
 
-__all__ = ["tb_model"]
+__all__ = ["tb_model", "kpm_reconstruct"]
 
 
 def _is_int(a):
     return np.issubdtype(type(a), np.integer)        # pythtb.py:3950
+
+
+def kpm_reconstruct(mu, energies, bounds, kernel="jackson", lam=4.0):
+    """Extension: the kernel-polynomial reconstruction of a density from its Chebyshev moments `mu` `(..., M)` (those of
+    `tb_model.kpm_moments` for the same `bounds` = (emin, emax)) at `energies` inside the open interval (emin, emax):
+
+        rho(E) = [g_0 mu_0 + 2 sum_{m >= 1} g_m mu_m T_m(x)] / (pi a sqrt(1 - x^2)),   x = (E - b) / a,
+
+    a = (emax - emin) / 2, b = (emax + emin) / 2; float `(..., nE)`.  kernel: "jackson" (non-negative, resolution ~ pi a / M),
+    "lorentz" (g_m = sinh(lam (1 - m / M)) / sinh(lam)) or None (g = 1: the truncated series, with Gibbs oscillations).
+    Host NumPy, O(M nE) work; the moments are the product of the device."""
+    mu = np.asarray(mu, dtype=float)
+    e = np.asarray(energies, dtype=float)
+    if mu.ndim < 1 or mu.shape[-1] < 1:
+        raise Exception("\n\nkpm_reconstruct: mu must have shape (..., M) with M >= 1")
+    if e.ndim != 1:
+        raise Exception("\n\nkpm_reconstruct: energies must be a one-dimensional list")
+    emin, emax = float(bounds[0]), float(bounds[1])
+    if not emax > emin:
+        raise Exception("\n\nkpm_reconstruct: bounds must be (emin, emax) with emin < emax")
+    if e.size and not (e.min() > emin and e.max() < emax):
+        raise Exception("\n\nkpm_reconstruct: energies must lie inside the open interval (%.12g, %.12g)" % (emin, emax))
+    M = mu.shape[-1]
+    m = np.arange(M, dtype=float)
+    if kernel == "jackson":
+        q = np.pi / (M + 1.0)
+        g = ((M - m + 1.0) * np.cos(q * m) + np.sin(q * m) / np.tan(q)) / (M + 1.0)
+    elif kernel == "lorentz":
+        g = np.sinh(lam * (1.0 - m / M)) / np.sinh(lam)
+    elif kernel is None:
+        g = np.ones(M)
+    else:
+        raise Exception("\n\nkpm_reconstruct: kernel must be \"jackson\", \"lorentz\" or None")
+    a, b = 0.5 * (emax - emin), 0.5 * (emax + emin)
+    x = (e - b) / a
+    w = g * np.where(m == 0, 1.0, 2.0)
+    T = np.cos(m[:, None] * np.arccos(x)[None, :])
+    return (mu * w) @ T / (np.pi * a * np.sqrt(1.0 - x * x))
 
 
 class tb_model(object):
@@ -86,6 +124,7 @@ class tb_model(object):
         self._tbk_epoch = 0        # bumped whenever the tables change
         self._tbk_cache = None     # (epoch, device handle)
         self._tbk_surface = {}     # fin_dir -> (fingerprint, cut_piece(2 L, fin_dir)) of the surface Green's functions
+        self._tbk_sparse = None    # (edit mark, context, handle of the sparse operator) of the kernel polynomial method
 
     # ------------------------------------------------------------------ tables
     def _val_to_block(self, val):
@@ -234,6 +273,7 @@ class tb_model(object):
         st = dict(self.__dict__)
         st["_tbk_cache"] = None
         st["_tbk_surface"] = {}
+        st["_tbk_sparse"] = None
         return st
 
     def __del__(self):
@@ -241,6 +281,12 @@ class tb_model(object):
         if cache is not None:
             try:
                 _lib.lib.tbk_model_free(cache[2])
+            except Exception:
+                pass
+        sparse = getattr(self, "_tbk_sparse", None)
+        if sparse is not None:
+            try:
+                _lib.lib.tbk_sparse_free(sparse[2])
             except Exception:
                 pass
 
@@ -1419,6 +1465,142 @@ class tb_model(object):
                                                   _lib.iptr(np.ascontiguousarray(mesh)), int(w.size), _lib.dptr(w), float(eta),
                                                   float(tol), int(max_iter), _lib.dptr(out)))
         return out
+
+    # ------------------------------------------------------------------ kernel polynomial method (extensions)
+    def _sparse_model(self):
+        """The sparse (CSR) operator of this model on the device: any number of states, no dense upload.  Cached with the edit
+        mark of `_device_model` and freed with it."""
+        ctx = _lib.default_context()
+        c = getattr(self, "_tbk_sparse", None)
+        mark = (self._tbk_epoch, len(self._hoppings), self._orb.tobytes(), np.asarray(self._site_energies).tobytes())
+        if c is not None and c[0] == mark and c[1] is ctx:
+            return c[2]
+        if c is not None:
+            _lib.lib.tbk_sparse_free(c[2])
+            self._tbk_sparse = None
+        orb_per, onsite, hop_i, hop_j, hop_R, hop_amp = self._flat_tables()
+        h = C.c_void_p()
+        _lib.check(_lib.lib.tbk_sparse_upload(
+            ctx.handle, self._dim_k, self._norb, self._nspin, _lib.dptr(orb_per),
+            _lib.dptr(onsite.view(float)), len(hop_i), _lib.iptr(hop_i), _lib.iptr(hop_j),
+            _lib.iptr(hop_R.reshape(-1)) if hop_R.size else None,
+            _lib.dptr(hop_amp.view(float)) if hop_amp.size else None, C.byref(h)))
+        self._tbk_sparse = (mark, ctx, h)
+        return h
+
+    def _kpm_k(self, k_list):
+        if k_list is None:
+            if self._dim_k != 0:
+                raise Exception("\n\nHave to provide a k-vector!")
+            return None, 1
+        if self._dim_k == 0:
+            raise Exception("\n\nA model with dim_k = 0 takes no k_list.")
+        k = self._k_array(k_list)
+        if len(k) < 1:
+            raise Exception("\n\nkpm: empty k_list")
+        return k, len(k)
+
+    def _kpm_bounds(self, bounds, sp):
+        if bounds is None:
+            g = np.zeros(2)
+            _lib.check(_lib.lib.tbk_sparse_info(sp, None, None, None, _lib.dptr(g)))
+            pad = 0.01 * (g[1] - g[0]) if g[1] > g[0] else 1.0
+            return float(g[0] - pad), float(g[1] + pad)
+        return bounds
+
+    @staticmethod
+    def _kpm_bounds_arg(bounds):
+        if bounds is None:
+            return None
+        b = np.array(bounds, dtype=float)
+        if b.shape != (2,) or not np.all(np.isfinite(b)) or not b[1] > b[0]:
+            raise Exception("\n\nkpm: bounds must be (emin, emax), finite, with emin < emax")
+        return float(b[0]), float(b[1])
+
+    def kpm_vectors(self, n_vectors, seed=0, first=0):
+        """Extension: the random-phase start vectors e^{i phi} of `kpm_moments`, complex `(n_vectors, nsta)`: vectors number
+        first .. first + n_vectors - 1 of `seed`.  Element i of vector g is a pure function of (seed, g, i), generated on the
+        device; `kpm_moments` uses the numbers q * n_vectors + v at the k-point with index q."""
+        if not _is_int(n_vectors) or n_vectors < 1:
+            raise Exception("\n\nkpm_vectors: n_vectors must be a positive integer")
+        if not _is_int(seed) or not 0 <= seed < 2 ** 64 or not _is_int(first) or first < 0:
+            raise Exception("\n\nkpm_vectors: seed must be an integer in [0, 2^64), first a non-negative integer")
+        out = np.empty((int(n_vectors), self._nsta), dtype=complex)
+        _lib.check(_lib.lib.tbk_kpm_vectors(self._sparse_model(), int(seed), int(first), int(n_vectors), _lib.dptr(out.view(float))))
+        return out
+
+    def kpm_moments(self, n_moments, k_list=None, vectors=None, n_vectors=8, seed=0, states=None, bounds=None):
+        """Extension: Chebyshev moments mu_m = <v|T_m(H~(k))|v> / <v|v>, m < n_moments, of the rescaled sparse Hamiltonian
+        H~ = (H - b) / a, a = (emax - emin) / 2, b = (emax + emin) / 2 (the kernel polynomial method; Weisse et al., Rev. Mod.
+        Phys. 78, 275) -- for models of any size: nothing is diagonalised and no dense matrix is built.  Returns
+        `(mu, (emin, emax))`, mu float `(nk, nvec, n_moments)`, without the k axis when k_list is None (dim_k = 0 only).
+
+        Start vectors, exactly one of: `vectors` complex128 `(nvec, nsta)`; `states`, state indices (unit vectors: the local
+        density of states); otherwise `n_vectors` random-phase vectors of `seed` (those `kpm_vectors` returns).
+        bounds=None: the Gershgorin interval of the hopping table widened by 1 % of its width on each side.  Bounds that do
+        not contain the spectrum make the recursion diverge: the call raises, naming them.  n_moments moments cost
+        n_moments / 2 sparse products per block of 8 vectors; fixed-order sums on the device: two calls give the same bits."""
+        if not _is_int(n_moments) or n_moments < 1:
+            raise Exception("\n\nkpm_moments: n_moments must be a positive integer")
+        if vectors is not None and states is not None:
+            raise Exception("\n\nkpm_moments: give either vectors or states, not both")
+        n = self._nsta
+        vec = st = None
+        if vectors is not None:
+            vec = np.asarray(vectors)
+            if vec.dtype != np.complex128 or vec.ndim != 2 or vec.shape[0] < 1 or vec.shape[1] != n:
+                raise Exception("\n\nkpm_moments: vectors must be a complex128 array of shape (nvec, %d)" % n)
+            vec = np.ascontiguousarray(vec)
+            nvec = vec.shape[0]
+        elif states is not None:
+            st = np.array(list(states))
+            if st.ndim != 1 or st.size < 1 or not np.issubdtype(st.dtype, np.integer):
+                raise Exception("\n\nkpm_moments: states must be a non-empty list of integers")
+            if st.min() < 0 or st.max() >= n:
+                raise Exception("\n\nkpm_moments: state index out of range [0, %d)" % n)
+            st = np.ascontiguousarray(st, dtype=np.int32)
+            nvec = st.size
+        else:
+            if not _is_int(n_vectors) or n_vectors < 1:
+                raise Exception("\n\nkpm_moments: n_vectors must be a positive integer")
+            nvec = int(n_vectors)
+        if not _is_int(seed) or not 0 <= seed < 2 ** 64:
+            raise Exception("\n\nkpm_moments: seed must be an integer in [0, 2^64)")
+        bounds = self._kpm_bounds_arg(bounds)
+        k, nk = self._kpm_k(k_list)
+        sp = self._sparse_model()
+        emin, emax = self._kpm_bounds(bounds, sp)
+        mu = np.empty((nk, nvec, int(n_moments)), dtype=float)
+        _lib.check(_lib.lib.tbk_kpm_moments(sp, _lib.dptr(k), nk, int(n_moments), emin, emax, nvec,
+                                            None if vec is None else _lib.dptr(vec.view(float)), _lib.iptr(st), int(seed),
+                                            _lib.dptr(mu)))
+        return (mu[0] if k_list is None else mu), (emin, emax)
+
+    def kpm_dos(self, energies, n_moments, k_list=None, n_vectors=8, seed=0, kernel="jackson", bounds=None, return_error=False,
+                states=None):
+        """Extension: the density of states per state rho(E) (integral 1) by the kernel polynomial method: the stochastic
+        trace over `n_vectors` random-phase vectors per k-point, averaged over `k_list`, reconstructed by `kpm_reconstruct`.
+        return_error=True: `(rho, err)` with the standard error of the mean over the k x vector samples.  states (a list of
+        state indices) replaces the random vectors by unit vectors; `range(nsta)` is the exact trace."""
+        mu, bnd = self.kpm_moments(n_moments, k_list, n_vectors=n_vectors, seed=seed, states=states, bounds=bounds)
+        samples = mu.reshape(-1, mu.shape[-1])
+        rho = kpm_reconstruct(samples.mean(axis=0), energies, bnd, kernel)
+        if not return_error:
+            return rho
+        each = kpm_reconstruct(samples, energies, bnd, kernel)
+        ns = each.shape[0]
+        err = each.std(axis=0, ddof=1) / np.sqrt(ns) if ns > 1 else np.full(rho.shape, np.nan)
+        return rho, err
+
+    def kpm_ldos(self, energies, states, n_moments, k_list=None, kernel="jackson", bounds=None):
+        """Extension: the local density of states rho_i(E) = sum_n |<i|n>|^2 delta(E - E_n) of the states `states`, averaged
+        over `k_list`, float `(len(states), nE)`: `kpm_moments` with unit start vectors, then `kpm_reconstruct`."""
+        if states is None:
+            raise Exception("\n\nkpm_ldos: states must be a non-empty list of integers")
+        mu, bnd = self.kpm_moments(n_moments, k_list, states=states, bounds=bounds)
+        if k_list is not None:
+            mu = mu.mean(axis=0)
+        return kpm_reconstruct(mu, energies, bnd, kernel)
 
     # ------------------------------------------------------------------ k generators (host)
     def k_uniform_mesh(self, mesh_size):
