@@ -469,6 +469,22 @@ int tbk_kpm_vectors(tbk_sparse* sp, uint64_t seed, int64_t first, int64_t count,
  * emax) does not contain the spectrum.  Fixed-order sums, no atomics on floating-point data: bit-reproducible.                  */
 int tbk_kpm_moments(tbk_sparse* sp, const double* k, int64_t nk, int n_moments, double emin, double emax, int nvec,
                     const double* vectors, const int32_t* states, uint64_t seed, double* mu);
+/* ---- kernel polynomial method: double moments of the Kubo-Bastin conductivity ------------------------
+ * No reference counterpart.  V^a = dH/dk_a in reduced coordinates, a periodic axis in [0, dim_k): the matrix of tbk_gen_dham, with the
+ * sparsity of H -- the entry of H times 2 pi i (R + orb_col - orb_row)_a.
+ * mu[nk][nvec][n_moments][n_moments] c128, mu_mn = <v| V^a T_m(H~(k)) V^b T_n(H~(k)) |v> / <v|v>, a = dir_a, b = dir_b (equal
+ * allowed), H~ and the start vectors as in tbk_kpm_moments (random-phase vectors number q nvec + v for the k-point with index q).
+ * 3 n_moments sparse products per block of 8 vectors and a device workspace of n_moments nsta 8 x 16 bytes for the vectors
+ * T_n(H~) v (TBK_ENOMEM, naming the byte count, when it cannot be had).  TBK_EINVAL for dim_k = 0, for a direction outside
+ * [0, dim_k) and, naming the bounds, when a moment is not finite or exceeds (1 + 1e-6) ||V^a|| ||V^b|| in modulus, the norms bounded
+ * by the largest row sum of |V|.  Fixed-order sums, no atomics on floating-point data: bit-reproducible.
+ * tbk_sparse_velocity_bounds_host: host only (no device call); vbound[4] = those row-sum bounds of the tables' operator per axis
+ * (zero from dim_k on).                                                                                                        */
+int tbk_kpm_double_moments(tbk_sparse* sp, const double* k, int64_t nk, int n_moments, double emin, double emax, int dir_a, int dir_b,
+                           int nvec, const double* vectors, const int32_t* states, uint64_t seed, double* mu);
+int tbk_sparse_velocity_bounds_host(int dim_k, int norb, int nspin, const double* orb, const double* onsite, int64_t nhop,
+                                    const int32_t* hop_i, const int32_t* hop_j, const int32_t* hop_R, const double* hop_amp,
+                                    double* vbound);
 
 /* ---- multi-GPU: one process per GPU, k-points sharded, one gather ------
  * Thin RCCL wrappers (librccl is dlopen'ed on first use).  The 128-byte id is

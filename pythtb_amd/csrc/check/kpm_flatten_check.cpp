@@ -2,7 +2,9 @@
 // AddressSanitizer + UBSan by `make -C pythtb_amd/csrc kpm-check` and run as an ordinary program.  Two tables: the spinless
 // Haldane cell (dim_k = 2) and a spinful three-orbital molecule (dim_k = 0) with a repeated hop, an R = 0 self-pair and an
 // isolated zero-energy orbital.  It expands the CSR table to a dense matrix, compares with the matrix built from the definition
-// (ham[i,s,j,t] += amp e^{2 pi i k.(R + tau_j - tau_i)}, plus the Hermitian conjugate), and checks the structure.
+// (ham[i,s,j,t] += amp e^{2 pi i k.(R + tau_j - tau_i)}, plus the Hermitian conjugate), and checks the structure.  The velocity
+// bounds of tbk_sparse_velocity_bounds_host (the guard of tbk_kpm_double_moments) are compared with the row sums of the table's
+// entries and, as upper bounds, with the row sums of dH/dk_d built from the definition at that k.
 #include <complex>
 #include <cstdarg>
 #include <cstdio>
@@ -50,6 +52,9 @@ static int check(const Table& t, const double* k, const char* name) {
         return std::polar(1.0, 2.0 * M_PI * x);
     };
     std::vector<cplx> ref((size_t)n * n), got((size_t)n * n);
+    std::vector<cplx> dref[4];
+    for (int d = 0; d < dk; ++d) dref[d].assign((size_t)n * n, cplx(0.0, 0.0));
+    auto disp = [&](int a, int b, const int32_t* Rv, int sign, int d) { return sign * Rv[d] + t.orb[(b / ns) * dk + d] - t.orb[(a / ns) * dk + d]; };
     for (int o = 0; o < t.norb; ++o)
         for (int s = 0; s < ns; ++s)
             for (int u = 0; u < ns; ++u) {
@@ -64,6 +69,10 @@ static int check(const Table& t, const double* k, const char* name) {
                 const int32_t* Rv = dk ? &t.hop_R[h * dk] : nullptr;
                 ref[(size_t)a * n + b] += cplx(p[0], p[1]) * phase(a, b, Rv, 1);
                 ref[(size_t)b * n + a] += cplx(p[0], -p[1]) * phase(b, a, Rv, -1);
+                for (int d = 0; d < dk; ++d) {
+                    dref[d][(size_t)a * n + b] += cplx(0.0, 2.0 * M_PI * disp(a, b, Rv, 1, d)) * cplx(p[0], p[1]) * phase(a, b, Rv, 1);
+                    dref[d][(size_t)b * n + a] += cplx(0.0, 2.0 * M_PI * disp(b, a, Rv, -1, d)) * cplx(p[0], -p[1]) * phase(b, a, Rv, -1);
+                }
             }
     int bad = 0;
     if (row_ptr[0] != 0 || row_ptr[n] != nnz) bad++;
@@ -80,6 +89,25 @@ static int check(const Table& t, const double* k, const char* name) {
                 if (c >= 0) bad++;
             }
             got[(size_t)a * n + col[e]] += cplx(amp[2 * e], amp[2 * e + 1]) * phase(a, col[e], &R[4 * e], 1);
+        }
+    }
+    double vb[4] = {-1.0, -1.0, -1.0, -1.0};
+    rc = tbk_sparse_velocity_bounds_host(dk, t.norb, ns, t.orb.data(), t.onsite.data(), nhop, t.hop_i.data(), t.hop_j.data(), t.hop_R.data(),
+                                         t.hop_amp.data(), vb);
+    if (rc) return printf("%s: velocity bounds: %s\n", name, g_err), 1;
+    for (int d = 0; d < 4; ++d) {
+        double table = 0.0, dense = 0.0;     // largest row sum of the table's entries, and of |dH/dk_d| at this k
+        for (int a = 0; a < n && d < dk; ++a) {
+            double rs = 0.0, rd = 0.0;
+            for (int64_t e = row_ptr[a]; e < row_ptr[a + 1]; ++e)
+                if (col[e] >= 0 && col[e] < n) rs += 2.0 * M_PI * std::abs(cplx(amp[2 * e], amp[2 * e + 1])) * std::fabs(disp(a, col[e], &R[4 * e], 1, d));
+            for (int b = 0; b < n; ++b) rd += std::abs(dref[d][(size_t)a * n + b]);
+            table = std::max(table, rs);
+            dense = std::max(dense, rd);
+        }
+        if (!(std::fabs(vb[d] - table) <= 1e-14 * (1.0 + table)) || !(dense <= vb[d] * (1.0 + 1e-14) + 1e-300) || (d >= dk && vb[d] != 0.0)) {
+            printf("%s: velocity bound of axis %d is %g, the table gives %g, |dH/dk| at k has row sum %g\n", name, d, vb[d], table, dense);
+            bad++;
         }
     }
     double err = 0.0, big = 0.0;

@@ -20,26 +20,10 @@
 #include <cmath>
 #include <new>
 #include <vector>
-#include "tbk_internal.h"
+#include "tbk_kpm.h"
 
-#define KPM_NV 8            // vectors per block
-#define KPM_MAX_WG 2048     // workgroups of a step (grid-stride over the row tiles beyond that)
 #define KPM_MAX_SLOTS 128   // steps between two reductions of the partial sums
 #define KPM_PART_BYTES ((size_t)32 << 20)
-
-struct tbk_sparse {
-    tbk_ctx* ctx = nullptr;
-    int dim_k = 0, nsta = 0;
-    int64_t nnz = 0;
-    double gmin = 0.0, gmax = 0.0;   // Gershgorin interval
-    void* blob = nullptr;            // one device allocation holding all tables
-    const int64_t* row_ptr = nullptr;
-    const int32_t* col = nullptr;
-    const int32_t* row_of = nullptr;
-    const cd* amp = nullptr;
-    const int4* R = nullptr;
-    const double4* orb = nullptr;
-};
 
 // ------------------------------------------------------------------ host assembly
 namespace {
@@ -64,6 +48,7 @@ struct SparseHost {
     std::vector<RawEntry> ent;      // the first nnz are the merged entries, rows in order, (col, R) sorted within a row
     std::vector<double> orb4;
     double gmin = 0.0, gmax = 0.0;
+    double vbound[4] = {0.0, 0.0, 0.0, 0.0};   // largest row sum of |dH/dk_d|, d < dim_k
 };
 }  // namespace
 
@@ -133,7 +118,7 @@ static int sparse_flatten(int dim_k, int norb, int nspin, const double* orb, con
         const int64_t e0 = start[a], e1 = ptr[a + 1];
         std::stable_sort(ent.begin() + e0, ent.begin() + e1, raw_less);   // equal keys are summed in table order
         const int64_t w0 = w;
-        double diag = 0.0, rad = 0.0;
+        double diag = 0.0, rad = 0.0, vrow[4] = {0.0, 0.0, 0.0, 0.0};
         for (int64_t e = e0; e < e1;) {
             RawEntry m = ent[(size_t)e];
             int64_t f = e + 1;
@@ -147,11 +132,15 @@ static int sparse_flatten(int dim_k, int norb, int nspin, const double* orb, con
             } else {
                 rad += sqrt(cabs2(m.amp));
             }
+            for (int d = 0; d < dim_k; ++d)   // |(dH/dk_d)_ab| = 2 pi |amp| |(R + orb_b - orb_a)_d| at every k
+                vrow[d] += 2.0 * M_PI * sqrt(cabs2(m.amp)) *
+                           fabs((double)m.R[d] + orb[(int64_t)(m.col / ns) * dim_k + d] - orb[(int64_t)(a / ns) * dim_k + d]);
             ent[(size_t)w++] = m;
         }
         ptr[a] = w0;
         gmin = std::min(gmin, diag - rad);
         gmax = std::max(gmax, diag + rad);
+        for (int d = 0; d < dim_k; ++d) S.vbound[d] = std::max(S.vbound[d], vrow[d]);
     }
     ptr[n] = w;
     S.nnz = w;
@@ -189,7 +178,16 @@ extern "C" int tbk_sparse_flatten_host(int dim_k, int norb, int nspin, const dou
     return TBK_OK;
 }
 
-static inline size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
+extern "C" int tbk_sparse_velocity_bounds_host(int dim_k, int norb, int nspin, const double* orb, const double* onsite, int64_t nhop,
+                                               const int32_t* hop_i, const int32_t* hop_j, const int32_t* hop_R, const double* hop_amp,
+                                               double* vbound) {
+    TBK_REQUIRE(vbound, TBK_EINVAL, "tbk_sparse_velocity_bounds_host: null vbound");
+    SparseHost S;
+    int rc = sparse_flatten(dim_k, norb, nspin, orb, onsite, nhop, hop_i, hop_j, hop_R, hop_amp, S);
+    if (rc) return rc;
+    for (int d = 0; d < 4; ++d) vbound[d] = S.vbound[d];
+    return TBK_OK;
+}
 
 extern "C" int tbk_sparse_upload(tbk_ctx* ctx, int dim_k, int norb, int nspin, const double* orb, const double* onsite,
                                  int64_t nhop, const int32_t* hop_i, const int32_t* hop_j, const int32_t* hop_R,
@@ -232,6 +230,7 @@ extern "C" int tbk_sparse_upload(tbk_ctx* ctx, int dim_k, int norb, int nspin, c
     sp->nnz = S.nnz;
     sp->gmin = S.gmin;
     sp->gmax = S.gmax;
+    for (int d = 0; d < 4; ++d) sp->vbound[d] = S.vbound[d];
     hipError_t e = hipSetDevice(ctx->device);
     if (e == hipSuccess) e = hipMalloc(&sp->blob, total);
     if (e == hipSuccess) e = hipMemcpyAsync(sp->blob, host.data(), total, hipMemcpyHostToDevice, ctx->stream);
@@ -295,74 +294,11 @@ __global__ __launch_bounds__(256) void k_kpm_values(const int64_t nnz, const int
     }
 }
 
-// element i of random-phase vector number g: a pure function of (seed, g, i)
-__host__ __device__ inline uint64_t kpm_mix(uint64_t z) {
-    z += 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-__device__ __forceinline__ cd kpm_random_phase(const uint64_t seed, const uint64_t g, const uint64_t i) {
-    const uint64_t h = kpm_mix(kpm_mix(kpm_mix(seed) ^ g) ^ i);
-    const double u = (double)(h >> 11) * 0x1.0p-53;      // [0, 1)
-    double s, c;
-    sincospi(2.0 * u, &s, &c);
-    return cd{c, s};
-}
-
 __global__ __launch_bounds__(256) void k_kpm_randvec(const int nsta, const uint64_t seed, const int64_t first, const int64_t count,
                                                      cd* __restrict__ out) {
     const int64_t total = count * nsta;
     for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256)
         out[e] = kpm_random_phase(seed, (uint64_t)(first + e / nsta), (uint64_t)(e % nsta));
-}
-
-// The sums of a workgroup's (A, B) over its rows, per vector: across the 64 / NV rows of a wavefront by shuffles, across the four
-// wavefronts through LDS in a fixed order -> part[workgroup][2][NV].
-template <int NV>
-__device__ __forceinline__ void kpm_block_sums(double dA, double dB, double* __restrict__ part) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int o = NV; o < 64; o <<= 1) {
-        dA += __shfl_xor(dA, o);
-        dB += __shfl_xor(dB, o);
-    }
-    __shared__ double red[4][2][NV];
-    if (lane < NV) {
-        red[wave][0][lane] = dA;
-        red[wave][1][lane] = dB;
-    }
-    __syncthreads();
-    if (threadIdx.x < 2 * NV) {
-        const int s = threadIdx.x / NV, v = threadIdx.x % NV;
-        part[(int64_t)blockIdx.x * 2 * NV + threadIdx.x] = ((red[0][s][v] + red[1][s][v]) + red[2][s][v]) + red[3][s][v];
-    }
-}
-
-// alpha_0 of one block of NV vectors, alpha[row][NV], and the partial sums of <alpha_0|alpha_0> (the slot of step 0).
-// mode 0: random phases, vector numbers g0 + v; 1: unit vectors at states[v]; 2: src[v][nsta].  Vectors v >= nv are zero.
-template <int NV>
-__global__ __launch_bounds__(256) void k_kpm_init(const int nsta, const int nv, const int mode, const uint64_t seed, const uint64_t g0,
-                                                  const int32_t* __restrict__ states, const cd* __restrict__ src,
-                                                  cd* __restrict__ cur, double* __restrict__ part) {
-    constexpr int RPW = 64 / NV, RPB = 4 * RPW;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, v = lane % NV, rw = lane / NV;
-    const int64_t ntiles = ((int64_t)nsta + RPB - 1) / RPB;
-    double dA = 0.0;
-    for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        const int64_t row = tile * RPB + wave * RPW + rw;
-        if (row < nsta) {
-            cd x{0.0, 0.0};
-            if (v < nv) {
-                if (mode == 0) x = kpm_random_phase(seed, g0 + (uint64_t)v, (uint64_t)row);
-                else if (mode == 1) x = cd{states[v] == row ? 1.0 : 0.0, 0.0};
-                else x = src[(int64_t)v * nsta + row];
-            }
-            cur[row * NV + v] = x;
-            dA += cabs2(x);
-        }
-    }
-    kpm_block_sums<NV>(dA, 0.0, part);
 }
 
 // One Chebyshev step for a block of NV vectors: nw = 2 H~ cur - prev (FIRST: nw = H~ cur), H~ = (H - b) / a, stored over prev -- row i
@@ -398,26 +334,6 @@ __global__ __launch_bounds__(256) void k_kpm_step(const int nsta, const int64_t*
     kpm_block_sums<NV>(dA, dB, part);
 }
 
-// dots[step][2][NV] = the sum over the workgroups of part[slot][workgroup][2][NV], one workgroup per step of the chunk: 256 / (2 NV)
-// strided partial sums per column, each in ascending workgroup order, then added in ascending order -- a fixed shape.
-template <int NV>
-__global__ __launch_bounds__(256) void k_kpm_reduce(const int nwg, const double* __restrict__ part, double* __restrict__ dots) {
-    constexpr int NC = 2 * NV, G = 256 / NC;
-    const int c = threadIdx.x % NC, g = threadIdx.x / NC;
-    const double* p = part + (int64_t)blockIdx.x * nwg * NC;
-    double s = 0.0;
-    for (int w = g; w < nwg; w += G) s += p[(int64_t)w * NC + c];
-    __shared__ double red[G][NC];
-    red[g][c] = s;
-    __syncthreads();
-    if (threadIdx.x < NC) {
-        double t = red[0][c];
-#pragma unroll
-        for (int i = 1; i < G; ++i) t += red[i][c];
-        dots[(int64_t)blockIdx.x * NC + c] = t;
-    }
-}
-
 // The doubling identities on dots[step] = (A_step[NV], B_step[NV]), A_j = <alpha_j|alpha_j>, B_j = Re <alpha_j|alpha_j-1>:
 // mu_0 = 1, mu_1 = B_1 / A_0, mu_2j = (2 A_j - A_0) / A_0, mu_2j-1 = (2 B_j - B_1) / A_0  ->  mu[v][m], v < nv
 template <int NV>
@@ -441,8 +357,6 @@ __global__ __launch_bounds__(256) void k_kpm_finish(const int nv, const int nmom
 }
 
 // ------------------------------------------------------------------ host entry points
-static unsigned kpm_stream_grid(int64_t items) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>((items + 255) / 256, 2048)); }
-
 extern "C" int tbk_kpm_vectors(tbk_sparse* sp, uint64_t seed, int64_t first, int64_t count, double* out) {
     TBK_REQUIRE(sp && (out || count == 0), TBK_EINVAL, "tbk_kpm_vectors: null argument");
     TBK_REQUIRE(first >= 0 && count >= 0, TBK_EINVAL, "tbk_kpm_vectors: first=%lld count=%lld", (long long)first, (long long)count);

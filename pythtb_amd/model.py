@@ -12,7 +12,7 @@ import numpy as np
 
 from . import _lib
 
-__all__ = ["tb_model", "kpm_reconstruct"]
+__all__ = ["tb_model", "kpm_reconstruct", "kpm_conductivity_reconstruct"]
 
 
 def _is_int(a):
@@ -55,6 +55,66 @@ def kpm_reconstruct(mu, energies, bounds, kernel="jackson", lam=4.0):
     w = g * np.where(m == 0, 1.0, 2.0)
     T = np.cos(m[:, None] * np.arccos(x)[None, :])
     return (mu * w) @ T / (np.pi * a * np.sqrt(1.0 - x * x))
+
+
+def _kpm_kernel(M, kernel, lam, who):
+    m = np.arange(M, dtype=float)
+    if kernel == "jackson":
+        q = np.pi / (M + 1.0)
+        return ((M - m + 1.0) * np.cos(q * m) + np.sin(q * m) / np.tan(q)) / (M + 1.0)
+    if kernel == "lorentz":
+        return np.sinh(lam * (1.0 - m / M)) / np.sinh(lam)
+    if kernel is None:
+        return np.ones(M)
+    raise Exception("\n\n%s: kernel must be \"jackson\", \"lorentz\" or None" % who)
+
+
+def kpm_conductivity_reconstruct(mu, energies, bounds, kernel="jackson", lam=4.0, kT=0.0, n_quad=None):
+    """Extension: the Kubo-Bastin conductivity per sample from double Chebyshev moments `mu` `(..., M, M)` (those of
+    `tb_model.kpm_double_moments` for the same `bounds` = (emin, emax)) at the Fermi levels `energies` inside the open
+    interval (emin, emax) (Garcia, Covaci, Rappoport, Phys. Rev. Lett. 114, 116602):
+
+        G_ab(E_F) = (2 / (pi^2 a^2)) int_{-1}^{1} dx f(x) (1 - x^2)^{-2} sum_{m,n} Gamma_mn(x) g_m g_n mu_mn / ((1 + d_m0)(1 + d_n0))
+        Gamma_mn(x) = (x - i n sqrt(1 - x^2)) e^{i n theta} T_m(x) + (x + i m sqrt(1 - x^2)) e^{-i m theta} T_n(x),   x = cos theta,
+
+    a = (emax - emin) / 2, b = (emax + emin) / 2, g the kernel coefficients of `kpm_reconstruct`, f the Fermi function of
+    E = a x + b at temperature kT (kT = 0: the step at E_F); complex `(..., nE)`.  The integral is a Chebyshev-Gauss
+    quadrature on the `n_quad` (default 8 M) nodes x_j = cos(pi (j + 1/2) / n_quad) with weights pi sqrt(1 - x_j^2) / n_quad;
+    at kT = 0 the nodes with x_j <= x_F.  Host NumPy, O(M^2 n_quad) work per moment set."""
+    mu = np.asarray(mu, dtype=complex)
+    e = np.asarray(energies, dtype=float)
+    if mu.ndim < 2 or mu.shape[-1] < 1 or mu.shape[-1] != mu.shape[-2]:
+        raise Exception("\n\nkpm_conductivity_reconstruct: mu must have shape (..., M, M) with M >= 1")
+    if e.ndim != 1:
+        raise Exception("\n\nkpm_conductivity_reconstruct: energies must be a one-dimensional list")
+    emin, emax = float(bounds[0]), float(bounds[1])
+    if not emax > emin:
+        raise Exception("\n\nkpm_conductivity_reconstruct: bounds must be (emin, emax) with emin < emax")
+    if e.size and not (e.min() > emin and e.max() < emax):
+        raise Exception("\n\nkpm_conductivity_reconstruct: energies must lie inside the open interval (%.12g, %.12g)" % (emin, emax))
+    if not np.isfinite(kT) or kT < 0.0:
+        raise Exception("\n\nkpm_conductivity_reconstruct: kT must be finite and >= 0")
+    M = mu.shape[-1]
+    K = 8 * M if n_quad is None else n_quad
+    if not _is_int(K) or K < 1:
+        raise Exception("\n\nkpm_conductivity_reconstruct: n_quad must be a positive integer")
+    g = _kpm_kernel(M, kernel, lam, "kpm_conductivity_reconstruct")
+    g[0] *= 0.5                                             # the factor 1 / (1 + delta_m0)
+    a, b = 0.5 * (emax - emin), 0.5 * (emax + emin)
+    th = np.pi * (np.arange(K) + 0.5) / K
+    x, sq = np.cos(th), np.sin(th)
+    m = np.arange(M, dtype=float)
+    T = np.cos(m[:, None] * th[None, :])                                               # T_m(x_j)
+    A = (x[None, :] - 1j * m[:, None] * sq[None, :]) * np.exp(1j * m[:, None] * th[None, :])   # (x - i n s) e^{i n theta}
+    c = mu * (g[:, None] * g[None, :])
+    # sum_mn Gamma_mn c_mn = sum_m T_m (c A)_m + sum_n T_n (c^T conj A)_n at every node
+    S = np.sum(T * (c @ A), axis=-2) + np.sum(T * (np.swapaxes(c, -1, -2) @ A.conj()), axis=-2)
+    S = S * ((np.pi / K) / sq ** 3)                         # the weight pi s / K over (1 - x^2)^2
+    if kT > 0.0:
+        f = 0.5 * (1.0 - np.tanh(0.5 * ((a * x + b)[:, None] - e[None, :]) / kT))
+    else:
+        f = (x[:, None] <= ((e - b) / a)[None, :]).astype(float)
+    return (2.0 / (np.pi * a) ** 2) * (S @ f)
 
 
 class tb_model(object):
@@ -1529,6 +1589,34 @@ class tb_model(object):
         _lib.check(_lib.lib.tbk_kpm_vectors(self._sparse_model(), int(seed), int(first), int(n_vectors), _lib.dptr(out.view(float))))
         return out
 
+    def _kpm_start(self, who, vectors, n_vectors, seed, states):
+        """Checked start vectors of the moment calls: (vectors or None, int32 states or None, nvec)."""
+        if vectors is not None and states is not None:
+            raise Exception("\n\n%s: give either vectors or states, not both" % who)
+        n = self._nsta
+        vec = st = None
+        if vectors is not None:
+            vec = np.asarray(vectors)
+            if vec.dtype != np.complex128 or vec.ndim != 2 or vec.shape[0] < 1 or vec.shape[1] != n:
+                raise Exception("\n\n%s: vectors must be a complex128 array of shape (nvec, %d)" % (who, n))
+            vec = np.ascontiguousarray(vec)
+            nvec = vec.shape[0]
+        elif states is not None:
+            st = np.array(list(states))
+            if st.ndim != 1 or st.size < 1 or not np.issubdtype(st.dtype, np.integer):
+                raise Exception("\n\n%s: states must be a non-empty list of integers" % who)
+            if st.min() < 0 or st.max() >= n:
+                raise Exception("\n\n%s: state index out of range [0, %d)" % (who, n))
+            st = np.ascontiguousarray(st, dtype=np.int32)
+            nvec = st.size
+        else:
+            if not _is_int(n_vectors) or n_vectors < 1:
+                raise Exception("\n\n%s: n_vectors must be a positive integer" % who)
+            nvec = int(n_vectors)
+        if not _is_int(seed) or not 0 <= seed < 2 ** 64:
+            raise Exception("\n\n%s: seed must be an integer in [0, 2^64)" % who)
+        return vec, st, nvec
+
     def kpm_moments(self, n_moments, k_list=None, vectors=None, n_vectors=8, seed=0, states=None, bounds=None):
         """Extension: Chebyshev moments mu_m = <v|T_m(H~(k))|v> / <v|v>, m < n_moments, of the rescaled sparse Hamiltonian
         H~ = (H - b) / a, a = (emax - emin) / 2, b = (emax + emin) / 2 (the kernel polynomial method; Weisse et al., Rev. Mod.
@@ -1542,30 +1630,7 @@ class tb_model(object):
         n_moments / 2 sparse products per block of 8 vectors; fixed-order sums on the device: two calls give the same bits."""
         if not _is_int(n_moments) or n_moments < 1:
             raise Exception("\n\nkpm_moments: n_moments must be a positive integer")
-        if vectors is not None and states is not None:
-            raise Exception("\n\nkpm_moments: give either vectors or states, not both")
-        n = self._nsta
-        vec = st = None
-        if vectors is not None:
-            vec = np.asarray(vectors)
-            if vec.dtype != np.complex128 or vec.ndim != 2 or vec.shape[0] < 1 or vec.shape[1] != n:
-                raise Exception("\n\nkpm_moments: vectors must be a complex128 array of shape (nvec, %d)" % n)
-            vec = np.ascontiguousarray(vec)
-            nvec = vec.shape[0]
-        elif states is not None:
-            st = np.array(list(states))
-            if st.ndim != 1 or st.size < 1 or not np.issubdtype(st.dtype, np.integer):
-                raise Exception("\n\nkpm_moments: states must be a non-empty list of integers")
-            if st.min() < 0 or st.max() >= n:
-                raise Exception("\n\nkpm_moments: state index out of range [0, %d)" % n)
-            st = np.ascontiguousarray(st, dtype=np.int32)
-            nvec = st.size
-        else:
-            if not _is_int(n_vectors) or n_vectors < 1:
-                raise Exception("\n\nkpm_moments: n_vectors must be a positive integer")
-            nvec = int(n_vectors)
-        if not _is_int(seed) or not 0 <= seed < 2 ** 64:
-            raise Exception("\n\nkpm_moments: seed must be an integer in [0, 2^64)")
+        vec, st, nvec = self._kpm_start("kpm_moments", vectors, n_vectors, seed, states)
         bounds = self._kpm_bounds_arg(bounds)
         k, nk = self._kpm_k(k_list)
         sp = self._sparse_model()
@@ -1601,6 +1666,67 @@ class tb_model(object):
         if k_list is not None:
             mu = mu.mean(axis=0)
         return kpm_reconstruct(mu, energies, bnd, kernel)
+
+    def kpm_double_moments(self, n_moments, dirs, k_list, vectors=None, n_vectors=8, seed=0, states=None, bounds=None):
+        """Extension: the double Chebyshev moments of the Kubo-Bastin conductivity on the sparse operator, for models of any
+        size with a periodic axis (dim_k = 0 raises):
+
+            mu_mn = <v| V^a T_m(H~(k)) V^b T_n(H~(k)) |v> / <v|v>,   m, n < n_moments,   (a, b) = dirs (a == b allowed),
+
+        H~ = (H - b) / a, a = (emax - emin) / 2, b = (emax + emin) / 2 as in `kpm_moments`, V^a = dH/dk_a in reduced
+        coordinates for a periodic axis a in [0, dim_k): the matrix `_gen_dham(k, a)` returns.  Returns `(mu, (emin, emax))`,
+        mu complex `(nk, nvec, n_moments, n_moments)`.  Start vectors, bounds and the random-vector numbering (q * nvec + v at
+        the k-point with index q) as in `kpm_moments`.  3 n_moments sparse products per block of 8 vectors, a contraction of
+        n_moments^2 nsta multiply-adds per vector and a device workspace of n_moments * nsta * 128 bytes; fixed-order sums:
+        two calls give the same bits.  Bounds that do not contain the spectrum raise, naming the Gershgorin interval."""
+        if not _is_int(n_moments) or n_moments < 1:
+            raise Exception("\n\nkpm_double_moments: n_moments must be a positive integer")
+        if self._dim_k < 1:
+            raise Exception("\n\nkpm_double_moments needs a model with dim_k >= 1: the velocity operator is dH/dk.")
+        dirs = list(dirs)
+        if len(dirs) != 2 or not all(_is_int(d) for d in dirs):
+            raise Exception("\n\nkpm_double_moments: dirs must be two integer axes.")
+        if min(dirs) < 0 or max(dirs) >= self._dim_k:
+            raise Exception("\n\nkpm_double_moments: dirs must be axes in [0, dim_k)")
+        vec, st, nvec = self._kpm_start("kpm_double_moments", vectors, n_vectors, seed, states)
+        bounds = self._kpm_bounds_arg(bounds)
+        k, nk = self._kpm_k(k_list)
+        sp = self._sparse_model()
+        emin, emax = self._kpm_bounds(bounds, sp)
+        M = int(n_moments)
+        mu = np.empty((nk, nvec, M, M), dtype=complex)
+        _lib.check(_lib.lib.tbk_kpm_double_moments(sp, _lib.dptr(k), nk, M, emin, emax, int(dirs[0]), int(dirs[1]), nvec,
+                                                   None if vec is None else _lib.dptr(vec.view(float)), _lib.iptr(st), int(seed),
+                                                   _lib.dptr(mu.view(float))))
+        return mu, (emin, emax)
+
+    def kpm_conductivity(self, energies, n_moments, dirs, k_list, n_vectors=8, seed=0, kernel="jackson", bounds=None, kT=0.0,
+                         return_error=False, states=None):
+        """Extension: the DC conductivity sigma_ab(E_F), (a, b) = dirs, at the Fermi levels `energies` by the Chebyshev
+        expansion of the Kubo-Bastin formula, the longitudinal (a == b) and the Hall component alike, float `(nE,)`:
+
+            sigma_ab(E_F) = nsta * Re mean_samples G_ab(E_F),
+
+        G_ab of `kpm_conductivity_reconstruct` from `kpm_double_moments`, the samples being the `n_vectors` random-phase
+        vectors per k-point of `k_list` (the stochastic trace).  Reduced coordinates: V^a = dH/dk_a as in
+        `optical_conductivity_mesh`; for dim_k = 2 sigma_ab is the sheet conductance of the model's cell in units of e^2/h
+        (no spin-degeneracy factor), and the Cartesian tensor is A^T sigma A / V_c in units of e^2/h x length^(2 - dim_k),
+        A = the periodic lattice vectors as rows, V_c = sqrt(det(A A^T)).  Sign: in a gap sigma_01 = -C, C the Chern number
+        of the occupied bands as `berry_curvature_mesh(mesh, occ, dirs=(0, 1)) / (2 pi)` gives it -- the sign of its
+        docstring's sigma_xy = -(e^2/h) I / 2 pi.  return_error=True: `(sigma, err)` with the standard error of the mean over
+        the k x vector samples.  states (a list of state indices) replaces the random vectors by unit vectors;
+        `range(nsta)` is the exact trace.  The resolution is ~ pi a / n_moments (Jackson kernel): a plateau needs a gap
+        several times that."""
+        mu, bnd = self.kpm_double_moments(n_moments, dirs, k_list, n_vectors=n_vectors, seed=seed, states=states, bounds=bounds)
+        samples = mu.reshape(-1, mu.shape[-2], mu.shape[-1])
+        n = self._nsta
+        sigma = n * kpm_conductivity_reconstruct(samples.mean(axis=0), energies, bnd, kernel, kT=kT).real
+        if not return_error:
+            return sigma
+        each = n * kpm_conductivity_reconstruct(samples, energies, bnd, kernel, kT=kT).real
+        ns = each.shape[0]
+        err = each.std(axis=0, ddof=1) / np.sqrt(ns) if ns > 1 else np.full(sigma.shape, np.nan)
+        return sigma, err
 
     # ------------------------------------------------------------------ k generators (host)
     def k_uniform_mesh(self, mesh_size):
