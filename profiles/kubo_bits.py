@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""A fixed list of Kubo-formula calls (berry_curvature*, orbital_moment, orbital_magnetization_mesh, optical_conductivity_mesh)
-that reaches every routed form of DESIGN.md sections 11 to 13, every output saved to one .npz:
+"""A fixed list of Kubo-formula calls (berry_curvature*, orbital_moment, orbital_magnetization_mesh, optical_conductivity_mesh,
+spin_berry_curvature, shift_current*, injection_current_mesh, quantum_geometric_tensor*) that reaches every routed form of DESIGN.md
+sections 11 to 13, 15, 17 and 20, every output saved to one .npz:
 
     TBK_LIBRARY=<libtbk.so> python profiles/kubo_bits.py out.npz      run the calls with that library (a fresh process each)
     python profiles/kubo_bits.py --compare a.npz b.npz                compare two runs as uint64 views (NaN and infinity patterns too)
@@ -58,6 +59,9 @@ MODELS = {
     "haldane_4x4_n32": (lambda: supercell(4), list(range(16)), [24, 20]),
     "random_n36": (lambda: hp.random_model(tb.tb_model, 36, 2, 1, 12), list(range(18)), [12, 10]),
     "random_n80": (lambda: hp.random_model(tb.tb_model, 40, 2, 2, 13), list(range(40)), [8, 6]),
+    # three directions at the last size of the LDS forms (80 KiB in k_opt_pairs and k_qgt_lds<3>) and at the first wide size
+    "random3d_n32": (lambda: hp.random_model(tb.tb_model, 16, 3, 2, 14), list(range(16)), [6, 5, 4]),
+    "random3d_n33": (lambda: hp.random_model(tb.tb_model, 33, 3, 1, 15), list(range(16)), [4, 3, 2]),
 }
 
 out = {}
@@ -90,6 +94,9 @@ for name, (make, occ, mesh) in MODELS.items():
         keep(tag + "orb mesh occ", m.orbital_magnetization_mesh(mesh, occ=occ, dirs=dirs))
         keep(tag + "orb mesh fermi", m.orbital_magnetization_mesh(mesh, fermi_levels=few, dirs=dirs))
         keep(tag + "orb mesh kT", m.orbital_magnetization_mesh(mesh, fermi_levels=few, kT=0.05, dirs=dirs))
+        if m._nspin == 2:
+            keep(tag + "spin curv list", m.spin_berry_curvature(k, dirs=dirs))
+            keep(tag + "spin curv list occ", m.spin_berry_curvature(k, spin=0, occ=occ, dirs=dirs))
     if name in ("haldane_n2", "kane_mele_n4", "silicon_n8"):
         keep(name + " curv mesh fermi5000", m.berry_curvature_mesh(mesh, fermi_levels=many))
         keep(name + " orb mesh fermi5000", m.orbital_magnetization_mesh(mesh, fermi_levels=many))
@@ -99,6 +106,18 @@ for name, (make, occ, mesh) in MODELS.items():
         for dirs in ((0, 0), (0, 1), None):
             keep("%s optics %s kT%g" % (name, dirs, kT),
                  m.optical_conductivity_mesh(mesh, omega, 0.03, fermi_level=mu, kT=kT, dirs=dirs))
+    one = (dk - 1, 0, dk - 1)
+    keep(name + " shift list", m.shift_current(k, occ, one))
+    keep(name + " shift list aaa", m.shift_current(k, occ, (0, 0, 0)))
+    for kT in (0.0, 0.05):
+        for dirs in (None, one):
+            keep("%s shift %s kT%g" % (name, dirs, kT), m.shift_current_mesh(mesh, omega, 0.03, fermi_level=mu, kT=kT, dirs=dirs))
+            keep("%s injection %s kT%g" % (name, dirs, kT),
+                 m.injection_current_mesh(mesh, omega, 0.03, fermi_level=mu, kT=kT, dirs=dirs))
+    keep(name + " qgt list", m.quantum_geometric_tensor(k))
+    keep(name + " qgt list occ", m.quantum_geometric_tensor(k, occ=occ))
+    keep(name + " qgt mesh", m.quantum_geometric_tensor_mesh(mesh))
+    keep(name + " qgt mesh occ", m.quantum_geometric_tensor_mesh(mesh, occ=occ))
     print(name, len(out), flush=True)
 
 np.savez(sys.argv[1], **out)

@@ -1,10 +1,13 @@
 // tbk_kubo.h -- what the Kubo-formula translation units share beyond the d H formula of tbk_dham.h (DESIGN.md sections 11 to 14):
-//   device   the contraction of the solver's eigenvectors with d_a H, d_b H (k_kubo_lds up to 32 states; k_kubo_wsp, k_kubo_contract and
-//            k_kubo_occ_sum from 33), templates over a policy Q that says what a (point, band) lane keeps of a pair; the n = 2 mesh
-//            source; the T = 0 Fermi scan k_kubo_fermi and the row sum k_kubo_rows
+//   device   the rotation of d H into the eigenbasis for several points in LDS (kubo_lds_load, kubo_lds_dut, kubo_lds_ut,
+//            kubo_lds_rotate: every kernel up to 32 states here, in tbk_qgt.hip and in tbk_pairs.h); the contraction of the solver's
+//            eigenvectors with d_a H, d_b H (k_kubo_lds up to 32 states; k_kubo_wsp, k_kubo_contract and k_kubo_occ_sum from 33),
+//            templates over a policy Q that says what a (point, band) lane keeps of a pair; the n = 2 mesh source; the T = 0 Fermi
+//            scan k_kubo_fermi and the row sum k_kubo_rows
 //   host     the argument checks, the mesh planes, the sort of the Fermi levels and the chunk pipeline (KuboChunks, kubo_for_chunks)
-// tbk_curv.hip and tbk_orbmag.hip use all of it, tbk_optics.hip the chunk pipeline.  The library is built without relocatable device
-// code, so every kernel here is a template or static: each unit that launches one holds its own definition and host stub.
+// tbk_curv.hip and tbk_orbmag.hip use all of it, tbk_qgt.hip and tbk_pairs.h (tbk_optics.hip, tbk_shift.hip) the rotation and the
+// chunk pipeline.  The library is built without relocatable device code, so every kernel here is a template or static: each unit
+// that launches one holds its own definition and host stub.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -150,7 +153,52 @@ template <class Q>
 struct kubo_contract_policy<Q, std::void_t<typename Q::Contract>> {
     using type = typename Q::Contract;
 };
-//
+
+// ---------------------------------------------------------------- the rotation into the eigenbasis in LDS (up to 32 states)
+// What every kernel that holds U and d H of np points in LDS shares (k_kubo_lds; k_qgt_lds; tbk_pairs.h's pair_lds_ops for k_opt_pairs
+// and k_sh_pairs): matrices of n^2 per point, point p at offset p n^2, one element per lane and step of 256.  Each kernel keeps its
+// own buffer layout and says which buffers D, T and U are, and passes nn = n^2 beside n (formed once, in the kernel: k_kubo_lds
+// compiles to 16 VGPRs more where these functions form it again).
+// U[p][b][i] = component i of eigenvector b of point ik0 + p, from evec[b][nk][n]; also(e) runs for every element e the lane loads
+template <class Also>
+__device__ __forceinline__ void kubo_lds_load(cd* U, const cd* __restrict__ evec, const int64_t nk, const int64_t ik0, const int np,
+                                              const int n, const int nn, const Also& also) {
+    for (int e = threadIdx.x; e < np * nn; e += 256) {
+        const int p = e / nn, r = e - p * nn, b = r / n, i = r - b * n;
+        U[e] = evec[((int64_t)b * nk + ik0 + p) * n + i];
+        also(e);
+    }
+}
+// T = D U^T
+__device__ __forceinline__ void kubo_lds_dut(cd* T, const cd* D, const cd* U, const int np, const int n, const int nn) {
+    for (int e = threadIdx.x; e < np * nn; e += 256) {
+        const int p = e / nn, r = e - p * nn, i = r / n, mm = r - i * n;
+        const cd* dr = D + p * nn + i * n;
+        const cd* um = U + p * nn + mm * n;
+        cd acc{0.0, 0.0};
+        for (int j = 0; j < n; ++j) cfma(acc, dr[j], um[j]);
+        T[e] = acc;
+    }
+}
+// D := conj(U) T   (reads U, T only)
+__device__ __forceinline__ void kubo_lds_ut(cd* D, const cd* U, const cd* T, const int np, const int n, const int nn) {
+    for (int e = threadIdx.x; e < np * nn; e += 256) {
+        const int p = e / nn, r = e - p * nn, b = r / n, mm = r - b * n;
+        const cd* ub = U + p * nn + b * n;
+        const cd* tc = T + p * nn + mm;
+        cd acc{0.0, 0.0};
+        for (int i = 0; i < n; ++i) cfmac(acc, ub[i], tc[i * n]);
+        D[e] = acc;
+    }
+}
+// D := conj(U) D U^T through T, behind a barrier of the caller's; D is ready for every lane on return
+__device__ __forceinline__ void kubo_lds_rotate(cd* D, cd* T, const cd* U, const int np, const int n, const int nn) {
+    kubo_lds_dut(T, D, U, np, n, nn);
+    __syncthreads();
+    kubo_lds_ut(D, U, T, np, n, nn);
+    __syncthreads();
+}
+
 // Up to 32 states: ONE kernel, P = min(64, 4096 / (4 n^2)) points per workgroup, everything of a point in LDS (64 KiB):
 // U (its eigenvectors, read once from HBM), D = d_{d0} H and X = d_{d1} H (built from the non-empty slots), T = D U^T, then
 // D := V^{d0} = conj(U) T, T := X U^T, and one lane per (point, band) forms V^{d1} from T on the fly and feeds Q.
@@ -170,12 +218,10 @@ __global__ __launch_bounds__(256) void k_kubo_lds(const ModelView mv, const doub
     cd* D = L + P * nn;
     cd* T = L + 2 * P * nn;
     cd* X = L + 3 * P * nn;
-    for (int e = threadIdx.x; e < np * nn; e += 256) {
-        const int p = e / nn, r = e - p * nn, b = r / n, i = r - b * n;
-        U[e] = evec[((int64_t)b * nk + ik0 + p) * n + i];
+    kubo_lds_load(U, evec, nk, ik0, np, n, nn, [&](const int e) {
         D[e] = cd{0.0, 0.0};
         X[e] = cd{0.0, 0.0};
-    }
+    });
     __syncthreads();
     for (int e = threadIdx.x; e < np * mv.nnz; e += 256) {
         const int p = e / mv.nnz;
@@ -203,32 +249,8 @@ __global__ __launch_bounds__(256) void k_kubo_lds(const ModelView mv, const doub
         T = t;
         __syncthreads();
     }
-    for (int e = threadIdx.x; e < np * nn; e += 256) {            // T = D U^T
-        const int p = e / nn, r = e - p * nn, i = r / n, mm = r - i * n;
-        const cd* dr = D + p * nn + i * n;
-        const cd* um = U + p * nn + mm * n;
-        cd acc{0.0, 0.0};
-        for (int j = 0; j < n; ++j) cfma(acc, dr[j], um[j]);
-        T[e] = acc;
-    }
-    __syncthreads();
-    for (int e = threadIdx.x; e < np * nn; e += 256) {            // D := V^{d0} = conj(U) T   (reads U, T only)
-        const int p = e / nn, r = e - p * nn, b = r / n, mm = r - b * n;
-        const cd* ub = U + p * nn + b * n;
-        const cd* tc = T + p * nn + mm;
-        cd acc{0.0, 0.0};
-        for (int i = 0; i < n; ++i) cfmac(acc, ub[i], tc[i * n]);
-        D[e] = acc;
-    }
-    __syncthreads();
-    for (int e = threadIdx.x; e < np * nn; e += 256) {            // T := X U^T
-        const int p = e / nn, r = e - p * nn, i = r / n, mm = r - i * n;
-        const cd* xr = X + p * nn + i * n;
-        const cd* um = U + p * nn + mm * n;
-        cd acc{0.0, 0.0};
-        for (int j = 0; j < n; ++j) cfma(acc, xr[j], um[j]);
-        T[e] = acc;
-    }
+    kubo_lds_rotate(D, T, U, np, n, nn);                            // D := V^{d0}
+    kubo_lds_dut(T, X, U, np, n, nn);                               // T := X U^T
     __syncthreads();
     double* share = (double*)X;                                    // (X is dead: the band shares, NSET np n <= 2 P n^2 doubles)
     for (int e = threadIdx.x; e < np * n; e += 256) {

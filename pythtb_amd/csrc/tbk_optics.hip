@@ -9,31 +9,46 @@
 // so a pair is a RECORD of 1 + ns + na doubles: eps (-1: the pair adds nothing), the symmetric weights A = c Re P_ab (a <= b) and
 // the antisymmetric ones B = c Im P_ab (a < b) of the components asked for.
 //
-// Pipeline, in chunks of a fixed number of points (tbk_kubo.h's chunk pipeline: kKuboChunkBytes of eigenvectors, here also
-// kOptRecBytes of records): the device k generator, the eigen-solver with vectors, then the PAIR stage writes the chunk's records at a fixed stride of n (n - 1) / 2 per point
+// Pipeline, in chunks of a fixed number of points (tbk_pairs.h's sweep driver on tbk_kubo.h's chunk pipeline: kKuboChunkBytes of
+// eigenvectors, kPairRecBytes of records): the device k generator, the eigen-solver with vectors, then the PAIR stage writes the
+// chunk's records at a fixed stride of n (n - 1) / 2 per point
 //   n <= 32    k_opt_pairs: U, d_d H for every direction asked for, and V^d = conj(U) d_d H U^T of several points in LDS
-//   n > 32     k_opt_wsp (W^d = d_d H U^T from the sparse slots), k_opt_vprod (V^d = conj(U) W^d, LDS tiles), k_opt_pairs_wide
+//   n > 32     k_pair_wsp (W^d = d_d H U^T from the sparse slots), k_opt_vprod (V^d = conj(U) W^d, LDS tiles), k_opt_pairs_wide
 // and the FREQUENCY stage k_opt_omega (two frequencies per lane, the records read as wave-uniform values) adds each k-group's sums
 // into part[G][row]; k_opt_rows sums the G groups in a fixed order.  Every partition depends on the mesh, n, dim_k, n_omega and the
 // components alone, and nothing uses atomics: two calls give the same bits on any machine.
-// (opt_pair_of, opt_weight, k_opt_vprod, opt_rcp and k_opt_rows live in tbk_pairs.h, which tbk_shift.hip shares.)
+// This unit holds the components (OptFields), the record writer and the frequency kernel; the pair stage around the record writer and
+// the sweep driver live in tbk_pairs.h, which tbk_shift.hip shares.
 #include <math.h>
 #include <string.h>
 #include "tbk_pairs.h"
 
-static const size_t kOptRecBytes = (size_t)256 << 20;    // pair records per chunk
-static const int kOptTile = 512;                         // frequencies per workgroup of k_opt_omega (two per lane)
-static const int64_t kOptPartCap = (int64_t)1 << 24;     // doubles of part[G][rows]: G shrinks as the frequencies grow
-static const int kOptGroupsMax = 1024;                   // k-groups G at most
 #define OPT_LDS_CD 5120                                  // c128 of LDS per workgroup of k_opt_pairs at most (80 KiB)
 
 // The components of one call: the velocity matrices of nd directions dir[] are formed; record field f < ns is A of the direction
-// pair (dir[fa[f]], dir[fb[f]]), field ns + f is B of (dir[fa[ns + f]], dir[fb[ns + f]]).
+// pair (dir[fa[f]], dir[fb[f]]), field ns + f is B of (dir[fa[ns + f]], dir[fb[ns + f]]).  As the SLOTS of tbk_pairs.h: operator d
+// is d_{dir[d]} H.
 struct OptFields {
     int nd;
     int dir[3];
     int ns, na;
     int fa[9], fb[9];
+    __host__ __device__ int nops() const { return nd; }
+    __device__ __forceinline__ cd one(const ModelView& mv, const int d, const int4 z4, const double (&kk)[4], const cd (&z)[4]) const {
+        cd h, v0, v1;
+        dham_terms(mv, z4.x & 0xffff, z4.x >> 16, z4.y, z4.z, kk, z, dir[d], dir[d], h, v0, v1);
+        return v0;
+    }
+    __device__ __forceinline__ void all(const ModelView& mv, const int4 z4, const double (&kk)[4], const cd (&z)[4],
+                                        cd (&sv)[3][256]) const {
+        for (int d = 0; d < nd; d += 2) {                          // dham_terms gives two directions per walk
+            cd h, v0, v1;
+            const int d1 = d + 1 < nd ? d + 1 : d;
+            dham_terms(mv, z4.x & 0xffff, z4.x >> 16, z4.y, z4.z, kk, z, dir[d], dir[d1], h, v0, v1);
+            sv[d][threadIdx.x] = v0;
+            if (d + 1 < nd) sv[d + 1][threadIdx.x] = v1;
+        }
+    }
 };
 
 // one record at r: vel(d, 0) = V^{dir[d]}_nm, vel(d, 1) = V^{dir[d]}_mn
@@ -56,60 +71,18 @@ __device__ __forceinline__ void opt_record(double* __restrict__ r, const OptFiel
 }
 
 // ---------------------------------------------------------------- pair stage, 1 .. 32 states
-// P points per workgroup; per point U (its eigenvectors, read once from HBM) and nd + 1 matrices in LDS.  For direction d, buffer d
-// takes d_d H (from the non-empty slots), buffer d + 1 takes T = d_d H U^T, then buffer d := V^d = conj(U) T; after the last
-// direction buffers 0 .. nd - 1 hold V^0 .. V^{nd-1}.  One lane per (point, pair) then writes the records.
+// P points per workgroup; per point U and nd + 1 matrices in LDS (pair_lds_ops): buffers 0 .. nd - 1 end up holding V^0 .. V^{nd-1}.
+// One lane per (point, pair) then writes the records.
 static inline int opt_lds_points(int n, int nd) { return std::max(1, std::min(64, OPT_LDS_CD / ((nd + 2) * n * n))); }
 __global__ __launch_bounds__(256) void k_opt_pairs(const ModelView mv, const double* __restrict__ k, const cd* __restrict__ evec,
                                                    const double* __restrict__ eval, const int64_t nk, const OptFields F, const int P,
                                                    const double mu, const double kT, double* __restrict__ rec) {
     extern __shared__ cd L[];
-    const int n = mv.nsta, nn = n * n, nd = F.nd;
+    const int n = mv.nsta, nn = n * n;
     const int64_t ik0 = (int64_t)blockIdx.x * P;
     const int np = (int)std::min<int64_t>(P, nk - ik0);
-    cd* U = L;
-    cd* Bf = L + P * nn;                                           // buffer j at Bf + j P nn, j = 0 .. nd
-    for (int e = threadIdx.x; e < np * nn; e += 256) {
-        const int p = e / nn, r = e - p * nn, b = r / n, i = r - b * n;
-        U[e] = evec[((int64_t)b * nk + ik0 + p) * n + i];
-    }
-    for (int d = 0; d < nd; ++d) {
-        cd* S = Bf + d * P * nn;
-        cd* T = Bf + (d + 1) * P * nn;
-        for (int e = threadIdx.x; e < np * nn; e += 256) S[e] = cd{0.0, 0.0};
-        __syncthreads();
-        for (int e = threadIdx.x; e < np * mv.nnz; e += 256) {
-            const int p = e / mv.nnz;
-            const int4 z4 = mv.nz[e - p * mv.nnz];
-            const int a = z4.x & 0xffff, b = z4.x >> 16;
-            double kk[4];
-            cd z[4];
-            k_phases(mv, k, ik0 + p, kk, z);
-            cd h, v0, v1;
-            dham_terms(mv, a, b, z4.y, z4.z, kk, z, F.dir[d], F.dir[d], h, v0, v1);
-            S[p * nn + a * n + b] = v0;
-            S[p * nn + b * n + a] = cconj(v0);
-        }
-        __syncthreads();
-        for (int e = threadIdx.x; e < np * nn; e += 256) {        // T = d_d H U^T
-            const int p = e / nn, r = e - p * nn, i = r / n, mm = r - i * n;
-            const cd* dr = S + p * nn + i * n;
-            const cd* um = U + p * nn + mm * n;
-            cd acc{0.0, 0.0};
-            for (int j = 0; j < n; ++j) cfma(acc, dr[j], um[j]);
-            T[e] = acc;
-        }
-        __syncthreads();
-        for (int e = threadIdx.x; e < np * nn; e += 256) {        // S := V^d = conj(U) T
-            const int p = e / nn, r = e - p * nn, b = r / n, mm = r - b * n;
-            const cd* ub = U + p * nn + b * n;
-            const cd* tc = T + p * nn + mm;
-            cd acc{0.0, 0.0};
-            for (int i = 0; i < n; ++i) cfmac(acc, ub[i], tc[i * n]);
-            S[e] = acc;
-        }
-        __syncthreads();
-    }
+    pair_lds_ops(mv, k, evec, nk, ik0, np, P, F, L);
+    const cd* Bf = L + P * nn;                                     // buffer j at Bf + j P nn
     const int npair = n * (n - 1) / 2, R = 1 + F.ns + F.na;
     for (int e = threadIdx.x; e < np * npair; e += 256) {
         const int p = e / npair, q = e - p * npair;
@@ -126,61 +99,7 @@ __global__ __launch_bounds__(256) void k_opt_pairs(const ModelView mv, const dou
     }
 }
 
-// ---------------------------------------------------------------- pair stage, 33 .. 2048 states
-// W^d[ik][i][m] = sum_j d_d H_ij u_m[j] of the nd directions from the non-empty slots (the form of k_curv_wsp): workgroup (point, block
-// of 256 columns), lane m owns column m of every W^d; the slot values are computed once per point and staged in LDS.  wt[ik][d][n][n].
-__global__ __launch_bounds__(256) void k_opt_wsp(const ModelView mv, const double* __restrict__ k, const cd* __restrict__ evec,
-                                                 const int64_t nk, const OptFields F, cd* __restrict__ wt) {
-    __shared__ int sab[256];
-    __shared__ cd sv[3][256];
-    const int n = mv.nsta, nd = F.nd;
-    const int64_t ik = blockIdx.x, nn = (int64_t)n * n;
-    const int m = blockIdx.y * 256 + threadIdx.x;
-    const bool live = m < n;
-    cd* w = wt + ik * nd * nn;
-    if (live)
-        for (int d = 0; d < nd; ++d)
-            for (int i = 0; i < n; ++i) w[d * nn + (int64_t)i * n + m] = cd{0.0, 0.0};
-    double kk[4];
-    cd z[4];
-    k_phases(mv, k, ik, kk, z);
-    const cd* u = evec + ((int64_t)(live ? m : 0) * nk + ik) * n;
-    for (int q0 = 0; q0 < mv.nnz; q0 += 256) {
-        __syncthreads();
-        if (q0 + (int)threadIdx.x < mv.nnz) {
-            const int4 z4 = mv.nz[q0 + threadIdx.x];
-            for (int d = 0; d < nd; d += 2) {
-                cd h, v0, v1;
-                const int d1 = d + 1 < nd ? d + 1 : d;
-                dham_terms(mv, z4.x & 0xffff, z4.x >> 16, z4.y, z4.z, kk, z, F.dir[d], F.dir[d1], h, v0, v1);
-                sv[d][threadIdx.x] = v0;
-                if (d + 1 < nd) sv[d + 1][threadIdx.x] = v1;
-            }
-            sab[threadIdx.x] = z4.x;
-        }
-        __syncthreads();
-        const int cnt = min(256, mv.nnz - q0);
-        if (!live) continue;
-        for (int q = 0; q < cnt; ++q) {
-            const int a = sab[q] & 0xffff, b = sab[q] >> 16;
-            const cd ub = u[b], ua = u[a];
-            for (int d = 0; d < nd; ++d) {
-                const cd v = sv[d][q];
-                cd* pa = w + d * nn + (int64_t)a * n + m;
-                cd t = *pa;
-                cfma(t, v, ub);
-                *pa = t;
-                if (a != b) {
-                    cd* pb = w + d * nn + (int64_t)b * n + m;
-                    cd s = *pb;
-                    cfma(s, cconj(v), ua);
-                    *pb = s;
-                }
-            }
-        }
-    }
-}
-
+// ---------------------------------------------------------------- pair stage, 33 .. 2048 states (behind tbk_pairs.h's k_pair_wsp, k_opt_vprod)
 // one lane per (point, pair): the records from vt
 __global__ __launch_bounds__(256) void k_opt_pairs_wide(const double* __restrict__ eval, const cd* __restrict__ vt, const int64_t nk,
                                                         const int n, const OptFields F, const double mu, const double kT,
@@ -201,7 +120,7 @@ __global__ __launch_bounds__(256) void k_opt_pairs_wide(const double* __restrict
 }
 
 // ---------------------------------------------------------------- frequency stage
-// Workgroup (tile of kOptTile frequencies, k-group g): lane t takes w[tile + t] and w[tile + 256 + t] and walks the records of the
+// Workgroup (tile of kPairTile frequencies, k-group g): lane t takes w[tile + t] and w[tile + 256 + t] and walks the records of the
 // points [g nk / G, (g + 1) nk / G) of the chunk in order.  Per lane and frequency the sums
 //   x_f = sum A_f G+.x (f < NS) or B_f G-.x,   y_f = sum A_f (r+ + r-) or B_f (r+ - r-)     (G+-.y = eta (r+ +- r-))
 // go to part[g][row], row = (2 f + {0: x, 1: y}) nw + w: written by the first chunk, added to by the later ones (stream order).
@@ -210,7 +129,7 @@ __global__ __launch_bounds__(256) void k_opt_omega(const double* __restrict__ re
                                                    const double* __restrict__ omega, const int nw, const double eta,
                                                    const int accumulate, double* __restrict__ part) {
     constexpr int NF = NS + NA, R = 1 + NF;
-    const int base = blockIdx.x * kOptTile;
+    const int base = blockIdx.x * kPairTile;
     if (base + (int)(threadIdx.x & ~63u) >= nw) return;            // a wavefront without a frequency (uniform)
     const int g = blockIdx.y;
     int wi[2];
@@ -276,27 +195,18 @@ static int opt_omega_launch(tbk_ctx* ctx, dim3 grid, const double* rec, int64_t 
 
 extern "C" int tbk_optical_cond_mesh(tbk_model* m, const int32_t* mesh, int nomega, const double* omega, double eta, double mu,
                                      double kT, int dir0, int dir1, double* out) {
-    TBK_REQUIRE(m && mesh && omega && out, TBK_EINVAL, "tbk_optical_cond_mesh: null argument");
+    const char* fn = "tbk_optical_cond_mesh";
+    TBK_REQUIRE(m && mesh && omega && out, TBK_EINVAL, "%s: null argument", fn);
     const int dk = m->dim_k;
-    TBK_REQUIRE(dk >= 1 && dk <= 3, TBK_EINVAL, "tbk_optical_cond_mesh: dim_k=%d (meshes of 1, 2 or 3 dimensions)", dk);
-    TBK_REQUIRE(nomega >= 1 && nomega <= 65536, TBK_EINVAL, "tbk_optical_cond_mesh: nomega=%d (1..65536 frequencies)", nomega);
-    for (int j = 0; j < nomega; ++j)
-        TBK_REQUIRE(std::isfinite(omega[j]), TBK_EINVAL, "tbk_optical_cond_mesh: frequency %d is not finite", j);
-    TBK_REQUIRE(std::isfinite(eta) && eta > 0.0, TBK_EINVAL, "tbk_optical_cond_mesh: eta must be finite and > 0");
-    TBK_REQUIRE(std::isfinite(kT) && kT >= 0.0, TBK_EINVAL, "tbk_optical_cond_mesh: kT must be finite and >= 0");
-    TBK_REQUIRE(std::isfinite(mu), TBK_EINVAL, "tbk_optical_cond_mesh: the Fermi level must be finite");
+    int64_t npts;
+    int rc = pair_sweep_check(fn, m, mesh, nomega, omega, eta, mu, kT, npts);
+    if (rc) return rc;
     const bool full = dir0 == -1 && dir1 == -1;
     TBK_REQUIRE(full || (dir0 >= 0 && dir0 < dk && dir1 >= 0 && dir1 < dk), TBK_EINVAL,
-                "tbk_optical_cond_mesh: dirs (%d, %d) must be axes in [0, %d), or both -1 for the full tensor", dir0, dir1, dk);
-    int64_t npts = 1;
-    for (int d = 0; d < dk; ++d) {
-        TBK_REQUIRE(mesh[d] >= 1, TBK_EINVAL, "tbk_optical_cond_mesh: mesh[%d]=%d", d, mesh[d]);
-        npts *= mesh[d];
-    }
+                "%s: dirs (%d, %d) must be axes in [0, %d), or both -1 for the full tensor", fn, dir0, dir1, dk);
     const int n = m->nsta;
-    const int64_t npair = (int64_t)n * (n - 1) / 2;
     const int64_t nout = full ? (int64_t)nomega * dk * dk : (int64_t)nomega;   // complex values
-    if (npair == 0) {
+    if (n < 2) {                                                   // no pair
         std::fill(out, out + 2 * nout, 0.0);
         return TBK_OK;
     }
@@ -322,81 +232,38 @@ extern "C" int tbk_optical_cond_mesh(tbk_model* m, const int32_t* mesh, int nome
         F.fa[0] = F.fa[1] = 0;
         F.fb[0] = F.fb[1] = 1;
     }
-    const int nf = F.ns + F.na, R = 1 + nf;
-    // chunk, k-groups and tiles: functions of (mesh, n, dim_k, nomega, components) only
-    const size_t vb = (size_t)n * n * sizeof(cd), rb = (size_t)npair * R * sizeof(double);
-    const int64_t chunk = std::min<int64_t>(kubo_chunk_len(n, npts), std::max<int64_t>(1, (int64_t)(kOptRecBytes / rb)));
-    const int64_t nrows = 2 * (int64_t)nf * nomega;
-    const int G = (int)std::max<int64_t>(1, std::min<int64_t>({kOptPartCap / nrows, (int64_t)kOptGroupsMax, chunk}));
-    const unsigned ntile = (unsigned)((nomega + kOptTile - 1) / kOptTile);
-    const bool wide = n > 32;
-    const size_t omb = al256((size_t)nomega * sizeof(double)), partb = al256((size_t)G * nrows * sizeof(double)),
-                 rowb = al256((size_t)nrows * sizeof(double)), wb = wide ? (size_t)chunk * F.nd * vb : 0;
-    KuboChunks cw(n, dk, chunk, (size_t)chunk * rb, wb, wb);   // the records, then W^d and V^d of the wide form
+    const int nf = F.ns + F.na;
     tbk_ctx* ctx = m->ctx;
-    TBK_HIP(hipSetDevice(ctx->device));
-    void* base = nullptr;
-    int rc = tbk_ctx_scratch(ctx, 256 + omb + partb + rowb + cw.bytes(), &base);
-    if (rc) return rc;
-    unsigned char* p = (unsigned char*)base + 256;
-    double* om_dev = (double*)p;
-    p += omb;
-    double* part = (double*)p;
-    p += partb;
-    double* rows = (double*)p;
-    cw.base = p + rowb;
-    double* rec = cw.extra<double>(0);
-    cd* wt = cw.extra<cd>(1);
-    cd* vt = cw.extra<cd>(2);
-    TBK_HIP(hipMemcpyAsync(om_dev, omega, (size_t)nomega * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     const int P = opt_lds_points(n, F.nd);
     const size_t lds = (size_t)(F.nd + 2) * P * n * n * sizeof(cd);
-    if (!wide && lds > 64 * 1024)
+    if (n <= 32 && lds > 64 * 1024) {
+        TBK_HIP(hipSetDevice(ctx->device));
         TBK_HIP(hipFuncSetAttribute((const void*)k_opt_pairs, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    rc = kubo_for_chunks(m, cw, nullptr, mesh, npts, [&](int64_t first, int64_t cnt, const double* kc, const double* ec, const cd* vc) -> int {
-        if (!wide) {
+    }
+    std::vector<double> sums;
+    rc = pair_sweep(m, mesh, npts, nomega, omega, 1 + nf, 2 * (int64_t)nf * nomega, F.nd, "opt_rows", sums,
+                    [&](const PairSweep& w, int64_t first, int64_t cnt, const double* kc, const double* ec, const cd* vc) -> int {
+        if (n <= 32) {
             ProfScope ps(ctx, "opt_pairs");
             hipLaunchKernelGGL(k_opt_pairs, dim3((unsigned)((cnt + P - 1) / P)), dim3(256), lds, ctx->stream, m->view,
-                               kc, vc, ec, cnt, F, P, mu, kT, rec);
+                               kc, vc, ec, cnt, F, P, mu, kT, w.rec);
             TBK_HIP(hipGetLastError());
         } else {
-            {
-                ProfScope ps(ctx, "opt_wide");
-                hipLaunchKernelGGL(k_opt_wsp, dim3((unsigned)cnt, (unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, m->view,
-                                   kc, vc, cnt, F, wt);
-                TBK_HIP(hipGetLastError());
-            }
-            {
-                // cnt nd <= 3 kKuboChunkBytes / (33^2 16 B) < 65536 (the grid's z limit)
-                ProfScope ps(ctx, "opt_wide");
-                const unsigned t = (unsigned)((n + 15) / 16);
-                hipLaunchKernelGGL(k_opt_vprod, dim3(t, t, (unsigned)(cnt * F.nd)), dim3(256), 0, ctx->stream, vc,
-                                   (const cd*)wt, cnt, n, F.nd, vt);
-                TBK_HIP(hipGetLastError());
-            }
-            ProfScope ps(ctx, "opt_pairs");
-            hipLaunchKernelGGL(k_opt_pairs_wide, dim3(nblk(cnt * npair)), dim3(256), 0, ctx->stream, ec, (const cd*)vt,
-                               cnt, n, F, mu, kT, rec);
-            TBK_HIP(hipGetLastError());
+            int r2 = pair_wide_stage<3>(m, F, cnt, kc, vc, w.wt, w.vt, "opt_wide", "opt_pairs", [&] {
+                hipLaunchKernelGGL(k_opt_pairs_wide, dim3(nblk(cnt * w.npair)), dim3(256), 0, ctx->stream, ec, (const cd*)w.vt, cnt, n, F,
+                                   mu, kT, w.rec);
+            });
+            if (r2) return r2;
         }
         ProfScope ps(ctx, "opt_omega");
-        const dim3 grid(ntile, (unsigned)G);
+        const dim3 grid(w.ntile, (unsigned)w.G);
         const int acc = first > 0 ? 1 : 0;
-        if (F.ns == 1 && F.na == 0) return opt_omega_launch<1, 0>(ctx, grid, rec, cnt, npair, G, om_dev, nomega, eta, acc, part);
-        if (F.ns == 1 && F.na == 1) return opt_omega_launch<1, 1>(ctx, grid, rec, cnt, npair, G, om_dev, nomega, eta, acc, part);
-        if (F.ns == 3) return opt_omega_launch<3, 1>(ctx, grid, rec, cnt, npair, G, om_dev, nomega, eta, acc, part);
-        return opt_omega_launch<6, 3>(ctx, grid, rec, cnt, npair, G, om_dev, nomega, eta, acc, part);
+        if (F.ns == 1 && F.na == 0) return opt_omega_launch<1, 0>(ctx, grid, w.rec, cnt, w.npair, w.G, w.om, nomega, eta, acc, w.part);
+        if (F.ns == 1 && F.na == 1) return opt_omega_launch<1, 1>(ctx, grid, w.rec, cnt, w.npair, w.G, w.om, nomega, eta, acc, w.part);
+        if (F.ns == 3) return opt_omega_launch<3, 1>(ctx, grid, w.rec, cnt, w.npair, w.G, w.om, nomega, eta, acc, w.part);
+        return opt_omega_launch<6, 3>(ctx, grid, w.rec, cnt, w.npair, w.G, w.om, nomega, eta, acc, w.part);
     });
     if (rc) return rc;
-    {
-        ProfScope ps(ctx, "opt_rows");
-        hipLaunchKernelGGL(k_opt_rows, dim3((unsigned)nrows), dim3(256), 0, ctx->stream, (const double*)part, G, nrows,
-                           1.0 / (double)npts, rows);
-        TBK_HIP(hipGetLastError());
-    }
-    std::vector<double> sums((size_t)nrows);
-    TBK_HIP(hipMemcpyAsync(sums.data(), rows, (size_t)nrows * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    TBK_HIP(hipStreamSynchronize(ctx->stream));
     // S_ab = i SA - SB, S_ba = i SA + SB with SA = (x_A, eta y_A), SB = (x_B, eta y_B) of the pair (a, b), a < b; S_aa = i SA
     auto X = [&](int f, int w) { return sums[(size_t)(2 * f) * nomega + w]; };
     auto Y = [&](int f, int w) { return eta * sums[(size_t)(2 * f + 1) * nomega + w]; };

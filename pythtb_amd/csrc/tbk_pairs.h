@@ -1,8 +1,20 @@
 // tbk_pairs.h -- what the two translation units that turn (point, pair) records into frequency sums share (tbk_optics.hip, DESIGN.md
-// section 12; tbk_shift.hip, section 17): the index of a pair, the occupation weight, the dense product V^d = conj(U) W^d of the wide
-// pair stage, the reciprocal of the frequency stage and the sum over k-groups.  Kernels are static: each unit holds its own copy.
+// section 12; tbk_shift.hip, section 17):
+//   device   the index of a pair, the occupation weight, the operators of a unit in the eigenbasis (pair_lds_ops up to 32 states;
+//            k_pair_wsp and k_opt_vprod from 33), the reciprocal of the frequency stage and the sum over k-groups
+//   host     the three launches of the wide pair stage (pair_wide_stage), the chunk plan of the records (pair_chunks) and the driver
+//            of a frequency sweep over a mesh (pair_sweep_check, pair_sweep)
+// A unit says what its operators are with a SLOTS type (OptFields, ShiftPass): nops() operators, one(mv, op, z4, kk, z) the value of
+// operator op at the non-empty slot z4 (ModelView.nz), and all(mv, z4, kk, z, sv) the values of every operator at once into
+// sv[op][threadIdx.x].  The unit keeps its record writer and its frequency kernel.  Kernels are static or templates: each unit holds
+// its own copy.
 #pragma once
 #include "tbk_kubo.h"
+
+static const size_t kPairRecBytes = (size_t)256 << 20;   // pair records per chunk
+static const int kPairTile = 512;                        // frequencies per workgroup of a frequency kernel (two per lane)
+static const int64_t kPairPartCap = (int64_t)1 << 24;    // doubles of part[G][rows]: G shrinks as the frequencies grow
+static const int kPairGroupsMax = 1024;                  // k-groups G at most
 
 // the pair (i, j), i < j, of index q in the row-major order of the strict upper triangle of n x n
 __device__ __forceinline__ void opt_pair_of(const int n, const int64_t q, int& i, int& j) {
@@ -25,7 +37,90 @@ __device__ __forceinline__ double opt_weight(const double en, const double em, c
     return exp(h - M) * expm1(-2.0 * h) / den / eps;
 }
 
-// V^d = conj(U) W^d for every (point, direction) z = ik nd + d (blockIdx.z): 16 x 16 output tiles, the 16-wide slices of conj(U) and
+// ---------------------------------------------------------------- pair stage, 1 .. 32 states
+// The operators of np <= P points in the eigenbasis, in the dynamic LDS L of (nops + 2) P n^2: U (the eigenvectors, read once from
+// HBM) at L and buffer j at L + (1 + j) P n^2, j = 0 .. nops.  For operator op, buffer op takes its values from the non-empty slots,
+// buffer op + 1 takes T = (operator) U^T, then buffer op := conj(U) T; after the last one buffers 0 .. nops - 1 hold the operators.
+template <class Slots>
+__device__ __forceinline__ void pair_lds_ops(const ModelView& mv, const double* __restrict__ k, const cd* __restrict__ evec,
+                                             const int64_t nk, const int64_t ik0, const int np, const int P, const Slots& sl, cd* L) {
+    const int n = mv.nsta, nn = n * n, nops = sl.nops();
+    cd* U = L;
+    cd* Bf = L + P * nn;
+    kubo_lds_load(U, evec, nk, ik0, np, n, nn, [](int) {});
+    for (int op = 0; op < nops; ++op) {
+        cd* S = Bf + op * P * nn;
+        cd* T = Bf + (op + 1) * P * nn;
+        for (int e = threadIdx.x; e < np * nn; e += 256) S[e] = cd{0.0, 0.0};
+        __syncthreads();
+        for (int e = threadIdx.x; e < np * mv.nnz; e += 256) {
+            const int p = e / mv.nnz;
+            const int4 z4 = mv.nz[e - p * mv.nnz];
+            const int a = z4.x & 0xffff, b = z4.x >> 16;
+            double kk[4];
+            cd z[4];
+            k_phases(mv, k, ik0 + p, kk, z);
+            const cd v = sl.one(mv, op, z4, kk, z);
+            S[p * nn + a * n + b] = v;
+            S[p * nn + b * n + a] = cconj(v);
+        }
+        __syncthreads();
+        kubo_lds_rotate(S, T, U, np, n, nn);
+    }
+}
+
+// ---------------------------------------------------------------- pair stage, 33 .. 2048 states
+// W^op[ik][i][m] = sum_j (operator op)_ij u_m[j] of the nops <= MAXOPS operators from the non-empty slots (the form of k_kubo_wsp):
+// workgroup (point, block of 256 columns), lane m owns column m of every W^op; the slot values are computed once per point and staged
+// in LDS.  wt[ik][op][n][n].
+template <int MAXOPS, class Slots>
+__global__ __launch_bounds__(256) void k_pair_wsp(const ModelView mv, const double* __restrict__ k, const cd* __restrict__ evec,
+                                                  const int64_t nk, const Slots sl, cd* __restrict__ wt) {
+    __shared__ int sab[256];
+    __shared__ cd sv[MAXOPS][256];
+    const int n = mv.nsta, nops = sl.nops();
+    const int64_t ik = blockIdx.x, nn = (int64_t)n * n;
+    const int m = blockIdx.y * 256 + threadIdx.x;
+    const bool live = m < n;
+    cd* w = wt + ik * nops * nn;
+    if (live)
+        for (int d = 0; d < nops; ++d)
+            for (int i = 0; i < n; ++i) w[d * nn + (int64_t)i * n + m] = cd{0.0, 0.0};
+    double kk[4];
+    cd z[4];
+    k_phases(mv, k, ik, kk, z);
+    const cd* u = evec + ((int64_t)(live ? m : 0) * nk + ik) * n;
+    for (int q0 = 0; q0 < mv.nnz; q0 += 256) {
+        __syncthreads();
+        if (q0 + (int)threadIdx.x < mv.nnz) {
+            const int4 z4 = mv.nz[q0 + threadIdx.x];
+            sl.all(mv, z4, kk, z, sv);
+            sab[threadIdx.x] = z4.x;
+        }
+        __syncthreads();
+        const int cnt = min(256, mv.nnz - q0);
+        if (!live) continue;
+        for (int q = 0; q < cnt; ++q) {
+            const int a = sab[q] & 0xffff, b = sab[q] >> 16;
+            const cd ub = u[b], ua = u[a];
+            for (int d = 0; d < nops; ++d) {
+                const cd v = sv[d][q];
+                cd* pa = w + d * nn + (int64_t)a * n + m;
+                cd t = *pa;
+                cfma(t, v, ub);
+                *pa = t;
+                if (a != b) {
+                    cd* pb = w + d * nn + (int64_t)b * n + m;
+                    cd s = *pb;
+                    cfma(s, cconj(v), ua);
+                    *pb = s;
+                }
+            }
+        }
+    }
+}
+
+// V^d = conj(U) W^d for every (point, operator) z = ik nd + d (blockIdx.z): 16 x 16 output tiles, the 16-wide slices of conj(U) and
 // W^d staged in LDS.  vt[ik][d][n][n], V^d[b][m] = <b| d_d H |m>.
 static __global__ __launch_bounds__(256) void k_opt_vprod(const cd* __restrict__ evec, const cd* __restrict__ wt, const int64_t nk, const int n,
                                                    const int nd, cd* __restrict__ vt) {
@@ -65,4 +160,110 @@ static __global__ __launch_bounds__(256) void k_opt_rows(const double* __restric
     for (int g = threadIdx.x; g < G; g += 256) acc += part[(int64_t)g * nrows + blockIdx.x];
     const double t = block_sum(acc, red);
     if (threadIdx.x == 0) rows[blockIdx.x] = t * inv;
+}
+
+// ---------------------------------------------------------------- host side
+// The wide pair stage of a chunk: k_pair_wsp (W = (operator) U^T from the slots, wt), k_opt_vprod (V = conj(U) W, vt), then the unit's
+// record kernel, launched by pairs() on vt.
+template <int MAXOPS, class Slots, class Pairs>
+static int pair_wide_stage(tbk_model* m, const Slots& sl, int64_t cnt, const double* kc, const cd* vc, cd* wt, cd* vt,
+                           const char* wide_label, const char* pairs_label, Pairs&& pairs) {
+    tbk_ctx* ctx = m->ctx;
+    const int n = m->nsta, nops = sl.nops();
+    {
+        ProfScope ps(ctx, wide_label);
+        hipLaunchKernelGGL((k_pair_wsp<MAXOPS, Slots>), dim3((unsigned)cnt, (unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream,
+                           m->view, kc, vc, cnt, sl, wt);
+        TBK_HIP(hipGetLastError());
+    }
+    {
+        // cnt nops <= 6 kKuboChunkBytes / (33^2 16 B) < 65536 (the grid's z limit)
+        ProfScope ps(ctx, wide_label);
+        const unsigned t = (unsigned)((n + 15) / 16);
+        hipLaunchKernelGGL(k_opt_vprod, dim3(t, t, (unsigned)(cnt * nops)), dim3(256), 0, ctx->stream, vc, (const cd*)wt, cnt, n, nops, vt);
+        TBK_HIP(hipGetLastError());
+    }
+    ProfScope ps(ctx, pairs_label);
+    pairs();
+    TBK_HIP(hipGetLastError());
+    return TBK_OK;
+}
+
+// The chunk workspace of a pair stage over nk points of a model of at least two states: records of R doubles per pair (extra 0),
+// then W and V of the wide form's wops operators (extras 1 and 2).  The chunk holds at most kKuboChunkBytes of eigenvectors and
+// kPairRecBytes of records.
+static KuboChunks pair_chunks(int n, int dk, int64_t nk, int R, int wops) {
+    const size_t rb = (size_t)n * (n - 1) / 2 * R * sizeof(double);
+    const int64_t chunk = std::min<int64_t>(kubo_chunk_len(n, nk), std::max<int64_t>(1, (int64_t)(kPairRecBytes / rb)));
+    const size_t wb = n > 32 ? (size_t)chunk * wops * n * n * sizeof(cd) : 0;
+    return KuboChunks(n, dk, chunk, (size_t)chunk * rb, wb, wb);
+}
+
+// The argument checks that the frequency sweeps over a mesh share, in the name of the unit's function fn; npts = the points of the
+// mesh.  The unit checks its pointers before and its directions after.
+static int pair_sweep_check(const char* fn, tbk_model* m, const int32_t* mesh, int nomega, const double* omega, double eta, double mu,
+                            double kT, int64_t& npts) {
+    const int dk = m->dim_k;
+    TBK_REQUIRE(dk >= 1 && dk <= 3, TBK_EINVAL, "%s: dim_k=%d (meshes of 1, 2 or 3 dimensions)", fn, dk);
+    TBK_REQUIRE(nomega >= 1 && nomega <= 65536, TBK_EINVAL, "%s: nomega=%d (1..65536 frequencies)", fn, nomega);
+    for (int j = 0; j < nomega; ++j) TBK_REQUIRE(std::isfinite(omega[j]), TBK_EINVAL, "%s: frequency %d is not finite", fn, j);
+    TBK_REQUIRE(std::isfinite(eta) && eta > 0.0, TBK_EINVAL, "%s: eta must be finite and > 0", fn);
+    TBK_REQUIRE(std::isfinite(kT) && kT >= 0.0, TBK_EINVAL, "%s: kT must be finite and >= 0", fn);
+    TBK_REQUIRE(std::isfinite(mu), TBK_EINVAL, "%s: the Fermi level must be finite", fn);
+    npts = 1;
+    for (int d = 0; d < dk; ++d) {
+        TBK_REQUIRE(mesh[d] >= 1, TBK_EINVAL, "%s: mesh[%d]=%d", fn, d, mesh[d]);
+        npts *= mesh[d];
+    }
+    return TBK_OK;
+}
+
+// One frequency sweep over the npts points of a mesh (checked; at least two states): sums[row] = (1 / npts) sum over the points of
+// what body adds to row `row` of the nrows rows (nomega per field).  The chunk, the G k-groups and the tiles are functions of (mesh, n,
+// dim_k, nomega, R, nrows, wops) only.  body(w, first, cnt, k, eval, evec) writes the chunk's records (R doubles per pair at w.rec,
+// through w.wt and w.vt from 33 states) and adds every k-group's sums into w.part[G][nrows] with grid (w.ntile, w.G): written by the
+// first chunk, added to by the later ones (stream order).
+struct PairSweep {
+    int64_t npair, nrows;
+    int G;
+    unsigned ntile;
+    const double* om;      // the nomega frequencies on the device
+    double *part, *rec;
+    cd *wt, *vt;
+};
+template <class Body>
+static int pair_sweep(tbk_model* m, const int32_t* mesh, int64_t npts, int nomega, const double* omega, int R, int64_t nrows, int wops,
+                      const char* rows_label, std::vector<double>& sums, Body&& body) {
+    const int n = m->nsta;
+    KuboChunks cw = pair_chunks(n, m->dim_k, npts, R, wops);
+    const int G = (int)std::max<int64_t>(1, std::min<int64_t>({kPairPartCap / nrows, (int64_t)kPairGroupsMax, cw.chunk}));
+    const size_t omb = al256((size_t)nomega * sizeof(double)), partb = al256((size_t)G * nrows * sizeof(double)),
+                 rowb = al256((size_t)nrows * sizeof(double));
+    tbk_ctx* ctx = m->ctx;
+    TBK_HIP(hipSetDevice(ctx->device));
+    void* base = nullptr;
+    int rc = tbk_ctx_scratch(ctx, 256 + omb + partb + rowb + cw.bytes(), &base);
+    if (rc) return rc;
+    unsigned char* p = (unsigned char*)base + 256;
+    double* om_dev = (double*)p;
+    double* part = (double*)(p + omb);
+    double* rows = (double*)(p + omb + partb);
+    cw.base = p + omb + partb + rowb;
+    const PairSweep w{(int64_t)n * (n - 1) / 2, nrows, G, (unsigned)((nomega + kPairTile - 1) / kPairTile), om_dev, part,
+                      cw.extra<double>(0), cw.extra<cd>(1), cw.extra<cd>(2)};
+    TBK_HIP(hipMemcpyAsync(om_dev, omega, (size_t)nomega * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    rc = kubo_for_chunks(m, cw, nullptr, mesh, npts, [&](int64_t first, int64_t cnt, const double* kc, const double* ec, const cd* vc) -> int {
+        return body(w, first, cnt, kc, ec, vc);
+    });
+    if (rc) return rc;
+    {
+        ProfScope ps(ctx, rows_label);
+        hipLaunchKernelGGL(k_opt_rows, dim3((unsigned)nrows), dim3(256), 0, ctx->stream, (const double*)part, G, nrows,
+                           1.0 / (double)npts, rows);
+        TBK_HIP(hipGetLastError());
+    }
+    sums.resize((size_t)nrows);
+    TBK_HIP(hipMemcpyAsync(sums.data(), rows, (size_t)nrows * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    TBK_HIP(hipStreamSynchronize(ctx->stream));
+    return TBK_OK;
 }

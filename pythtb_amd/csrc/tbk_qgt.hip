@@ -160,12 +160,10 @@ __global__ __launch_bounds__(256) void k_qgt_lds(const ModelView mv, const doubl
     cd* U = L;
     cd* T = L + P * nn;
     cd* V = L + 2 * P * nn;                                        // slot d at V + d P nn
-    for (int e = threadIdx.x; e < np * nn; e += 256) {
-        const int p = e / nn, r = e - p * nn, b = r / n, i = r - b * n;
-        U[e] = evec[((int64_t)b * nk + ik0 + p) * n + i];
+    kubo_lds_load(U, evec, nk, ik0, np, n, nn, [&](const int e) {
 #pragma unroll
         for (int d = 0; d < DK; ++d) V[d * P * nn + e] = cd{0.0, 0.0};
-    }
+    });
     __syncthreads();
     for (int e = threadIdx.x; e < np * mv.nnz; e += 256) {
         const int p = e / mv.nnz;
@@ -190,27 +188,7 @@ __global__ __launch_bounds__(256) void k_qgt_lds(const ModelView mv, const doubl
         }
     }
     __syncthreads();
-    for (int d = 0; d < DK; ++d) {
-        cd* D = V + d * P * nn;
-        for (int e = threadIdx.x; e < np * nn; e += 256) {        // T = D U^T
-            const int p = e / nn, r = e - p * nn, i = r / n, mm = r - i * n;
-            const cd* dr = D + p * nn + i * n;
-            const cd* um = U + p * nn + mm * n;
-            cd acc{0.0, 0.0};
-            for (int j = 0; j < n; ++j) cfma(acc, dr[j], um[j]);
-            T[e] = acc;
-        }
-        __syncthreads();
-        for (int e = threadIdx.x; e < np * nn; e += 256) {        // D := V^d = conj(U) T   (reads U, T only)
-            const int p = e / nn, r = e - p * nn, b = r / n, mm = r - b * n;
-            const cd* ub = U + p * nn + b * n;
-            const cd* tc = T + p * nn + mm;
-            cd acc{0.0, 0.0};
-            for (int i = 0; i < n; ++i) cfmac(acc, ub[i], tc[i * n]);
-            D[e] = acc;
-        }
-        __syncthreads();
-    }
+    for (int d = 0; d < DK; ++d) kubo_lds_rotate(V + d * P * nn, T, U, np, n, nn);   // slot d := V^d
     double* share = (double*)L;                                    // (U and T are dead)
     for (int e = threadIdx.x; e < np * n; e += 256) {
         const int p = e / n, b = e - p * n;

@@ -12,27 +12,25 @@
 //   D(eps, w) = (eta / pi) [1 / ((eps - w)^2 + eta^2) + 1 / ((eps + w)^2 + eta^2)]
 // The sums over (n in G1, m in G2) do not change when the solver's eigenvectors are rotated inside a group.
 //
-// Pipeline (tbk_kubo.h's chunk loop): the device k generator, the eigen-solver with vectors, then per current direction a one PASS:
+// Pipeline (tbk_pairs.h's sweep driver on tbk_kubo.h's chunk loop): the device k generator, the eigen-solver with vectors, then per
+// current direction a one PASS:
 // the PAIR stage writes a record (eps, fields...) per (point, pair i < j) -- eps = -1 for a pair that adds nothing, which is decided
 // before the walk over p -- and the FREQUENCY stage k_sh_omega adds each k-group's sums into part[G][row]; k_opt_rows sums the groups.
 //   n <= 32    k_sh_pairs: U, the V^d and W^{da} of the pass and one scratch matrix of several points in LDS
-//   n > 32     k_sh_wsp (d H U^T and d d H U^T from the sparse slots), k_opt_vprod (conj(U) times it), k_sh_pairs_wide
+//   n > 32     k_pair_wsp (d H U^T and d d H U^T from the sparse slots), k_opt_vprod (conj(U) times it), k_sh_pairs_wide
 // A pass of the full tensor holds at most 3 V + 3 W: at 32 states 8 matrices of 16 KiB with U and the scratch, 128 KiB of the CU's 160.
 // Every partition depends on the mesh, n, dim_k, n_omega and the components alone, and nothing uses atomics: two calls give the same bits.
 #include <math.h>
 #include <string.h>
 #include "tbk_pairs.h"
 
-static const size_t kShRecBytes = (size_t)256 << 20;     // pair records per chunk
-static const int kShTile = 512;                          // frequencies per workgroup of k_sh_omega (two per lane)
-static const int64_t kShPartCap = (int64_t)1 << 24;      // doubles of part[G][rows]
-static const int kShGroupsMax = 1024;                    // k-groups G at most
 #define SH_LDS_CD 4096                                   // c128 of LDS per workgroup of k_sh_pairs while more than one point fits
 
 // One pass: the current direction a and the light directions bdir[nb].  Operator j < nv is V^{vdir[j]}; operator nv + j (shift only) is
 // W^{bdir[j] a}.  Field f is the light pair (bdir[f1[f]], bdir[f2[f]]): one double (Im X, shift) or two (Re Y, Im Y; injection).
 // The small index lists are packed two bits per entry (sh_get, sh_set), so that no kernel indexes an argument array with a loop
 // variable: the pass stays in scalar registers.
+__host__ __device__ __forceinline__ int sh_get(const unsigned pk, const int i) { return (int)((pk >> (2 * i)) & 3u); }
 struct ShiftPass {
     int kind;   // 0 shift, 1 injection
     int a, ia;  // V^a is operator ia
@@ -40,9 +38,22 @@ struct ShiftPass {
     unsigned vdir, bdir, ib, f1, f2;
     __host__ __device__ int nops() const { return kind == 0 ? nv + nb : nv; }
     __host__ __device__ int nf() const { return kind == 0 ? nfld : 2 * nfld; }
+    // as the SLOTS of tbk_pairs.h: the slot value of operator op, d_{vdir[op]} H_ab or d_{bdir[op - nv]} d_a H_ab
+    __device__ __forceinline__ cd one(const ModelView& mv, const int op, const int4 z4, const double (&kk)[4], const cd (&z)[4]) const {
+        const int sa = z4.x & 0xffff, sb = z4.x >> 16;
+        if (op < nv) {
+            cd h, v0, v1;
+            dham_terms(mv, sa, sb, z4.y, z4.z, kk, z, sh_get(vdir, op), sh_get(vdir, op), h, v0, v1);
+            return v0;
+        }
+        return ddham_terms(mv, sa, sb, z4.y, z4.z, kk, z, sh_get(bdir, op - nv), a);
+    }
+    __device__ __forceinline__ void all(const ModelView& mv, const int4 z4, const double (&kk)[4], const cd (&z)[4],
+                                        cd (&sv)[6][256]) const {
+        for (int d = 0; d < nops(); ++d) sv[d][threadIdx.x] = one(mv, d, z4, kk, z);
+    }
 };
 
-__host__ __device__ __forceinline__ int sh_get(const unsigned pk, const int i) { return (int)((pk >> (2 * i)) & 3u); }
 static inline void sh_set(unsigned& pk, const int i, const int v) { pk = (pk & ~(3u << (2 * i))) | ((unsigned)v << (2 * i)); }
 
 // the weight of the pair (i, j), E_j >= E_i: f_i - f_j on a mesh; with a band set, +1 for i in occ and j outside, -1 the other way
@@ -152,21 +163,9 @@ __device__ __forceinline__ void sh_record(double* __restrict__ r, const ShiftPas
     }
 }
 
-// the slot value of operator op of the pass: d_{vdir[op]} H_ab, or d_{bdir[op - nv]} d_a H_ab
-__device__ __forceinline__ cd sh_slot(const ModelView& mv, const ShiftPass& S, const int op, const int4 z4, const double (&kk)[4],
-                                      const cd (&z)[4]) {
-    const int a = z4.x & 0xffff, b = z4.x >> 16;
-    if (op < S.nv) {
-        cd h, v0, v1;
-        dham_terms(mv, a, b, z4.y, z4.z, kk, z, sh_get(S.vdir, op), sh_get(S.vdir, op), h, v0, v1);
-        return v0;
-    }
-    return ddham_terms(mv, a, b, z4.y, z4.z, kk, z, sh_get(S.bdir, op - S.nv), S.a);
-}
-
 // ---------------------------------------------------------------- pair stage, 1 .. 32 states
-// P points per workgroup; per point U and nops + 1 matrices in LDS, as k_opt_pairs: buffer j takes operator j from the non-empty
-// slots, buffer j + 1 takes T = (operator) U^T, then buffer j := conj(U) T.  One lane per (point, pair) then walks p once.
+// P points per workgroup; per point U and nops + 1 matrices in LDS (pair_lds_ops), as k_opt_pairs.  One lane per (point, pair) then
+// walks p once.
 static inline int sh_lds_points(int n, int nops) { return std::max(1, std::min(64, SH_LDS_CD / ((nops + 2) * n * n))); }
 template <int KIND>
 __global__ __launch_bounds__(256) void k_sh_pairs(const ModelView mv, const double* __restrict__ k, const cd* __restrict__ evec,
@@ -174,51 +173,11 @@ __global__ __launch_bounds__(256) void k_sh_pairs(const ModelView mv, const doub
                                                   const double mu, const double kT, const int* __restrict__ occ,
                                                   double* __restrict__ rec) {
     extern __shared__ cd L[];
-    const int n = mv.nsta, nn = n * n, nops = S.nops();
+    const int n = mv.nsta, nn = n * n;
     const int64_t ik0 = (int64_t)blockIdx.x * P;
     const int np = (int)std::min<int64_t>(P, nk - ik0);
-    cd* U = L;
-    cd* Bf = L + P * nn;                                           // buffer j at Bf + j P nn, j = 0 .. nops
-    for (int e = threadIdx.x; e < np * nn; e += 256) {
-        const int p = e / nn, r = e - p * nn, b = r / n, i = r - b * n;
-        U[e] = evec[((int64_t)b * nk + ik0 + p) * n + i];
-    }
-    for (int op = 0; op < nops; ++op) {
-        cd* Sm = Bf + op * P * nn;
-        cd* T = Bf + (op + 1) * P * nn;
-        for (int e = threadIdx.x; e < np * nn; e += 256) Sm[e] = cd{0.0, 0.0};
-        __syncthreads();
-        for (int e = threadIdx.x; e < np * mv.nnz; e += 256) {
-            const int p = e / mv.nnz;
-            const int4 z4 = mv.nz[e - p * mv.nnz];
-            const int a = z4.x & 0xffff, b = z4.x >> 16;
-            double kk[4];
-            cd z[4];
-            k_phases(mv, k, ik0 + p, kk, z);
-            const cd v = sh_slot(mv, S, op, z4, kk, z);
-            Sm[p * nn + a * n + b] = v;
-            Sm[p * nn + b * n + a] = cconj(v);
-        }
-        __syncthreads();
-        for (int e = threadIdx.x; e < np * nn; e += 256) {        // T = (operator) U^T
-            const int p = e / nn, r = e - p * nn, i = r / n, mm = r - i * n;
-            const cd* dr = Sm + p * nn + i * n;
-            const cd* um = U + p * nn + mm * n;
-            cd acc{0.0, 0.0};
-            for (int j = 0; j < n; ++j) cfma(acc, dr[j], um[j]);
-            T[e] = acc;
-        }
-        __syncthreads();
-        for (int e = threadIdx.x; e < np * nn; e += 256) {        // buffer := conj(U) T
-            const int p = e / nn, r = e - p * nn, b = r / n, mm = r - b * n;
-            const cd* ub = U + p * nn + b * n;
-            const cd* tc = T + p * nn + mm;
-            cd acc{0.0, 0.0};
-            for (int i = 0; i < n; ++i) cfmac(acc, ub[i], tc[i * n]);
-            Sm[e] = acc;
-        }
-        __syncthreads();
-    }
+    pair_lds_ops(mv, k, evec, nk, ik0, np, P, S, L);
+    const cd* Bf = L + P * nn;                                     // buffer j at Bf + j P nn
     const int npair = n * (n - 1) / 2, R = 1 + S.nf();
     for (int e = threadIdx.x; e < np * npair; e += 256) {
         const int p = e / npair, q = e - p * npair;
@@ -238,55 +197,7 @@ __global__ __launch_bounds__(256) void k_sh_pairs(const ModelView mv, const doub
     }
 }
 
-// ---------------------------------------------------------------- pair stage, 33 .. 2048 states
-// (operator) U^T of the pass's operators from the non-empty slots, the form of k_opt_wsp: workgroup (point, block of 256 columns), lane m
-// owns column m of every product; the slot values are computed once per point and staged in LDS.  wt[ik][op][n][n].
-__global__ __launch_bounds__(256) void k_sh_wsp(const ModelView mv, const double* __restrict__ k, const cd* __restrict__ evec,
-                                                const int64_t nk, const ShiftPass S, cd* __restrict__ wt) {
-    __shared__ int sab[256];
-    __shared__ cd sv[6][256];
-    const int n = mv.nsta, nops = S.nops();
-    const int64_t ik = blockIdx.x, nn = (int64_t)n * n;
-    const int m = blockIdx.y * 256 + threadIdx.x;
-    const bool live = m < n;
-    cd* w = wt + ik * nops * nn;
-    if (live)
-        for (int d = 0; d < nops; ++d)
-            for (int i = 0; i < n; ++i) w[d * nn + (int64_t)i * n + m] = cd{0.0, 0.0};
-    double kk[4];
-    cd z[4];
-    k_phases(mv, k, ik, kk, z);
-    const cd* u = evec + ((int64_t)(live ? m : 0) * nk + ik) * n;
-    for (int q0 = 0; q0 < mv.nnz; q0 += 256) {
-        __syncthreads();
-        if (q0 + (int)threadIdx.x < mv.nnz) {
-            const int4 z4 = mv.nz[q0 + threadIdx.x];
-            for (int d = 0; d < nops; ++d) sv[d][threadIdx.x] = sh_slot(mv, S, d, z4, kk, z);
-            sab[threadIdx.x] = z4.x;
-        }
-        __syncthreads();
-        const int cnt = min(256, mv.nnz - q0);
-        if (!live) continue;
-        for (int q = 0; q < cnt; ++q) {
-            const int a = sab[q] & 0xffff, b = sab[q] >> 16;
-            const cd ub = u[b], ua = u[a];
-            for (int d = 0; d < nops; ++d) {
-                const cd v = sv[d][q];
-                cd* pa = w + d * nn + (int64_t)a * n + m;
-                cd t = *pa;
-                cfma(t, v, ub);
-                *pa = t;
-                if (a != b) {
-                    cd* pb = w + d * nn + (int64_t)b * n + m;
-                    cd s = *pb;
-                    cfma(s, cconj(v), ua);
-                    *pb = s;
-                }
-            }
-        }
-    }
-}
-
+// ---------------------------------------------------------------- pair stage, 33 .. 2048 states (behind tbk_pairs.h's k_pair_wsp, k_opt_vprod)
 // one lane per (point, pair): the records from vt[ik][op][n][n] (k_opt_vprod's).  Neighbouring lanes hold neighbouring columns j, so
 // the walk down column j is coalesced and row i is shared by most of a wavefront.
 template <int KIND>
@@ -312,7 +223,7 @@ __global__ __launch_bounds__(256) void k_sh_pairs_wide(const double* __restrict_
 }
 
 // ---------------------------------------------------------------- frequency stage
-// k_opt_omega's pattern for the one sum that is needed: workgroup (tile of kShTile frequencies, k-group g), lane t takes w[tile + t] and
+// k_opt_omega's pattern for the one sum that is needed: workgroup (tile of kPairTile frequencies, k-group g), lane t takes w[tile + t] and
 // w[tile + 256 + t] and walks the records of the points [g nk / G, (g + 1) nk / G) of the chunk in order; per lane and frequency
 //   y_f = sum field_f [1 / ((eps - w)^2 + eta^2) + 1 / ((eps + w)^2 + eta^2)]
 // for the NF fields f0 .. f0 + NF - 1 of records of R doubles goes to part[g][(row0 + f) nw + w]: written by the first chunk, added to by
@@ -322,7 +233,7 @@ __global__ __launch_bounds__(256) void k_sh_omega(const double* __restrict__ rec
                                                   const int f0, const int G, const double* __restrict__ omega, const int nw,
                                                   const double eta, const int accumulate, const int64_t nrows, const int row0,
                                                   double* __restrict__ part) {
-    const int base = blockIdx.x * kShTile;
+    const int base = blockIdx.x * kPairTile;
     if (base + (int)(threadIdx.x & ~63u) >= nw) return;            // a wavefront without a frequency (uniform)
     const int g = blockIdx.y;
     int wi[2];
@@ -457,28 +368,13 @@ static int sh_pair_stage(tbk_model* m, const ShiftPass& S, int64_t cnt, const do
         TBK_HIP(hipGetLastError());
         return TBK_OK;
     }
-    {
-        ProfScope ps(ctx, "shift_wide");
-        hipLaunchKernelGGL(k_sh_wsp, dim3((unsigned)cnt, (unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, m->view, kc, vc, cnt, S,
-                           wt);
-        TBK_HIP(hipGetLastError());
-    }
-    {
-        // cnt nops <= 6 kKuboChunkBytes / (33^2 16 B) < 65536 (the grid's z limit)
-        ProfScope ps(ctx, "shift_wide");
-        const unsigned t = (unsigned)((n + 15) / 16);
-        hipLaunchKernelGGL(k_opt_vprod, dim3(t, t, (unsigned)(cnt * nops)), dim3(256), 0, ctx->stream, vc, (const cd*)wt, cnt, n, nops, vt);
-        TBK_HIP(hipGetLastError());
-    }
-    ProfScope ps(ctx, "shift_pairs");
-    if (S.kind == 0)
-        hipLaunchKernelGGL(k_sh_pairs_wide<0>, dim3(nblk(cnt * npair)), dim3(256), 0, ctx->stream, ec, (const cd*)vt, cnt, n, S, mu, kT, occ,
-                           rec);
-    else
-        hipLaunchKernelGGL(k_sh_pairs_wide<1>, dim3(nblk(cnt * npair)), dim3(256), 0, ctx->stream, ec, (const cd*)vt, cnt, n, S, mu, kT, occ,
-                           rec);
-    TBK_HIP(hipGetLastError());
-    return TBK_OK;
+    return pair_wide_stage<6>(m, S, cnt, kc, vc, wt, vt, "shift_wide", "shift_pairs", [&] {
+        const dim3 grid(nblk(cnt * npair));
+        if (S.kind == 0)
+            hipLaunchKernelGGL(k_sh_pairs_wide<0>, grid, dim3(256), 0, ctx->stream, ec, (const cd*)vt, cnt, n, S, mu, kT, occ, rec);
+        else
+            hipLaunchKernelGGL(k_sh_pairs_wide<1>, grid, dim3(256), 0, ctx->stream, ec, (const cd*)vt, cnt, n, S, mu, kT, occ, rec);
+    });
 }
 
 template <int NF>
@@ -539,10 +435,7 @@ extern "C" int tbk_shift_list(tbk_model* m, const double* k, int64_t nk, int a, 
     }
     const ShiftPass S = sh_pass_one(0, a, b, c);
     const int64_t npair = (int64_t)n * (n - 1) / 2;
-    const size_t vb = (size_t)n * n * sizeof(cd), rb = (size_t)npair * 2 * sizeof(double);
-    const int64_t chunk = std::min<int64_t>(kubo_chunk_len(n, nk), std::max<int64_t>(1, (int64_t)(kShRecBytes / rb)));
-    const size_t wb = n > 32 ? (size_t)chunk * S.nops() * vb : 0;
-    KuboChunks cw(n, dk, chunk, (size_t)chunk * rb, wb, wb);
+    KuboChunks cw = pair_chunks(n, dk, nk, 2, S.nops());
     tbk_ctx* ctx = m->ctx;
     TBK_HIP(hipSetDevice(ctx->device));
     const size_t kb = al256((size_t)nk * dk * sizeof(double)), ob = al256((size_t)nk * sizeof(double)), mb = al256((size_t)n * sizeof(int));
@@ -573,29 +466,20 @@ extern "C" int tbk_shift_list(tbk_model* m, const double* k, int64_t nk, int a, 
 
 extern "C" int tbk_photocurrent_mesh(tbk_model* m, const int32_t* mesh, int kind, int nomega, const double* omega, double eta, double mu,
                                      double kT, int a, int b, int c, double* out) {
-    TBK_REQUIRE(m && mesh && omega && out, TBK_EINVAL, "tbk_photocurrent_mesh: null argument");
+    const char* fn = "tbk_photocurrent_mesh";
+    TBK_REQUIRE(m && mesh && omega && out, TBK_EINVAL, "%s: null argument", fn);
     const int dk = m->dim_k;
-    TBK_REQUIRE(kind == 0 || kind == 1, TBK_EINVAL, "tbk_photocurrent_mesh: kind=%d (0 shift, 1 injection)", kind);
-    TBK_REQUIRE(dk >= 1 && dk <= 3, TBK_EINVAL, "tbk_photocurrent_mesh: dim_k=%d (meshes of 1, 2 or 3 dimensions)", dk);
-    TBK_REQUIRE(nomega >= 1 && nomega <= 65536, TBK_EINVAL, "tbk_photocurrent_mesh: nomega=%d (1..65536 frequencies)", nomega);
-    for (int j = 0; j < nomega; ++j)
-        TBK_REQUIRE(std::isfinite(omega[j]), TBK_EINVAL, "tbk_photocurrent_mesh: frequency %d is not finite", j);
-    TBK_REQUIRE(std::isfinite(eta) && eta > 0.0, TBK_EINVAL, "tbk_photocurrent_mesh: eta must be finite and > 0");
-    TBK_REQUIRE(std::isfinite(kT) && kT >= 0.0, TBK_EINVAL, "tbk_photocurrent_mesh: kT must be finite and >= 0");
-    TBK_REQUIRE(std::isfinite(mu), TBK_EINVAL, "tbk_photocurrent_mesh: the Fermi level must be finite");
+    TBK_REQUIRE(kind == 0 || kind == 1, TBK_EINVAL, "%s: kind=%d (0 shift, 1 injection)", fn, kind);
+    int64_t npts;
+    int rc = pair_sweep_check(fn, m, mesh, nomega, omega, eta, mu, kT, npts);
+    if (rc) return rc;
     const bool full = a == -1 && b == -1 && c == -1;
     TBK_REQUIRE(full || (a >= 0 && a < dk && b >= 0 && b < dk && c >= 0 && c < dk), TBK_EINVAL,
-                "tbk_photocurrent_mesh: dirs (%d, %d, %d) must be axes in [0, %d), or all -1 for the full tensor", a, b, c, dk);
-    int64_t npts = 1;
-    for (int d = 0; d < dk; ++d) {
-        TBK_REQUIRE(mesh[d] >= 1, TBK_EINVAL, "tbk_photocurrent_mesh: mesh[%d]=%d", d, mesh[d]);
-        npts *= mesh[d];
-    }
+                "%s: dirs (%d, %d, %d) must be axes in [0, %d), or all -1 for the full tensor", fn, a, b, c, dk);
     const int n = m->nsta, cplx = kind == 1 ? 2 : 1;
-    const int64_t npair = (int64_t)n * (n - 1) / 2;
     const int64_t nout = (full ? (int64_t)nomega * dk * dk * dk : (int64_t)nomega) * cplx;   // doubles
     std::fill(out, out + nout, 0.0);
-    if (npair == 0) return TBK_OK;
+    if (n < 2) return TBK_OK;                                      // no pair
     ShiftPass pass[3];
     int npass = 0, row0[4] = {0, 0, 0, 0}, rmax = 0;
     if (full)
@@ -607,59 +491,29 @@ extern "C" int tbk_photocurrent_mesh(tbk_model* m, const int32_t* mesh, int kind
         rmax = std::max(rmax, 1 + pass[s].nf());
     }
     const int nft = row0[npass], nopmax = pass[0].nops();          // (every pass of a call has as many operators)
-    // chunk, k-groups and tiles: functions of (mesh, n, dim_k, nomega, components) only
-    const size_t vb = (size_t)n * n * sizeof(cd), rb = (size_t)npair * rmax * sizeof(double);
-    const int64_t chunk = std::min<int64_t>(kubo_chunk_len(n, npts), std::max<int64_t>(1, (int64_t)(kShRecBytes / rb)));
-    const int64_t nrows = (int64_t)nft * nomega;
-    const int G = (int)std::max<int64_t>(1, std::min<int64_t>({kShPartCap / nrows, (int64_t)kShGroupsMax, chunk}));
-    const unsigned ntile = (unsigned)((nomega + kShTile - 1) / kShTile);
-    const bool wide = n > 32;
-    const size_t omb = al256((size_t)nomega * sizeof(double)), partb = al256((size_t)G * nrows * sizeof(double)),
-                 rowb = al256((size_t)nrows * sizeof(double)), wb = wide ? (size_t)chunk * nopmax * vb : 0;
-    KuboChunks cw(n, dk, chunk, (size_t)chunk * rb, wb, wb);       // the records, then the two dense stages of the wide form
     tbk_ctx* ctx = m->ctx;
-    TBK_HIP(hipSetDevice(ctx->device));
-    void* base = nullptr;
-    int rc = tbk_ctx_scratch(ctx, 256 + omb + partb + rowb + cw.bytes(), &base);
-    if (rc) return rc;
-    unsigned char* p = (unsigned char*)base + 256;
-    double* om_dev = (double*)p;
-    p += omb;
-    double* part = (double*)p;
-    p += partb;
-    double* rows = (double*)p;
-    cw.base = p + rowb;
-    double* rec = cw.extra<double>(0);
-    TBK_HIP(hipMemcpyAsync(om_dev, omega, (size_t)nomega * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    rc = kubo_for_chunks(m, cw, nullptr, mesh, npts, [&](int64_t first, int64_t cnt, const double* kc, const double* ec, const cd* vc) -> int {
-        const dim3 grid(ntile, (unsigned)G);
+    std::vector<double> sums;
+    rc = pair_sweep(m, mesh, npts, nomega, omega, rmax, (int64_t)nft * nomega, nopmax, "shift_rows", sums,
+                    [&](const PairSweep& w, int64_t first, int64_t cnt, const double* kc, const double* ec, const cd* vc) -> int {
+        const dim3 grid(w.ntile, (unsigned)w.G);
         const int acc = first > 0 ? 1 : 0;
         for (int s = 0; s < npass; ++s) {
             const ShiftPass& S = pass[s];
-            int r2 = sh_pair_stage(m, S, cnt, kc, ec, vc, mu, kT, nullptr, cw.extra<cd>(1), cw.extra<cd>(2), rec);
+            int r2 = sh_pair_stage(m, S, cnt, kc, ec, vc, mu, kT, nullptr, w.wt, w.vt, w.rec);
             if (r2) return r2;
             ProfScope ps(ctx, "shift_omega");
             const int nf = S.nf(), R = 1 + nf;
             for (int f0 = 0; f0 < nf;) {
-                const int left = nf - f0, w = left >= 6 ? 6 : (left >= 3 ? 3 : (left >= 2 ? 2 : 1));
-                auto go = w == 6 ? sh_omega_launch<6> : (w == 3 ? sh_omega_launch<3> : (w == 2 ? sh_omega_launch<2> : sh_omega_launch<1>));
-                r2 = go(ctx, grid, rec, cnt, npair, R, f0, G, om_dev, nomega, eta, acc, nrows, row0[s] + f0, part);
+                const int left = nf - f0, wd = left >= 6 ? 6 : (left >= 3 ? 3 : (left >= 2 ? 2 : 1));
+                auto go = wd == 6 ? sh_omega_launch<6> : (wd == 3 ? sh_omega_launch<3> : (wd == 2 ? sh_omega_launch<2> : sh_omega_launch<1>));
+                r2 = go(ctx, grid, w.rec, cnt, w.npair, R, f0, w.G, w.om, nomega, eta, acc, w.nrows, row0[s] + f0, w.part);
                 if (r2) return r2;
-                f0 += w;
+                f0 += wd;
             }
         }
         return TBK_OK;
     });
     if (rc) return rc;
-    {
-        ProfScope ps(ctx, "shift_rows");
-        hipLaunchKernelGGL(k_opt_rows, dim3((unsigned)nrows), dim3(256), 0, ctx->stream, (const double*)part, G, nrows,
-                           1.0 / (double)npts, rows);
-        TBK_HIP(hipGetLastError());
-    }
-    std::vector<double> sums((size_t)nrows);
-    TBK_HIP(hipMemcpyAsync(sums.data(), rows, (size_t)nrows * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    TBK_HIP(hipStreamSynchronize(ctx->stream));
     const double pref = eta / M_PI;
     for (int w = 0; w < nomega; ++w)
         for (int s = 0; s < npass; ++s) {

@@ -19,6 +19,23 @@ def _is_int(a):
     return np.issubdtype(type(a), np.integer)        # pythtb.py:3950
 
 
+def _sweep_args(omega, eta, fermi_level, kT):
+    """The checked frequencies of a frequency sweep (`optical_conductivity_mesh`, the photocurrent meshes) as a contiguous
+    float array, after the checks of eta, kT and fermi_level that these calls share."""
+    w = np.array(omega, dtype=float)
+    if w.ndim != 1 or w.size < 1 or w.size > 65536:
+        raise Exception("\n\nomega must be a 1-D array of 1..65536 frequencies.")
+    if not np.all(np.isfinite(w)):
+        raise Exception("\n\nomega must be finite.")
+    if not np.isfinite(eta) or not eta > 0.0:
+        raise Exception("\n\neta must be finite and > 0.")
+    if not np.isfinite(kT) or not kT >= 0.0:
+        raise Exception("\n\nkT must be finite and >= 0.")
+    if not np.isfinite(fermi_level):
+        raise Exception("\n\nfermi_level must be finite.")
+    return np.ascontiguousarray(w)
+
+
 def kpm_reconstruct(mu, energies, bounds, kernel="jackson", lam=4.0):
     """Extension: the kernel-polynomial reconstruction of a density from its Chebyshev moments `mu` `(..., M)` (those of
     `tb_model.kpm_moments` for the same `bounds` = (emin, emax)) at `energies` inside the open interval (emin, emax):
@@ -827,18 +844,7 @@ class tb_model(object):
         if self._dim_k not in (1, 2, 3):
             raise Exception("\n\noptical_conductivity_mesh needs a model with dim_k 1, 2 or 3.")
         mesh, nk = self._mesh_arg(mesh_size)
-        w = np.array(omega, dtype=float)
-        if w.ndim != 1 or w.size < 1 or w.size > 65536:
-            raise Exception("\n\nomega must be a 1-D array of 1..65536 frequencies.")
-        if not np.all(np.isfinite(w)):
-            raise Exception("\n\nomega must be finite.")
-        w = np.ascontiguousarray(w)
-        if not np.isfinite(eta) or not eta > 0.0:
-            raise Exception("\n\neta must be finite and > 0.")
-        if not np.isfinite(kT) or not kT >= 0.0:
-            raise Exception("\n\nkT must be finite and >= 0.")
-        if not np.isfinite(fermi_level):
-            raise Exception("\n\nfermi_level must be finite.")
+        w = _sweep_args(omega, eta, fermi_level, kT)
         if dirs is None:
             d0 = d1 = -1
         else:
@@ -926,18 +932,7 @@ class tb_model(object):
         if self._dim_k not in (1, 2, 3):
             raise Exception("\n\n%s needs a model with dim_k 1, 2 or 3." % what)
         mesh, nk = self._mesh_arg(mesh_size)
-        w = np.array(omega, dtype=float)
-        if w.ndim != 1 or w.size < 1 or w.size > 65536:
-            raise Exception("\n\nomega must be a 1-D array of 1..65536 frequencies.")
-        if not np.all(np.isfinite(w)):
-            raise Exception("\n\nomega must be finite.")
-        w = np.ascontiguousarray(w)
-        if not np.isfinite(eta) or not eta > 0.0:
-            raise Exception("\n\neta must be finite and > 0.")
-        if not np.isfinite(kT) or not kT >= 0.0:
-            raise Exception("\n\nkT must be finite and >= 0.")
-        if not np.isfinite(fermi_level):
-            raise Exception("\n\nfermi_level must be finite.")
+        w = _sweep_args(omega, eta, fermi_level, kT)
         if dirs is None:
             a = b = c = -1
         else:

@@ -170,7 +170,8 @@ def test_haldane_two_states():
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("name", ["kane_mele", "silicon", "cubic16", "haldane_4x4", "haldane_5x5", "ribbon_20", "ribbon_100"])
+@pytest.mark.parametrize("name", ["kane_mele", "silicon", "cubic16", "haldane_4x4", "haldane_5x5", "ribbon_20", "ribbon_100",
+                                  "random3d_n32", "random3d_n33"])
 def test_models(name):
     if name == "kane_mele":
         m, mesh = hp.kane_mele(tb.tb_model), [20, 20]
@@ -182,6 +183,12 @@ def test_models(name):
         m, mesh = supercell(haldane(), 4), [48, 48]         # 2304 points: two chunks of 32-state eigenvectors
     elif name == "haldane_5x5":
         m, mesh = supercell(haldane(), 5), [8, 8]
+    elif name == "random3d_n32":
+        # three directions of 32 states: one point per workgroup and 80 KiB of LDS, above the default limit of a kernel
+        m, mesh = hp.random_model(tb.tb_model, 16, 3, 2, 21), [2, 2, 2]
+    elif name == "random3d_n33":
+        # the first wide shape: three operators, the 16-wide tiles of the dense product overhang by one
+        m, mesh = hp.random_model(tb.tb_model, 33, 3, 1, 22), [2, 2, 2]
     else:
         m, mesh = ribbon(int(name.split("_")[1])), [64]
     ev = levels(m, mesh)
