@@ -485,6 +485,22 @@ int tbk_kpm_double_moments(tbk_sparse* sp, const double* k, int64_t nk, int n_mo
 int tbk_sparse_velocity_bounds_host(int dim_k, int norb, int nspin, const double* orb, const double* onsite, int64_t nhop,
                                     const int32_t* hop_i, const int32_t* hop_j, const int32_t* hop_R, const double* hop_amp,
                                     double* vbound);
+/* ---- kernel polynomial method: operator functions and the local Chern marker ------------------------
+ * out[nk][nset][nvec][nsta] c128, out_s = sum_{m < ncoef} coeffs[s][m] T_m(H~(k)) v, coeffs[nset][ncoef] c128: a function of H applied
+ * to vectors (Chebyshev coefficients of a step: the Fermi projector; (2 - delta_m0) (-i)^m J_m(a t) e^{-i b t}: e^{-i H t}).  H~, the
+ * bounds, the start vectors and the random-vector numbering exactly as in tbk_kpm_moments; the result is not divided by <v|v>.
+ * ncoef - 1 sparse products per block of 8 vectors, every set accumulated in the same pass.  TBK_EINVAL, naming the bounds, when a
+ * norm <T_j v|T_j v> is not finite or exceeds (1 + 1e-6) <v|v>: (emin, emax) does not contain the spectrum.  TBK_ENOMEM, naming the
+ * byte count, when the device workspace (2 + nset vectors of nsta x 8 x 16 bytes, the values at k, the output) cannot be had.
+ * Fixed-order sums, no atomics on floating-point data: bit-reproducible.
+ * tbk_kpm_marker: out[nvec] c128, out_v = <s_v| F A F B F |s_v>, F = sum_m coeffs[m] T_m(H~) with REAL coeffs[ncoef] (F Hermitian),
+ * A = diag(da[nsta]), B = diag(db[nsta]), s_v the unit vector at states[v]; dim_k must be 0 (TBK_EINVAL).  With the coefficients of
+ * the Fermi projector and da, db two position coordinates, 4 pi Im out_v is the local Chern marker (Bianco, Resta, Phys. Rev. B 84,
+ * 241106).  2 (ncoef - 1) sparse products per block of 8 states; no vector leaves the device.  Guard and errors as above.        */
+int tbk_kpm_apply_series(tbk_sparse* sp, const double* k, int64_t nk, int ncoef, int nset, const double* coeffs, double emin,
+                         double emax, int nvec, const double* vectors, const int32_t* states, uint64_t seed, double* out);
+int tbk_kpm_marker(tbk_sparse* sp, int ncoef, const double* coeffs, double emin, double emax, const double* da, const double* db,
+                   int nvec, const int32_t* states, double* out);
 
 /* ---- multi-GPU: one process per GPU, k-points sharded, one gather ------
  * Thin RCCL wrappers (librccl is dlopen'ed on first use).  The 128-byte id is

@@ -1,6 +1,6 @@
 // tbk_kpm.h -- what the translation units of the kernel polynomial method share (tbk_kpm.hip: the operator and the single moments;
-// tbk_kpm_cond.hip: the double moments of the Kubo-Bastin conductivity): the operator's handle, the random-phase generator, the start
-// vectors and the fixed-order sums.  DESIGN.md sections 21 and 22.
+// tbk_kpm_cond.hip: the double moments of the Kubo-Bastin conductivity; tbk_kpm_series.hip: operator functions and the local Chern
+// marker): the operator's handle, the random-phase generator, the start vectors and the fixed-order sums.  DESIGN.md sections 21 to 23.
 #pragma once
 #include <algorithm>
 #include "tbk_internal.h"
@@ -22,6 +22,10 @@ struct tbk_sparse {
     const int4* R = nullptr;
     const double4* orb = nullptr;
 };
+
+// val[nnz] = the values of the operator at the k-point k_dev[dim_k] (device memory), on the context's stream (tbk_kpm.hip); a model
+// with dim_k = 0 needs none: its values are sp->amp
+int kpm_values_at(const tbk_sparse* sp, const double* k_dev, cd* val);
 
 static inline size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
 static inline unsigned kpm_stream_grid(int64_t items) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>((items + 255) / 256, 2048)); }

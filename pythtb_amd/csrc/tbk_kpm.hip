@@ -357,6 +357,15 @@ __global__ __launch_bounds__(256) void k_kpm_finish(const int nv, const int nmom
 }
 
 // ------------------------------------------------------------------ host entry points
+int kpm_values_at(const tbk_sparse* sp, const double* k_dev, cd* val) {
+    tbk_ctx* ctx = sp->ctx;
+    ProfScope ps(ctx, "kpm_values");
+    hipLaunchKernelGGL(k_kpm_values, dim3(kpm_stream_grid(sp->nnz)), dim3(256), 0, ctx->stream, sp->nnz, sp->dim_k, k_dev, sp->col,
+                       sp->row_of, sp->amp, sp->R, sp->orb, val);
+    TBK_HIP(hipGetLastError());
+    return TBK_OK;
+}
+
 extern "C" int tbk_kpm_vectors(tbk_sparse* sp, uint64_t seed, int64_t first, int64_t count, double* out) {
     TBK_REQUIRE(sp && (out || count == 0), TBK_EINVAL, "tbk_kpm_vectors: null argument");
     TBK_REQUIRE(first >= 0 && count >= 0, TBK_EINVAL, "tbk_kpm_vectors: first=%lld count=%lld", (long long)first, (long long)count);
@@ -432,10 +441,8 @@ extern "C" int tbk_kpm_moments(tbk_sparse* sp, const double* k, int64_t nk, int 
     for (int64_t q = 0; q < nk; ++q) {
         const cd* val = sp->amp;
         if (dim_k > 0) {
-            ProfScope ps(ctx, "kpm_values");
-            hipLaunchKernelGGL(k_kpm_values, dim3(kpm_stream_grid(sp->nnz)), dim3(256), 0, ctx->stream, sp->nnz, dim_k,
-                               k_dev + q * dim_k, sp->col, sp->row_of, sp->amp, sp->R, sp->orb, val_dev);
-            TBK_HIP(hipGetLastError());
+            rc = kpm_values_at(sp, k_dev + q * dim_k, val_dev);
+            if (rc) return rc;
             val = val_dev;
         }
         for (int v0 = 0; v0 < nvec; v0 += NV) {

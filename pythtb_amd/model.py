@@ -12,7 +12,7 @@ import numpy as np
 
 from . import _lib
 
-__all__ = ["tb_model", "kpm_reconstruct", "kpm_conductivity_reconstruct"]
+__all__ = ["tb_model", "kpm_reconstruct", "kpm_conductivity_reconstruct", "kpm_coefficients", "kpm_fermi_coefficients"]
 
 
 def _is_int(a):
@@ -132,6 +132,77 @@ def kpm_conductivity_reconstruct(mu, energies, bounds, kernel="jackson", lam=4.0
     else:
         f = (x[:, None] <= ((e - b) / a)[None, :]).astype(float)
     return (2.0 / (np.pi * a) ** 2) * (S @ f)
+
+
+def kpm_coefficients(f, n_terms, bounds, kernel=None, lam=4.0, n_quad=None):
+    """Extension: the Chebyshev coefficients c_m, m < n_terms, of a function f of the energy on `bounds` = (emin, emax), for
+    `tb_model.kpm_apply`:
+
+        f(H) ~ sum_m c_m T_m(H~),   c_m = (2 - delta_m0) / K sum_j f(a x_j + b) cos(m theta_j),   x_j = cos theta_j,
+
+    H~ = (H - b) / a, a = (emax - emin) / 2, b = (emax + emin) / 2, by the Chebyshev-Gauss quadrature on the `n_quad` (default
+    4 n_terms) nodes theta_j = pi (j + 1/2) / K.  f is called once with the array of node energies; a complex f gives complex
+    coefficients.  kernel: None (the truncated series), "jackson" or "lorentz" -- the damping factors g_m of `kpm_reconstruct`
+    multiply c_m.  Host NumPy, O(n_terms n_quad) work."""
+    if not _is_int(n_terms) or n_terms < 1:
+        raise Exception("\n\nkpm_coefficients: n_terms must be a positive integer")
+    K = 4 * int(n_terms) if n_quad is None else n_quad
+    if not _is_int(K) or K < 1:
+        raise Exception("\n\nkpm_coefficients: n_quad must be a positive integer")
+    emin, emax = float(bounds[0]), float(bounds[1])
+    if not emax > emin:
+        raise Exception("\n\nkpm_coefficients: bounds must be (emin, emax) with emin < emax")
+    g = _kpm_kernel(int(n_terms), kernel, lam, "kpm_coefficients")
+    a, b = 0.5 * (emax - emin), 0.5 * (emax + emin)
+    th = np.pi * (np.arange(K) + 0.5) / K
+    fx = np.asarray(f(a * np.cos(th) + b))
+    if fx.shape != th.shape:
+        raise Exception("\n\nkpm_coefficients: f must map an array of energies to an array of the same shape")
+    m = np.arange(int(n_terms), dtype=float)
+    c = np.cos(m[:, None] * th[None, :]) @ fx * (np.where(m == 0, 1.0, 2.0) / K)
+    return c * g
+
+
+def kpm_fermi_coefficients(fermi_level, n_moments, bounds, kernel="jackson", lam=4.0, kT=0.0):
+    """Extension: the Chebyshev coefficients of the occupation, float `(n_moments,)`: with them `tb_model.kpm_apply` applies the
+    Fermi projector P = theta(E_F - H) (kT = 0) or the Fermi function of H.  At kT = 0 analytic,
+
+        c_0 = 1 - theta_F / pi,   c_m = -2 sin(m theta_F) / (m pi),   theta_F = arccos((E_F - b) / a),
+
+    at kT > 0 `kpm_coefficients` of the Fermi function; both times the kernel factors g_m ("jackson" by default: the step is
+    smoothed over ~ pi a / n_moments and has no Gibbs oscillations).  `fermi_level` must lie inside the open interval of
+    `bounds` = (emin, emax); a, b as in `kpm_coefficients`."""
+    if not _is_int(n_moments) or n_moments < 1:
+        raise Exception("\n\nkpm_fermi_coefficients: n_moments must be a positive integer")
+    emin, emax = float(bounds[0]), float(bounds[1])
+    if not emax > emin:
+        raise Exception("\n\nkpm_fermi_coefficients: bounds must be (emin, emax) with emin < emax")
+    if not np.isfinite(fermi_level) or not emin < fermi_level < emax:
+        raise Exception("\n\nkpm_fermi_coefficients: fermi_level must lie inside the open interval (%.12g, %.12g)" % (emin, emax))
+    if not np.isfinite(kT) or kT < 0.0:
+        raise Exception("\n\nkpm_fermi_coefficients: kT must be finite and >= 0")
+    if kT > 0.0:
+        return kpm_coefficients(lambda e: 0.5 * (1.0 - np.tanh(0.5 * (e - fermi_level) / kT)), n_moments, bounds, kernel, lam)
+    g = _kpm_kernel(int(n_moments), kernel, lam, "kpm_fermi_coefficients")
+    a, b = 0.5 * (emax - emin), 0.5 * (emax + emin)
+    thf = np.arccos((fermi_level - b) / a)
+    m = np.arange(1, int(n_moments), dtype=float)
+    c = np.empty(int(n_moments))
+    c[0] = 1.0 - thf / np.pi
+    c[1:] = -2.0 * np.sin(m * thf) / (m * np.pi)
+    return c * g
+
+
+def _kpm_evolution_coefficients(z):
+    """(2 - delta_m0) (-i)^m J_m(z), cut after the last modulus above 1e-17: e^{-i z cos(theta)} = sum_m of these times cos(m theta),
+    so its discrete Fourier transform over theta_j = 2 pi j / N gives (-i)^m J_m(z) up to the aliases J_{N -+ m}(z); N is a power of
+    two of at least 2 |z| + 128, and large enough that the aliases of the kept terms lie where J has decayed below the cut."""
+    z = float(z)
+    N = 1 << int(np.ceil(np.log2(2.0 * abs(z) + 40.0 * abs(z) ** (1.0 / 3.0) + 128.0)))
+    c = np.fft.fft(np.exp(-1j * z * np.cos(2.0 * np.pi * np.arange(N) / N)))[:N // 2] / N
+    c[1:] *= 2.0
+    keep = np.nonzero(np.abs(c) > 1e-17)[0]
+    return c[:keep[-1] + 1]
 
 
 class tb_model(object):
@@ -1722,6 +1793,99 @@ class tb_model(object):
         ns = each.shape[0]
         err = each.std(axis=0, ddof=1) / np.sqrt(ns) if ns > 1 else np.full(sigma.shape, np.nan)
         return sigma, err
+
+    def kpm_apply(self, coeffs, k_list=None, vectors=None, n_vectors=8, seed=0, states=None, bounds=None):
+        """Extension: a function of the sparse Hamiltonian applied to vectors by its Chebyshev series,
+
+            out_s = sum_m coeffs[s][m] T_m(H~(k)) v,   H~ = (H - b) / a,   a = (emax - emin) / 2,   b = (emax + emin) / 2,
+
+        for models of any size: nothing is diagonalised.  `coeffs` `(nset, ncoef)`, real or complex, holds one coefficient set
+        per row -- `kpm_fermi_coefficients` (the Fermi projector), `kpm_coefficients` (any function of the energy); all sets
+        share the ncoef - 1 sparse products per block of 8 vectors.  Returns `(out, (emin, emax))`, out complex
+        `(nk, nset, nvec, nsta)`, without the k axis when k_list is None (dim_k = 0 only) and without the set axis for 1-D
+        `coeffs`; not divided by <v|v>.  Start vectors, bounds and the random-vector numbering (q * nvec + v at the k-point with
+        index q) as in `kpm_moments`; the coefficients must belong to the same bounds.  Bounds that do not contain the spectrum
+        raise, naming the Gershgorin interval.  Fixed-order sums on the device: two calls give the same bits."""
+        c = np.asarray(coeffs)
+        if c.ndim not in (1, 2) or c.size < 1 or not (np.issubdtype(c.dtype, np.number) and c.dtype != bool):
+            raise Exception("\n\nkpm_apply: coeffs must be a non-empty numeric array of shape (ncoef,) or (nset, ncoef)")
+        c2 = np.ascontiguousarray(np.atleast_2d(c), dtype=complex)
+        if not np.all(np.isfinite(c2)):
+            raise Exception("\n\nkpm_apply: coeffs must be finite")
+        vec, st, nvec = self._kpm_start("kpm_apply", vectors, n_vectors, seed, states)
+        bounds = self._kpm_bounds_arg(bounds)
+        k, nk = self._kpm_k(k_list)
+        sp = self._sparse_model()
+        emin, emax = self._kpm_bounds(bounds, sp)
+        nset, ncoef = c2.shape
+        out = np.empty((nk, nset, nvec, self._nsta), dtype=complex)
+        _lib.check(_lib.lib.tbk_kpm_apply_series(sp, _lib.dptr(k), nk, ncoef, nset, _lib.dptr(c2.view(float)), emin, emax, nvec,
+                                                 None if vec is None else _lib.dptr(vec.view(float)), _lib.iptr(st), int(seed),
+                                                 _lib.dptr(out.view(float))))
+        if c.ndim == 1:
+            out = out[:, 0]
+        return (out[0] if k_list is None else out), (emin, emax)
+
+    def kpm_evolve(self, times, k_list=None, vectors=None, states=None, bounds=None):
+        """Extension: the time evolution e^{-i H(k) t} |v> of the supplied `vectors` (complex128 `(nvec, nsta)`) or of the unit
+        vectors at `states`, for every t of `times` (hbar = 1), by the Chebyshev series with the coefficients
+        c_m(t) = (2 - delta_m0) (-i)^m J_m(a t) e^{-i b t} (Tal-Ezer, Kosloff, J. Chem. Phys. 81, 3967): one coefficient set per
+        time through `kpm_apply`, so all times share one run of ~ a max|t| + 10 (a max|t|)^(1/3) sparse products.  The series is
+        cut where |c_m| falls below 1e-17: the result is e^{-iHt} v to rounding, and the norm is kept.  Returns
+        `(psi, (emin, emax))`, psi complex `(nk, nt, nvec, nsta)`, without the k axis when k_list is None (dim_k = 0 only) and
+        without the time axis for a scalar `times`."""
+        t = np.asarray(times, dtype=float)
+        if t.ndim not in (0, 1) or t.size < 1 or not np.all(np.isfinite(t)):
+            raise Exception("\n\nkpm_evolve: times must be a finite number or a non-empty one-dimensional list of them")
+        if vectors is None and states is None:
+            raise Exception("\n\nkpm_evolve: give the vectors or the states to evolve")
+        bounds = self._kpm_bounds(self._kpm_bounds_arg(bounds), self._sparse_model())
+        a, b = 0.5 * (bounds[1] - bounds[0]), 0.5 * (bounds[1] + bounds[0])
+        sets = [_kpm_evolution_coefficients(a * ti) * np.exp(-1j * b * ti) for ti in t.reshape(-1)]
+        c = np.zeros((len(sets), max(len(s) for s in sets)), dtype=complex)
+        for row, s in zip(c, sets):
+            row[:len(s)] = s
+        return self.kpm_apply(c if t.ndim else c[0], k_list, vectors=vectors, states=states, bounds=bounds)
+
+    def local_chern_marker(self, fermi_level, n_moments, states=None, dirs=(0, 1), kernel="jackson", bounds=None):
+        """Extension: the local Chern marker of Bianco and Resta (Phys. Rev. B 84, 241106) of an open sample (dim_k = 0),
+
+            c(s) = 4 pi Im <s| P r_a P r_b P |s>,   (a, b) = dirs,
+
+        at the states `states` (default: all), float `(nstates,)`: a Chern number resolved in real space, for flakes, domain
+        walls and disorder.  P is the Fermi projector as the Chebyshev series of `kpm_fermi_coefficients(fermi_level,
+        n_moments, bounds, kernel)` on the sparse operator; r_a, r_b are the reduced coordinates of the orbitals along the
+        axes a, b in [0, dim_r) (`cut_piece` keeps them unwrapped; in reduced coordinates the cell has area 1).
+        2 (n_moments - 1) sparse products per block of 8 states, everything on the device; two calls give the same bits.
+
+        - The sum of c(s) over the states of one cell deep in the bulk is the Chern number of the occupied bands as
+          `berry_curvature_mesh(mesh, occ, dirs) / (2 pi)` of the periodic model gives it; dirs=(b, a) gives the negative.
+        - The sum over a whole open sample is NOT a Chern number: with the exact projector it vanishes (the edge
+          compensates the bulk), and with the series it is dominated by the edge states inside the gap, which no finite
+          n_moments resolves.  Use bulk cells.
+        - The resolution in energy is ~ pi a / n_moments (Jackson kernel), as in `kpm_conductivity`: the gap has to be
+          several times that."""
+        if self._dim_k != 0:
+            raise Exception("\n\nlocal_chern_marker needs an open sample: cut_piece every periodic direction (dim_k = 0).")
+        dirs = list(dirs)
+        if len(dirs) != 2 or not all(_is_int(d) for d in dirs):
+            raise Exception("\n\nlocal_chern_marker: dirs must be two integer axes.")
+        if min(dirs) < 0 or max(dirs) >= self._dim_r or dirs[0] == dirs[1]:
+            raise Exception("\n\nlocal_chern_marker: dirs must be two different axes in [0, dim_r)")
+        if not _is_int(n_moments) or n_moments < 1:
+            raise Exception("\n\nlocal_chern_marker: n_moments must be a positive integer")
+        n = self._nsta
+        _, st, nvec = self._kpm_start("local_chern_marker", None, 1, 0, range(n) if states is None else states)
+        bounds = self._kpm_bounds_arg(bounds)
+        sp = self._sparse_model()
+        emin, emax = self._kpm_bounds(bounds, sp)
+        c = np.ascontiguousarray(kpm_fermi_coefficients(fermi_level, n_moments, (emin, emax), kernel), dtype=float)
+        da = np.ascontiguousarray(np.repeat(self._orb[:, dirs[0]], self._nspin), dtype=float)
+        db = np.ascontiguousarray(np.repeat(self._orb[:, dirs[1]], self._nspin), dtype=float)
+        out = np.empty(nvec, dtype=complex)
+        _lib.check(_lib.lib.tbk_kpm_marker(sp, len(c), _lib.dptr(c), emin, emax, _lib.dptr(da), _lib.dptr(db), nvec, _lib.iptr(st),
+                                           _lib.dptr(out.view(float))))
+        return 4.0 * np.pi * out.imag
 
     # ------------------------------------------------------------------ k generators (host)
     def k_uniform_mesh(self, mesh_size):
