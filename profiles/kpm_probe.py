@@ -8,7 +8,10 @@ Two figures per size: the kernel time of k_kpm_step from the library's per-launc
 wall time per step of an unbracketed call, which includes the launch gaps.  Past the 256 MiB cache the rate is also given as a
 fraction of the measured plain-copy rate of the device, 6.29 TB/s (float4 copy).
 
-    python profiles/kpm_probe.py [--sizes 32,224,1000] [--moments 512] [--out FILE]"""
+At L = --double-size (224) one more figure: the wall time of a whole tbk_kpm_double_moments call with
+--double-moments (64) moments, 8 vectors, one k, directions (0, 1).
+
+    python profiles/kpm_probe.py [--sizes 32,224,1000] [--moments 512] [--double-size 224] [--double-moments 64] [--out FILE]"""
 import argparse
 import ctypes as C
 import json
@@ -64,10 +67,19 @@ def moments(sp, k, M, bounds, nvec=NV, seed=1):
     return mu
 
 
+def double_moments(sp, k, M, bounds, nvec=NV, seed=1):
+    mu = np.empty((len(k), nvec, M, M), dtype=complex)
+    _lib.check(_lib.lib.tbk_kpm_double_moments(sp, _lib.dptr(k), len(k), M, bounds[0], bounds[1], 0, 1, nvec, None, None, seed,
+                                               _lib.dptr(mu.view(float))))
+    return mu
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", default="32,224,1000")
     ap.add_argument("--moments", type=int, default=512)
+    ap.add_argument("--double-size", type=int, default=224)
+    ap.add_argument("--double-moments", type=int, default=64)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     ctx = _lib.default_context()
@@ -112,6 +124,14 @@ def main():
                    fraction_of_copy_kernel=model_bytes / t_kernel / COPY_RATE, past_cache=footprint > (256 << 20),
                    values_us=rep["kpm_values"]["total_ms"] * 1e3, max_abs_mu=float(np.abs(mu).max()),
                    kernels={kk: vv for kk, vv in rep.items()})
+        if L == a.double_size:
+            double_moments(sp, k, a.double_moments, bnd)         # warm-up: workspace
+            runs = []
+            for _ in range(3):
+                w0 = time.perf_counter()
+                double_moments(sp, k, a.double_moments, bnd)
+                runs.append((time.perf_counter() - w0) * 1e3)
+            row.update(double_moments=a.double_moments, double_ms=float(np.median(runs)), double_ms_runs=runs)
         rows.append(row)
         print(json.dumps(row), flush=True)
         _lib.check(_lib.lib.tbk_sparse_free(sp))

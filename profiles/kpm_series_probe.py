@@ -1,5 +1,6 @@
-"""Time per Chebyshev step of tbk_kpm_apply_series (k_kpm_series_step, nset coefficient sets) against the bare step of
-tbk_kpm_moments (k_kpm_step) on the same periodic Haldane supercell of about 10^6 states (nvec = 8, 256 sparse products each),
+"""Time per Chebyshev step of tbk_kpm_apply_series (k_kpm_step with the series epilogue, nset coefficient sets) against the bare
+step of tbk_kpm_moments (the same kernel with the dot-product epilogue) on the same periodic Haldane supercell of about 10^6
+states (nvec = 8, 256 sparse products each),
 and the traffic model of DESIGN.md section 23:
 
     bytes per step = nnz * 20 (value + column) + nsta * NV * 16 * (3 + 2 nset)

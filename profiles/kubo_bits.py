@@ -32,93 +32,97 @@ def compare(fa, fb):
     return 1 if bad else 0
 
 
-if len(sys.argv) == 4 and sys.argv[1] == "--compare":
-    sys.exit(compare(sys.argv[2], sys.argv[3]))
-
-import pythtb_amd as tb  # noqa: E402
-import helpers as hp  # noqa: E402
-from pythtb_amd import w90  # noqa: E402
+def main():
+    import pythtb_amd as tb  # noqa: E402
+    import helpers as hp  # noqa: E402
+    from pythtb_amd import w90  # noqa: E402
 
 
-def quiet(fn, *a, **k):
-    with contextlib.redirect_stdout(io.StringIO()):
-        return fn(*a, **k)
+    def quiet(fn, *a, **k):
+        with contextlib.redirect_stdout(io.StringIO()):
+            return fn(*a, **k)
 
 
-def supercell(s):
-    return quiet(hp.haldane(tb.tb_model, 0.2).make_supercell, [[s, 0], [0, s]])
+    def supercell(s):
+        return quiet(hp.haldane(tb.tb_model, 0.2).make_supercell, [[s, 0], [0, s]])
 
 
-# name -> (model, occupied bands, 2-D or 3-D mesh); the number of states routes the form
-MODELS = {
-    "haldane_n2": (lambda: hp.haldane(tb.tb_model, 0.2), [0], [96, 80]),
-    "random_n3": (lambda: hp.random_model(tb.tb_model, 3, 2, 1, 11), [0], [40, 36]),
-    "kane_mele_n4": (lambda: hp.kane_mele(tb.tb_model), [0, 1], [48, 40]),
-    "silicon_n8": (lambda: quiet(w90(os.path.join(_ROOT, "tests", "golden", "w90_silicon"), "silicon").model), [0, 1, 2, 3], [12, 10, 8]),
-    "cubic16_n16": (lambda: hp.cubic16(tb.tb_model), list(range(8)), [24, 24, 16]),   # two chunks
-    "haldane_4x4_n32": (lambda: supercell(4), list(range(16)), [24, 20]),
-    "random_n36": (lambda: hp.random_model(tb.tb_model, 36, 2, 1, 12), list(range(18)), [12, 10]),
-    "random_n80": (lambda: hp.random_model(tb.tb_model, 40, 2, 2, 13), list(range(40)), [8, 6]),
-    # three directions at the last size of the LDS forms (80 KiB in k_opt_pairs and k_qgt_lds<3>) and at the first wide size
-    "random3d_n32": (lambda: hp.random_model(tb.tb_model, 16, 3, 2, 14), list(range(16)), [6, 5, 4]),
-    "random3d_n33": (lambda: hp.random_model(tb.tb_model, 33, 3, 1, 15), list(range(16)), [4, 3, 2]),
-}
+    # name -> (model, occupied bands, 2-D or 3-D mesh); the number of states routes the form
+    MODELS = {
+        "haldane_n2": (lambda: hp.haldane(tb.tb_model, 0.2), [0], [96, 80]),
+        "random_n3": (lambda: hp.random_model(tb.tb_model, 3, 2, 1, 11), [0], [40, 36]),
+        "kane_mele_n4": (lambda: hp.kane_mele(tb.tb_model), [0, 1], [48, 40]),
+        "silicon_n8": (lambda: quiet(w90(os.path.join(_ROOT, "tests", "golden", "w90_silicon"), "silicon").model), [0, 1, 2, 3], [12, 10, 8]),
+        "cubic16_n16": (lambda: hp.cubic16(tb.tb_model), list(range(8)), [24, 24, 16]),   # two chunks
+        "haldane_4x4_n32": (lambda: supercell(4), list(range(16)), [24, 20]),
+        "random_n36": (lambda: hp.random_model(tb.tb_model, 36, 2, 1, 12), list(range(18)), [12, 10]),
+        "random_n80": (lambda: hp.random_model(tb.tb_model, 40, 2, 2, 13), list(range(40)), [8, 6]),
+        # three directions at the last size of the LDS forms (80 KiB in k_opt_pairs and k_qgt_lds<3>) and at the first wide size
+        "random3d_n32": (lambda: hp.random_model(tb.tb_model, 16, 3, 2, 14), list(range(16)), [6, 5, 4]),
+        "random3d_n33": (lambda: hp.random_model(tb.tb_model, 33, 3, 1, 15), list(range(16)), [4, 3, 2]),
+    }
 
-out = {}
-
-
-def keep(name, a):
-    assert name not in out
-    out[name] = np.ascontiguousarray(np.asarray(a)).view(float)
+    out = {}
 
 
-rng = np.random.default_rng(2024)
-for name, (make, occ, mesh) in MODELS.items():
-    m = make()
-    dk = m._dim_k
-    e = m.solve_all_mesh([6] * dk)
-    lo, hi = float(e.min()), float(e.max())
-    few = np.linspace(lo - 0.1, hi + 0.1, 37)
-    # more levels than one window of either Fermi kernel, unsorted, with ties
-    many = rng.permutation(np.concatenate([np.linspace(lo, hi, 4000), np.linspace(lo, hi, 500), np.full(500, 0.5 * (lo + hi))]))
-    k = rng.random((70, dk))
-    for dirs in ([(0, 1), (1, 2), (2, 0)] if dk == 3 else [(0, 1), (1, 0)]):
-        tag = "%s d%d%d " % ((name,) + dirs)
-        keep(tag + "curv list", m.berry_curvature(k, dirs=dirs))
-        keep(tag + "curv list occ", m.berry_curvature(k, occ=occ, dirs=dirs))
-        keep(tag + "orb list", m.orbital_moment(k, dirs=dirs))
-        keep(tag + "orb list occ", m.orbital_moment(k, occ=occ, dirs=dirs))
-        keep(tag + "curv mesh", m.berry_curvature_mesh(mesh, dirs=dirs))
-        keep(tag + "curv mesh occ", m.berry_curvature_mesh(mesh, occ=occ, dirs=dirs))
-        keep(tag + "curv mesh fermi", m.berry_curvature_mesh(mesh, dirs=dirs, fermi_levels=few))
-        keep(tag + "orb mesh occ", m.orbital_magnetization_mesh(mesh, occ=occ, dirs=dirs))
-        keep(tag + "orb mesh fermi", m.orbital_magnetization_mesh(mesh, fermi_levels=few, dirs=dirs))
-        keep(tag + "orb mesh kT", m.orbital_magnetization_mesh(mesh, fermi_levels=few, kT=0.05, dirs=dirs))
-        if m._nspin == 2:
-            keep(tag + "spin curv list", m.spin_berry_curvature(k, dirs=dirs))
-            keep(tag + "spin curv list occ", m.spin_berry_curvature(k, spin=0, occ=occ, dirs=dirs))
-    if name in ("haldane_n2", "kane_mele_n4", "silicon_n8"):
-        keep(name + " curv mesh fermi5000", m.berry_curvature_mesh(mesh, fermi_levels=many))
-        keep(name + " orb mesh fermi5000", m.orbital_magnetization_mesh(mesh, fermi_levels=many))
-    omega = np.linspace(-1.0, 0.5 * (hi - lo), 23)
-    mu = 0.5 * (lo + hi) + 0.013
-    for kT in (0.0, 0.05):
-        for dirs in ((0, 0), (0, 1), None):
-            keep("%s optics %s kT%g" % (name, dirs, kT),
-                 m.optical_conductivity_mesh(mesh, omega, 0.03, fermi_level=mu, kT=kT, dirs=dirs))
-    one = (dk - 1, 0, dk - 1)
-    keep(name + " shift list", m.shift_current(k, occ, one))
-    keep(name + " shift list aaa", m.shift_current(k, occ, (0, 0, 0)))
-    for kT in (0.0, 0.05):
-        for dirs in (None, one):
-            keep("%s shift %s kT%g" % (name, dirs, kT), m.shift_current_mesh(mesh, omega, 0.03, fermi_level=mu, kT=kT, dirs=dirs))
-            keep("%s injection %s kT%g" % (name, dirs, kT),
-                 m.injection_current_mesh(mesh, omega, 0.03, fermi_level=mu, kT=kT, dirs=dirs))
-    keep(name + " qgt list", m.quantum_geometric_tensor(k))
-    keep(name + " qgt list occ", m.quantum_geometric_tensor(k, occ=occ))
-    keep(name + " qgt mesh", m.quantum_geometric_tensor_mesh(mesh))
-    keep(name + " qgt mesh occ", m.quantum_geometric_tensor_mesh(mesh, occ=occ))
-    print(name, len(out), flush=True)
+    def keep(name, a):
+        assert name not in out
+        out[name] = np.ascontiguousarray(np.asarray(a)).view(float)
 
-np.savez(sys.argv[1], **out)
-print("saved %d arrays to %s (library %s)" % (len(out), sys.argv[1], os.environ.get("TBK_LIBRARY", "default")))
+
+    rng = np.random.default_rng(2024)
+    for name, (make, occ, mesh) in MODELS.items():
+        m = make()
+        dk = m._dim_k
+        e = m.solve_all_mesh([6] * dk)
+        lo, hi = float(e.min()), float(e.max())
+        few = np.linspace(lo - 0.1, hi + 0.1, 37)
+        # more levels than one window of either Fermi kernel, unsorted, with ties
+        many = rng.permutation(np.concatenate([np.linspace(lo, hi, 4000), np.linspace(lo, hi, 500), np.full(500, 0.5 * (lo + hi))]))
+        k = rng.random((70, dk))
+        for dirs in ([(0, 1), (1, 2), (2, 0)] if dk == 3 else [(0, 1), (1, 0)]):
+            tag = "%s d%d%d " % ((name,) + dirs)
+            keep(tag + "curv list", m.berry_curvature(k, dirs=dirs))
+            keep(tag + "curv list occ", m.berry_curvature(k, occ=occ, dirs=dirs))
+            keep(tag + "orb list", m.orbital_moment(k, dirs=dirs))
+            keep(tag + "orb list occ", m.orbital_moment(k, occ=occ, dirs=dirs))
+            keep(tag + "curv mesh", m.berry_curvature_mesh(mesh, dirs=dirs))
+            keep(tag + "curv mesh occ", m.berry_curvature_mesh(mesh, occ=occ, dirs=dirs))
+            keep(tag + "curv mesh fermi", m.berry_curvature_mesh(mesh, dirs=dirs, fermi_levels=few))
+            keep(tag + "orb mesh occ", m.orbital_magnetization_mesh(mesh, occ=occ, dirs=dirs))
+            keep(tag + "orb mesh fermi", m.orbital_magnetization_mesh(mesh, fermi_levels=few, dirs=dirs))
+            keep(tag + "orb mesh kT", m.orbital_magnetization_mesh(mesh, fermi_levels=few, kT=0.05, dirs=dirs))
+            if m._nspin == 2:
+                keep(tag + "spin curv list", m.spin_berry_curvature(k, dirs=dirs))
+                keep(tag + "spin curv list occ", m.spin_berry_curvature(k, spin=0, occ=occ, dirs=dirs))
+        if name in ("haldane_n2", "kane_mele_n4", "silicon_n8"):
+            keep(name + " curv mesh fermi5000", m.berry_curvature_mesh(mesh, fermi_levels=many))
+            keep(name + " orb mesh fermi5000", m.orbital_magnetization_mesh(mesh, fermi_levels=many))
+        omega = np.linspace(-1.0, 0.5 * (hi - lo), 23)
+        mu = 0.5 * (lo + hi) + 0.013
+        for kT in (0.0, 0.05):
+            for dirs in ((0, 0), (0, 1), None):
+                keep("%s optics %s kT%g" % (name, dirs, kT),
+                     m.optical_conductivity_mesh(mesh, omega, 0.03, fermi_level=mu, kT=kT, dirs=dirs))
+        one = (dk - 1, 0, dk - 1)
+        keep(name + " shift list", m.shift_current(k, occ, one))
+        keep(name + " shift list aaa", m.shift_current(k, occ, (0, 0, 0)))
+        for kT in (0.0, 0.05):
+            for dirs in (None, one):
+                keep("%s shift %s kT%g" % (name, dirs, kT), m.shift_current_mesh(mesh, omega, 0.03, fermi_level=mu, kT=kT, dirs=dirs))
+                keep("%s injection %s kT%g" % (name, dirs, kT),
+                     m.injection_current_mesh(mesh, omega, 0.03, fermi_level=mu, kT=kT, dirs=dirs))
+        keep(name + " qgt list", m.quantum_geometric_tensor(k))
+        keep(name + " qgt list occ", m.quantum_geometric_tensor(k, occ=occ))
+        keep(name + " qgt mesh", m.quantum_geometric_tensor_mesh(mesh))
+        keep(name + " qgt mesh occ", m.quantum_geometric_tensor_mesh(mesh, occ=occ))
+        print(name, len(out), flush=True)
+
+    np.savez(sys.argv[1], **out)
+    print("saved %d arrays to %s (library %s)" % (len(out), sys.argv[1], os.environ.get("TBK_LIBRARY", "default")))
+
+
+if __name__ == "__main__":
+    if len(sys.argv) == 4 and sys.argv[1] == "--compare":
+        sys.exit(compare(sys.argv[2], sys.argv[3]))
+    main()

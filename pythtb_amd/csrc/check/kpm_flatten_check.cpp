@@ -5,12 +5,15 @@
 // (ham[i,s,j,t] += amp e^{2 pi i k.(R + tau_j - tau_i)}, plus the Hermitian conjugate), and checks the structure.  The velocity
 // bounds of tbk_sparse_velocity_bounds_host (the guard of tbk_kpm_double_moments) are compared with the row sums of the table's
 // entries and, as upper bounds, with the row sums of dH/dk_d built from the definition at that k.
+// A second part drives kpm_slot_schedule (tbk_kpm.h), the order of steps and reductions every KPM call follows, with callables that
+// only record: every step 0 .. nsteps is reduced exactly once, into dots[step] and from the slot it was written to, and no slot is
+// written again before its reduction.
 #include <complex>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
-#include "../tbk_internal.h"
+#include "../tbk_kpm.h"
 
 // what tbk_kpm.hip takes from tbk_core.hip (this program links the one translation unit alone)
 static char g_err[512];
@@ -120,8 +123,39 @@ static int check(const Table& t, const double* k, const char* name) {
     return (bad || !(err <= 1e-14 * big) || !(gersh[0] < gersh[1])) ? 1 : 0;
 }
 
+// slot_of[s] = the step slot s holds and has not given up yet (-1: free); reduced[j] = how often step j reached dots[j]
+static int check_schedule(int nsteps, int nslots) {
+    std::vector<int> slot_of((size_t)nslots, -1), reduced((size_t)nsteps + 1, 0);
+    int bad = 0;
+    slot_of[0] = 0;      // the start vectors
+    int rc = kpm_slot_schedule(
+        nsteps, nslots,
+        [&](int j, int slot) {
+            if (slot < 0 || slot >= nslots || slot_of[(size_t)slot] != -1) return ++bad;     // outside part, or over an unreduced step
+            slot_of[(size_t)slot] = j;
+            return 0;
+        },
+        [&](int first, int count) {
+            if (count < 1 || count > nslots || first < 0 || first + count > nsteps + 1) return ++bad;
+            for (int i = 0; i < count; ++i) {          // k_kpm_reduce: dots[first + i] = the sums of slot i
+                if (slot_of[(size_t)i] != first + i) bad++;
+                else reduced[(size_t)(first + i)]++;
+                slot_of[(size_t)i] = -1;
+            }
+            return 0;
+        });
+    for (int j = 0; j <= nsteps; ++j)
+        if (reduced[(size_t)j] != 1) bad++;
+    if (rc || bad) printf("slot schedule nsteps = %d, nslots = %d: rc %d, %d faults\n", nsteps, nslots, rc, bad);
+    return (rc || bad) ? 1 : 0;
+}
+
 int main() {
     int fail = 0;
+    for (int nsteps : {0, 1, 2, 127, 128, 129, 300})
+        for (int nslots : {1, 2, 128}) fail += check_schedule(nsteps, nslots);
+    if (kpm_plan(65569, 300).nwg != 2048 || kpm_plan(65569, 300).nslots != 128 || kpm_plan(33, 0).nwg != 2 || kpm_plan(33, 0).nslots != 1)
+        fail += printf("kpm_plan: unexpected launch plan\n");
     {
         Table t{2, 2, 1, {1.0 / 3, 1.0 / 3, 2.0 / 3, 2.0 / 3}, {-0.2, 0.0, 0.2, 0.0}, {}, {}, {}, {}};
         const double t2[2] = {0.0, 0.15};

@@ -1,12 +1,18 @@
 // tbk_kpm.h -- what the translation units of the kernel polynomial method share (tbk_kpm.hip: the operator and the single moments;
 // tbk_kpm_cond.hip: the double moments of the Kubo-Bastin conductivity; tbk_kpm_series.hip: operator functions and the local Chern
-// marker): the operator's handle, the random-phase generator, the start vectors and the fixed-order sums.  DESIGN.md sections 21 to 23.
+// marker): the operator's handle, the random-phase generator, the fixed-order sums, the values of the operator at a k-point, the
+// row mapping, the sparse row product and the one Chebyshev step kernel; on the host the argument checks, the launch plan, the
+// workspace carving, the start vectors and the driver of the steps.  Templates and static functions: the library has no
+// relocatable device code.  DESIGN.md sections 21 to 24.
 #pragma once
 #include <algorithm>
+#include <cmath>
 #include "tbk_internal.h"
 
 #define KPM_NV 8            // vectors per block
 #define KPM_MAX_WG 2048     // workgroups of a step (grid-stride over the row tiles beyond that)
+#define KPM_MAX_SLOTS 128   // steps between two reductions of the partial sums
+#define KPM_PART_BYTES ((size_t)32 << 20)   // ... and the workspace they may take
 
 struct tbk_sparse {
     tbk_ctx* ctx = nullptr;
@@ -67,29 +73,47 @@ __device__ __forceinline__ void kpm_block_sums(double dA, double dB, double* __r
     }
 }
 
+// body(row, v) for every row of this workgroup's tiles: a wavefront covers 64 / NV rows x NV vectors (the vector index fastest, so
+// the NV lanes of a row read the same matrix entry and one contiguous 16 NV-byte segment of a vector block), a workgroup 4 x 64 / NV
+// rows, and the workgroups stride over the row tiles beyond KPM_MAX_WG of them.
+template <int NV, class Body>
+__device__ __forceinline__ void kpm_for_rows(const int nsta, Body body) {
+    constexpr int RPW = 64 / NV, RPB = 4 * RPW;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, v = lane % NV, rw = lane / NV;
+    const int64_t ntiles = ((int64_t)nsta + RPB - 1) / RPB;
+    for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        const int64_t row = tile * RPB + wave * RPW + rw;
+        if (row < nsta) body(row, v);
+    }
+}
+
+// sum over the entries e of the CSR row of val[e] in[col[e]][v]; each lane walks the entries of its row
+template <int NV>
+__device__ __forceinline__ cd kpm_row_product(const int64_t* __restrict__ row_ptr, const int32_t* __restrict__ col,
+                                              const cd* __restrict__ val, const cd* __restrict__ in, const int64_t row, const int v) {
+    const int64_t e0 = row_ptr[row], e1 = row_ptr[row + 1];
+    cd acc{0.0, 0.0};
+    for (int64_t e = e0; e < e1; ++e) cfma(acc, val[e], in[(int64_t)col[e] * NV + v]);
+    return acc;
+}
+
 // alpha_0 of one block of NV vectors, alpha[row][NV], and the partial sums of <alpha_0|alpha_0> (the slot of step 0).
 // mode 0: random phases, vector numbers g0 + v; 1: unit vectors at states[v]; 2: src[v][nsta].  Vectors v >= nv are zero.
 template <int NV>
 __global__ __launch_bounds__(256) void k_kpm_init(const int nsta, const int nv, const int mode, const uint64_t seed, const uint64_t g0,
                                                   const int32_t* __restrict__ states, const cd* __restrict__ src,
                                                   cd* __restrict__ cur, double* __restrict__ part) {
-    constexpr int RPW = 64 / NV, RPB = 4 * RPW;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, v = lane % NV, rw = lane / NV;
-    const int64_t ntiles = ((int64_t)nsta + RPB - 1) / RPB;
     double dA = 0.0;
-    for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        const int64_t row = tile * RPB + wave * RPW + rw;
-        if (row < nsta) {
-            cd x{0.0, 0.0};
-            if (v < nv) {
-                if (mode == 0) x = kpm_random_phase(seed, g0 + (uint64_t)v, (uint64_t)row);
-                else if (mode == 1) x = cd{states[v] == row ? 1.0 : 0.0, 0.0};
-                else x = src[(int64_t)v * nsta + row];
-            }
-            cur[row * NV + v] = x;
-            dA += cabs2(x);
+    kpm_for_rows<NV>(nsta, [&](const int64_t row, const int v) {
+        cd x{0.0, 0.0};
+        if (v < nv) {
+            if (mode == 0) x = kpm_random_phase(seed, g0 + (uint64_t)v, (uint64_t)row);
+            else if (mode == 1) x = cd{states[v] == row ? 1.0 : 0.0, 0.0};
+            else x = src[(int64_t)v * nsta + row];
         }
-    }
+        cur[row * NV + v] = x;
+        dA += cabs2(x);
+    });
     kpm_block_sums<NV>(dA, 0.0, part);
 }
 
@@ -111,4 +135,212 @@ __global__ __launch_bounds__(256) void k_kpm_reduce(const int nwg, const double*
         for (int i = 1; i < G; ++i) t += red[i][c];
         dots[(int64_t)blockIdx.x * NC + c] = t;
     }
+}
+
+// val[e] = amp[e] exp(2 pi i k.(R_e + orb_col - orb_row)) for one k; VEL: also the two velocity operators,
+// va[e] = 2 pi i (R_e + orb_col - orb_row)_da val[e] and vb the same along db.  A lane per entry.
+__device__ __forceinline__ double kpm_pick(const double4 a, const int d) { return d == 0 ? a.x : (d == 1 ? a.y : (d == 2 ? a.z : a.w)); }
+__device__ __forceinline__ int kpm_pick(const int4 a, const int d) { return d == 0 ? a.x : (d == 1 ? a.y : (d == 2 ? a.z : a.w)); }
+template <bool VEL>
+__global__ __launch_bounds__(256) void k_kpm_values(const int64_t nnz, const int dim_k, const int da, const int db,
+                                                    const double* __restrict__ k, const int32_t* __restrict__ col,
+                                                    const int32_t* __restrict__ row_of, const cd* __restrict__ amp,
+                                                    const int4* __restrict__ R, const double4* __restrict__ orb, cd* __restrict__ val,
+                                                    cd* __restrict__ va, cd* __restrict__ vb) {
+    double kk[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int d = 0; d < dim_k; ++d) kk[d] = k[d];
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < nnz; e += (int64_t)gridDim.x * 256) {
+        const int4 r = R[e];
+        const double4 oc = orb[col[e]], orw = orb[row_of[e]];
+        double x = kk[0] * ((double)r.x + oc.x - orw.x);
+        x = fma(kk[1], (double)r.y + oc.y - orw.y, x);
+        x = fma(kk[2], (double)r.z + oc.z - orw.z, x);
+        x = fma(kk[3], (double)r.w + oc.w - orw.w, x);
+        double s, c;
+        sincospi(2.0 * x, &s, &c);
+        const cd h = cmul(amp[e], cd{c, s});
+        if (VEL) {
+            const double ta = 2.0 * M_PI * ((double)kpm_pick(r, da) + kpm_pick(oc, da) - kpm_pick(orw, da));
+            const double tb = 2.0 * M_PI * ((double)kpm_pick(r, db) + kpm_pick(oc, db) - kpm_pick(orw, db));
+            va[e] = cd{-ta * h.y, ta * h.x};
+            vb[e] = cd{-tb * h.y, tb * h.x};
+        }
+        val[e] = h;
+    }
+}
+
+// What a step does with the new value nw of (row, v) besides storing it (x0 is cur's element): row<NV, FIRST>() may add to the
+// row-local sums (dA, dB), which go to `part` through kpm_block_sums where SUMS is set.  tbk_kpm_series.hip has a third policy.
+struct KpmDots {   // A = <nw|nw>, B = Re <nw|cur>
+    static constexpr bool SUMS = true;
+    double* part;
+    template <int NV, bool FIRST>
+    __device__ __forceinline__ void row(int, int64_t, int, const cd x0, const cd nw, double& dA, double& dB) const {
+        dA += cabs2(nw);
+        dB += nw.x * x0.x + nw.y * x0.y;
+    }
+};
+struct KpmNoSums {   // the vector alone: no sums, no LDS, no barrier
+    static constexpr bool SUMS = false;
+    template <int NV, bool FIRST>
+    __device__ __forceinline__ void row(int, int64_t, int, cd, cd, double&, double&) const {}
+};
+
+// One Chebyshev step for a block of NV vectors: out = nw = 2 H~ cur - prev (FIRST: nw = H~ cur, prev unused), H~ = (A - b) / a
+// with A the CSR operator of the values `val`, then the epilogue.  IN_PLACE: prev is out (the argument is not read): the element
+// of prev is read from out before nw goes there -- row i reads only its own element, so two buffers are enough for a recursion.
+// Said at compile time, not as "out may be prev", so that out can be __restrict__: without it every store to out stands between
+// the epilogue and what it reads (the coefficients of a series would come through vector instead of scalar loads).  out is never
+// cur.  An empty row gives nw = -(2 b / a) cur - prev.  With (b, inv_a) = (0, 1) and FIRST it is the plain product A cur (a
+// velocity operator).
+template <int NV, bool FIRST, class Epi, bool IN_PLACE = true>
+__global__ __launch_bounds__(256) void k_kpm_step(const int nsta, const int64_t* __restrict__ row_ptr, const int32_t* __restrict__ col,
+                                                  const cd* __restrict__ val, const cd* __restrict__ cur, const cd* prev,
+                                                  cd* __restrict__ out, const double b, const double inv_a, const Epi epi) {
+    const cd* pv = IN_PLACE ? out : prev;
+    double dA = 0.0, dB = 0.0;
+    kpm_for_rows<NV>(nsta, [&](const int64_t row, const int v) {
+        const cd acc = kpm_row_product<NV>(row_ptr, col, val, cur, row, v);
+        const cd x0 = cur[row * NV + v];
+        const cd h{(acc.x - b * x0.x) * inv_a, (acc.y - b * x0.y) * inv_a};
+        cd nw = h;
+        if (!FIRST) {
+            const cd p = pv[row * NV + v];
+            nw = cd{2.0 * h.x - p.x, 2.0 * h.y - p.y};
+        }
+        out[row * NV + v] = nw;
+        epi.template row<NV, FIRST>(nsta, row, v, x0, nw, dA, dB);
+    });
+    if constexpr (Epi::SUMS) kpm_block_sums<NV>(dA, dB, epi.part);
+}
+
+// ------------------------------------------------------------------ host
+// The arguments the entry points share; `who` is the entry point and `order_name` its name for the number of terms.  A model with
+// dim_k = 0 has one (empty) k-point.
+static int kpm_check_args(const char* who, const tbk_sparse* sp, const char* order_name, int order, int nvec, const double* vectors,
+                          const int32_t* states, double emin, double emax, const double* k, int64_t* nk) {
+    TBK_REQUIRE(order >= 1, TBK_EINVAL, "%s: %s=%d", who, order_name, order);
+    TBK_REQUIRE(nvec >= 1, TBK_EINVAL, "%s: nvec=%d", who, nvec);
+    TBK_REQUIRE(!(vectors && states), TBK_EINVAL, "%s: both vectors and states given", who);
+    TBK_REQUIRE(std::isfinite(emin) && std::isfinite(emax) && emax > emin, TBK_EINVAL, "%s: bounds (%g, %g)", who, emin, emax);
+    if (sp->dim_k == 0) *nk = 1;
+    TBK_REQUIRE(*nk >= 0 && (sp->dim_k == 0 || k || *nk == 0), TBK_EINVAL, "%s: null k list", who);
+    if (states)
+        for (int v = 0; v < nvec; ++v)
+            TBK_REQUIRE(states[v] >= 0 && states[v] < sp->nsta, TBK_EINVAL, "%s: state %d out of range [0, %d)", who, states[v], sp->nsta);
+    return TBK_OK;
+}
+
+// The launch plan of a call: the workgroups of every kernel on the row mapping, and the slots of `part`, one per step between two
+// reductions (steps 0 .. nsteps; step 0 is the norm of the start vectors).
+struct KpmPlan {
+    int nwg, nslots;
+    size_t slot_len() const { return (size_t)nwg * 2 * KPM_NV; }      // doubles of one slot
+    size_t part_len() const { return (size_t)nslots * slot_len(); }
+};
+static inline KpmPlan kpm_plan(int nsta, int nsteps) {
+    constexpr int RPB = 4 * (64 / KPM_NV);
+    const int64_t ntiles = ((int64_t)nsta + RPB - 1) / RPB;
+    KpmPlan P{(int)std::min<int64_t>(ntiles, KPM_MAX_WG), 1};
+    P.nslots = (int)std::max<size_t>(1, std::min<size_t>(std::min<size_t>(KPM_MAX_SLOTS, (size_t)nsteps + 1),
+                                                         KPM_PART_BYTES / (P.slot_len() * sizeof(double))));
+    return P;
+}
+
+// A device workspace carved by one list: layout(c) names every buffer once, c.take(pointer, elements); it runs once to add the
+// sizes up and once more on the allocation.
+struct KpmCarve {
+    unsigned char* base = nullptr;
+    size_t off = 0;
+    template <class T>
+    void take(T*& p, size_t count) {
+        p = base ? (T*)(base + off) : nullptr;
+        off += up256(count * sizeof(T));
+    }
+};
+template <class Layout>
+static int kpm_workspace(tbk_ctx* ctx, Layout&& layout, size_t* total) {
+    KpmCarve c;
+    layout(c);
+    *total = c.off;
+    void* ws = nullptr;
+    int rc = tbk_ctx_scratch(ctx, c.off, &ws);
+    if (rc) return rc;
+    c = KpmCarve{(unsigned char*)ws, 0};
+    layout(c);
+    return TBK_OK;
+}
+
+// The k list and the start vectors of a call: random phases (mode 0), unit vectors at `states` (1) or supplied `vectors` (2).
+struct KpmStart {
+    int dim_k, nsta, nvec, mode;
+    int64_t nk;
+    uint64_t seed;
+    const double* k;
+    const void* src;
+    double* k_dev = nullptr;
+    unsigned char* src_dev = nullptr;
+    KpmStart(const tbk_sparse* sp, const double* k_, int64_t nk_, int nvec_, const double* vectors, const int32_t* states, uint64_t seed_)
+        : dim_k(sp->dim_k), nsta(sp->nsta), nvec(nvec_), mode(vectors ? 2 : (states ? 1 : 0)), nk(nk_), seed(seed_), k(k_),
+          src(vectors ? (const void*)vectors : (const void*)states) {}
+    size_t src_bytes() const { return mode == 2 ? (size_t)nvec * nsta * sizeof(cd) : (mode == 1 ? (size_t)nvec * sizeof(int32_t) : 0); }
+    void carve(KpmCarve& c) {
+        c.take(k_dev, (size_t)nk * std::max(dim_k, 1));
+        c.take(src_dev, src_bytes());
+    }
+    int upload(tbk_ctx* ctx) const {
+        if (dim_k > 0) TBK_HIP(hipMemcpyAsync(k_dev, k, (size_t)nk * dim_k * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        if (mode != 0) TBK_HIP(hipMemcpyAsync(src_dev, src, src_bytes(), hipMemcpyHostToDevice, ctx->stream));
+        return TBK_OK;
+    }
+    const double* k_at(int64_t q) const { return k_dev + q * dim_k; }
+    // vectors v0 .. v0 + nv - 1 of k-point q -> cur, the partial sums of their norms -> part (one slot)
+    int launch(tbk_ctx* ctx, int nwg, int64_t q, int v0, int nv, cd* cur, double* part) const {
+        ProfScope ps(ctx, "kpm_init");
+        hipLaunchKernelGGL((k_kpm_init<KPM_NV>), dim3(nwg), dim3(256), 0, ctx->stream, nsta, nv, mode, seed, (uint64_t)(q * nvec + v0),
+                           mode == 1 ? (const int32_t*)src_dev + v0 : nullptr, mode == 2 ? (const cd*)src_dev + (size_t)v0 * nsta : nullptr,
+                           cur, part);
+        TBK_HIP(hipGetLastError());
+        return TBK_OK;
+    }
+};
+
+// dots[i] = the sums of slot i of part, i < count
+static int kpm_reduce(tbk_ctx* ctx, int nwg, int count, const double* part, double* dots) {
+    ProfScope ps(ctx, "kpm_reduce");
+    hipLaunchKernelGGL((k_kpm_reduce<KPM_NV>), dim3(count), dim3(256), 0, ctx->stream, nwg, part, dots);
+    TBK_HIP(hipGetLastError());
+    return TBK_OK;
+}
+
+// The order of a series of steps whose partial sums share nslots slots.  Step 0 (the start vectors) is in slot 0 on entry; steps
+// 1 .. nsteps follow, step(j, slot), and reduce(first, count) empties the slots 0 .. count - 1, which hold the steps first ..
+// first + count - 1, when all nslots are full and once more at the end.  No device call of its own.
+template <class Step, class Reduce>
+static int kpm_slot_schedule(int nsteps, int nslots, Step&& step, Reduce&& reduce) {
+    int chunk0 = 0;    // first step of the partial sums not yet reduced; step j sits in slot j - chunk0
+    for (int j = 1; j <= nsteps; ++j) {
+        if (j - chunk0 == nslots) {
+            int rc = reduce(chunk0, nslots);
+            if (rc) return rc;
+            chunk0 = j;
+        }
+        int rc = step(j, j - chunk0);
+        if (rc) return rc;
+    }
+    return reduce(chunk0, nsteps + 1 - chunk0);
+}
+
+// Steps 1 .. nsteps of a recursion on the buffers (cur, prev): launch(j, cur, prev, part_j) starts step j, which writes alpha_j
+// over prev (in place) and its partial sums into part_j; the buffers swap after every step.  -> dots[step][2][NV], steps 0 .. nsteps
+template <class Launch>
+static int kpm_run_steps(tbk_ctx* ctx, const KpmPlan& P, int nsteps, cd* cur, cd* prev, double* part, double* dots, Launch&& launch) {
+    return kpm_slot_schedule(
+        nsteps, P.nslots,
+        [&](int j, int slot) {
+            int rc = launch(j, (const cd*)cur, prev, part + (size_t)slot * P.slot_len());
+            std::swap(cur, prev);
+            return rc;
+        },
+        [&](int first, int count) { return kpm_reduce(ctx, P.nwg, count, part, dots + (size_t)first * 2 * KPM_NV); });
 }

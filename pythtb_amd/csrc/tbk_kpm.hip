@@ -22,9 +22,6 @@
 #include <vector>
 #include "tbk_kpm.h"
 
-#define KPM_MAX_SLOTS 128   // steps between two reductions of the partial sums
-#define KPM_PART_BYTES ((size_t)32 << 20)
-
 // ------------------------------------------------------------------ host assembly
 namespace {
 struct RawEntry {
@@ -274,64 +271,11 @@ extern "C" int tbk_sparse_info(tbk_sparse* sp, int* dim_k, int* nsta, int64_t* n
 }
 
 // ------------------------------------------------------------------ kernels
-// val[e] = amp[e] exp(2 pi i k.(R_e + orb_col - orb_row)) for one k; a lane per entry
-__global__ __launch_bounds__(256) void k_kpm_values(const int64_t nnz, const int dim_k, const double* __restrict__ k,
-                                                    const int32_t* __restrict__ col, const int32_t* __restrict__ row_of,
-                                                    const cd* __restrict__ amp, const int4* __restrict__ R,
-                                                    const double4* __restrict__ orb, cd* __restrict__ val) {
-    double kk[4] = {0.0, 0.0, 0.0, 0.0};
-    for (int d = 0; d < dim_k; ++d) kk[d] = k[d];
-    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < nnz; e += (int64_t)gridDim.x * 256) {
-        const int4 r = R[e];
-        const double4 oc = orb[col[e]], orw = orb[row_of[e]];
-        double x = kk[0] * ((double)r.x + oc.x - orw.x);
-        x = fma(kk[1], (double)r.y + oc.y - orw.y, x);
-        x = fma(kk[2], (double)r.z + oc.z - orw.z, x);
-        x = fma(kk[3], (double)r.w + oc.w - orw.w, x);
-        double s, c;
-        sincospi(2.0 * x, &s, &c);
-        val[e] = cmul(amp[e], cd{c, s});
-    }
-}
-
 __global__ __launch_bounds__(256) void k_kpm_randvec(const int nsta, const uint64_t seed, const int64_t first, const int64_t count,
                                                      cd* __restrict__ out) {
     const int64_t total = count * nsta;
     for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256)
         out[e] = kpm_random_phase(seed, (uint64_t)(first + e / nsta), (uint64_t)(e % nsta));
-}
-
-// One Chebyshev step for a block of NV vectors: nw = 2 H~ cur - prev (FIRST: nw = H~ cur), H~ = (H - b) / a, stored over prev -- row i
-// reads only its own element of prev, so two buffers are enough -- and the row-local parts of A = <nw|nw>, B = Re <nw|cur>.
-// A wavefront covers 64 / NV rows x NV vectors; each lane walks the entries of its row: the NV lanes of a row read the same
-// (val, col) pair and one contiguous 16 NV-byte segment of cur.  An empty row gives nw = -(2 b / a) cur - prev.
-template <int NV, bool FIRST>
-__global__ __launch_bounds__(256) void k_kpm_step(const int nsta, const int64_t* __restrict__ row_ptr, const int32_t* __restrict__ col,
-                                                  const cd* __restrict__ val, const cd* __restrict__ cur, cd* __restrict__ prev,
-                                                  const double b, const double inv_a, double* __restrict__ part) {
-    constexpr int RPW = 64 / NV, RPB = 4 * RPW;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, v = lane % NV, rw = lane / NV;
-    const int64_t ntiles = ((int64_t)nsta + RPB - 1) / RPB;
-    double dA = 0.0, dB = 0.0;
-    for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        const int64_t row = tile * RPB + wave * RPW + rw;
-        if (row < nsta) {
-            const int64_t e0 = row_ptr[row], e1 = row_ptr[row + 1];
-            cd acc{0.0, 0.0};
-            for (int64_t e = e0; e < e1; ++e) cfma(acc, val[e], cur[(int64_t)col[e] * NV + v]);
-            const cd x0 = cur[row * NV + v];
-            const cd h{(acc.x - b * x0.x) * inv_a, (acc.y - b * x0.y) * inv_a};
-            cd nw = h;
-            if (!FIRST) {
-                const cd p = prev[row * NV + v];
-                nw = cd{2.0 * h.x - p.x, 2.0 * h.y - p.y};
-            }
-            prev[row * NV + v] = nw;
-            dA += cabs2(nw);
-            dB += nw.x * x0.x + nw.y * x0.y;
-        }
-    }
-    kpm_block_sums<NV>(dA, dB, part);
 }
 
 // The doubling identities on dots[step] = (A_step[NV], B_step[NV]), A_j = <alpha_j|alpha_j>, B_j = Re <alpha_j|alpha_j-1>:
@@ -360,8 +304,8 @@ __global__ __launch_bounds__(256) void k_kpm_finish(const int nv, const int nmom
 int kpm_values_at(const tbk_sparse* sp, const double* k_dev, cd* val) {
     tbk_ctx* ctx = sp->ctx;
     ProfScope ps(ctx, "kpm_values");
-    hipLaunchKernelGGL(k_kpm_values, dim3(kpm_stream_grid(sp->nnz)), dim3(256), 0, ctx->stream, sp->nnz, sp->dim_k, k_dev, sp->col,
-                       sp->row_of, sp->amp, sp->R, sp->orb, val);
+    hipLaunchKernelGGL(k_kpm_values<false>, dim3(kpm_stream_grid(sp->nnz)), dim3(256), 0, ctx->stream, sp->nnz, sp->dim_k, 0, 0, k_dev,
+                       sp->col, sp->row_of, sp->amp, sp->R, sp->orb, val, (cd*)nullptr, (cd*)nullptr);
     TBK_HIP(hipGetLastError());
     return TBK_OK;
 }
@@ -391,101 +335,58 @@ extern "C" int tbk_kpm_moments(tbk_sparse* sp, const double* k, int64_t nk, int 
                                const double* vectors, const int32_t* states, uint64_t seed, double* mu) {
     constexpr int NV = KPM_NV, NC = 2 * NV;
     TBK_REQUIRE(sp && mu, TBK_EINVAL, "tbk_kpm_moments: null argument");
-    TBK_REQUIRE(n_moments >= 1, TBK_EINVAL, "tbk_kpm_moments: n_moments=%d", n_moments);
-    TBK_REQUIRE(nvec >= 1, TBK_EINVAL, "tbk_kpm_moments: nvec=%d", nvec);
-    TBK_REQUIRE(!(vectors && states), TBK_EINVAL, "tbk_kpm_moments: both vectors and states given");
-    TBK_REQUIRE(std::isfinite(emin) && std::isfinite(emax) && emax > emin, TBK_EINVAL, "tbk_kpm_moments: bounds (%g, %g)", emin, emax);
-    const int dim_k = sp->dim_k, n = sp->nsta;
-    if (dim_k == 0) nk = 1;
-    TBK_REQUIRE(nk >= 0 && (dim_k == 0 || k || nk == 0), TBK_EINVAL, "tbk_kpm_moments: null k list");
-    if (states)
-        for (int v = 0; v < nvec; ++v)
-            TBK_REQUIRE(states[v] >= 0 && states[v] < n, TBK_EINVAL, "tbk_kpm_moments: state %d out of range [0, %d)", states[v], n);
+    int rc = kpm_check_args("tbk_kpm_moments", sp, "n_moments", n_moments, nvec, vectors, states, emin, emax, k, &nk);
+    if (rc) return rc;
     if (nk == 0) return TBK_OK;
+    const int dim_k = sp->dim_k, n = sp->nsta;
     tbk_ctx* ctx = sp->ctx;
     TBK_HIP(hipSetDevice(ctx->device));
     const double a = 0.5 * (emax - emin), b = 0.5 * (emax + emin), inv_a = 1.0 / a;
     const int nsteps = n_moments / 2;                 // alpha_1 .. alpha_nsteps; step 0 is the norm of alpha_0
-    const int64_t ntiles = ((int64_t)n + 4 * (64 / NV) - 1) / (4 * (64 / NV));
-    const int nwg = (int)std::min<int64_t>(ntiles, KPM_MAX_WG);
-    const int nslots = (int)std::max<size_t>(1, std::min<size_t>(std::min<size_t>(KPM_MAX_SLOTS, (size_t)nsteps + 1),
-                                                                 KPM_PART_BYTES / ((size_t)nwg * NC * sizeof(double))));
-    const int mode = vectors ? 2 : (states ? 1 : 0);
-    const size_t b_val = dim_k > 0 ? up256((size_t)sp->nnz * sizeof(cd)) : 0, b_vec = up256((size_t)n * NV * sizeof(cd)),
-                 b_part = up256((size_t)nslots * nwg * NC * sizeof(double)), b_dots = up256((size_t)(nsteps + 1) * NC * sizeof(double)),
-                 b_mu = up256((size_t)nk * nvec * n_moments * sizeof(double)), b_k = up256((size_t)nk * std::max(dim_k, 1) * sizeof(double)),
-                 b_src = mode == 2 ? up256((size_t)nvec * n * sizeof(cd)) : (mode == 1 ? up256((size_t)nvec * sizeof(int32_t)) : 0);
-    void* ws = nullptr;
-    int rc = tbk_ctx_scratch(ctx, b_val + 2 * b_vec + b_part + b_dots + b_mu + b_k + b_src, &ws);
+    const KpmPlan P = kpm_plan(n, nsteps);
+    KpmStart start(sp, k, nk, nvec, vectors, states, seed);
+    cd *val_dev, *cur, *prev;
+    double *part, *dots, *mu_dev;
+    size_t total;
+    rc = kpm_workspace(ctx, [&](KpmCarve& c) {
+        c.take(val_dev, dim_k > 0 ? (size_t)sp->nnz : 0);
+        c.take(cur, (size_t)n * NV);
+        c.take(prev, (size_t)n * NV);
+        c.take(part, P.part_len());
+        c.take(dots, (size_t)(nsteps + 1) * NC);
+        c.take(mu_dev, (size_t)nk * nvec * n_moments);
+        start.carve(c);
+    }, &total);
     if (rc) return rc;
-    unsigned char* p = (unsigned char*)ws;
-    cd* val_dev = (cd*)p;
-    p += b_val;
-    cd* cur = (cd*)p;
-    p += b_vec;
-    cd* prev = (cd*)p;
-    p += b_vec;
-    double* part = (double*)p;
-    p += b_part;
-    double* dots = (double*)p;
-    p += b_dots;
-    double* mu_dev = (double*)p;
-    p += b_mu;
-    double* k_dev = (double*)p;
-    p += b_k;
-    void* src_dev = p;
-    if (dim_k > 0) TBK_HIP(hipMemcpyAsync(k_dev, k, (size_t)nk * dim_k * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    if (mode == 2) TBK_HIP(hipMemcpyAsync(src_dev, vectors, (size_t)nvec * n * sizeof(cd), hipMemcpyHostToDevice, ctx->stream));
-    if (mode == 1) TBK_HIP(hipMemcpyAsync(src_dev, states, (size_t)nvec * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-    const size_t part_slot = (size_t)nwg * NC;
+    rc = start.upload(ctx);
+    if (rc) return rc;
     for (int64_t q = 0; q < nk; ++q) {
         const cd* val = sp->amp;
         if (dim_k > 0) {
-            rc = kpm_values_at(sp, k_dev + q * dim_k, val_dev);
+            rc = kpm_values_at(sp, start.k_at(q), val_dev);
             if (rc) return rc;
             val = val_dev;
         }
         for (int v0 = 0; v0 < nvec; v0 += NV) {
             const int nv = std::min(NV, nvec - v0);
-            cd *x = cur, *y = prev;
-            {
-                ProfScope ps(ctx, "kpm_init");
-                hipLaunchKernelGGL((k_kpm_init<NV>), dim3(nwg), dim3(256), 0, ctx->stream, n, nv, mode, seed,
-                                   (uint64_t)(q * nvec + v0), mode == 1 ? (const int32_t*)src_dev + v0 : nullptr,
-                                   mode == 2 ? (const cd*)src_dev + (size_t)v0 * n : nullptr, x, part);
-                TBK_HIP(hipGetLastError());
-            }
-            int chunk0 = 0;    // first step of the partial sums not yet reduced; step j sits in slot j - chunk0
-            for (int j = 1; j <= nsteps; ++j) {
-                if (j - chunk0 == nslots) {
-                    ProfScope ps(ctx, "kpm_reduce");
-                    hipLaunchKernelGGL((k_kpm_reduce<NV>), dim3(nslots), dim3(256), 0, ctx->stream, nwg, part, dots + (size_t)chunk0 * NC);
-                    TBK_HIP(hipGetLastError());
-                    chunk0 = j;
-                }
-                double* pj = part + (size_t)(j - chunk0) * part_slot;
+            rc = start.launch(ctx, P.nwg, q, v0, nv, cur, part);
+            if (rc) return rc;
+            rc = kpm_run_steps(ctx, P, nsteps, cur, prev, part, dots, [&](int j, const cd* x, cd* y, double* pj) {
                 ProfScope ps(ctx, "kpm_step");
                 if (j == 1)
-                    hipLaunchKernelGGL((k_kpm_step<NV, true>), dim3(nwg), dim3(256), 0, ctx->stream, n, sp->row_ptr, sp->col, val, x, y, b,
-                                       inv_a, pj);
+                    hipLaunchKernelGGL((k_kpm_step<NV, true, KpmDots>), dim3(P.nwg), dim3(256), 0, ctx->stream, n, sp->row_ptr, sp->col, val,
+                                       x, nullptr, y, b, inv_a, KpmDots{pj});
                 else
-                    hipLaunchKernelGGL((k_kpm_step<NV, false>), dim3(nwg), dim3(256), 0, ctx->stream, n, sp->row_ptr, sp->col, val, x, y, b,
-                                       inv_a, pj);
+                    hipLaunchKernelGGL((k_kpm_step<NV, false, KpmDots>), dim3(P.nwg), dim3(256), 0, ctx->stream, n, sp->row_ptr, sp->col, val,
+                                       x, nullptr, y, b, inv_a, KpmDots{pj});
                 TBK_HIP(hipGetLastError());
-                std::swap(x, y);
-            }
-            {
-                ProfScope ps(ctx, "kpm_reduce");
-                hipLaunchKernelGGL((k_kpm_reduce<NV>), dim3(nsteps + 1 - chunk0), dim3(256), 0, ctx->stream, nwg, part,
-                                   dots + (size_t)chunk0 * NC);
-                TBK_HIP(hipGetLastError());
-            }
-            {
-                ProfScope ps(ctx, "kpm_finish");
-                hipLaunchKernelGGL((k_kpm_finish<NV>), dim3((unsigned)((nv * n_moments + 255) / 256)), dim3(256), 0, ctx->stream, nv,
-                                   n_moments, dots, mu_dev + ((size_t)q * nvec + v0) * n_moments);
-                TBK_HIP(hipGetLastError());
-            }
+                return TBK_OK;
+            });
+            if (rc) return rc;
+            ProfScope ps(ctx, "kpm_finish");
+            hipLaunchKernelGGL((k_kpm_finish<NV>), dim3((unsigned)((nv * n_moments + 255) / 256)), dim3(256), 0, ctx->stream, nv, n_moments,
+                               dots, mu_dev + ((size_t)q * nvec + v0) * n_moments);
+            TBK_HIP(hipGetLastError());
         }
     }
     const size_t nmu = (size_t)nk * nvec * n_moments;

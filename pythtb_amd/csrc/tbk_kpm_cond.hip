@@ -29,63 +29,6 @@
 #define KPMC_PART_BYTES ((size_t)64 << 20)   // ... and the workspace they may take
 
 // ------------------------------------------------------------------ kernels
-__device__ __forceinline__ double kpmc_pick(const double4 a, const int d) { return d == 0 ? a.x : (d == 1 ? a.y : (d == 2 ? a.z : a.w)); }
-__device__ __forceinline__ int kpmc_pick(const int4 a, const int d) { return d == 0 ? a.x : (d == 1 ? a.y : (d == 2 ? a.z : a.w)); }
-
-// k_kpm_values with the two velocity operators: val[e] = amp[e] exp(2 pi i k.(R_e + orb_col - orb_row)) and
-// va[e] = 2 pi i (R_e + orb_col - orb_row)_da val[e], vb the same along db; a lane per entry
-__global__ __launch_bounds__(256) void k_kpm_cond_values(const int64_t nnz, const int dim_k, const int da, const int db,
-                                                         const double* __restrict__ k, const int32_t* __restrict__ col,
-                                                         const int32_t* __restrict__ row_of, const cd* __restrict__ amp,
-                                                         const int4* __restrict__ R, const double4* __restrict__ orb,
-                                                         cd* __restrict__ val, cd* __restrict__ va, cd* __restrict__ vb) {
-    double kk[4] = {0.0, 0.0, 0.0, 0.0};
-    for (int d = 0; d < dim_k; ++d) kk[d] = k[d];
-    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < nnz; e += (int64_t)gridDim.x * 256) {
-        const int4 r = R[e];
-        const double4 oc = orb[col[e]], orw = orb[row_of[e]];
-        double x = kk[0] * ((double)r.x + oc.x - orw.x);
-        x = fma(kk[1], (double)r.y + oc.y - orw.y, x);
-        x = fma(kk[2], (double)r.z + oc.z - orw.z, x);
-        x = fma(kk[3], (double)r.w + oc.w - orw.w, x);
-        double s, c;
-        sincospi(2.0 * x, &s, &c);
-        const cd h = cmul(amp[e], cd{c, s});
-        const double ta = 2.0 * M_PI * ((double)kpmc_pick(r, da) + kpmc_pick(oc, da) - kpmc_pick(orw, da));
-        const double tb = 2.0 * M_PI * ((double)kpmc_pick(r, db) + kpmc_pick(oc, db) - kpmc_pick(orw, db));
-        val[e] = h;
-        va[e] = cd{-ta * h.y, ta * h.x};
-        vb[e] = cd{-tb * h.y, tb * h.x};
-    }
-}
-
-// out = s (A in - b in) - c prev for a block of NV vectors, A the CSR operator with the values `val`; prev == nullptr: no last term.
-// (b, s, prev) = (b, 1 / a, null): H~ in;  (b, 2 / a, prev): the Chebyshev step;  (0, 1, null): a velocity operator.  out may be
-// prev (row i reads only its own element of prev), never in.  The thread layout of k_kpm_step.
-template <int NV>
-__global__ __launch_bounds__(256) void k_kpm_apply(const int nsta, const int64_t* __restrict__ row_ptr, const int32_t* __restrict__ col,
-                                                   const cd* __restrict__ val, const cd* __restrict__ in, const cd* prev, cd* out,
-                                                   const double b, const double s) {
-    constexpr int RPW = 64 / NV, RPB = 4 * RPW;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, v = lane % NV, rw = lane / NV;
-    const int64_t ntiles = ((int64_t)nsta + RPB - 1) / RPB;
-    for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        const int64_t row = tile * RPB + wave * RPW + rw;
-        if (row < nsta) {
-            const int64_t e0 = row_ptr[row], e1 = row_ptr[row + 1];
-            cd acc{0.0, 0.0};
-            for (int64_t e = e0; e < e1; ++e) cfma(acc, val[e], in[(int64_t)col[e] * NV + v]);
-            const cd x0 = in[row * NV + v];
-            cd nw{(acc.x - b * x0.x) * s, (acc.y - b * x0.y) * s};
-            if (prev) {
-                const cd p = prev[row * NV + v];
-                nw = cd{nw.x - p.x, nw.y - p.y};
-            }
-            out[row * NV + v] = nw;
-        }
-    }
-}
-
 // part[chunk][m][n][NV] = sum over the rows of the chunk of conj(psi[m][row][v]) phi[n][row][v], m < KPMC_TM (zero from mt on),
 // n < nmom.  grid (chunks, ceil(nmom / KPMC_TN)); chunk c takes the row tiles c, c + chunks, ... of 64 / NV rows.  A lane owns one
 // (row, vector) pair and a 4 x 4 tile of sums: wavefront w the moments 4 w .. 4 w + 3 of psi, the workgroup the moments
@@ -153,100 +96,72 @@ extern "C" int tbk_kpm_double_moments(tbk_sparse* sp, const double* k, int64_t n
     TBK_REQUIRE(dim_k >= 1, TBK_EINVAL, "tbk_kpm_double_moments: the velocity operator needs a periodic axis (dim_k = 0)");
     TBK_REQUIRE(dir_a >= 0 && dir_a < dim_k && dir_b >= 0 && dir_b < dim_k, TBK_EINVAL,
                 "tbk_kpm_double_moments: directions (%d, %d) outside [0, %d)", dir_a, dir_b, dim_k);
-    TBK_REQUIRE(M >= 1, TBK_EINVAL, "tbk_kpm_double_moments: n_moments=%d", M);
-    TBK_REQUIRE(nvec >= 1, TBK_EINVAL, "tbk_kpm_double_moments: nvec=%d", nvec);
-    TBK_REQUIRE(!(vectors && states), TBK_EINVAL, "tbk_kpm_double_moments: both vectors and states given");
-    TBK_REQUIRE(std::isfinite(emin) && std::isfinite(emax) && emax > emin, TBK_EINVAL, "tbk_kpm_double_moments: bounds (%g, %g)", emin,
-                emax);
-    TBK_REQUIRE(nk >= 0 && (k || nk == 0), TBK_EINVAL, "tbk_kpm_double_moments: null k list");
-    if (states)
-        for (int v = 0; v < nvec; ++v)
-            TBK_REQUIRE(states[v] >= 0 && states[v] < n, TBK_EINVAL, "tbk_kpm_double_moments: state %d out of range [0, %d)", states[v], n);
+    int rc = kpm_check_args("tbk_kpm_double_moments", sp, "n_moments", M, nvec, vectors, states, emin, emax, k, &nk);
+    if (rc) return rc;
     if (nk == 0) return TBK_OK;
     tbk_ctx* ctx = sp->ctx;
     TBK_HIP(hipSetDevice(ctx->device));
     const double a = 0.5 * (emax - emin), b = 0.5 * (emax + emin), inv_a = 1.0 / a;
-    const int64_t ntiles = ((int64_t)n + 4 * (64 / NV) - 1) / (4 * (64 / NV));
-    const int nwg = (int)std::min<int64_t>(ntiles, KPM_MAX_WG);
-    const size_t vec_bytes = (size_t)n * NV * sizeof(cd);          // one block of vectors
-    const size_t chunk_bytes = (size_t)KPMC_TM * M * NV * sizeof(cd);   // the partial sums of one row chunk
+    const int nwg = kpm_plan(n, 0).nwg;
+    const size_t vec_len = (size_t)n * NV;                        // one block of vectors
+    const size_t chunk_len = (size_t)KPMC_TM * M * NV;            // the partial sums of one row chunk
     const int nchunk = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(((int64_t)n + 64 / NV - 1) / (64 / NV), KPMC_MAX_CHUNKS),
-                                                                   (int64_t)(KPMC_PART_BYTES / chunk_bytes)));
-    const int mode = vectors ? 2 : (states ? 1 : 0);
-    const size_t b_val = up256((size_t)sp->nnz * sizeof(cd)), b_vec = up256(vec_bytes), b_phi = up256((size_t)M * vec_bytes),
-                 b_psi = up256((size_t)KPMC_TM * vec_bytes), b_part = up256((size_t)nchunk * chunk_bytes),
-                 b_npart = up256((size_t)nwg * NC * sizeof(double)), b_norm = up256((size_t)NC * sizeof(double)),
-                 b_mu = up256((size_t)nk * nvec * M * M * sizeof(cd)), b_k = up256((size_t)nk * dim_k * sizeof(double)),
-                 b_src = mode == 2 ? up256((size_t)nvec * n * sizeof(cd)) : (mode == 1 ? up256((size_t)nvec * sizeof(int32_t)) : 0);
-    const size_t total = 3 * b_val + 2 * b_vec + b_phi + b_psi + b_part + b_npart + b_norm + b_mu + b_k + b_src;
-    void* ws = nullptr;
-    {
-        int rc = tbk_ctx_scratch(ctx, total, &ws);
-        if (rc == TBK_ENOMEM) {
-            (void)hipGetLastError();
-            tbk_set_error("tbk_kpm_double_moments: no device workspace of %zu bytes (%zu of them for the %d vectors T_n(H~) r of %d "
-                          "states, 8 start vectors at a time): use fewer moments",
-                          total, b_phi, M, n);
-        }
-        if (rc) return rc;
+                                                                   (int64_t)(KPMC_PART_BYTES / (chunk_len * sizeof(cd)))));
+    KpmStart start(sp, k, nk, nvec, vectors, states, seed);
+    cd *val, *va, *vb, *chi0, *chi1, *phi, *psi, *part, *mu_dev;
+    double *npart, *norm;
+    size_t total;
+    rc = kpm_workspace(ctx, [&](KpmCarve& c) {
+        c.take(val, (size_t)sp->nnz);
+        c.take(va, (size_t)sp->nnz);
+        c.take(vb, (size_t)sp->nnz);
+        c.take(chi0, vec_len);
+        c.take(chi1, vec_len);
+        c.take(phi, (size_t)M * vec_len);
+        c.take(psi, (size_t)KPMC_TM * vec_len);
+        c.take(part, (size_t)nchunk * chunk_len);
+        c.take(npart, (size_t)nwg * NC);
+        c.take(norm, (size_t)NC);
+        c.take(mu_dev, (size_t)nk * nvec * M * M);
+        start.carve(c);
+    }, &total);
+    if (rc == TBK_ENOMEM) {
+        (void)hipGetLastError();
+        tbk_set_error("tbk_kpm_double_moments: no device workspace of %zu bytes (%zu of them for the %d vectors T_n(H~) r of %d "
+                      "states, 8 start vectors at a time): use fewer moments",
+                      total, up256((size_t)M * vec_len * sizeof(cd)), M, n);
     }
-    unsigned char* p = (unsigned char*)ws;
-    auto take = [&p](size_t bytes) {
-        unsigned char* q = p;
-        p += bytes;
-        return q;
-    };
-    cd* val = (cd*)take(b_val);
-    cd* va = (cd*)take(b_val);
-    cd* vb = (cd*)take(b_val);
-    cd* chi0 = (cd*)take(b_vec);
-    cd* chi1 = (cd*)take(b_vec);
-    cd* phi = (cd*)take(b_phi);
-    cd* psi = (cd*)take(b_psi);
-    cd* part = (cd*)take(b_part);
-    double* npart = (double*)take(b_npart);
-    double* norm = (double*)take(b_norm);
-    cd* mu_dev = (cd*)take(b_mu);
-    double* k_dev = (double*)take(b_k);
-    void* src_dev = take(b_src);
-    TBK_HIP(hipMemcpyAsync(k_dev, k, (size_t)nk * dim_k * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    if (mode == 2) TBK_HIP(hipMemcpyAsync(src_dev, vectors, (size_t)nvec * n * sizeof(cd), hipMemcpyHostToDevice, ctx->stream));
-    if (mode == 1) TBK_HIP(hipMemcpyAsync(src_dev, states, (size_t)nvec * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-    const size_t vec_len = (size_t)n * NV;
-    // out = s (A in - shift in) - prev
-    auto apply = [&](const char* name, const cd* values, const cd* in, const cd* prev, cd* out, double shift, double s) -> int {
+    if (rc) return rc;
+    rc = start.upload(ctx);
+    if (rc) return rc;
+    // out = 2 H~ in - prev, out possibly prev; first: out = H~ in, or with the values of a velocity operator and (shift, scale) =
+    // (0, 1) the plain product
+    auto apply = [&](const char* name, const cd* values, const cd* in, bool first, const cd* prev, cd* out, double shift,
+                     double scale) -> int {
+        auto kernel = first ? k_kpm_step<NV, true, KpmNoSums>
+                            : (prev == out ? k_kpm_step<NV, false, KpmNoSums> : k_kpm_step<NV, false, KpmNoSums, false>);
         ProfScope ps(ctx, name);
-        hipLaunchKernelGGL((k_kpm_apply<NV>), dim3(nwg), dim3(256), 0, ctx->stream, n, sp->row_ptr, sp->col, values, in, prev, out, shift,
-                           s);
+        hipLaunchKernelGGL(kernel, dim3(nwg), dim3(256), 0, ctx->stream, n, sp->row_ptr, sp->col, values, in, prev, out, shift, scale,
+                           KpmNoSums{});
         TBK_HIP(hipGetLastError());
         return TBK_OK;
     };
     for (int64_t q = 0; q < nk; ++q) {
         {
             ProfScope ps(ctx, "kpm_cond_values");
-            hipLaunchKernelGGL(k_kpm_cond_values, dim3(kpm_stream_grid(sp->nnz)), dim3(256), 0, ctx->stream, sp->nnz, dim_k, dir_a, dir_b,
-                               k_dev + q * dim_k, sp->col, sp->row_of, sp->amp, sp->R, sp->orb, val, va, vb);
+            hipLaunchKernelGGL(k_kpm_values<true>, dim3(kpm_stream_grid(sp->nnz)), dim3(256), 0, ctx->stream, sp->nnz, dim_k, dir_a, dir_b,
+                               start.k_at(q), sp->col, sp->row_of, sp->amp, sp->R, sp->orb, val, va, vb);
             TBK_HIP(hipGetLastError());
         }
         for (int v0 = 0; v0 < nvec; v0 += NV) {
             const int nv = std::min(NV, nvec - v0);
-            int rc;
-            {   // Phi_0 = r and the partial sums of <r|r>
-                ProfScope ps(ctx, "kpm_init");
-                hipLaunchKernelGGL((k_kpm_init<NV>), dim3(nwg), dim3(256), 0, ctx->stream, n, nv, mode, seed, (uint64_t)(q * nvec + v0),
-                                   mode == 1 ? (const int32_t*)src_dev + v0 : nullptr,
-                                   mode == 2 ? (const cd*)src_dev + (size_t)v0 * n : nullptr, phi, npart);
-                TBK_HIP(hipGetLastError());
-            }
-            {
-                ProfScope ps(ctx, "kpm_reduce");
-                hipLaunchKernelGGL((k_kpm_reduce<NV>), dim3(1), dim3(256), 0, ctx->stream, nwg, npart, norm);
-                TBK_HIP(hipGetLastError());
-            }
+            rc = start.launch(ctx, nwg, q, v0, nv, phi, npart);    // Phi_0 = r and the partial sums of <r|r>
+            if (rc) return rc;
+            rc = kpm_reduce(ctx, nwg, 1, npart, norm);
+            if (rc) return rc;
             for (int j = 1; j < M; ++j) {   // Phi_j = T_j(H~) r
                 cd* out = phi + (size_t)j * vec_len;
-                rc = j == 1 ? apply("kpm_apply", val, phi, nullptr, out, b, inv_a)
-                            : apply("kpm_apply", val, out - vec_len, out - 2 * vec_len, out, b, 2.0 * inv_a);
+                rc = apply("kpm_apply", val, out - vec_len, j == 1, out - 2 * vec_len, out, b, inv_a);
                 if (rc) return rc;
             }
             cd *x = chi0, *y = chi1;        // x = chi_m, y = chi_m-1
@@ -254,14 +169,13 @@ extern "C" int tbk_kpm_double_moments(tbk_sparse* sp, const double* k, int64_t n
                 const int mt = std::min(KPMC_TM, M - m0);
                 for (int m = m0; m < m0 + mt; ++m) {
                     if (m == 0) {
-                        rc = apply("kpm_apply_v", va, phi, nullptr, x, 0.0, 1.0);              // chi_0 = V^a r
+                        rc = apply("kpm_apply_v", va, phi, true, nullptr, x, 0.0, 1.0);              // chi_0 = V^a r
                     } else {
-                        rc = m == 1 ? apply("kpm_apply", val, x, nullptr, y, b, inv_a)          // chi_1 = H~ chi_0
-                                    : apply("kpm_apply", val, x, y, y, b, 2.0 * inv_a);         // chi_m+1 = 2 H~ chi_m - chi_m-1, over chi_m-1
+                        rc = apply("kpm_apply", val, x, m == 1, y, y, b, inv_a);    // chi_1 = H~ chi_0, chi_m+1 = 2 H~ chi_m - chi_m-1 over chi_m-1
                         std::swap(x, y);
                     }
                     if (rc) return rc;
-                    rc = apply("kpm_apply_v", vb, x, nullptr, psi + (size_t)(m - m0) * vec_len, 0.0, 1.0);   // psi_m = V^b chi_m
+                    rc = apply("kpm_apply_v", vb, x, true, nullptr, psi + (size_t)(m - m0) * vec_len, 0.0, 1.0);   // psi_m = V^b chi_m
                     if (rc) return rc;
                 }
                 {

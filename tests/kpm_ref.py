@@ -150,3 +150,18 @@ def gauss_nodes(n, bounds):
     a, b = 0.5 * (bounds[1] - bounds[0]), 0.5 * (bounds[1] + bounds[0])
     x = np.cos(np.pi * (np.arange(n) + 0.5) / n)
     return x, a * x + b
+
+
+RING_N = 2048 * 32 + 33      # one more full row tile for workgroup 0 and a tail tile of one row for workgroup 1, past 2048 workgroups
+
+
+def ring_tables(n=RING_N, hop=-0.8 + 0.3j, seed=41):
+    """The tables tbk_sparse_upload takes for a ring of n orbitals in one cell (dim_k = 1): orbital i at i / n, random real on-site
+    energies in [-0.5, 0.5], the hop `hop` from every orbital to the next, the closing bond to the next cell (R = 1).  Built as
+    arrays: a model of this size does not go through set_hop."""
+    i = np.arange(n, dtype=np.int32)
+    R = np.zeros((n, 1), dtype=np.int32)
+    R[-1] = 1
+    return dict(orb=np.ascontiguousarray((np.arange(n) / n).reshape(n, 1)),
+                onsite=np.random.default_rng(seed).uniform(-0.5, 0.5, n).astype(complex), hop_i=i,
+                hop_j=np.ascontiguousarray((i + 1) % n, dtype=np.int32), hop_R=R, hop_amp=np.full(n, hop, dtype=complex))

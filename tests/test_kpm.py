@@ -3,6 +3,7 @@ DESIGN.md section 21).  The CPU tests check the NumPy restatement kpm_ref.py aga
 CSR operator against the dense H(k) of the oracle, and the reconstruction against Chebyshev-Gauss quadrature; the GPU tests check
 the device moments against the restatement with the same vectors (moments satisfy |mu| <= 1: absolute bounds), against the exact
 eigen-moments, past the dense limit of 2048 states, and the generator's and the error paths' contracts."""
+import ctypes as C
 import functools
 import time
 
@@ -284,6 +285,113 @@ def test_generator_contract(gpu_ctx):
     mk, _ = h.kpm_moments(33, k, n_vectors=3, seed=7)
     assert np.array_equal(mk[1], h.kpm_moments(33, k[1:], vectors=h.kpm_vectors(3, seed=7, first=3))[0][0])
     assert np.array_equal(mk, h.kpm_moments(33, k, n_vectors=3, seed=7)[0])
+
+
+@pytest.mark.gpu
+def test_two_calls_same_bits(gpu_ctx):
+    """the partial sums of a step are added in a fixed order: nine vectors (a full and a short block) at two k-points"""
+    m = model("haldane6x6")
+    k = kpoints(m, 2)
+    a, _ = m.kpm_moments(64, k, n_vectors=9, seed=5)
+    b, _ = m.kpm_moments(64, k, n_vectors=9, seed=5)
+    assert a.shape == (2, 9, 64) and np.array_equal(a, b)
+
+
+@functools.lru_cache(maxsize=None)
+def ring_reference(ctype=complex):
+    """The long ring of kpm_ref.ring_tables at one k with nine supplied vectors, in NumPy: H v = eps v + h roll(v, -1) +
+    conj(h) roll(v, 1) with h = hop e^{2 pi i k / n}, and V = dH/dk the hopping part times +- 2 pi i / n.  Returns the arguments
+    (tables, k, bounds, vectors, coefficients (2, 4)) and the references: moments (9, 5), series (2, 9, n), double moments (9, 3, 3).
+    ctype=np.clongdouble runs the same recursions in extended precision (the check of this float64 reference)."""
+    tab = kr.ring_tables()
+    n = kr.RING_N
+    ftype = np.longdouble if ctype is np.clongdouble else float
+    k = 0.3125
+    eps = tab["onsite"].real.astype(ftype)
+    hop0 = complex(tab["hop_amp"][0])
+    lo, hi = eps.min() - 2 * abs(hop0), eps.max() + 2 * abs(hop0)          # the Gershgorin interval, 1 % wider on each side
+    bnd = (float(lo - 0.01 * (hi - lo)), float(hi + 0.01 * (hi - lo)))
+    a, b = ftype(0.5) * (ftype(bnd[1]) - ftype(bnd[0])), ftype(0.5) * (ftype(bnd[1]) + ftype(bnd[0]))
+    two_pi = 8 * np.arctan(ftype(1))
+    h = ctype(hop0) * np.exp(ctype(1j) * (two_pi * ftype(k) / n))
+    rng = np.random.default_rng(17)
+    vec = rng.standard_normal((9, n)) + 1j * rng.standard_normal((9, n))
+    coef = rng.standard_normal((2, 4)) + 1j * rng.standard_normal((2, 4))
+
+    def Ht(v):
+        return (eps * v + h * np.roll(v, -1, axis=-1) + np.conj(h) * np.roll(v, 1, axis=-1) - b * v) / a
+
+    def Vel(v):
+        return ctype(1j) * (two_pi / n) * (h * np.roll(v, -1, axis=-1) - np.conj(h) * np.roll(v, 1, axis=-1))
+
+    def cheb(v, M):
+        T = [v, Ht(v)]
+        while len(T) < M:
+            T.append(2 * Ht(T[-1]) - T[-2])
+        return T[:M]
+
+    def dot(x, y):       # pairwise sums over the ring
+        return np.sum(np.conj(x) * y, axis=-1)
+
+    v = vec.astype(ctype)
+    norm = dot(v, v).real
+    T = cheb(v, 5)
+    mu = np.stack([dot(v, t).real / norm for t in T], axis=1)
+    series = np.stack([sum(ctype(c) * t for c, t in zip(cs, T)) for cs in coef])
+    dbl = np.stack([np.stack([dot(v, Vel(tm)) / norm for tm in cheb(Vel(tn), 3)], axis=1) for tn in T[:3]], axis=2)
+    return (tab, k, bnd, vec, coef), (mu, series, dbl)
+
+
+def ring_velocity_bound(tab):
+    n, vb = len(tab["orb"]), np.zeros(4)
+    tb._lib.check(tb._lib.lib.tbk_sparse_velocity_bounds_host(
+        1, n, 1, tb._lib.dptr(tab["orb"]), tb._lib.dptr(tab["onsite"].view(float)), n, tb._lib.iptr(tab["hop_i"]),
+        tb._lib.iptr(tab["hop_j"]), tb._lib.iptr(tab["hop_R"].reshape(-1)), tb._lib.dptr(tab["hop_amp"].view(float)), tb._lib.dptr(vb)))
+    return vb[0]
+
+
+def test_ring_reference_against_extended_precision():
+    """the float64 reference of test_rows_past_the_grid stays within a tenth of each of its bounds of the same recursions in
+    numpy.longdouble (measured: moments 2.3e-16, series 4.7e-16 of max|result|, double moments 2.6e-16 of ||V||^2, each against
+    a bound of 1e-12; printed)"""
+    (tab, _, _, _, _), (mu, series, dbl) = ring_reference()
+    _, (mu_x, series_x, dbl_x) = ring_reference(np.clongdouble)
+    e_mu = np.abs(mu - mu_x).max()
+    e_series = np.abs(series - series_x).max() / np.abs(series).max()
+    e_dbl = np.abs(dbl - dbl_x).max() / ring_velocity_bound(tab) ** 2
+    print("ring reference against longdouble: moments %.2e, series %.2e, double moments %.2e" % (e_mu, e_series, e_dbl))
+    assert max(e_mu, e_series, e_dbl) <= 0.1 * TOL
+
+
+@pytest.mark.gpu
+def test_rows_past_the_grid(gpu_ctx):
+    """A ring of 2048 * 32 + 33 orbitals: more row tiles than the 2048 workgroups of a step, so workgroup 0 strides to a second
+    full tile and workgroup 1 to a tail tile of one row -- in every kernel on the row mapping (start vectors, the steps with each
+    epilogue).  Moments, a series and double moments of nine supplied vectors against the NumPy ring."""
+    (tab, k, bnd, vec, coef), (mu_ref, series_ref, dbl_ref) = ring_reference()
+    L, n, nvec = tb._lib, kr.RING_N, len(vec)
+    sp = C.c_void_p()
+    L.check(L.lib.tbk_sparse_upload(gpu_ctx.handle, 1, n, 1, L.dptr(tab["orb"]), L.dptr(tab["onsite"].view(float)), n,
+                                    L.iptr(tab["hop_i"]), L.iptr(tab["hop_j"]), L.iptr(tab["hop_R"].reshape(-1)),
+                                    L.dptr(tab["hop_amp"].view(float)), C.byref(sp)))
+    try:
+        kk, V = np.array([[k]]), L.dptr(vec.view(float))
+        mu = np.empty((nvec, 5))
+        L.check(L.lib.tbk_kpm_moments(sp, L.dptr(kk), 1, 5, bnd[0], bnd[1], nvec, V, None, 0, L.dptr(mu)))
+        out = np.empty((2, nvec, n), dtype=complex)
+        L.check(L.lib.tbk_kpm_apply_series(sp, L.dptr(kk), 1, 4, 2, L.dptr(coef.view(float)), bnd[0], bnd[1], nvec, V, None, 0,
+                                           L.dptr(out.view(float))))
+        dbl = np.empty((nvec, 3, 3), dtype=complex)
+        L.check(L.lib.tbk_kpm_double_moments(sp, L.dptr(kk), 1, 3, bnd[0], bnd[1], 0, 0, nvec, V, None, 0, L.dptr(dbl.view(float))))
+    finally:
+        L.check(L.lib.tbk_sparse_free(sp))
+    e_mu = np.abs(mu - mu_ref).max()
+    e_series = np.abs(out - series_ref).max() / np.abs(series_ref).max()
+    e_dbl = np.abs(dbl - dbl_ref).max() / ring_velocity_bound(tab) ** 2
+    print("ring of %d: moments %.2e, series %.2e of max|result|, double moments %.2e of |V|^2" % (n, e_mu, e_series, e_dbl))
+    assert e_mu < TOL
+    assert e_series <= TOL
+    assert e_dbl <= TOL
 
 
 @pytest.fixture(scope="module")
