@@ -691,38 +691,30 @@ __global__ __launch_bounds__(256) void k_flux(const FluxArgs A) {
 // loads overlap, then an LDS tree) -- the same order every run, no atomics
 __global__ __launch_bounds__(1024) void k_flux_reduce(const double* __restrict__ partial, int bps,
                                                       double* __restrict__ totals, const DoneArgs done) {
-    const double* p = partial + (int64_t)blockIdx.x * bps;
-    double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
     // (four loads in flight per thread, the tail included: the 2112 partials of a 2048^2 mesh are one round of loads -- this kernel
-    // is pure latency in front of every berry_flux return; the shape of the sum depends on bps alone)
-    for (int i = threadIdx.x; i < bps; i += 4 * 1024) {
-        const double v0 = p[i];
-        const double v1 = i + 1024 < bps ? p[i + 1024] : 0.0;
-        const double v2 = i + 2048 < bps ? p[i + 2048] : 0.0;
-        const double v3 = i + 3072 < bps ? p[i + 3072] : 0.0;
-        s0 += v0;
-        s1 += v1;
-        s2 += v2;
-        s3 += v3;
-    }
-    // fixed-shape tree: xor-butterfly inside each wavefront (the same bits in every lane), then the 16 wavefront sums in
-    // index order -- two barriers instead of the ten of an LDS tree over 1024 entries
-    double s = (s0 + s1) + (s2 + s3);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
+    // is pure latency in front of every berry_flux return; the shape of the sum depends on bps alone.  The sum itself is
+    // tbk_flux_sum_fixed, tbk_internal.h: a mesh solve that carries the reduction forms the same bits with it)
     __shared__ double red[16];
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
+    const double t = tbk_flux_sum_fixed<1024>(partial + (int64_t)blockIdx.x * bps, bps, red);
     if (threadIdx.x == 0) {
-        double t = red[0];
-#pragma unroll
-        for (int i = 1; i < 16; ++i) t += red[i];
-        red[0] = t;
-    }
-    if (threadIdx.x == 0) {
-        totals[blockIdx.x] = red[0];
+        totals[blockIdx.x] = t;
         tbk_signal_done(done);      // (the call's last kernel: tbk_berry_flux_result may be polling the completion word)
     }
+}
+
+// A reduction left pending by tbk_berry_flux_async, launched on its own: by tbk_berry_flux_result when no mesh solve has taken it
+// along, and in front of every call that would overwrite the partials or the totals (every requested total is computed).
+int tbk_flux_flush_pending(tbk_wfs* w, bool arm) {
+    if (w->flux_pend_n <= 0) return TBK_OK;
+    tbk_ctx* ctx = w->ctx;
+    ProfScope ps(ctx, "flux_reduce");
+    w->flux_done = (arm && w->flux_totals_host) ? tbk_done_arm(ctx, false) : DoneArgs{nullptr, nullptr, nullptr, 0u};
+    hipLaunchKernelGGL(k_flux_reduce, dim3((unsigned)w->flux_pend_nslices), dim3(1024), 0, ctx->stream,
+                       (const double*)w->flux_partial_dev, w->flux_pend_n, w->flux_totals_dev, w->flux_done);
+    w->flux_pend_n = 0;
+    w->flux_pend_nslices = 0;
+    TBK_HIP(hipGetLastError());
+    return TBK_OK;
 }
 
 static int check_occ(const tbk_wfs* w, const int32_t* occ, int nocc) {
@@ -814,6 +806,9 @@ extern "C" int tbk_berry_flux_async(tbk_wfs* w, const int32_t* occ, int nocc, in
     if (rc) return rc;
     tbk_ctx* ctx = w->ctx;
     TBK_HIP(hipSetDevice(ctx->device));
+    // this call rewrites the partials and the totals: a reduction still pending from the call before is launched first
+    rc = tbk_flux_flush_pending(w, false);
+    if (rc) return rc;
     A.v = v;
     A.nocc = nocc;
     A.n0 = v.mesh[dir0] - 1;
@@ -1015,7 +1010,14 @@ extern "C" int tbk_berry_flux_async(tbk_wfs* w, const int32_t* occ, int nocc, in
         }
         TBK_HIP(hipGetLastError());
     }
-    if (!rows || !A.fused || slices_k) {
+    if ((!rows || !A.fused || slices_k) && nslices == 1 && !want_plaq && tbk_knobs().flux_defer != 0) {
+        // ---- the sum is left pending: the next row-kernel mesh solve of this array does it in one extra workgroup
+        // (solve_window_impl) -- in a loop that queues the next solve before it fetches this total the step is two launches, not
+        // three -- and tbk_berry_flux_result launches it itself when nothing has.  One slice only: what that workgroup serves.
+        w->flux_pend_n = (rows && !slices_k) ? A.bpb : A.bps;
+        w->flux_pend_nslices = 1;
+        w->flux_done = DoneArgs{nullptr, nullptr, nullptr, 0u};
+    } else if (!rows || !A.fused || slices_k) {
         ProfScope ps(ctx, "flux_reduce");
         // totals in mapped host memory and no per-plaquette output: this is the call's last kernel, the result call polls its
         // completion word instead of synchronising the stream
@@ -1033,6 +1035,12 @@ extern "C" int tbk_berry_flux_result(tbk_wfs* w, double* totals, double* plaq) {
     TBK_REQUIRE(w && totals, TBK_EINVAL, "tbk_berry_flux_result: null argument");
     TBK_REQUIRE(w->flux_nslices > 0, TBK_EINVAL, "tbk_berry_flux_result: no flux launch pending");
     tbk_ctx* ctx = w->ctx;
+    {
+        // a reduction no mesh solve has taken along: launched here, completion word armed, as tbk_berry_flux_async used to.  One that
+        // a solve did take along has no completion word of its own (w->flux_done is not armed): the wait below is for the stream.
+        const int rc = tbk_flux_flush_pending(w, true);
+        if (rc) return rc;
+    }
     if (plaq) {
         TBK_REQUIRE(w->flux_plaq_n > 0, TBK_EINVAL, "tbk_berry_flux_result: plaquettes were not requested");
         TBK_HIP(hipMemcpyAsync(plaq, w->flux_plaq_dev, w->flux_plaq_n * sizeof(double), hipMemcpyDeviceToHost,

@@ -76,6 +76,7 @@ static void knobs_parse() {
     geti("TBK_FLUX_TI", k.flux_ti);
     geti("TBK_FLUX_FUSED", k.flux_fused);
     geti("TBK_FLUX_ORDER", k.flux_order);
+    geti("TBK_FLUX_DEFER", k.flux_defer);
     geti("TBK_REG_DIRECT", k.reg_direct);
     geti("TBK_REG_CELLS", k.reg_cells);
     geti("TBK_FLUX_SLICES", k.flux_slices);
@@ -316,6 +317,11 @@ void tbk_wfs_totals_free(tbk_wfs* w) {
     w->flux_totals_dev = nullptr;
 }
 int tbk_wfs_totals_alloc(tbk_wfs* w, int64_t nslices) {
+    if (w->flux_pend_n > 0) {   // (a pending reduction still wants the old totals: computed first, and finished before they go)
+        const int rc = tbk_flux_flush_pending(w, false);
+        if (rc) return rc;
+        TBK_HIP(hipStreamSynchronize(w->ctx->stream));
+    }
     tbk_wfs_totals_free(w);
     const size_t bytes = (size_t)std::max<int64_t>(nslices, 1) * sizeof(double);
     if (bytes <= 64 * 1024 && tbk_knobs().zero_copy_kb > 0) {

@@ -84,6 +84,7 @@ struct TbkKnobs {
     int flux_slices = 1;        // TBK_FLUX_SLICES   0: planes without the fastest mesh axis on the row kernel instead of k_flux_slices (lane = slice)
     int flux_fused = 0;         // TBK_FLUX_FUSED    1: final flux sum inside the kernel
     int flux_order = -1;        // TBK_FLUX_ORDER    0: row tiles newest rows first, 1: oldest first (default: by the array's size)
+    int flux_defer = 1;         // TBK_FLUX_DEFER    0: tbk_berry_flux_async launches k_flux_reduce itself instead of leaving the sum to the next mesh solve / the result call
     int trigv_from = -1;        // TBK_TRIGV_FROM    smallest n of the workgroup-scale direct eigenvector path (default 65; A/B runs down to 17)
     int chain_ws_mb = 1024;     // TBK_CHAIN_WS_MB   link-matrix workspace per batch of strings, MiB
     int mesh_rows = 1;          // TBK_MESH_ROWS     0: eigenvalues on a generated uniform mesh by the list kernel on the generated list instead of the row kernel k_mesh_evals
@@ -298,6 +299,43 @@ __device__ inline void tbk_signal_done(const DoneArgs& d) {
         __hip_atomic_store(d.word, d.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     }
 }
+
+// ---- the total of one slice's flux partials: ONE summation shape, used by k_flux_reduce (tbk_berry.hip, 1024 threads) and by the
+// extra workgroup of a mesh solve that carries a pending reduction (k_grid_rows, tbk_solve.hip, 256 threads).  1024 VIRTUAL threads:
+// virtual thread v adds p[v + 1024 k + 4096 j] into accumulator s_k (k = 0..3, j ascending; four loads in flight, the tail included),
+// forms (s0 + s1) + (s2 + s3), an xor butterfly inside its group of 64 leaves the group's sum in every lane, and the 16 group sums
+// are added in index order.  A workgroup of NT threads plays the virtual threads in 1024 / NT rounds of its NT / 64 wavefronts
+// (round r, thread t: v = r NT + t -- a wavefront always is one whole group).  The shape depends on n alone, and the function holds
+// nothing but additions, so there is nothing the compiler could contract differently in its two instantiations: the same bits.
+// `red`: 16 doubles of LDS.  Every thread of the workgroup calls it; the return value is the total in every thread.
+template <int NT>
+__device__ __forceinline__ double tbk_flux_sum_fixed(const double* __restrict__ p, const int n, double* red) {
+    static_assert(NT % 64 == 0 && 1024 % NT == 0, "tbk_flux_sum_fixed: whole wavefronts, whole rounds");
+#pragma unroll
+    for (int r = 0; r < 1024 / NT; ++r) {
+        const int v = r * NT + (int)threadIdx.x;
+        double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
+        for (int i = v; i < n; i += 4 * 1024) {
+            const double v0 = p[i];
+            const double v1 = i + 1024 < n ? p[i + 1024] : 0.0;
+            const double v2 = i + 2048 < n ? p[i + 2048] : 0.0;
+            const double v3 = i + 3072 < n ? p[i + 3072] : 0.0;
+            s0 += v0;
+            s1 += v1;
+            s2 += v2;
+            s3 += v3;
+        }
+        double s = (s0 + s1) + (s2 + s3);
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
+        if ((threadIdx.x & 63) == 0) red[v >> 6] = s;
+    }
+    __syncthreads();
+    double t = red[0];
+#pragma unroll
+    for (int i = 1; i < 16; ++i) t += red[i];
+    return t;
+}
 #endif
 
 // RAII bracket recording HIP events around one kernel launch when profiling.
@@ -402,7 +440,16 @@ struct tbk_wfs {
     int64_t flux_plaq_cap = 0, flux_plaq_n = 0;
     double* flux_partial_dev = nullptr;
     int64_t flux_partial_cap = 0;
+    // a reduction tbk_berry_flux_async left pending (TBK_FLUX_DEFER): flux_pend_nslices slices of flux_pend_n partials each in
+    // flux_partial_dev, their totals wanted in flux_totals_dev.  flux_pend_n == 0: none.  Consumed by the next row-kernel mesh
+    // solve of this array (one extra workgroup), by tbk_berry_flux_result, or by tbk_flux_flush_pending in front of whatever
+    // would overwrite the partials or the totals -- whichever comes first; tbk_wfs_free drops it.
+    int flux_pend_n = 0;
+    int64_t flux_pend_nslices = 0;
 };
+// tbk_berry.hip: launch k_flux_reduce for a pending reduction of `w` (no-op without one).  `arm`: with the completion word for
+// tbk_berry_flux_result to poll (w->flux_done), as the launch inside tbk_berry_flux_async arms it.
+int tbk_flux_flush_pending(struct tbk_wfs* w, bool arm);
 
 // tbk_solve.hip: eigenvalues on k_uniform_mesh(mesh) by the row kernel (n <= 4); *done = false where it does not apply
 int tbk_mesh_evals_rows(struct tbk_model* m, const int32_t* mesh, double* e_dev, bool* done);

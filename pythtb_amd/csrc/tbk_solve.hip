@@ -1109,9 +1109,25 @@ __device__ __forceinline__ double uniform_d(const double v) {
 #ifndef TBK_ROWS_OCC
 #define TBK_ROWS_OCC
 #endif
+// ---- the flux total a berry_flux call left pending on this array (tbk_berry_flux_async, TBK_FLUX_DEFER), carried by the mesh solve
+// that follows it on the stream: ONE extra workgroup, the launch's last, forms it with k_flux_reduce's own summation
+// (tbk_flux_sum_fixed: the same bits) and returns.  The partials were written by an earlier kernel of the same stream, so plain loads
+// see them; the total is read by the host after this launch has completed.  Inlined behind a uniform branch at the very top of the
+// kernel, it leaves the tile path's registers, LDS and occupancy as they were (as a call it cost k_grid_rows<2,1> five scalar
+// registers for the calling convention).
+__device__ __forceinline__ void grid_carried_flux_sum(const double* __restrict__ partial, const int n, double* __restrict__ total,
+                                                      double* red) {
+    const double t = tbk_flux_sum_fixed<256>(partial, n, red);
+    if (threadIdx.x == 0) total[0] = t;
+}
+
 template <int N, int PM>
 __global__ __launch_bounds__(256) TBK_ROWS_OCC void k_grid_rows(const ModelView mv, const GridArgs G) {
     extern __shared__ __align__(16) unsigned char lds_rows[];
+    if (G.red_n > 0 && (int64_t)blockIdx.x * 4 >= G.ntiles) {   // (the workgroup past the last tile; uniform, before anything else: no tile is touched or delayed)
+        grid_carried_flux_sum(G.red_partial, G.red_n, G.red_total, reinterpret_cast<double*>(lds_rows));
+        return;
+    }
     constexpr int NSLOT = N * (N + 1) / 2;
     // (the wavefront's number in scalar registers: the tile, its row, chunk range, LDS regions and output base are then scalar too)
     const int wib = N > 2 ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : (int)(threadIdx.x >> 6);
@@ -2922,6 +2938,11 @@ static int solve_window_impl(tbk_wfs* w, tbk_model* m, const double* start_k, co
                     TBK_EUNSUPPORTED, "tbk_wfs_solve_grid_flux: a %d-D array of %d states (last-axis range %d): the fused kernel "
                     "serves 2-D arrays of 2 states (range <= 2) or 4 states (range 1)", D, n, pm);
         const TbkKnobs& K = tbk_knobs();
+        // the fused kernel writes the flux partials itself: a reduction still pending on them is finished by its own launch first
+        {
+            const int rcp = tbk_flux_flush_pending(w, false);
+            if (rcp) return rcp;
+        }
         FusedArgs F{};
         // tile shape (measured, profiles/fused_sweep.py, us per step, rows R x chunks seg).  2048^2 (the array fits the 256 MiB
         // last-level cache): R = 3 73-86, 4 67-79, 5 67-75, 6 65-74, 8 63-87, 12 63-66, best around 6 x 2.  4096^2 (beyond it): tall
@@ -3060,7 +3081,7 @@ static int solve_window_impl(tbk_wfs* w, tbk_model* m, const double* start_k, co
                         160 * 1024 / 2 + 1024);
             if (tbk_knobs().grid_occ > 0 && tbk_knobs().grid_occ < 8)
                 lds = std::max(lds, (size_t)(160 * 1024) / (size_t)(tbk_knobs().grid_occ + 1) + 1024);
-            const unsigned blocks = (unsigned)((G.ntiles + 3) / 4);
+            unsigned blocks = (unsigned)((G.ntiles + 3) / 4);
             const int64_t npart = G.ntiles * std::max(n - 1, 1);
             if (w->gap_part_cap < npart) {
                 TBK_HIP(hipStreamSynchronize(ctx->stream));
@@ -3072,6 +3093,18 @@ static int solve_window_impl(tbk_wfs* w, tbk_model* m, const double* start_k, co
             }
             G.gap_part = w->gap_part_dev;
             w->gap_part_n = G.ntiles;       // tbk_wfs_solve_grid_result reduces these instead of the shards
+            // a flux total left pending on this array (tbk_berry_flux_async) rides along: one workgroup more, behind the tiles'
+            // (grid_carried_flux_sum).  From here on the total has no completion word of its own: tbk_berry_flux_result waits for
+            // the stream.
+            if (w->flux_pend_n > 0 && w->flux_pend_nslices == 1) {
+                G.red_n = w->flux_pend_n;
+                G.red_partial = w->flux_partial_dev;
+                G.red_total = w->flux_totals_dev;
+                blocks += 1u;
+                lds = std::max(lds, (size_t)16 * sizeof(double));
+                w->flux_pend_n = 0;
+                w->flux_pend_nslices = 0;
+            }
 #define TBK_ROWS(NN, PP) hipLaunchKernelGGL((k_grid_rows<NN, PP>), dim3(blocks), dim3(256), lds, ctx->stream, m->view, G)
             const int pm = m->view.pmax;
             // (ranges 0..4 along the last axis are compiled in; the generic-range instance costs 1.7 x at 4 states:

@@ -44,6 +44,10 @@ struct GridArgs {
     int tpr;                 // wave tiles per row
     int64_t ntiles;
     int reg_cells;           // k_solve_regd on a mesh: S(k) from the row's coefficient cells (reg_assemble_cells; TBK_REG_CELLS=0: the tiled sum)
+    int red_n;               // k_grid_rows: > 0 -- the launch has ONE workgroup more than its tiles need (the last one), which adds up the
+                             // red_n flux partials a berry_flux call left pending on this array and touches no tile (grid_carried_flux_sum)
+    const double* red_partial;   // [red_n]
+    double* red_total;           // [1]
 #ifdef TBK_DIAG
     int ablate;              // diagnostic build only (TBK_ABLATE_GRID): 1 = no stores, 2 = no eigen-solve, ...
 #endif
