@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """A fixed list of Kubo-formula calls (berry_curvature*, orbital_moment, orbital_magnetization_mesh, optical_conductivity_mesh,
-spin_berry_curvature, shift_current*, injection_current_mesh, quantum_geometric_tensor*) that reaches every routed form of DESIGN.md
-sections 11 to 13, 15, 17 and 20, every output saved to one .npz:
+spin_berry_curvature, spin_hall_conductivity_mesh, band_velocity, anomalous_transport_mesh, drude_weight_mesh, shift_current*,
+injection_current_mesh, quantum_geometric_tensor*) that reaches every routed form of DESIGN.md sections 11 to 13, 15 to 17 and 20,
+every output saved to one .npz:
 
     TBK_LIBRARY=<libtbk.so> python profiles/kubo_bits.py out.npz      run the calls with that library (a fresh process each)
     python profiles/kubo_bits.py --compare a.npz b.npz                compare two runs as uint64 views (NaN and infinity patterns too)
@@ -70,6 +71,11 @@ def main():
         out[name] = np.ascontiguousarray(np.asarray(a)).view(float)
 
 
+    def keep_all(name, arrays):
+        for i, a in enumerate(arrays):
+            keep("%s %d" % (name, i), a)
+
+
     rng = np.random.default_rng(2024)
     for name, (make, occ, mesh) in MODELS.items():
         m = make()
@@ -92,12 +98,22 @@ def main():
             keep(tag + "orb mesh occ", m.orbital_magnetization_mesh(mesh, occ=occ, dirs=dirs))
             keep(tag + "orb mesh fermi", m.orbital_magnetization_mesh(mesh, fermi_levels=few, dirs=dirs))
             keep(tag + "orb mesh kT", m.orbital_magnetization_mesh(mesh, fermi_levels=few, kT=0.05, dirs=dirs))
+            keep_all(tag + "transport", m.anomalous_transport_mesh(mesh, few, 0.05, dirs=dirs))
             if m._nspin == 2:
                 keep(tag + "spin curv list", m.spin_berry_curvature(k, dirs=dirs))
                 keep(tag + "spin curv list occ", m.spin_berry_curvature(k, spin=0, occ=occ, dirs=dirs))
+                keep(tag + "spin hall mesh", m.spin_hall_conductivity_mesh(mesh, dirs=dirs))
+                keep(tag + "spin hall mesh occ", m.spin_hall_conductivity_mesh(mesh, spin=0, occ=occ, dirs=dirs))
+                keep(tag + "spin hall mesh fermi", m.spin_hall_conductivity_mesh(mesh, dirs=dirs, fermi_levels=few))
+        keep(name + " velocity", m.band_velocity(k))
+        keep(name + " drude", m.drude_weight_mesh(mesh, few, 0.05))
         if name in ("haldane_n2", "kane_mele_n4", "silicon_n8"):
             keep(name + " curv mesh fermi5000", m.berry_curvature_mesh(mesh, fermi_levels=many))
             keep(name + " orb mesh fermi5000", m.orbital_magnetization_mesh(mesh, fermi_levels=many))
+            # the thermal scan over twenty tiles of levels
+            keep(name + " orb mesh kT5000", m.orbital_magnetization_mesh(mesh, fermi_levels=many, kT=0.05))
+            keep_all(name + " transport kT5000", m.anomalous_transport_mesh(mesh, many, 0.05))
+            keep(name + " drude kT5000", m.drude_weight_mesh(mesh, many, 0.05))
         omega = np.linspace(-1.0, 0.5 * (hi - lo), 23)
         mu = 0.5 * (lo + hi) + 0.013
         for kT in (0.0, 0.05):
@@ -117,6 +133,17 @@ def main():
         keep(name + " qgt mesh", m.quantum_geometric_tensor_mesh(mesh))
         keep(name + " qgt mesh occ", m.quantum_geometric_tensor_mesh(mesh, occ=occ))
         print(name, len(out), flush=True)
+
+    # one dimension: the whole-mesh forms alone (sections 16 and 20)
+    m = hp.chain3(tb.tb_model, -1.3, 0.4, 0.7)
+    k = rng.random((70, 1))
+    keep("chain3 qgt list", m.quantum_geometric_tensor(k))
+    keep("chain3 qgt list occ", m.quantum_geometric_tensor(k, occ=[0]))
+    keep("chain3 qgt mesh", m.quantum_geometric_tensor_mesh([500]))
+    keep("chain3 qgt mesh occ", m.quantum_geometric_tensor_mesh([500], occ=[0]))
+    keep("chain3 drude", m.drude_weight_mesh([500], np.linspace(-3.0, 3.0, 37), 0.05))
+    keep("chain3 velocity", m.band_velocity(k))
+    print("chain3", len(out), flush=True)
 
     np.savez(sys.argv[1], **out)
     print("saved %d arrays to %s (library %s)" % (len(out), sys.argv[1], os.environ.get("TBK_LIBRARY", "default")))

@@ -2,7 +2,7 @@
 """Per-call wall time and per-kernel times (tbk_prof_*) of orbital_magnetization_mesh beside
 berry_curvature_mesh's Fermi scan on the same mesh: Haldane 2048^2 (n = 2), Kane-Mele 1024^2 (n = 4), cubic16 65^3 (n = 16)
 and w90 silicon 48^3 (n = 8), each with 512 levels spread over the spectrum.  Per model: the curvature scan, the T = 0 scan,
-the kT = 0.05 scan and the band set.  Prints one JSON line per call, with k_orb_kt's time per (record, level) in ps."""
+the kT = 0.05 scan and the band set.  Prints one JSON line per call, with the thermal scan's (orb_kt) time per (record, level) in ps."""
 import contextlib
 import io
 import json

@@ -15,8 +15,9 @@
 // Spin form (section 15): Omega^s_n with the first velocity replaced by the spin current J^{s,a} = (Sigma_s d_a H + d_a H Sigma_s) / 2,
 // Sigma_s = 1_orb (x) s.sigma, for spinful models.  The policy SpinQ (CurvQ's sums, kSpin) takes the same kernels at every n -- the n = 2
 // closed form is for two velocities and is not used; the mesh reductions are those of the charge form.
-// Reductions are fixed-shape trees (per-workgroup partials in a grid-stride order that depends on the mesh shape alone, then one
-// workgroup per output): two calls on the same input give the same bits.  No floating-point atomics anywhere.
+// Reductions are tbk_kubo.h's (k_kubo_plane, k_kubo_fermi, k_kubo_rows over this unit's sources): fixed-shape trees (per-workgroup
+// partials in a grid-stride order that depends on the mesh shape alone, then one workgroup per output): two calls on the same input
+// give the same bits.  No floating-point atomics anywhere.
 #include <math.h>
 #include <string.h>
 #include "tbk_kubo.h"
@@ -76,7 +77,8 @@ __global__ __launch_bounds__(256) void k_curv2_list(const ModelView mv, const in
 }
 
 // ---------------------------------------------------------------- mesh planes (PlaneArgs, plane_point: tbk_dham.h)
-// sources of per-point values for the reductions.  band(): Omega_ch with the degeneracy rule and E_ch; man(): the manifold value
+// sources of per-point values for the reductions.  band(): Omega_ch with the degeneracy rule and E_ch (k_kubo_fermi); plane(): that
+// Omega_ch, or the manifold value of a band set (k_kubo_plane)
 struct Curv2Src : Kubo2Src {
     __device__ __forceinline__ void band(const PlaneArgs& P, const int (&ii)[3], int64_t, const int ch, double& e, double (&w)[1]) const {
         const Curv2 c = at(P, ii);
@@ -84,9 +86,13 @@ struct Curv2Src : Kubo2Src {
         const double o = c.degenerate ? 0.0 : c.om;
         w[0] = ch ? -o : o;
     }
-    __device__ __forceinline__ double man(const PlaneArgs& P, const int (&ii)[3], int64_t) const {
+    __device__ __forceinline__ void plane(const PlaneArgs& P, const int s, const int64_t p, const int ch, double (&w)[1]) const {
+        int ii[3];
+        const int64_t idx = plane_point(P, s, p, ii);
+        double e;
+        if (occ_sign == 0) return band(P, ii, idx, ch, e, w);
         const Curv2 c = at(P, ii);
-        return occ_sign > 0 ? c.om : -c.om;
+        w[0] = occ_sign > 0 ? c.om : -c.om;
     }
 };
 struct ArraySrc {
@@ -97,30 +103,11 @@ struct ArraySrc {
         e = ev ? ev[(int64_t)ch * P.npts + idx] : 0.0;
         w[0] = om[(int64_t)ch * P.npts + idx];
     }
-    __device__ __forceinline__ double man(const PlaneArgs&, const int (&)[3], const int64_t idx) const { return om[idx]; }
-};
-
-// plane sums: row = s * nch + ch (blockIdx.y and every gridDim.y after it), blockIdx.x = g of gx; part[row][gx]
-template <class Src>
-__global__ __launch_bounds__(256) void k_curv_plane(const Src src, const PlaneArgs P, const int manifold, const int nch,
-                                                    const int64_t nrows, double* __restrict__ part) {
-    __shared__ double red[4];
-    for (int64_t row = blockIdx.y; row < nrows; row += gridDim.y) {   // (rows beyond the grid's y limit: the next pass)
-        const int s = (int)(row / nch), ch = (int)(row - (int64_t)s * nch);
-        double acc = 0.0;
-        for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < P.nplane; p += (int64_t)gridDim.x * 256) {
-            int ii[3];
-            const int64_t idx = plane_point(P, s, p, ii);
-            double e, w[1];
-            if (manifold) w[0] = src.man(P, ii, idx);
-            else src.band(P, ii, idx, ch, e, w);
-            acc += w[0];
-        }
-        const double t = block_sum(acc, red);
-        if (threadIdx.x == 0) part[row * gridDim.x + blockIdx.x] = t;
-        __syncthreads();                                              // (red is reused by the next row)
+    __device__ __forceinline__ void plane(const PlaneArgs& P, const int s, const int64_t p, const int ch, double (&w)[1]) const {
+        int ii[3];
+        w[0] = om[(int64_t)ch * P.npts + plane_point(P, s, p, ii)];   // (a band set: one channel)
     }
-}
+};
 
 // ---------------------------------------------------------------- n != 2: what a (point, band) lane of tbk_kubo.h's contraction keeps
 // (CurvQ, the policy of the charge curvature, is in tbk_kubo.h: tbk_transport.hip sums with it too)
@@ -161,12 +148,13 @@ static int gen_dham(const char* fn, tbk_model* m, const double* k, int64_t nk, i
     TBK_HIP(hipSetDevice(ctx->device));
     const int n = m->nsta;
     const size_t kb = (size_t)nk * m->dim_k * sizeof(double), hb = (size_t)nk * n * n * sizeof(cd);
-    void* base = nullptr;
-    int rc = tbk_ctx_scratch(ctx, 256 + al256(kb) + (spin ? 2 : 1) * al256(hb), &base);
+    double* k_dev;
+    cd *h_dev, *j_dev;
+    KuboCarve ws;
+    ws.add(k_dev, kb), ws.add(h_dev, hb), ws.add(j_dev, spin ? hb : 0);
+    int rc = kubo_carve(ctx, ws);
     if (rc) return rc;
-    double* k_dev = (double*)((unsigned char*)base + 256);
-    cd* h_dev = (cd*)((unsigned char*)k_dev + al256(kb));
-    cd* j_dev = spin ? (cd*)((unsigned char*)h_dev + al256(hb)) : h_dev;
+    if (!spin) j_dev = h_dev;
     TBK_HIP(hipMemcpyAsync(k_dev, k, kb, hipMemcpyHostToDevice, ctx->stream));
     TBK_HIP(hipMemsetAsync(h_dev, 0, hb, ctx->stream));
     if (m->view.nnz > 0) {
@@ -214,15 +202,13 @@ static int curv_list(const char* fn, tbk_model* m, const double* k, int64_t nk, 
     }
     tbk_ctx* ctx = m->ctx;
     TBK_HIP(hipSetDevice(ctx->device));
-    const size_t kb = al256((size_t)nk * dk * sizeof(double)), ob = al256((size_t)nout * sizeof(double));
     const bool general = n != 2 || spin;   // (the n = 2 closed form is for two velocities)
     KuboChunks cw = general ? kubo_contract_chunks(n, dk, nk, manifold, CurvQ::NSET) : KuboChunks();
-    void* base = nullptr;
-    rc = tbk_ctx_scratch(ctx, 256 + kb + ob + cw.bytes(), &base);
+    double *k_dev, *o_dev;
+    KuboCarve ws;
+    ws.add(k_dev, (size_t)nk * dk * sizeof(double)), ws.add(o_dev, (size_t)nout * sizeof(double)), ws.add(cw.base, cw.bytes());
+    rc = kubo_carve(ctx, ws);
     if (rc) return rc;
-    unsigned char* p = (unsigned char*)base + 256;
-    double* k_dev = (double*)p;
-    double* o_dev = (double*)(p + kb);
     TBK_HIP(hipMemcpyAsync(k_dev, k, (size_t)nk * dk * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     if (!general) {
         ProfScope ps(ctx, "curv2_list");
@@ -231,7 +217,6 @@ static int curv_list(const char* fn, tbk_model* m, const double* k, int64_t nk, 
                            sign, o_dev);
         TBK_HIP(hipGetLastError());
     } else {
-        cw.base = p + kb + ob;
         if (spin) rc = kubo_contract<SpinQ>(m, k_dev, nullptr, nk, dir0, dir1, mask, cw, SpinQ::Out{{o_dev, nullptr}, sv});
         else rc = kubo_contract<CurvQ>(m, k_dev, nullptr, nk, dir0, dir1, mask, cw, CurvQ::Out{o_dev, nullptr});
         if (rc) return rc;
@@ -263,10 +248,11 @@ static int curv_mesh(const char* fn, tbk_model* m, const int32_t* mesh, int dir0
     }
     TBK_REQUIRE(mesh && out, TBK_EINVAL, "%s: null argument", fn);
     TBK_REQUIRE(m->dim_k == 2 || m->dim_k == 3, TBK_EINVAL, "%s: dim_k=%d (meshes of 2 or 3 dimensions)", fn, m->dim_k);
-    TBK_REQUIRE(nmu >= 0 && nmu <= 8192 && (nmu == 0 || mu), TBK_EINVAL, "%s: nmu=%d (0..8192 levels)", fn, nmu);
+    rc = kubo_levels_check(fn, nmu, mu, 0);
+    if (rc) return rc;
     TBK_REQUIRE(!(nmu > 0 && occ), TBK_EINVAL, "%s: a band set and a Fermi scan are exclusive", fn);
-    for (int j = 0; j < nmu; ++j)
-        TBK_REQUIRE(std::isfinite(mu[j]), TBK_EINVAL, "%s: Fermi level %d is not finite", fn, j);
+    rc = kubo_levels_finite(fn, nmu, mu);
+    if (rc) return rc;
     const int n = m->nsta, dk = m->dim_k;
     PlaneArgs P;
     rc = kubo_planes(fn, mesh, dir0, dir1, dk, P);
@@ -291,37 +277,24 @@ static int curv_mesh(const char* fn, tbk_model* m, const int32_t* mesh, int dir0
     const int nplane_ch = (!fermi && !manifold && !general) ? 1 : nch;   // n = 2 per band: band 1 is -band 0, bit for bit
     const int gx = fermi ? kubo_fermi_gx(P, n, nmu, 1) : kubo_plane_gx(P);
     const int64_t nrows = (int64_t)nslice * nplane_ch;
-    const size_t partb = al256((size_t)nrows * gx * sizeof(double)), rowb = al256((size_t)nrows * sizeof(double));
-    const size_t mub = al256((size_t)std::max(nmu, 1) * sizeof(double));
-    const size_t omb = general ? al256((size_t)(manifold ? 1 : n) * npts * sizeof(double)) : 0;
-    const size_t evb = general && fermi ? al256((size_t)n * npts * sizeof(double)) : 0;
     KuboChunks cw = general ? kubo_contract_chunks(n, dk, npts, manifold, CurvQ::NSET) : KuboChunks();
-    void* base = nullptr;
-    rc = tbk_ctx_scratch(ctx, 256 + partb + rowb + mub + omb + evb + cw.bytes(), &base);
+    double *part, *rows, *mu_dev, *om_dev, *ev_dev;
+    KuboCarve ws;
+    ws.add(part, (size_t)nrows * gx * sizeof(double)), ws.add(rows, (size_t)nrows * sizeof(double));
+    ws.add(mu_dev, (size_t)std::max(nmu, 1) * sizeof(double));
+    ws.add(om_dev, general ? (size_t)(manifold ? 1 : n) * npts * sizeof(double) : 0);
+    ws.add(ev_dev, general && fermi ? (size_t)n * npts * sizeof(double) : 0);
+    ws.add(cw.base, cw.bytes());
+    rc = kubo_carve(ctx, ws);
     if (rc) return rc;
-    unsigned char* p = (unsigned char*)base + 256;
-    double* part = (double*)p;
-    double* rows = (double*)(p + partb);
-    double* mu_dev = (double*)(p + partb + rowb);
-    double* om_dev = (double*)(p + partb + rowb + mub);
-    double* ev_dev = evb ? (double*)(p + partb + rowb + mub + omb) : nullptr;
-    cw.base = p + partb + rowb + mub + omb + evb;
     if (fermi) TBK_HIP(hipMemcpyAsync(mu_dev, mus.data(), (size_t)nmu * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     auto reduce = [&](auto src) -> int {
         if (fermi) {
             ProfScope ps(ctx, general ? "curv_fermi" : "curv2_fermi");
-            int rc = kubo_fermi_launch<1>(ctx, src, P, n, mu_dev, nmu, gx, part);
-            if (rc) return rc;
-        } else {
-            ProfScope ps(ctx, general ? "curv_plane" : "curv2_plane");
-            hipLaunchKernelGGL(k_curv_plane<decltype(src)>, dim3(gx, (unsigned)std::min<int64_t>(nrows, 65535)), dim3(256), 0, ctx->stream, src,
-                               P, manifold ? 1 : 0, nplane_ch, nrows, part);
-            TBK_HIP(hipGetLastError());
+            return kubo_fermi_launch<1>(ctx, src, P, n, mu_dev, nmu, gx, part);
         }
-        ProfScope ps(ctx, "curv_rows");
-        hipLaunchKernelGGL(k_kubo_rows, dim3((unsigned)nrows), dim3(256), 0, ctx->stream, (const double*)part, gx, rows);
-        TBK_HIP(hipGetLastError());
-        return TBK_OK;
+        ProfScope ps(ctx, general ? "curv_plane" : "curv2_plane");
+        return kubo_plane_launch<1>(ctx, src, P, nplane_ch, nrows, gx, part);
     };
     if (general) {
         if (spin) rc = kubo_contract<SpinQ>(m, nullptr, mesh, npts, dir0, dir1, mask, cw, SpinQ::Out{{om_dev, ev_dev}, sv});
@@ -332,9 +305,9 @@ static int curv_mesh(const char* fn, tbk_model* m, const int32_t* mesh, int dir0
         rc = reduce(Curv2Src{{m->view, dir0, dir1, manifold ? (mask[0] ? 1 : -1) : 0}});
     }
     if (rc) return rc;
-    std::vector<double> sums((size_t)nrows);
-    TBK_HIP(hipMemcpyAsync(sums.data(), rows, (size_t)nrows * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    TBK_HIP(hipStreamSynchronize(ctx->stream));
+    std::vector<double> sums;
+    rc = kubo_rows_to_host(ctx, "curv_rows", part, gx, nrows, rows, sums);
+    if (rc) return rc;
     const double inv = 1.0 / (double)P.nplane;
     // out[ch][s]: the Python shapes (nch,) for a 2-D mesh, (nch, nslice) for a 3-D one
     for (int s = 0; s < nslice; ++s) {

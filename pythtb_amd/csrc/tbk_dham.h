@@ -180,6 +180,13 @@ __device__ __forceinline__ int64_t plane_point(const PlaneArgs& P, const int s, 
     if (P.dc >= 0) ii[P.dc] = s;
     return ((int64_t)ii[0] * P.N[1] + ii[1]) * P.N[2] + ii[2];
 }
+// the inverse of that index: point idx of k_uniform_mesh(N) is (ii[0], ii[1], ii[2])
+__device__ __forceinline__ void mesh_point(const int (&N)[3], const int64_t idx, int (&ii)[3]) {
+    const int64_t i01 = idx / N[2];
+    ii[2] = (int)(idx - i01 * N[2]);
+    ii[0] = (int)(i01 / N[1]);
+    ii[1] = (int)(i01 - (int64_t)ii[0] * N[1]);
+}
 
 // sum over the 256 threads of a workgroup in a fixed order (shuffle tree in each wavefront, then the four in order); thread 0 has it
 __device__ __forceinline__ double block_sum(double v, double* red) {

@@ -2,15 +2,18 @@
 //   device   the rotation of d H into the eigenbasis for several points in LDS (kubo_lds_load, kubo_lds_dut, kubo_lds_ut,
 //            kubo_lds_rotate: every kernel up to 32 states here, in tbk_qgt.hip and in tbk_pairs.h); the contraction of the solver's
 //            eigenvectors with d_a H, d_b H (k_kubo_lds up to 32 states; k_kubo_wsp, k_kubo_contract and k_kubo_occ_sum from 33),
-//            templates over a policy Q that says what a (point, band) lane keeps of a pair; the n = 2 mesh source; the T = 0 Fermi
-//            scan k_kubo_fermi and the row sum k_kubo_rows
-//   host     the argument checks, the mesh planes, the sort of the Fermi levels and the chunk pipeline (KuboChunks, kubo_for_chunks)
-// tbk_curv.hip and tbk_orbmag.hip use all of it, tbk_qgt.hip and tbk_pairs.h (tbk_optics.hip, tbk_shift.hip) the rotation and the
-// chunk pipeline.  The library is built without relocatable device code, so every kernel here is a template or static: each unit
+//            templates over a policy Q that says what a (point, band) lane keeps of a pair; the n = 2 mesh source; the mesh
+//            reductions behind a chunk's per-point values: the plane sum k_kubo_plane over a source, the T = 0 Fermi scan
+//            k_kubo_fermi, the thermal scan k_kubo_thermal over a policy, and the row sum k_kubo_rows
+//   host     the argument checks (bands, Fermi levels, kT), the mesh planes, the sort of the Fermi levels, the tail
+//            kubo_rows_to_host, the workspace carver KuboCarve and the chunk pipeline (KuboChunks, kubo_for_chunks)
+// tbk_curv.hip, tbk_orbmag.hip and tbk_transport.hip use all of it, tbk_qgt.hip everything but the contraction and the scans, and
+// tbk_pairs.h (tbk_optics.hip, tbk_shift.hip) the rotation and the chunk pipeline.  The library is built without relocatable device code, so every kernel here is a template or static: each unit
 // that launches one holds its own definition and host stub.
 #pragma once
 #include <algorithm>
 #include <cmath>
+#include <cstring>
 #include <numeric>
 #include <type_traits>
 #include <vector>
@@ -111,6 +114,112 @@ static __global__ __launch_bounds__(256) void k_kubo_rows(const double* __restri
     for (int g = threadIdx.x; g < gx; g += 256) acc += p[g];
     const double t = block_sum(acc, red);
     if (threadIdx.x == 0) out[blockIdx.x] = t;
+}
+
+static int kubo_rows_launch(tbk_ctx* ctx, const double* part, int gx, int64_t nrows, double* rows) {
+    hipLaunchKernelGGL(k_kubo_rows, dim3((unsigned)nrows), dim3(256), 0, ctx->stream, part, gx, rows);
+    TBK_HIP(hipGetLastError());
+    return TBK_OK;
+}
+// sums = the nrows doubles at rows, on the host
+static int kubo_to_host(tbk_ctx* ctx, const double* rows, int64_t nrows, std::vector<double>& sums) {
+    sums.resize((size_t)nrows);
+    TBK_HIP(hipMemcpyAsync(sums.data(), rows, (size_t)nrows * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    TBK_HIP(hipStreamSynchronize(ctx->stream));
+    return TBK_OK;
+}
+// the tail of every mesh call: rows[r] = sum_g part[r][g] under the caller's label, then sums = rows on the host
+static int kubo_rows_to_host(tbk_ctx* ctx, const char* label, const double* part, int gx, int64_t nrows, double* rows,
+                             std::vector<double>& sums) {
+    {
+        ProfScope ps(ctx, label);
+        int rc = kubo_rows_launch(ctx, part, gx, nrows, rows);
+        if (rc) return rc;
+    }
+    return kubo_to_host(ctx, rows, nrows, sums);
+}
+
+// Plane sums: src.plane(P, s, p, ch, w) gives the NQ values of channel ch at plane point p of slice s; row = s * nch + ch
+// (blockIdx.y and every gridDim.y after it), blockIdx.x = g of gx (points g 256 + t, then every gx 256 after it), one block_sum
+// per quantity.  part[row][NQ][gx]
+template <class Src, int NQ>
+__global__ __launch_bounds__(256) void k_kubo_plane(const Src src, const PlaneArgs P, const int nch, const int64_t nrows,
+                                                    double* __restrict__ part) {
+    __shared__ double red[NQ][4];
+    for (int64_t row = blockIdx.y; row < nrows; row += gridDim.y) {   // (rows beyond the grid's y limit: the next pass)
+        const int s = (int)(row / nch), ch = (int)(row - (int64_t)s * nch);
+        double acc[NQ];
+#pragma unroll
+        for (int c = 0; c < NQ; ++c) acc[c] = 0.0;
+        for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < P.nplane; p += (int64_t)gridDim.x * 256) {
+            double w[NQ];
+            src.plane(P, s, p, ch, w);
+#pragma unroll
+            for (int c = 0; c < NQ; ++c) acc[c] += w[c];
+        }
+#pragma unroll
+        for (int c = 0; c < NQ; ++c) {
+            const double t = block_sum(acc[c], red[c]);
+            if (threadIdx.x == 0) part[(row * NQ + c) * gridDim.x + blockIdx.x] = t;
+        }
+        __syncthreads();                                              // (red is reused by the next row)
+    }
+}
+template <int NQ, class Src>
+static int kubo_plane_launch(tbk_ctx* ctx, const Src& src, const PlaneArgs& P, int nch, int64_t nrows, int gx, double* part) {
+    hipLaunchKernelGGL((k_kubo_plane<Src, NQ>), dim3(gx, (unsigned)std::min<int64_t>(nrows, 65535)), dim3(256), 0, ctx->stream, src, P,
+                       nch, nrows, part);
+    TBK_HIP(hipGetLastError());
+    return TBK_OK;
+}
+
+// Thermal scan (kT > 0) over the per-band records rec[1 + NR][nb][npts]: E, then the policy's NR records.  Workgroup (tile of
+// kThermalTile levels, k-group g, slice s): lane t takes level j = tile + t and walks the records of the plane points
+// [g nplane / G, (g + 1) nplane / G) of slice s (Pol::kWhole: the plane is the whole mesh in k_uniform_mesh order), every band of
+// a point in order; a record's address depends on the workgroup and the loop alone, so it is read as a wave-uniform value.  The
+// policy's add(e, r, u, kT, ikT, acc) is the arithmetic of one (record, level) on its NQ sums.  part[s][j][NQ][G]
+static const int kThermalTile = 256;                     // levels per workgroup (one per lane)
+template <class Pol>
+__global__ __launch_bounds__(256) void k_kubo_thermal(const PlaneArgs P, const int nb, const double* __restrict__ rec,
+                                                      const double* __restrict__ mu, const int nmu, const double kT, const int G,
+                                                      double* __restrict__ part) {
+    constexpr int NR = Pol::NR, NQ = Pol::NQ;
+    const int base = blockIdx.x * kThermalTile;
+    if (base + (int)(threadIdx.x & ~63u) >= nmu) return;            // a wavefront without a level (uniform)
+    const int j = base + threadIdx.x, g = blockIdx.y;
+    const double u = j < nmu ? mu[j] : 0.0;
+    const double ikT = 1.0 / kT;
+    const int64_t stride = (int64_t)nb * P.npts;
+    const int64_t p0 = (int64_t)g * P.nplane / G, p1 = (int64_t)(g + 1) * P.nplane / G;
+    for (int s = blockIdx.z; s < P.nslice; s += gridDim.z) {
+        double acc[NQ];
+#pragma unroll
+        for (int c = 0; c < NQ; ++c) acc[c] = 0.0;
+        for (int64_t p = p0; p < p1; ++p) {
+            int ii[3];
+            const int64_t idx = Pol::kWhole ? p : plane_point(P, s, p, ii);
+            for (int b = 0; b < nb; ++b) {
+                const int64_t i = (int64_t)b * P.npts + idx;
+                const double e = rec[i];
+                double r[NR];
+#pragma unroll
+                for (int c = 0; c < NR; ++c) r[c] = rec[(1 + c) * stride + i];
+                Pol::add(e, r, u, kT, ikT, acc);
+            }
+        }
+        if (j < nmu)
+#pragma unroll
+            for (int c = 0; c < NQ; ++c) part[(((int64_t)s * nmu + j) * NQ + c) * G + g] = acc[c];
+    }
+}
+template <class Pol>
+static int kubo_thermal_launch(tbk_ctx* ctx, const PlaneArgs& P, int n, const double* rec, const double* mu_dev, int nmu, double kT,
+                               int G, double* part) {
+    const unsigned ntile = (unsigned)((nmu + kThermalTile - 1) / kThermalTile);
+    hipLaunchKernelGGL(k_kubo_thermal<Pol>, dim3(ntile, (unsigned)G, (unsigned)std::min(P.nslice, 65535)), dim3(256), 0, ctx->stream, P, n,
+                       rec, mu_dev, nmu, kT, G, part);
+    TBK_HIP(hipGetLastError());
+    return TBK_OK;
 }
 
 // ---------------------------------------------------------------- n != 2: contraction of the solver's eigenvectors
@@ -429,12 +538,7 @@ __global__ __launch_bounds__(256) void k_kubo_occ_sum(const double* __restrict__
 
 // ---------------------------------------------------------------- host side: checks and mesh set-up
 // the argument checks of a (dir0, dir1) quantity `what`; mask (n entries) = 1 for the bands of occ, empty without occ
-static int kubo_check(const char* fn, const char* what, tbk_model* m, int dir0, int dir1, const int32_t* occ, int nocc,
-                      std::vector<int>& mask) {
-    TBK_REQUIRE(m, TBK_EINVAL, "%s: null model", fn);
-    TBK_REQUIRE(m->dim_k >= 2, TBK_EINVAL, "%s: the %s needs dim_k >= 2 (the model has %d)", fn, what, m->dim_k);
-    TBK_REQUIRE(dir0 >= 0 && dir0 < m->dim_k && dir1 >= 0 && dir1 < m->dim_k && dir0 != dir1, TBK_EINVAL,
-                "%s: dirs (%d, %d) must be two different axes in [0, %d)", fn, dir0, dir1, m->dim_k);
+static int kubo_occ_mask(const char* fn, tbk_model* m, const int32_t* occ, int nocc, std::vector<int>& mask) {
     const int n = m->nsta;
     mask.clear();
     if (occ) {
@@ -450,9 +554,32 @@ static int kubo_check(const char* fn, const char* what, tbk_model* m, int dir0, 
     }
     return TBK_OK;
 }
+static int kubo_check(const char* fn, const char* what, tbk_model* m, int dir0, int dir1, const int32_t* occ, int nocc,
+                      std::vector<int>& mask) {
+    TBK_REQUIRE(m, TBK_EINVAL, "%s: null model", fn);
+    TBK_REQUIRE(m->dim_k >= 2, TBK_EINVAL, "%s: the %s needs dim_k >= 2 (the model has %d)", fn, what, m->dim_k);
+    TBK_REQUIRE(dir0 >= 0 && dir0 < m->dim_k && dir1 >= 0 && dir1 < m->dim_k && dir0 != dir1, TBK_EINVAL,
+                "%s: dirs (%d, %d) must be two different axes in [0, %d)", fn, dir0, dir1, m->dim_k);
+    return kubo_occ_mask(fn, m, occ, nocc, mask);
+}
+// the checks of the Fermi levels of a mesh call, in the order its other checks fall between them: their number (min_levels..8192),
+// the temperature (positive: kT > 0, else kT >= 0), every level finite
+static int kubo_levels_check(const char* fn, int nmu, const double* mu, int min_levels) {
+    TBK_REQUIRE(nmu >= min_levels && nmu <= 8192 && (nmu == 0 || mu), TBK_EINVAL, "%s: nmu=%d (%d..8192 levels)", fn, nmu, min_levels);
+    return TBK_OK;
+}
+static int kubo_kt_check(const char* fn, double kT, bool positive) {
+    TBK_REQUIRE(std::isfinite(kT) && (positive ? kT > 0.0 : kT >= 0.0), TBK_EINVAL, "%s: kT must be finite and %s 0", fn,
+                positive ? ">" : ">=");
+    return TBK_OK;
+}
+static int kubo_levels_finite(const char* fn, int nmu, const double* mu) {
+    for (int j = 0; j < nmu; ++j) TBK_REQUIRE(std::isfinite(mu[j]), TBK_EINVAL, "%s: Fermi level %d is not finite", fn, j);
+    return TBK_OK;
+}
 
-// the (dir0, dir1) planes of a mesh of dim_k = 2 or 3 dimensions (checked by the caller)
-static int kubo_planes(const char* fn, const int32_t* mesh, int dir0, int dir1, int dk, PlaneArgs& P) {
+// a mesh of dk = 1, 2 or 3 dimensions as one "plane": every point, in k_uniform_mesh order
+static int kubo_whole_mesh(const char* fn, const int32_t* mesh, int dk, PlaneArgs& P) {
     P = PlaneArgs{};
     P.npts = 1;
     for (int d = 0; d < 3; ++d) {
@@ -460,6 +587,17 @@ static int kubo_planes(const char* fn, const int32_t* mesh, int dir0, int dir1, 
         P.N[d] = d < dk ? mesh[d] : 1;
         P.npts *= P.N[d];
     }
+    P.da = 0;
+    P.db = dk > 1 ? 1 : 0;
+    P.dc = -1;
+    P.nplane = P.npts;
+    P.nslice = 1;
+    return TBK_OK;
+}
+// the (dir0, dir1) planes of a mesh of dim_k = 2 or 3 dimensions (checked by the caller)
+static int kubo_planes(const char* fn, const int32_t* mesh, int dir0, int dir1, int dk, PlaneArgs& P) {
+    int rc = kubo_whole_mesh(fn, mesh, dk, P);
+    if (rc) return rc;
     P.da = dir0;
     P.db = dir1;
     P.dc = dk == 3 ? 3 - dir0 - dir1 : -1;
@@ -477,7 +615,8 @@ static void kubo_levels(const double* mu, int nmu, bool sorted, std::vector<int>
     for (int j = 0; j < nmu; ++j) mus[j] = mu[ord[j]];
 }
 
-// workgroups per row of the plane sums and per (slice, level, quantity) of the Fermi scan: functions of the mesh shape, n, nmu, nq alone
+// workgroups per row of the plane sums and per (slice, level, quantity) of the Fermi scan, k-groups of the thermal scan: functions of
+// the mesh shape, n, nmu, nq alone
 static inline int kubo_plane_gx(const PlaneArgs& P) {
     return (int)std::max<int64_t>(1, std::min<int64_t>((P.nplane + 2047) / 2048, 1024));
 }
@@ -485,6 +624,45 @@ static inline int kubo_fermi_gx(const PlaneArgs& P, int n, int nmu, int nq) {
     const int64_t tiles = (P.nplane * n + 255) / 256;
     const int64_t cap = std::max<int64_t>(1, ((int64_t)1 << 22) / ((int64_t)P.nslice * nmu * nq));
     return (int)std::max<int64_t>(1, std::min<int64_t>({(tiles + 7) / 8, 512, cap}));
+}
+static inline int kubo_thermal_groups(const PlaneArgs& P, int n, int nmu, int nq) {
+    const int64_t cap = std::max<int64_t>(1, ((int64_t)1 << 22) / ((int64_t)P.nslice * nmu * nq));
+    return (int)std::max<int64_t>(1, std::min<int64_t>({(P.nplane * n + 1023) / 1024, 1024, cap}));
+}
+
+// ---------------------------------------------------------------- host side: a call's workspace
+// The device buffers of one call, carved from the context's scratch block: add(p, bytes) registers the buffer of pointer p once
+// (0 bytes: not wanted), kubo_carve() asks for the total (256 leading bytes, every buffer at a multiple of 256) and place() sets
+// the pointers (null for a buffer not wanted).  No HIP types: check/kubo_carve_check.cpp drives the arithmetic on the host alone.
+struct KuboCarve {
+    static const int kMax = 8;
+    void* ptr[kMax];                       // where each buffer's pointer lives
+    size_t off[kMax], total = 256;
+    int cnt = 0;
+    bool full = false;                     // a buffer beyond kMax was registered: kubo_carve fails
+    template <class T>
+    void add(T*& p, size_t bytes) {
+        if (cnt == kMax) {
+            full = true;
+            return;
+        }
+        ptr[cnt] = &p;
+        off[cnt++] = bytes ? total : 0;
+        total += al256(bytes);
+    }
+    void place(void* base) const {
+        for (int i = 0; i < cnt; ++i) {
+            void* p = off[i] ? (unsigned char*)base + off[i] : nullptr;
+            memcpy(ptr[i], &p, sizeof p);
+        }
+    }
+};
+static int kubo_carve(tbk_ctx* ctx, const KuboCarve& c) {
+    TBK_REQUIRE(!c.full, TBK_EINVAL, "kubo_carve: more than %d buffers", KuboCarve::kMax);
+    void* base = nullptr;
+    int rc = tbk_ctx_scratch(ctx, c.total, &base);
+    if (!rc) c.place(base);
+    return rc;
 }
 
 // ---------------------------------------------------------------- host side: the chunk pipeline

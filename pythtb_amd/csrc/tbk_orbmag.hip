@@ -15,15 +15,13 @@
 //             plane and T = 0 reductions directly; for kT > 0 it writes the (E, m, Omega) records.
 //   n != 2    the chunk pipeline and the contraction kernels of tbk_kubo.h with the policy OrbQ: two accumulators per (point, band)
 //             lane, three shares for a band set.
-// Reductions: k_orb_plane (the three band-set sums in one pass), k_kubo_fermi with two quantities per item, k_orb_kt (levels across
-// lanes, records read as wave-uniform values, sums in registers), k_kubo_rows.  Every partition depends on the mesh, n and the
+// Reductions, all of tbk_kubo.h: k_kubo_plane with three quantities (the band-set sums in one pass), k_kubo_fermi with two per item,
+// k_kubo_thermal with the policy OrbThermal (levels across lanes, records read as wave-uniform values, sums in registers),
+// k_kubo_rows.  This unit owns the sources, OrbThermal's arithmetic and OrbQ.  Every partition depends on the mesh, n and the
 // number of levels alone, and nothing uses atomics: two calls give the same bits.
 #include <math.h>
 #include <string.h>
 #include "tbk_kubo.h"
-
-static const int kOrbKtTile = 256;                       // levels per workgroup of k_orb_kt (one per lane)
-static const int kOrbKtGroupsMax = 1024;                 // k-groups of k_orb_kt at most
 
 // ---------------------------------------------------------------- n = 2: closed form in registers
 // list form: out[2][nk] = m (occ_sign == 0), or out[nk] = LC + IC of the band set {0} (occ_sign = +1) or {1} (-1)
@@ -44,8 +42,9 @@ __global__ __launch_bounds__(256) void k_orb2_list(const ModelView mv, const int
     }
 }
 
-// Sources of per-point values for the reductions.  band(): w = (Omega_ch (degeneracy rule), m_ch - E_ch Omega_ch) and E_ch;
-// set(): (LC, IC, Omega_occ) of the band set.
+// Sources of per-point values for the reductions.  band(): w = (Omega_ch (degeneracy rule), m_ch - E_ch Omega_ch) and E_ch
+// (k_kubo_fermi); plane(): (LC, IC, Omega_occ) of the band set (k_kubo_plane; each sum in the order of the curvature's plane
+// sums, and the Omega sum is its manifold sum, bit for bit).
 struct Orb2Src : Kubo2Src {
     __device__ __forceinline__ void band(const PlaneArgs& P, const int (&ii)[3], int64_t, const int ch, double& e, double (&w)[2]) const {
         const Curv2 c = at(P, ii);
@@ -54,12 +53,14 @@ struct Orb2Src : Kubo2Src {
         w[0] = ch ? -o : o;
         w[1] = -0.5 * (c.e0 + c.e1) * w[0];   // sum_m P_nm (E_n + E_m) / Delta^2
     }
-    __device__ __forceinline__ void set(const PlaneArgs& P, const int (&ii)[3], int64_t, double& lc, double& ic, double& om) const {
+    __device__ __forceinline__ void plane(const PlaneArgs& P, const int s, const int64_t p, int, double (&w)[3]) const {
+        int ii[3];
+        plane_point(P, s, p, ii);
         const Curv2 c = at(P, ii);
-        om = occ_sign > 0 ? c.om : -c.om;   // the manifold value of tbk_curv.hip, bit for bit
-        const double h = -0.5 * om;
-        lc = h * (occ_sign > 0 ? c.e1 : c.e0);
-        ic = h * (occ_sign > 0 ? c.e0 : c.e1);
+        w[2] = occ_sign > 0 ? c.om : -c.om;   // the manifold value of tbk_curv.hip, bit for bit
+        const double h = -0.5 * w[2];
+        w[0] = h * (occ_sign > 0 ? c.e1 : c.e0);
+        w[1] = h * (occ_sign > 0 ? c.e0 : c.e1);
     }
 };
 struct OrbArraySrc {
@@ -74,11 +75,12 @@ struct OrbArraySrc {
         w[0] = om[i];
         w[1] = mm[i] - e * w[0];
     }
-    __device__ __forceinline__ void set(const PlaneArgs& P, const int (&)[3], const int64_t idx, double& lc, double& ic,
-                                        double& om) const {
-        lc = st[idx];
-        ic = st[P.npts + idx];
-        om = st[2 * P.npts + idx];
+    __device__ __forceinline__ void plane(const PlaneArgs& P, const int s, const int64_t p, int, double (&w)[3]) const {
+        int ii[3];
+        const int64_t idx = plane_point(P, s, p, ii);
+        w[0] = st[idx];
+        w[1] = st[P.npts + idx];
+        w[2] = st[2 * P.npts + idx];
     }
 };
 
@@ -88,10 +90,7 @@ __global__ __launch_bounds__(256) void k_orb2_records(const ModelView mv, const 
     const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (idx >= P.npts) return;
     int ii[3];
-    const int64_t i01 = idx / P.N[2];
-    ii[2] = (int)(idx - i01 * P.N[2]);
-    ii[0] = (int)(i01 / P.N[1]);
-    ii[1] = (int)(i01 - (int64_t)ii[0] * P.N[1]);
+    mesh_point(P.N, idx, ii);
     const Curv2 c = Kubo2Src{mv, d0, d1, 0}.at(P, ii);
     const double w = c.degenerate ? 0.0 : c.om;
     const double m = c.degenerate ? 0.0 : 0.5 * (c.e0 - c.e1) * c.om;
@@ -104,67 +103,24 @@ __global__ __launch_bounds__(256) void k_orb2_records(const ModelView mv, const 
 }
 
 // ---------------------------------------------------------------- reductions
-// band-set plane sums: blockIdx.x = g of gx, blockIdx.y = slice s (and every gridDim.y after it); part[s][c][gx], c = LC, IC, Omega.
-// Each sum runs in k_curv_plane's order (and the Omega sum is its manifold sum, bit for bit).
-template <class Src>
-__global__ __launch_bounds__(256) void k_orb_plane(const Src src, const PlaneArgs P, double* __restrict__ part) {
-    __shared__ double red[3][4];
-    for (int s = blockIdx.y; s < P.nslice; s += gridDim.y) {
-        double acc[3] = {0.0, 0.0, 0.0};
-        for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < P.nplane; p += (int64_t)gridDim.x * 256) {
-            int ii[3];
-            const int64_t idx = plane_point(P, s, p, ii);
-            double lc, ic, om;
-            src.set(P, ii, idx, lc, ic, om);
-            acc[0] += lc;
-            acc[1] += ic;
-            acc[2] += om;
-        }
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const double t = block_sum(acc[c], red[c]);
-            if (threadIdx.x == 0) part[((int64_t)s * 3 + c) * gridDim.x + blockIdx.x] = t;
-        }
-        __syncthreads();                                          // (red is reused by the next slice)
+// kT > 0 (k_kubo_thermal): the records (m, Omega) beside E.  Per (record, level) one exp, one log1p and one division:
+// t = e^{-|x|},  f = 1 / (1 + t) (x < 0) or t / (1 + t),  g = kT log1p(t) (x >= 0) or mu - E + kT log1p(t)
+struct OrbThermal {
+    static constexpr int NR = 2, NQ = 1;
+    static constexpr bool kWhole = false;
+    static __device__ __forceinline__ void add(const double e, const double (&rc)[2], const double u, const double kT, const double ikT,
+                                               double (&acc)[1]) {
+        const double m = rc[0], o = rc[1];
+        const double x = (e - u) * ikT;
+        const double t = exp(-fabs(x));
+        const double r = 1.0 / (1.0 + t);
+        const double l = kT * log1p(t);
+        const bool up = x >= 0.0;
+        const double f = up ? t * r : r;
+        const double gg = up ? l : (u - e) + l;
+        acc[0] = fma(f, m, fma(gg, o, acc[0]));
     }
-}
-
-// kT > 0 scan.  Workgroup (tile of kOrbKtTile levels, k-group g, slice s): lane t takes level j = tile + t and walks the records
-// (E, m, Omega) of the plane points [g nplane / G, (g + 1) nplane / G) of slice s, every band of a point in order; a record's
-// address depends on the workgroup and the loop alone, so it is read as a wave-uniform value.  Per (record, level) one exp, one
-// log1p and one division:  t = e^{-|x|},  f = 1 / (1 + t) (x < 0) or t / (1 + t),  g = kT log1p(t) (x >= 0) or
-// mu - E + kT log1p(t).  part[s][j][G]
-__global__ __launch_bounds__(256) void k_orb_kt(const PlaneArgs P, const int nb, const double* __restrict__ ev,
-                                                const double* __restrict__ mm, const double* __restrict__ om,
-                                                const double* __restrict__ mu, const int nmu, const double kT, const int G,
-                                                double* __restrict__ part) {
-    const int base = blockIdx.x * kOrbKtTile;
-    if (base + (int)(threadIdx.x & ~63u) >= nmu) return;            // a wavefront without a level (uniform)
-    const int j = base + threadIdx.x, g = blockIdx.y;
-    const double u = j < nmu ? mu[j] : 0.0;
-    const double ikT = 1.0 / kT;
-    const int64_t p0 = (int64_t)g * P.nplane / G, p1 = (int64_t)(g + 1) * P.nplane / G;
-    for (int s = blockIdx.z; s < P.nslice; s += gridDim.z) {
-        double acc = 0.0;
-        for (int64_t p = p0; p < p1; ++p) {
-            int ii[3];
-            const int64_t idx = plane_point(P, s, p, ii);
-            for (int b = 0; b < nb; ++b) {
-                const int64_t i = (int64_t)b * P.npts + idx;
-                const double e = ev[i], m = mm[i], o = om[i];
-                const double x = (e - u) * ikT;
-                const double t = exp(-fabs(x));
-                const double r = 1.0 / (1.0 + t);
-                const double l = kT * log1p(t);
-                const bool up = x >= 0.0;
-                const double f = up ? t * r : r;
-                const double gg = up ? l : (u - e) + l;
-                acc = fma(f, m, fma(gg, o, acc));
-            }
-        }
-        if (j < nmu) part[((int64_t)s * nmu + j) * G + g] = acc;
-    }
-}
+};
 
 // ---------------------------------------------------------------- n != 2: what a (point, band) lane of tbk_kubo.h's contraction keeps
 // Omega's and m's weights of the same P_nm (per band: mm[b], om[b] and ev[b] at [nfull] stride, om and ev nullable) or the band's
@@ -217,14 +173,12 @@ extern "C" int tbk_orb_moment_list(tbk_model* m, const double* k, int64_t nk, in
     tbk_ctx* ctx = m->ctx;
     TBK_HIP(hipSetDevice(ctx->device));
     const int64_t ndev = manifold && n != 2 ? 3 * nk : nout;   // a band set of the n != 2 path: st[3][nk]
-    const size_t kb = al256((size_t)nk * dk * sizeof(double)), ob = al256((size_t)ndev * sizeof(double));
     KuboChunks cw = n == 2 ? KuboChunks() : kubo_contract_chunks(n, dk, nk, manifold, OrbQ::NSET);
-    void* base = nullptr;
-    rc = tbk_ctx_scratch(ctx, 256 + kb + ob + cw.bytes(), &base);
+    double *k_dev, *o_dev;
+    KuboCarve ws;
+    ws.add(k_dev, (size_t)nk * dk * sizeof(double)), ws.add(o_dev, (size_t)ndev * sizeof(double)), ws.add(cw.base, cw.bytes());
+    rc = kubo_carve(ctx, ws);
     if (rc) return rc;
-    unsigned char* p = (unsigned char*)base + 256;
-    double* k_dev = (double*)p;
-    double* o_dev = (double*)(p + kb);
     TBK_HIP(hipMemcpyAsync(k_dev, k, (size_t)nk * dk * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     if (n == 2) {
         ProfScope ps(ctx, "orb2_list");
@@ -233,7 +187,6 @@ extern "C" int tbk_orb_moment_list(tbk_model* m, const double* k, int64_t nk, in
                            o_dev);
         TBK_HIP(hipGetLastError());
     } else {
-        cw.base = p + kb + ob;
         rc = kubo_contract<OrbQ>(m, k_dev, nullptr, nk, dir0, dir1, mask, cw,
                                  OrbQ::Out{manifold ? nullptr : o_dev, nullptr, nullptr, manifold ? o_dev : nullptr});
         if (rc) return rc;
@@ -257,12 +210,14 @@ extern "C" int tbk_orb_mag_mesh(tbk_model* m, const int32_t* mesh, int dir0, int
     if (rc) return rc;
     TBK_REQUIRE(mesh && out, TBK_EINVAL, "tbk_orb_mag_mesh: null argument");
     TBK_REQUIRE(m->dim_k == 2 || m->dim_k == 3, TBK_EINVAL, "tbk_orb_mag_mesh: dim_k=%d (meshes of 2 or 3 dimensions)", m->dim_k);
-    TBK_REQUIRE(nmu >= 0 && nmu <= 8192 && (nmu == 0 || mu), TBK_EINVAL, "tbk_orb_mag_mesh: nmu=%d (0..8192 levels)", nmu);
+    rc = kubo_levels_check("tbk_orb_mag_mesh", nmu, mu, 0);
+    if (rc) return rc;
     TBK_REQUIRE((nmu > 0) != (occ != nullptr), TBK_EINVAL, "tbk_orb_mag_mesh: give exactly one of a band set and Fermi levels");
-    TBK_REQUIRE(std::isfinite(kT) && kT >= 0.0, TBK_EINVAL, "tbk_orb_mag_mesh: kT must be finite and >= 0");
+    rc = kubo_kt_check("tbk_orb_mag_mesh", kT, false);
+    if (rc) return rc;
     TBK_REQUIRE(kT == 0.0 || nmu > 0, TBK_EINVAL, "tbk_orb_mag_mesh: kT > 0 needs Fermi levels");
-    for (int j = 0; j < nmu; ++j)
-        TBK_REQUIRE(std::isfinite(mu[j]), TBK_EINVAL, "tbk_orb_mag_mesh: Fermi level %d is not finite", j);
+    rc = kubo_levels_finite("tbk_orb_mag_mesh", nmu, mu);
+    if (rc) return rc;
     const int n = m->nsta, dk = m->dim_k;
     PlaneArgs P;
     rc = kubo_planes("tbk_orb_mag_mesh", mesh, dir0, dir1, dk, P);
@@ -292,47 +247,32 @@ extern "C" int tbk_orb_mag_mesh(tbk_model* m, const int32_t* mesh, int dir0, int
         gx = kubo_fermi_gx(P, n, nmu, 2);
         nrows = (int64_t)nslice * nmu * 2;
     } else {
-        const int64_t cap = std::max<int64_t>(1, ((int64_t)1 << 22) / ((int64_t)nslice * nmu));
-        gx = (int)std::max<int64_t>(1, std::min<int64_t>({(P.nplane * n + 1023) / 1024, (int64_t)kOrbKtGroupsMax, cap}));
+        gx = kubo_thermal_groups(P, n, nmu, 1);
         nrows = (int64_t)nslice * nmu;
     }
-    const size_t partb = al256((size_t)nrows * gx * sizeof(double)), rowb = al256((size_t)nrows * sizeof(double));
-    const size_t mub = al256((size_t)std::max(nmu, 1) * sizeof(double));
     const bool general = n != 2;
-    // per-point arrays: band set st[3][npts] (n != 2); per band ev, mm, om [n][npts] (n != 2, or n = 2 with kT > 0)
-    const size_t stb = general && manifold ? al256((size_t)3 * npts * sizeof(double)) : 0;
-    const size_t recb = (general && !manifold) || hot ? al256((size_t)n * npts * sizeof(double)) : 0;
+    // per-point arrays: band set st[3][npts] (n != 2); per band rec[3][n][npts] = ev, mm, om (n != 2, or n = 2 with kT > 0)
+    const bool recs = (general && !manifold) || hot;
+    const size_t recn = (size_t)n * npts;
     KuboChunks cw = general ? kubo_contract_chunks(n, dk, npts, manifold, OrbQ::NSET) : KuboChunks();
-    void* base = nullptr;
-    rc = tbk_ctx_scratch(ctx, 256 + partb + rowb + mub + stb + 3 * recb + cw.bytes(), &base);
+    double *part, *rows, *mu_dev, *st_dev, *ev_dev;
+    KuboCarve ws;
+    ws.add(part, (size_t)nrows * gx * sizeof(double)), ws.add(rows, (size_t)nrows * sizeof(double));
+    ws.add(mu_dev, (size_t)std::max(nmu, 1) * sizeof(double));
+    ws.add(st_dev, general && manifold ? (size_t)3 * npts * sizeof(double) : 0);
+    ws.add(ev_dev, recs ? 3 * recn * sizeof(double) : 0), ws.add(cw.base, cw.bytes());
+    rc = kubo_carve(ctx, ws);
     if (rc) return rc;
-    unsigned char* p = (unsigned char*)base + 256;
-    double* part = (double*)p;
-    p += partb;
-    double* rows = (double*)p;
-    p += rowb;
-    double* mu_dev = (double*)p;
-    p += mub;
-    double* st_dev = stb ? (double*)p : nullptr;
-    p += stb;
-    double* ev_dev = recb ? (double*)p : nullptr;
-    double* mm_dev = recb ? (double*)(p + recb) : nullptr;
-    double* om_dev = recb ? (double*)(p + 2 * recb) : nullptr;
-    p += 3 * recb;
-    cw.base = p;
+    double* mm_dev = recs ? ev_dev + recn : nullptr;
+    double* om_dev = recs ? ev_dev + 2 * recn : nullptr;
     if (nmu) TBK_HIP(hipMemcpyAsync(mu_dev, mus.data(), (size_t)nmu * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     auto reduce = [&](auto src) -> int {
         if (manifold) {
             ProfScope ps(ctx, n == 2 ? "orb2_plane" : "orb_plane");
-            hipLaunchKernelGGL(k_orb_plane<decltype(src)>, dim3(gx, (unsigned)std::min(nslice, 65535)), dim3(256), 0, ctx->stream, src,
-                               P, part);
-            TBK_HIP(hipGetLastError());
-        } else {
-            ProfScope ps(ctx, n == 2 ? "orb2_fermi" : "orb_fermi");
-            int rc = kubo_fermi_launch<2>(ctx, src, P, n, mu_dev, nmu, gx, part);
-            if (rc) return rc;
+            return kubo_plane_launch<3>(ctx, src, P, 1, nslice, gx, part);
         }
-        return TBK_OK;
+        ProfScope ps(ctx, n == 2 ? "orb2_fermi" : "orb_fermi");
+        return kubo_fermi_launch<2>(ctx, src, P, n, mu_dev, nmu, gx, part);
     };
     if (general) {
         rc = kubo_contract<OrbQ>(m, nullptr, mesh, npts, dir0, dir1, mask, cw, OrbQ::Out{mm_dev, om_dev, ev_dev, st_dev});
@@ -344,25 +284,16 @@ extern "C" int tbk_orb_mag_mesh(tbk_model* m, const int32_t* mesh, int dir0, int
     }
     if (hot) {
         ProfScope ps(ctx, "orb_kt");
-        const unsigned ntile = (unsigned)((nmu + kOrbKtTile - 1) / kOrbKtTile);
-        hipLaunchKernelGGL(k_orb_kt, dim3(ntile, (unsigned)gx, (unsigned)std::min(nslice, 65535)), dim3(256), 0, ctx->stream, P, n,
-                           (const double*)ev_dev, (const double*)mm_dev, (const double*)om_dev, (const double*)mu_dev, nmu, kT, gx,
-                           part);
-        TBK_HIP(hipGetLastError());
+        rc = kubo_thermal_launch<OrbThermal>(ctx, P, n, ev_dev, mu_dev, nmu, kT, gx, part);
     } else if (general) {
         rc = reduce(OrbArraySrc{ev_dev, mm_dev, om_dev, st_dev});
     } else {
         rc = reduce(Orb2Src{{m->view, dir0, dir1, manifold ? (mask[0] ? 1 : -1) : 0}});
     }
     if (rc) return rc;
-    {
-        ProfScope ps(ctx, "orb_rows");
-        hipLaunchKernelGGL(k_kubo_rows, dim3((unsigned)nrows), dim3(256), 0, ctx->stream, (const double*)part, gx, rows);
-        TBK_HIP(hipGetLastError());
-    }
-    std::vector<double> sums((size_t)nrows);
-    TBK_HIP(hipMemcpyAsync(sums.data(), rows, (size_t)nrows * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    TBK_HIP(hipStreamSynchronize(ctx->stream));
+    std::vector<double> sums;
+    rc = kubo_rows_to_host(ctx, "orb_rows", part, gx, nrows, rows, sums);
+    if (rc) return rc;
     const double inv = 1.0 / (double)P.nplane;
     // out[ch][s]: the Python shapes (nch,) for a 2-D mesh, (nch, nslice) for a 3-D one
     for (int s = 0; s < nslice; ++s) {

@@ -12,8 +12,9 @@
 //   n = 1, 3..32   k_qgt_lds: the tiling of k_kubo_lds with one LDS slot per direction: U, T and dim_k slots of n^2 per point
 //   33..2048       per chunk and per pair a <= b: k_kubo_wsp (as it is) builds W^a and W^b, k_qgt_contract keeps both parts of the
 //                  pair sums, k_qgt_occ_sum adds a band set's shares
-// Mesh means: per-workgroup partials in a grid-stride order that depends on the mesh shape alone, block_sum inside a workgroup,
-// k_kubo_rows across workgroups, chunk results added in chunk order on the host.  No floating-point atomics anywhere.
+// Mesh means: per-workgroup partials in a grid-stride order that depends on the mesh shape alone (k_qgt2's own sums at n = 2,
+// tbk_kubo.h's k_kubo_plane over a chunk's buffer otherwise), block_sum inside a workgroup, k_kubo_rows across workgroups, chunk
+// results added in chunk order on the host.  No floating-point atomics anywhere.
 #include <math.h>
 #include <string.h>
 #include "tbk_kubo.h"
@@ -106,11 +107,11 @@ __global__ __launch_bounds__(256) void k_qgt2(const ModelView mv, const double* 
 #pragma unroll
             for (int d = 0; d < DK; ++d) kk[d] = k[ik * DK + d];
         } else {                                           // k_uniform_mesh's point, bit for bit
-            const int64_t i01 = ik / N2;
-            const int i2 = (int)(ik - i01 * N2), i0 = (int)(i01 / N1), i1 = (int)(i01 - (int64_t)i0 * N1);
-            kk[0] = (double)i0 / (double)N0;
-            if (DK > 1) kk[1] = (double)i1 / (double)N1;
-            if (DK > 2) kk[2] = (double)i2 / (double)N2;
+            const int N[3] = {N0, N1, N2};
+            int ii[3];
+            mesh_point(N, ik, ii);
+#pragma unroll
+            for (int d = 0; d < DK; ++d) kk[d] = (double)ii[d] / (double)N[d];
         }
         double q[NC];
         const bool deg = qgt2_point<DK>(mv, kk, q);
@@ -321,21 +322,14 @@ __global__ __launch_bounds__(256) void k_qgt_occ_sum(const double* __restrict__ 
 }
 
 // ---------------------------------------------------------------- mesh means of the chunked forms
-// part[row][gridDim.x] of buf[row][stride] over its first cnt entries (row = blockIdx.y and every gridDim.y after it)
-__global__ __launch_bounds__(256) void k_qgt_part(const double* __restrict__ buf, const int64_t stride, const int64_t cnt,
-                                                  const int64_t nrows, double* __restrict__ part) {
-    __shared__ double red[4];
-    for (int64_t row = blockIdx.y; row < nrows; row += gridDim.y) {
-        const double* p = buf + row * stride;
-        double acc = 0.0;
-        for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < cnt; i += (int64_t)gridDim.x * 256) acc += p[i];
-        const double t = block_sum(acc, red);
-        if (threadIdx.x == 0) part[row * gridDim.x + blockIdx.x] = t;
-        __syncthreads();                                           // (red is reused by the next row)
+// k_kubo_plane's source: channel `row` of buf[row][stride], the chunk's first P.nplane entries as the plane
+struct QgtBufSrc {
+    const double* buf;
+    int64_t stride;
+    __device__ __forceinline__ void plane(const PlaneArgs&, int, const int64_t p, const int row, double (&w)[1]) const {
+        w[0] = buf[row * stride + p];
     }
-}
-// workgroups per row: a function of the number of points alone
-static inline int qgt_gx(int64_t npts) { return (int)std::max<int64_t>(1, std::min<int64_t>((npts + 2047) / 2048, 1024)); }
+};
 
 // ---------------------------------------------------------------- host side
 // this unit's own checks (kubo_check demands dim_k >= 2 and two different axes); mask as kubo_check's
@@ -343,20 +337,7 @@ static int qgt_check(const char* fn, tbk_model* m, const int32_t* occ, int nocc,
     TBK_REQUIRE(m, TBK_EINVAL, "%s: null model", fn);
     TBK_REQUIRE(m->dim_k >= 1 && m->dim_k <= 3, TBK_EINVAL, "%s: the quantum geometric tensor needs dim_k 1..3 (the model has %d)", fn,
                 m->dim_k);
-    const int n = m->nsta;
-    mask.clear();
-    if (occ) {
-        TBK_REQUIRE(nocc >= 1 && nocc <= n, TBK_EINVAL, "%s: nocc=%d (1..%d)", fn, nocc, n);
-        mask.assign(n, 0);
-        for (int i = 0; i < nocc; ++i) {
-            TBK_REQUIRE(occ[i] >= 0 && occ[i] < n, TBK_EINVAL, "%s: occ[%d]=%d outside [0, %d)", fn, i, occ[i], n);
-            TBK_REQUIRE(!mask[occ[i]], TBK_EINVAL, "%s: band %d appears twice in occ", fn, occ[i]);
-            mask[occ[i]] = 1;
-        }
-    } else {
-        TBK_REQUIRE(nocc == 0, TBK_EINVAL, "%s: nocc=%d without occ", fn, nocc);
-    }
-    return TBK_OK;
+    return kubo_occ_mask(fn, m, occ, nocc, mask);
 }
 
 static int qgt2_launch(tbk_model* m, const double* k_dev, int64_t nk, const int32_t* mesh, int sel, const QgtOut& out, int gx,
@@ -439,20 +420,17 @@ extern "C" int tbk_qgt_list(tbk_model* m, const double* k, int64_t nk, const int
     }
     tbk_ctx* ctx = m->ctx;
     TBK_HIP(hipSetDevice(ctx->device));
-    const size_t kb = al256((size_t)nk * dk * sizeof(double)), ob = al256((size_t)nout * sizeof(double));
     KuboChunks cw = n != 2 ? kubo_contract_chunks(n, dk, nk, manifold, 2) : KuboChunks();
-    void* base = nullptr;
-    rc = tbk_ctx_scratch(ctx, 256 + kb + ob + cw.bytes(), &base);
+    double *k_dev, *o_dev;
+    KuboCarve ws;
+    ws.add(k_dev, (size_t)nk * dk * sizeof(double)), ws.add(o_dev, (size_t)nout * sizeof(double)), ws.add(cw.base, cw.bytes());
+    rc = kubo_carve(ctx, ws);
     if (rc) return rc;
-    unsigned char* p = (unsigned char*)base + 256;
-    double* k_dev = (double*)p;
-    double* o_dev = (double*)(p + kb);
     const QgtOut o{o_dev, nk * nc, nc, 1};                         // out[ch][ik][c]
     TBK_HIP(hipMemcpyAsync(k_dev, k, (size_t)nk * dk * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     if (n == 2) {
         rc = qgt2_launch(m, k_dev, nk, nullptr, manifold ? (mask[0] ? 1 : -1) : 0, o, 0, nullptr);
     } else {
-        cw.base = p + kb + ob;
         rc = qgt_contract(m, k_dev, nullptr, nk, mask, cw, o, true, [](int64_t, int64_t) -> int { return TBK_OK; });
     }
     if (rc) return rc;
@@ -468,11 +446,10 @@ extern "C" int tbk_qgt_mesh(tbk_model* m, const int32_t* mesh, const int32_t* oc
     if (rc) return rc;
     TBK_REQUIRE(mesh && out, TBK_EINVAL, "%s: null argument", fn);
     const int n = m->nsta, dk = m->dim_k, nc = dk * dk, ng = dk * (dk + 1) / 2;
-    int64_t npts = 1;
-    for (int d = 0; d < dk; ++d) {
-        TBK_REQUIRE(mesh[d] >= 1, TBK_EINVAL, "%s: mesh[%d]=%d", fn, d, mesh[d]);
-        npts *= mesh[d];
-    }
+    PlaneArgs P;                           // one "plane": the whole mesh
+    rc = kubo_whole_mesh(fn, mesh, dk, P);
+    if (rc) return rc;
+    const int64_t npts = P.npts;
     const bool manifold = occ != nullptr;
     const int nch = manifold ? 1 : n;
     if (manifold && nocc == n) {
@@ -482,24 +459,18 @@ extern "C" int tbk_qgt_mesh(tbk_model* m, const int32_t* mesh, const int32_t* oc
     tbk_ctx* ctx = m->ctx;
     TBK_HIP(hipSetDevice(ctx->device));
     const double inv = 1.0 / (double)npts;
-    void* base = nullptr;
+    double *buf, *part, *rows;
+    KuboCarve ws;
+    std::vector<double> sums;
     if (n == 2) {                          // the lanes make their own k: nothing per point touches HBM
-        const int gx = qgt_gx(npts);
-        const size_t partb = al256((size_t)nc * gx * sizeof(double));
-        rc = tbk_ctx_scratch(ctx, 256 + partb + al256((size_t)nc * sizeof(double)), &base);
+        const int gx = kubo_plane_gx(P);
+        ws.add(part, (size_t)nc * gx * sizeof(double)), ws.add(rows, (size_t)nc * sizeof(double));
+        rc = kubo_carve(ctx, ws);
         if (rc) return rc;
-        double* part = (double*)((unsigned char*)base + 256);
-        double* rows = (double*)((unsigned char*)part + partb);
         rc = qgt2_launch(m, nullptr, npts, mesh, manifold ? (mask[0] ? 1 : -1) : 0, QgtOut{nullptr, 0, 0, 0}, gx, part);
         if (rc) return rc;
-        {
-            ProfScope ps(ctx, "qgt_rows");
-            hipLaunchKernelGGL(k_kubo_rows, dim3((unsigned)nc), dim3(256), 0, ctx->stream, (const double*)part, gx, rows);
-            TBK_HIP(hipGetLastError());
-        }
-        double sums[9];
-        TBK_HIP(hipMemcpyAsync(sums, rows, (size_t)nc * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-        TBK_HIP(hipStreamSynchronize(ctx->stream));
+        rc = kubo_rows_to_host(ctx, "qgt_rows", part, gx, nc, rows, sums);
+        if (rc) return rc;
         for (int c = 0; c < nc; ++c) {
             out[c] = sums[c] * inv;
             if (!manifold) out[nc + c] = c >= ng ? -out[c] : out[c];   // band 1: the same g, -Omega, bit for bit
@@ -507,34 +478,24 @@ extern "C" int tbk_qgt_mesh(tbk_model* m, const int32_t* mesh, const int32_t* oc
         return TBK_OK;
     }
     // chunked forms: a chunk's values buf[c][ch][chunk], its partials, one row of sums per chunk
-    const KuboChunks cw0 = kubo_contract_chunks(n, dk, npts, manifold, 2);
-    const int64_t chunk = cw0.chunk, nchunks = (npts + chunk - 1) / chunk, nrows = (int64_t)nc * nch;
-    const int gx = qgt_gx(chunk);
-    const size_t bufb = al256((size_t)nrows * chunk * sizeof(double)), partb = al256((size_t)nrows * gx * sizeof(double));
-    const size_t rowb = al256((size_t)nchunks * nrows * sizeof(double));
-    rc = tbk_ctx_scratch(ctx, 256 + bufb + partb + rowb + cw0.bytes(), &base);
+    KuboChunks cw = kubo_contract_chunks(n, dk, npts, manifold, 2);
+    const int64_t chunk = cw.chunk, nchunks = (npts + chunk - 1) / chunk, nrows = (int64_t)nc * nch;
+    P.nplane = chunk;
+    const int gx = kubo_plane_gx(P);
+    ws.add(buf, (size_t)nrows * chunk * sizeof(double)), ws.add(part, (size_t)nrows * gx * sizeof(double));
+    ws.add(rows, (size_t)nchunks * nrows * sizeof(double)), ws.add(cw.base, cw.bytes());
+    rc = kubo_carve(ctx, ws);
     if (rc) return rc;
-    unsigned char* p = (unsigned char*)base + 256;
-    double* buf = (double*)p;
-    double* part = (double*)(p + bufb);
-    double* rows = (double*)(p + bufb + partb);
-    KuboChunks cw = cw0;
-    cw.base = p + bufb + partb + rowb;
     const QgtOut o{buf, chunk, 1, (int64_t)nch * chunk};           // buf[c][ch][i]: row = c nch + ch
     rc = qgt_contract(m, nullptr, mesh, npts, mask, cw, o, false, [&](int64_t first, int64_t cnt) -> int {
         ProfScope ps(ctx, "qgt_rows");
-        hipLaunchKernelGGL(k_qgt_part, dim3(gx, (unsigned)std::min<int64_t>(nrows, 65535)), dim3(256), 0, ctx->stream, (const double*)buf,
-                           chunk, cnt, nrows, part);
-        TBK_HIP(hipGetLastError());
-        hipLaunchKernelGGL(k_kubo_rows, dim3((unsigned)nrows), dim3(256), 0, ctx->stream, (const double*)part, gx,
-                           rows + (first / chunk) * nrows);
-        TBK_HIP(hipGetLastError());
-        return TBK_OK;
+        P.nplane = cnt;
+        int rc = kubo_plane_launch<1>(ctx, QgtBufSrc{buf, chunk}, P, (int)nrows, nrows, gx, part);
+        return rc ? rc : kubo_rows_launch(ctx, part, gx, nrows, rows + (first / chunk) * nrows);
     });
     if (rc) return rc;
-    std::vector<double> sums((size_t)(nchunks * nrows));
-    TBK_HIP(hipMemcpyAsync(sums.data(), rows, sums.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    TBK_HIP(hipStreamSynchronize(ctx->stream));
+    rc = kubo_to_host(ctx, rows, nchunks * nrows, sums);
+    if (rc) return rc;
     for (int ch = 0; ch < nch; ++ch)
         for (int c = 0; c < nc; ++c) {
             double acc = 0.0;                                      // chunk results in chunk order

@@ -15,15 +15,13 @@
 //
 // Pipeline: the chunk loop of tbk_kubo.h (k generator, solver with vectors); per chunk the contraction with CurvQ (E_n, Omega_n; every
 // n, two states included) and the velocity kernel below -- a sparse bilinear form over the non-empty slots, O(nnz) per matrix element,
-// no dense d H and no matrix product; then one thermal scan over the per-band records of the whole mesh (k_orb_kt's pattern: levels
-// across lanes, records read as wave-uniform values, sums in registers) and k_kubo_rows.  Every partition depends on the mesh, n and
+// no dense d H and no matrix product; then one thermal scan over the per-band records of the whole mesh (k_kubo_thermal of
+// tbk_kubo.h with the policies TrThermal and DrudeThermal below) and k_kubo_rows.  Every partition depends on the mesh, n and
 // the number of levels alone, and nothing uses atomics on floating-point data: two calls give the same bits.
 #include <math.h>
 #include <string.h>
 #include "tbk_kubo.h"
 
-static const int kTrTile = 256;                          // levels per workgroup of k_tr_scan (one per lane)
-static const int kTrGroupsMax = 1024;                    // k-groups of k_tr_scan at most
 #define TR_LDS_U 1024                                    // k_tr_vel_lds: eigenvectors of a workgroup's points, P n^2 <= 1024 cd
 #define TR_LDS_SV 2048                                   // and their slot values, 3 P nnz <= 3 P n (n + 1) / 2 <= 1920 cd
 
@@ -244,71 +242,50 @@ __global__ __launch_bounds__(256) void k_tr_vel_wide(const ModelView mv, const d
 }
 
 // ---------------------------------------------------------------- thermal scan
-// k_orb_kt's pattern with NQ sums per lane.  rec[1 + NR][nb][npts]: E, then Omega and vbar^c (transport, NR = 1 + DK, NQ = 2 + DK:
-// hall, nernst, dipole_c) or the w^{cd} (Drude, NR = NQ = DK (DK + 1) / 2; one slice, the plane is the whole mesh in k_uniform_mesh
-// order).  Workgroup (tile of kTrTile levels, k-group g, slice s): lane t takes level j = tile + t and walks the records of the plane
-// points [g nplane / G, (g + 1) nplane / G) of slice s, every band of a point in order; a record's address depends on the workgroup
-// and the loop alone, so it is read as a wave-uniform value.  Per (record, level) one exp, one division and (transport) one log1p.
-// part[s][j][NQ][G]
-template <int DK, bool DRUDE>
-__global__ __launch_bounds__(256) void k_tr_scan(const PlaneArgs P, const int nb, const double* __restrict__ rec,
-                                                 const double* __restrict__ mu, const int nmu, const double kT, const int G,
-                                                 double* __restrict__ part) {
-    constexpr int NR = DRUDE ? DK * (DK + 1) / 2 : 1 + DK;
-    constexpr int NQ = DRUDE ? DK * (DK + 1) / 2 : 2 + DK;
-    const int base = blockIdx.x * kTrTile;
-    if (base + (int)(threadIdx.x & ~63u) >= nmu) return;            // a wavefront without a level (uniform)
-    const int j = base + threadIdx.x, g = blockIdx.y;
-    const double u = j < nmu ? mu[j] : 0.0;
-    const double ikT = 1.0 / kT;
-    const int64_t stride = (int64_t)nb * P.npts;
-    const int64_t p0 = (int64_t)g * P.nplane / G, p1 = (int64_t)(g + 1) * P.nplane / G;
-    for (int s = blockIdx.z; s < P.nslice; s += gridDim.z) {
-        double acc[NQ];
+// The policies of k_kubo_thermal (tbk_kubo.h): the records beside E are Omega and vbar^c (transport: hall, nernst, dipole_c) or the
+// w^{cd} (Drude; the whole mesh).  Per (record, level) one exp, one division and (transport) one log1p.
+template <int DK>
+struct TrThermal {
+    static constexpr int NR = 1 + DK, NQ = 2 + DK;
+    static constexpr bool kWhole = false;
+    static __device__ __forceinline__ void add(const double e, const double (&r)[NR], const double u, double, const double ikT,
+                                               double (&acc)[NQ]) {
+        const double x = (e - u) * ikT, ax = fabs(x);
+        const double t = exp(-ax);
+        const double q = 1.0 / (1.0 + t);
+        const double tq = t * q;
+        const double df = tq * q * ikT;                             // -df/dE
+        const double f = x >= 0.0 ? tq : q;
+        const double en = fma(ax, tq, log1p(t));                    // -f ln f - (1 - f) ln(1 - f)
+        acc[0] = fma(f, r[0], acc[0]);
+        acc[1] = fma(en, r[0], acc[1]);
+        const double dw = df * r[0];
 #pragma unroll
-        for (int c = 0; c < NQ; ++c) acc[c] = 0.0;
-        for (int64_t p = p0; p < p1; ++p) {
-            int ii[3];
-            const int64_t idx = DRUDE ? p : plane_point(P, s, p, ii);
-            for (int b = 0; b < nb; ++b) {
-                const int64_t i = (int64_t)b * P.npts + idx;
-                const double e = rec[i];
-                double r[NR];
-#pragma unroll
-                for (int c = 0; c < NR; ++c) r[c] = rec[(1 + c) * stride + i];
-                const double x = (e - u) * ikT, ax = fabs(x);
-                const double t = exp(-ax);
-                const double q = 1.0 / (1.0 + t);
-                const double tq = t * q;
-                const double df = tq * q * ikT;                     // -df/dE
-                if constexpr (DRUDE) {
-#pragma unroll
-                    for (int c = 0; c < NQ; ++c) acc[c] = fma(df, r[c], acc[c]);
-                } else {
-                    const double f = x >= 0.0 ? tq : q;
-                    const double en = fma(ax, tq, log1p(t));        // -f ln f - (1 - f) ln(1 - f)
-                    acc[0] = fma(f, r[0], acc[0]);
-                    acc[1] = fma(en, r[0], acc[1]);
-                    const double dw = df * r[0];
-#pragma unroll
-                    for (int c = 0; c < DK; ++c) acc[2 + c] = fma(dw, r[1 + c], acc[2 + c]);
-                }
-            }
-        }
-        if (j < nmu)
-#pragma unroll
-            for (int c = 0; c < NQ; ++c) part[(((int64_t)s * nmu + j) * NQ + c) * G + g] = acc[c];
+        for (int c = 0; c < DK; ++c) acc[2 + c] = fma(dw, r[1 + c], acc[2 + c]);
     }
-}
+};
+template <int DK>
+struct DrudeThermal {
+    static constexpr int NR = DK * (DK + 1) / 2, NQ = NR;
+    static constexpr bool kWhole = true;
+    static __device__ __forceinline__ void add(const double e, const double (&r)[NR], const double u, double, const double ikT,
+                                               double (&acc)[NQ]) {
+        const double x = (e - u) * ikT, ax = fabs(x);
+        const double t = exp(-ax);
+        const double q = 1.0 / (1.0 + t);
+        const double tq = t * q;
+        const double df = tq * q * ikT;                             // -df/dE
+#pragma unroll
+        for (int c = 0; c < NQ; ++c) acc[c] = fma(df, r[c], acc[c]);
+    }
+};
 
 // ---------------------------------------------------------------- host side
 static int tr_levels_check(const char* fn, int nmu, const double* mu, double kT) {
-    TBK_REQUIRE(nmu >= 1 && nmu <= 8192 && mu, TBK_EINVAL, "%s: nmu=%d (1..8192 levels)", fn, nmu);
-    TBK_REQUIRE(std::isfinite(kT) && kT > 0.0, TBK_EINVAL, "%s: kT must be finite and > 0", fn);
-    for (int j = 0; j < nmu; ++j) TBK_REQUIRE(std::isfinite(mu[j]), TBK_EINVAL, "%s: Fermi level %d is not finite", fn, j);
-    return TBK_OK;
+    int rc = kubo_levels_check(fn, nmu, mu, 1);
+    if (!rc) rc = kubo_kt_check(fn, kT, true);
+    return rc ? rc : kubo_levels_finite(fn, nmu, mu);
 }
-
 // the velocity kernel of one chunk (eigenpairs ec[n][cnt], vc[n][cnt][n] of the points kp)
 static int tr_velocity(tbk_model* m, const double* kp, const double* ec, const cd* vc, int64_t cnt, const VelOut& o) {
     tbk_ctx* ctx = m->ctx;
@@ -332,32 +309,15 @@ static int tr_velocity(tbk_model* m, const double* kp, const double* ec, const c
 }
 
 // the thermal scan of rec over the planes P and the row sums: sums[s][j][NQ] on the host
-template <int DK, bool DRUDE>
+template <class Pol>
 static int tr_scan(tbk_ctx* ctx, const PlaneArgs& P, int n, const double* rec, const double* mu_dev, int nmu, double kT, int G,
                    double* part, double* rows, std::vector<double>& sums) {
-    constexpr int NQ = DRUDE ? DK * (DK + 1) / 2 : 2 + DK;
-    const int64_t nrows = (int64_t)P.nslice * nmu * NQ;
     {
-        ProfScope ps(ctx, DRUDE ? "drude_scan" : "tr_scan");
-        const unsigned ntile = (unsigned)((nmu + kTrTile - 1) / kTrTile);
-        hipLaunchKernelGGL((k_tr_scan<DK, DRUDE>), dim3(ntile, (unsigned)G, (unsigned)std::min(P.nslice, 65535)), dim3(256), 0, ctx->stream, P,
-                           n, rec, mu_dev, nmu, kT, G, part);
-        TBK_HIP(hipGetLastError());
+        ProfScope ps(ctx, Pol::kWhole ? "drude_scan" : "tr_scan");
+        int rc = kubo_thermal_launch<Pol>(ctx, P, n, rec, mu_dev, nmu, kT, G, part);
+        if (rc) return rc;
     }
-    {
-        ProfScope ps(ctx, "tr_rows");
-        hipLaunchKernelGGL(k_kubo_rows, dim3((unsigned)nrows), dim3(256), 0, ctx->stream, (const double*)part, G, rows);
-        TBK_HIP(hipGetLastError());
-    }
-    sums.resize((size_t)nrows);
-    TBK_HIP(hipMemcpyAsync(sums.data(), rows, (size_t)nrows * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    TBK_HIP(hipStreamSynchronize(ctx->stream));
-    return TBK_OK;
-}
-// k-groups of the scan: a function of the mesh shape, n, nmu and nq alone
-static inline int tr_scan_groups(const PlaneArgs& P, int n, int nmu, int nq) {
-    const int64_t cap = std::max<int64_t>(1, ((int64_t)1 << 22) / ((int64_t)P.nslice * nmu * nq));
-    return (int)std::max<int64_t>(1, std::min<int64_t>({(P.nplane * n + 1023) / 1024, (int64_t)kTrGroupsMax, cap}));
+    return kubo_rows_to_host(ctx, "tr_rows", part, G, (int64_t)P.nslice * nmu * Pol::NQ, rows, sums);
 }
 
 extern "C" int tbk_band_velocity_list(tbk_model* m, const double* k, int64_t nk, int dir, double* out) {
@@ -371,15 +331,12 @@ extern "C" int tbk_band_velocity_list(tbk_model* m, const double* k, int64_t nk,
     const int n = m->nsta, dk = m->dim_k;
     tbk_ctx* ctx = m->ctx;
     TBK_HIP(hipSetDevice(ctx->device));
-    const size_t kb = al256((size_t)nk * dk * sizeof(double)), vb = al256((size_t)dk * n * nk * sizeof(double));
     KuboChunks cw(n, dk, kubo_chunk_len(n, nk), 0, 0, 0);
-    void* base = nullptr;
-    int rc = tbk_ctx_scratch(ctx, 256 + kb + vb + cw.bytes(), &base);
+    double *k_dev, *v_dev;
+    KuboCarve ws;
+    ws.add(k_dev, (size_t)nk * dk * sizeof(double)), ws.add(v_dev, (size_t)dk * n * nk * sizeof(double)), ws.add(cw.base, cw.bytes());
+    int rc = kubo_carve(ctx, ws);
     if (rc) return rc;
-    unsigned char* p = (unsigned char*)base + 256;
-    double* k_dev = (double*)p;
-    double* v_dev = (double*)(p + kb);
-    cw.base = p + kb + vb;
     TBK_HIP(hipMemcpyAsync(k_dev, k, (size_t)nk * dk * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     rc = kubo_for_chunks(m, cw, k_dev, nullptr, nk, [&](int64_t first, int64_t cnt, const double* kp, const double* ec, const cd* vc) -> int {
         return tr_velocity(m, kp, ec, vc, cnt, VelOut{nullptr, v_dev, nullptr, nullptr, first, nk});
@@ -413,28 +370,16 @@ extern "C" int tbk_anom_transport_mesh(tbk_model* m, const int32_t* mesh, int di
     }
     tbk_ctx* ctx = m->ctx;
     TBK_HIP(hipSetDevice(ctx->device));
-    const int G = tr_scan_groups(P, n, nmu, nq);
-    const int64_t nrows = (int64_t)nslice * nmu * nq;
-    const size_t partb = al256((size_t)nrows * G * sizeof(double)), rowb = al256((size_t)nrows * sizeof(double));
-    const size_t mub = al256((size_t)nmu * sizeof(double));
-    const size_t recb = (size_t)n * npts * sizeof(double);                       // rec[2 + dk][n][npts]: E, Omega, vbar^c
-    const size_t vb = n > 32 ? al256((size_t)dk * recb) : 0;                     // raw velocities: the wide form's diagonal
+    const int G = kubo_thermal_groups(P, n, nmu, nq);
     KuboChunks cw = kubo_contract_chunks(n, dk, npts, false, CurvQ::NSET);
-    void* base = nullptr;
-    rc = tbk_ctx_scratch(ctx, 256 + partb + rowb + mub + al256((2 + dk) * recb) + vb + cw.bytes(), &base);
+    const int64_t nrows = (int64_t)nslice * nmu * nq;
+    const size_t recb = (size_t)n * npts * sizeof(double);                       // rec[2 + dk][n][npts]: E, Omega, vbar^c
+    double *part, *rows, *mu_dev, *rec, *v_dev;
+    KuboCarve ws;
+    ws.add(part, (size_t)nrows * G * sizeof(double)), ws.add(rows, (size_t)nrows * sizeof(double)), ws.add(mu_dev, (size_t)nmu * sizeof(double));
+    ws.add(rec, (2 + dk) * recb), ws.add(v_dev, n > 32 ? dk * recb : 0), ws.add(cw.base, cw.bytes());   // v: the wide form's diagonal
+    rc = kubo_carve(ctx, ws);
     if (rc) return rc;
-    unsigned char* p = (unsigned char*)base + 256;
-    double* part = (double*)p;
-    p += partb;
-    double* rows = (double*)p;
-    p += rowb;
-    double* mu_dev = (double*)p;
-    p += mub;
-    double* rec = (double*)p;
-    p += al256((2 + dk) * recb);
-    double* v_dev = vb ? (double*)p : nullptr;
-    p += vb;
-    cw.base = p;
     double* ev_dev = rec;
     double* om_dev = rec + (size_t)n * npts;
     double* vbar_dev = rec + 2 * (size_t)n * npts;
@@ -445,8 +390,8 @@ extern "C" int tbk_anom_transport_mesh(tbk_model* m, const int32_t* mesh, int di
                               });
     if (rc) return rc;
     std::vector<double> sums;
-    rc = dk == 2 ? tr_scan<2, false>(ctx, P, n, rec, mu_dev, nmu, kT, G, part, rows, sums)
-                 : tr_scan<3, false>(ctx, P, n, rec, mu_dev, nmu, kT, G, part, rows, sums);
+    rc = dk == 2 ? tr_scan<TrThermal<2>>(ctx, P, n, rec, mu_dev, nmu, kT, G, part, rows, sums)
+                 : tr_scan<TrThermal<3>>(ctx, P, n, rec, mu_dev, nmu, kT, G, part, rows, sums);
     if (rc) return rc;
     const double inv = 1.0 / (double)P.nplane;
     // out[q][j][s], q = hall, nernst, dipole_0 .. dipole_{dk - 1}
@@ -462,52 +407,31 @@ extern "C" int tbk_drude_mesh(tbk_model* m, const int32_t* mesh, int nmu, const 
     int rc = tr_levels_check("tbk_drude_mesh", nmu, mu, kT);
     if (rc) return rc;
     const int n = m->nsta, dk = m->dim_k, nq = dk * (dk + 1) / 2;
-    PlaneArgs P{};                             // one "plane": the whole mesh in k_uniform_mesh order
-    P.npts = 1;
-    for (int d = 0; d < 3; ++d) {
-        if (d < dk) TBK_REQUIRE(mesh[d] >= 1, TBK_EINVAL, "tbk_drude_mesh: mesh[%d]=%d", d, mesh[d]);
-        P.N[d] = d < dk ? mesh[d] : 1;
-        P.npts *= P.N[d];
-    }
-    P.da = 0;
-    P.db = dk > 1 ? 1 : 0;
-    P.dc = -1;
-    P.nplane = P.npts;
-    P.nslice = 1;
+    PlaneArgs P;                               // one "plane": the whole mesh in k_uniform_mesh order
+    rc = kubo_whole_mesh("tbk_drude_mesh", mesh, dk, P);
+    if (rc) return rc;
     const int64_t npts = P.npts;
     tbk_ctx* ctx = m->ctx;
     TBK_HIP(hipSetDevice(ctx->device));
-    const int G = tr_scan_groups(P, n, nmu, nq);
+    const int G = kubo_thermal_groups(P, n, nmu, nq);
     const int64_t nrows = (int64_t)nmu * nq;
-    const size_t partb = al256((size_t)nrows * G * sizeof(double)), rowb = al256((size_t)nrows * sizeof(double));
-    const size_t mub = al256((size_t)nmu * sizeof(double));
-    const size_t recb = (size_t)n * npts * sizeof(double);                       // rec[1 + nq][n][npts]: E, w^{cd}
-    const size_t vb = n > 32 ? al256((size_t)dk * recb) : 0;
     KuboChunks cw(n, dk, kubo_chunk_len(n, npts), 0, 0, 0);
-    void* base = nullptr;
-    rc = tbk_ctx_scratch(ctx, 256 + partb + rowb + mub + al256((1 + nq) * recb) + vb + cw.bytes(), &base);
+    const size_t recb = (size_t)n * npts * sizeof(double);                       // rec[1 + nq][n][npts]: E, w^{cd}
+    double *part, *rows, *mu_dev, *rec, *v_dev;
+    KuboCarve ws;
+    ws.add(part, (size_t)nrows * G * sizeof(double)), ws.add(rows, (size_t)nrows * sizeof(double)), ws.add(mu_dev, (size_t)nmu * sizeof(double));
+    ws.add(rec, (1 + nq) * recb), ws.add(v_dev, n > 32 ? dk * recb : 0), ws.add(cw.base, cw.bytes());
+    rc = kubo_carve(ctx, ws);
     if (rc) return rc;
-    unsigned char* p = (unsigned char*)base + 256;
-    double* part = (double*)p;
-    p += partb;
-    double* rows = (double*)p;
-    p += rowb;
-    double* mu_dev = (double*)p;
-    p += mub;
-    double* rec = (double*)p;
-    p += al256((1 + nq) * recb);
-    double* v_dev = vb ? (double*)p : nullptr;
-    p += vb;
-    cw.base = p;
     TBK_HIP(hipMemcpyAsync(mu_dev, mu, (size_t)nmu * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     rc = kubo_for_chunks(m, cw, nullptr, mesh, npts, [&](int64_t first, int64_t cnt, const double* kp, const double* ec, const cd* vc) -> int {
         return tr_velocity(m, kp, ec, vc, cnt, VelOut{rec, v_dev, nullptr, rec + (size_t)n * npts, first, npts});
     });
     if (rc) return rc;
     std::vector<double> sums;
-    rc = dk == 1   ? tr_scan<1, true>(ctx, P, n, rec, mu_dev, nmu, kT, G, part, rows, sums)
-         : dk == 2 ? tr_scan<2, true>(ctx, P, n, rec, mu_dev, nmu, kT, G, part, rows, sums)
-                   : tr_scan<3, true>(ctx, P, n, rec, mu_dev, nmu, kT, G, part, rows, sums);
+    rc = dk == 1   ? tr_scan<DrudeThermal<1>>(ctx, P, n, rec, mu_dev, nmu, kT, G, part, rows, sums)
+         : dk == 2 ? tr_scan<DrudeThermal<2>>(ctx, P, n, rec, mu_dev, nmu, kT, G, part, rows, sums)
+                   : tr_scan<DrudeThermal<3>>(ctx, P, n, rec, mu_dev, nmu, kT, G, part, rows, sums);
     if (rc) return rc;
     const double inv = 1.0 / (double)npts;
     for (size_t i = 0; i < (size_t)nrows; ++i) out[i] = sums[i] * inv;           // out[j][q], q over c <= d row by row

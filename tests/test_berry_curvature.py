@@ -266,6 +266,23 @@ def test_slices_of_a_3d_mesh():
 
 
 @pytest.mark.gpu
+def test_rows_beyond_the_grid_y_limit():
+    """cubic16 per band on 2 x 2 x 4100: 4100 slices of 16 bands are 65 600 rows of the plane sum, more than a grid's 65 535 in y --
+    the last 65 rows (band 15 of slice 4095, and slices 4096 to 4099) are a workgroup's second pass."""
+    m = hp.cubic16(tb.tb_model)
+    mesh = [2, 2, 4100]
+    got = m.berry_curvature_mesh(mesh, dirs=(0, 1))
+    assert got.shape == (16, 4100)
+    pick = [0, 1, 4094, 4095, 4096, 4099]
+    kk = m.k_uniform_mesh(mesh).reshape(2, 2, 4100, 3)[:, :, pick].reshape(-1, 3)
+    want = m.berry_curvature(kk, dirs=(0, 1)).reshape(16, 4, len(pick)).mean(axis=1)
+    err = np.max(np.abs(got[:, pick] - want))
+    print("rows beyond the y limit: max |mesh - list mean| = %.3e, max |list| = %.3e" % (err, np.max(np.abs(want))))
+    assert err < 1e-9
+    np.testing.assert_array_equal(got, m.berry_curvature_mesh(mesh, dirs=(0, 1)))
+
+
+@pytest.mark.gpu
 def test_list_and_mesh_forms_agree_and_repeat():
     for m, mesh, occ in [(haldane(), [64, 64], [0]), (hp.kane_mele(tb.tb_model), [32, 32], [0, 1]),
                          (supercell(haldane(), 3), [16, 16], list(range(9)))]:

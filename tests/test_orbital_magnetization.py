@@ -233,6 +233,28 @@ def test_mesh_forms_against_numpy(name):
 
 
 @pytest.mark.gpu
+def test_kt_scan_of_two_tiles_in_any_order():
+    """321 unsorted levels with two repeats on cubic16, slices along axis 1: two tiles of the thermal scan, the second with one full
+    wavefront, one that holds a single level and two without a level.  A level's result does not depend on where it stands."""
+    m = hp.cubic16(tb.tb_model)
+    mesh, dirs, kT = [6, 5, 4], (2, 0), 0.05
+    e, mom, om = omr.moments(m, m.k_uniform_mesh(mesh), dirs)
+    rng = np.random.default_rng(5)
+    lv = rng.uniform(e.min() - 0.3, e.max() + 0.3, 319)
+    levels = rng.permutation(np.concatenate([lv, lv[:2]]))
+    assert len(levels) == 321 and len(np.unique(levels)) == 319 and np.any(np.diff(levels) < 0)
+    base = m.orbital_magnetization_mesh(mesh, fermi_levels=levels, kT=kT, dirs=dirs)
+    assert base.shape == (321, mesh[1])
+    eight = np.array([0, 63, 255, 256, 257, 319, 320, 128])
+    scale = np.max(np.abs(mom)) + np.max(np.abs(om)) * (np.max(np.abs(levels)) + np.max(np.abs(e)))
+    close(base[eight], omr.plane_means(omr.scan_kt(e, mom, om, levels[eight], kT), mesh, dirs), scale)
+    for idx in (rng.permutation(321), np.concatenate([rng.permutation(321)[:65], [7, 7, 320]]), np.array([320]), np.arange(256, 321)):
+        got = m.orbital_magnetization_mesh(mesh, fermi_levels=levels[idx], kT=kT, dirs=dirs)
+        assert got.shape == (len(idx), mesh[1])
+        np.testing.assert_array_equal(np.ascontiguousarray(got).view(np.uint64), np.ascontiguousarray(base[idx]).view(np.uint64))
+
+
+@pytest.mark.gpu
 def test_streda_in_the_haldane_gap():
     m = haldane()
     mesh = [64, 64]
