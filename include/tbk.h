@@ -501,6 +501,27 @@ int tbk_kpm_apply_series(tbk_sparse* sp, const double* k, int64_t nk, int ncoef,
                          double emax, int nvec, const double* vectors, const int32_t* states, uint64_t seed, double* out);
 int tbk_kpm_marker(tbk_sparse* sp, int ncoef, const double* coeffs, double emin, double emax, const double* da, const double* db,
                    int nvec, const int32_t* states, double* out);
+/* ---- kernel polynomial method: eigenpairs in an energy window ------------------------------------------
+ * All eigenpairs of the sparse H(k) with e_lo <= E <= e_hi, for any number of states, by Chebyshev-filtered subspace iteration: the
+ * n_search random-phase vectors number 0 .. n_search - 1 of `seed` (scaled by 1 / sqrt(nsta)) are filtered with the Jackson-damped
+ * series of degree `degree` of the indicator of [e_lo - delta, e_hi + delta], delta = 2 pi a / degree, orthonormalised through their
+ * Gram matrix (directions at or below 1e-12 of its largest eigenvalue are dropped), and rotated to Ritz vectors; a Ritz pair counts
+ * when the norm tau of its filtered vector is >= 1/2 (a mixture of states on both sides of the window has a smaller one).  The call
+ * returns when every counting pair inside the window has |H x - theta x| <= tol a AND fewer pairs count than the subspace has
+ * directions; at least two filter applications are made.  k: dim_k doubles (dim_k = 0: ignored); H~, a and the bounds as in
+ * tbk_kpm_moments.  n_search: a multiple of 8 in [8, min(nsta rounded down to 8, 2048)]; it must exceed the number of states in
+ * the widened window.  Results: *n_found = m, eval[m] ascending, evec[m][nsta] c128 orthonormal, resid[m] (nullable); the arrays
+ * have room for n_search entries.  info[4]: filter applications made, directions kept in the last orthonormalisation, pairs with
+ * tau >= 1/2, pairs returned.  m = 0 is a valid answer.
+ * TBK_EINVAL: an empty window (e_lo > e_hi) or one not inside (emin, emax), a bad n_search, degree (2 .. 65536), tol or max_iter
+ * (< 2); bounds that do not contain the spectrum (the message of tbk_kpm_apply_series).  TBK_ENOCONV, nothing returned: the
+ * subspace is saturated -- as many pairs count as it has directions, states may be missing; the message says "raise n_search" and
+ * names the count -- or, after max_iter filter applications, a counting pair inside the window misses tol (the message names the
+ * worst residual).  TBK_ENOMEM, naming the byte count, when the device workspace (3 n_search nsta 16 bytes for X, Y, H Y, the two
+ * vectors of a series, the Gram sums and three n_search^2 matrices) cannot be had.  (degree + 2) n_search / 8 sparse products of
+ * 8 vectors per filter application.  Fixed-order sums, no atomics on floating-point data: bit-reproducible.                      */
+int tbk_kpm_eigs(tbk_sparse* sp, const double* k, double e_lo, double e_hi, double emin, double emax, int n_search, int degree,
+                 double tol, int max_iter, uint64_t seed, int* n_found, double* eval, double* evec, double* resid, int32_t* info);
 
 /* ---- multi-GPU: one process per GPU, k-points sharded, one gather ------
  * Thin RCCL wrappers (librccl is dlopen'ed on first use).  The 128-byte id is

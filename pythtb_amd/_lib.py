@@ -128,6 +128,8 @@ SIGNATURES = {
     "tbk_kpm_double_moments": (_i, [_p, _dp, _i64, _i, C.c_double, C.c_double, _i, _i, _i, _dp, _ip, C.c_uint64, _dp]),
     "tbk_kpm_apply_series": (_i, [_p, _dp, _i64, _i, _i, _dp, C.c_double, C.c_double, _i, _dp, _ip, C.c_uint64, _dp]),
     "tbk_kpm_marker": (_i, [_p, _i, _dp, C.c_double, C.c_double, _dp, _dp, _i, _ip, _dp]),
+    "tbk_kpm_eigs": (_i, [_p, _dp, C.c_double, C.c_double, C.c_double, C.c_double, _i, _i, C.c_double, _i, C.c_uint64,
+                          C.POINTER(C.c_int), _dp, _dp, _dp, _ip]),
     "tbk_sparse_velocity_bounds_host": (_i, [_i, _i, _i, _dp, _dp, _i64, _ip, _ip, _ip, _dp, _dp]),
     "tbk_comm_unique_id":(_i, [C.POINTER(C.c_ubyte)]),
     "tbk_comm_init": (_i, [_p, C.POINTER(C.c_ubyte), _i, _i]),

@@ -1,9 +1,10 @@
 // tbk_kpm.h -- what the translation units of the kernel polynomial method share (tbk_kpm.hip: the operator and the single moments;
 // tbk_kpm_cond.hip: the double moments of the Kubo-Bastin conductivity; tbk_kpm_series.hip: operator functions and the local Chern
-// marker): the operator's handle, the random-phase generator, the fixed-order sums, the values of the operator at a k-point, the
-// row mapping, the sparse row product and the one Chebyshev step kernel; on the host the argument checks, the launch plan, the
-// workspace carving, the start vectors and the driver of the steps.  Templates and static functions: the library has no
-// relocatable device code.  DESIGN.md sections 21 to 24.
+// marker; tbk_kpm_eigs.hip: eigenpairs in an energy window): the operator's handle, the random-phase generator, the fixed-order
+// sums, the values of the operator at a k-point, the row mapping, the sparse row product and the one Chebyshev step kernel; on the
+// host the argument checks, the launch plan, the workspace carving, the start vectors and the driver of the steps; and the series
+// f(H) v of tbk_kpm_series.hip, which tbk_kpm_eigs.hip filters with: its epilogue, guard and gather kernels and its driver.
+// Templates and static functions: the library has no relocatable device code.  DESIGN.md sections 21 to 25.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -170,7 +171,8 @@ __global__ __launch_bounds__(256) void k_kpm_values(const int64_t nnz, const int
 }
 
 // What a step does with the new value nw of (row, v) besides storing it (x0 is cur's element): row<NV, FIRST>() may add to the
-// row-local sums (dA, dB), which go to `part` through kpm_block_sums where SUMS is set.  tbk_kpm_series.hip has a third policy.
+// row-local sums (dA, dB), which go to `part` through kpm_block_sums where SUMS is set.  KpmSeriesTerm (below) and KpmResid
+// (tbk_kpm_eigs.hip) are two more.
 struct KpmDots {   // A = <nw|nw>, B = Re <nw|cur>
     static constexpr bool SUMS = true;
     double* part;
@@ -212,6 +214,102 @@ __global__ __launch_bounds__(256) void k_kpm_step(const int nsta, const int64_t*
         epi.template row<NV, FIRST>(nsta, row, v, x0, nw, dA, dB);
     });
     if constexpr (Epi::SUMS) kpm_block_sums<NV>(dA, dB, epi.part);
+}
+
+// ------------------------------------------------------------------ series (tbk_kpm_series.hip, tbk_kpm_eigs.hip)
+#define KPMS_GUARD 5                         // doubles of the guard record: flag, <T_j v|T_j v>, <v|v>, sample, vector
+
+// The epilogue of k_kpm_step that adds the term of step j to every series: acc[s][row][NV] += coef[s][j] nw, s ascending; FIRST
+// (j = 1) writes acc[s] = coef[s][0] cur + coef[s][1] nw instead.  part: the row-local sums of <nw|nw> (the second slot stays zero).
+struct KpmSeriesTerm {
+    static constexpr bool SUMS = true;
+    int nset, ncoef, j;
+    const cd* coef;
+    cd* acc;
+    double* part;
+    template <int NV, bool FIRST>
+    __device__ __forceinline__ void row(const int nsta, const int64_t row, const int v, const cd x0, const cd nw, double& dA, double&) const {
+        add<NV, FIRST>(nset, ncoef, j, coef, acc, nsta, row, v, x0, nw);
+        dA += cabs2(nw);
+    }
+    // a function of its own for the __restrict__ of its arguments, which a member cannot carry: with it the coefficients come
+    // through scalar loads
+    template <int NV, bool FIRST>
+    static __device__ __forceinline__ void add(const int nset, const int ncoef, const int j, const cd* __restrict__ coef,
+                                               cd* __restrict__ acc, const int nsta, const int64_t row, const int v, const cd x0,
+                                               const cd nw) {
+        for (int s = 0; s < nset; ++s) {
+            cd* dst = acc + ((int64_t)s * nsta + row) * NV + v;
+            cd t = FIRST ? cmul_x(coef[(int64_t)s * ncoef], x0) : *dst;
+            cfma_x(t, coef[(int64_t)s * ncoef + j], nw);
+            *dst = t;
+        }
+    }
+};
+
+// ncoef = 1: acc[s][row][NV] = coef[s][0] cur, no sparse product; a lane per element
+static __global__ __launch_bounds__(256) void k_kpm_series_const(const int64_t len, const int nset, const int ncoef, const cd* __restrict__ coef,
+                                                          const cd* __restrict__ cur, cd* __restrict__ acc) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < len; i += (int64_t)gridDim.x * 256) {
+        const cd x = cur[i];
+        for (int s = 0; s < nset; ++s) acc[(int64_t)s * len + i] = cmul_x(coef[(int64_t)s * ncoef], x);
+    }
+}
+
+// The guard of one series: dots[step][2][NV] holds A_step = <T_step v|T_step v> per vector, A_0 = <v|v>.  The largest A per vector
+// (a NaN counts as infinite) against (1 + 1e-6) A_0; the first violation of a call is recorded in rec = (1, A, A_0, sample, vector).
+// One workgroup; the launches of a call are ordered on the stream, so "first" is the same in every run.
+template <int NV>
+__global__ __launch_bounds__(256) void k_kpm_series_guard(const int nstep, const double* __restrict__ dots, const double sample,
+                                                          double* __restrict__ rec) {
+    constexpr int NC = 2 * NV, G = 256 / NV;
+    const int v = threadIdx.x % NV, g = threadIdx.x / NV;
+    double mx = 0.0;
+    for (int s = g; s < nstep; s += G) {
+        const double A = dots[(int64_t)s * NC + v];
+        mx = fmax(mx, A == A ? A : INFINITY);
+    }
+    __shared__ double red[G][NV];
+    red[g][v] = mx;
+    __syncthreads();
+    if (threadIdx.x == 0 && rec[0] == 0.0)
+        for (int u = 0; u < NV; ++u) {
+            double t = red[0][u];
+            for (int i = 1; i < G; ++i) t = fmax(t, red[i][u]);
+            const double a0 = dots[u];
+            if (!(t <= (1.0 + 1e-6) * a0)) {
+                rec[0] = 1.0;
+                rec[1] = t;
+                rec[2] = a0;
+                rec[3] = sample;
+                rec[4] = (double)u;
+                break;
+            }
+        }
+}
+
+// out[s][v][nsta] = acc[s][row][v], v < nv: a tile of 32 rows x NV vectors through LDS, so that both sides move whole segments.
+// grid (row tiles, sets); out is the slice of this block of vectors, set_stride elements between two sets.
+template <int NV>
+__global__ __launch_bounds__(256) void k_kpm_series_gather(const int nsta, const int nv, const int64_t set_stride,
+                                                           const cd* __restrict__ acc, cd* __restrict__ out) {
+    constexpr int RPB = 256 / NV;
+    __shared__ cd t[NV][RPB + 1];
+    const int64_t ntiles = ((int64_t)nsta + RPB - 1) / RPB;
+    const int s = blockIdx.y;
+    for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        const int64_t row0 = tile * RPB;
+        {
+            const int r = threadIdx.x / NV, v = threadIdx.x % NV;
+            if (row0 + r < nsta) t[v][r] = acc[((int64_t)s * nsta + row0 + r) * NV + v];
+        }
+        __syncthreads();
+        {
+            const int v = threadIdx.x / RPB, r = threadIdx.x % RPB;
+            if (v < nv && row0 + r < nsta) out[(int64_t)s * set_stride + (int64_t)v * nsta + row0 + r] = t[v][r];
+        }
+        __syncthreads();
+    }
 }
 
 // ------------------------------------------------------------------ host
@@ -343,4 +441,67 @@ static int kpm_run_steps(tbk_ctx* ctx, const KpmPlan& P, int nsteps, cd* cur, cd
             return rc;
         },
         [&](int first, int count) { return kpm_reduce(ctx, P.nwg, count, part, dots + (size_t)first * 2 * KPM_NV); });
+}
+
+// ------------------------------------------------------------------ series, host
+// One series for a block of NV vectors.  On entry `cur` holds the start vectors and slot 0 of `part` the partial sums of their
+// norms; on return (of the launches) acc[s][row][NV] holds sum_m coef[s][m] T_m(H~) cur and the guard has seen every norm.
+struct KpmSeries {
+    tbk_ctx* ctx;
+    const tbk_sparse* sp;
+    KpmPlan plan;
+    int nset, ncoef;
+    double b, inv_a;
+    const cd* coef;      // device, [nset][ncoef]
+    cd *cur, *prev;
+    double *part, *dots, *rec;
+};
+
+static int kpm_series_run(const KpmSeries& S, const cd* val, cd* acc, double sample) {
+    constexpr int NV = KPM_NV;
+    tbk_ctx* ctx = S.ctx;
+    const int n = S.sp->nsta, nsteps = S.ncoef - 1, nwg = S.plan.nwg;
+    if (nsteps == 0) {
+        ProfScope ps(ctx, "kpm_series_const");
+        hipLaunchKernelGGL(k_kpm_series_const, dim3(kpm_stream_grid((int64_t)n * NV)), dim3(256), 0, ctx->stream, (int64_t)n * NV, S.nset,
+                           S.ncoef, S.coef, S.cur, acc);
+        TBK_HIP(hipGetLastError());
+    }
+    int rc = kpm_run_steps(ctx, S.plan, nsteps, S.cur, S.prev, S.part, S.dots, [&](int j, const cd* x, cd* y, double* pj) {
+        const KpmSeriesTerm term{S.nset, S.ncoef, j, S.coef, acc, pj};
+        ProfScope ps(ctx, "kpm_series_step");
+        if (j == 1)
+            hipLaunchKernelGGL((k_kpm_step<NV, true, KpmSeriesTerm>), dim3(nwg), dim3(256), 0, ctx->stream, n, S.sp->row_ptr, S.sp->col, val,
+                               x, nullptr, y, S.b, S.inv_a, term);
+        else
+            hipLaunchKernelGGL((k_kpm_step<NV, false, KpmSeriesTerm>), dim3(nwg), dim3(256), 0, ctx->stream, n, S.sp->row_ptr, S.sp->col, val,
+                               x, nullptr, y, S.b, S.inv_a, term);
+        TBK_HIP(hipGetLastError());
+        return TBK_OK;
+    });
+    if (rc) return rc;
+    ProfScope ps(ctx, "kpm_series_guard");
+    hipLaunchKernelGGL((k_kpm_series_guard<NV>), dim3(1), dim3(256), 0, ctx->stream, nsteps + 1, S.dots, sample, S.rec);
+    TBK_HIP(hipGetLastError());
+    return TBK_OK;
+}
+
+// the verdict of the guard record after the call's synchronisation
+static int kpm_series_verdict(const char* who, const double* rec, const tbk_sparse* sp, double emin, double emax) {
+    if (rec[0] == 0.0) return TBK_OK;
+    tbk_set_error("%s: <T_j v|T_j v> reaches %g for vector %lld of sample %lld, beyond <v|v> = %g: the bounds (%.17g, %.17g) do not "
+                  "contain the spectrum (Gershgorin interval of this operator: (%.17g, %.17g))",
+                  who, rec[1], (long long)rec[4], (long long)rec[3], rec[2], emin, emax, sp->gmin, sp->gmax);
+    return TBK_EINVAL;
+}
+
+template <class Layout>
+static int kpm_series_workspace(const char* who, tbk_ctx* ctx, Layout&& layout) {
+    size_t total;
+    int rc = kpm_workspace(ctx, layout, &total);
+    if (rc == TBK_ENOMEM) {
+        (void)hipGetLastError();
+        tbk_set_error("%s: no device workspace of %zu bytes", who, total);
+    }
+    return rc;
 }

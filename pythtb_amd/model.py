@@ -193,6 +193,35 @@ def kpm_fermi_coefficients(fermi_level, n_moments, bounds, kernel="jackson", lam
     return c * g
 
 
+def kpm_window_coefficients(window, n_terms, bounds, kernel="jackson", lam=4.0):
+    """Extension: the Chebyshev coefficients of the indicator function of `window` = (e_lo, e_hi), float `(n_terms,)`: with them
+    `tb_model.kpm_apply` applies the spectral projector on the window, smoothed by the kernel.  Analytic,
+
+        c_0 = (theta_lo - theta_hi) / pi,   c_m = 2 (sin(m theta_lo) - sin(m theta_hi)) / (m pi),   theta = arccos((e - b) / a),
+
+    times the kernel factors g_m ("jackson" by default: each edge is smoothed over ~ pi a / n_terms, the value at an edge is
+    1/2, and there are no Gibbs oscillations).  The window must lie inside the open interval of `bounds` = (emin, emax) with
+    e_lo <= e_hi; a, b as in `kpm_coefficients`.  `tb_model.kpm_eigs` filters with these coefficients of its widened window."""
+    if not _is_int(n_terms) or n_terms < 1:
+        raise Exception("\n\nkpm_window_coefficients: n_terms must be a positive integer")
+    emin, emax = float(bounds[0]), float(bounds[1])
+    if not emax > emin:
+        raise Exception("\n\nkpm_window_coefficients: bounds must be (emin, emax) with emin < emax")
+    w = np.array(window, dtype=float)
+    if w.shape != (2,) or not np.all(np.isfinite(w)) or w[0] > w[1]:
+        raise Exception("\n\nkpm_window_coefficients: window must be (e_lo, e_hi), finite, with e_lo <= e_hi")
+    if not (emin < w[0] and w[1] < emax):
+        raise Exception("\n\nkpm_window_coefficients: window must lie inside the open interval (%.12g, %.12g)" % (emin, emax))
+    g = _kpm_kernel(int(n_terms), kernel, lam, "kpm_window_coefficients")
+    a, b = 0.5 * (emax - emin), 0.5 * (emax + emin)
+    tlo, thi = np.arccos((w[0] - b) / a), np.arccos((w[1] - b) / a)
+    m = np.arange(1, int(n_terms), dtype=float)
+    c = np.empty(int(n_terms))
+    c[0] = (tlo - thi) / np.pi
+    c[1:] = 2.0 * (np.sin(m * tlo) - np.sin(m * thi)) / (m * np.pi)
+    return c * g
+
+
 def _kpm_evolution_coefficients(z):
     """(2 - delta_m0) (-i)^m J_m(z), cut after the last modulus above 1e-17: e^{-i z cos(theta)} = sum_m of these times cos(m theta),
     so its discrete Fourier transform over theta_j = 2 pi j / N gives (-i)^m J_m(z) up to the aliases J_{N -+ m}(z); N is a power of
@@ -1886,6 +1915,70 @@ class tb_model(object):
         _lib.check(_lib.lib.tbk_kpm_marker(sp, len(c), _lib.dptr(c), emin, emax, _lib.dptr(da), _lib.dptr(db), nvec, _lib.iptr(st),
                                            _lib.dptr(out.view(float))))
         return 4.0 * np.pi * out.imag
+
+    def kpm_eigs(self, window, n_search=64, k_point=None, degree=None, tol=1e-10, max_iter=40, seed=0, bounds=None,
+                 return_info=False):
+        """Extension: all eigenvalues and eigenvectors of the sparse H(k) inside `window` = (e_lo, e_hi), for models of any size
+        (edge states of a flake or ribbon past the dense limit of `solve_all`): Chebyshev-filtered subspace iteration (Pieper
+        et al., J. Comput. Phys. 325, 226) on the operator of `kpm_moments`.  The dense model is never built.  Returns
+        `(evals, evecs)`: evals float `(m,)` ascending, evecs complex `(m, norb)` (`(m, norb, 2)` for nspin = 2) -- the layout
+        of `solve_one(k_point, eig_vectors=True)`, orthonormal; m = 0 is a valid answer.
+
+        The contract: the call returns every eigenpair with e_lo <= E <= e_hi, or it raises -- never a part of them.
+        `n_search` random-phase vectors of `seed` are filtered with the series of `kpm_window_coefficients` (Jackson kernel,
+        `degree` + 1 terms) of the window widened by 2 pi a / degree on each side, orthonormalised, and rotated to Ritz
+        vectors, until every pair inside the window has |H x - E x| <= tol a, a = (emax - emin) / 2.  `n_search` (a multiple of
+        8, at most the number of states rounded down to 8 and 2048) must exceed the number of states in the WIDENED window:
+        `nsta * kpm_dos` integrated over it estimates that number.  When as many Ritz vectors pass the filter as the subspace has
+        directions the call raises ("raise n_search"): states could be missing.  It also raises when `max_iter` filter
+        applications (at least 2) do not reach `tol`; a larger `degree` separates the window from its neighbours faster.
+
+        degree=None: ceil(8 a / (e_hi - e_lo)) clipped to [64, 4096] -- chosen from a NumPy prototype of the algorithm (3 to 13
+        filter applications on flakes and chains of 63 to 2112 states), not from a timing.  bounds as in `kpm_moments`
+        (None: the Gershgorin interval widened by 1 %; bounds that do not contain the spectrum raise).  k_point: one k-vector,
+        None for dim_k = 0.  return_info=True adds a dict: `residuals` `(m,)`, `applications`, `rank`, `strong` (pairs with
+        filter norm >= 1/2), `returned`, `degree`, `bounds`.  Fixed-order sums on the device: two calls give the same bits."""
+        w = np.array(window, dtype=float)
+        if w.shape != (2,) or not np.all(np.isfinite(w)) or w[0] > w[1]:
+            raise Exception("\n\nkpm_eigs: window must be (e_lo, e_hi), finite, with e_lo <= e_hi")
+        n = self._nsta
+        top = min(n - n % 8, 2048)
+        if not _is_int(n_search) or n_search < 8 or n_search % 8 != 0 or n_search > top:
+            raise Exception("\n\nkpm_eigs: n_search must be a multiple of 8 in [8, %d] for this model of %d states" % (top, n))
+        if degree is not None and (not _is_int(degree) or not 2 <= degree <= 65536):
+            raise Exception("\n\nkpm_eigs: degree must be an integer in [2, 65536] or None")
+        if not np.isfinite(tol) or not tol > 0.0:
+            raise Exception("\n\nkpm_eigs: tol must be positive")
+        if not _is_int(max_iter) or max_iter < 2:
+            raise Exception("\n\nkpm_eigs: max_iter must be an integer of at least 2")
+        if not _is_int(seed) or not 0 <= seed < 2 ** 64:
+            raise Exception("\n\nkpm_eigs: seed must be an integer in [0, 2^64)")
+        bounds = self._kpm_bounds_arg(bounds)
+        k, _ = self._kpm_k(None if k_point is None else [k_point])
+        sp = self._sparse_model()
+        emin, emax = self._kpm_bounds(bounds, sp)
+        if not (emin < w[0] and w[1] < emax):
+            raise Exception("\n\nkpm_eigs: window must lie inside the open interval of the bounds (%.12g, %.12g)" % (emin, emax))
+        if degree is None:
+            width = w[1] - w[0]
+            degree = 4096 if width <= 0.0 else int(min(4096, max(64, np.ceil(4.0 * (emax - emin) / width))))
+        ns = int(n_search)
+        nfound = C.c_int(0)
+        ev = np.zeros(ns)
+        vec = np.empty((ns, n), dtype=complex)
+        res = np.zeros(ns)
+        inf = np.zeros(4, dtype=np.int32)
+        _lib.check(_lib.lib.tbk_kpm_eigs(sp, _lib.dptr(k), float(w[0]), float(w[1]), emin, emax, ns, int(degree), float(tol),
+                                         int(max_iter), int(seed), C.byref(nfound), _lib.dptr(ev), _lib.dptr(vec.view(float)),
+                                         _lib.dptr(res), _lib.iptr(inf)))
+        m = nfound.value
+        evals, evecs = ev[:m].copy(), vec[:m].copy()
+        if self._nspin == 2:
+            evecs = evecs.reshape(m, self._norb, 2)
+        if not return_info:
+            return evals, evecs
+        return evals, evecs, dict(residuals=res[:m].copy(), applications=int(inf[0]), rank=int(inf[1]), strong=int(inf[2]),
+                                  returned=int(inf[3]), degree=int(degree), bounds=(emin, emax))
 
     # ------------------------------------------------------------------ k generators (host)
     def k_uniform_mesh(self, mesh_size):
