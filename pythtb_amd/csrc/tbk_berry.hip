@@ -710,7 +710,7 @@ int tbk_flux_flush_pending(tbk_wfs* w, bool arm) {
     ProfScope ps(ctx, "flux_reduce");
     w->flux_done = (arm && w->flux_totals_host) ? tbk_done_arm(ctx, false) : DoneArgs{nullptr, nullptr, nullptr, 0u};
     hipLaunchKernelGGL(k_flux_reduce, dim3((unsigned)w->flux_pend_nslices), dim3(1024), 0, ctx->stream,
-                       (const double*)w->flux_partial_dev, w->flux_pend_n, w->flux_totals_dev, w->flux_done);
+                       (const double*)w->flux_partial.p, w->flux_pend_n, w->flux_totals_dev, w->flux_done);
     w->flux_pend_n = 0;
     w->flux_pend_nslices = 0;
     TBK_HIP(hipGetLastError());
@@ -790,37 +790,47 @@ static bool lanes_dets_applies(const WfsView& v, int nocc, size_t lds_max);
 static int lanes_link_dets(tbk_wfs* w, const int32_t* occ, int nocc, int dir, cd* dets_out);          // (tbk_berry_lanes.inl kernels, OUT = 2)
 static bool chain_wave_applies(const WfsView& v, int nocc);
 
-extern "C" int tbk_berry_flux_async(tbk_wfs* w, const int32_t* occ, int nocc, int dir0, int dir1,
-                                    int want_plaq) {
+// ---- tbk_berry_flux_async in steps: what one call launches (FluxPlan), the buffers it writes (tbk_flux_buffers, shared with the
+// fused mesh solve), one launch function per route, and the sum of the partials (flux_sum_partials).
+struct FluxPlan {
+    FluxArgs A;
+    FluxSliceArgs SL;
+    int64_t nslices, per;     // planes (dir0, dir1) in the array, plaquettes per plane
+    bool big;                 // link determinants by LU, a workgroup per link (tbk_berry_big.inl)
+    bool rows, slices_k;      // register-resident row-streaming kernel (up to 4 components); its form with the lanes along the slices
+    bool lanes_flux;          // link determinants by the LDS-tile kernels of tbk_berry_lanes.inl
+};
+
+// step 1: the arguments (pythtb.py:3126-3130), and which determinant route the band count takes -- that decides how `occ` is held
+static int flux_check_args(tbk_wfs* w, const int32_t* occ, int nocc, int dir0, int dir1, FluxPlan& P) {
     TBK_REQUIRE(w, TBK_EINVAL, "tbk_berry_flux: null wfs");
     const WfsView& v = w->view;
-    // pythtb.py:3126-3130
     TBK_REQUIRE(dir0 != dir1, TBK_EINVAL, "Need to specify two different directions for Berry flux calculation.");
     TBK_REQUIRE(dir0 >= 0 && dir1 >= 0 && dir0 < v.dim_arr && dir1 < v.dim_arr, TBK_EINVAL,
                 "Direction for Berry flux calculation out of bounds.");
-    FluxArgs A{};
     int det_from = 9;      // up to 8 bands the register LU per thread wins; from 9 the workgroup-per-link LU is 4-100x faster (profiles/det_big_probe.py)
     if (tbk_knobs().det_big_from >= 0) det_from = std::max(2, tbk_knobs().det_big_from);
-    const bool big = nocc >= det_from;        // link determinants by LU (tbk_berry_big.inl)
-    int rc = big ? check_occ(w, occ, nocc) : fill_occ(w, occ, nocc, A.occ);
-    if (rc) return rc;
-    tbk_ctx* ctx = w->ctx;
-    TBK_HIP(hipSetDevice(ctx->device));
-    // this call rewrites the partials and the totals: a reduction still pending from the call before is launched first
-    rc = tbk_flux_flush_pending(w, false);
-    if (rc) return rc;
+    P.big = nocc >= det_from;
+    return P.big ? check_occ(w, occ, nocc) : fill_occ(w, occ, nocc, P.A.occ);
+}
+
+// step 2: the geometry -- FluxArgs, FluxSliceArgs and the route
+static int flux_geometry(const tbk_wfs* w, int nocc, int dir0, int dir1, int want_plaq, FluxPlan& P) {
+    const WfsView& v = w->view;
+    const tbk_ctx* ctx = w->ctx;
+    FluxArgs& A = P.A;
     A.v = v;
     A.nocc = nocc;
     A.n0 = v.mesh[dir0] - 1;
     A.n1 = v.mesh[dir1] - 1;
     A.s0 = v.stride[dir0];
     A.s1 = v.stride[dir1];
-    int64_t nslices = 1;
-    other_axes(v, dir0, dir1, &A.other, &nslices);
-    const int64_t per = (int64_t)A.n0 * A.n1;
-    TBK_REQUIRE(per < (int64_t)0xffffffffu, TBK_EUNSUPPORTED, "plane of %lld plaquettes is too large", (long long)per);
-    const bool rows = !big && v.ncomp <= 4 && nocc <= v.ncomp;   // register-resident row-streaming kernel
-    if (rows) {
+    other_axes(v, dir0, dir1, &A.other, &P.nslices);
+    const int64_t nslices = P.nslices;
+    P.per = (int64_t)A.n0 * A.n1;
+    TBK_REQUIRE(P.per < (int64_t)0xffffffffu, TBK_EUNSUPPORTED, "plane of %lld plaquettes is too large", (long long)P.per);
+    P.rows = !P.big && v.ncomp <= 4 && nocc <= v.ncomp;
+    if (P.rows) {
         A.swap = A.s0 < A.s1;                            // lanes run along the smaller stride
         A.na = A.swap ? A.n1 : A.n0;
         A.nb = A.swap ? A.n0 : A.n1;
@@ -837,14 +847,14 @@ extern "C" int tbk_berry_flux_async(tbk_wfs* w, const int32_t* occ, int nocc, in
         if (tbk_knobs().flux_ti >= 0) A.ti = std::max(1, tbk_knobs().flux_ti);
         A.bps = ((A.na + A.ti - 1) / A.ti) * A.ncolw;
     } else {
-        A.bps = (int)((per + 255) / 256);
+        A.bps = (int)((P.per + 255) / 256);
     }
     // planes without the fastest mesh axis: lanes along the slices (k_flux_slices; TBK_FLUX_SLICES=0: the row kernel)
-    FluxSliceArgs SL{};
+    FluxSliceArgs& SL = P.SL;
     const int Dm = v.dim_arr;
-    const bool slices_k = rows && !want_plaq && Dm >= 3 && dir0 != Dm - 1 && dir1 != Dm - 1 && v.mesh[Dm - 1] >= 16 &&
-                          tbk_knobs().flux_slices != 0;
-    if (slices_k) {
+    P.slices_k = P.rows && !want_plaq && Dm >= 3 && dir0 != Dm - 1 && dir1 != Dm - 1 && v.mesh[Dm - 1] >= 16 &&
+                 tbk_knobs().flux_slices != 0;
+    if (P.slices_k) {
         SL.nfast = v.mesh[Dm - 1];
         SL.ngrp = (SL.nfast + 63) / 64;
         const int64_t rows_w = (nslices / SL.nfast) * SL.ngrp * A.n0;      // wavefronts with one run per row
@@ -863,172 +873,169 @@ extern "C" int tbk_berry_flux_async(tbk_wfs* w, const int32_t* occ, int nocc, in
     A.ablate = tbk_knobs().ablate_flux;
 #endif
     TBK_REQUIRE(nslices * A.bps < (int64_t)0x7fffffff, TBK_EUNSUPPORTED, "too many plaquette blocks");
-    if (w->flux_nslices_cap < nslices) {
+    P.lanes_flux = !P.big && !P.rows && lanes_dets_applies(v, nocc, TBK_LANES_FLUX_LDS_MAX) && tbk_knobs().chain_wave != 2;
+    return TBK_OK;
+}
+
+// step 3: the buffers of a flux launch (tbk_internal.h), also what the fused mesh solve writes its flux through
+int tbk_flux_buffers(tbk_wfs* w, int64_t nslices, int64_t npartial, int64_t nplaq) {
+    tbk_ctx* ctx = w->ctx;
+    const size_t cnt_bytes = (size_t)nslices * 16 * sizeof(unsigned);
+    if (cnt_bytes > w->flux_cnt.bytes) {
+        // the totals are sized with the counters: the counters are emptied first, so that a failure on the way leaves both to
+        // be made again by the next call
         TBK_HIP(hipStreamSynchronize(ctx->stream));
-        if (w->flux_cnt_dev) TBK_HIP(hipFree(w->flux_cnt_dev));
-        w->flux_cnt_dev = nullptr;
-        w->flux_nslices_cap = 0;
-        {
-            const int rct = tbk_wfs_totals_alloc(w, nslices);
-            if (rct) return rct;
-        }
-        TBK_HIP(hipMalloc((void**)&w->flux_cnt_dev, nslices * 16 * sizeof(unsigned)));
-        TBK_HIP(hipMemsetAsync(w->flux_cnt_dev, 0, nslices * 16 * sizeof(unsigned), ctx->stream));
-        w->flux_nslices_cap = nslices;
+        tbk_devbuf_free(w->flux_cnt);
+        int rc = tbk_wfs_totals_alloc(w, nslices);
+        if (rc) return rc;
+        rc = tbk_devbuf_grow(ctx->stream, w->flux_cnt, cnt_bytes, "tbk_berry_flux: slice counters");
+        if (rc) return rc;
+        TBK_HIP(hipMemsetAsync(w->flux_cnt.p, 0, cnt_bytes, ctx->stream));
     }
     w->flux_nslices = nslices;
-    A.counters = w->flux_cnt_dev;
-    A.totals = w->flux_totals_dev;
-    if (w->flux_partial_cap < nslices * A.bps) {
-        TBK_HIP(hipStreamSynchronize(ctx->stream));
-        if (w->flux_partial_dev) TBK_HIP(hipFree(w->flux_partial_dev));
-        w->flux_partial_dev = nullptr;
-        TBK_HIP(hipMalloc((void**)&w->flux_partial_dev, nslices * A.bps * sizeof(double)));
-        w->flux_partial_cap = nslices * A.bps;
-    }
+    int rc = tbk_devbuf_grow(ctx->stream, w->flux_partial, (size_t)npartial * sizeof(double), "tbk_berry_flux: flux partials");
+    if (rc) return rc;
     w->flux_plaq_n = 0;
-    if (want_plaq) {
-        if (w->flux_plaq_cap < nslices * per) {
-            TBK_HIP(hipStreamSynchronize(ctx->stream));
-            if (w->flux_plaq_dev) TBK_HIP(hipFree(w->flux_plaq_dev));
-            w->flux_plaq_dev = nullptr;
-            hipError_t e = hipMalloc((void**)&w->flux_plaq_dev, nslices * per * sizeof(double));
-            if (e != hipSuccess) {
-                w->flux_plaq_cap = 0;
-                tbk_set_error("tbk_berry_flux: plaquette buffer of %lld doubles: %s", (long long)(nslices * per),
-                              hipGetErrorString(e));
-                return TBK_ENOMEM;
-            }
-            w->flux_plaq_cap = nslices * per;
-        }
-        w->flux_plaq_n = nslices * per;
-        A.plaq = w->flux_plaq_dev;
-    }
-    A.partial = w->flux_partial_dev;
-    const bool lanes_flux = !big && !rows && lanes_dets_applies(v, nocc, TBK_LANES_FLUX_LDS_MAX) && tbk_knobs().chain_wave != 2;
-    if (!big && (chain_wave_applies(v, nocc) || lanes_flux)) {
-        // 5..8 bands of wide states: every lane of the plaquette kernel would walk its own 256-byte rows; instead the link
-        // determinants along both directions come from the wave-per-string kernels (coalesced), then the same combine
-        // kernel as for large band sets
-        void* base = nullptr;
-        const size_t db = ((size_t)v.npts * sizeof(cd) + 255) & ~(size_t)255;
-        rc = tbk_ctx_scratch(ctx, 256 + 2 * db, &base);
+    if (nplaq > 0) {
+        rc = tbk_devbuf_grow(ctx->stream, w->flux_plaq, (size_t)nplaq * sizeof(double), "tbk_berry_flux: plaquette buffer");
         if (rc) return rc;
-        cd* dets = (cd*)((unsigned char*)base + 256);
-        // (1..4 bands of states with fewer than 8 components, round 6: the LDS-tile kernels of tbk_berry_lanes.inl)
-        rc = lanes_flux ? lanes_link_dets(w, occ, nocc, dir0, dets) : chain_wave_link_dets(w, occ, nocc, dir0, dets);
-        if (rc) return rc;
-        rc = lanes_flux ? lanes_link_dets(w, occ, nocc, dir1, (cd*)((unsigned char*)dets + db))
-                        : chain_wave_link_dets(w, occ, nocc, dir1, (cd*)((unsigned char*)dets + db));
-        if (rc) return rc;
-        PlaqDetArgs P{};
-        P.d0 = dets;
-        P.d1 = (cd*)((unsigned char*)dets + db);
-        P.n0 = A.n0;
-        P.n1 = A.n1;
-        P.s0 = A.s0;
-        P.s1 = A.s1;
-        P.other = A.other;
-        P.bps = A.bps;
-        P.plaq = A.plaq;
-        P.partial = A.partial;
-        ProfScope ps(ctx, "berry_flux");
-        hipLaunchKernelGGL(k_flux_from_dets, dim3((unsigned)(nslices * A.bps)), dim3(256), 0, ctx->stream, P);
-        TBK_HIP(hipGetLastError());
-    } else if (big) {
-        int* occ_dev = nullptr;
-        cd* dets = nullptr;
-        void* work = nullptr;
-        size_t work_bytes = 0;
-        rc = big_scratch(w, occ, nocc, 2, 0, &occ_dev, &dets, &work, &work_bytes, nullptr);
-        if (rc) return rc;
-        rc = launch_link_dets(w, occ_dev, nocc, dir0, dets, work, work_bytes);
-        if (rc) return rc;
-        rc = launch_link_dets(w, occ_dev, nocc, dir1, dets + v.npts, work, work_bytes);
-        if (rc) return rc;
-        PlaqDetArgs P{};
-        P.d0 = dets;
-        P.d1 = dets + v.npts;
-        P.n0 = A.n0;
-        P.n1 = A.n1;
-        P.s0 = A.s0;
-        P.s1 = A.s1;
-        P.other = A.other;
-        P.bps = A.bps;
-        P.plaq = A.plaq;
-        P.partial = A.partial;
-        ProfScope ps(ctx, "berry_flux");
-        hipLaunchKernelGGL(k_flux_from_dets, dim3((unsigned)(nslices * A.bps)), dim3(256), 0, ctx->stream, P);
-        TBK_HIP(hipGetLastError());
-    } else {
-        ProfScope ps(ctx, "berry_flux");
-        if (slices_k) {
-            const int64_t nitems = nslices * A.n0 * SL.nrun;          // (slices x rows x runs)
-            const dim3 grid((unsigned)((nitems + 255) / 256)), blk(256);
-#define TBK_SLC(NO, NC) hipLaunchKernelGGL((k_flux_slices<NO, NC>), grid, blk, 0, ctx->stream, A, SL, nitems)
-            switch (v.ncomp * 8 + nocc) {
-                case 1 * 8 + 1: TBK_SLC(1, 1); break;
-                case 2 * 8 + 1: TBK_SLC(1, 2); break;
-                case 2 * 8 + 2: TBK_SLC(2, 2); break;
-                case 3 * 8 + 1: TBK_SLC(1, 3); break;
-                case 3 * 8 + 2: TBK_SLC(2, 3); break;
-                case 3 * 8 + 3: TBK_SLC(3, 3); break;
-                case 4 * 8 + 1: TBK_SLC(1, 4); break;
-                case 4 * 8 + 2: TBK_SLC(2, 4); break;
-                case 4 * 8 + 3: TBK_SLC(3, 4); break;
-                default: TBK_SLC(4, 4); break;
-            }
-#undef TBK_SLC
-        } else if (rows) {
-            const dim3 grid((unsigned)(nslices * A.bpb)), blk(256);
-#define TBK_ROWS(NO, NC) hipLaunchKernelGGL((k_flux_rows<NO, NC>), grid, blk, 0, ctx->stream, A)
-            switch (v.ncomp * 8 + nocc) {
-                case 1 * 8 + 1: TBK_ROWS(1, 1); break;
-                case 2 * 8 + 1: TBK_ROWS(1, 2); break;
-                case 2 * 8 + 2: TBK_ROWS(2, 2); break;
-                case 3 * 8 + 1: TBK_ROWS(1, 3); break;
-                case 3 * 8 + 2: TBK_ROWS(2, 3); break;
-                case 3 * 8 + 3: TBK_ROWS(3, 3); break;
-                case 4 * 8 + 1: TBK_ROWS(1, 4); break;
-                case 4 * 8 + 2: TBK_ROWS(2, 4); break;
-                case 4 * 8 + 3: TBK_ROWS(3, 4); break;
-                default: TBK_ROWS(4, 4); break;
-            }
-#undef TBK_ROWS
-        } else {
-            switch (nocc) {
-                case 1: launch_flux<1, 1>(ctx, A, nslices); break;
-                case 2: launch_flux<2, 1>(ctx, A, nslices); break;
-                case 3: launch_flux<3, 1>(ctx, A, nslices); break;
-                case 4: launch_flux<4, 1>(ctx, A, nslices); break;
-                case 5: launch_flux<5, 1>(ctx, A, nslices); break;
-                case 6: launch_flux<6, 1>(ctx, A, nslices); break;
-                case 7: launch_flux<7, 1>(ctx, A, nslices); break;
-                case 8: launch_flux<8, 1>(ctx, A, nslices); break;
-                default: launch_flux<0, TBK_MAX_NOCC>(ctx, A, nslices);
-            }
-        }
-        TBK_HIP(hipGetLastError());
-    }
-    if ((!rows || !A.fused || slices_k) && nslices == 1 && !want_plaq && tbk_knobs().flux_defer != 0) {
-        // ---- the sum is left pending: the next row-kernel mesh solve of this array does it in one extra workgroup
-        // (solve_window_impl) -- in a loop that queues the next solve before it fetches this total the step is two launches, not
-        // three -- and tbk_berry_flux_result launches it itself when nothing has.  One slice only: what that workgroup serves.
-        w->flux_pend_n = (rows && !slices_k) ? A.bpb : A.bps;
-        w->flux_pend_nslices = 1;
-        w->flux_done = DoneArgs{nullptr, nullptr, nullptr, 0u};
-    } else if (!rows || !A.fused || slices_k) {
-        ProfScope ps(ctx, "flux_reduce");
-        // totals in mapped host memory and no per-plaquette output: this is the call's last kernel, the result call polls its
-        // completion word instead of synchronising the stream
-        w->flux_done = (w->flux_totals_host && !want_plaq) ? tbk_done_arm(ctx, false) : DoneArgs{nullptr, nullptr, nullptr, 0u};
-        hipLaunchKernelGGL(k_flux_reduce, dim3((unsigned)nslices), dim3(1024), 0, ctx->stream,
-                           (const double*)w->flux_partial_dev, (rows && !slices_k) ? A.bpb : A.bps, w->flux_totals_dev, w->flux_done);
-        TBK_HIP(hipGetLastError());
-    } else {
-        w->flux_done = DoneArgs{nullptr, nullptr, nullptr, 0u};
+        w->flux_plaq_n = nplaq;
     }
     return TBK_OK;
+}
+
+// step 4, the determinant routes: link determinants along both directions (d0, d1: one per mesh point), combined per plaquette
+static int launch_flux_from_dets(tbk_ctx* ctx, const FluxPlan& P, const cd* d0, const cd* d1) {
+    const FluxArgs& A = P.A;
+    const PlaqDetArgs D{d0, d1, A.n0, A.n1, A.s0, A.s1, A.other, A.bps, A.plaq, A.partial};
+    ProfScope ps(ctx, "berry_flux");
+    hipLaunchKernelGGL(k_flux_from_dets, dim3((unsigned)(P.nslices * A.bps)), dim3(256), 0, ctx->stream, D);
+    TBK_HIP(hipGetLastError());
+    return TBK_OK;
+}
+
+// 5..8 bands of wide states: every lane of the plaquette kernel would walk its own 256-byte rows; instead the link
+// determinants come from the wave-per-string kernels (coalesced) -- or, 1..4 bands of states with fewer than 8 components
+// (round 6), from the LDS-tile kernels of tbk_berry_lanes.inl
+static int launch_flux_string_dets(tbk_wfs* w, const int32_t* occ, int nocc, int dir0, int dir1, const FluxPlan& P) {
+    tbk_ctx* ctx = w->ctx;
+    void* base = nullptr;
+    const size_t db = ((size_t)w->view.npts * sizeof(cd) + 255) & ~(size_t)255;
+    int rc = tbk_ctx_scratch(ctx, 256 + 2 * db, &base);
+    if (rc) return rc;
+    cd* const d0 = (cd*)((unsigned char*)base + 256);
+    cd* const d1 = (cd*)((unsigned char*)d0 + db);
+    rc = P.lanes_flux ? lanes_link_dets(w, occ, nocc, dir0, d0) : chain_wave_link_dets(w, occ, nocc, dir0, d0);
+    if (rc) return rc;
+    rc = P.lanes_flux ? lanes_link_dets(w, occ, nocc, dir1, d1) : chain_wave_link_dets(w, occ, nocc, dir1, d1);
+    if (rc) return rc;
+    return launch_flux_from_dets(ctx, P, d0, d1);
+}
+
+// large band sets: link determinants by LU, one workgroup per link
+static int launch_flux_big_dets(tbk_wfs* w, const int32_t* occ, int nocc, int dir0, int dir1, const FluxPlan& P) {
+    int* occ_dev = nullptr;
+    cd* dets = nullptr;
+    void* work = nullptr;
+    size_t work_bytes = 0;
+    int rc = big_scratch(w, occ, nocc, 2, 0, &occ_dev, &dets, &work, &work_bytes, nullptr);
+    if (rc) return rc;
+    rc = launch_link_dets(w, occ_dev, nocc, dir0, dets, work, work_bytes);
+    if (rc) return rc;
+    rc = launch_link_dets(w, occ_dev, nocc, dir1, dets + w->view.npts, work, work_bytes);
+    if (rc) return rc;
+    return launch_flux_from_dets(w->ctx, P, dets, dets + w->view.npts);
+}
+
+// the register-resident kernels are compiled per (bands, components) of up to 4 x 4: LAUNCH(NOCC, NCOMP)
+#define TBK_FLUX_BY_SHAPE(ncomp, nocc, LAUNCH)  \
+    switch ((ncomp) * 8 + (nocc)) {             \
+        case 1 * 8 + 1: LAUNCH(1, 1); break;    \
+        case 2 * 8 + 1: LAUNCH(1, 2); break;    \
+        case 2 * 8 + 2: LAUNCH(2, 2); break;    \
+        case 3 * 8 + 1: LAUNCH(1, 3); break;    \
+        case 3 * 8 + 2: LAUNCH(2, 3); break;    \
+        case 3 * 8 + 3: LAUNCH(3, 3); break;    \
+        case 4 * 8 + 1: LAUNCH(1, 4); break;    \
+        case 4 * 8 + 2: LAUNCH(2, 4); break;    \
+        case 4 * 8 + 3: LAUNCH(3, 4); break;    \
+        default: LAUNCH(4, 4); break;           \
+    }
+
+// the plaquette kernels proper: lanes along the slices, the row kernel, or the generic thread-per-plaquette kernel
+static int launch_flux_plaquettes(tbk_ctx* ctx, const FluxPlan& P) {
+    const FluxArgs& A = P.A;
+    const int64_t nslices = P.nslices;
+    ProfScope ps(ctx, "berry_flux");
+    if (P.slices_k) {
+        const FluxSliceArgs& SL = P.SL;
+        const int64_t nitems = nslices * A.n0 * SL.nrun;          // (slices x rows x runs)
+        const dim3 grid((unsigned)((nitems + 255) / 256)), blk(256);
+#define TBK_SLC(NO, NC) hipLaunchKernelGGL((k_flux_slices<NO, NC>), grid, blk, 0, ctx->stream, A, SL, nitems)
+        TBK_FLUX_BY_SHAPE(A.v.ncomp, A.nocc, TBK_SLC)
+#undef TBK_SLC
+    } else if (P.rows) {
+        const dim3 grid((unsigned)(nslices * A.bpb)), blk(256);
+#define TBK_ROWS(NO, NC) hipLaunchKernelGGL((k_flux_rows<NO, NC>), grid, blk, 0, ctx->stream, A)
+        TBK_FLUX_BY_SHAPE(A.v.ncomp, A.nocc, TBK_ROWS)
+#undef TBK_ROWS
+    } else {
+        switch (A.nocc) {
+            case 1: launch_flux<1, 1>(ctx, A, nslices); break;
+            case 2: launch_flux<2, 1>(ctx, A, nslices); break;
+            case 3: launch_flux<3, 1>(ctx, A, nslices); break;
+            case 4: launch_flux<4, 1>(ctx, A, nslices); break;
+            case 5: launch_flux<5, 1>(ctx, A, nslices); break;
+            case 6: launch_flux<6, 1>(ctx, A, nslices); break;
+            case 7: launch_flux<7, 1>(ctx, A, nslices); break;
+            case 8: launch_flux<8, 1>(ctx, A, nslices); break;
+            default: launch_flux<0, TBK_MAX_NOCC>(ctx, A, nslices);
+        }
+    }
+    TBK_HIP(hipGetLastError());
+    return TBK_OK;
+}
+
+// step 5: the sum of the partials -- inside the row kernel (TBK_FLUX_FUSED), left pending, or k_flux_reduce now
+static int flux_sum_partials(tbk_wfs* w, const FluxPlan& P, int want_plaq) {
+    const bool row_kernel = P.rows && !P.slices_k;
+    if (row_kernel && P.A.fused) {     // (TBK_FLUX_FUSED: summed inside the row kernel)
+        tbk_flux_leave_pending(w, 0, 0);
+        return TBK_OK;
+    }
+    tbk_flux_leave_pending(w, row_kernel ? P.A.bpb : P.A.bps, P.nslices);
+    // ---- one slice, no plaquettes: the sum stays pending.  The next row-kernel mesh solve of this array does it in one extra
+    // workgroup (launch_grid_rows) -- in a loop that queues the next solve before it fetches this total the step is two launches,
+    // not three -- and tbk_berry_flux_result launches it itself when nothing has.  One slice only: what that workgroup serves.
+    if (P.nslices == 1 && !want_plaq && tbk_knobs().flux_defer != 0) return TBK_OK;
+    // ---- else k_flux_reduce now.  Totals in mapped host memory and no per-plaquette output: it is the call's last kernel, and
+    // the result call polls its completion word instead of synchronising the stream
+    return tbk_flux_flush_pending(w, !want_plaq);
+}
+
+extern "C" int tbk_berry_flux_async(tbk_wfs* w, const int32_t* occ, int nocc, int dir0, int dir1,
+                                    int want_plaq) {
+    FluxPlan P{};
+    int rc = flux_check_args(w, occ, nocc, dir0, dir1, P);
+    if (rc) return rc;
+    tbk_ctx* ctx = w->ctx;
+    TBK_HIP(hipSetDevice(ctx->device));
+    // this call rewrites the partials and the totals: a reduction still pending from the call before is launched first
+    rc = tbk_flux_flush_pending(w, false);
+    if (rc) return rc;
+    rc = flux_geometry(w, nocc, dir0, dir1, want_plaq, P);
+    if (rc) return rc;
+    rc = tbk_flux_buffers(w, P.nslices, P.nslices * P.A.bps, want_plaq ? P.nslices * P.per : 0);
+    if (rc) return rc;
+    P.A.counters = w->flux_cnt.as<unsigned>();
+    P.A.totals = w->flux_totals_dev;
+    P.A.partial = w->flux_partial.as<double>();
+    if (want_plaq) P.A.plaq = w->flux_plaq.as<double>();
+    if (!P.big && (chain_wave_applies(w->view, nocc) || P.lanes_flux)) rc = launch_flux_string_dets(w, occ, nocc, dir0, dir1, P);
+    else if (P.big) rc = launch_flux_big_dets(w, occ, nocc, dir0, dir1, P);
+    else rc = launch_flux_plaquettes(ctx, P);
+    if (rc) return rc;
+    return flux_sum_partials(w, P, want_plaq);
 }
 
 extern "C" int tbk_berry_flux_result(tbk_wfs* w, double* totals, double* plaq) {
@@ -1043,7 +1050,7 @@ extern "C" int tbk_berry_flux_result(tbk_wfs* w, double* totals, double* plaq) {
     }
     if (plaq) {
         TBK_REQUIRE(w->flux_plaq_n > 0, TBK_EINVAL, "tbk_berry_flux_result: plaquettes were not requested");
-        TBK_HIP(hipMemcpyAsync(plaq, w->flux_plaq_dev, w->flux_plaq_n * sizeof(double), hipMemcpyDeviceToHost,
+        TBK_HIP(hipMemcpyAsync(plaq, w->flux_plaq.p, w->flux_plaq_n * sizeof(double), hipMemcpyDeviceToHost,
                                ctx->stream));
     }
     if (w->flux_totals_host) {                       // mapped host memory: the kernel's stores were the transfer
@@ -1389,16 +1396,9 @@ static int launch_chain_wave(tbk_ctx* ctx, const WfsView& v, const ChainArgs& A,
         if (!dets_out && nocc >= 5 && nocc <= 8 && tbk_knobs().chain_prod != 0 && 2 * lds_p1 <= 64 * 1024) {
             const int64_t nw = A.nstrings * A.nseg;
             const size_t wbytes = (size_t)nw * 64 * sizeof(cd);
-            if (wbytes > ctx->work_bytes) {
-                TBK_HIP(hipStreamSynchronize(ctx->stream));
-                if (ctx->work) TBK_HIP(hipFree(ctx->work));
-                ctx->work = nullptr;
-                ctx->work_bytes = 0;
-                hipError_t e = hipMalloc(&ctx->work, wbytes);
-                TBK_REQUIRE(e == hipSuccess, TBK_ENOMEM, "string-product workspace of %zu bytes: %s", wbytes, hipGetErrorString(e));
-                ctx->work_bytes = wbytes;
-            }
-            cd* pw = (cd*)ctx->work;
+            void* wsp = nullptr;
+            if (const int rcw = tbk_ctx_work(ctx, wbytes, "string-product workspace", &wsp)) return rcw;
+            cd* pw = (cd*)wsp;
             const int nld = (nocc * v.ncomp + 63) / 64;
             const dim3 gp((unsigned)((nw + 1) / 2)), gd((unsigned)((nw + 63) / 64));
 #define TBK_CHAINP(NN, LL)                                                                                                       \
@@ -1429,16 +1429,9 @@ static int launch_chain_wave(tbk_ctx* ctx, const WfsView& v, const ChainArgs& A,
     const size_t ws_cap = (size_t)std::max(1, tbk_knobs().chain_ws_mb) << 20;
     const int64_t nsb = std::max<int64_t>(1, std::min<int64_t>(A.nstrings, (int64_t)(ws_cap / per_string)));
     const size_t wbytes = (size_t)nsb * per_string;
-    if (wbytes > ctx->work_bytes) {
-        TBK_HIP(hipStreamSynchronize(ctx->stream));
-        if (ctx->work) TBK_HIP(hipFree(ctx->work));
-        ctx->work = nullptr;
-        ctx->work_bytes = 0;
-        hipError_t e = hipMalloc(&ctx->work, wbytes);
-        TBK_REQUIRE(e == hipSuccess, TBK_ENOMEM, "link-matrix workspace of %zu bytes: %s", wbytes, hipGetErrorString(e));
-        ctx->work_bytes = wbytes;
-    }
-    cd* ws = (cd*)ctx->work;
+    void* wsp = nullptr;
+    if (const int rcw = tbk_ctx_work(ctx, wbytes, "link-matrix workspace", &wsp)) return rcw;
+    cd* ws = (cd*)wsp;
     const size_t lds_a = (size_t)4 * 2 * (nocc * (v.ncomp + 1) + 1) * sizeof(cd);
     const size_t lds_b = (size_t)TBK_CHAINW_PASS * (nn + 1) * sizeof(cd);
     // 5..8 bands: four links per wavefront step (k_chain_links_tile) while its five staged points fit 64 KB per block

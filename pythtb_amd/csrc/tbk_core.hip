@@ -189,7 +189,7 @@ extern "C" int tbk_ctx_destroy(tbk_ctx* c) {
         hipEventDestroy(r.t1);
     }
     for (auto e : c->event_pool) hipEventDestroy(e);
-    if (c->scratch) hipFree(c->scratch);
+    tbk_devbuf_free(c->scratch);
     if (c->zc_host) hipHostFree(c->zc_host);
     for (auto& b : c->blob_pool) hipFree(b.p);
     c->blob_pool.clear();
@@ -197,7 +197,7 @@ extern "C" int tbk_ctx_destroy(tbk_ctx* c) {
     if (c->done_host) hipHostFree(c->done_host);
     if (c->done_cnt_dev) hipFree(c->done_cnt_dev);
     if (c->pinned) hipHostFree(c->pinned);
-    if (c->work) hipFree(c->work);
+    tbk_devbuf_free(c->work);
     hipEventDestroy(c->timer0);
     hipEventDestroy(c->timer1);
     for (int i = 0; i < 3; ++i)
@@ -340,21 +340,15 @@ int tbk_wfs_totals_alloc(tbk_wfs* w, int64_t nslices) {
 }
 
 int tbk_ctx_scratch(tbk_ctx* c, size_t bytes, void** out) {
-    if (bytes > c->scratch_bytes) {
-        TBK_HIP(hipStreamSynchronize(c->stream));
-        if (c->scratch) TBK_HIP(hipFree(c->scratch));
-        c->scratch = nullptr;
-        c->scratch_bytes = 0;
-        size_t want = std::max(bytes, (size_t)1 << 20);
-        hipError_t e = hipMalloc(&c->scratch, want);
-        if (e != hipSuccess) {
-            tbk_set_error("device scratch of %zu bytes: %s", want, hipGetErrorString(e));
-            return TBK_ENOMEM;
-        }
-        c->scratch_bytes = want;
-    }
-    *out = c->scratch;
-    return TBK_OK;
+    const int rc = tbk_devbuf_grow(c->stream, c->scratch, bytes, "device scratch", (size_t)1 << 20);
+    *out = c->scratch.p;
+    return rc;
+}
+
+int tbk_ctx_work(tbk_ctx* c, size_t bytes, const char* what, void** out, size_t at_least) {
+    const int rc = tbk_devbuf_grow(c->stream, c->work, bytes, what, at_least);
+    *out = c->work.p;
+    return rc;
 }
 
 // mapped host memory of at least `bytes` (grown on demand; null when the platform refuses: callers then copy)
@@ -1011,13 +1005,13 @@ extern "C" int tbk_wfs_free(tbk_wfs* w) {
     hipStreamSynchronize(w->ctx->stream);
     if (w->view.data) hipFree(w->view.data);
     if (w->gaps_dev) hipFree(w->gaps_dev);
-    if (w->gap_part_dev) hipFree(w->gap_part_dev);
+    tbk_devbuf_free(w->gap_part);
     if (w->pbc_dev) hipFree(w->pbc_dev);
-    if (w->tab_dev) hipFree(w->tab_dev);
+    tbk_devbuf_free(w->tab);
     tbk_wfs_totals_free(w);
-    if (w->flux_cnt_dev) hipFree(w->flux_cnt_dev);
-    if (w->flux_plaq_dev) hipFree(w->flux_plaq_dev);
-    if (w->flux_partial_dev) hipFree(w->flux_partial_dev);
+    tbk_devbuf_free(w->flux_cnt);
+    tbk_devbuf_free(w->flux_plaq);
+    tbk_devbuf_free(w->flux_partial);
     delete w;
     return TBK_OK;
 }

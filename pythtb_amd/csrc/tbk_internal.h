@@ -5,6 +5,7 @@
 #include <string>
 #include <vector>
 #include "../../include/tbk.h"
+#include "tbk_devbuf.h"
 
 // ---------------------------------------------------------------- errors
 void tbk_set_error(const char* fmt, ...);
@@ -26,6 +27,17 @@ void tbk_set_error(const char* fmt, ...);
             return (code);                                                              \
         }                                                                               \
     } while (0)
+
+// tbk_devbuf_regrow behind a synchronisation of `stream`, whose queued kernels may still use the old buffer; and the release
+static inline int tbk_devbuf_grow(hipStream_t stream, TbkDevBuf& b, size_t need, const char* what, size_t at_least = 0) {
+    if (need <= b.bytes) return TBK_OK;
+    TBK_HIP(hipStreamSynchronize(stream));
+    return tbk_devbuf_regrow(b, need, at_least, what);
+}
+static inline void tbk_devbuf_free(TbkDevBuf& b) {
+    if (b.p) hipFree(b.p);
+    b = TbkDevBuf{};
+}
 
 // ---------------------------------------------------------------- run-time knobs
 // Every TBK_* environment variable the library honours, parsed ONCE (first use) into this struct;
@@ -226,8 +238,7 @@ struct tbk_ctx {
     std::vector<hipEvent_t> event_pool;
     std::vector<ProfAgg> prof_agg;
     // scratch reused across calls (grown on demand, stream-ordered use only)
-    void* scratch = nullptr;
-    size_t scratch_bytes = 0;
+    TbkDevBuf scratch;
     // host memory the device reads and writes directly (hipHostMalloc, mapped): small calls hand their k list over and take their
     // eigenvalues / eigenvectors back through it -- one stream synchronisation instead of a copy each way (tbk_solve_list)
     // table blobs of freed models (<= 1 MiB each, at most 8): a parameter sweep edits and re-uploads a small model per point, and a
@@ -248,8 +259,7 @@ struct tbk_ctx {
     unsigned* done_dev = nullptr;
     unsigned* done_cnt_dev = nullptr;
     unsigned done_seq = 0;
-    void* work = nullptr;      // workspace of the workgroup-per-matrix eigen-solver (n > 64)
-    size_t work_bytes = 0;
+    TbkDevBuf work;            // workspace of the eigen-solvers and the string kernels (tbk_ctx_work)
     // whole-array / per-point wf_array transfers across PCIe (tbk_ctx_transfer_stats)
     int64_t xfer_h2d_bytes = 0, xfer_d2h_bytes = 0, xfer_h2d_calls = 0, xfer_d2h_calls = 0;
     // RCCL
@@ -259,6 +269,8 @@ struct tbk_ctx {
 };
 
 int tbk_ctx_scratch(tbk_ctx* ctx, size_t bytes, void** out);
+// ctx->work of at least `bytes` (tbk_devbuf_grow: contents not kept; `what` names it in the TBK_ENOMEM message)
+int tbk_ctx_work(tbk_ctx* ctx, size_t bytes, const char* what, void** out, size_t at_least = 0);
 int tbk_ctx_zero_copy(tbk_ctx* ctx, size_t bytes, void** host, void** dev);
 // small device-to-host result (min gaps, flux totals, status words): through a pinned staging buffer -- an async copy into
 // pageable memory is staged by the runtime and cost ~10 us more per call on the Python-API path -- then stream sync
@@ -418,8 +430,8 @@ struct tbk_wfs {
     // each launch min-reduces into its parity and re-arms the other one for the next launch
     unsigned long long* gaps_dev = nullptr;
     int gaps_n = 0, gaps_parity = 0;
-    double* gap_part_dev = nullptr;          // per-tile minima of the row kernel (n <= 4), [ntiles][n-1]
-    int64_t gap_part_cap = 0, gap_part_n = 0; // gap_part_n > 0: the last solve wrote partials, not shards
+    TbkDevBuf gap_part;                      // per-tile minima of the row kernel (n <= 4), double [ntiles][n-1]
+    int64_t gap_part_n = 0;                  // > 0: the last solve wrote partials, not shards
     cd* pbc_dev = nullptr;                   // [TBK_MAX_DIM][nsta]
     // the last solve_grid launch, kept so that tbk_wfs_solve_grid_result can repeat it on other kernels
     struct tbk_model* last_model = nullptr;
@@ -427,21 +439,19 @@ struct tbk_wfs {
     int64_t last_off[TBK_MAX_DIM] = {0, 0, 0, 0}, last_gmesh[TBK_MAX_DIM] = {1, 1, 1, 1};
     std::vector<double> last_pbc;
     // per-axis phase tables of the regular mesh (rebuilt only when their inputs change)
-    cd* tab_dev = nullptr;                   // z[d][i] then f[d][i][n]
-    int64_t tab_cap = 0;
+    TbkDevBuf tab;                           // cd: z[d][i] then f[d][i][n]
     std::vector<double> tab_key;
     // flux results
     double* flux_totals_dev = nullptr;   // device pointer of the per-slice totals; mapped HOST memory when small (flux_totals_host != null)
     double* flux_totals_host = nullptr;  // ... its host address: the result is read after one synchronisation, no copy operation
     DoneArgs flux_done{nullptr, nullptr, nullptr, 0u};   // completion word armed by the pending berry_flux launch (word null: synchronise)
-    unsigned* flux_cnt_dev = nullptr;        // [slices][16] arrival tickets of the row kernel
-    int64_t flux_nslices = 0, flux_nslices_cap = 0;
-    double* flux_plaq_dev = nullptr;
-    int64_t flux_plaq_cap = 0, flux_plaq_n = 0;
-    double* flux_partial_dev = nullptr;
-    int64_t flux_partial_cap = 0;
+    TbkDevBuf flux_cnt;                      // unsigned [slices][16] arrival tickets of the row kernel; the totals hold as many slices
+    int64_t flux_nslices = 0;
+    TbkDevBuf flux_plaq;                     // double
+    int64_t flux_plaq_n = 0;
+    TbkDevBuf flux_partial;                  // double
     // a reduction tbk_berry_flux_async left pending (TBK_FLUX_DEFER): flux_pend_nslices slices of flux_pend_n partials each in
-    // flux_partial_dev, their totals wanted in flux_totals_dev.  flux_pend_n == 0: none.  Consumed by the next row-kernel mesh
+    // flux_partial, their totals wanted in flux_totals_dev.  flux_pend_n == 0: none.  Consumed by the next row-kernel mesh
     // solve of this array (one extra workgroup), by tbk_berry_flux_result, or by tbk_flux_flush_pending in front of whatever
     // would overwrite the partials or the totals -- whichever comes first; tbk_wfs_free drops it.
     int flux_pend_n = 0;
@@ -450,9 +460,26 @@ struct tbk_wfs {
 // tbk_berry.hip: launch k_flux_reduce for a pending reduction of `w` (no-op without one).  `arm`: with the completion word for
 // tbk_berry_flux_result to poll (w->flux_done), as the launch inside tbk_berry_flux_async arms it.
 int tbk_flux_flush_pending(struct tbk_wfs* w, bool arm);
+// ... leave pending: `nslices` slices of `n` partials, no completion word armed
+inline void tbk_flux_leave_pending(struct tbk_wfs* w, int n, int64_t nslices) {
+    w->flux_pend_n = n;
+    w->flux_pend_nslices = nslices;
+    w->flux_done = DoneArgs{nullptr, nullptr, nullptr, 0u};
+}
+// ... take pending, for a mesh solve that carries the sum of ONE slice: the number of partials, 0 when there is none it can carry
+inline int tbk_flux_take_pending(struct tbk_wfs* w) {
+    if (w->flux_pend_n <= 0 || w->flux_pend_nslices != 1) return 0;
+    const int n = w->flux_pend_n;
+    w->flux_pend_n = 0;
+    w->flux_pend_nslices = 0;
+    return n;
+}
 
 // tbk_solve.hip: eigenvalues on k_uniform_mesh(mesh) by the row kernel (n <= 4); *done = false where it does not apply
 int tbk_mesh_evals_rows(struct tbk_model* m, const int32_t* mesh, double* e_dev, bool* done);
+// tbk_berry.hip: the buffers of a flux launch made to hold -- totals and counters of `nslices` slices, `npartial` partial sums,
+// `nplaq` plaquette phases (0: none); sets flux_nslices and flux_plaq_n.  For tbk_berry_flux_async and the fused mesh solve.
+int tbk_flux_buffers(struct tbk_wfs* w, int64_t nslices, int64_t npartial, int64_t nplaq);
 // tbk_core.hip: (re)allocate / release the per-slice flux totals (mapped host memory up to 64 KB, device memory beyond)
 int tbk_wfs_totals_alloc(struct tbk_wfs* w, int64_t nslices);
 void tbk_wfs_totals_free(struct tbk_wfs* w);

@@ -27,6 +27,7 @@
 #include "tbk_internal.h"
 #include <cstring>
 
+#include "tbk_solve_plan.h"  // tile balance of the row kernels, chain window of k_solve_wave (host arithmetic, check/plan_check.cpp)
 #include "tbk_solve_dev.h"   // GridArgs / ListArgs, exp(2 pi i x), mesh-point decoding, DPP row helpers, the lane-per-matrix QL step
 
 // ---------------------------------------------------------------------------
@@ -1712,16 +1713,9 @@ int tbk_mesh_evals_rows(tbk_model* m, const int32_t* mesh, double* e_dev, bool* 
     if (v.npts / mesh[D - 1] >= (int64_t)0xffffffffu) return TBK_OK;
     // per-axis tables in the context's work area (tz | tf); tf (orbital phases) is written by k_grid_tables and not used here
     const size_t tbytes = (size_t)ntab * (1 + n) * sizeof(cd) + (size_t)TBK_MAX_DIM * n * sizeof(cd);
-    if (tbytes > ctx->work_bytes) {
-        TBK_HIP(hipStreamSynchronize(ctx->stream));
-        if (ctx->work) TBK_HIP(hipFree(ctx->work));
-        ctx->work = nullptr;
-        ctx->work_bytes = 0;
-        hipError_t e = hipMalloc(&ctx->work, std::max(tbytes, (size_t)1 << 20));
-        TBK_REQUIRE(e == hipSuccess, TBK_ENOMEM, "mesh tables of %zu bytes: %s", tbytes, hipGetErrorString(e));
-        ctx->work_bytes = std::max(tbytes, (size_t)1 << 20);
-    }
-    cd* tab = (cd*)ctx->work;
+    void* wsp = nullptr;
+    if (const int rcw = tbk_ctx_work(ctx, tbytes, "mesh tables", &wsp, (size_t)1 << 20)) return rcw;
+    cd* tab = (cd*)wsp;
     cd* pbc = tab + ntab * (1 + n);
     TBK_HIP(hipMemsetAsync(pbc, 0, (size_t)TBK_MAX_DIM * n * sizeof(cd), ctx->stream));
     G.pbc = pbc;
@@ -2415,6 +2409,88 @@ extern "C" const char* tbk_solver_regime(int n, int with_vectors, int form, int6
     return names[(int)r];
 }
 
+// k_solve_wave on a mesh: the window of aligned chains of `run` points along the last axis (G.wcfirst, G.wnchunk); returns the
+// number of workgroups, one per chain and mesh row
+static int64_t wave_mesh_chunks(GridArgs& G, int64_t run) {
+    const int64_t nl = G.wv.mesh[G.last];
+    G.wnchunk = tbk_chunk_window(G.off[G.last], nl, run, &G.wcfirst);
+    return (G.wv.npts / nl) * G.wnchunk;
+}
+
+// the LDS workgroup solver on NT threads; a dynamic LDS request above 64 KB needs the kernel's attribute, set once per instantiation
+template <int MODE, bool VEC, int NT>
+static int launch_wave_few(tbk_ctx* ctx, const ModelView& mv, int64_t nk, const ListArgs& L, const GridArgs& G, int64_t nblocks,
+                           size_t lds, int run, int warm) {
+    static bool attr_set = false;
+    if (lds > 64 * 1024 && !attr_set) {
+        TBK_HIP(hipFuncSetAttribute((const void*)k_solve_wave<MODE, VEC, NT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        attr_set = true;
+    }
+    hipLaunchKernelGGL((k_solve_wave<MODE, VEC, NT, true>), dim3((unsigned)nblocks), dim3(NT), lds, ctx->stream, mv, nk, L, G,
+                       ctx->flags_dev, run, (cd*)nullptr, warm);
+    TBK_HIP(hipGetLastError());
+    return TBK_OK;
+}
+
+// A 256-thread workgroup per LDS-resident matrix instead of one wavefront:
+//  * n >= 22, any batch: a wavefront's matrix with its warm-start buffer takes 3 n(n+1) 16 B of LDS (n = 48:
+//    113 KB, ONE wavefront per CU); several wavefronts sharing one matrix keep 8-16 wavefronts per CU busy, and
+//    large batches warm-start along their runs as well where that still leaves two matrices per CU (n <= 40).
+//    Eigenvalues, mesh-ordered k (ms, wavefront kernel -> this one): 65536 x n=24 13.6 -> 10.6, 16384 x n=32
+//    11.0 -> 5.5, n=40 (4.7 at 1024 k) -> 11.7 (1.8), n=48 92 -> 33, 8192 x n=64 209 -> 39; n=22 9.4 -> 8.3 is
+//    the crossover (n=20: 6.7 vs 7.5).
+//  * n < 22: only while the batch cannot fill the chip with wavefronts (one 30x30 matrix: 0.77 -> 0.31 ms).
+template <int MODE, bool VEC>
+static int launch_wave_workgroup(tbk_ctx* ctx, const ModelView& mv, int n, int64_t nk, int64_t nk_eff, const ListArgs& L,
+                                 GridArgs& G, bool few) {
+    const TbkKnobs& K = tbk_knobs();
+    int* flag = ctx->flags_dev;
+    // ---- workgroup per matrix: 256 threads, cold start; n = 65..256: A and V^T in a global workspace
+    // (ribbon / slab models: few, large matrices), n <= 64: in LDS.
+    // a large batch walks runs of consecutive points per workgroup anyway: warm-start along them when the
+    // extra buffer still leaves two matrices per CU (TBK_FEW_WARM=0 disables)
+    const bool warm_knob = K.few_warm != 0;
+    const int64_t cap = std::max<int64_t>(64, (int64_t)ctx->cus * 4);
+    const int warm_few = few && warm_knob && nk_eff >= 2 * cap && wave_lds_bytes(n, true, mv.nR) <= 80 * 1024 ? 1 : 0;
+    const size_t lds = few ? wave_lds_bytes(n, warm_few != 0, mv.nR)
+                           : wave_lds_bytes(n, false) - (size_t)2 * n * (n + 1) * sizeof(cd);   // small arrays only
+    int64_t run, nblocks;
+    if (MODE == 1) {
+        // (warm runs must not depend on the window: the run length comes from the global mesh size)
+        run = std::max<int64_t>(1, ((warm_few ? nk_eff : G.wv.npts) + cap - 1) / cap);
+        if (warm_few) run = std::min<int64_t>(run, 16);
+        nblocks = wave_mesh_chunks(G, run);
+    } else {
+        run = std::max<int64_t>(1, (nk + cap - 1) / cap);
+        if (warm_few) run = std::min<int64_t>(run, 64);   // short chains: V's orthonormality drift stays ~1e-15
+        nblocks = (nk + run - 1) / run;
+    }
+    TBK_REQUIRE(nblocks < (int64_t)0x7fffffff, TBK_EUNSUPPORTED, "too many k-points for one launch");
+    const size_t wbytes = few ? 0 : (size_t)nblocks * 2 * n * (n + 1) * sizeof(cd);
+    if (few) {
+        // threads per matrix, measured (eigenvalues, ms; 256 / 512 / 1024 threads): 16384 matrices n=32 9.1 / 12.3 /
+        // 19.8, n=48 41 / 33 / 42, 8192 of n=64 66 / 46 / 39; a single matrix n=50 1.13 / 0.84 / 0.70, n=64 1.96 / 1.41 / 1.18
+        int nt;
+        if (nk_eff > (int64_t)ctx->cus) nt = n <= 40 ? 256 : (n <= 56 ? 512 : 1024);
+        else nt = n <= 24 ? 256 : (n <= 36 ? 512 : 1024);
+        if (K.few_nt >= 0) nt = K.few_nt >= 1024 ? 1024 : (K.few_nt >= 512 ? 512 : 256);
+        return nt == 256   ? launch_wave_few<MODE, VEC, 256>(ctx, mv, nk, L, G, nblocks, lds, (int)run, warm_few)
+               : nt == 512 ? launch_wave_few<MODE, VEC, 512>(ctx, mv, nk, L, G, nblocks, lds, (int)run, warm_few)
+                           : launch_wave_few<MODE, VEC, 1024>(ctx, mv, nk, L, G, nblocks, lds, (int)run, warm_few);
+    }
+    void* wsp = nullptr;
+    if (const int rcw = tbk_ctx_work(ctx, wbytes, "eigen-solver workspace", &wsp)) return rcw;
+    const int wg_nt = K.wg_nt;
+    if (wg_nt >= 1024)
+        hipLaunchKernelGGL((k_solve_wave<MODE, VEC, 1024, false>), dim3((unsigned)nblocks), dim3(1024), lds, ctx->stream, mv, nk,
+                           L, G, flag, (int)run, (cd*)wsp, 0);
+    else
+        hipLaunchKernelGGL((k_solve_wave<MODE, VEC, 256>), dim3((unsigned)nblocks), dim3(256), lds, ctx->stream, mv, nk, L,
+                           G, flag, (int)run, (cd*)wsp, 0);
+    TBK_HIP(hipGetLastError());
+    return TBK_OK;
+}
+
 template <int MODE, bool VEC>
 static int launch_wave(tbk_ctx* ctx, const ModelView& mv, int n, int64_t nk, const ListArgs& L,
                        const GridArgs& G) {
@@ -2445,96 +2521,15 @@ static int launch_wave(tbk_ctx* ctx, const ModelView& mv, int n, int64_t nk, con
             break;
         default: break;
     }
-    // A 256-thread workgroup per LDS-resident matrix instead of one wavefront:
-    //  * n >= 22, any batch: a wavefront's matrix with its warm-start buffer takes 3 n(n+1) 16 B of LDS (n = 48:
-    //    113 KB, ONE wavefront per CU); several wavefronts sharing one matrix keep 8-16 wavefronts per CU busy, and
-    //    large batches warm-start along their runs as well where that still leaves two matrices per CU (n <= 40).
-    //    Eigenvalues, mesh-ordered k (ms, wavefront kernel -> this one): 65536 x n=24 13.6 -> 10.6, 16384 x n=32
-    //    11.0 -> 5.5, n=40 (4.7 at 1024 k) -> 11.7 (1.8), n=48 92 -> 33, 8192 x n=64 209 -> 39; n=22 9.4 -> 8.3 is
-    //    the crossover (n=20: 6.7 vs 7.5).
-    //  * n < 22: only while the batch cannot fill the chip with wavefronts (one 30x30 matrix: 0.77 -> 0.31 ms).
-    const bool few = regime == Regime::WgLds;
-    if (regime == Regime::WgGlobal || few) {
-        // ---- workgroup per matrix: 256 threads, cold start; n = 65..256: A and V^T in a global workspace
-        // (ribbon / slab models: few, large matrices), n <= 64: in LDS.
-        // a large batch walks runs of consecutive points per workgroup anyway: warm-start along them when the
-        // extra buffer still leaves two matrices per CU (TBK_FEW_WARM=0 disables)
-        const bool warm_knob = K.few_warm != 0;
-        const int64_t cap = std::max<int64_t>(64, (int64_t)ctx->cus * 4);
-        const int warm_few = few && warm_knob && nk_eff >= 2 * cap && wave_lds_bytes(n, true, mv.nR) <= 80 * 1024 ? 1 : 0;
-        const size_t lds = few ? wave_lds_bytes(n, warm_few != 0, mv.nR)
-                               : wave_lds_bytes(n, false) - (size_t)2 * n * (n + 1) * sizeof(cd);   // small arrays only
-        int64_t run, nblocks;
-        if (MODE == 1) {
-            const int last = G.last;
-            const int64_t off = G.off[last], nl = G.wv.mesh[last];
-            // (warm runs must not depend on the window: the run length comes from the global mesh size)
-            run = std::max<int64_t>(1, ((warm_few ? nk_eff : G.wv.npts) + cap - 1) / cap);
-            if (warm_few) run = std::min<int64_t>(run, 16);
-            G2.wcfirst = off / run;
-            G2.wnchunk = (int)((off + nl - 1) / run - G2.wcfirst + 1);
-            nblocks = (G.wv.npts / nl) * G2.wnchunk;
-        } else {
-            run = std::max<int64_t>(1, (nk + cap - 1) / cap);
-            if (warm_few) run = std::min<int64_t>(run, 64);   // short chains: V's orthonormality drift stays ~1e-15
-            nblocks = (nk + run - 1) / run;
-        }
-        TBK_REQUIRE(nblocks < (int64_t)0x7fffffff, TBK_EUNSUPPORTED, "too many k-points for one launch");
-        const size_t wbytes = few ? 0 : (size_t)nblocks * 2 * n * (n + 1) * sizeof(cd);
-        if (few) {
-            // threads per matrix, measured (eigenvalues, ms; 256 / 512 / 1024 threads): 16384 matrices n=32 9.1 / 12.3 /
-            // 19.8, n=48 41 / 33 / 42, 8192 of n=64 66 / 46 / 39; a single matrix n=50 1.13 / 0.84 / 0.70, n=64 1.96 / 1.41 / 1.18
-            int nt;
-            if (nk_eff > (int64_t)ctx->cus) nt = n <= 40 ? 256 : (n <= 56 ? 512 : 1024);
-            else nt = n <= 24 ? 256 : (n <= 36 ? 512 : 1024);
-            if (K.few_nt >= 0) nt = K.few_nt >= 1024 ? 1024 : (K.few_nt >= 512 ? 512 : 256);
-            static bool attr_few[2][3][3] = {};
-            const int ti = nt == 256 ? 0 : (nt == 512 ? 1 : 2);
-            if (lds > 64 * 1024 && !attr_few[VEC][MODE][ti]) {
-                const void* fn = nt == 256 ? (const void*)k_solve_wave<MODE, VEC, 256, true>
-                                 : nt == 512 ? (const void*)k_solve_wave<MODE, VEC, 512, true> : (const void*)k_solve_wave<MODE, VEC, 1024, true>;
-                TBK_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                attr_few[VEC][MODE][ti] = true;
-            }
-            if (nt == 256)
-                hipLaunchKernelGGL((k_solve_wave<MODE, VEC, 256, true>), dim3((unsigned)nblocks), dim3(256), lds, ctx->stream, mv, nk, L,
-                                   G2, flag, (int)run, (cd*)nullptr, warm_few);
-            else if (nt == 512)
-                hipLaunchKernelGGL((k_solve_wave<MODE, VEC, 512, true>), dim3((unsigned)nblocks), dim3(512), lds, ctx->stream, mv, nk, L,
-                                   G2, flag, (int)run, (cd*)nullptr, warm_few);
-            else
-                hipLaunchKernelGGL((k_solve_wave<MODE, VEC, 1024, true>), dim3((unsigned)nblocks), dim3(1024), lds, ctx->stream, mv, nk,
-                                   L, G2, flag, (int)run, (cd*)nullptr, warm_few);
-            TBK_HIP(hipGetLastError());
-            return TBK_OK;
-        }
-        if (wbytes > ctx->work_bytes) {
-            TBK_HIP(hipStreamSynchronize(ctx->stream));
-            if (ctx->work) TBK_HIP(hipFree(ctx->work));
-            ctx->work = nullptr;
-            ctx->work_bytes = 0;
-            hipError_t e = hipMalloc(&ctx->work, wbytes);
-            TBK_REQUIRE(e == hipSuccess, TBK_ENOMEM, "eigen-solver workspace of %zu bytes: %s", wbytes, hipGetErrorString(e));
-            ctx->work_bytes = wbytes;
-        }
-        const int wg_nt = K.wg_nt;
-        if (wg_nt >= 1024)
-            hipLaunchKernelGGL((k_solve_wave<MODE, VEC, 1024, false>), dim3((unsigned)nblocks), dim3(1024), lds, ctx->stream, mv, nk,
-                               L, G2, flag, (int)run, (cd*)ctx->work, 0);
-        else
-            hipLaunchKernelGGL((k_solve_wave<MODE, VEC, 256>), dim3((unsigned)nblocks), dim3(256), lds, ctx->stream, mv, nk, L,
-                               G2, flag, (int)run, (cd*)ctx->work, 0);
-        TBK_HIP(hipGetLastError());
-        return TBK_OK;
-    }
+    if (regime == Regime::WgGlobal || regime == Regime::WgLds)
+        return launch_wave_workgroup<MODE, VEC>(ctx, mv, n, nk, nk_eff, L, G2, regime == Regime::WgLds);
     const bool with_t = wave_lds_bytes(n, true, mv.nR) <= 160 * 1024;   // else every point starts cold
     const size_t lds = wave_lds_bytes(n, with_t, mv.nR);
     TBK_REQUIRE(lds <= 160 * 1024, TBK_EUNSUPPORTED, "nsta=%d needs %zu bytes of LDS per wavefront", n, lds);
-    static bool attr_set[2][3] = {{false, false, false}, {false, false, false}};
-    if (lds > 64 * 1024 && !attr_set[VEC][MODE]) {
-        TBK_HIP(hipFuncSetAttribute((const void*)k_solve_wave<MODE, VEC, 64>,
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        attr_set[VEC][MODE] = true;
+    static bool attr_set = false;    // (per instantiation)
+    if (lds > 64 * 1024 && !attr_set) {
+        TBK_HIP(hipFuncSetAttribute((const void*)k_solve_wave<MODE, VEC, 64>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        attr_set = true;
     }
     // enough resident wavefronts to fill the chip
     const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(16, (160 * 1024) / lds));
@@ -2546,11 +2541,7 @@ static int launch_wave(tbk_ctx* ctx, const ModelView& mv, int n, int64_t nk, con
         run = 16;
         if (K.wave_run >= 0) run = std::max(1, K.wave_run);   // (1 = always cold)
         if (!with_t) run = 1;
-        const int last = G.last;
-        const int64_t off = G.off[last], nl = G.wv.mesh[last];
-        G2.wcfirst = off / run;
-        G2.wnchunk = (int)((off + nl - 1) / run - G2.wcfirst + 1);
-        nblocks = (G.wv.npts / nl) * G2.wnchunk;
+        nblocks = wave_mesh_chunks(G2, run);
     } else {
         // k list: contiguous runs by list position, at most 64 long
         run = std::max<int64_t>(1, std::min<int64_t>(64, (nk + want - 1) / want));
@@ -2796,43 +2787,242 @@ extern "C" int tbk_gen_ham(tbk_model* m, const double* k, int64_t nk, double* ha
 // ---------------------------------------------------------------------------
 // solve_on_grid
 // ---------------------------------------------------------------------------
-extern "C" int tbk_wfs_solve_grid_async(tbk_wfs* w, tbk_model* m, const double* start_k,
-                                        const double* pbc_phase, int64_t row0, int64_t global_n0) {
-    TBK_REQUIRE(w, TBK_EINVAL, "tbk_wfs_solve_grid: null argument");
-    int64_t off[TBK_MAX_DIM] = {row0, 0, 0, 0}, gm[TBK_MAX_DIM];
-    for (int d = 0; d < TBK_MAX_DIM; ++d) gm[d] = w->view.mesh[d];
-    gm[0] = global_n0;
-    return tbk_wfs_solve_window_async(w, m, start_k, pbc_phase, off, gm);
-}
-
 struct FusedFluxReq {
     int occ[2];
     int nocc;
 };
-static int solve_window_impl(tbk_wfs* w, tbk_model* m, const double* start_k, const double* pbc_phase, const int64_t* offset,
-                             const int64_t* global_mesh, const FusedFluxReq* ff);
 
-extern "C" int tbk_wfs_solve_window_async(tbk_wfs* w, tbk_model* m, const double* start_k,
-                                          const double* pbc_phase, const int64_t* offset,
-                                          const int64_t* global_mesh) {
-    return solve_window_impl(w, m, start_k, pbc_phase, offset, global_mesh, nullptr);
+// ---- the per-axis phase tables of the regular mesh: G.tz / G.tf / G.tf0 point into w->tab, which is rebuilt (k_grid_tables,
+// behind the upload of the boundary phases) only when something it depends on has changed
+static int grid_axis_tables(tbk_wfs* w, tbk_model* m, const double* start_k, const double* pbc_phase, const int64_t* offset,
+                            const int64_t* global_mesh, GridArgs& G) {
+    tbk_ctx* ctx = w->ctx;
+    const WfsView& v = w->view;
+    const int n = m->nsta, D = v.dim_arr;
+    std::vector<double> key;
+    key.reserve(1 + 3 * (size_t)D + (size_t)D * n * 2);
+    key.push_back((double)m->upload_id);
+    for (int d = 0; d < D; ++d) {
+        key.push_back(start_k[d]);
+        key.push_back((double)offset[d]);
+        key.push_back((double)global_mesh[d]);
+    }
+    key.insert(key.end(), pbc_phase, pbc_phase + (size_t)D * n * 2);
+    int64_t ntab = 0;
+    for (int d = 0; d < D; ++d) ntab += v.mesh[d];
+    const size_t need = (size_t)(ntab * (1 + n) + n) * sizeof(cd);   // (+ n: the last axis' phases at global index 0, GridArgs::tf0)
+    if (need > w->tab.bytes) {
+        const int rc = tbk_devbuf_grow(ctx->stream, w->tab, need, "tbk_wfs_solve_grid: mesh tables");
+        w->tab_key.clear();
+        if (rc) return rc;
+    }
+    cd* const tab = w->tab.as<cd>();
+    int64_t zo = 0, fo = ntab;
+    for (int d = 0; d < D; ++d) {
+        G.tz[d] = tab + zo;
+        G.tf[d] = tab + fo;
+        zo += v.mesh[d];
+        fo += (int64_t)v.mesh[d] * n;
+    }
+    G.tf0 = tab + ntab * (1 + n);
+    if (key == w->tab_key) return TBK_OK;
+    std::vector<cd> st((size_t)TBK_MAX_DIM * n, cd{0.0, 0.0});
+    for (int d = 0; d < D; ++d)
+        for (int o = 0; o < n; ++o)
+            st[d * n + o] = cd{pbc_phase[2 * (d * n + o)], pbc_phase[2 * (d * n + o) + 1]};
+    TBK_HIP(hipMemcpyAsync(w->pbc_dev, st.data(), st.size() * sizeof(cd), hipMemcpyHostToDevice, ctx->stream));
+    TBK_HIP(hipStreamSynchronize(ctx->stream));  // st is a local: finish before it dies
+    ProfScope ps(ctx, "grid_tables");
+    hipLaunchKernelGGL(k_grid_tables, dim3((unsigned)((ntab + 255) / 256)), dim3(256), 0, ctx->stream, m->view, G, tab, tab + ntab,
+                       tab + ntab * (1 + n));
+    TBK_HIP(hipGetLastError());
+    w->tab_key.swap(key);
+    return TBK_OK;
 }
 
-// solve_on_grid + berry_flux(occ, dirs = [0, 1]) of a 2-D array in one pass (tbk_solve_fused.inl); results through
-// tbk_wfs_solve_grid_result (min gaps) and tbk_berry_flux_result (the total).  TBK_EUNSUPPORTED where the fused kernel does
-// not apply (the caller then issues the two calls).
-extern "C" int tbk_wfs_solve_grid_flux_async(tbk_wfs* w, tbk_model* m, const double* start_k, const double* pbc_phase,
-                                             int64_t row0, int64_t global_n0, const int32_t* occ, int nocc) {
-    TBK_REQUIRE(w && occ, TBK_EINVAL, "tbk_wfs_solve_grid_flux: null argument");
-    TBK_REQUIRE(nocc >= 1 && nocc <= 2, TBK_EUNSUPPORTED, "tbk_wfs_solve_grid_flux: %d occupied bands (1 or 2)", nocc);
-    FusedFluxReq ff{{occ[0], nocc > 1 ? occ[1] : occ[0]}, nocc};
-    for (int a = 0; a < nocc; ++a)
-        TBK_REQUIRE(occ[a] >= 0 && occ[a] < w->view.nsta, TBK_EINVAL, "tbk_wfs_solve_grid_flux: band %d out of range", occ[a]);
-    TBK_REQUIRE(nocc == 1 || occ[0] != occ[1], TBK_EINVAL, "tbk_wfs_solve_grid_flux: repeated band");
-    int64_t off[TBK_MAX_DIM] = {row0, 0, 0, 0}, gm[TBK_MAX_DIM];
-    for (int d = 0; d < TBK_MAX_DIM; ++d) gm[d] = w->view.mesh[d];
-    gm[0] = global_n0;
-    return solve_window_impl(w, m, start_k, pbc_phase, off, gm, &ff);
+// ---- a cap on the resident wavefronts per SIMD, set through the LDS request (160 KB per CU / blocks per CU), the only
+// launch-time handle on occupancy.  A dynamic LDS request above 64 KB needs a function attribute these launches do not set:
+// occ = 1 (82 944 B) cannot be honoured and is an explicit error, not an opaque launch failure or a silently different kernel --
+// and not TBK_EUNSUPPORTED, which would send solve_on_grid_flux to the two-call path and an A/B run would time the wrong kernel
+// (ADVICE r3).  `knob`: the value of the environment variable `knob_name`; `occ_cap`: what applies (0: none).
+static int grid_occ_cap_lds(int knob, const char* knob_name, int occ_cap, size_t& lds) {
+    TBK_REQUIRE(knob != 1, TBK_EINVAL,
+                "%s=1 asks for %d bytes of LDS per workgroup (limit 65536 without a function attribute): use 2..7", knob_name,
+                160 * 1024 / 2 + 1024);
+    if (occ_cap > 0 && occ_cap < 8) lds = std::max(lds, (size_t)(160 * 1024) / (size_t)(occ_cap + 1) + 1024);
+    return TBK_OK;
+}
+
+// ---- gap partials of G.ntiles tiles: the row kernels' per-tile minima, which tbk_wfs_solve_grid_result reduces instead of the shards
+static int grid_gap_partials(tbk_wfs* w, int n, GridArgs& G) {
+    const size_t bytes = (size_t)(G.ntiles * std::max(n - 1, 1)) * sizeof(double);
+    const int rc = tbk_devbuf_grow(w->ctx->stream, w->gap_part, bytes, "tbk_wfs_solve_grid: gap partials");
+    if (rc) return rc;
+    G.gap_part = w->gap_part.as<double>();
+    w->gap_part_n = G.ntiles;
+    return TBK_OK;
+}
+
+static int launch_fused_seams(tbk_wfs* w, int n, const GridArgs& G, const FusedArgs& F, int nocc, int nseam, int64_t nsb);
+
+// ---- the fused kernel: 2-D arrays of 2 or 4 states, short-ranged along the last axis
+static int launch_grid_fused(tbk_wfs* w, tbk_model* m, GridArgs& G, const FusedFluxReq& ff) {
+    tbk_ctx* ctx = w->ctx;
+    const WfsView& v = w->view;
+    const int n = m->nsta, D = v.dim_arr, pm = m->view.pmax;
+    const TbkKnobs& K = tbk_knobs();
+    TBK_REQUIRE(D == 2 && (n == 2 || n == 4) && ff.nocc <= n && pm >= 0 && pm <= 2 && (n == 2 || pm == 1) &&
+                    K.grid_kernel != 1 && v.npts < (int64_t)0x7fffffff,
+                TBK_EUNSUPPORTED, "tbk_wfs_solve_grid_flux: a %d-D array of %d states (last-axis range %d): the fused kernel "
+                "serves 2-D arrays of 2 states (range <= 2) or 4 states (range 1)", D, n, pm);
+    // the fused kernel writes the flux partials itself: a reduction still pending on them is finished by its own launch first
+    int rc = tbk_flux_flush_pending(w, false);
+    if (rc) return rc;
+    FusedArgs F{};
+    // tile shape (measured, profiles/fused_sweep.py, us per step, rows R x chunks seg).  2048^2 (the array fits the 256 MiB
+    // last-level cache): R = 3 73-86, 4 67-79, 5 67-75, 6 65-74, 8 63-87, 12 63-66, best around 6 x 2.  4096^2 (beyond it): tall
+    // and narrow wins -- seg = 1: R = 4 303, 6 266, 8 258, 10 251, 12 257; seg >= 2: 275-318.  After the register diet (five
+    // wavefronts per SIMD, no column tables in LDS at seg = 1): 2048^2 flat over R = 5-12 (60-63), 4096^2 R = 8 257, 10 265
+    const bool in_llc = w->bytes <= ((int64_t)256 << 20) + (1 << 20);
+    F.R = K.fused_rows > 0 ? std::min(K.fused_rows, 16) : (in_llc ? 6 : 8);
+    F.nrg = (v.mesh[0] + F.R - 1) / F.R;
+    F.occ[0] = ff.occ[0];
+    F.occ[1] = ff.occ[1];
+    // wave tiles that fill the chip; beyond the cache no number of them is worth a second chunk (seg = 1 unless TBK_GRID_SEG says so)
+    const int64_t want = in_llc ? (int64_t)ctx->cus * 32 : INT64_MAX;
+    const int R1 = F.R + 1, ncell = (n * (n + 1) / 2) * (2 * pm + 1), ncar = ff.nocc * n + 1;
+    // LDS per wavefront: cells, leading-axis phases and carries of R + 1 rows, the staging tile, the per-column tables of
+    // `seg` chunks; at most 16 KB per wavefront
+    const size_t fixed_cd = (size_t)R1 * (ncell + n + ncar) + (size_t)64 * n;   // (k_grid_rows_flux: NB = 1 band staged at once)
+    const int seg_cap = (int)std::max<size_t>(1, (1024 - std::min<size_t>(fixed_cd, 960)) / ((size_t)64 * (1 + n)));
+    G.ntiles = tbk_tile_balance(G.cpr, F.nrg, want, seg_cap, K.grid_seg, true, &G.seg, &G.tpr);
+    const int nseam = G.tpr - 1;
+    const int64_t seam_threads = (int64_t)(v.mesh[0] - 1) * nseam;
+    const int64_t nsb = (seam_threads + 255) / 256;
+    // buffers: per-tile gap minima; flux partials (tiles, then seam blocks, two spare) and the total of the one slice
+    rc = grid_gap_partials(w, n, G);
+    if (rc) return rc;
+    rc = tbk_flux_buffers(w, 1, G.ntiles + nsb + 2, 0);
+    if (rc) return rc;
+    F.partial = w->flux_partial.as<double>();
+    size_t lds = (size_t)4 * (fixed_cd + (G.seg > 1 ? (size_t)G.seg * 64 * (1 + n) : 0)) * sizeof(cd);   // (seg = 1: no column tables in LDS)
+    // beyond the last-level cache FEWER resident wavefronts write faster (us per step at 4096^2 for 2 / 3 / 4 / 5 per SIMD:
+    // 284 / 245 / 259 / 263; at 2048^2: 72.0 / 61.7 / 59.5 / 58.7)
+    rc = grid_occ_cap_lds(K.fused_occ, "TBK_FUSED_OCC", K.fused_occ > 0 ? K.fused_occ : (in_llc ? 0 : 3), lds);
+    if (rc) return rc;
+    TBK_REQUIRE(lds <= 64 * 1024, TBK_EUNSUPPORTED, "tbk_wfs_solve_grid_flux: %zu bytes of LDS per block", lds);
+    const unsigned blocks = (unsigned)((G.ntiles + 3) / 4);
+    {
+        ProfScope ps(ctx, "solve_grid_flux");   // (the fused kernel alone)
+#define TBK_FUSED(NN, PP, OO) hipLaunchKernelGGL((k_grid_rows_flux<NN, PP, OO>), dim3(blocks), dim3(256), lds, ctx->stream, m->view, G, F)
+#define TBK_FUSED_N2(OO) { if (pm == 0) TBK_FUSED(2, 0, OO); else if (pm == 1) TBK_FUSED(2, 1, OO); else TBK_FUSED(2, 2, OO); }
+        if (n == 2 && ff.nocc == 1) TBK_FUSED_N2(1) else if (n == 2) TBK_FUSED_N2(2) else if (ff.nocc == 1) TBK_FUSED(4, 1, 1); else TBK_FUSED(4, 1, 2);
+#undef TBK_FUSED_N2
+#undef TBK_FUSED
+    }
+    return launch_fused_seams(w, n, G, F, ff.nocc, nseam, nsb);
+}
+
+// ---- the fused kernel's second launch: seams + total (k_flux_seams_sum); TBK_FUSED_SUM=0: the total by a kernel of its own
+static int launch_fused_seams(tbk_wfs* w, int n, const GridArgs& G, const FusedArgs& F, int nocc, int nseam, int64_t nsb) {
+    tbk_ctx* ctx = w->ctx;
+    const WfsView& v = w->view;
+    ProfScope ps2(ctx, "flux_seams_sum");
+    const bool own_sum = tbk_knobs().fused_sum == 0;
+    const unsigned sblocks = (unsigned)std::max<int64_t>(nsb, 1);
+    double* const blk_partial = F.partial + G.ntiles;
+#define TBK_SEAMS(NN, OO)                                                                                                              \
+    hipLaunchKernelGGL((k_flux_seams_sum<NN, OO>), dim3(sblocks), dim3(256), 0, ctx->stream, v, F.occ[0], F.occ[1], G.seg, nseam,        \
+                       (const double*)F.partial, own_sum ? (int64_t)0 : G.ntiles, blk_partial, w->flux_cnt.as<unsigned>(),                   \
+                       own_sum ? blk_partial + sblocks : w->flux_totals_dev)
+    if (n == 2 && nocc == 1) TBK_SEAMS(2, 1);
+    else if (n == 2) TBK_SEAMS(2, 2);
+    else if (nocc == 1) TBK_SEAMS(4, 1);
+    else TBK_SEAMS(4, 2);
+#undef TBK_SEAMS
+    if (own_sum)   // (the seam kernel's own total goes to a spare slot; the blocks' sums stand behind the tiles' partials)
+        hipLaunchKernelGGL(k_sum_fixed, dim3(1), dim3(1024), 0, ctx->stream, (const double*)F.partial, (int64_t)(G.ntiles + sblocks), w->flux_totals_dev);
+    TBK_HIP(hipGetLastError());
+    return TBK_OK;
+}
+
+// ---- k_grid_rows: the row-polynomial kernel of up to 4 states (`lds`: its LDS need), with a flux total left pending on this
+// array (tbk_berry_flux_async) riding along
+static int launch_grid_rows(tbk_wfs* w, tbk_model* m, GridArgs& G, size_t lds) {
+    tbk_ctx* ctx = w->ctx;
+    const int n = m->nsta, pm = m->view.pmax;
+    // (TBK_GRID_OCC: cap on the resident wavefronts per SIMD, diagnostic)
+    int rc = grid_occ_cap_lds(tbk_knobs().grid_occ, "TBK_GRID_OCC", tbk_knobs().grid_occ, lds);
+    if (rc) return rc;
+    unsigned blocks = (unsigned)((G.ntiles + 3) / 4);
+    rc = grid_gap_partials(w, n, G);
+    if (rc) return rc;
+    // the pending total: one workgroup more, behind the tiles' (grid_carried_flux_sum).  From here on the total has no
+    // completion word of its own: tbk_berry_flux_result waits for the stream.
+    if (const int red_n = tbk_flux_take_pending(w)) {
+        G.red_n = red_n;
+        G.red_partial = w->flux_partial.as<double>();
+        G.red_total = w->flux_totals_dev;
+        blocks += 1u;
+        lds = std::max(lds, (size_t)16 * sizeof(double));
+    }
+#define TBK_ROWS(NN, PP) hipLaunchKernelGGL((k_grid_rows<NN, PP>), dim3(blocks), dim3(256), lds, ctx->stream, m->view, G)
+#define TBK_ROWS_PM(NN)                    \
+    switch (pm) {                          \
+        case 0: TBK_ROWS(NN, 0); break;    \
+        case 1: TBK_ROWS(NN, 1); break;    \
+        case 2: TBK_ROWS(NN, 2); break;    \
+        case 3: TBK_ROWS(NN, 3); break;    \
+        case 4: TBK_ROWS(NN, 4); break;    \
+        default: TBK_ROWS(NN, -1); break;  \
+    }
+    // (ranges 0..4 along the last axis are compiled in, 0..2 for one state; the generic-range instance costs 1.7 x at 4 states:
+    // profiles/hop_range_probe.py)
+    if (n == 1) {
+        if (pm == 0) TBK_ROWS(1, 0); else if (pm == 1) TBK_ROWS(1, 1); else if (pm == 2) TBK_ROWS(1, 2); else TBK_ROWS(1, -1);
+    } else if (n == 2) { TBK_ROWS_PM(2) } else if (n == 3) { TBK_ROWS_PM(3) } else { TBK_ROWS_PM(4) }
+#undef TBK_ROWS_PM
+#undef TBK_ROWS
+    TBK_HIP(hipGetLastError());
+    return TBK_OK;
+}
+
+// ---- k_grid_small: very long-ranged models (or TBK_GRID_KERNEL=1) walk the term table per point
+static int launch_grid_small(tbk_ctx* ctx, tbk_model* m, const GridArgs& G) {
+    const unsigned blocks = (unsigned)((G.nchunks + 3) / 4);
+    switch (m->nsta) {
+        case 1: hipLaunchKernelGGL((k_grid_small<1>), dim3(blocks), dim3(256), 0, ctx->stream, m->view, G); break;
+        case 2: hipLaunchKernelGGL((k_grid_small<2>), dim3(blocks), dim3(256), 0, ctx->stream, m->view, G); break;
+        case 3: hipLaunchKernelGGL((k_grid_small<3>), dim3(blocks), dim3(256), 0, ctx->stream, m->view, G); break;
+        default: hipLaunchKernelGGL((k_grid_small<4>), dim3(blocks), dim3(256), 0, ctx->stream, m->view, G); break;
+    }
+    TBK_HIP(hipGetLastError());
+    return TBK_OK;
+}
+
+// ---- up to 4 states without the fused flux: the geometry of the row kernel (periodic images, tiles), then it or k_grid_small
+static int launch_grid_upto4(tbk_wfs* w, tbk_model* m, GridArgs& G) {
+    tbk_ctx* ctx = w->ctx;
+    const WfsView& v = w->view;
+    const int n = m->nsta, D = v.dim_arr;
+    TBK_REQUIRE(v.npts / v.mesh[D - 1] < (int64_t)0xffffffffu && G.nchunks < (int64_t)0x7fffffff * 4, TBK_EUNSUPPORTED,
+                "tbk_wfs_solve_grid: mesh too large for 32-bit row indices");
+    const int64_t nrows = v.npts / v.mesh[D - 1];
+    // wave tiles that fill the chip (n = 3, 4: 16 wavefronts per compute unit are resident since round 5, and a tile is a long
+    // chain of eigen-solves -- four rounds of shorter tiles measured 5 % faster than two rounds of tiles twice as long)
+    const int64_t want = (int64_t)ctx->cus * (n > 2 ? 64 : 32);
+    const size_t lds_rows_need = ((size_t)4 * (n * (n + 1) / 2) * (2 * m->view.pmax + 1) + (size_t)4 * rows_stage_slots(n)) * sizeof(cd);
+    const bool rows_kernel = lds_rows_need <= 48 * 1024 && tbk_knobs().grid_kernel != 1;     // (else k_grid_small: every column)
+    // the last column as the periodic image of the first (k_grid_rows): the whole last axis inside the window
+    // (TBK_GRID_IMG=0: every column solved on its own, the A/B and the reference for the bit-identity test)
+    G.img_last = rows_kernel && tbk_knobs().grid_img != 0 && v.mesh[D - 1] >= 2 && G.off[D - 1] == 0 && v.mesh[D - 1] == G.gmesh[D - 1] ? 1 : 0;
+    if (G.img_last) {
+        G.cpr = (v.mesh[D - 1] - 1 + 63) / 64;
+        G.nchunks = nrows * G.cpr;
+    }
+    G.img_win = rows_kernel && n > 2 && !G.img_last && G.off[D - 1] + v.mesh[D - 1] == G.gmesh[D - 1] ? 1 : 0;
+    G.ntiles = tbk_tile_balance(G.cpr, nrows, want, 8, tbk_knobs().grid_seg, false, &G.seg, &G.tpr);
+    return rows_kernel ? launch_grid_rows(w, m, G, lds_rows_need) : launch_grid_small(ctx, m, G);
 }
 
 static int solve_window_impl(tbk_wfs* w, tbk_model* m, const double* start_k, const double* pbc_phase, const int64_t* offset,
@@ -2872,50 +3062,8 @@ static int solve_window_impl(tbk_wfs* w, tbk_model* m, const double* start_k, co
     }
     G.pbc = w->pbc_dev;
     G.flags = ctx->flags_dev;
-    // everything the per-axis tables depend on; rebuild them only when it changes
-    std::vector<double> key;
-    key.push_back((double)m->upload_id);
-    for (int d = 0; d < D; ++d) {
-        key.push_back(start_k[d]);
-        key.push_back((double)offset[d]);
-        key.push_back((double)global_mesh[d]);
-    }
-    key.insert(key.end(), pbc_phase, pbc_phase + (size_t)D * n * 2);
-    int64_t ntab = 0;
-    for (int d = 0; d < D; ++d) ntab += v.mesh[d];
-    const int64_t need = ntab * (1 + n) + n;           // (+ n: the last axis' phases at global index 0, GridArgs::tf0)
-    if (w->tab_cap < need) {
-        TBK_HIP(hipStreamSynchronize(ctx->stream));
-        if (w->tab_dev) TBK_HIP(hipFree(w->tab_dev));
-        w->tab_dev = nullptr;
-        w->tab_cap = 0;
-        TBK_HIP(hipMalloc((void**)&w->tab_dev, need * sizeof(cd)));
-        w->tab_cap = need;
-        w->tab_key.clear();
-    }
-    {
-        int64_t zo = 0, fo = ntab;
-        for (int d = 0; d < D; ++d) {
-            G.tz[d] = w->tab_dev + zo;
-            G.tf[d] = w->tab_dev + fo;
-            zo += v.mesh[d];
-            fo += (int64_t)v.mesh[d] * n;
-        }
-        G.tf0 = w->tab_dev + ntab * (1 + n);
-    }
-    if (key != w->tab_key) {
-        std::vector<cd> st((size_t)TBK_MAX_DIM * n, cd{0.0, 0.0});
-        for (int d = 0; d < D; ++d)
-            for (int o = 0; o < n; ++o)
-                st[d * n + o] = cd{pbc_phase[2 * (d * n + o)], pbc_phase[2 * (d * n + o) + 1]};
-        TBK_HIP(hipMemcpyAsync(w->pbc_dev, st.data(), st.size() * sizeof(cd), hipMemcpyHostToDevice, ctx->stream));
-        TBK_HIP(hipStreamSynchronize(ctx->stream));  // st is a local: finish before it dies
-        ProfScope ps(ctx, "grid_tables");
-        hipLaunchKernelGGL(k_grid_tables, dim3((unsigned)((ntab + 255) / 256)), dim3(256), 0, ctx->stream, m->view, G,
-                           w->tab_dev, w->tab_dev + ntab, w->tab_dev + ntab * (1 + n));
-        TBK_HIP(hipGetLastError());
-        w->tab_key = key;
-    }
+    int rc = grid_axis_tables(w, m, start_k, pbc_phase, offset, global_mesh, G);
+    if (rc) return rc;
     // min gaps: this launch reduces into one parity and re-arms the other
     const size_t half = (size_t)TBK_GAP_SHARDS * w->view.ncomp;
     G.gaps = w->gaps_dev + (size_t)w->gaps_parity * half;
@@ -2930,227 +3078,48 @@ static int solve_window_impl(tbk_wfs* w, tbk_model* m, const double* start_k, co
 #ifdef TBK_DIAG
     G.ablate = tbk_knobs().ablate_grid;
 #endif
-    if (ff) {
-        // ---- the fused kernel: 2-D arrays of 2 or 4 states, short-ranged along the last axis
-        const int pm = m->view.pmax;
-        TBK_REQUIRE(D == 2 && (n == 2 || n == 4) && ff->nocc <= n && pm >= 0 && pm <= 2 && (n == 2 || pm == 1) &&
-                        tbk_knobs().grid_kernel != 1 && v.npts < (int64_t)0x7fffffff,
-                    TBK_EUNSUPPORTED, "tbk_wfs_solve_grid_flux: a %d-D array of %d states (last-axis range %d): the fused kernel "
-                    "serves 2-D arrays of 2 states (range <= 2) or 4 states (range 1)", D, n, pm);
-        const TbkKnobs& K = tbk_knobs();
-        // the fused kernel writes the flux partials itself: a reduction still pending on them is finished by its own launch first
-        {
-            const int rcp = tbk_flux_flush_pending(w, false);
-            if (rcp) return rcp;
-        }
-        FusedArgs F{};
-        // tile shape (measured, profiles/fused_sweep.py, us per step, rows R x chunks seg).  2048^2 (the array fits the 256 MiB
-        // last-level cache): R = 3 73-86, 4 67-79, 5 67-75, 6 65-74, 8 63-87, 12 63-66, best around 6 x 2.  4096^2 (beyond it): tall
-        // and narrow wins -- seg = 1: R = 4 303, 6 266, 8 258, 10 251, 12 257; seg >= 2: 275-318.  After the register diet (five
-        // wavefronts per SIMD, no column tables in LDS at seg = 1): 2048^2 flat over R = 5-12 (60-63), 4096^2 R = 8 257, 10 265
-        const bool in_llc = w->bytes <= ((int64_t)256 << 20) + (1 << 20);
-        F.R = K.fused_rows > 0 ? std::min(K.fused_rows, 16) : (in_llc ? 6 : 8);
-        F.nrg = (v.mesh[0] + F.R - 1) / F.R;
-        F.occ[0] = ff->occ[0];
-        F.occ[1] = ff->occ[1];
-        const int64_t want = (int64_t)ctx->cus * 32;     // wave tiles that fill the chip
-        const int R1 = F.R + 1, ncell = (n * (n + 1) / 2) * (2 * pm + 1), ncar = ff->nocc * n + 1;
-        // LDS per wavefront: cells, leading-axis phases and carries of R + 1 rows, the staging tile, the per-column tables of
-        // `seg` chunks; at most 16 KB per wavefront
-        const size_t fixed_cd = (size_t)R1 * (ncell + n + ncar) + (size_t)64 * n;   // (k_grid_rows_flux: NB = 1 band staged at once)
-        const int seg_cap = (int)std::max<size_t>(1, (1024 - std::min<size_t>(fixed_cd, 960)) / ((size_t)64 * (1 + n)));
-        G.seg = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(seg_cap, G.cpr), (int64_t)G.cpr * F.nrg / want));
-        if (!in_llc) G.seg = 1;
-        if (K.grid_seg >= 0) G.seg = std::max(1, std::min(std::min(K.grid_seg, seg_cap), G.cpr));
-        G.tpr = (G.cpr + G.seg - 1) / G.seg;
-        G.seg = (G.cpr + G.tpr - 1) / G.tpr;
-        G.ntiles = (int64_t)F.nrg * G.tpr;
-        const int nseam = G.tpr - 1;
-        const int64_t seam_threads = (int64_t)(v.mesh[0] - 1) * nseam;
-        const int64_t nsb = (seam_threads + 255) / 256;
-        // buffers: per-tile gap minima; flux partials (tiles, then seam blocks) and the total
-        const int64_t npart = G.ntiles * std::max(n - 1, 1);
-        if (w->gap_part_cap < npart) {
-            TBK_HIP(hipStreamSynchronize(ctx->stream));
-            if (w->gap_part_dev) TBK_HIP(hipFree(w->gap_part_dev));
-            w->gap_part_dev = nullptr;
-            w->gap_part_cap = 0;
-            TBK_HIP(hipMalloc((void**)&w->gap_part_dev, (size_t)npart * sizeof(double)));
-            w->gap_part_cap = npart;
-        }
-        G.gap_part = w->gap_part_dev;
-        w->gap_part_n = G.ntiles;
-        if (w->flux_nslices_cap < 1) {
-            TBK_HIP(hipStreamSynchronize(ctx->stream));
-            if (w->flux_cnt_dev) TBK_HIP(hipFree(w->flux_cnt_dev));
-            w->flux_cnt_dev = nullptr;
-            {
-                const int rct = tbk_wfs_totals_alloc(w, 1);
-                if (rct) return rct;
-            }
-            TBK_HIP(hipMalloc((void**)&w->flux_cnt_dev, 16 * sizeof(unsigned)));
-            TBK_HIP(hipMemsetAsync(w->flux_cnt_dev, 0, 16 * sizeof(unsigned), ctx->stream));
-            w->flux_nslices_cap = 1;
-        }
-        if (w->flux_partial_cap < G.ntiles + nsb + 2) {
-            TBK_HIP(hipStreamSynchronize(ctx->stream));
-            if (w->flux_partial_dev) TBK_HIP(hipFree(w->flux_partial_dev));
-            w->flux_partial_dev = nullptr;
-            TBK_HIP(hipMalloc((void**)&w->flux_partial_dev, (size_t)(G.ntiles + nsb + 2) * sizeof(double)));
-            w->flux_partial_cap = G.ntiles + nsb + 2;
-        }
-        w->flux_nslices = 1;
-        w->flux_plaq_n = 0;
-        F.partial = w->flux_partial_dev;
-        size_t lds = (size_t)4 * (fixed_cd + (G.seg > 1 ? (size_t)G.seg * 64 * (1 + n) : 0)) * sizeof(cd);   // (seg = 1: no column tables in LDS)
-        // beyond the last-level cache FEWER resident wavefronts write faster (us per step at 4096^2 for 2 / 3 / 4 / 5 per SIMD:
-        // 284 / 245 / 259 / 263; at 2048^2: 72.0 / 61.7 / 59.5 / 58.7): the cap is set through the LDS request (160 KB per CU /
-        // blocks per CU), the only launch-time handle on occupancy
-        const int occ_cap = K.fused_occ > 0 ? K.fused_occ : (in_llc ? 0 : 3);
-        // (a knob that cannot be honoured is an error of its own kind: TBK_EUNSUPPORTED would send solve_on_grid_flux to the
-        // two-call path and an A/B run would time the wrong kernel -- ADVICE r3)
-        TBK_REQUIRE(K.fused_occ != 1, TBK_EINVAL,
-                    "TBK_FUSED_OCC=1 asks for %d bytes of LDS per workgroup (limit 65536 without a function attribute): use 2..7",
-                    160 * 1024 / 2 + 1024);
-        if (occ_cap > 0 && occ_cap < 8) lds = std::max(lds, (size_t)(160 * 1024) / (size_t)(occ_cap + 1) + 1024);
-        TBK_REQUIRE(lds <= 64 * 1024, TBK_EUNSUPPORTED, "tbk_wfs_solve_grid_flux: %zu bytes of LDS per block", lds);
-        const unsigned blocks = (unsigned)((G.ntiles + 3) / 4);
-        {
-        ProfScope ps(ctx, "solve_grid_flux");   // (the fused kernel alone)
-#define TBK_FUSED(NN, PP, OO) hipLaunchKernelGGL((k_grid_rows_flux<NN, PP, OO>), dim3(blocks), dim3(256), lds, ctx->stream, m->view, G, F)
-        if (n == 2 && ff->nocc == 1) {
-            if (pm == 0) TBK_FUSED(2, 0, 1); else if (pm == 1) TBK_FUSED(2, 1, 1); else TBK_FUSED(2, 2, 1);
-        } else if (n == 2) {
-            if (pm == 0) TBK_FUSED(2, 0, 2); else if (pm == 1) TBK_FUSED(2, 1, 2); else TBK_FUSED(2, 2, 2);
-        } else if (ff->nocc == 1) {
-            TBK_FUSED(4, 1, 1);
-        } else {
-            TBK_FUSED(4, 1, 2);
-        }
-#undef TBK_FUSED
-        }
-        // ---- seams + total in one launch (k_flux_seams_sum); TBK_FUSED_SUM=0: the total by a kernel of its own
-        ProfScope ps2(ctx, "flux_seams_sum");
-        const bool own_sum = K.fused_sum == 0;
-        const unsigned sblocks = (unsigned)std::max<int64_t>(nsb, 1);
-        double* const blk_partial = F.partial + G.ntiles;
-#define TBK_SEAMS(NN, OO)                                                                                                              \
-    hipLaunchKernelGGL((k_flux_seams_sum<NN, OO>), dim3(sblocks), dim3(256), 0, ctx->stream, v, F.occ[0], F.occ[1], G.seg, nseam,        \
-                       (const double*)F.partial, own_sum ? (int64_t)0 : G.ntiles, blk_partial, w->flux_cnt_dev,                            \
-                       own_sum ? blk_partial + sblocks : w->flux_totals_dev)
-        if (n == 2 && ff->nocc == 1) TBK_SEAMS(2, 1);
-        else if (n == 2) TBK_SEAMS(2, 2);
-        else if (ff->nocc == 1) TBK_SEAMS(4, 1);
-        else TBK_SEAMS(4, 2);
-#undef TBK_SEAMS
-        if (own_sum)   // (the seam kernel's own total goes to a spare slot; the blocks' sums stand behind the tiles' partials)
-            hipLaunchKernelGGL(k_sum_fixed, dim3(1), dim3(1024), 0, ctx->stream, (const double*)F.partial, (int64_t)(G.ntiles + sblocks), w->flux_totals_dev);
-        TBK_HIP(hipGetLastError());
-        return TBK_OK;
-    }
+    if (ff) return launch_grid_fused(w, m, G, *ff);
     ProfScope ps(ctx, "solve_grid");
-    if (n <= 4) {
-        TBK_REQUIRE(v.npts / v.mesh[D - 1] < (int64_t)0xffffffffu && G.nchunks < (int64_t)0x7fffffff * 4, TBK_EUNSUPPORTED,
-                    "tbk_wfs_solve_grid: mesh too large for 32-bit row indices");
-        const int64_t nrows = v.npts / v.mesh[D - 1];
-        // wave tiles that fill the chip (n = 3, 4: 16 wavefronts per compute unit are resident since round 5, and a tile is a long
-        // chain of eigen-solves -- four rounds of shorter tiles measured 5 % faster than two rounds of tiles twice as long)
-        const int64_t want = (int64_t)ctx->cus * (n > 2 ? 64 : 32);
-        // the last column as the periodic image of the first (k_grid_rows): the whole last axis inside the window
-        // (TBK_GRID_IMG=0: every column solved on its own, the A/B and the reference for the bit-identity test)
-        const size_t lds_rows_need = ((size_t)4 * (n * (n + 1) / 2) * (2 * m->view.pmax + 1) + (size_t)4 * rows_stage_slots(n)) * sizeof(cd);
-        const bool rows_kernel = lds_rows_need <= 48 * 1024 && tbk_knobs().grid_kernel != 1;     // (else k_grid_small: every column)
-        G.img_last = rows_kernel && tbk_knobs().grid_img != 0 && v.mesh[D - 1] >= 2 && G.off[D - 1] == 0 && v.mesh[D - 1] == G.gmesh[D - 1] ? 1 : 0;
-        if (G.img_last) {
-            G.cpr = (v.mesh[D - 1] - 1 + 63) / 64;
-            G.nchunks = nrows * G.cpr;
-        }
-        G.img_win = rows_kernel && n > 2 && !G.img_last && G.off[D - 1] + v.mesh[D - 1] == G.gmesh[D - 1] ? 1 : 0;
-        G.seg = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(8, G.cpr), G.nchunks / want));
-        if (tbk_knobs().grid_seg >= 0) G.seg = std::max(1, std::min(tbk_knobs().grid_seg, G.cpr));
-        G.tpr = (G.cpr + G.seg - 1) / G.seg;
-        G.seg = (G.cpr + G.tpr - 1) / G.tpr;             // balance the tiles of a row (33 chunks -> 7,7,7,7,5)
-        G.ntiles = nrows * G.tpr;
-        size_t lds = lds_rows_need;
-        if (lds <= 48 * 1024 && tbk_knobs().grid_kernel != 1) {
-            // (TBK_GRID_OCC: cap on the resident wavefronts per SIMD through the LDS request, as in the fused pass)
-            // A dynamic LDS request above 64 KB needs a function attribute this launch does not set: occ = 1 (82 944 B) cannot
-            // be honoured and is an explicit error, not an opaque launch failure or a silently different kernel
-            TBK_REQUIRE(tbk_knobs().grid_occ != 1, TBK_EINVAL,
-                        "TBK_GRID_OCC=1 asks for %d bytes of LDS per workgroup (limit 65536 without a function attribute): use 2..7",
-                        160 * 1024 / 2 + 1024);
-            if (tbk_knobs().grid_occ > 0 && tbk_knobs().grid_occ < 8)
-                lds = std::max(lds, (size_t)(160 * 1024) / (size_t)(tbk_knobs().grid_occ + 1) + 1024);
-            unsigned blocks = (unsigned)((G.ntiles + 3) / 4);
-            const int64_t npart = G.ntiles * std::max(n - 1, 1);
-            if (w->gap_part_cap < npart) {
-                TBK_HIP(hipStreamSynchronize(ctx->stream));
-                if (w->gap_part_dev) TBK_HIP(hipFree(w->gap_part_dev));
-                w->gap_part_dev = nullptr;
-                w->gap_part_cap = 0;
-                TBK_HIP(hipMalloc((void**)&w->gap_part_dev, (size_t)npart * sizeof(double)));
-                w->gap_part_cap = npart;
-            }
-            G.gap_part = w->gap_part_dev;
-            w->gap_part_n = G.ntiles;       // tbk_wfs_solve_grid_result reduces these instead of the shards
-            // a flux total left pending on this array (tbk_berry_flux_async) rides along: one workgroup more, behind the tiles'
-            // (grid_carried_flux_sum).  From here on the total has no completion word of its own: tbk_berry_flux_result waits for
-            // the stream.
-            if (w->flux_pend_n > 0 && w->flux_pend_nslices == 1) {
-                G.red_n = w->flux_pend_n;
-                G.red_partial = w->flux_partial_dev;
-                G.red_total = w->flux_totals_dev;
-                blocks += 1u;
-                lds = std::max(lds, (size_t)16 * sizeof(double));
-                w->flux_pend_n = 0;
-                w->flux_pend_nslices = 0;
-            }
-#define TBK_ROWS(NN, PP) hipLaunchKernelGGL((k_grid_rows<NN, PP>), dim3(blocks), dim3(256), lds, ctx->stream, m->view, G)
-            const int pm = m->view.pmax;
-            // (ranges 0..4 along the last axis are compiled in; the generic-range instance costs 1.7 x at 4 states:
-            // profiles/hop_range_probe.py)
-            switch (n * 8 + (pm <= 4 ? pm : 5)) {
-                case 8 + 0: TBK_ROWS(1, 0); break;
-                case 8 + 1: TBK_ROWS(1, 1); break;
-                case 8 + 2: TBK_ROWS(1, 2); break;
-                case 8 + 3: case 8 + 4: case 8 + 5: TBK_ROWS(1, -1); break;
-                case 16 + 0: TBK_ROWS(2, 0); break;
-                case 16 + 1: TBK_ROWS(2, 1); break;
-                case 16 + 2: TBK_ROWS(2, 2); break;
-                case 16 + 3: TBK_ROWS(2, 3); break;
-                case 16 + 4: TBK_ROWS(2, 4); break;
-                case 16 + 5: TBK_ROWS(2, -1); break;
-                case 24 + 0: TBK_ROWS(3, 0); break;
-                case 24 + 1: TBK_ROWS(3, 1); break;
-                case 24 + 2: TBK_ROWS(3, 2); break;
-                case 24 + 3: TBK_ROWS(3, 3); break;
-                case 24 + 4: TBK_ROWS(3, 4); break;
-                case 24 + 5: TBK_ROWS(3, -1); break;
-                case 32 + 0: TBK_ROWS(4, 0); break;
-                case 32 + 1: TBK_ROWS(4, 1); break;
-                case 32 + 2: TBK_ROWS(4, 2); break;
-                case 32 + 3: TBK_ROWS(4, 3); break;
-                case 32 + 4: TBK_ROWS(4, 4); break;
-                default: TBK_ROWS(4, -1); break;
-            }
-#undef TBK_ROWS
-        } else {   // very long-ranged models: walk the term table per point
-            const unsigned blocks = (unsigned)((G.nchunks + 3) / 4);
-            switch (n) {
-                case 1: hipLaunchKernelGGL((k_grid_small<1>), dim3(blocks), dim3(256), 0, ctx->stream, m->view, G); break;
-                case 2: hipLaunchKernelGGL((k_grid_small<2>), dim3(blocks), dim3(256), 0, ctx->stream, m->view, G); break;
-                case 3: hipLaunchKernelGGL((k_grid_small<3>), dim3(blocks), dim3(256), 0, ctx->stream, m->view, G); break;
-                default: hipLaunchKernelGGL((k_grid_small<4>), dim3(blocks), dim3(256), 0, ctx->stream, m->view, G); break;
-            }
-        }
-        TBK_HIP(hipGetLastError());
-        return TBK_OK;
-    }
-    {   // wavefront-per-matrix path re-arms the other parity with a tiny memset-like kernel
-        hipLaunchKernelGGL(k_arm_gaps, dim3(1), dim3(256), 0, ctx->stream, G.gaps_next, n);
-    }
+    if (n <= 4) return launch_grid_upto4(w, m, G);
+    // the wavefront-per-matrix paths re-arm the other parity with a tiny memset-like kernel, then take the mesh as a batch
+    hipLaunchKernelGGL(k_arm_gaps, dim3(1), dim3(256), 0, ctx->stream, G.gaps_next, n);
     ListArgs L{};
     return launch_wave<1, true>(ctx, m->view, n, v.npts, L, G);
+}
+
+// rows [row0, row0 + mesh[0]) of a mesh whose leading axis has global_n0 points: the window form of the two entries below
+static int solve_rows_window(tbk_wfs* w, tbk_model* m, const double* start_k, const double* pbc_phase, int64_t row0,
+                             int64_t global_n0, const FusedFluxReq* ff) {
+    int64_t off[TBK_MAX_DIM] = {row0, 0, 0, 0}, gm[TBK_MAX_DIM];
+    for (int d = 0; d < TBK_MAX_DIM; ++d) gm[d] = w->view.mesh[d];
+    gm[0] = global_n0;
+    return solve_window_impl(w, m, start_k, pbc_phase, off, gm, ff);
+}
+
+extern "C" int tbk_wfs_solve_grid_async(tbk_wfs* w, tbk_model* m, const double* start_k,
+                                        const double* pbc_phase, int64_t row0, int64_t global_n0) {
+    TBK_REQUIRE(w, TBK_EINVAL, "tbk_wfs_solve_grid: null argument");
+    return solve_rows_window(w, m, start_k, pbc_phase, row0, global_n0, nullptr);
+}
+
+extern "C" int tbk_wfs_solve_window_async(tbk_wfs* w, tbk_model* m, const double* start_k,
+                                          const double* pbc_phase, const int64_t* offset,
+                                          const int64_t* global_mesh) {
+    return solve_window_impl(w, m, start_k, pbc_phase, offset, global_mesh, nullptr);
+}
+
+// solve_on_grid + berry_flux(occ, dirs = [0, 1]) of a 2-D array in one pass (tbk_solve_fused.inl); results through
+// tbk_wfs_solve_grid_result (min gaps) and tbk_berry_flux_result (the total).  TBK_EUNSUPPORTED where the fused kernel does
+// not apply (the caller then issues the two calls).
+extern "C" int tbk_wfs_solve_grid_flux_async(tbk_wfs* w, tbk_model* m, const double* start_k, const double* pbc_phase,
+                                             int64_t row0, int64_t global_n0, const int32_t* occ, int nocc) {
+    TBK_REQUIRE(w && occ, TBK_EINVAL, "tbk_wfs_solve_grid_flux: null argument");
+    TBK_REQUIRE(nocc >= 1 && nocc <= 2, TBK_EUNSUPPORTED, "tbk_wfs_solve_grid_flux: %d occupied bands (1 or 2)", nocc);
+    FusedFluxReq ff{{occ[0], nocc > 1 ? occ[1] : occ[0]}, nocc};
+    for (int a = 0; a < nocc; ++a)
+        TBK_REQUIRE(occ[a] >= 0 && occ[a] < w->view.nsta, TBK_EINVAL, "tbk_wfs_solve_grid_flux: band %d out of range", occ[a]);
+    TBK_REQUIRE(nocc == 1 || occ[0] != occ[1], TBK_EINVAL, "tbk_wfs_solve_grid_flux: repeated band");
+    return solve_rows_window(w, m, start_k, pbc_phase, row0, global_n0, &ff);
 }
 
 static int solve_grid_result_once(tbk_wfs* w, double* min_gaps, bool can_retry) {
@@ -3173,7 +3142,7 @@ static int solve_grid_result_once(tbk_wfs* w, double* min_gaps, bool can_retry) 
         // with the gaps in mapped memory the reduction is the call's last kernel: it also copies the status words and stores the
         // completion word the host polls (tbk_done_wait) -- no hipStreamSynchronize, no second round trip for the status
         const DoneArgs done = zh ? tbk_done_arm(ctx, w->view.nsta > 2) : DoneArgs{nullptr, nullptr, nullptr, 0u};
-        hipLaunchKernelGGL(k_gap_part_reduce, dim3(w->gaps_n), dim3(1024), 0, ctx->stream, w->gap_part_dev, w->gap_part_n,
+        hipLaunchKernelGGL(k_gap_part_reduce, dim3(w->gaps_n), dim3(1024), 0, ctx->stream, w->gap_part.as<double>(), w->gap_part_n,
                            w->gaps_n, out_dev, done);
         TBK_HIP(hipGetLastError());
         if (zh) {

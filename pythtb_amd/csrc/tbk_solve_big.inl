@@ -347,21 +347,14 @@ static int launch_big(tbk_ctx* ctx, const ModelView& mv, int n, int64_t nk, cons
                        al((size_t)n * sizeof(int)) + al((size_t)nbn * 2 * sizeof(double));
     size_t free_b = 0, total_b = 0;
     TBK_HIP(hipMemGetInfo(&free_b, &total_b));
-    const size_t budget = std::max<size_t>(per, std::min<size_t>((size_t)8 << 30, (free_b + ctx->work_bytes) / 2));
+    const size_t budget = std::max<size_t>(per, std::min<size_t>((size_t)8 << 30, (free_b + ctx->work.bytes) / 2));
     int64_t B = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(nk, 32768), (int64_t)(budget / per)));
     if (tbk_knobs().big_batch >= 0) B = std::max<int64_t>(1, std::min<int64_t>(B, tbk_knobs().big_batch));   // test hook: matrices per batch
     const size_t wbytes = (size_t)B * per + al((size_t)B * sizeof(int)) * 2 + 256;
-    if (wbytes > ctx->work_bytes) {
-        TBK_HIP(hipStreamSynchronize(ctx->stream));
-        if (ctx->work) TBK_HIP(hipFree(ctx->work));
-        ctx->work = nullptr;
-        ctx->work_bytes = 0;
-        hipError_t e = hipMalloc(&ctx->work, wbytes);
-        TBK_REQUIRE(e == hipSuccess, TBK_ENOMEM, "eigen-solver workspace of %zu bytes: %s", wbytes, hipGetErrorString(e));
-        ctx->work_bytes = wbytes;
-    }
+    void* wsp = nullptr;
+    if (const int rcw = tbk_ctx_work(ctx, wbytes, "eigen-solver workspace", &wsp)) return rcw;
     BigWs W{};
-    unsigned char* p = (unsigned char*)ctx->work;
+    unsigned char* p = (unsigned char*)wsp;
     W.pending = (int*)p;
     p += 256;
     W.A0 = (cd*)p;

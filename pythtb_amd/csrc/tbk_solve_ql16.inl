@@ -700,16 +700,9 @@ static int launch_ql16(tbk_ctx* ctx, const ModelView& mv, int64_t nk, const List
         // and its latency exceeds what the replication costs; TBK_QL16_EVONLY=0: always the single replicated kernel)
         if (tbk_knobs().ql16_evonly != 0 && nk >= 8192) {
             const size_t wbytes = (size_t)nk * 16 * sizeof(double2);
-            if (wbytes > ctx->work_bytes) {
-                TBK_HIP(hipStreamSynchronize(ctx->stream));
-                if (ctx->work) TBK_HIP(hipFree(ctx->work));
-                ctx->work = nullptr;
-                ctx->work_bytes = 0;
-                hipError_t e = hipMalloc(&ctx->work, wbytes);
-                TBK_REQUIRE(e == hipSuccess, TBK_ENOMEM, "tridiagonal workspace of %zu bytes: %s", wbytes, hipGetErrorString(e));
-                ctx->work_bytes = wbytes;
-            }
-            double2* de = (double2*)ctx->work;
+            void* wsp = nullptr;
+            if (const int rcw = tbk_ctx_work(ctx, wbytes, "tridiagonal workspace", &wsp)) return rcw;
+            double2* de = (double2*)wsp;
             hipLaunchKernelGGL((k_solve_ql16<MODE, false, 1>), dim3(blocks), dim3(256), 0, ctx->stream, mv, nk, L, G, ctx->flags_dev, de,
                                (int64_t)0, nk);
             hipLaunchKernelGGL(k_tridiag_eigvals, dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, ctx->stream, mv.nsta, nk,
@@ -735,16 +728,9 @@ static int launch_ql16(tbk_ctx* ctx, const ModelView& mv, int64_t nk, const List
             chunk = (nk + (nk + chunk - 1) / chunk - 1) / ((nk + chunk - 1) / chunk);
             const size_t wbytes = al((size_t)chunk * 16 * sizeof(double2)) + al((size_t)chunk * scap * 16 * sizeof(double2)) +
                                   al((size_t)chunk * scap * sizeof(unsigned)) + al((size_t)chunk * sizeof(int)) + al((size_t)chunk * 16) + 1024;
-            if (wbytes > ctx->work_bytes) {
-                TBK_HIP(hipStreamSynchronize(ctx->stream));
-                if (ctx->work) TBK_HIP(hipFree(ctx->work));
-                ctx->work = nullptr;
-                ctx->work_bytes = 0;
-                hipError_t e = hipMalloc(&ctx->work, wbytes);
-                TBK_REQUIRE(e == hipSuccess, TBK_ENOMEM, "QL record workspace of %zu bytes: %s", wbytes, hipGetErrorString(e));
-                ctx->work_bytes = wbytes;
-            }
-            unsigned char* p = (unsigned char*)ctx->work;
+            void* wsp = nullptr;
+            if (const int rcw = tbk_ctx_work(ctx, wbytes, "QL record workspace", &wsp)) return rcw;
+            unsigned char* p = (unsigned char*)wsp;
             double2* de = (double2*)p;
             p += al((size_t)chunk * 16 * sizeof(double2));
             Ql16Rec R{};

@@ -796,19 +796,12 @@ static int launch_qlw(tbk_ctx* ctx, const ModelView& mv, int n, int64_t nk, cons
                           (tw32 ? al((size_t)chunk * n * sizeof(double)) + al((size_t)chunk * sizeof(uint2)) + al((size_t)chunk * sizeof(int)) + 256 : 0) +
                           (refl || hintq ? al((size_t)chunk * hh32_rec_size(nm32) * sizeof(cd)) : 0);
     const size_t wbytes = wone * ns;
-    if (wbytes > ctx->work_bytes) {
-        TBK_HIP(hipStreamSynchronize(ctx->stream));
-        if (ctx->work) TBK_HIP(hipFree(ctx->work));
-        ctx->work = nullptr;
-        ctx->work_bytes = 0;
-        hipError_t e = hipMalloc(&ctx->work, wbytes);
-        TBK_REQUIRE(e == hipSuccess, TBK_ENOMEM, "tridiagonal-path workspace of %zu bytes: %s", wbytes, hipGetErrorString(e));
-        ctx->work_bytes = wbytes;
-    }
+    void* wsp = nullptr;
+    if (const int rcw = tbk_ctx_work(ctx, wbytes, "tridiagonal-path workspace", &wsp)) return rcw;
     QlwWork Wsl[3];
     for (int sl = 0; sl < ns; ++sl) {
     QlwWork W{};
-    unsigned char* p = (unsigned char*)ctx->work + (size_t)sl * wone;
+    unsigned char* p = (unsigned char*)wsp + (size_t)sl * wone;
     W.de = (double2*)p;
     p += al((size_t)chunk * n * sizeof(double2));
     p += 256;                                  // (the back-transform's eight-entry loads may start before a sweep's first entry)

@@ -298,21 +298,14 @@ static int launch_trig(tbk_ctx* ctx, const ModelView& mv, int n, int64_t nk, con
     const size_t per = al((size_t)n * n * sizeof(cd)) + al((size_t)n * sizeof(double2));
     size_t free_b = 0, total_b = 0;
     TBK_HIP(hipMemGetInfo(&free_b, &total_b));
-    const size_t budget = std::max<size_t>(per, std::min<size_t>((size_t)4 << 30, (free_b + ctx->work_bytes) / 2));
+    const size_t budget = std::max<size_t>(per, std::min<size_t>((size_t)4 << 30, (free_b + ctx->work.bytes) / 2));
     int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(nk, (int64_t)(budget / per)));
     chunk = (nk + (nk + chunk - 1) / chunk - 1) / ((nk + chunk - 1) / chunk);
     const size_t wbytes = (size_t)chunk * per + 256;
-    if (wbytes > ctx->work_bytes) {
-        TBK_HIP(hipStreamSynchronize(ctx->stream));
-        if (ctx->work) TBK_HIP(hipFree(ctx->work));
-        ctx->work = nullptr;
-        ctx->work_bytes = 0;
-        hipError_t e = hipMalloc(&ctx->work, wbytes);
-        TBK_REQUIRE(e == hipSuccess, TBK_ENOMEM, "tridiagonalisation workspace of %zu bytes: %s", wbytes, hipGetErrorString(e));
-        ctx->work_bytes = wbytes;
-    }
-    cd* work = (cd*)ctx->work;
-    double2* de = (double2*)((unsigned char*)ctx->work + (size_t)chunk * al((size_t)n * n * sizeof(cd)));
+    void* wsp = nullptr;
+    if (const int rcw = tbk_ctx_work(ctx, wbytes, "tridiagonalisation workspace", &wsp)) return rcw;
+    cd* work = (cd*)wsp;
+    double2* de = (double2*)((unsigned char*)wsp + (size_t)chunk * al((size_t)n * n * sizeof(cd)));
     const int nR = MODE == 2 ? 0 : mv.nR;
     const size_t lds_vec = ((size_t)5 * n + std::max(nR, 1) + 2) * sizeof(cd) + (((size_t)n + 16 + 1) & ~(size_t)1) * sizeof(double);
     const size_t lds_a = (size_t)n * (n | 1) * sizeof(cd);

@@ -386,21 +386,14 @@ static int launch_trigv(tbk_ctx* ctx, const ModelView& mv, int n, int64_t nk, co
                        al((size_t)n * sizeof(double)) + 64;
     size_t free_b = 0, total_b = 0;
     TBK_HIP(hipMemGetInfo(&free_b, &total_b));
-    const size_t budget = std::max<size_t>(per, std::min<size_t>((size_t)6 << 30, (free_b + ctx->work_bytes) / 2));
+    const size_t budget = std::max<size_t>(per, std::min<size_t>((size_t)6 << 30, (free_b + ctx->work.bytes) / 2));
     int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(nk, (int64_t)(budget / per)));
     chunk = (nk + (nk + chunk - 1) / chunk - 1) / ((nk + chunk - 1) / chunk);
     const size_t wbytes = al((size_t)chunk * nn * sizeof(cd)) + 3 * al((size_t)chunk * nn * sizeof(double)) + al((size_t)chunk * n * sizeof(double2)) +
                           al((size_t)chunk * n * 3 * sizeof(double2)) + al((size_t)chunk * n * sizeof(double)) + al((size_t)chunk * 2 * sizeof(unsigned long long)) + 256;
-    if (wbytes > ctx->work_bytes) {
-        TBK_HIP(hipStreamSynchronize(ctx->stream));
-        if (ctx->work) TBK_HIP(hipFree(ctx->work));
-        ctx->work = nullptr;
-        ctx->work_bytes = 0;
-        hipError_t e = hipMalloc(&ctx->work, wbytes);
-        TBK_REQUIRE(e == hipSuccess, TBK_ENOMEM, "tridiagonalisation workspace of %zu bytes: %s", wbytes, hipGetErrorString(e));
-        ctx->work_bytes = wbytes;
-    }
-    unsigned char* p = (unsigned char*)ctx->work;
+    void* wsp = nullptr;
+    if (const int rcw = tbk_ctx_work(ctx, wbytes, "tridiagonalisation workspace", &wsp)) return rcw;
+    unsigned char* p = (unsigned char*)wsp;
     cd* work = (cd*)p;
     p += al((size_t)chunk * nn * sizeof(cd));
     double* V = (double*)p;

@@ -645,18 +645,11 @@ static int launch_tw16(tbk_ctx* ctx, const ModelView& mv, int64_t nk, const List
                         al((size_t)chunk * scap * 16 * sizeof(double2)) + al((size_t)chunk * scap * sizeof(unsigned)) +
                         al((size_t)chunk * sizeof(int)) + al((size_t)chunk * 16) + 1024;
     const size_t wbytes = wone * ns;
-    if (wbytes > ctx->work_bytes) {
-        TBK_HIP(hipStreamSynchronize(ctx->stream));
-        if (ctx->work) TBK_HIP(hipFree(ctx->work));
-        ctx->work = nullptr;
-        ctx->work_bytes = 0;
-        hipError_t e = hipMalloc(&ctx->work, wbytes);
-        TBK_REQUIRE(e == hipSuccess, TBK_ENOMEM, "tridiagonal workspace of %zu bytes: %s", wbytes, hipGetErrorString(e));
-        ctx->work_bytes = wbytes;
-    }
+    void* wsp = nullptr;
+    if (const int rcw = tbk_ctx_work(ctx, wbytes, "tridiagonal workspace", &wsp)) return rcw;
     Tw16Work W[3];
     for (int s = 0; s < ns; ++s) {
-        unsigned char* p = (unsigned char*)ctx->work + (size_t)s * wone;
+        unsigned char* p = (unsigned char*)wsp + (size_t)s * wone;
         W[s].de = (double2*)p;
         p += al((size_t)chunk * 16 * sizeof(double2));
         W[s].refl = (cd*)p;

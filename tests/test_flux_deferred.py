@@ -273,3 +273,46 @@ def test_solve_that_carried_a_reduction_is_unchanged(tb, models, size):
     assert np.array_equal(vec_carry.view(np.uint64), vec_plain.view(np.uint64))
     assert np.abs(vec_plain).max() > 0.1
     assert same(tot, reference(tb, models, size))
+
+
+def _fresh_copy(tb, w, model, mesh):
+    """A new wf_array (a new device array: none of its buffers sized yet) holding the vectors of `w`."""
+    f = tb.wf_array(model, mesh)
+    f._wfs = np.array(w.to_host())
+    return f
+
+
+def test_one_array_buffers_grow_and_shrink_3d(tb):
+    """The per-array buffers (totals and counters, partials, plaquettes) of ONE array through planes of 20, 8 and 9 slices, with
+    and without plaquettes, each route sizing them after another has: every result equals, bit for bit, the same call on a fresh
+    array holding the same vectors."""
+    mesh = [9, 8, 20]
+    m = hp.random_model(tb.tb_model, 2, 3, 1, seed=77, nhop=8, rmax=1)
+    w = tb.wf_array(m, mesh)
+    w.solve_on_grid([0.01, 0.02, 0.03])
+    calls = [((0, 1), False), ((1, 2), True), ((0, 2), False), ((0, 1), True), ((1, 2), False)]
+    nsl = {(0, 1): 20, (1, 2): 9, (0, 2): 8}
+    for dirs, ind in calls:
+        got = np.asarray(w.berry_flux([0], list(dirs), individual_phases=ind))
+        ref = np.asarray(_fresh_copy(tb, w, m, mesh).berry_flux([0], list(dirs), individual_phases=ind))
+        assert got.shape[0] == nsl[dirs] and got.shape == ref.shape
+        assert np.isfinite(ref).all() and np.abs(ref).max() > 1e-6
+        assert same(got, ref), (dirs, ind)
+
+
+def test_one_array_buffers_grow_and_shrink_2d(tb, models):
+    """The same on a 2-D array, alternating the fused solve (its own partials and gap minima), plaquettes, and the row kernel at
+    two tile heights (TBK_FLUX_TI: 4 rows, 80 partials; 24 rows, 16)."""
+    from pythtb_amd import _lib
+    mesh, m = [33, 40], models[0.0]
+    w = tb.wf_array(m, mesh)
+
+    for _ in range(2):
+        gaps, tot = w.solve_on_grid_flux(START, [0])
+        rgaps, rtot = tb.wf_array(m, mesh).solve_on_grid_flux(START, [0])
+        assert same(gaps, rgaps) and same(tot, rtot) and round(tot / (2 * np.pi)) == -1
+        plaq = w.berry_flux([0], individual_phases=True)
+        assert plaq.shape == (32, 39) and same(plaq, _fresh_copy(tb, w, m, mesh).berry_flux([0], individual_phases=True))
+        for ti in (4, 24):
+            with _lib.knob("TBK_FLUX_TI", ti):
+                assert same(w.berry_flux([0]), _fresh_copy(tb, w, m, mesh).berry_flux([0])), ti

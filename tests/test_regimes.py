@@ -687,3 +687,20 @@ def test_direct_small_solvers_on_special_matrices(tb, n):
         # (the Jacobi kernel's convergence test squares the entries: on the 1e-150 matrix it stops at a residual of 5e-13 |H| -- the
         # direct method, which works on norms with rsqrt, does not have that cliff)
         assert res.max() < (1e-14 if name == "direct" else 2e-12) and orth.max() < 1e-14, (name, res.max(), orth.max())
+
+
+def test_workspace_shared_across_regimes_on_one_context():
+    """One context, one workspace (tbk_ctx::work) behind every regime: 64 matrices of 17 states with eigenvectors, then 4 of 96
+    states, eigenvalues only (another regime, a larger workspace), then the first batch again -- the same bits as before the
+    workspace was regrown under it; the second batch against LAPACK."""
+    ha, hb = _matrices(17, 64, 3017), _matrices(96, 4, 3096)
+    ev0, vec0 = _eigh_batch(ha)
+    evb, _ = _eigh_batch(hb, vectors=False)
+    ev1, vec1 = _eigh_batch(ha)
+    assert np.array_equal(ev1.view(np.uint64), ev0.view(np.uint64))
+    assert np.array_equal(vec1.view(np.uint64), vec0.view(np.uint64))
+    assert np.abs(vec0).max() > 0.1
+    ref = np.linalg.eigvalsh(hb)
+    scale = np.maximum(np.abs(ref).max(axis=1), 1.0)
+    assert np.max(np.abs(evb.T - ref) / scale[:, None]) < 3e-12       # (above 64 states, as in test_forced_regime_eigenvalues_only)
+    assert np.all(np.diff(evb, axis=0) >= 0.0)
