@@ -523,6 +523,22 @@ int tbk_kpm_marker(tbk_sparse* sp, int ncoef, const double* coeffs, double emin,
 int tbk_kpm_eigs(tbk_sparse* sp, const double* k, double e_lo, double e_hi, double emin, double emax, int n_search, int degree,
                  double tol, int max_iter, uint64_t seed, int* n_found, double* eval, double* evec, double* resid, int32_t* info);
 
+/* ---- bare (Lindhard) susceptibility at finite momentum transfer ----------
+ * k and q reduced, E_n(k), u_n(k) the eigenpairs of the solver (the convention-II matrix of tbk_gen_ham: u is the cell-periodic part),
+ * f as in tbk_optical_cond_mesh, M_nm(k, q) = sum_j conj(u_n(k)[j]) u_m(k+q)[j] = <psi_nk| e^{-i q.r} |psi_m,k+q> with r at the orbital
+ * positions; the mean over k_uniform_mesh(mesh) (dim_k 1..3, N_k points), all n^2 ordered pairs (n = m included), no spin factor:
+ *   omega given (nomega 1..65536 finite frequencies in any order, eta > 0; nq nomega <= 2^22): out[nq][nomega] c128,
+ *     chi0(q, w) = -(1 / N_k) sum_k sum_{n,m} [f(E_n(k)) - f(E_m(k+q))] |M_nm|^2 / (w + i eta + E_n(k) - E_m(k+q))
+ *   omega NULL (nomega = 0, eta = 0): the exact static limit, out[nq] doubles,
+ *     chi0(q) = (1 / N_k) sum_k sum_{n,m} L_nm |M_nm|^2,  L = -(f_n - f_m) / (E_n - E_m) (kT = 0: 0 where f_n = f_m; kT > 0:
+ *     (sinh h / h) / (2 kT (cosh h + cosh u)), h = (E_m - E_n) / 2kT, u = ((E_n + E_m) / 2 - mu) / kT, which is -f'(E) at h = 0).
+ * q[nq][dim_k]: 1..65536 finite points, any real values (k + q goes through the list solver as it is).  flags: 0 replaces |M|^2 by 1
+ * (the band-only Lindhard function; eigenvalue-only solves).  Per unit cell and per energy.  The chunks, groups and tiles do not
+ * depend on the q list and nothing uses atomics: bit-reproducible, and a q gives the same bits alone and inside a longer list. */
+#define TBK_CHI_MATRIX_ELEMENTS 1
+int tbk_susceptibility_mesh(tbk_model* model, const int32_t* mesh, int nq, const double* q, int nomega, const double* omega_or_null,
+                            double eta, double mu, double kT, int flags, double* out);
+
 /* ---- multi-GPU: one process per GPU, k-points sharded, one gather ------
  * Thin RCCL wrappers (librccl is dlopen'ed on first use).  The 128-byte id is
  * created on rank 0 and distributed by the launcher (any out-of-band channel). */

@@ -968,6 +968,72 @@ class tb_model(object):
         vc = np.sqrt(np.linalg.det(a @ a.T))
         return np.einsum("ia,wij,jb->wab", a, out, a) / ((2.0 * np.pi) ** 2 * vc)
 
+    def susceptibility_mesh(self, mesh_size, q_list, omega=None, eta=None, fermi_level=0.0, kT=0.0, matrix_elements=True):
+        """Extension: the bare (Lindhard) susceptibility at momentum transfer q, averaged over the whole
+        `k_uniform_mesh(mesh_size)` (1-, 2- or 3-D, generated on the device).  Dynamic (`omega` and `eta > 0` given):
+
+            chi0(q, w) = -(1 / N_k) sum_k sum_{n,m} [f(E_n(k)) - f(E_m(k+q))] |M_nm(k,q)|^2 / (w + i eta + E_n(k) - E_m(k+q))
+            M_nm(k,q)  = sum_j conj(u_n(k)[j]) u_m(k+q)[j]        (= <psi_nk| e^{-i q.r} |psi_m,k+q>, r at the orbital positions)
+
+        k and q reduced, E_n and u_n the eigenpairs of `solve_all` (the matrix of `_gen_ham`, whose phases carry the orbital
+        positions: u is the cell-periodic part), f = [E <= fermi_level] for kT = 0, else the Fermi function.  All n^2 ordered
+        pairs take part, n = m (intraband) included; nothing is left out (every term is finite for eta > 0); no
+        spin-degeneracy factor.  Sign: Re chi0(q, 0) >= 0 and Im chi0(q, w > 0) >= 0.  Units: per unit cell and per energy.
+
+        Static (`omega=None`; `eta` must then be None): the exact eta -> 0, w = 0 limit, float `(nq,)`,
+
+            chi0(q) = (1 / N_k) sum_k sum_{n,m} L_nm |M_nm|^2,    L = -(f_n - f_m) / (E_n - E_m)
+
+        with L = 0 where f_n = f_m at kT = 0, and L = (sinh h / h) / (2 kT (cosh h + cosh u)), h = (E_m(k+q) - E_n(k)) / 2kT,
+        u = ((E_n + E_m) / 2 - fermi_level) / kT at kT > 0: smooth through E_n = E_m, where it is -f'(E).  The dynamic form at
+        any eta > 0 and w = 0 DROPS the terms with E_n(k) = E_m(k+q) exactly (a nested Fermi surface on a commensurate mesh,
+        q = 0): their numerator vanishes before the denominator does.  The static mode keeps them -- that is why it exists.
+
+        q_list: `(nq, dim_k)`, 1 <= nq <= 65536, or `(dim_k,)` for one q (the leading axis of the result is then dropped);
+        finite, any real values (a `k_path`, a `k_uniform_mesh`, incommensurate points).  omega: 1-D, 1..65536 finite
+        frequencies in any order, nq * nw <= 2**22; the result is complex `(nq, nw)`.  matrix_elements=False replaces
+        |M|^2 by 1: the band-only Lindhard (nesting) function, from eigenvalue-only solves.
+
+        chi0(q = 0, w) = 0 to rounding (charge conservation).  Two symmetries one might expect do NOT hold in general:
+        chi0(-q, -w) = conj chi0(q, w) holds only for q commensurate with the mesh (for other q the discrete k sum is not
+        invariant under the shift k -> k - q), and chi0(q + G) = chi0(q) holds only when every orbital sits on a lattice
+        point (otherwise e^{-i q.r} gives a form factor).  At kT = 0 a Fermi level below or above every level gives exact
+        zeros.  Fixed reduction order: two calls give the same bits, and a q gives the same bits alone and inside a longer
+        q_list.  Each q costs a second eigen-solve of the mesh, the larger part of a static map's time; no timing is claimed
+        beyond the measured cases of DESIGN.md section 26."""
+        if self._dim_k not in (1, 2, 3):
+            raise Exception("\n\nsusceptibility_mesh needs a model with dim_k 1, 2 or 3.")
+        mesh, nk = self._mesh_arg(mesh_size)
+        q = np.array(q_list, dtype=float)
+        single = q.ndim == 1
+        if single:
+            q = q.reshape(1, -1)
+        if q.ndim != 2 or q.shape[1] != self._dim_k or q.shape[0] < 1 or q.shape[0] > 65536:
+            raise Exception("\n\nq_list must have shape (nq, dim_k) with 1..65536 points, or (dim_k,).")
+        if not np.all(np.isfinite(q)):
+            raise Exception("\n\nq_list must be finite.")
+        q = np.ascontiguousarray(q)
+        nq = q.shape[0]
+        flags = 1 if matrix_elements else 0
+        if omega is None:
+            if eta is not None:
+                raise Exception("\n\nThe static mode (omega=None) is the eta -> 0 limit: eta must be None.")
+            _sweep_args([0.0], 1.0, fermi_level, kT)
+            out = np.zeros(nq, dtype=float)
+            _lib.check(_lib.lib.tbk_susceptibility_mesh(self._device_model(), _lib.iptr(mesh), nq, _lib.dptr(q), 0, None, 0.0,
+                                                        float(fermi_level), float(kT), flags, _lib.dptr(out)))
+        else:
+            if eta is None:
+                raise Exception("\n\nThe dynamic mode (omega given) needs eta > 0.")
+            w = _sweep_args(omega, eta, fermi_level, kT)
+            if nq * w.size > 2 ** 22:
+                raise Exception("\n\nnq * nw must be at most 2**22: split q_list or omega.")
+            out = np.zeros((nq, w.size), dtype=complex)
+            _lib.check(_lib.lib.tbk_susceptibility_mesh(self._device_model(), _lib.iptr(mesh), nq, _lib.dptr(q), int(w.size),
+                                                        _lib.dptr(w), float(eta), float(fermi_level), float(kT), flags,
+                                                        _lib.dptr(out.view(float))))
+        return out[0] if single else out
+
     # ------------------------------------------------------------------ shift and injection photocurrents (extensions)
     def _gen_ddham(self, k_input, dir0, dir1):
         """Extension: d^2 H / dk_dir0 dk_dir1 for one k in reduced coordinates, with the shapes of `_gen_ham` (`(norb, 2, norb, 2)`
