@@ -539,6 +539,36 @@ int tbk_kpm_eigs(tbk_sparse* sp, const double* k, double e_lo, double e_hi, doub
 int tbk_susceptibility_mesh(tbk_model* model, const int32_t* mesh, int nq, const double* q, int nomega, const double* omega_or_null,
                             double eta, double mu, double kT, int flags, double* out);
 
+/* ---- the occupied states on k meshes: thermodynamic sums, the Fermi level of a filling, the density matrix ----
+ * E_n(k), u_n(k) the eigenpairs of the solver (the convention-II matrix of tbk_gen_ham) on k_uniform_mesh(mesh) (dim_k 1..3, N_k < 2^31
+ * points), f = [E <= mu] (kT = 0) or 1 / (1 + exp((E - mu) / kT)); a state counts once (no spin factor: a spinful model has 2 norb).
+ * Fixed-order sums, no floating-point atomics, no partition that depends on the number of levels, fillings or lattice vectors:
+ * bit-reproducible, and a level, a filling or an R gives the same bits alone and inside a longer list.
+ *
+ * tbk_thermodynamics_mesh: out[3][nmu] for nmu = 1..8192 finite levels in any order,
+ *   N = (1 / N_k) sum f,   E = (1 / N_k) sum f E_n,   S = -(1 / N_k) sum [f ln f + (1 - f) ln(1 - f)]  (exactly 0 at kT = 0).
+ *   Eigenvalues only; those of the whole mesh stay on the device.  At kT = 0, N is an integer count divided by N_k.
+ *
+ * tbk_fermi_level_mesh: mu_out[nfill] for nfill = 1..64 electron counts per cell; ONE eigen-solve of the mesh, then 64 bisection steps
+ *   on the ordered integer key of a double, for all fillings at once, without a host synchronisation between them.
+ *   kT = 0: c = n_electrons N_k must lie within 1e-6 of an integer in [1, nsta N_k - 1]; with the levels of the mesh sorted,
+ *     mu = (e_{c-1} + e_c) / 2 and edges_or_null[nfill][2] = (e_{c-1}, e_c), the device's own eigenvalues.  Equal edges: the level cuts
+ *     a degenerate group, and tbk_thermodynamics_mesh at that mu counts more than c.
+ *   kT > 0: 0 < n_electrons < nsta; mu is the first double at which the device's occupation sum reaches n_electrons N_k
+ *     (edges_or_null must be NULL).  Inside a gap at kT << gap, mu is only as determined as N(mu) is.
+ *
+ * tbk_density_matrix_mesh: out[nR][nsta][nsta] c128,
+ *   D_ij(R) = (1 / N_k) sum_k [sum_n f_n u_n[i] conj(u_n[j])] e^{-2 pi i k.(R + tau_j - tau_i)} = <c+_{j,R} c_{i,0}>
+ *   in the index layout and phase convention of the hopping table (amp, i, j, R): D_ii(0) is the occupation of state i,
+ *   D_ji(-R) = conj D_ij(R), and E = Re sum conj(t_ij(R)) D_ij(R) over the whole table (both directions of every hop, on-site terms at
+ *   R = 0).  R[nR][dim_k]: 1..4096 integer vectors, |R_a| < 2^30, nR nsta^2 <= 2^22.  The phase e^{-2 pi i k.R} is formed from the
+ *   exact integer (i_a R_a mod N_a): an R equal to a mesh period gives D(0) bit for bit.  nsta <= 32: one kernel with the
+ *   eigenvectors of a group of points in LDS; beyond: 16 x 16 tiles, plain VALU.                                                       */
+int tbk_thermodynamics_mesh(tbk_model* model, const int32_t* mesh, int nmu, const double* mu, double kT, double* out);
+int tbk_fermi_level_mesh(tbk_model* model, const int32_t* mesh, int nfill, const double* n_electrons, double kT, double* mu_out,
+                         double* edges_or_null);
+int tbk_density_matrix_mesh(tbk_model* model, const int32_t* mesh, double mu, double kT, int nR, const int32_t* R, double* out);
+
 /* ---- multi-GPU: one process per GPU, k-points sharded, one gather ------
  * Thin RCCL wrappers (librccl is dlopen'ed on first use).  The 128-byte id is
  * created on rank 0 and distributed by the launcher (any out-of-band channel). */

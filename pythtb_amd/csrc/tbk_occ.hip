@@ -1,0 +1,579 @@
+// tbk_occ.hip -- the occupied states of a model on uniform meshes: the thermodynamic sums N, E, S at given Fermi
+// levels, the Fermi level of a given filling, and the real-space density matrix D_ij(R).
+//
+// E_n(k) and u_n(k) are the eigenpairs of the solver (the convention-II matrix of tbk_gen_ham), f = [E <= mu] (kT = 0) or
+// 1 / (1 + exp((E - mu) / kT)); a state counts once (no spin factor).  With N_k the points of k_uniform_mesh(mesh):
+//   N(mu) = (1 / N_k) sum_{k,n} f,   E(mu) = (1 / N_k) sum f E_n,   S(mu) = -(1 / N_k) sum [f ln f + (1 - f) ln(1 - f)]
+//   D_ij(R) = (1 / N_k) sum_k [sum_n f_n u_n[i] conj(u_n[j])] e^{-2 pi i k.(R + tau_j - tau_i)} = <c+_{j,R} c_{i,0}>
+//
+// tbk_thermodynamics_mesh and tbk_fermi_level_mesh solve for the eigenvalues of the whole mesh once and keep them on the device as one
+// flat array of L = n N_k levels.  kT = 0 sums: tbk_kubo.h's Fermi scan k_kubo_fermi over the sorted levels and a prefix sum on the host;
+// kT > 0 sums: k_occ_scan, one lane per Fermi level, group g of G walking the levels [g L / G, (g + 1) L / G) in order (k_kubo_thermal
+// wants at least one record beside E: its shape does not fit), then k_kubo_rows and the tail kubo_rows_to_host.  The Fermi selection
+// bisects on the ordered 64-bit key of a double (occ_key): kOccSteps times k_occ_count (the occupation of every filling's midpoint into
+// per-group partials, the lanes over the levels) and k_occ_bisect (a wavefront per filling adds the partials in a fixed order and moves
+// the bracket in device memory) -- no host synchronisation between steps and no workgroup that waits for another.  At kT = 0 the same pass
+// counts with the step function and ends on the level e_{c-1} itself; one more pass (k_occ_count<true>, k_occ_edges) finds the next
+// level above.
+//
+// tbk_density_matrix_mesh goes through the mesh in tbk_kubo.h's chunks (solve with eigenvectors), per chunk
+//   k_dm_weights   f[n][cnt], once per (point, state)
+//   n <= 32  k_dm_lds: a batch of P points' eigenvectors in LDS, multiplied by the orbital phases e^{2 pi i k.tau_i} on the way in; a lane
+//            owns an element (i, j) (and a share of the batch's points where n^2 < 256, or ES elements where n^2 > 256), forms
+//            P_ij(k) = sum_n f_n w_n[i] conj(w_n[j]) skipping f_n = 0, and adds P_ij e^{-2 pi i k.R} for OCC_RB lattice vectors in registers
+//   n > 32   k_dm_tile: 16 x 16 tiles of P(k), strips of 16 states through LDS, plain VALU
+//            both write part[g][R][i][j] for the k-group g of the chunk
+//   k_dm_rows      acc[R][i][j] (+)= sum_g part[g][R][i][j], the groups in index order, chunk after chunk in stream order
+// The phase e^{-2 pi i k.R} at mesh point (i_a / N_a) is formed from the exact integer (i_a R_a mod N_a).  Nothing uses floating-point
+// atomics and no partition depends on the number of levels, fillings or lattice vectors: two calls give the same bits.
+#include <math.h>
+#include "tbk_occ.h"
+
+// ---------------------------------------------------------------- occupation
+// f and, where wanted, s = -f ln f - (1 - f) ln(1 - f) of x = (E - mu) / kT: t = e^{-|x|}, f = t / (1 + t) or 1 / (1 + t),
+// s = |x| t / (1 + t) + log1p(t) -- and 0 once t has underflowed, so that no 0 * inf is formed
+__device__ __forceinline__ double occ_fermi(const double e, const double mu, const double kT, double* s) {
+    if (kT == 0.0) {
+        if (s) *s = 0.0;
+        return e <= mu ? 1.0 : 0.0;
+    }
+    const double x = (e - mu) / kT, ax = fabs(x);
+    const double t = exp(-ax);
+    const double q = 1.0 / (1.0 + t);
+    const double tq = t * q;
+    if (s) *s = tq > 0.0 ? fma(ax, tq, log1p(t)) : 0.0;
+    return x >= 0.0 ? tq : q;
+}
+
+// the Fermi scan's source (k_kubo_fermi, the mesh as one row of N_k points): a level adds (1, E) to its bin
+struct OccEvSrc {
+    const double* ev;   // [n][npts]
+    __device__ __forceinline__ void band(const PlaneArgs& P, const int (&)[3], const int64_t idx, const int b, double& e,
+                                         double (&w)[2]) const {
+        e = ev[(int64_t)b * P.npts + idx];
+        w[0] = 1.0;
+        w[1] = e;
+    }
+};
+
+// ---------------------------------------------------------------- level scans
+// The thermal sums of tbk_thermodynamics_mesh.  Workgroup (tile of 256 Fermi levels, group g): lane t takes level j = tile + t and
+// walks the mesh levels [g L / G, (g + 1) L / G) in order (wave-uniform reads), adding N, E and S.  part[j][3][G] (the rows of
+// k_kubo_rows).
+__global__ __launch_bounds__(256) void k_occ_scan(const double* __restrict__ ev, const int64_t nlev, const int G, const double* __restrict__ mu,
+                                                  const int nmu, const double kT, double* __restrict__ part) {
+    const int base = blockIdx.x * 256;
+    if (base + (int)(threadIdx.x & ~63u) >= nmu) return;            // a wavefront without a level (uniform)
+    const int j = base + threadIdx.x, g = blockIdx.y;
+    const double u = j < nmu ? mu[j] : 0.0;
+    const int64_t l0 = (int64_t)g * nlev / G, l1 = (int64_t)(g + 1) * nlev / G;
+    double a0 = 0.0, a1 = 0.0, a2 = 0.0;
+    for (int64_t l = l0; l < l1; ++l) {
+        const double e = ev[l];
+        double s;
+        const double f = occ_fermi(e, u, kT, &s);
+        a0 += f;
+        a1 = fma(f, e, a1);
+        a2 += s;
+    }
+    if (j >= nmu) return;
+    double* p = part + ((int64_t)j * 3) * G + g;
+    p[0] = a0;
+    p[G] = a1;
+    p[2 * (int64_t)G] = a2;
+}
+
+// A pass of the Fermi selection: the few fillings (at most 64) against all the levels, so the LANES take the levels.  Workgroup g
+// holds the mesh levels [g L / G, (g + 1) L / G), lane t those at t, t + 256, ...; for every filling j in turn it adds the
+// occupation at mu[j] (the step function at kT = 0) and block_sum leaves the group's sum in part[j][G] -- a filling's sum does not
+// depend on the fillings beside it.  NEXT (kT = 0, after the last step; mu[j] is the KEY of the lower edge): the count of levels at
+// or below the edge and the smallest level above it (+inf: none), part[j][2][G].
+template <bool NEXT>
+__global__ __launch_bounds__(256) void k_occ_count(const double* __restrict__ ev, const int64_t nlev, const int G, const double* __restrict__ mu,
+                                                   const int nfill, const double kT, double* __restrict__ part) {
+    __shared__ double red[4], low[4];
+    const int g = blockIdx.x;
+    const int64_t l0 = (int64_t)g * nlev / G, l1 = (int64_t)(g + 1) * nlev / G;
+    for (int j = 0; j < nfill; ++j) {
+        const double u = NEXT ? occ_unkey(((const uint64_t*)mu)[j]) : mu[j];
+        double acc = 0.0, nxt = INFINITY;
+        for (int64_t l = l0 + threadIdx.x; l < l1; l += 256) {
+            const double e = ev[l];
+            if constexpr (NEXT) {
+                if (e <= u) acc += 1.0;
+                else nxt = fmin(nxt, e);
+            } else {
+                acc += occ_fermi(e, u, kT, nullptr);
+            }
+        }
+        if constexpr (NEXT) {
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) nxt = fmin(nxt, __shfl_xor(nxt, o));
+            if ((threadIdx.x & 63) == 0) low[threadIdx.x >> 6] = nxt;
+        }
+        const double tot = block_sum(acc, red);                    // (its barrier also orders `low`)
+        if (threadIdx.x == 0) {
+            if constexpr (NEXT) {
+                part[((int64_t)j * 2) * G + g] = tot;
+                part[((int64_t)j * 2 + 1) * G + g] = fmin(fmin(low[0], low[1]), fmin(low[2], low[3]));
+            } else {
+                part[(int64_t)j * G + g] = tot;
+            }
+        }
+        __syncthreads();                                           // (red and low are reused by the next filling)
+    }
+}
+
+// One wavefront per filling j (blockIdx.x): lane t adds the partials t, t + 64, ... in order, a shuffle tree adds the lanes, and lane 0
+// moves the bracket -- hi to the midpoint where the occupation reaches the target, lo otherwise -- then stores the next midpoint's
+// double for the next pass.  The invariant: the occupation at lo is below the target, at hi it is not; a bracket of neighbouring
+// keys stays as it is.
+__global__ __launch_bounds__(64) void k_occ_bisect(const double* __restrict__ part, const int G, const double* __restrict__ target,
+                                                   uint64_t* __restrict__ lo, uint64_t* __restrict__ hi, double* __restrict__ mu) {
+    const int j = blockIdx.x;
+    double tot = 0.0;
+    for (int g = threadIdx.x; g < G; g += 64) tot += part[(int64_t)j * G + g];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) tot += __shfl_xor(tot, o);
+    if (threadIdx.x != 0) return;
+    uint64_t a = lo[j], b = hi[j];
+    const uint64_t mid = a + (b - a) / 2;
+    if (b - a > 1) {
+        if (tot >= target[j]) b = mid;
+        else a = mid;
+    }
+    lo[j] = a;
+    hi[j] = b;
+    mu[j] = occ_unkey(a + (b - a) / 2);
+}
+// The same shape after the NEXT pass: edges[j] = (e_{c-1}, e_c) -- e_c = e_{c-1} where more than c levels lie at or below it
+__global__ __launch_bounds__(64) void k_occ_edges(const double* __restrict__ part, const int G, const double* __restrict__ target,
+                                                  const uint64_t* __restrict__ hi, double* __restrict__ edges) {
+    const int j = blockIdx.x;
+    double cnt = 0.0, nxt = INFINITY;
+    for (int g = threadIdx.x; g < G; g += 64) {
+        cnt += part[((int64_t)j * 2) * G + g];
+        nxt = fmin(nxt, part[((int64_t)j * 2 + 1) * G + g]);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        cnt += __shfl_xor(cnt, o);
+        nxt = fmin(nxt, __shfl_xor(nxt, o));
+    }
+    if (threadIdx.x != 0) return;
+    const double lower = occ_unkey(hi[j]);
+    edges[2 * j] = lower;
+    edges[2 * j + 1] = cnt > target[j] ? lower : nxt;
+}
+
+// ---------------------------------------------------------------- density matrix
+struct OccMesh {
+    int N[3];   // the mesh, 1 beyond dim_k
+    int dk;
+};
+// e^{-2 pi i k.R} at point idx of the mesh: per axis the exact integer m = i_a R_a mod N_a, then sincospi(-2 m / N_a)
+__device__ __forceinline__ cd dm_phase(const OccMesh& M, const int64_t idx, const int32_t* __restrict__ R) {
+    int ii[3];
+    mesh_point(M.N, idx, ii);
+    cd ph{1.0, 0.0};
+    for (int d = 0; d < M.dk; ++d) {
+        int64_t mm = ((int64_t)ii[d] * (int64_t)R[d]) % M.N[d];
+        if (mm < 0) mm += M.N[d];
+        if (mm == 0) continue;
+        double sn, cs;
+        sincospi(-2.0 * ((double)mm / (double)M.N[d]), &sn, &cs);
+        ph = cmul_x(ph, cd{cs, sn});
+    }
+    return ph;
+}
+__device__ __forceinline__ cd dm_orb_phase(const ModelView& mv, const double* __restrict__ k, const int64_t ik, const int o) {
+    double kk[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int d = 0; d < mv.dim_k; ++d) kk[d] = k[ik * mv.dim_k + d];
+    return expi2pi(kdot(kk, mv.orb[o]));
+}
+
+// f[b][ik] of a chunk
+__global__ __launch_bounds__(256) void k_dm_weights(const double* __restrict__ ev, const int64_t total, const double mu, const double kT,
+                                                    double* __restrict__ fw) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < total) fw[i] = occ_fermi(ev[i], mu, kT, nullptr);
+}
+
+// Up to 32 states.  Workgroup (k-group g, block of OCC_RB lattice vectors): batches of P points.  A batch's weights, orbital phases and
+// lattice phases are staged first, then its eigenvectors come in through kubo_lds_load as w_n[i] = u_n[i] e^{2 pi i k.tau_i}.  Lane
+// mapping: n^2 <= 256 -- lane t = q n^2 + (i n + j) takes the points q, q + Q, ... of the batch (Q = 256 / n^2 shares, added in index
+// order through LDS at the end); n^2 > 256 -- lane t takes the elements t, t + 256, ... (ES of them).  Every lane of a wavefront reads
+// the same state b at the same time, w_b[j] at consecutive addresses and w_b[i] as a broadcast: no bank conflict at n = 16 or 32 (the
+// 16-way conflict of k_chi_pairs comes from lanes on different rows).
+template <int ES>
+__global__ __launch_bounds__(256) void k_dm_lds(const ModelView mv, const double* __restrict__ k, const cd* __restrict__ evec,
+                                                const double* __restrict__ fw, const int64_t nk, const int64_t first, const OccMesh M,
+                                                const int P, const int G, const int32_t* __restrict__ R, const int nr, cd* __restrict__ part) {
+    __shared__ cd U[OCC_LDS_CD];
+    __shared__ cd eph[OCC_LDS_PN];
+    __shared__ cd phs[64 * OCC_RB];
+    __shared__ double fs[OCC_LDS_PN];
+    const int n = mv.nsta, nn = n * n, t = threadIdx.x;
+    const int g = blockIdx.x, rb0 = blockIdx.y * OCC_RB, nrb = min(OCC_RB, nr - rb0);
+    const int64_t p0 = (int64_t)g * nk / G, p1 = (int64_t)(g + 1) * nk / G;
+    const int Q = ES == 1 ? max(1, 256 / nn) : 1;
+    const int q = ES == 1 ? t / nn : 0;
+    const int el0 = ES == 1 ? t - q * nn : t;
+    const bool live = ES > 1 || q < Q;
+    cd acc[ES][OCC_RB];
+#pragma unroll
+    for (int s = 0; s < ES; ++s)
+#pragma unroll
+        for (int r = 0; r < OCC_RB; ++r) acc[s][r] = cd{0.0, 0.0};
+    for (int64_t b0 = p0; b0 < p1; b0 += P) {
+        const int np = (int)std::min<int64_t>(P, p1 - b0);
+        for (int e = t; e < np * n; e += 256) {
+            const int p = e / n, b = e - p * n;
+            fs[e] = fw[(int64_t)b * nk + b0 + p];
+            eph[e] = dm_orb_phase(mv, k, b0 + p, b);
+        }
+        for (int e = t; e < np * nrb; e += 256) {
+            const int p = e / nrb, r = e - p * nrb;
+            phs[p * OCC_RB + r] = dm_phase(M, first + b0 + p, R + (int64_t)(rb0 + r) * M.dk);
+        }
+        __syncthreads();
+        kubo_lds_load(U, evec, nk, b0, np, n, nn, [&](const int e) {
+            const int p = e / nn, r = e - p * nn, i = r % n;
+            U[e] = cmul_x(U[e], eph[p * n + i]);
+        });
+        __syncthreads();
+        if (live) {
+#pragma unroll
+            for (int s = 0; s < ES; ++s) {
+                const int el = el0 + 256 * s;
+                if (el >= nn) continue;
+                const int i = el / n, j = el - i * n;
+                for (int p = q; p < np; p += Q) {
+                    const cd* W = U + p * nn;
+                    const double* fp = fs + p * n;
+                    cd pij{0.0, 0.0};
+                    for (int b = 0; b < n; ++b) {
+                        const double f = fp[b];
+                        if (f == 0.0) continue;                    // (kT = 0: the empty states)
+                        cfmac_x(pij, cscale(W[b * n + i], f), W[b * n + j]);   // += f w[i] conj(w[j])
+                    }
+#pragma unroll
+                    for (int r = 0; r < OCC_RB; ++r)
+                        if (r < nrb) cfma_x(acc[s][r], pij, phs[p * OCC_RB + r]);
+                }
+            }
+        }
+        __syncthreads();                                           // (the batch is consumed)
+    }
+    if (ES == 1 && Q > 1) {
+        cd* buf = U;                                               // OCC_RB x 256 <= OCC_LDS_CD
+#pragma unroll
+        for (int r = 0; r < OCC_RB; ++r) buf[r * 256 + t] = acc[0][r];
+        __syncthreads();
+        if (t < nn)
+            for (int r = 0; r < nrb; ++r) {
+                cd s = buf[r * 256 + t];
+                for (int qq = 1; qq < Q; ++qq) s = cadd(s, buf[r * 256 + qq * nn + t]);
+                part[((int64_t)g * nr + rb0 + r) * nn + t] = s;
+            }
+        return;
+    }
+#pragma unroll
+    for (int s = 0; s < ES; ++s) {
+        const int el = el0 + 256 * s;
+        if (!live || el >= nn) continue;
+#pragma unroll
+        for (int r = 0; r < OCC_RB; ++r)
+            if (r < nrb) part[((int64_t)g * nr + rb0 + r) * nn + el] = acc[s][r];
+    }
+}
+
+// 33 .. 2048 states.  Workgroup (16 x 16 tile (ti, tj) of P(k), k-group g, block of OCC_RB lattice vectors): lane (ty, tx) owns the
+// element (16 ti + ty, 16 tj + tx).  Per point the states go through LDS in strips of 16 (their components of the tile's rows and of
+// its columns, both read along the components); the weights fall with the level, so the first strip whose leading weight is 0 ends the
+// point.  The orbital phases are applied to the finished P_ij.
+__global__ __launch_bounds__(256) void k_dm_tile(const ModelView mv, const double* __restrict__ k, const cd* __restrict__ evec,
+                                                 const double* __restrict__ fw, const int64_t nk, const int64_t first, const OccMesh M,
+                                                 const int T, const int G, const int32_t* __restrict__ R, const int nr, cd* __restrict__ part) {
+    __shared__ cd As[16][16], Bs[16][16], eo[32], phs[OCC_RB];
+    __shared__ double fs[16];
+    const int n = mv.nsta, t = threadIdx.x, tx = t & 15, ty = t >> 4;
+    const int ti = blockIdx.x / T, tj = blockIdx.x - ti * T;
+    const int i = ti * 16 + ty, j = tj * 16 + tx;
+    const int g = blockIdx.y, rb0 = blockIdx.z * OCC_RB, nrb = min(OCC_RB, nr - rb0);
+    const int64_t p0 = (int64_t)g * nk / G, p1 = (int64_t)(g + 1) * nk / G;
+    cd acc[OCC_RB];
+#pragma unroll
+    for (int r = 0; r < OCC_RB; ++r) acc[r] = cd{0.0, 0.0};
+    for (int64_t ik = p0; ik < p1; ++ik) {
+        if (t < 32) {
+            const int o = t < 16 ? ti * 16 + t : tj * 16 + t - 16;
+            eo[t] = o < n ? dm_orb_phase(mv, k, ik, o) : cd{0.0, 0.0};
+        } else if (t < 32 + nrb) {
+            phs[t - 32] = dm_phase(M, first + ik, R + (int64_t)(rb0 + t - 32) * M.dk);
+        }
+        cd pij{0.0, 0.0};
+        for (int b0 = 0; b0 < n; b0 += 16) {
+            __syncthreads();                                       // (the previous strip is consumed; eo and phs are staged)
+            if (t < 16) fs[t] = b0 + t < n ? fw[(int64_t)(b0 + t) * nk + ik] : 0.0;
+            const int b = b0 + ty;
+            const cd* u = evec + ((int64_t)(b < n ? b : 0) * nk + ik) * n;
+            As[ty][tx] = (b < n && ti * 16 + tx < n) ? u[ti * 16 + tx] : cd{0.0, 0.0};
+            Bs[ty][tx] = (b < n && tj * 16 + tx < n) ? u[tj * 16 + tx] : cd{0.0, 0.0};
+            __syncthreads();
+            if (fs[0] == 0.0) break;                               // (uniform: every later state is empty too)
+#pragma unroll
+            for (int bb = 0; bb < 16; ++bb) {
+                const double f = fs[bb];
+                if (f == 0.0) continue;
+                cfmac_x(pij, cscale(As[bb][ty], f), Bs[bb][tx]);
+            }
+        }
+        pij = cmul_x(cmul_x(pij, eo[ty]), cconj(eo[16 + tx]));
+#pragma unroll
+        for (int r = 0; r < OCC_RB; ++r)
+            if (r < nrb) cfma_x(acc[r], pij, phs[r]);
+        __syncthreads();                                           // (eo and phs are read)
+    }
+    if (i < n && j < n)
+#pragma unroll
+        for (int r = 0; r < OCC_RB; ++r)
+            if (r < nrb) part[((int64_t)g * nr + rb0 + r) * n * n + (int64_t)i * n + j] = acc[r];
+}
+
+// acc[row] (+)= sum_g part[g][row], the groups in index order: one LANE per row (a row is one double of part[g][R][i][j]; there are
+// up to 2^23 of them and at most kOccGroupsMax groups, where k_chi_rows' workgroup per row would be nearly idle)
+__global__ __launch_bounds__(256) void k_dm_rows(const double* __restrict__ part, const int G, const int64_t nrows, const int accumulate,
+                                                 double* __restrict__ acc) {
+    const int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (row >= nrows) return;
+    double s = 0.0;
+    for (int g = 0; g < G; ++g) s += part[(int64_t)g * nrows + row];
+    acc[row] = accumulate ? acc[row] + s : s;
+}
+
+// ---------------------------------------------------------------- host side
+// the eigenvalues e[n][npts] of the whole mesh, generated and kept on the device (the front end of tbk_dos_mesh)
+static int occ_mesh_evals(tbk_model* m, const int32_t* mesh, int64_t npts, double* k_dev, double* e_dev) {
+    bool done = false;
+    int rc = tbk_mesh_evals_rows(m, mesh, e_dev, &done);          // up to 4 states: straight from the mesh, no k list
+    if (rc) return rc;
+    if (done) return tbk_eigh_check(m->ctx, m->nsta);
+    rc = tbk_k_uniform_mesh_dev(m->ctx, m->dim_k, mesh, k_dev);
+    if (rc) return rc;
+    return tbk_solve_list_dev_checked(m, k_dev, npts, e_dev, nullptr);
+}
+
+extern "C" int tbk_thermodynamics_mesh(tbk_model* m, const int32_t* mesh, int nmu, const double* mu, double kT, double* out) {
+    const char* fn = "tbk_thermodynamics_mesh";
+    TBK_REQUIRE(m && mesh && out, TBK_EINVAL, "%s: null argument", fn);
+    const int dk = m->dim_k, n = m->nsta;
+    int64_t npts;
+    int rc = occ_thermo_check(fn, dk, n, mesh, nmu, mu, kT, npts);
+    if (rc) return rc;
+    const bool thermal = kT > 0.0;
+    const OccScanPlan pl = occ_scan_plan(n, dk, npts, nmu, thermal, false);
+    tbk_ctx* ctx = m->ctx;
+    TBK_HIP(hipSetDevice(ctx->device));
+    void* base = nullptr;
+    rc = tbk_ctx_scratch(ctx, pl.total, &base);
+    if (rc) return rc;
+    unsigned char* b = (unsigned char*)base;
+    double* k_dev = (double*)(b + pl.off_k);
+    double* e_dev = (double*)(b + pl.off_e);
+    double* part = (double*)(b + pl.off_part);
+    double* rows = (double*)(b + pl.off_rows);
+    double* mu_dev = (double*)(b + pl.off_mu);
+    std::vector<int> ord;
+    std::vector<double> mus;
+    kubo_levels(mu, nmu, !thermal, ord, mus);                       // kT = 0: sorted (ties by index) for the bins of the Fermi scan
+    TBK_HIP(hipMemcpyAsync(mu_dev, mus.data(), (size_t)nmu * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    rc = occ_mesh_evals(m, mesh, npts, k_dev, e_dev);
+    if (rc) return rc;
+    std::vector<double> sums;
+    const double nk = (double)npts;
+    if (thermal) {
+        {
+            ProfScope ps(ctx, "occ_scan");
+            hipLaunchKernelGGL(k_occ_scan, dim3((unsigned)((nmu + 255) / 256), (unsigned)pl.G), dim3(256), 0, ctx->stream,
+                               (const double*)e_dev, pl.nlev, pl.G, (const double*)mu_dev, nmu, kT, part);
+            TBK_HIP(hipGetLastError());
+        }
+        rc = kubo_rows_to_host(ctx, "occ_rows", part, pl.G, pl.nrows, rows, sums);
+        if (rc) return rc;
+        for (int j = 0; j < nmu; ++j)
+            for (int c = 0; c < 3; ++c) out[(size_t)c * nmu + j] = sums[(size_t)j * 3 + c] / nk;
+        return TBK_OK;
+    }
+    PlaneArgs P{};                                                  // the mesh as one row of N_k points: plane point p is mesh point p
+    P.N[0] = (int)npts, P.N[1] = P.N[2] = 1;
+    P.da = 0, P.db = 1, P.dc = -1;
+    P.nplane = P.npts = npts;
+    P.nslice = 1;
+    {
+        ProfScope ps(ctx, "occ_fermi");
+        rc = kubo_fermi_launch<2>(ctx, OccEvSrc{e_dev}, P, n, mu_dev, nmu, pl.gx, part);
+        if (rc) return rc;
+    }
+    rc = kubo_rows_to_host(ctx, "occ_rows", part, pl.gx, pl.nrows, rows, sums);
+    if (rc) return rc;
+    double cnt = 0.0, en = 0.0;                                     // a level's sums: those of the bins up to it (counts: exact integers)
+    for (int j = 0; j < nmu; ++j) {
+        cnt += sums[(size_t)j * 2];
+        en += sums[(size_t)j * 2 + 1];
+        out[ord[j]] = cnt / nk;
+        out[(size_t)nmu + ord[j]] = en / nk;
+        out[(size_t)2 * nmu + ord[j]] = 0.0;
+    }
+    return TBK_OK;
+}
+
+extern "C" int tbk_fermi_level_mesh(tbk_model* m, const int32_t* mesh, int nfill, const double* n_electrons, double kT, double* mu_out,
+                                    double* edges_or_null) {
+    const char* fn = "tbk_fermi_level_mesh";
+    TBK_REQUIRE(m && mesh && mu_out, TBK_EINVAL, "%s: null argument", fn);
+    const int dk = m->dim_k, n = m->nsta;
+    int64_t npts;
+    std::vector<double> target;
+    int rc = occ_fermi_check(fn, dk, n, mesh, nfill, n_electrons, kT, edges_or_null != nullptr, npts, target);
+    if (rc) return rc;
+    const OccScanPlan pl = occ_scan_plan(n, dk, npts, nfill, kT > 0.0, true);
+    tbk_ctx* ctx = m->ctx;
+    TBK_HIP(hipSetDevice(ctx->device));
+    void* base = nullptr;
+    rc = tbk_ctx_scratch(ctx, pl.total, &base);
+    if (rc) return rc;
+    unsigned char* b = (unsigned char*)base;
+    double* k_dev = (double*)(b + pl.off_k);
+    double* e_dev = (double*)(b + pl.off_e);
+    double* part = (double*)(b + pl.off_part);
+    double* mu_dev = (double*)(b + pl.off_mu);
+    uint64_t* lo_dev = (uint64_t*)(b + pl.off_lo);
+    uint64_t* hi_dev = (uint64_t*)(b + pl.off_hi);
+    double* target_dev = (double*)(b + pl.off_target);
+    double* edges_dev = (double*)(b + pl.off_edges);
+    // the bracket of every filling: every finite double.  Nothing is occupied at -DBL_MAX and everything at DBL_MAX
+    const uint64_t klo = occ_key(-DBL_MAX), khi = occ_key(DBL_MAX);
+    std::vector<uint64_t> lo((size_t)nfill, klo), hi((size_t)nfill, khi);
+    std::vector<double> mid((size_t)nfill, occ_unkey(klo + (khi - klo) / 2));
+    const size_t fb = (size_t)nfill * sizeof(double);
+    TBK_HIP(hipMemcpyAsync(lo_dev, lo.data(), fb, hipMemcpyHostToDevice, ctx->stream));
+    TBK_HIP(hipMemcpyAsync(hi_dev, hi.data(), fb, hipMemcpyHostToDevice, ctx->stream));
+    TBK_HIP(hipMemcpyAsync(mu_dev, mid.data(), fb, hipMemcpyHostToDevice, ctx->stream));
+    TBK_HIP(hipMemcpyAsync(target_dev, target.data(), fb, hipMemcpyHostToDevice, ctx->stream));
+    rc = occ_mesh_evals(m, mesh, npts, k_dev, e_dev);               // ONE eigen-solve for every filling and every step
+    if (rc) return rc;
+    const dim3 grid((unsigned)pl.G);
+    for (int step = 0; step < kOccSteps; ++step) {
+        {
+            ProfScope ps(ctx, "occ_count");
+            hipLaunchKernelGGL(k_occ_count<false>, grid, dim3(256), 0, ctx->stream, (const double*)e_dev, pl.nlev, pl.G,
+                               (const double*)mu_dev, nfill, kT, part);
+            TBK_HIP(hipGetLastError());
+        }
+        ProfScope ps(ctx, "occ_bisect");
+        hipLaunchKernelGGL(k_occ_bisect, dim3((unsigned)nfill), dim3(64), 0, ctx->stream, (const double*)part, pl.G,
+                           (const double*)target_dev, lo_dev, hi_dev, mu_dev);
+        TBK_HIP(hipGetLastError());
+    }
+    if (kT > 0.0) {                                                 // the first double whose occupation reaches the target
+        TBK_HIP(hipMemcpyAsync(hi.data(), hi_dev, fb, hipMemcpyDeviceToHost, ctx->stream));
+        TBK_HIP(hipStreamSynchronize(ctx->stream));
+        for (int j = 0; j < nfill; ++j) mu_out[j] = occ_unkey(hi[j]) + 0.0;
+        return TBK_OK;
+    }
+    {                                                               // kT = 0: hi is the level e_{c-1} itself; the next one above
+        ProfScope ps(ctx, "occ_next");
+        hipLaunchKernelGGL(k_occ_count<true>, grid, dim3(256), 0, ctx->stream, (const double*)e_dev, pl.nlev, pl.G,
+                           (const double*)hi_dev, nfill, 0.0, part);
+        TBK_HIP(hipGetLastError());
+    }
+    {
+        ProfScope ps(ctx, "occ_edges");
+        hipLaunchKernelGGL(k_occ_edges, dim3((unsigned)nfill), dim3(64), 0, ctx->stream, (const double*)part, pl.G,
+                           (const double*)target_dev, (const uint64_t*)hi_dev, edges_dev);
+        TBK_HIP(hipGetLastError());
+    }
+    std::vector<double> edges((size_t)2 * nfill);
+    TBK_HIP(hipMemcpyAsync(edges.data(), edges_dev, 2 * fb, hipMemcpyDeviceToHost, ctx->stream));
+    TBK_HIP(hipStreamSynchronize(ctx->stream));
+    for (int j = 0; j < nfill; ++j) {
+        const double e0 = edges[2 * j] + 0.0, e1 = edges[2 * j + 1] + 0.0;   // (+ 0.0: -0 becomes +0)
+        mu_out[j] = 0.5 * (e0 + e1);
+        if (edges_or_null) {
+            edges_or_null[2 * j] = e0;
+            edges_or_null[2 * j + 1] = e1;
+        }
+    }
+    return TBK_OK;
+}
+
+extern "C" int tbk_density_matrix_mesh(tbk_model* m, const int32_t* mesh, double mu, double kT, int nR, const int32_t* R, double* out) {
+    const char* fn = "tbk_density_matrix_mesh";
+    TBK_REQUIRE(m && mesh && out, TBK_EINVAL, "%s: null argument", fn);
+    const int dk = m->dim_k, n = m->nsta;
+    int64_t npts;
+    int rc = occ_dm_check(fn, dk, n, mesh, mu, kT, nR, R, npts);
+    if (rc) return rc;
+    const OccDmPlan pl = occ_dm_plan(n, dk, npts, nR);
+    tbk_ctx* ctx = m->ctx;
+    TBK_HIP(hipSetDevice(ctx->device));
+    void* base = nullptr;
+    rc = tbk_ctx_scratch(ctx, pl.total, &base);
+    if (rc) return rc;
+    unsigned char* b = (unsigned char*)base;
+    int32_t* R_dev = (int32_t*)(b + pl.off_R);
+    cd* acc = (cd*)(b + pl.off_acc);
+    cd* part = (cd*)(b + pl.off_part);
+    KuboChunks cw = pl.cw;
+    cw.base = b + pl.off_chunks;
+    double* fw = cw.extra<double>(0);
+    TBK_HIP(hipMemcpyAsync(R_dev, R, (size_t)nR * dk * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    OccMesh M{{1, 1, 1}, dk};
+    for (int d = 0; d < dk; ++d) M.N[d] = mesh[d];
+    const int64_t nn = (int64_t)n * n;
+    rc = kubo_for_chunks(m, cw, nullptr, mesh, npts, [&](int64_t first, int64_t cnt, const double* kp, const double* ec, const cd* vc) -> int {
+        {
+            ProfScope ps(ctx, "dm_weights");
+            hipLaunchKernelGGL(k_dm_weights, dim3(nblk(cnt * n)), dim3(256), 0, ctx->stream, ec, cnt * n, mu, kT, fw);
+            TBK_HIP(hipGetLastError());
+        }
+        for (int r0 = 0; r0 < nR; r0 += pl.RT) {
+            const int nr = std::min(pl.RT, nR - r0);
+            const unsigned nrb = (unsigned)((nr + OCC_RB - 1) / OCC_RB);
+            const int32_t* Rp = R_dev + (int64_t)r0 * dk;
+            if (pl.lds) {
+                ProfScope ps(ctx, "dm_lds");
+                const dim3 grid((unsigned)pl.G, nrb);
+                if (pl.ES == 1)
+                    hipLaunchKernelGGL(k_dm_lds<1>, grid, dim3(256), 0, ctx->stream, m->view, kp, vc, (const double*)fw, cnt, first, M, pl.P, pl.G,
+                                       Rp, nr, part);
+                else if (pl.ES == 2)
+                    hipLaunchKernelGGL(k_dm_lds<2>, grid, dim3(256), 0, ctx->stream, m->view, kp, vc, (const double*)fw, cnt, first, M, pl.P, pl.G,
+                                       Rp, nr, part);
+                else
+                    hipLaunchKernelGGL(k_dm_lds<4>, grid, dim3(256), 0, ctx->stream, m->view, kp, vc, (const double*)fw, cnt, first, M, pl.P, pl.G,
+                                       Rp, nr, part);
+                TBK_HIP(hipGetLastError());
+            } else {
+                ProfScope ps(ctx, "dm_tile");
+                hipLaunchKernelGGL(k_dm_tile, dim3((unsigned)(pl.T * pl.T), (unsigned)pl.G, nrb), dim3(256), 0, ctx->stream, m->view, kp, vc,
+                                   (const double*)fw, cnt, first, M, pl.T, pl.G, Rp, nr, part);
+                TBK_HIP(hipGetLastError());
+            }
+            ProfScope ps(ctx, "dm_rows");
+            const int64_t nrows = (int64_t)nr * nn * 2;
+            hipLaunchKernelGGL(k_dm_rows, dim3(nblk(nrows)), dim3(256), 0, ctx->stream, (const double*)part, pl.G, nrows, first > 0 ? 1 : 0,
+                               (double*)(acc + (int64_t)r0 * nn));
+            TBK_HIP(hipGetLastError());
+        }
+        return TBK_OK;
+    });
+    if (rc) return rc;
+    const size_t nd = (size_t)pl.acc_cd * 2;
+    TBK_HIP(hipMemcpyAsync(out, acc, nd * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    TBK_HIP(hipStreamSynchronize(ctx->stream));
+    const double nk = (double)npts;
+    for (size_t i = 0; i < nd; ++i) out[i] /= nk;
+    return TBK_OK;
+}

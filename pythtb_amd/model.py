@@ -1034,6 +1034,146 @@ class tb_model(object):
                                                         _lib.dptr(out.view(float))))
         return out[0] if single else out
 
+    # ------------------------------------------------------------------ occupied states: N, E, S, the Fermi level, the density matrix
+    def _occ_args(self, what, mesh_size, kT):
+        """(mesh, N_k, kT) of the occupied-state calls: dim_k 1, 2 or 3, the mesh of `_mesh_arg`, kT finite and >= 0."""
+        if self._dim_k not in (1, 2, 3):
+            raise Exception("\n\n%s needs a model with dim_k 1, 2 or 3." % what)
+        mesh, nk = self._mesh_arg(mesh_size)
+        try:
+            kT = float(kT)
+        except (TypeError, ValueError):
+            raise Exception("\n\nkT must be finite and >= 0.")
+        if not np.isfinite(kT) or not kT >= 0.0:
+            raise Exception("\n\nkT must be finite and >= 0.")
+        return mesh, nk, kT
+
+    def thermodynamics_mesh(self, mesh_size, fermi_levels, kT=0.0):
+        """Extension: the electron count, the band energy and the electronic entropy per cell as means over
+        `k_uniform_mesh(mesh_size)` (1-, 2- or 3-D, generated on the device), for many Fermi levels at once: float `(3, nmu)`,
+
+            N(mu) = (1 / N_k) sum_{k,n} f        E(mu) = (1 / N_k) sum f E_n        S(mu) = -(1 / N_k) sum [f ln f + (1 - f) ln(1 - f)]
+
+        with E_n(k) the eigenvalues of `solve_all`, f = [E <= mu] for kT = 0, else the Fermi function.  No spin-degeneracy
+        factor: a state counts once (a spinful model has 2 norb of them).  fermi_levels: 1-D, 1..8192 finite values in any
+        order (repeats allowed; each gets its own value), or a scalar (the last axis is then dropped).  S in units of k_B; it
+        is exactly 0 at kT = 0, where N is an integer count divided by N_k.  Eigenvalues only, kept on the device; fixed-order
+        sums: two calls give the same bits."""
+        mesh, nk, kT = self._occ_args("thermodynamics_mesh", mesh_size, kT)
+        mu = np.array(fermi_levels, dtype=float)
+        scalar = mu.ndim == 0
+        if scalar:
+            mu = mu.reshape(1)
+        if mu.ndim != 1 or mu.size < 1 or mu.size > 8192:
+            raise Exception("\n\nfermi_levels must be a scalar or a 1-D array of 1..8192 levels.")
+        if not np.all(np.isfinite(mu)):
+            raise Exception("\n\nfermi_levels must be finite.")
+        mu = np.ascontiguousarray(mu)
+        out = np.zeros((3, mu.size), dtype=float)
+        _lib.check(_lib.lib.tbk_thermodynamics_mesh(self._device_model(), _lib.iptr(mesh), int(mu.size), _lib.dptr(mu), kT,
+                                                    _lib.dptr(out)))
+        return out[:, 0] if scalar else out
+
+    def fermi_level_mesh(self, mesh_size, n_electrons, kT=0.0, return_edges=False):
+        """Extension: the Fermi level that puts `n_electrons` electrons per cell into the levels of `k_uniform_mesh(mesh_size)`
+        (no spin factor: a state holds one electron).  n_electrons: a scalar, or 1-D with 1..64 values (a doping scan); the
+        result has the same shape.  The mesh is solved ONCE per call, whatever the number of fillings, and the selection runs
+        on the device (a bisection on the integer key of a double: 64 passes over the resident levels, for all fillings at once).
+
+        kT = 0: c = n_electrons * N_k must lie within 1e-6 of an integer in [1, nsta N_k - 1].  With all levels of the mesh
+        sorted, e_0 <= e_1 <= ..., the result is mu = (e_{c-1} + e_c) / 2, from the device's own eigenvalues;
+        return_edges=True returns (mu, edges) with edges `(2,)` or `(nfill, 2)` = (e_{c-1}, e_c): the band edges of an
+        insulator.  EQUAL edges mean that the Fermi level cuts a group of degenerate levels (a metal whose Fermi surface passes
+        through mesh points, e.g. the half-filled square lattice): `thermodynamics_mesh` at that mu then counts MORE than c,
+        the whole group.  Nothing is hidden: compare the edges.
+
+        kT > 0: any real 0 < n_electrons < nsta; the result is the first double at which the occupation sum reaches
+        n_electrons, |N(mu) - n_electrons| <= 1e-12 nsta.  Inside a gap at kT much smaller than the gap, N(mu) is flat to
+        rounding, and mu is only as determined as N is: any level of the plateau satisfies the bound, and which one is returned
+        is decided by the last bits of the sum (the same ones every call).  return_edges needs kT = 0.
+
+        Fixed-order sums: the result is reproducible bit for bit, and a filling gives the same bits alone and in a list."""
+        mesh, nk, kT = self._occ_args("fermi_level_mesh", mesh_size, kT)
+        nel = np.array(n_electrons, dtype=float)
+        scalar = nel.ndim == 0
+        if scalar:
+            nel = nel.reshape(1)
+        if nel.ndim != 1 or nel.size < 1 or nel.size > 64:
+            raise Exception("\n\nn_electrons must be a scalar or a 1-D array of 1..64 values.")
+        if not np.all(np.isfinite(nel)):
+            raise Exception("\n\nn_electrons must be finite.")
+        if return_edges and kT > 0.0:
+            raise Exception("\n\nreturn_edges needs kT = 0: the levels on both sides of the Fermi level exist at kT = 0 only.")
+        n = self._nsta
+        if kT > 0.0:
+            if not (np.all(nel > 0.0) and np.all(nel < n)):
+                raise Exception("\n\nn_electrons must lie in the open interval (0, %d) at kT > 0." % n)
+        else:
+            c = nel * nk
+            if np.any(np.abs(c - np.round(c)) > 1e-6):
+                raise Exception("\n\nn_electrons times the %d mesh points must be an integer at kT = 0." % nk)
+            if np.any(np.round(c) < 1) or np.any(np.round(c) > n * nk - 1):
+                raise Exception("\n\nn_electrons must select between 1 and %d of the %d levels at kT = 0." % (n * nk - 1, n * nk))
+        nel = np.ascontiguousarray(nel)
+        mu = np.zeros(nel.size, dtype=float)
+        edges = np.zeros((nel.size, 2), dtype=float) if return_edges else None
+        _lib.check(_lib.lib.tbk_fermi_level_mesh(self._device_model(), _lib.iptr(mesh), int(nel.size), _lib.dptr(nel), kT,
+                                                 _lib.dptr(mu), _lib.dptr(edges) if return_edges else None))
+        res = float(mu[0]) if scalar else mu
+        if return_edges:
+            return res, (edges[0] if scalar else edges)
+        return res
+
+    def density_matrix_mesh(self, mesh_size, fermi_level, kT=0.0, R_list=None):
+        """Extension: the one-particle density matrix in real space, as a mean over `k_uniform_mesh(mesh_size)` (1-, 2- or 3-D,
+        generated on the device): complex `(nR, nsta, nsta)`,
+
+            P(k)    = sum_n f(E_n(k)) u_n(k) u_n(k)^+
+            D_ij(R) = (1 / N_k) sum_k P_ij(k) e^{-2 pi i k.(R + tau_j - tau_i)} = <i,0| rho |j,R> = <c+_{j,R} c_{i,0}>
+
+        with the eigenpairs of `solve_all` and f as in `thermodynamics_mesh` (no spin factor).  Index layout and phase
+        convention are those of `set_hop(amp, i, j, R)`: D is the thermal average of the operator whose hopping table is t, so
+        D_ii(0) is the occupation of state i, sum_i D_ii(0) = N(mu), D_ji(-R) = conj D_ij(R), and the band energy is
+        E(mu) = Re sum conj(t_ij(R)) D_ij(R) over the whole table (both directions of every hop, on-site terms at R = 0, spin
+        blocks included).  For an insulator at kT = 0, D is the projector onto the occupied bands on the torus of the mesh.
+
+        R_list: `(nR, dim_k)` integers with |R_a| < 2**30, 1 <= nR <= 4096 and nR * nsta**2 <= 2**22; `(dim_k,)` alone drops
+        the leading axis; None is R = 0 (`(nsta, nsta)`).  Spinful models return `(nR, norb, 2, norb, 2)`, as `_gen_ham`
+        does.  The phase e^{-2 pi i k.R} is formed from exact integers: an R equal to a period of the mesh gives D(0) bit for
+        bit (the mesh cannot tell them apart).  The eigenvectors never leave the device.  At kT = 0 a Fermi level within
+        rounding of an eigenvalue makes that state's occupation depend on the last bits; take `fermi_level_mesh`'s midpoint.
+        Fixed-order sums: two calls give the same bits, and an R gives the same bits alone and inside a longer list."""
+        mesh, nk, kT = self._occ_args("density_matrix_mesh", mesh_size, kT)
+        try:
+            fermi_level = float(fermi_level)
+        except (TypeError, ValueError):
+            raise Exception("\n\nfermi_level must be one finite number.")
+        if not np.isfinite(fermi_level):
+            raise Exception("\n\nfermi_level must be finite.")
+        dk, n = self._dim_k, self._nsta
+        Rf = np.zeros(dk) if R_list is None else np.array(R_list)
+        if Rf.dtype == object or not (np.issubdtype(Rf.dtype, np.integer) or np.issubdtype(Rf.dtype, np.floating)):
+            raise Exception("\n\nR_list must hold integers.")
+        single = Rf.ndim == 1
+        if single:
+            Rf = Rf.reshape(1, -1)
+        if Rf.ndim != 2 or Rf.shape[1] != dk or Rf.shape[0] < 1 or Rf.shape[0] > 4096:
+            raise Exception("\n\nR_list must have shape (nR, dim_k) with 1..4096 lattice vectors, or (dim_k,).")
+        if not np.all(np.isfinite(Rf)) or np.any(Rf != np.round(Rf)):
+            raise Exception("\n\nR_list must hold integers.")
+        if np.any(np.abs(Rf) >= 2 ** 30):
+            raise Exception("\n\nR_list: every component must be below 2**30 in magnitude.")
+        nR = Rf.shape[0]
+        if nR * n * n > 2 ** 22:
+            raise Exception("\n\nnR * nsta**2 must be at most 2**22: split R_list.")
+        R = np.ascontiguousarray(Rf, dtype=np.int32)
+        out = np.zeros((nR, n, n), dtype=complex)
+        _lib.check(_lib.lib.tbk_density_matrix_mesh(self._device_model(), _lib.iptr(mesh), fermi_level, kT, nR, _lib.iptr(R),
+                                                    _lib.dptr(out.view(float))))
+        if self._nspin == 2:
+            out = out.reshape(nR, self._norb, 2, self._norb, 2)
+        return out[0] if single else out
+
     # ------------------------------------------------------------------ shift and injection photocurrents (extensions)
     def _gen_ddham(self, k_input, dir0, dir1):
         """Extension: d^2 H / dk_dir0 dk_dir1 for one k in reduced coordinates, with the shapes of `_gen_ham` (`(norb, 2, norb, 2)`
