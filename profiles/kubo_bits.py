@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """A fixed list of Kubo-formula calls (berry_curvature*, orbital_moment, orbital_magnetization_mesh, optical_conductivity_mesh,
 spin_berry_curvature, spin_hall_conductivity_mesh, band_velocity, anomalous_transport_mesh, drude_weight_mesh, shift_current*,
-injection_current_mesh, quantum_geometric_tensor*) that reaches every routed form of DESIGN.md sections 11 to 13, 15 to 17 and 20,
-every output saved to one .npz:
+injection_current_mesh, quantum_geometric_tensor*, susceptibility_mesh, thermodynamics_mesh, fermi_level_mesh, density_matrix_mesh,
+dos_mesh) that reaches every routed form of DESIGN.md sections 11 to 13, 15 to 17, 20, 26 and 27, every output saved to one .npz:
 
     TBK_LIBRARY=<libtbk.so> python profiles/kubo_bits.py out.npz      run the calls with that library (a fresh process each)
     python profiles/kubo_bits.py --compare a.npz b.npz                compare two runs as uint64 views (NaN and infinity patterns too)
@@ -10,6 +10,7 @@ every output saved to one .npz:
 Two builds that claim the same results must give equal files: the comparison has no tolerance."""
 import contextlib
 import io
+import itertools
 import os
 import sys
 
@@ -132,6 +133,25 @@ def main():
         keep(name + " qgt list occ", m.quantum_geometric_tensor(k, occ=occ))
         keep(name + " qgt mesh", m.quantum_geometric_tensor_mesh(mesh))
         keep(name + " qgt mesh occ", m.quantum_geometric_tensor_mesh(mesh, occ=occ))
+        # the susceptibility and the occupied-state calls (sections 26 and 27): q = 0, a mesh vector and a general q
+        qs = np.array([[0.0] * dk, [1.0 / mesh[0]] + [0.0] * (dk - 1), [0.37, 0.21, 0.11][:dk]])
+        nocc = len(occ)
+        for kT in (0.0, 0.05):
+            for me in (True, False):
+                keep("%s chi static me%d kT%g" % (name, me, kT), m.susceptibility_mesh(mesh, qs, fermi_level=mu, kT=kT, matrix_elements=me))
+                for w in (omega, np.linspace(-1.0, hi - lo, 1030)) if name == "haldane_n2" else (omega,):
+                    keep("%s chi w%d me%d kT%g" % (name, len(w), me, kT),
+                         m.susceptibility_mesh(mesh, qs, w, 0.03, fermi_level=mu, kT=kT, matrix_elements=me))
+            keep("%s thermo kT%g" % (name, kT), m.thermodynamics_mesh(mesh, few, kT=kT))
+            if name in ("haldane_n2", "kane_mele_n4", "silicon_n8"):
+                keep("%s thermo5000 kT%g" % (name, kT), m.thermodynamics_mesh(mesh, many, kT=kT))
+            keep("%s density matrix kT%g" % (name, kT),
+                 m.density_matrix_mesh(mesh, mu, kT=kT, R_list=list(itertools.product((-1, 0, 1), repeat=dk))))
+        nkp = int(np.prod(mesh))
+        keep_all(name + " fermi level kT0", m.fermi_level_mesh(mesh, [nocc, (nocc * nkp - 1) / nkp, (nocc * nkp + 1) / nkp], return_edges=True))
+        keep(name + " fermi level kT0.05", m.fermi_level_mesh(mesh, [nocc, nocc - 0.37, nocc + 0.21], kT=0.05))
+        if name in ("haldane_n2", "silicon_n8"):
+            keep_all(name + " dos", m.dos_mesh(mesh, bins=50, range=(lo, hi)))
         print(name, len(out), flush=True)
 
     # one dimension: the whole-mesh forms alone (sections 16 and 20)

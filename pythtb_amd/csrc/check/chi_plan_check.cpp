@@ -4,7 +4,8 @@
 // buffer against its cap; that the k-groups of every chunk (the last, shorter one included) cover its points once; that nothing but
 // acc and the offsets behind it depends on nq; and the layout of the scratch block -- every buffer at a multiple of 256, in order,
 // none overlapping, the last one ending at the total (each is filled with its own index over a real host block and read back, under
-// the sanitizer, where the block is at most 512 MiB).  Then the argument checks: every rule of chi_check, one bad value at a time.
+// the sanitizer, where the block is at most 512 MiB).  Then the argument checks: every rule of chi_check, one bad value at a time; and
+// what tbk_kubo.h shares between the mesh sweeps: the eigenvalue-only chunk workspace and the one mesh check.
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -71,7 +72,7 @@ static int check_layout(const char* tag, const ChiPlan& p, int n, int dk, int nq
         {p.off_part, (size_t)p.part_doubles * D},
         {cb + p.cw.off[0], (size_t)p.chunk * dk * D},
         {cb + p.cw.off[1], (size_t)p.chunk * n * D},
-        {cb + p.cw.off[2], (size_t)p.chunk * nn * sizeof(cd)},
+        {cb + p.cw.off[2], p.me ? (size_t)p.chunk * nn * sizeof(cd) : 0},
         {x0, (size_t)p.chunk * dk * D},
         {x0 + p.off_e2, (size_t)p.chunk * n * D},
         {x0 + p.off_v2, p.me ? (size_t)p.chunk * nn * sizeof(cd) : 0},
@@ -86,6 +87,7 @@ static int check_layout(const char* tag, const ChiPlan& p, int n, int dk, int nq
         end = buf[i][0] + buf[i][1];
     }
     if (end > p.total || p.total - end >= 256 + 256) return printf("%s: the last buffer ends at %zu, the total is %zu\n", tag, end, p.total);
+    if (!p.me && p.cw.off[3] != p.cw.off[2]) return printf("%s: bytes for eigenvectors in an eigenvalue-only plan\n", tag);
     if (p.x0 != p.off_v2 + (p.me ? al256((size_t)p.chunk * nn * sizeof(cd)) : 0)) return printf("%s: x0\n", tag);
     if (p.total > ((size_t)512 << 20)) return 0;
     unsigned char* base = (unsigned char*)aligned_alloc(256, al256(p.total));
@@ -193,6 +195,35 @@ static int check_args() {
     return bad;
 }
 
+// What the mesh sweeps share (tbk_kubo.h): an eigenvalue-only KuboChunks has no bytes for eigenvectors and is that much shorter; the
+// one mesh check gives every caller the same return code for a bad mesh and the same point count for a good one.
+static int check_shared() {
+    const char* fn = "chi_plan_check";
+    const size_t vb = al256((size_t)100 * 34 * 34 * sizeof(cd));
+    const KuboChunks full(34, 2, 100, 512, 0, 768), ev(34, 2, 100, 512, 0, 768, false);
+    if (full.off[3] - full.off[2] != vb || ev.off[3] != ev.off[2] || ev.bytes() + vb != full.bytes() || ev.off[2] != full.off[2])
+        return printf("KuboChunks: an eigenvalue-only workspace holds %zu bytes of eigenvectors\n", ev.off[3] - ev.off[2]);
+    const int32_t good[3] = {4, 5, 6}, zero[3] = {4, 0, 6}, neg[3] = {4, -5, 6};
+    const double q[2] = {0.1, 0.2}, w[1] = {0.5};
+    tbk_model mm;
+    mm.dim_k = 2, mm.nsta = 3;
+    for (const int32_t* mesh : {good, zero, neg}) {
+        const int want = mesh == good ? TBK_OK : TBK_EINVAL;
+        int64_t np[3] = {0, 0, 0};
+        PlaneArgs P;
+        const int rc[4] = {kubo_mesh_points(fn, 2, mesh, np[0]), pair_sweep_check(fn, &mm, mesh, 1, w, 0.05, 0.0, 0.0, np[1]),
+                           chi_check(fn, 2, 3, mesh, 1, q, 1, w, 0.05, 0.0, 0.0, 1, np[2]), kubo_whole_mesh(fn, mesh, 2, P)};
+        for (int i = 0; i < 4; ++i)
+            if (rc[i] != want) return printf("mesh %dx%d: caller %d returns %d, not %d\n", mesh[0], mesh[1], i, rc[i], want);
+        if (want == TBK_OK && (np[0] != 20 || np[1] != 20 || np[2] != 20 || P.npts != 20)) return printf("mesh 4x5: the point count\n");
+    }
+    mm.dim_k = 4;
+    int64_t np = 0;
+    if (pair_sweep_check(fn, &mm, good, 1, w, 0.05, 0.0, 0.0, np) != TBK_EINVAL || kubo_mesh_dim(fn, 0) != TBK_EINVAL || kubo_mesh_dim(fn, 3))
+        return printf("the dimension of the mesh\n");
+    return 0;
+}
+
 int main() {
     int bad = 0, cases = 0;
     for (const Case& c : kCases) {
@@ -200,6 +231,7 @@ int main() {
         ++cases;
     }
     bad |= check_args() ? 1 : 0;
+    bad |= check_shared() ? 1 : 0;
     if (bad) return printf("chi_plan_check: FAILED\n"), 1;
     printf("chi_plan_check: %d plans and the argument checks ok\n", cases);
     return 0;

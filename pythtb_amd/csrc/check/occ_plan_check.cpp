@@ -217,6 +217,17 @@ static int check_args() {
         no(occ_mesh_check(fn, 2, 3, huge, npts), "2^31 mesh points");
         ok(occ_mesh_check(fn, 2, 3, most, npts), "just under 2^31 mesh points");
     }
+    // the mesh check is the one of every mesh sweep (tbk_kubo.h): the same return code and point count from each caller
+    {
+        const int32_t mb[3] = {4, 0, 6}, mneg[3] = {4, -5, 6};
+        for (const int32_t* ms : {mesh, mb, mneg}) {
+            int64_t n0 = 0, n1 = 0;
+            PlaneArgs P;
+            const int r0 = kubo_mesh_points(fn, 2, ms, n0), r1 = occ_mesh_check(fn, 2, 3, ms, n1), r2 = kubo_whole_mesh(fn, ms, 2, P);
+            if (r0 != (ms == mesh ? TBK_OK : TBK_EINVAL) || r1 != r0 || r2 != r0) bad |= printf("mesh %dx%d: %d %d %d\n", ms[0], ms[1], r0, r1, r2);
+            if (!r0 && (n0 != 20 || n1 != 20 || P.npts != 20)) bad |= printf("mesh 4x5: the point count\n");
+        }
+    }
     // thermodynamics
     {
         const double mu[3] = {0.5, -1.0, 0.5};

@@ -11,7 +11,7 @@
 #define TBK_CHI_FLAGS_ALL TBK_CHI_MATRIX_ELEMENTS
 #define CHI_LDS_CD 2048                                  // c128 of LDS per workgroup of k_chi_pairs (32 KiB: five workgroups per CU)
 static const int64_t kChiOutCap = (int64_t)1 << 22;      // nq nw at most
-static const int kChiListMax = 65536;                    // q points, frequencies at most
+static const int kChiListMax = 65536;                    // q points at most (frequencies: kKuboOmegaMax)
 
 // points per workgroup of k_chi_pairs: U(k) and U(k+q) of every point in LDS
 static inline int chi_lds_points(int n) { return std::max(1, std::min(64, CHI_LDS_CD / (2 * n * n))); }
@@ -35,30 +35,24 @@ struct ChiPlan {
 // the checks of tbk_susceptibility_mesh behind its pointers; npts = the points of the mesh
 static int chi_check(const char* fn, int dk, int n, const int32_t* mesh, int nq, const double* q, int nomega, const double* omega,
                      double eta, double mu, double kT, int flags, int64_t& npts) {
-    TBK_REQUIRE(dk >= 1 && dk <= 3, TBK_EINVAL, "%s: dim_k=%d (meshes of 1, 2 or 3 dimensions)", fn, dk);
+    int rc = kubo_mesh_dim(fn, dk);
+    if (rc) return rc;
     TBK_REQUIRE(n >= 1 && n <= 2048, TBK_EINVAL, "%s: nsta=%d (1..2048 states)", fn, n);
     TBK_REQUIRE((flags & ~TBK_CHI_FLAGS_ALL) == 0, TBK_EINVAL, "%s: flags=%d (TBK_CHI_MATRIX_ELEMENTS or 0)", fn, flags);
     TBK_REQUIRE(nq >= 1 && nq <= kChiListMax, TBK_EINVAL, "%s: nq=%d (1..%d q points)", fn, nq, kChiListMax);
     for (int64_t j = 0; j < (int64_t)nq * dk; ++j)
         TBK_REQUIRE(std::isfinite(q[j]), TBK_EINVAL, "%s: q point %lld is not finite", fn, (long long)(j / dk));
     if (omega) {
-        TBK_REQUIRE(nomega >= 1 && nomega <= kChiListMax, TBK_EINVAL, "%s: nomega=%d (1..%d frequencies)", fn, nomega, kChiListMax);
-        for (int j = 0; j < nomega; ++j) TBK_REQUIRE(std::isfinite(omega[j]), TBK_EINVAL, "%s: frequency %d is not finite", fn, j);
-        TBK_REQUIRE(std::isfinite(eta) && eta > 0.0, TBK_EINVAL, "%s: eta must be finite and > 0", fn);
+        rc = kubo_omega_check(fn, nomega, omega, eta);
+        if (rc) return rc;
         TBK_REQUIRE((int64_t)nq * nomega <= kChiOutCap, TBK_EINVAL, "%s: nq * nomega = %lld (at most %lld)", fn,
                     (long long)nq * nomega, (long long)kChiOutCap);
     } else {
         TBK_REQUIRE(nomega == 0, TBK_EINVAL, "%s: nomega=%d without omega (the static mode takes 0)", fn, nomega);
         TBK_REQUIRE(eta == 0.0, TBK_EINVAL, "%s: the static mode is the eta -> 0 limit: eta must be 0", fn);
     }
-    TBK_REQUIRE(std::isfinite(kT) && kT >= 0.0, TBK_EINVAL, "%s: kT must be finite and >= 0", fn);
-    TBK_REQUIRE(std::isfinite(mu), TBK_EINVAL, "%s: the Fermi level must be finite", fn);
-    npts = 1;
-    for (int d = 0; d < dk; ++d) {
-        TBK_REQUIRE(mesh[d] >= 1, TBK_EINVAL, "%s: mesh[%d]=%d", fn, d, mesh[d]);
-        npts *= mesh[d];
-    }
-    return TBK_OK;
+    rc = kubo_occupation_check(fn, kT, mu);
+    return rc ? rc : kubo_mesh_points(fn, dk, mesh, npts);
 }
 
 // the plan of a checked call
@@ -84,7 +78,7 @@ static ChiPlan chi_plan(int n, int dk, int64_t npts, int nq, int nw, int flags) 
     p.x0 = p.off_v2 + (p.me ? al256((size_t)p.chunk * nn * sizeof(cd)) : 0);
     p.x1 = p.dynamic ? (size_t)p.chunk * nn * 2 * sizeof(double) : 0;
     p.x2 = p.wide ? (size_t)p.chunk * nn * sizeof(double) : 0;
-    p.cw = KuboChunks(n, dk, p.chunk, p.x0, p.x1, p.x2);
+    p.cw = KuboChunks(n, dk, p.chunk, p.x0, p.x1, p.x2, p.me);
     p.off_om = 256;
     p.off_q = p.off_om + al256((size_t)nw * sizeof(double));
     p.off_acc = p.off_q + al256((size_t)nq * dk * sizeof(double));

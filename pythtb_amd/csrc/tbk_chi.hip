@@ -6,8 +6,8 @@
 //   static    chi0(q)    =  (1 / N_k) sum_k sum_{n,m} L_nm |M_nm|^2,   L = -(f_n - f_m) / (E_n - E_m), -f'(E) where the levels meet
 // over ALL n^2 ordered pairs (n = m included); without TBK_CHI_MATRIX_ELEMENTS |M|^2 = 1 and no eigenvector is formed anywhere.
 //
-// Pipeline, in chunks of a fixed number of mesh points (tbk_chi.h's plan; tbk_kubo.h's chunk length): the device k generator and the
-// list solver at k ONCE per chunk, then for every q of the list
+// Pipeline, in chunks of a fixed number of mesh points (tbk_chi.h's plan; tbk_kubo.h's chunk loop kubo_for_chunks): the device k
+// generator and the list solver at k ONCE per chunk, then for every q of the list
 //   k_chi_kq       k + q
 //   the list solver at k + q (eigenvalues only without matrix elements) into the chunk's first extra buffer
 //   PAIR stage     n <= 32   k_chi_pairs: U(k) and U(k+q) of P points in LDS, one lane per (point, n, m) forms M_nm
@@ -16,20 +16,20 @@
 //                  static: every lane forms L |M|^2 and the workgroup's sum goes to part[g]; dynamic: a record (d, c) =
 //                  (E_n - E_m, (f_n - f_m) |M|^2) per ordered pair
 //   FREQUENCY stage (dynamic) k_chi_omega: x = sum c (w + d) r and y = sum c r, r = 1 / ((w + d)^2 + eta^2), per k-group
-//   k_chi_rows     acc[q][row] (+)= sum_g part[g][row], the groups in a fixed order, chunk after chunk in stream order
+//   k_group_rows   acc[q][row] (+)= sum_g part[g][row], the groups in a fixed order, chunk after chunk in stream order
 // and chi0 = (-x + i eta y) / N_k on the host.  The chunk, the groups and the tiles do not depend on the q list and nothing uses
 // atomics: two calls give the same bits, and a q gives the same bits alone and inside a longer list.
 #include <math.h>
 #include "tbk_chi.h"
 
 // ---------------------------------------------------------------- occupation weights
-// f_n - f_m without cancellation: sinh h / (cosh h + cosh u), h = (E_m - E_n) / 2kT, u = ((E_n + E_m) / 2 - mu) / kT, scaled by
-// exp(-max(|h|, |u|)) as opt_weight does
+// f_n - f_m without cancellation: sinh h / (cosh h + cosh u), h = (E_m - E_n) / 2kT, u = ((E_n + E_m) / 2 - mu) / kT, by tbk_kubo.h's
+// FermiPair
 __device__ __forceinline__ double chi_fdiff(const double en, const double em, const double mu, const double kT) {
     if (kT == 0.0) return (en <= mu ? 1.0 : 0.0) - (em <= mu ? 1.0 : 0.0);
-    const double h = 0.5 * (em - en) / kT, a = fabs(h), u = fabs((0.5 * (en + em) - mu) / kT), M = fmax(a, u);
-    const double den = exp(a - M) + exp(-a - M) + exp(u - M) + exp(-u - M);
-    const double mag = -exp(a - M) * expm1(-2.0 * a) / den;
+    const double h = 0.5 * (em - en) / kT;
+    const FermiPair p(fabs(h), fabs((0.5 * (en + em) - mu) / kT));
+    const double mag = -p.num() / p.den;
     return h < 0.0 ? -mag : mag;
 }
 // L = -(f_n - f_m) / (E_n - E_m) = (sinh h / h) / (2 kT (cosh h + cosh u)): smooth through h = 0, where it is -f'(E)
@@ -38,10 +38,10 @@ __device__ __forceinline__ double chi_static_weight(const double en, const doubl
         const bool fn = en <= mu, fm = em <= mu;
         return fn == fm ? 0.0 : (fn ? 1.0 : -1.0) / (em - en);
     }
-    const double a = fabs(0.5 * (em - en) / kT), u = fabs((0.5 * (en + em) - mu) / kT), M = fmax(a, u);
-    const double den = exp(a - M) + exp(-a - M) + exp(u - M) + exp(-u - M);
-    const double s = a < 1e-4 ? (1.0 + a * a * (1.0 / 6.0)) * exp(-M) : -exp(a - M) * expm1(-2.0 * a) / (2.0 * a);
-    return s / (kT * den);
+    const double a = fabs(0.5 * (em - en) / kT);
+    const FermiPair p(a, fabs((0.5 * (en + em) - mu) / kT));
+    const double s = a < 1e-4 ? (1.0 + a * a * (1.0 / 6.0)) * exp(-p.M) : -p.num() / (2.0 * a);
+    return s / (kT * p.den);
 }
 
 // what a lane does with its ordered pair (n at k, m at k + q) of point ik: the record, or its term of the static sum
@@ -147,8 +147,10 @@ __global__ __launch_bounds__(256) void k_chi_lanes(const double* __restrict__ e1
 }
 
 // ---------------------------------------------------------------- frequency stage
-// Workgroup (tile of kPairTile frequencies, k-group g), the plan of k_opt_omega: lane t takes w[tile + t] and w[tile + 256 + t] and
-// walks the records of the points [g nk / G, (g + 1) nk / G) of the chunk in order (wave-uniform values; c = 0: skipped).
+// Workgroup (tile of kPairTile frequencies, k-group g), the plan of tbk_pairs.h's k_pair_omega, kept as this unit's own text: as a
+// policy of that kernel the same loop body compiled with its scalar adds in another order and measured slower (DESIGN.md section 14,
+// last addendum).  Lane t takes w[tile + t] and w[tile + 256 + t] and walks the records of the points [g nk / G, (g + 1) nk / G) of
+// the chunk in order (wave-uniform values; c = 0: skipped).
 // part[g][0][w] = sum c (w + d) r, part[g][1][w] = sum c r with r = 1 / ((w + d)^2 + eta^2).  A tile whose second half holds no
 // frequency (nw <= 256, or the last tile) walks with one frequency per lane: the same operations on that one, half the work.
 template <int NS>
@@ -189,16 +191,6 @@ __global__ __launch_bounds__(256) void k_chi_omega(const double* __restrict__ re
         out[wi[s]] = sx[s];
         out[nw + wi[s]] = sy[s];
     }
-}
-
-// acc[row] (+)= sum_g part[g][row] in a fixed order (one workgroup per row; the form of k_opt_rows)
-__global__ __launch_bounds__(256) void k_chi_rows(const double* __restrict__ part, const int G, const int64_t nrows, const int accumulate,
-                                                  double* __restrict__ acc) {
-    __shared__ double red[4];
-    double s = 0.0;
-    for (int g = threadIdx.x; g < G; g += 256) s += part[(int64_t)g * nrows + blockIdx.x];
-    const double t = block_sum(s, red);
-    if (threadIdx.x == 0) acc[blockIdx.x] = accumulate ? acc[blockIdx.x] + t : t;
 }
 
 // ---------------------------------------------------------------- host side
@@ -250,9 +242,6 @@ extern "C" int tbk_susceptibility_mesh(tbk_model* m, const int32_t* mesh, int nq
     double* part = (double*)(b + pl.off_part);
     KuboChunks cw = pl.cw;
     cw.base = b + pl.off_chunks;
-    double* kc = (double*)(cw.base + cw.off[0]);
-    double* e1 = (double*)(cw.base + cw.off[1]);
-    cd* v1 = pl.me ? (cd*)(cw.base + cw.off[2]) : nullptr;
     unsigned char* x0 = cw.extra<unsigned char>(0);
     double* kq = (double*)x0;
     double* e2 = (double*)(x0 + pl.off_e2);
@@ -262,40 +251,38 @@ extern "C" int tbk_susceptibility_mesh(tbk_model* m, const int32_t* mesh, int nq
     if (pl.dynamic) TBK_HIP(hipMemcpyAsync(om_dev, omega, (size_t)nomega * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     TBK_HIP(hipMemcpyAsync(q_dev, q, (size_t)nq * dk * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     const int64_t nn = (int64_t)n * n;
-    for (int64_t first = 0; first < npts; first += pl.chunk) {
-        const int64_t cnt = std::min<int64_t>(pl.chunk, npts - first);
-        rc = tbk_k_uniform_mesh_range_dev(ctx, dk, mesh, first, cnt, kc);
-        if (rc) return rc;
-        rc = tbk_solve_list_dev_checked(m, kc, cnt, e1, (double*)v1);
-        if (rc) return rc;
+    // the solve at k once per chunk (eigenvalues only without matrix elements: v1 is null), then every q of the list
+    rc = kubo_for_chunks(m, cw, nullptr, mesh, npts, [&](int64_t first, int64_t cnt, const double* kc, const double* e1, const cd* v1) -> int {
         for (int iq = 0; iq < nq; ++iq) {
             {
                 ProfScope ps(ctx, "chi_kq");
-                hipLaunchKernelGGL(k_chi_kq, dim3(nblk(cnt * dk)), dim3(256), 0, ctx->stream, (const double*)kc,
-                                   (const double*)(q_dev + (int64_t)iq * dk), cnt, dk, kq);
+                hipLaunchKernelGGL(k_chi_kq, dim3(nblk(cnt * dk)), dim3(256), 0, ctx->stream, kc, (const double*)(q_dev + (int64_t)iq * dk), cnt,
+                                   dk, kq);
                 TBK_HIP(hipGetLastError());
             }
-            rc = tbk_solve_list_dev_checked(m, kq, cnt, e2, (double*)v2);
-            if (rc) return rc;
+            int r2 = tbk_solve_list_dev_checked(m, kq, cnt, e2, (double*)v2);
+            if (r2) return r2;
             int groups = 0;
             if (pl.dynamic) {
-                rc = chi_pair_stage<false>(m, pl, cnt, e1, v1, e2, v2, m2, mu, kT, rec, groups);
-                if (rc) return rc;
+                r2 = chi_pair_stage<false>(m, pl, cnt, e1, v1, e2, v2, m2, mu, kT, rec, groups);
+                if (r2) return r2;
                 ProfScope ps(ctx, "chi_omega");
                 groups = pl.G;
                 hipLaunchKernelGGL(k_chi_omega, dim3(pl.ntile, (unsigned)pl.G), dim3(256), 0, ctx->stream, (const double*)rec, cnt, nn, pl.G,
                                    (const double*)om_dev, nomega, eta, part);
                 TBK_HIP(hipGetLastError());
             } else {
-                rc = chi_pair_stage<true>(m, pl, cnt, e1, v1, e2, v2, m2, mu, kT, part, groups);
-                if (rc) return rc;
+                r2 = chi_pair_stage<true>(m, pl, cnt, e1, v1, e2, v2, m2, mu, kT, part, groups);
             }
+            if (r2) return r2;
             ProfScope ps(ctx, "chi_rows");
-            hipLaunchKernelGGL(k_chi_rows, dim3((unsigned)pl.nrows), dim3(256), 0, ctx->stream, (const double*)part, groups, pl.nrows,
+            hipLaunchKernelGGL(k_group_rows, dim3((unsigned)pl.nrows), dim3(256), 0, ctx->stream, (const double*)part, groups, pl.nrows, 1.0,
                                first > 0 ? 1 : 0, acc + (int64_t)iq * pl.nrows);
             TBK_HIP(hipGetLastError());
         }
-    }
+        return TBK_OK;
+    });
+    if (rc) return rc;
     std::vector<double> sums((size_t)pl.acc_doubles);
     TBK_HIP(hipMemcpyAsync(sums.data(), acc, sums.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     TBK_HIP(hipStreamSynchronize(ctx->stream));

@@ -166,6 +166,18 @@ extern "C" int tbk_k_path_dev(tbk_ctx* ctx, int dim_k, int n_nodes, const double
     return TBK_OK;
 }
 
+// the eigenvalues e[n][npts] of the whole mesh (checked by the caller), generated and kept on the device: up to 4 states straight from
+// the mesh (k_mesh_evals), no k list at all.  For mesh_solve_dev below and tbk_occ.hip.
+int tbk_mesh_evals_dev(tbk_model* m, const int32_t* mesh, int64_t npts, double* k_dev, double* e_dev) {
+    bool done = false;
+    int rc = tbk_mesh_evals_rows(m, mesh, e_dev, &done);
+    if (rc) return rc;
+    if (done) return tbk_eigh_check(m->ctx, m->nsta);
+    rc = tbk_k_uniform_mesh_dev(m->ctx, m->dim_k, mesh, k_dev);
+    if (rc) return rc;
+    return tbk_solve_list_dev_checked(m, k_dev, npts, e_dev, nullptr);
+}
+
 // shared front end: eigenvalues (and optionally vectors) of the model on k_uniform_mesh(mesh),
 // everything generated and kept on the device.  Scratch layout: [flags | k | eval | evec].
 static int mesh_solve_dev(tbk_model* m, const int32_t* mesh, bool vec, size_t extra, int64_t* nk_out, double** k_dev,
@@ -190,12 +202,7 @@ static int mesh_solve_dev(tbk_model* m, const int32_t* mesh, bool vec, size_t ex
     *v_dev = vec ? (double*)(p + al(kb) + al(eb)) : nullptr;
     if (extra_dev) *extra_dev = p + al(kb) + al(eb) + al(vb);
     *nk_out = nk;
-    if (!vec) {          // eigenvalues only, up to 4 states: straight from the mesh (k_mesh_evals), no k list at all
-        bool done = false;
-        rc = tbk_mesh_evals_rows(m, mesh, *e_dev, &done);
-        if (rc) return rc;
-        if (done) return tbk_eigh_check(ctx, n);
-    }
+    if (!vec) return tbk_mesh_evals_dev(m, mesh, nk, *k_dev, *e_dev);
     rc = tbk_k_uniform_mesh_dev(ctx, d, mesh, *k_dev);
     if (rc) return rc;
     return tbk_solve_list_dev_checked(m, *k_dev, nk, *e_dev, *v_dev);

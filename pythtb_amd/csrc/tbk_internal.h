@@ -477,6 +477,8 @@ inline int tbk_flux_take_pending(struct tbk_wfs* w) {
 
 // tbk_solve.hip: eigenvalues on k_uniform_mesh(mesh) by the row kernel (n <= 4); *done = false where it does not apply
 int tbk_mesh_evals_rows(struct tbk_model* m, const int32_t* mesh, double* e_dev, bool* done);
+// tbk_dos.hip: the eigenvalues e_dev[nsta][npts] of the whole (checked) mesh, resident; k_dev takes the k list where one is needed
+int tbk_mesh_evals_dev(struct tbk_model* m, const int32_t* mesh, int64_t npts, double* k_dev, double* e_dev);
 // tbk_berry.hip: the buffers of a flux launch made to hold -- totals and counters of `nslices` slices, `npartial` partial sums,
 // `nplaq` plaquette phases (0: none); sets flux_nslices and flux_plaq_n.  For tbk_berry_flux_async and the fused mesh solve.
 int tbk_flux_buffers(struct tbk_wfs* w, int64_t nslices, int64_t npartial, int64_t nplaq);

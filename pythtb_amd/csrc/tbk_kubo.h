@@ -22,6 +22,31 @@
 static inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 static inline unsigned nblk(int64_t threads) { return (unsigned)((threads + 255) / 256); }
 
+// ---------------------------------------------------------------- the occupation arithmetic (kT > 0), overflow-safe
+// One level at x = (E - mu) / kT, formed by the caller: t = e^{-|x|}, q = 1 / (1 + t), tq = t q.  From them f, -df/dx and the entropy
+// term -f ln f - (1 - f) ln(1 - f) = |x| t q + log1p(t).  t is 0 from |x| = 746 on; |x| is cut at 1024 there, so that no 0 * inf is
+// formed and the sum is 0 once t has underflowed -- one v_min_f64, where a test of tq compiles to a divergent branch around log1p in
+// the thermal scans' inner loop.
+struct FermiTerms {
+    double x, t, q, tq;
+    __device__ __forceinline__ double f() const { return x >= 0.0 ? tq : q; }
+    __device__ __forceinline__ double mdf() const { return tq * q; }
+    __device__ __forceinline__ double entropy() const { return fma(fmin(fabs(x), 1024.0), tq, log1p(t)); }
+};
+__device__ __forceinline__ FermiTerms fermi_terms(const double x) {
+    const double t = exp(-fabs(x)), q = 1.0 / (1.0 + t);
+    return FermiTerms{x, t, q, t * q};
+}
+// Two levels a = |E_m - E_n| / 2kT and u = |(E_n + E_m) / 2 - mu| / kT apart: |f_n - f_m| = sinh a / (cosh a + cosh u) = -num() / den
+// with both scaled by e^{-M}, M = max(a, u): no cancellation for close levels, no overflow far from mu.
+struct FermiPair {
+    double a, M, den;
+    __device__ __forceinline__ FermiPair(const double a_, const double u) : a(a_), M(fmax(a_, u)) {
+        den = exp(a - M) + exp(-a - M) + exp(u - M) + exp(-u - M);
+    }
+    __device__ __forceinline__ double num() const { return exp(a - M) * expm1(-2.0 * a); }
+};
+
 // ---------------------------------------------------------------- n = 2 on a mesh: the closed form at plane point ii
 struct Kubo2Src {
     ModelView mv;
@@ -114,6 +139,27 @@ static __global__ __launch_bounds__(256) void k_kubo_rows(const double* __restri
     for (int g = threadIdx.x; g < gx; g += 256) acc += p[g];
     const double t = block_sum(acc, red);
     if (threadIdx.x == 0) out[blockIdx.x] = t;
+}
+
+// The same sum over the other layout, part[g][row] (the frequency sweeps of tbk_pairs.h, tbk_chi.hip, tbk_occ.hip):
+// acc[row] (+)= inv sum_g part[g][row], the groups in index order.  k_group_rows is one workgroup per row, for many groups and few
+// rows (G up to 1024, rows = sums x frequencies); k_group_rows_lanes is one LANE per row, for the density matrix's up to 2^23 rows of
+// at most 512 groups, where a workgroup per row would be nearly idle.
+static __global__ __launch_bounds__(256) void k_group_rows(const double* __restrict__ part, const int G, const int64_t nrows, const double inv,
+                                                           const int accumulate, double* __restrict__ acc) {
+    __shared__ double red[4];
+    double s = 0.0;
+    for (int g = threadIdx.x; g < G; g += 256) s += part[(int64_t)g * nrows + blockIdx.x];
+    const double t = block_sum(s, red);
+    if (threadIdx.x == 0) acc[blockIdx.x] = accumulate ? acc[blockIdx.x] + t * inv : t * inv;
+}
+static __global__ __launch_bounds__(256) void k_group_rows_lanes(const double* __restrict__ part, const int G, const int64_t nrows,
+                                                                 const int accumulate, double* __restrict__ acc) {
+    const int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (row >= nrows) return;
+    double s = 0.0;
+    for (int g = 0; g < G; ++g) s += part[(int64_t)g * nrows + row];
+    acc[row] = accumulate ? acc[row] + s : s;
 }
 
 static int kubo_rows_launch(tbk_ctx* ctx, const double* part, int gx, int64_t nrows, double* rows) {
@@ -578,15 +624,40 @@ static int kubo_levels_finite(const char* fn, int nmu, const double* mu) {
     return TBK_OK;
 }
 
+// the checks that the mesh sweeps share, each where the caller's order of checks has it: the dimension of the mesh; npts = its
+// points; the frequencies (1..kKuboOmegaMax, finite) and eta; kT and the Fermi level
+static const int kKuboOmegaMax = 65536;
+static int kubo_mesh_dim(const char* fn, int dk) {
+    TBK_REQUIRE(dk >= 1 && dk <= 3, TBK_EINVAL, "%s: dim_k=%d (meshes of 1, 2 or 3 dimensions)", fn, dk);
+    return TBK_OK;
+}
+static int kubo_mesh_points(const char* fn, int dk, const int32_t* mesh, int64_t& npts) {
+    npts = 1;
+    for (int d = 0; d < dk; ++d) {
+        TBK_REQUIRE(mesh[d] >= 1, TBK_EINVAL, "%s: mesh[%d]=%d", fn, d, mesh[d]);
+        npts *= mesh[d];
+    }
+    return TBK_OK;
+}
+static int kubo_omega_check(const char* fn, int nomega, const double* omega, double eta) {
+    TBK_REQUIRE(nomega >= 1 && nomega <= kKuboOmegaMax, TBK_EINVAL, "%s: nomega=%d (1..%d frequencies)", fn, nomega, kKuboOmegaMax);
+    for (int j = 0; j < nomega; ++j) TBK_REQUIRE(std::isfinite(omega[j]), TBK_EINVAL, "%s: frequency %d is not finite", fn, j);
+    TBK_REQUIRE(std::isfinite(eta) && eta > 0.0, TBK_EINVAL, "%s: eta must be finite and > 0", fn);
+    return TBK_OK;
+}
+static int kubo_occupation_check(const char* fn, double kT, double mu) {
+    int rc = kubo_kt_check(fn, kT, false);
+    if (rc) return rc;
+    TBK_REQUIRE(std::isfinite(mu), TBK_EINVAL, "%s: the Fermi level must be finite", fn);
+    return TBK_OK;
+}
+
 // a mesh of dk = 1, 2 or 3 dimensions as one "plane": every point, in k_uniform_mesh order
 static int kubo_whole_mesh(const char* fn, const int32_t* mesh, int dk, PlaneArgs& P) {
     P = PlaneArgs{};
-    P.npts = 1;
-    for (int d = 0; d < 3; ++d) {
-        if (d < dk) TBK_REQUIRE(mesh[d] >= 1, TBK_EINVAL, "%s: mesh[%d]=%d", fn, d, mesh[d]);
-        P.N[d] = d < dk ? mesh[d] : 1;
-        P.npts *= P.N[d];
-    }
+    int rc = kubo_mesh_points(fn, std::min(dk, 3), mesh, P.npts);
+    if (rc) return rc;
+    for (int d = 0; d < 3; ++d) P.N[d] = d < dk ? mesh[d] : 1;
     P.da = 0;
     P.db = dk > 1 ? 1 : 0;
     P.dc = -1;
@@ -668,8 +739,9 @@ static int kubo_carve(tbk_ctx* ctx, const KuboCarve& c) {
 // ---------------------------------------------------------------- host side: the chunk pipeline
 // The points [0, nk) of a k list or a mesh go through the solver in chunks of a fixed length, so that the chunking -- and with it
 // every result -- does not depend on the machine: at most kKuboChunkBytes of eigenvectors (a caller may shorten it further).
-// KuboChunks describes a chunk's workspace: k, eigenvalues and eigenvectors of `chunk` points, then up to three buffers of the caller
-// (x0, x1, x2 bytes); bytes() of scratch at `base`.
+// KuboChunks describes a chunk's workspace: k, eigenvalues and eigenvectors of `chunk` points (vectors = false: eigenvalues only -- no
+// bytes for eigenvectors, and the solver and the body get a null vector pointer), then up to three buffers of the caller (x0, x1, x2
+// bytes); bytes() of scratch at `base`.
 static const size_t kKuboChunkBytes = (size_t)32 << 20;
 static inline int64_t kubo_chunk_len(int n, int64_t nk) {
     const int64_t chunk = std::max<int64_t>(1, (int64_t)(kKuboChunkBytes / ((size_t)n * n * sizeof(cd))));
@@ -680,9 +752,9 @@ struct KuboChunks {
     size_t off[7] = {0, 0, 0, 0, 0, 0, 0};   // of k, eigenvalues, eigenvectors, the three extra buffers, the end
     unsigned char* base = nullptr;
     KuboChunks() {}
-    KuboChunks(int n, int dk, int64_t chunk_, size_t x0, size_t x1, size_t x2) : chunk(chunk_) {
+    KuboChunks(int n, int dk, int64_t chunk_, size_t x0, size_t x1, size_t x2, bool vectors = true) : chunk(chunk_) {
         const size_t b[6] = {(size_t)chunk * dk * sizeof(double), (size_t)chunk * n * sizeof(double),
-                             (size_t)chunk * n * n * sizeof(cd), x0, x1, x2};
+                             vectors ? (size_t)chunk * n * n * sizeof(cd) : 0, x0, x1, x2};
         for (int i = 0; i < 6; ++i) off[i + 1] = off[i] + al256(b[i]);
     }
     size_t bytes() const { return off[6]; }
@@ -696,7 +768,7 @@ template <class Body>
 static int kubo_for_chunks(tbk_model* m, const KuboChunks& w, const double* k_all_dev, const int32_t* mesh, int64_t nk, Body&& body) {
     double* kc = (double*)(w.base + w.off[0]);
     double* ec = (double*)(w.base + w.off[1]);
-    cd* vc = (cd*)(w.base + w.off[2]);
+    cd* vc = w.off[3] > w.off[2] ? (cd*)(w.base + w.off[2]) : nullptr;
     for (int64_t first = 0; first < nk; first += w.chunk) {
         const int64_t cnt = std::min<int64_t>(w.chunk, nk - first);
         const double* kp = kc;

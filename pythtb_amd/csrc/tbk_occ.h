@@ -41,13 +41,11 @@ __host__ __device__ inline double occ_unkey(const uint64_t k) {
 // ---------------------------------------------------------------- checks
 // the mesh of a model with dim_k 1..3 and 1..2048 states; npts = its points
 static int occ_mesh_check(const char* fn, int dk, int n, const int32_t* mesh, int64_t& npts) {
-    TBK_REQUIRE(dk >= 1 && dk <= 3, TBK_EINVAL, "%s: dim_k=%d (meshes of 1, 2 or 3 dimensions)", fn, dk);
+    int rc = kubo_mesh_dim(fn, dk);
+    if (rc) return rc;
     TBK_REQUIRE(n >= 1 && n <= 2048, TBK_EINVAL, "%s: nsta=%d (1..2048 states)", fn, n);
-    npts = 1;
-    for (int d = 0; d < dk; ++d) {
-        TBK_REQUIRE(mesh[d] >= 1, TBK_EINVAL, "%s: mesh[%d]=%d", fn, d, mesh[d]);
-        npts *= mesh[d];
-    }
+    rc = kubo_mesh_points(fn, dk, mesh, npts);
+    if (rc) return rc;
     TBK_REQUIRE(npts < ((int64_t)1 << 31), TBK_EINVAL, "%s: a mesh of %lld points (fewer than 2^31)", fn, (long long)npts);
     return TBK_OK;
 }

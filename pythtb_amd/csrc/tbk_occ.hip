@@ -23,26 +23,23 @@
 //            P_ij(k) = sum_n f_n w_n[i] conj(w_n[j]) skipping f_n = 0, and adds P_ij e^{-2 pi i k.R} for OCC_RB lattice vectors in registers
 //   n > 32   k_dm_tile: 16 x 16 tiles of P(k), strips of 16 states through LDS, plain VALU
 //            both write part[g][R][i][j] for the k-group g of the chunk
-//   k_dm_rows      acc[R][i][j] (+)= sum_g part[g][R][i][j], the groups in index order, chunk after chunk in stream order
+//   k_group_rows_lanes (tbk_kubo.h)  acc[R][i][j] (+)= sum_g part[g][R][i][j], the groups in index order, chunk after chunk in
+//            stream order
 // The phase e^{-2 pi i k.R} at mesh point (i_a / N_a) is formed from the exact integer (i_a R_a mod N_a).  Nothing uses floating-point
 // atomics and no partition depends on the number of levels, fillings or lattice vectors: two calls give the same bits.
 #include <math.h>
 #include "tbk_occ.h"
 
 // ---------------------------------------------------------------- occupation
-// f and, where wanted, s = -f ln f - (1 - f) ln(1 - f) of x = (E - mu) / kT: t = e^{-|x|}, f = t / (1 + t) or 1 / (1 + t),
-// s = |x| t / (1 + t) + log1p(t) -- and 0 once t has underflowed, so that no 0 * inf is formed
+// f and, where wanted, the entropy term s = -f ln f - (1 - f) ln(1 - f) of x = (E - mu) / kT (tbk_kubo.h's fermi_terms)
 __device__ __forceinline__ double occ_fermi(const double e, const double mu, const double kT, double* s) {
     if (kT == 0.0) {
         if (s) *s = 0.0;
         return e <= mu ? 1.0 : 0.0;
     }
-    const double x = (e - mu) / kT, ax = fabs(x);
-    const double t = exp(-ax);
-    const double q = 1.0 / (1.0 + t);
-    const double tq = t * q;
-    if (s) *s = tq > 0.0 ? fma(ax, tq, log1p(t)) : 0.0;
-    return x >= 0.0 ? tq : q;
+    const FermiTerms ft = fermi_terms((e - mu) / kT);
+    if (s) *s = ft.entropy();
+    return ft.f();
 }
 
 // the Fermi scan's source (k_kubo_fermi, the mesh as one row of N_k points): a level adds (1, E) to its bin
@@ -341,29 +338,7 @@ __global__ __launch_bounds__(256) void k_dm_tile(const ModelView mv, const doubl
             if (r < nrb) part[((int64_t)g * nr + rb0 + r) * n * n + (int64_t)i * n + j] = acc[r];
 }
 
-// acc[row] (+)= sum_g part[g][row], the groups in index order: one LANE per row (a row is one double of part[g][R][i][j]; there are
-// up to 2^23 of them and at most kOccGroupsMax groups, where k_chi_rows' workgroup per row would be nearly idle)
-__global__ __launch_bounds__(256) void k_dm_rows(const double* __restrict__ part, const int G, const int64_t nrows, const int accumulate,
-                                                 double* __restrict__ acc) {
-    const int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (row >= nrows) return;
-    double s = 0.0;
-    for (int g = 0; g < G; ++g) s += part[(int64_t)g * nrows + row];
-    acc[row] = accumulate ? acc[row] + s : s;
-}
-
 // ---------------------------------------------------------------- host side
-// the eigenvalues e[n][npts] of the whole mesh, generated and kept on the device (the front end of tbk_dos_mesh)
-static int occ_mesh_evals(tbk_model* m, const int32_t* mesh, int64_t npts, double* k_dev, double* e_dev) {
-    bool done = false;
-    int rc = tbk_mesh_evals_rows(m, mesh, e_dev, &done);          // up to 4 states: straight from the mesh, no k list
-    if (rc) return rc;
-    if (done) return tbk_eigh_check(m->ctx, m->nsta);
-    rc = tbk_k_uniform_mesh_dev(m->ctx, m->dim_k, mesh, k_dev);
-    if (rc) return rc;
-    return tbk_solve_list_dev_checked(m, k_dev, npts, e_dev, nullptr);
-}
-
 extern "C" int tbk_thermodynamics_mesh(tbk_model* m, const int32_t* mesh, int nmu, const double* mu, double kT, double* out) {
     const char* fn = "tbk_thermodynamics_mesh";
     TBK_REQUIRE(m && mesh && out, TBK_EINVAL, "%s: null argument", fn);
@@ -388,7 +363,7 @@ extern "C" int tbk_thermodynamics_mesh(tbk_model* m, const int32_t* mesh, int nm
     std::vector<double> mus;
     kubo_levels(mu, nmu, !thermal, ord, mus);                       // kT = 0: sorted (ties by index) for the bins of the Fermi scan
     TBK_HIP(hipMemcpyAsync(mu_dev, mus.data(), (size_t)nmu * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    rc = occ_mesh_evals(m, mesh, npts, k_dev, e_dev);
+    rc = tbk_mesh_evals_dev(m, mesh, npts, k_dev, e_dev);
     if (rc) return rc;
     std::vector<double> sums;
     const double nk = (double)npts;
@@ -461,7 +436,7 @@ extern "C" int tbk_fermi_level_mesh(tbk_model* m, const int32_t* mesh, int nfill
     TBK_HIP(hipMemcpyAsync(hi_dev, hi.data(), fb, hipMemcpyHostToDevice, ctx->stream));
     TBK_HIP(hipMemcpyAsync(mu_dev, mid.data(), fb, hipMemcpyHostToDevice, ctx->stream));
     TBK_HIP(hipMemcpyAsync(target_dev, target.data(), fb, hipMemcpyHostToDevice, ctx->stream));
-    rc = occ_mesh_evals(m, mesh, npts, k_dev, e_dev);               // ONE eigen-solve for every filling and every step
+    rc = tbk_mesh_evals_dev(m, mesh, npts, k_dev, e_dev);               // ONE eigen-solve for every filling and every step
     if (rc) return rc;
     const dim3 grid((unsigned)pl.G);
     for (int step = 0; step < kOccSteps; ++step) {
@@ -563,7 +538,7 @@ extern "C" int tbk_density_matrix_mesh(tbk_model* m, const int32_t* mesh, double
             }
             ProfScope ps(ctx, "dm_rows");
             const int64_t nrows = (int64_t)nr * nn * 2;
-            hipLaunchKernelGGL(k_dm_rows, dim3(nblk(nrows)), dim3(256), 0, ctx->stream, (const double*)part, pl.G, nrows, first > 0 ? 1 : 0,
+            hipLaunchKernelGGL(k_group_rows_lanes, dim3(nblk(nrows)), dim3(256), 0, ctx->stream, (const double*)part, pl.G, nrows, first > 0 ? 1 : 0,
                                (double*)(acc + (int64_t)r0 * nn));
             TBK_HIP(hipGetLastError());
         }

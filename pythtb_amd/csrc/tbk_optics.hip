@@ -14,11 +14,11 @@
 // chunk's records at a fixed stride of n (n - 1) / 2 per point
 //   n <= 32    k_opt_pairs: U, d_d H for every direction asked for, and V^d = conj(U) d_d H U^T of several points in LDS
 //   n > 32     k_pair_wsp (W^d = d_d H U^T from the sparse slots), k_opt_vprod (V^d = conj(U) W^d, LDS tiles), k_opt_pairs_wide
-// and the FREQUENCY stage k_opt_omega (two frequencies per lane, the records read as wave-uniform values) adds each k-group's sums
-// into part[G][row]; k_opt_rows sums the G groups in a fixed order.  Every partition depends on the mesh, n, dim_k, n_omega and the
+// and the FREQUENCY stage (k_pair_omega over OptOmega: two frequencies per lane, the records read as wave-uniform values) adds each
+// k-group's sums into part[G][row]; k_group_rows sums the G groups in a fixed order.  Every partition depends on the mesh, n, dim_k, n_omega and the
 // components alone, and nothing uses atomics: two calls give the same bits on any machine.
-// This unit holds the components (OptFields), the record writer and the frequency kernel; the pair stage around the record writer and
-// the sweep driver live in tbk_pairs.h, which tbk_shift.hip shares.
+// This unit holds the components (OptFields), the record writer and the frequency policy; the pair stage around the record writer, the
+// frequency walk and the sweep driver live in tbk_pairs.h, which tbk_shift.hip shares.
 #include <math.h>
 #include <string.h>
 #include "tbk_pairs.h"
@@ -120,77 +120,40 @@ __global__ __launch_bounds__(256) void k_opt_pairs_wide(const double* __restrict
 }
 
 // ---------------------------------------------------------------- frequency stage
-// Workgroup (tile of kPairTile frequencies, k-group g): lane t takes w[tile + t] and w[tile + 256 + t] and walks the records of the
-// points [g nk / G, (g + 1) nk / G) of the chunk in order.  Per lane and frequency the sums
+// The policy of tbk_pairs.h's k_pair_omega: a record is (eps, NS fields A, NA fields B), eps < 0 adds nothing.  Per lane and frequency
 //   x_f = sum A_f G+.x (f < NS) or B_f G-.x,   y_f = sum A_f (r+ + r-) or B_f (r+ - r-)     (G+-.y = eta (r+ +- r-))
-// go to part[g][row], row = (2 f + {0: x, 1: y}) nw + w: written by the first chunk, added to by the later ones (stream order).
+// are sums 2 f and 2 f + 1: part[g][row], row = (2 f + {0: x, 1: y}) nw + w.
 template <int NS, int NA>
-__global__ __launch_bounds__(256) void k_opt_omega(const double* __restrict__ rec, const int64_t nk, const int64_t npair, const int G,
-                                                   const double* __restrict__ omega, const int nw, const double eta,
-                                                   const int accumulate, double* __restrict__ part) {
-    constexpr int NF = NS + NA, R = 1 + NF;
-    const int base = blockIdx.x * kPairTile;
-    if (base + (int)(threadIdx.x & ~63u) >= nw) return;            // a wavefront without a frequency (uniform)
-    const int g = blockIdx.y;
-    int wi[2];
-    double om[2];
+struct OptOmega {
+    static constexpr int NF = NS + NA, NV = 1 + NF, NQ = 2 * NF;
+    __device__ __forceinline__ int rlen() const { return NV; }
+    __device__ __forceinline__ bool load(const double* __restrict__ p, double (&v)[NV]) const {
 #pragma unroll
-    for (int s = 0; s < 2; ++s) {
-        wi[s] = base + s * 256 + threadIdx.x;
-        om[s] = wi[s] < nw ? omega[wi[s]] : 0.0;
+        for (int f = 0; f < NV; ++f) v[f] = p[f];
+        return !(v[0] < 0.0);                                      // c = 0 or a degenerate pair
     }
-    double sx[2][NF], sy[2][NF];
+    __device__ __forceinline__ void add(const double (&v)[NV], const double om, const double eta2, double (&s)[NQ]) const {
+        const double xp = v[0] - om, xm = -v[0] - om;
+        const double rp = opt_rcp(fma(xp, xp, eta2)), rm = opt_rcp(fma(xm, xm, eta2));
+        const double gp = xp * rp, gm = xm * rm;
+        const double Gpx = gp + gm, Gmx = gp - gm, Gpy = rp + rm, Gmy = rp - rm;
 #pragma unroll
-    for (int s = 0; s < 2; ++s)
+        for (int f = 0; f < NS; ++f) {
+            s[2 * f] = fma(v[1 + f], Gpx, s[2 * f]);
+            s[2 * f + 1] = fma(v[1 + f], Gpy, s[2 * f + 1]);
+        }
 #pragma unroll
-        for (int f = 0; f < NF; ++f) sx[s][f] = sy[s][f] = 0.0;
-    const double eta2 = eta * eta;
-    const int64_t r0 = (int64_t)g * nk / G * npair, r1 = (int64_t)(g + 1) * nk / G * npair;
-    const double* __restrict__ p = rec + r0 * R;
-    for (int64_t r = r0; r < r1; ++r, p += R) {
-        double v[R];
-#pragma unroll
-        for (int f = 0; f < R; ++f) v[f] = p[f];
-        if (v[0] < 0.0) continue;                                  // c = 0 or a degenerate pair (uniform branch)
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-            const double xp = v[0] - om[s], xm = -v[0] - om[s];
-            const double rp = opt_rcp(fma(xp, xp, eta2)), rm = opt_rcp(fma(xm, xm, eta2));
-            const double gp = xp * rp, gm = xm * rm;
-            const double Gpx = gp + gm, Gmx = gp - gm, Gpy = rp + rm, Gmy = rp - rm;
-#pragma unroll
-            for (int f = 0; f < NS; ++f) {
-                sx[s][f] = fma(v[1 + f], Gpx, sx[s][f]);
-                sy[s][f] = fma(v[1 + f], Gpy, sy[s][f]);
-            }
-#pragma unroll
-            for (int f = NS; f < NF; ++f) {
-                sx[s][f] = fma(v[1 + f], Gmx, sx[s][f]);
-                sy[s][f] = fma(v[1 + f], Gmy, sy[s][f]);
-            }
+        for (int f = NS; f < NF; ++f) {
+            s[2 * f] = fma(v[1 + f], Gmx, s[2 * f]);
+            s[2 * f + 1] = fma(v[1 + f], Gmy, s[2 * f + 1]);
         }
     }
-    double* out = part + (int64_t)g * 2 * NF * nw;
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-        if (wi[s] >= nw) continue;
-#pragma unroll
-        for (int f = 0; f < NF; ++f) {
-            double* px = out + (int64_t)(2 * f) * nw + wi[s];
-            double* py = px + nw;
-            *px = accumulate ? *px + sx[s][f] : sx[s][f];
-            *py = accumulate ? *py + sy[s][f] : sy[s][f];
-        }
-    }
-}
+};
 
 // ---------------------------------------------------------------- host side
 template <int NS, int NA>
-static int opt_omega_launch(tbk_ctx* ctx, dim3 grid, const double* rec, int64_t cnt, int64_t npair, int G, const double* om, int nw,
-                            double eta, int accumulate, double* part) {
-    hipLaunchKernelGGL((k_opt_omega<NS, NA>), grid, dim3(256), 0, ctx->stream, rec, cnt, npair, G, om, nw, eta, accumulate, part);
-    TBK_HIP(hipGetLastError());
-    return TBK_OK;
+static int opt_omega_launch(tbk_ctx* ctx, dim3 grid, const PairSweep& w, int64_t cnt, int nw, double eta, int accumulate) {
+    return pair_omega_launch(ctx, grid, OptOmega<NS, NA>{}, w.rec, cnt, w.npair, w.G, w.om, nw, eta, accumulate, w.nrows, 0, w.part);
 }
 
 extern "C" int tbk_optical_cond_mesh(tbk_model* m, const int32_t* mesh, int nomega, const double* omega, double eta, double mu,
@@ -258,10 +221,10 @@ extern "C" int tbk_optical_cond_mesh(tbk_model* m, const int32_t* mesh, int nome
         ProfScope ps(ctx, "opt_omega");
         const dim3 grid(w.ntile, (unsigned)w.G);
         const int acc = first > 0 ? 1 : 0;
-        if (F.ns == 1 && F.na == 0) return opt_omega_launch<1, 0>(ctx, grid, w.rec, cnt, w.npair, w.G, w.om, nomega, eta, acc, w.part);
-        if (F.ns == 1 && F.na == 1) return opt_omega_launch<1, 1>(ctx, grid, w.rec, cnt, w.npair, w.G, w.om, nomega, eta, acc, w.part);
-        if (F.ns == 3) return opt_omega_launch<3, 1>(ctx, grid, w.rec, cnt, w.npair, w.G, w.om, nomega, eta, acc, w.part);
-        return opt_omega_launch<6, 3>(ctx, grid, w.rec, cnt, w.npair, w.G, w.om, nomega, eta, acc, w.part);
+        if (F.ns == 1 && F.na == 0) return opt_omega_launch<1, 0>(ctx, grid, w, cnt, nomega, eta, acc);
+        if (F.ns == 1 && F.na == 1) return opt_omega_launch<1, 1>(ctx, grid, w, cnt, nomega, eta, acc);
+        if (F.ns == 3) return opt_omega_launch<3, 1>(ctx, grid, w, cnt, nomega, eta, acc);
+        return opt_omega_launch<6, 3>(ctx, grid, w, cnt, nomega, eta, acc);
     });
     if (rc) return rc;
     // S_ab = i SA - SB, S_ba = i SA + SB with SA = (x_A, eta y_A), SB = (x_B, eta y_B) of the pair (a, b), a < b; S_aa = i SA

@@ -104,21 +104,17 @@ __global__ __launch_bounds__(256) void k_orb2_records(const ModelView mv, const 
 
 // ---------------------------------------------------------------- reductions
 // kT > 0 (k_kubo_thermal): the records (m, Omega) beside E.  Per (record, level) one exp, one log1p and one division:
-// t = e^{-|x|},  f = 1 / (1 + t) (x < 0) or t / (1 + t),  g = kT log1p(t) (x >= 0) or mu - E + kT log1p(t)
+// t = e^{-|x|},  f = 1 / (1 + t) (x < 0) or t / (1 + t) (tbk_kubo.h's fermi_terms),  g = kT log1p(t) (x >= 0) or mu - E + kT log1p(t)
 struct OrbThermal {
     static constexpr int NR = 2, NQ = 1;
     static constexpr bool kWhole = false;
     static __device__ __forceinline__ void add(const double e, const double (&rc)[2], const double u, const double kT, const double ikT,
                                                double (&acc)[1]) {
         const double m = rc[0], o = rc[1];
-        const double x = (e - u) * ikT;
-        const double t = exp(-fabs(x));
-        const double r = 1.0 / (1.0 + t);
-        const double l = kT * log1p(t);
-        const bool up = x >= 0.0;
-        const double f = up ? t * r : r;
-        const double gg = up ? l : (u - e) + l;
-        acc[0] = fma(f, m, fma(gg, o, acc[0]));
+        const FermiTerms ft = fermi_terms((e - u) * ikT);
+        const double l = kT * log1p(ft.t);
+        const double gg = ft.x >= 0.0 ? l : (u - e) + l;
+        acc[0] = fma(ft.f(), m, fma(gg, o, acc[0]));
     }
 };
 

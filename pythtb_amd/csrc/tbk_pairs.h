@@ -1,13 +1,13 @@
-// tbk_pairs.h -- what the two translation units that turn (point, pair) records into frequency sums share (tbk_optics.hip, DESIGN.md
-// section 12; tbk_shift.hip, section 17):
+// tbk_pairs.h -- what the translation units that turn (point, pair) records into frequency sums share (tbk_optics.hip, DESIGN.md
+// section 12; tbk_shift.hip, section 17; constants, opt_rcp and the plan of the frequency stage also tbk_chi.hip, section 26):
 //   device   the index of a pair, the occupation weight, the operators of a unit in the eigenbasis (pair_lds_ops up to 32 states;
-//            k_pair_wsp and k_opt_vprod from 33), the reciprocal of the frequency stage and the sum over k-groups
+//            k_pair_wsp and k_opt_vprod from 33), the frequency stage k_pair_omega over a policy and its reciprocal
 //   host     the three launches of the wide pair stage (pair_wide_stage), the chunk plan of the records (pair_chunks) and the driver
 //            of a frequency sweep over a mesh (pair_sweep_check, pair_sweep)
 // A unit says what its operators are with a SLOTS type (OptFields, ShiftPass): nops() operators, one(mv, op, z4, kk, z) the value of
 // operator op at the non-empty slot z4 (ModelView.nz), and all(mv, z4, kk, z, sv) the values of every operator at once into
-// sv[op][threadIdx.x].  The unit keeps its record writer and its frequency kernel.  Kernels are static or templates: each unit holds
-// its own copy.
+// sv[op][threadIdx.x].  The unit keeps its record writer and the policy of its frequency stage.  Kernels are static or templates: each
+// unit holds its own copy.
 #pragma once
 #include "tbk_kubo.h"
 
@@ -28,13 +28,11 @@ __device__ __forceinline__ void opt_pair_of(const int n, const int64_t q, int& i
 }
 
 // c = (f_m - f_n) / eps for E_m = E_n + eps, eps > 0.  kT > 0: with h = eps / 2kT and u = ((E_n + E_m) / 2 - mu) / kT,
-// f_m - f_n = -sinh h / (cosh h + cosh u), evaluated as exp(h - M) expm1(-2h) / (e^{h-M} + e^{-h-M} + e^{|u|-M} + e^{-|u|-M}),
-// M = max(h, |u|): no cancellation for close levels, no overflow far from mu.
+// f_m - f_n = -sinh h / (cosh h + cosh u) by tbk_kubo.h's FermiPair.
 __device__ __forceinline__ double opt_weight(const double en, const double em, const double eps, const double mu, const double kT) {
     if (kT == 0.0) return (en <= mu && !(em <= mu)) ? -1.0 / eps : 0.0;
-    const double h = 0.5 * eps / kT, u = fabs((0.5 * (en + em) - mu) / kT), M = fmax(h, u);
-    const double den = exp(h - M) + exp(-h - M) + exp(u - M) + exp(-u - M);
-    return exp(h - M) * expm1(-2.0 * h) / den / eps;
+    const FermiPair p(0.5 * eps / kT, fabs((0.5 * (en + em) - mu) / kT));
+    return p.num() / p.den / eps;
 }
 
 // ---------------------------------------------------------------- pair stage, 1 .. 32 states
@@ -152,14 +150,62 @@ __device__ __forceinline__ double opt_rcp(const double x) {
     return fma(r, e, r);
 }
 
-// rows[r] = inv sum_g part[g][r] in a fixed order (one workgroup per row)
-static __global__ __launch_bounds__(256) void k_opt_rows(const double* __restrict__ part, const int G, const int64_t nrows, const double inv,
-                                                  double* __restrict__ rows) {
-    __shared__ double red[4];
-    double acc = 0.0;
-    for (int g = threadIdx.x; g < G; g += 256) acc += part[(int64_t)g * nrows + blockIdx.x];
-    const double t = block_sum(acc, red);
-    if (threadIdx.x == 0) rows[blockIdx.x] = t * inv;
+// ---------------------------------------------------------------- frequency stage
+// Workgroup (tile of kPairTile frequencies, k-group g): lane t takes w[tile + t] and w[tile + 256 + t] and walks the records of the
+// points [g nk / G, (g + 1) nk / G) of the chunk (nrec records per point) in order, as wave-uniform values.  The policy says what a
+// record is (OptOmega in tbk_optics.hip, ShOmega in tbk_shift.hip; tbk_chi.hip's k_chi_omega is this plan in its own text):
+//   NV, NQ               doubles a lane keeps of a record; sums per frequency
+//   rlen()               doubles per record
+//   load(p, v)           v = what it reads of the record at p; false: the record adds nothing (uniform branch)
+//   add(v, om, eta2, s)  the arithmetic of one (record, frequency) on its NQ sums
+// Sum q of frequency w goes to part[g][(row0 + q) nw + w], nrows doubles per group: written, or added to (accumulate: the later
+// chunks, in stream order).
+template <class Pol>
+__global__ __launch_bounds__(256) void k_pair_omega(const Pol pol, const double* __restrict__ rec, const int64_t nk, const int64_t nrec,
+                                                    const int G, const double* __restrict__ omega, const int nw, const double eta,
+                                                    const int accumulate, const int64_t nrows, const int row0,
+                                                    double* __restrict__ part) {
+    constexpr int NQ = Pol::NQ;
+    const int base = blockIdx.x * kPairTile;
+    if (base + (int)(threadIdx.x & ~63u) >= nw) return;            // a wavefront without a frequency (uniform)
+    const int g = blockIdx.y;
+    int wi[2];
+    double om[2], s[2][NQ];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        wi[h] = base + h * 256 + threadIdx.x;
+        om[h] = wi[h] < nw ? omega[wi[h]] : 0.0;
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) s[h][q] = 0.0;
+    }
+    const int64_t r0 = (int64_t)g * nk / G * nrec, r1 = (int64_t)(g + 1) * nk / G * nrec;
+    const double eta2 = eta * eta;
+    const int R = pol.rlen();
+    const double* __restrict__ p = rec + r0 * R;
+    for (int64_t r = r0; r < r1; ++r, p += R) {
+        double v[Pol::NV];
+        if (!pol.load(p, v)) continue;
+#pragma unroll
+        for (int h = 0; h < 2; ++h) pol.add(v, om[h], eta2, s[h]);
+    }
+    double* out = part + (int64_t)g * nrows + (int64_t)row0 * nw;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        if (wi[h] >= nw) continue;
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) {
+            double* py = out + (int64_t)q * nw + wi[h];
+            *py = accumulate ? *py + s[h][q] : s[h][q];
+        }
+    }
+}
+template <class Pol>
+static int pair_omega_launch(tbk_ctx* ctx, dim3 grid, const Pol& pol, const double* rec, int64_t cnt, int64_t nrec, int G, const double* om,
+                             int nw, double eta, int accumulate, int64_t nrows, int row0, double* part) {
+    hipLaunchKernelGGL(k_pair_omega<Pol>, grid, dim3(256), 0, ctx->stream, pol, rec, cnt, nrec, G, om, nw, eta, accumulate, nrows, row0,
+                       part);
+    TBK_HIP(hipGetLastError());
+    return TBK_OK;
 }
 
 // ---------------------------------------------------------------- host side
@@ -203,19 +249,10 @@ static KuboChunks pair_chunks(int n, int dk, int64_t nk, int R, int wops) {
 // mesh.  The unit checks its pointers before and its directions after.
 static int pair_sweep_check(const char* fn, tbk_model* m, const int32_t* mesh, int nomega, const double* omega, double eta, double mu,
                             double kT, int64_t& npts) {
-    const int dk = m->dim_k;
-    TBK_REQUIRE(dk >= 1 && dk <= 3, TBK_EINVAL, "%s: dim_k=%d (meshes of 1, 2 or 3 dimensions)", fn, dk);
-    TBK_REQUIRE(nomega >= 1 && nomega <= 65536, TBK_EINVAL, "%s: nomega=%d (1..65536 frequencies)", fn, nomega);
-    for (int j = 0; j < nomega; ++j) TBK_REQUIRE(std::isfinite(omega[j]), TBK_EINVAL, "%s: frequency %d is not finite", fn, j);
-    TBK_REQUIRE(std::isfinite(eta) && eta > 0.0, TBK_EINVAL, "%s: eta must be finite and > 0", fn);
-    TBK_REQUIRE(std::isfinite(kT) && kT >= 0.0, TBK_EINVAL, "%s: kT must be finite and >= 0", fn);
-    TBK_REQUIRE(std::isfinite(mu), TBK_EINVAL, "%s: the Fermi level must be finite", fn);
-    npts = 1;
-    for (int d = 0; d < dk; ++d) {
-        TBK_REQUIRE(mesh[d] >= 1, TBK_EINVAL, "%s: mesh[%d]=%d", fn, d, mesh[d]);
-        npts *= mesh[d];
-    }
-    return TBK_OK;
+    int rc = kubo_mesh_dim(fn, m->dim_k);
+    if (!rc) rc = kubo_omega_check(fn, nomega, omega, eta);
+    if (!rc) rc = kubo_occupation_check(fn, kT, mu);
+    return rc ? rc : kubo_mesh_points(fn, m->dim_k, mesh, npts);
 }
 
 // One frequency sweep over the npts points of a mesh (checked; at least two states): sums[row] = (1 / npts) sum over the points of
@@ -258,8 +295,8 @@ static int pair_sweep(tbk_model* m, const int32_t* mesh, int64_t npts, int nomeg
     if (rc) return rc;
     {
         ProfScope ps(ctx, rows_label);
-        hipLaunchKernelGGL(k_opt_rows, dim3((unsigned)nrows), dim3(256), 0, ctx->stream, (const double*)part, G, nrows,
-                           1.0 / (double)npts, rows);
+        hipLaunchKernelGGL(k_group_rows, dim3((unsigned)nrows), dim3(256), 0, ctx->stream, (const double*)part, G, nrows,
+                           1.0 / (double)npts, 0, rows);
         TBK_HIP(hipGetLastError());
     }
     sums.resize((size_t)nrows);

@@ -449,7 +449,7 @@ static int sgf_check_call(const char* who, int nw, const double* omega, double e
 
 // ---------------------------------------------------------------- the chunk driver
 // A call works through its k points in chunks.  The list forms take k[nk][dim_k] from the host (mesh == null), the mesh means
-// generate k_uniform_mesh(mesh) per chunk and sum rows[] doubles per k point with the fixed-order k_opt_rows.
+// generate k_uniform_mesh(mesh) per chunk and sum rows[] doubles per k point with the fixed-order k_group_rows.
 struct SgfPlan {
     int N, nw;
     int64_t nk, chunk, nchunk, rows;   // rows: doubles per k point of the mesh mean
@@ -545,8 +545,8 @@ static int sgf_drive(const char* who, tbk_model* cut, const SgfPlan& P, const do
         if (rc) return rc;
         if (P.mesh) {
             ProfScope ps(ctx, rows_name);
-            hipLaunchKernelGGL(k_opt_rows, dim3((unsigned)rows), dim3(256), 0, ctx->stream, (const double*)out_dev, (int)C.cnt, rows, 1.0,
-                               csum + c * rows);
+            hipLaunchKernelGGL(k_group_rows, dim3((unsigned)rows), dim3(256), 0, ctx->stream, (const double*)out_dev, (int)C.cnt, rows, 1.0,
+                               0, csum + c * rows);
             TBK_HIP(hipGetLastError());
         } else {
             rc = download(C);
@@ -558,8 +558,8 @@ static int sgf_drive(const char* who, tbk_model* cut, const SgfPlan& P, const do
     }
     if (P.mesh) {
         ProfScope ps(ctx, rows_name);
-        hipLaunchKernelGGL(k_opt_rows, dim3((unsigned)rows), dim3(256), 0, ctx->stream, (const double*)csum, (int)P.nchunk, rows,
-                           1.0 / (double)nk, csum + P.nchunk * rows);
+        hipLaunchKernelGGL(k_group_rows, dim3((unsigned)rows), dim3(256), 0, ctx->stream, (const double*)csum, (int)P.nchunk, rows,
+                           1.0 / (double)nk, 0, csum + P.nchunk * rows);
         TBK_HIP(hipGetLastError());
         TBK_HIP(hipMemcpyAsync(out, csum + P.nchunk * rows, (size_t)rows * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     }

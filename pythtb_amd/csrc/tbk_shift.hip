@@ -15,7 +15,8 @@
 // Pipeline (tbk_pairs.h's sweep driver on tbk_kubo.h's chunk loop): the device k generator, the eigen-solver with vectors, then per
 // current direction a one PASS:
 // the PAIR stage writes a record (eps, fields...) per (point, pair i < j) -- eps = -1 for a pair that adds nothing, which is decided
-// before the walk over p -- and the FREQUENCY stage k_sh_omega adds each k-group's sums into part[G][row]; k_opt_rows sums the groups.
+// before the walk over p -- and the FREQUENCY stage (k_pair_omega over ShOmega) adds each k-group's sums into part[G][row]; k_group_rows
+// sums the groups.
 //   n <= 32    k_sh_pairs: U, the V^d and W^{da} of the pass and one scratch matrix of several points in LDS
 //   n > 32     k_pair_wsp (d H U^T and d d H U^T from the sparse slots), k_opt_vprod (conj(U) times it), k_sh_pairs_wide
 // A pass of the full tensor holds at most 3 V + 3 W: at 32 states 8 matrices of 16 KiB with U and the scratch, 128 KiB of the CU's 160.
@@ -223,59 +224,28 @@ __global__ __launch_bounds__(256) void k_sh_pairs_wide(const double* __restrict_
 }
 
 // ---------------------------------------------------------------- frequency stage
-// k_opt_omega's pattern for the one sum that is needed: workgroup (tile of kPairTile frequencies, k-group g), lane t takes w[tile + t] and
-// w[tile + 256 + t] and walks the records of the points [g nk / G, (g + 1) nk / G) of the chunk in order; per lane and frequency
+// The policy of tbk_pairs.h's k_pair_omega for the one sum that is needed: of records (eps, fields...) of R doubles, eps < 0 adding
+// nothing, the NF fields f0 .. f0 + NF - 1; per lane and frequency
 //   y_f = sum field_f [1 / ((eps - w)^2 + eta^2) + 1 / ((eps + w)^2 + eta^2)]
-// for the NF fields f0 .. f0 + NF - 1 of records of R doubles goes to part[g][(row0 + f) nw + w]: written by the first chunk, added to by
-// the later ones (stream order).  A pass with more than 6 fields takes several launches.
+// goes to part[g][(row0 + f) nw + w].  A pass with more than 6 fields takes several launches.
 template <int NF>
-__global__ __launch_bounds__(256) void k_sh_omega(const double* __restrict__ rec, const int64_t nk, const int64_t npair, const int R,
-                                                  const int f0, const int G, const double* __restrict__ omega, const int nw,
-                                                  const double eta, const int accumulate, const int64_t nrows, const int row0,
-                                                  double* __restrict__ part) {
-    const int base = blockIdx.x * kPairTile;
-    if (base + (int)(threadIdx.x & ~63u) >= nw) return;            // a wavefront without a frequency (uniform)
-    const int g = blockIdx.y;
-    int wi[2];
-    double om[2];
+struct ShOmega {
+    static constexpr int NV = 1 + NF, NQ = NF;
+    int R, f0;
+    __device__ __forceinline__ int rlen() const { return R; }
+    __device__ __forceinline__ bool load(const double* __restrict__ p, double (&v)[NV]) const {
+        v[0] = p[0];
 #pragma unroll
-    for (int s = 0; s < 2; ++s) {
-        wi[s] = base + s * 256 + threadIdx.x;
-        om[s] = wi[s] < nw ? omega[wi[s]] : 0.0;
+        for (int f = 0; f < NF; ++f) v[1 + f] = p[1 + f0 + f];
+        return !(v[0] < 0.0);                                      // a pair that adds nothing
     }
-    double sy[2][NF];
+    __device__ __forceinline__ void add(const double (&v)[NV], const double om, const double eta2, double (&s)[NQ]) const {
+        const double xp = v[0] - om, xm = -v[0] - om;
+        const double d = opt_rcp(fma(xp, xp, eta2)) + opt_rcp(fma(xm, xm, eta2));
 #pragma unroll
-    for (int s = 0; s < 2; ++s)
-#pragma unroll
-        for (int f = 0; f < NF; ++f) sy[s][f] = 0.0;
-    const double eta2 = eta * eta;
-    const int64_t r0 = (int64_t)g * nk / G * npair, r1 = (int64_t)(g + 1) * nk / G * npair;
-    const double* __restrict__ p = rec + r0 * R;
-    for (int64_t r = r0; r < r1; ++r, p += R) {
-        const double eps = p[0];
-        if (eps < 0.0) continue;                                   // a pair that adds nothing (uniform branch)
-        double v[NF];
-#pragma unroll
-        for (int f = 0; f < NF; ++f) v[f] = p[1 + f0 + f];
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-            const double xp = eps - om[s], xm = -eps - om[s];
-            const double d = opt_rcp(fma(xp, xp, eta2)) + opt_rcp(fma(xm, xm, eta2));
-#pragma unroll
-            for (int f = 0; f < NF; ++f) sy[s][f] = fma(v[f], d, sy[s][f]);
-        }
+        for (int f = 0; f < NF; ++f) s[f] = fma(v[1 + f], d, s[f]);
     }
-    double* out = part + (int64_t)g * nrows + (int64_t)row0 * nw;
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-        if (wi[s] >= nw) continue;
-#pragma unroll
-        for (int f = 0; f < NF; ++f) {
-            double* py = out + (int64_t)f * nw + wi[s];
-            *py = accumulate ? *py + sy[s][f] : sy[s][f];
-        }
-    }
-}
+};
 
 // out[first + ik] = the sum of the one-field records of point ik in pair order (the k-list call)
 __global__ __launch_bounds__(256) void k_sh_list_sum(const double* __restrict__ rec, const int64_t nk, const int64_t npair,
@@ -378,12 +348,9 @@ static int sh_pair_stage(tbk_model* m, const ShiftPass& S, int64_t cnt, const do
 }
 
 template <int NF>
-static int sh_omega_launch(tbk_ctx* ctx, dim3 grid, const double* rec, int64_t cnt, int64_t npair, int R, int f0, int G, const double* om,
-                           int nw, double eta, int accumulate, int64_t nrows, int row0, double* part) {
-    hipLaunchKernelGGL((k_sh_omega<NF>), grid, dim3(256), 0, ctx->stream, rec, cnt, npair, R, f0, G, om, nw, eta, accumulate, nrows, row0,
-                       part);
-    TBK_HIP(hipGetLastError());
-    return TBK_OK;
+static int sh_omega_launch(tbk_ctx* ctx, dim3 grid, const PairSweep& w, int64_t cnt, int R, int f0, int nw, double eta, int accumulate,
+                           int row0) {
+    return pair_omega_launch(ctx, grid, ShOmega<NF>{R, f0}, w.rec, cnt, w.npair, w.G, w.om, nw, eta, accumulate, w.nrows, row0, w.part);
 }
 
 extern "C" int tbk_gen_ddham(tbk_model* m, const double* k, int64_t nk, int dir0, int dir1, double* out) {
@@ -506,7 +473,7 @@ extern "C" int tbk_photocurrent_mesh(tbk_model* m, const int32_t* mesh, int kind
             for (int f0 = 0; f0 < nf;) {
                 const int left = nf - f0, wd = left >= 6 ? 6 : (left >= 3 ? 3 : (left >= 2 ? 2 : 1));
                 auto go = wd == 6 ? sh_omega_launch<6> : (wd == 3 ? sh_omega_launch<3> : (wd == 2 ? sh_omega_launch<2> : sh_omega_launch<1>));
-                r2 = go(ctx, grid, w.rec, cnt, w.npair, R, f0, w.G, w.om, nomega, eta, acc, w.nrows, row0[s] + f0, w.part);
+                r2 = go(ctx, grid, w, cnt, R, f0, nomega, eta, acc, row0[s] + f0);
                 if (r2) return r2;
                 f0 += wd;
             }

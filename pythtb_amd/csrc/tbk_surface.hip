@@ -21,7 +21,7 @@
 // the last stage of the same kernels inverts z - es, z - et, z - e and writes whole matrices, exposed-cell diagonals or their
 // traces.  k_sgf_wg alone keeps the text of the shared workgroup functions in its body, for its speed (see the kernel).  A problem's arithmetic depends on its own (k, w) alone -- a finished problem is masked off and only keeps its
 // neighbours company at the barriers -- so its bits do not depend on the batch, its position in it or the chunk.  The mesh mean sums
-// per-k rows with the fixed-order k_opt_rows of tbk_pairs.h.  No floating-point atomics anywhere.
+// per-k rows with the fixed-order k_group_rows of tbk_kubo.h.  No floating-point atomics anywhere.
 #include <math.h>
 #include <string.h>
 #include "tbk_sgf.h"

@@ -243,22 +243,17 @@ __global__ __launch_bounds__(256) void k_tr_vel_wide(const ModelView mv, const d
 
 // ---------------------------------------------------------------- thermal scan
 // The policies of k_kubo_thermal (tbk_kubo.h): the records beside E are Omega and vbar^c (transport: hall, nernst, dipole_c) or the
-// w^{cd} (Drude; the whole mesh).  Per (record, level) one exp, one division and (transport) one log1p.
+// w^{cd} (Drude; the whole mesh).  Per (record, level) one exp, one division and (transport) one log1p (tbk_kubo.h's fermi_terms).
 template <int DK>
 struct TrThermal {
     static constexpr int NR = 1 + DK, NQ = 2 + DK;
     static constexpr bool kWhole = false;
     static __device__ __forceinline__ void add(const double e, const double (&r)[NR], const double u, double, const double ikT,
                                                double (&acc)[NQ]) {
-        const double x = (e - u) * ikT, ax = fabs(x);
-        const double t = exp(-ax);
-        const double q = 1.0 / (1.0 + t);
-        const double tq = t * q;
-        const double df = tq * q * ikT;                             // -df/dE
-        const double f = x >= 0.0 ? tq : q;
-        const double en = fma(ax, tq, log1p(t));                    // -f ln f - (1 - f) ln(1 - f)
-        acc[0] = fma(f, r[0], acc[0]);
-        acc[1] = fma(en, r[0], acc[1]);
+        const FermiTerms ft = fermi_terms((e - u) * ikT);
+        const double df = ft.mdf() * ikT;                           // -df/dE
+        acc[0] = fma(ft.f(), r[0], acc[0]);
+        acc[1] = fma(ft.entropy(), r[0], acc[1]);                   // -f ln f - (1 - f) ln(1 - f)
         const double dw = df * r[0];
 #pragma unroll
         for (int c = 0; c < DK; ++c) acc[2 + c] = fma(dw, r[1 + c], acc[2 + c]);
@@ -270,11 +265,7 @@ struct DrudeThermal {
     static constexpr bool kWhole = true;
     static __device__ __forceinline__ void add(const double e, const double (&r)[NR], const double u, double, const double ikT,
                                                double (&acc)[NQ]) {
-        const double x = (e - u) * ikT, ax = fabs(x);
-        const double t = exp(-ax);
-        const double q = 1.0 / (1.0 + t);
-        const double tq = t * q;
-        const double df = tq * q * ikT;                             // -df/dE
+        const double df = fermi_terms((e - u) * ikT).mdf() * ikT;   // -df/dE
 #pragma unroll
         for (int c = 0; c < NQ; ++c) acc[c] = fma(df, r[c], acc[c]);
     }

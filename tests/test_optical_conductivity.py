@@ -170,6 +170,27 @@ def test_haldane_two_states():
 
 
 @pytest.mark.gpu
+def test_frequency_tile_edges():
+    """The frequency walk at the edges of its tile of 512 (two per lane): one lane, one full half-tile, one lane into the second
+    half, a second tile of one frequency -- the same frequencies each time, so a shorter call is a prefix of the longest, bit for bit."""
+    m = haldane()
+    mesh = [6, 5]
+    ev = levels(m, mesh)
+    mu = safe_mu(ev, 0.5 * (ev[0].min() + ev[0].max()))
+    w = np.linspace(-3.0, 3.0, 513)
+    want = opr.conductivity(m, mesh, w, ETA, mu=mu, kT=0.05)
+    got = {}
+    for dirs in ((0, 1), None):
+        ref = want[:, 0, 1] if dirs else want
+        for nw in (1, 256, 257, 513):
+            got[nw] = m.optical_conductivity_mesh(mesh, w[:nw], ETA, fermi_level=mu, kT=0.05, dirs=dirs)
+            assert got[nw].shape == ref[:nw].shape
+            rel = 1e-10 * np.max(np.abs(want[:nw])) / np.max(np.abs(ref[:nw]))   # (check_model's bound for one component)
+            close(got[nw], ref[:nw], rel)
+        np.testing.assert_array_equal(got[257], got[513][:257])
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("name", ["kane_mele", "silicon", "cubic16", "haldane_4x4", "haldane_5x5", "ribbon_20", "ribbon_100",
                                   "random3d_n32", "random3d_n33"])
 def test_models(name):
