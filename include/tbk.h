@@ -539,6 +539,24 @@ int tbk_kpm_eigs(tbk_sparse* sp, const double* k, double e_lo, double e_hi, doub
 int tbk_susceptibility_mesh(tbk_model* model, const int32_t* mesh, int nq, const double* q, int nomega, const double* omega_or_null,
                             double eta, double mu, double kT, int flags, double* out);
 
+/* ---- the orbital-resolved susceptibility matrix and its RPA ----------
+ * Every convention of tbk_susceptibility_mesh.  a, b run over nsel = 1..16 distinct STATE indices sel[] in [0, nsta) (components of the
+ * eigenvector; a spinful model has 2 norb of them), in the order given; A^{nm}_a(k, q) = conj(u_n(k)[a]) u_m(k+q)[a]:
+ *   omega given: chi0[nq][nomega][nsel][nsel] c128,
+ *     chi0_ab(q, w) = -(1 / N_k) sum_k sum_{n,m} [f(E_n(k)) - f(E_m(k+q))] A_a conj(A_b) / (w + i eta + E_n(k) - E_m(k+q))
+ *   omega NULL (nomega = 0, eta = 0): chi0[nq][nsel][nsel] c128 (Hermitian, positive semidefinite, not real in general),
+ *     chi0_ab(q) = (1 / N_k) sum_k sum_{n,m} L_nm A_a conj(A_b)
+ * The sum over a, b of ALL states is the scalar chi0 of tbk_susceptibility_mesh with TBK_CHI_MATRIX_ELEMENTS.
+ * nq max(nomega, 1) nsel^2 <= 2^22.  v NULL (nvq = 0, chi_rpa and det NULL): chi0 alone.  v[nvq][nsel][nsel] c128, finite, nvq = 1 (one
+ * interaction) or nq (a V(q)), not necessarily Hermitian: chi_rpa, shaped like chi0, is chi = (1 - chi0 V)^-1 chi0 per (q, w), by LU with
+ * partial pivoting on the device, and det_or_null[nq][max(nomega, 1)] c128 is det(1 - chi0 V), the signed product of the pivots.  A pivot
+ * that is exactly 0 is no error: that matrix of chi_rpa is NaN and its det is 0.  The chunks, groups, tiles and blocks do not depend on
+ * the q list and nothing uses atomics: bit-reproducible, a q gives the same bits alone and inside a longer list, and chi0 has the same
+ * bits with and without an interaction.                                                                                        */
+int tbk_susceptibility_matrix_mesh(tbk_model* model, const int32_t* mesh, int nq, const double* q, int nomega, const double* omega_or_null,
+                                   double eta, double mu, double kT, int nsel, const int32_t* sel, const double* v_or_null, int nvq,
+                                   double* chi0, double* chi_rpa_or_null, double* det_or_null);
+
 /* ---- the occupied states on k meshes: thermodynamic sums, the Fermi level of a filling, the density matrix ----
  * E_n(k), u_n(k) the eigenpairs of the solver (the convention-II matrix of tbk_gen_ham) on k_uniform_mesh(mesh) (dim_k 1..3, N_k < 2^31
  * points), f = [E <= mu] (kT = 0) or 1 / (1 + exp((E - mu) / kT)); a state counts once (no spin factor: a spinful model has 2 norb).

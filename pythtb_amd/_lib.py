@@ -104,6 +104,8 @@ SIGNATURES = {
     "tbk_spin_curv_mesh": (_i, [_p, _ip, _i, _i, _ip, _i, _i, _dp, _dp, _dp]),
     "tbk_optical_cond_mesh": (_i, [_p, _ip, _i, _dp, C.c_double, C.c_double, C.c_double, _i, _i, _dp]),
     "tbk_susceptibility_mesh": (_i, [_p, _ip, _i, _dp, _i, _dp, C.c_double, C.c_double, C.c_double, _i, _dp]),
+    "tbk_susceptibility_matrix_mesh": (_i, [_p, _ip, _i, _dp, _i, _dp, C.c_double, C.c_double, C.c_double, _i, _ip, _dp, _i, _dp, _dp,
+                                            _dp]),
     "tbk_thermodynamics_mesh": (_i, [_p, _ip, _i, _dp, C.c_double, _dp]),
     "tbk_fermi_level_mesh": (_i, [_p, _ip, _i, _dp, C.c_double, _dp, _dp]),
     "tbk_density_matrix_mesh": (_i, [_p, _ip, C.c_double, C.c_double, _i, _ip, _dp]),

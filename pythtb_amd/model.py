@@ -968,6 +968,19 @@ class tb_model(object):
         vc = np.sqrt(np.linalg.det(a @ a.T))
         return np.einsum("ia,wij,jb->wab", a, out, a) / ((2.0 * np.pi) ** 2 * vc)
 
+    def _q_list_arg(self, q_list):
+        """(q, single) of the susceptibility calls: the checked q list as a contiguous `(nq, dim_k)` array; single: it was one
+        `(dim_k,)` point."""
+        q = np.array(q_list, dtype=float)
+        single = q.ndim == 1
+        if single:
+            q = q.reshape(1, -1)
+        if q.ndim != 2 or q.shape[1] != self._dim_k or q.shape[0] < 1 or q.shape[0] > 65536:
+            raise Exception("\n\nq_list must have shape (nq, dim_k) with 1..65536 points, or (dim_k,).")
+        if not np.all(np.isfinite(q)):
+            raise Exception("\n\nq_list must be finite.")
+        return np.ascontiguousarray(q), single
+
     def susceptibility_mesh(self, mesh_size, q_list, omega=None, eta=None, fermi_level=0.0, kT=0.0, matrix_elements=True):
         """Extension: the bare (Lindhard) susceptibility at momentum transfer q, averaged over the whole
         `k_uniform_mesh(mesh_size)` (1-, 2- or 3-D, generated on the device).  Dynamic (`omega` and `eta > 0` given):
@@ -1004,15 +1017,7 @@ class tb_model(object):
         if self._dim_k not in (1, 2, 3):
             raise Exception("\n\nsusceptibility_mesh needs a model with dim_k 1, 2 or 3.")
         mesh, nk = self._mesh_arg(mesh_size)
-        q = np.array(q_list, dtype=float)
-        single = q.ndim == 1
-        if single:
-            q = q.reshape(1, -1)
-        if q.ndim != 2 or q.shape[1] != self._dim_k or q.shape[0] < 1 or q.shape[0] > 65536:
-            raise Exception("\n\nq_list must have shape (nq, dim_k) with 1..65536 points, or (dim_k,).")
-        if not np.all(np.isfinite(q)):
-            raise Exception("\n\nq_list must be finite.")
-        q = np.ascontiguousarray(q)
+        q, single = self._q_list_arg(q_list)
         nq = q.shape[0]
         flags = 1 if matrix_elements else 0
         if omega is None:
@@ -1033,6 +1038,96 @@ class tb_model(object):
                                                         _lib.dptr(w), float(eta), float(fermi_level), float(kT), flags,
                                                         _lib.dptr(out.view(float))))
         return out[0] if single else out
+
+    def susceptibility_matrix_mesh(self, mesh_size, q_list, omega=None, eta=None, fermi_level=0.0, kT=0.0, states=None,
+                                   interaction=None, return_det=False):
+        """Extension: the orbital-resolved bare susceptibility and the RPA on top of it.  Every convention of
+        `susceptibility_mesh` (k and q reduced, the eigenpairs of `solve_all`, f = [E <= fermi_level] or the Fermi function, all
+        n^2 ordered pairs, no spin factor, the mean over `k_uniform_mesh(mesh_size)` generated on the device, any real q), with
+        the orbital index kept:
+
+            chi0_ab(q, w) = -(1 / N_k) sum_k sum_{n,m} [f(E_n(k)) - f(E_m(k+q))] A_a conj(A_b) / (w + i eta + E_n(k) - E_m(k+q))
+            A_a(k, q)     = conj(u_n(k)[a]) u_m(k+q)[a]
+
+        complex `(nq, nw, na, na)`; static (`omega=None`, `eta=None`): chi0_ab(q) = (1 / N_k) sum_k sum_{n,m} L_nm A_a conj(A_b)
+        with the weight L of `susceptibility_mesh`, complex `(nq, na, na)`: Hermitian and positive semidefinite, but not real in
+        general.  A single `(dim_k,)` q drops the leading axis.  The sum over a, b of ALL states is the scalar chi0 of
+        `susceptibility_mesh`.  At q = 0 every row and column sum of the dynamic matrix vanishes (charge conservation per
+        orbital); the static ones at kT > 0 do not (the intraband -f' term stays).
+
+        states: the indices a -- STATE indices 0 .. nsta - 1, components of the eigenvector in the layout of
+        `solve_one(..., eig_vectors=True)` (a spinful model has 2 norb of them, orbital-major).  None: all states (nsta <= 16);
+        else 1..16 distinct integers in [0, nsta) in any order (no negative indices); the a, b axes follow the order given.
+        nq * max(nw, 1) * na^2 <= 2**22.
+
+        interaction: None returns chi0.  A finite complex `(na, na)` matrix V, or `(nq, na, na)` for a V(q), not necessarily
+        Hermitian, returns `(chi0, chi_rpa)` with chi_rpa = (1 - chi0 V)^-1 chi0 per (q, w), and with `return_det=True`
+        `(chi0, chi_rpa, det)`, det = det(1 - chi0 V), complex `(nq,)` or `(nq, nw)`: the generalized Stoner criterion, whose
+        zeros in w are the collective modes.  With chi0 per spin, as here, the transverse spin channel of an on-site Hubbard U
+        is V = U * identity, the charge channel V = -U * identity (-(U + 2 V(q)) with an extended term).  The solve is an LU
+        with partial pivoting on the device.  A pivot that is exactly 0 does NOT raise: that matrix of chi_rpa is NaN and its
+        det is 0 -- the Stoner point itself is a legitimate input.  The eigenvalues of chi0 V, if wanted, are one line on the
+        host: `np.linalg.eigvals(chi0 @ V)`.
+
+        Fixed reduction order: two calls give the same bits, a q gives the same bits alone and inside a longer q_list, and chi0
+        has the same bits with and without an interaction.  Each q costs a second eigen-solve of the mesh; the measured cases
+        are in DESIGN.md section 28."""
+        if self._dim_k not in (1, 2, 3):
+            raise Exception("\n\nsusceptibility_matrix_mesh needs a model with dim_k 1, 2 or 3.")
+        mesh, nk = self._mesh_arg(mesh_size)
+        q, single = self._q_list_arg(q_list)
+        nq = q.shape[0]
+        if omega is None:
+            if eta is not None:
+                raise Exception("\n\nThe static mode (omega=None) is the eta -> 0 limit: eta must be None.")
+            _sweep_args([0.0], 1.0, fermi_level, kT)
+            w, nw, eta = None, 0, 0.0
+        else:
+            if eta is None:
+                raise Exception("\n\nThe dynamic mode (omega given) needs eta > 0.")
+            w = _sweep_args(omega, eta, fermi_level, kT)
+            nw = int(w.size)
+        if states is None:
+            if self._nsta > 16:
+                raise Exception("\n\nstates=None means all states, which needs nsta <= 16: give states (1..16 state indices).")
+            sel = np.arange(self._nsta, dtype=np.int32)
+        else:
+            st = np.asarray(states)
+            if st.ndim != 1 or st.size < 1 or st.size > 16 or not np.issubdtype(st.dtype, np.integer):
+                raise Exception("\n\nstates must be a list of 1..16 integer state indices.")
+            if st.min() < 0 or st.max() >= self._nsta or np.unique(st).size != st.size:
+                raise Exception("\n\nstates must be distinct indices in [0, nsta).")
+            sel = np.ascontiguousarray(st, dtype=np.int32)
+        na = int(sel.size)
+        if nq * max(nw, 1) * na * na > 2 ** 22:
+            raise Exception("\n\nnq * max(nw, 1) * na^2 must be at most 2**22: split q_list or omega.")
+        v, nvq = None, 0
+        if interaction is None:
+            if return_det:
+                raise Exception("\n\nreturn_det=True needs an interaction.")
+        else:
+            try:
+                v = np.array(interaction, dtype=complex)
+            except (TypeError, ValueError):
+                raise Exception("\n\ninteraction must be a complex (na, na) or (nq, na, na) array.")
+            if v.shape not in ((na, na), (nq, na, na)):
+                raise Exception("\n\ninteraction must have shape (na, na) or (nq, na, na).")
+            if not np.all(np.isfinite(v)):
+                raise Exception("\n\ninteraction must be finite.")
+            v = np.ascontiguousarray(v.reshape(-1, na, na))
+            nvq = v.shape[0]
+        shape = (nq, na, na) if w is None else (nq, nw, na, na)
+        chi0 = np.zeros(shape, dtype=complex)
+        chi = np.zeros(shape, dtype=complex) if v is not None else None
+        det = np.zeros(shape[:-2], dtype=complex) if return_det else None
+        _lib.check(_lib.lib.tbk_susceptibility_matrix_mesh(
+            self._device_model(), _lib.iptr(mesh), nq, _lib.dptr(q), nw, _lib.dptr(w), float(eta), float(fermi_level), float(kT), na,
+            _lib.iptr(sel), None if v is None else _lib.dptr(v.view(float)), nvq, _lib.dptr(chi0.view(float)),
+            None if chi is None else _lib.dptr(chi.view(float)), None if det is None else _lib.dptr(det.view(float))))
+        out = (chi0,) if v is None else ((chi0, chi, det) if return_det else (chi0, chi))
+        if single:
+            out = tuple(x[0] for x in out)
+        return out[0] if v is None else out
 
     # ------------------------------------------------------------------ occupied states: N, E, S, the Fermi level, the density matrix
     def _occ_args(self, what, mesh_size, kT):
