@@ -587,6 +587,33 @@ int tbk_fermi_level_mesh(tbk_model* model, const int32_t* mesh, int nfill, const
                          double* edges_or_null);
 int tbk_density_matrix_mesh(tbk_model* model, const int32_t* mesh, double mu, double kT, int nR, const int32_t* R, double* out);
 
+/* ---- the linear tetrahedron method on k meshes (no reference counterpart) ----
+ * Bloechl, Jepsen, Andersen, PRB 49, 16223.  E_b(k) is the solver's b-th eigenvalue at every point of k_uniform_mesh(mesh), dim_k 1, 2
+ * or 3, N_k < 2^31, periodic.  The cell with origin o is cut along the fixed diagonal o -> o + (1, .., 1) into dim_k! simplices, one per
+ * permutation (a, b, c) of the axes, with corners o, o + e_a, o + e_a + e_b, o + e_a + e_b + e_c (this breaks the lattice's point
+ * symmetry slightly; an axis of one or two points is allowed).  Inside a simplex each band is interpolated linearly, and
+ *   w_i(E): sum_i w_i X_i = int theta(E - e) X over the simplex as a fraction of the zone,   d_i(E) = dw_i / dE
+ * in closed form, the level at E occupied (f = [e <= E]); corners sorted by energy, ties by corner slot.  A band that is flat over a
+ * simplex adds a step to N and nothing to g.  No spin factor.  Fixed-order sums: bit-reproducible, and an energy gives the same bits
+ * alone and inside a longer list.
+ *
+ * tbk_tetrahedron_dos_mesh: energies[nE], 1..65536 finite values in any order.  dos = g(E) = sum d_i and idos = N(E) = sum w_i,
+ *   [nE], or [nsta][nE] per band with per_band != 0 (at most 2^22 doubles each).  sel[nsel], 1..16 distinct state indices, with
+ *   pdos_or_null[nsel][nE] (or [nsel][nsta][nE]) = sum d_i(E) |u_b(k_i)[a]|^2 (at most 2^22 doubles), from a second solve with
+ *   eigenvectors in chunks; nsel = 0, sel = NULL and pdos_or_null = NULL: none.
+ *
+ * tbk_tetrahedron_weights_mesh: out[nsta][N_k], the sum of w_i(mu) over the simplices with mesh point k as corner i, so that
+ *   sum_{b,k} out X_b(k) is the tetrahedron integral of X; derivative != 0: the sum of d_i(mu).  correction != 0 (dim_k = 3, not with
+ *   derivative) adds Bloechl's curvature correction g_T / 40 sum_j (e_j - e_i) per tetrahedron, which leaves the sum over k unchanged.
+ *
+ * tbk_tetrahedron_fermi_level_mesh: one eigen-solve.  n_electrons within 1e-9 of an integer m in [1, nsta - 1] with
+ *   max_k E_{m-1} < min_k E_m gives the middle of that gap; else (0 < n_electrons < nsta) the first double at which the device's own
+ *   N(mu) reaches n_electrons, by rounds of up to 256 trial energies per launch on the ordered key of a double.                          */
+int tbk_tetrahedron_dos_mesh(tbk_model* model, const int32_t* mesh, int nE, const double* energies, int per_band, int nsel,
+                             const int32_t* sel, double* dos, double* idos, double* pdos_or_null);
+int tbk_tetrahedron_weights_mesh(tbk_model* model, const int32_t* mesh, double mu, int correction, int derivative, double* out);
+int tbk_tetrahedron_fermi_level_mesh(tbk_model* model, const int32_t* mesh, double n_electrons, double* mu_out);
+
 /* ---- multi-GPU: one process per GPU, k-points sharded, one gather ------
  * Thin RCCL wrappers (librccl is dlopen'ed on first use).  The 128-byte id is
  * created on rank 0 and distributed by the launcher (any out-of-band channel). */

@@ -1269,6 +1269,124 @@ class tb_model(object):
             out = out.reshape(nR, self._norb, 2, self._norb, 2)
         return out[0] if single else out
 
+    # ------------------------------------------------------------------ the linear tetrahedron method (extensions)
+    def _tetra_mesh_arg(self, what, mesh_size):
+        if self._dim_k not in (1, 2, 3):
+            raise Exception("\n\n%s needs a model with dim_k 1, 2 or 3." % what)
+        mesh, nk = self._mesh_arg(mesh_size)
+        if nk >= 2 ** 31:
+            raise Exception("\n\n%s: the mesh must have fewer than 2**31 points." % what)
+        return mesh, nk
+
+    def tetrahedron_dos_mesh(self, mesh_size, energies, per_band=False, states=None):
+        """Extension: the density of states g(E) and its integral N(E) per cell by the linear tetrahedron method (Bloechl, Jepsen,
+        Andersen, PRB 49, 16223) on `k_uniform_mesh(mesh_size)` (1-, 2- or 3-D, periodic, generated on the device):
+        `(dos, idos)`, each float `(nE,)`, or `(nsta, nE)` with per_band=True (a "band" is the sorted index of `solve_all`).
+
+        Each mesh cell with origin o is cut along the fixed diagonal o -> o + (1, .., 1): in 3-D six tetrahedra, one per
+        permutation (a, b, c) of the axes, with corners o, o + e_a, o + e_a + e_b, o + (1, 1, 1); in 2-D the two triangles
+        (o, o + e_0, o + e_0 + e_1) and (o, o + e_1, o + e_0 + e_1); in 1-D the segment.  Every band is interpolated linearly
+        inside a simplex, and theta(E - e), delta(E - e) are integrated in closed form: a continuous g(E) with its van Hove
+        kinks, and an N(E) that converges like 1 / N^2 with the mesh.  The level at E counts as occupied (f = [e <= E]); a band
+        that is flat over a simplex adds a step to N and nothing to g.  The fixed diagonal breaks the lattice's point symmetry
+        slightly (the shortest diagonal is not chosen).  No spin factor: N above the spectrum is nsta.
+
+        energies: 1-D, 1..65536 finite values in any order (repeats allowed).  Each result holds at most 2**22 values.
+
+        states: None, or 1..16 distinct STATE indices in [0, nsta), read as `susceptibility_matrix_mesh` reads its `states`.
+        With it a third array is returned, the projected DOS g_a(E) = sum d_i(E) |u_b(k_i)[a]|^2 over simplices, bands and
+        corners: `(nsel, nE)`, or `(nsel, nsta, nE)` with per_band=True.  It costs a second solve with eigenvectors, which stay
+        on the device.  Over ALL states it sums to g(E).  Where bands are degenerate at a mesh point the split of g_a between
+        them follows the solver's choice of eigenvectors; their sum does not.
+
+        Fixed-order sums: two calls give the same bits, and an energy gives the same bits alone and inside a longer list."""
+        mesh, nk = self._tetra_mesh_arg("tetrahedron_dos_mesh", mesh_size)
+        try:
+            en = np.array(energies, dtype=float)
+        except (TypeError, ValueError):
+            raise Exception("\n\nenergies must be a 1-D array of 1..65536 finite values.")
+        if en.ndim != 1 or en.size < 1 or en.size > 65536:
+            raise Exception("\n\nenergies must be a 1-D array of 1..65536 finite values.")
+        if not np.all(np.isfinite(en)):
+            raise Exception("\n\nenergies must be finite.")
+        en = np.ascontiguousarray(en)
+        n, nE = self._nsta, int(en.size)
+        nb = n if per_band else 1
+        if nb * nE > 2 ** 22:
+            raise Exception("\n\nnsta * nE must be at most 2**22 with per_band=True: split energies.")
+        sel = None
+        if states is not None:
+            st = np.asarray(states)
+            if st.ndim != 1 or st.size < 1 or st.size > 16 or not np.issubdtype(st.dtype, np.integer):
+                raise Exception("\n\nstates must be a list of 1..16 integer state indices.")
+            if st.min() < 0 or st.max() >= n or np.unique(st).size != st.size:
+                raise Exception("\n\nstates must be distinct indices in [0, nsta).")
+            sel = np.ascontiguousarray(st, dtype=np.int32)
+            if sel.size * nb * nE > 2 ** 22:
+                raise Exception("\n\nThe projected DOS holds at most 2**22 values: split energies or states.")
+        dos = np.zeros((nb, nE), dtype=float)
+        idos = np.zeros((nb, nE), dtype=float)
+        pdos = None if sel is None else np.zeros((sel.size, nb, nE), dtype=float)
+        _lib.check(_lib.lib.tbk_tetrahedron_dos_mesh(self._device_model(), _lib.iptr(mesh), nE, _lib.dptr(en), int(bool(per_band)),
+                                                     0 if sel is None else int(sel.size), _lib.iptr(sel), _lib.dptr(dos),
+                                                     _lib.dptr(idos), _lib.dptr(pdos)))
+        if not per_band:
+            dos, idos = dos[0], idos[0]
+            pdos = None if pdos is None else pdos[:, 0]
+        return (dos, idos) if pdos is None else (dos, idos, pdos)
+
+    def tetrahedron_weights_mesh(self, mesh_size, fermi_level, correction=False, derivative=False):
+        """Extension: the occupation weights of the linear tetrahedron method at `fermi_level`, float `(nsta, N_k)` in the order
+        of `k_uniform_mesh(mesh_size)`: entry (b, k) is the sum of w_i(mu) over every simplex that has mesh point k as its
+        corner i (the simplices and conventions of `tetrahedron_dos_mesh`), so that
+
+            sum_{b,k} w[b, k] X_b(k) = the tetrahedron integral of theta(mu - E_b) X_b over the zone, per cell
+
+        for any X given on the mesh; sum_k w[b] is the band's N(mu).  derivative=True gives the sum of d_i(mu) = dw_i / dmu
+        instead: the weights of a Fermi-surface integral, sum_k of which is the band's g(mu).  correction=True (dim_k = 3 only,
+        not together with derivative) adds Bloechl's curvature correction (1 / 40) g_T(mu) sum_j (e_j - e_i) per tetrahedron,
+        which sums to zero over the corners: N is unchanged.  Eigenvalues only.  Two calls give the same bits."""
+        mesh, nk = self._tetra_mesh_arg("tetrahedron_weights_mesh", mesh_size)
+        try:
+            fermi_level = float(fermi_level)
+        except (TypeError, ValueError):
+            raise Exception("\n\nfermi_level must be one finite number.")
+        if not np.isfinite(fermi_level):
+            raise Exception("\n\nfermi_level must be finite.")
+        if correction and self._dim_k != 3:
+            raise Exception("\n\ncorrection=True needs dim_k = 3: the curvature correction is that of tetrahedra.")
+        if correction and derivative:
+            raise Exception("\n\ncorrection=True applies to the occupation weights, not to derivative=True.")
+        if self._nsta * nk > 2 ** 31:
+            raise Exception("\n\nnsta * N_k must be at most 2**31 weights.")
+        out = np.zeros((self._nsta, nk), dtype=float)
+        _lib.check(_lib.lib.tbk_tetrahedron_weights_mesh(self._device_model(), _lib.iptr(mesh), fermi_level, int(bool(correction)),
+                                                         int(bool(derivative)), _lib.dptr(out)))
+        return out
+
+    def tetrahedron_fermi_level_mesh(self, mesh_size, n_electrons):
+        """Extension: the T = 0 Fermi level that puts `n_electrons` electrons per cell (one real number, no spin factor) into
+        the tetrahedron-method N(E) of `tetrahedron_dos_mesh`, from ONE eigen-solve of the mesh.
+
+        If n_electrons is within 1e-9 of an integer m in [1, nsta - 1] and band m - 1 lies wholly below band m
+        (max_k E_{m-1} < min_k E_m on the mesh), the result is the middle of that gap.  Otherwise 0 < n_electrons < nsta is
+        required, and the result is the first double at which the device's own N(mu) reaches n_electrons, found by rounds of up
+        to 256 trial energies per launch between the lowest and the highest level of the mesh (eight or nine rounds).  Unlike
+        `fermi_level_mesh` at kT = 0 the level of a metal does not jump from mesh level to mesh level.  Where N is flat (touching
+        bands at an integer filling, a Dirac point) mu is only as determined as N is.  Two calls give the same bits."""
+        mesh, nk = self._tetra_mesh_arg("tetrahedron_fermi_level_mesh", mesh_size)
+        try:
+            nel = float(n_electrons)
+        except (TypeError, ValueError):
+            raise Exception("\n\nn_electrons must be one finite number.")
+        if not np.isfinite(nel):
+            raise Exception("\n\nn_electrons must be finite.")
+        if not 0.0 < nel < self._nsta:
+            raise Exception("\n\nn_electrons must lie in the open interval (0, %d)." % self._nsta)
+        mu = np.zeros(1, dtype=float)
+        _lib.check(_lib.lib.tbk_tetrahedron_fermi_level_mesh(self._device_model(), _lib.iptr(mesh), nel, _lib.dptr(mu)))
+        return float(mu[0])
+
     # ------------------------------------------------------------------ shift and injection photocurrents (extensions)
     def _gen_ddham(self, k_input, dir0, dir1):
         """Extension: d^2 H / dk_dir0 dk_dir1 for one k in reduced coordinates, with the shapes of `_gen_ham` (`(norb, 2, norb, 2)`
