@@ -614,6 +614,40 @@ int tbk_tetrahedron_dos_mesh(tbk_model* model, const int32_t* mesh, int nE, cons
 int tbk_tetrahedron_weights_mesh(tbk_model* model, const int32_t* mesh, double mu, int correction, int derivative, double* out);
 int tbk_tetrahedron_fermi_level_mesh(tbk_model* model, const int32_t* mesh, double n_electrons, double* mu_out);
 
+/* ---- the lattice Green's function on k meshes, the T-matrix of a local impurity and the LDOS around it ----
+ * E_n(k), u_n(k) the eigenpairs of the solver on k_uniform_mesh(mesh) (dim_k 1..3, N_k < 2^31 points), z = omega + i eta with eta > 0
+ * (retarded), omega[nomega]: 1..65536 finite frequencies in any order.  In the index layout and phase convention of
+ * tbk_density_matrix_mesh and of the hopping table (amp, i, j, R):
+ *   G_ij(R, w) = (1 / N_k) sum_k sum_n u_n[i] conj(u_n[j]) / (z - E_n(k)) e^{-2 pi i k.(R + tau_j - tau_i)} = <i,0| (z - H)^-1 |j,R>
+ * which is exactly the resolvent of the torus of the mesh (its block from cell c to cell c + R mod mesh is t(R)); the infinite crystal
+ * is approached for eta above the level spacing of the mesh.  Phases from exact integers: an R equal to a mesh period gives the bits of
+ * R = 0.  Fixed-order sums, no floating-point atomics, a partition that depends on (mesh, nsta, dim_k) alone: bit-reproducible, and a
+ * frequency or an R gives the same bits alone and inside a longer list.  The eigenvectors never leave the device.
+ *
+ * tbk_green_function_mesh: out[nomega][nR][na][na] c128.  R[nR][dim_k]: 1..4096 integer vectors, |R_a| < 2^30.  sel[nsel]: 1..32
+ *   distinct state indices, the block G_{sel a, sel b} at a cost of nsta na^2 per point and frequency; nsel = 0 and sel = NULL: all
+ *   states (na = nsta).  nomega nR na^2 <= 2^22 (the message says "split omega or R_list").  nsta <= 32: one kernel with the selected
+ *   components of the eigenvectors of a group of points in LDS; beyond: 16 x 16 tiles, plain VALU.
+ *
+ * tbk_impurity_t_matrix_mesh: a perturbation V on nsite = 1..16 sites (site_state[a], site_R[a][dim_k]), distinct as sites of the torus;
+ *   potential[nsite][nsite] c128, finite and Hermitian.  g_ab = G_{i_a i_b}(R_b - R_a), t_out[nomega][nsite][nsite] = V (1 - g V)^-1
+ *   and det_or_null[nomega] = det(1 - g V), c128, by an LU with partial pivoting per frequency on the device.  A pivot that is exactly
+ *   0 is TBK_EINVAL; the message names the frequency.
+ *
+ * tbk_impurity_ldos_mesh: ldos0[nomega][na] = -(1 / pi) Im G_{s_a s_a}(0), the bulk LDOS of the probe states sel (nsel = 0, sel = NULL:
+ *   all states, nsta <= 32), and dldos[nomega][nR][na] = -(1 / pi) Im sum_{bc} G_{s_a i_b}(R_b - R_r) T_bc G_{i_c s_a}(R_r - R_c), the
+ *   change of the LDOS of state s_a in the probe cell R_r.  The G blocks are computed into device scratch for the union of the probe
+ *   and site states and for the probe-site differences reduced modulo the mesh and de-duplicated (at most 16384 of them), and
+ *   contracted there: nomega nR_int na_int^2 <= 2^23 and nomega nR na <= 2^24 (TBK_EINVAL beyond; split omega or R).              */
+int tbk_green_function_mesh(tbk_model* model, const int32_t* mesh, int nomega, const double* omega, double eta, int nR, const int32_t* R,
+                            int nsel, const int32_t* sel, double* out);
+int tbk_impurity_t_matrix_mesh(tbk_model* model, const int32_t* mesh, int nomega, const double* omega, double eta, int nsite,
+                               const int32_t* site_state, const int32_t* site_R, const double* potential, double* t_out,
+                               double* det_or_null);
+int tbk_impurity_ldos_mesh(tbk_model* model, const int32_t* mesh, int nomega, const double* omega, double eta, int nsite,
+                           const int32_t* site_state, const int32_t* site_R, const double* potential, int nR, const int32_t* R, int nsel,
+                           const int32_t* sel, double* ldos0, double* dldos);
+
 /* ---- multi-GPU: one process per GPU, k-points sharded, one gather ------
  * Thin RCCL wrappers (librccl is dlopen'ed on first use).  The 128-byte id is
  * created on rank 0 and distributed by the launcher (any out-of-band channel). */

@@ -25,6 +25,7 @@
 #include <math.h>
 #include "tbk_chim.h"
 #include "tbk_chi_dev.h"
+#include "tbk_small_solve.h"
 
 // ---------------------------------------------------------------- static, 1 .. 32 states
 // Workgroup g takes the points [g nk / G, (g + 1) nk / G) of the chunk in batches of P.  Per point the LDS holds u1[s][a] =
@@ -252,14 +253,14 @@ __global__ __launch_bounds__(256) void k_chim_finish(const double* __restrict__ 
     chi0[i] = cd{a[0] / nk, a[nwz] / nk};
 }
 
-// RPA, one matrix per workgroup of ONE wavefront: M = [1 - chi0 V | chi0] (na rows of 2 na) in LDS, Gaussian elimination with
-// partial pivoting (pivot: the largest |.|^2 of the column, the lowest row winning ties), back substitution, det = the signed product
-// of the pivots.  A pivot of squared modulus exactly 0: det = 0 and the matrix of chi is NaN.  V is V[0] or V[q].
+// RPA, one matrix per workgroup of ONE wavefront: M = [1 - chi0 V | chi0] (na rows of 2 na) in LDS through tbk_small_solve.h's
+// small_solve (Gaussian elimination with partial pivoting, back substitution, det = the signed product of the pivots).  A pivot of
+// squared modulus exactly 0: det = 0 and the matrix of chi is NaN.  V is V[0] or V[q].
 __global__ __launch_bounds__(64) void k_chim_rpa(const cd* __restrict__ chi0, const cd* __restrict__ V, const int vq, const int nwz,
                                                  const int na, cd* __restrict__ chi, cd* __restrict__ det) {
     __shared__ cd M[kChimSelMax][2 * kChimSelMax + 1];
     __shared__ cd C0[kChimSelMax * kChimSelMax], Vs[kChimSelMax * kChimSelMax];
-    const int t = threadIdx.x, nab = na * na, w2 = 2 * na;
+    const int t = threadIdx.x, nab = na * na;
     const int64_t im = blockIdx.x;
     const cd* c0 = chi0 + im * nab;
     const cd* v = V + (vq ? im / nwz : 0) * nab;
@@ -280,57 +281,13 @@ __global__ __launch_bounds__(64) void k_chim_rpa(const cd* __restrict__ chi0, co
         M[a][na + b] = C0[e];
     }
     __syncthreads();
-    cd d{1.0, 0.0};
-    bool singular = false;
-    for (int k = 0; k < na; ++k) {
-        int piv = k;                                               // (every lane finds the same pivot from the same values)
-        double best = cabs2(M[k][k]);
-        for (int r = k + 1; r < na; ++r) {
-            const double m2 = cabs2(M[r][k]);
-            if (m2 > best) best = m2, piv = r;
-        }
-        if (best == 0.0) {
-            singular = true;
-            break;
-        }
-        __syncthreads();
-        if (piv != k) {
-            for (int c = t; c < w2; c += 64) {
-                const cd x = M[k][c];
-                M[k][c] = M[piv][c];
-                M[piv][c] = x;
-            }
-            d = cd{-d.x, -d.y};
-            __syncthreads();
-        }
-        const cd pv = M[k][k];
-        d = cmul(d, pv);
-        const cd inv{pv.x / best, -pv.y / best};
-        // rows below k, columns right of k: lane (r, c); column k itself (the factors) and row k are only read
-        const int nr = na - 1 - k, nc = w2 - 1 - k;
-        for (int e = t; e < nr * nc; e += 64) {
-            const int r = k + 1 + e / nc, c = k + 1 + e % nc;
-            M[r][c] = csub(M[r][c], cmul(cmul(M[r][k], inv), M[k][c]));
-        }
-        __syncthreads();
-    }
-    if (singular) {                                                // (uniform over the workgroup)
+    cd d;
+    if (!small_solve<kChimSelMax>(M, na, t, d)) {                  // (uniform over the workgroup)
         const double nan = __builtin_nan("");
         for (int e = t; e < nab; e += 64) chi[im * nab + e] = cd{nan, nan};
         if (t == 0) det[im] = cd{0.0, 0.0};
         return;
     }
-    // back substitution, one lane per column of the right-hand side
-    if (t < na) {
-        for (int r = na - 1; r >= 0; --r) {
-            cd s = M[r][na + t];
-            for (int c = r + 1; c < na; ++c) s = csub(s, cmul(M[r][c], M[c][na + t]));
-            const cd pv = M[r][r];
-            const double m2 = cabs2(pv);
-            M[r][na + t] = cmul(s, cd{pv.x / m2, -pv.y / m2});
-        }
-    }
-    __syncthreads();
     for (int e = t; e < nab; e += 64) chi[im * nab + e] = M[e / na][na + e % na];
     if (t == 0) det[im] = d;
 }
@@ -339,7 +296,8 @@ __global__ __launch_bounds__(64) void k_chim_rpa(const cd* __restrict__ chi0, co
 static int chim_group_sum(tbk_ctx* ctx, const ChimPlan& pl, const double* part, int accumulate, double* acc) {
     ProfScope ps(ctx, "chim_rows");
     if (pl.lane_rows)
-        hipLaunchKernelGGL(k_group_rows_lanes, dim3(nblk(pl.nrows)), dim3(256), 0, ctx->stream, part, pl.G, pl.nrows, accumulate, acc);
+        hipLaunchKernelGGL(k_group_rows_lanes, dim3(nblk(pl.nrows)), dim3(256), 0, ctx->stream, part, pl.G, pl.nrows, pl.nrows, pl.nrows,
+                           accumulate, acc);
     else
         hipLaunchKernelGGL(k_group_rows, dim3((unsigned)pl.nrows), dim3(256), 0, ctx->stream, part, pl.G, pl.nrows, 1.0, accumulate, acc);
     TBK_HIP(hipGetLastError());

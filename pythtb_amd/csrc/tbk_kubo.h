@@ -144,7 +144,9 @@ static __global__ __launch_bounds__(256) void k_kubo_rows(const double* __restri
 // The same sum over the other layout, part[g][row] (the frequency sweeps of tbk_pairs.h, tbk_chi.hip, tbk_occ.hip):
 // acc[row] (+)= inv sum_g part[g][row], the groups in index order.  k_group_rows is one workgroup per row, for many groups and few
 // rows (G up to 1024, rows = sums x frequencies); k_group_rows_lanes is one LANE per row, for the density matrix's up to 2^23 rows of
-// at most 512 groups, where a workgroup per row would be nearly idle.
+// at most 512 groups, where a workgroup per row would be nearly idle.  Its rows may be scattered: row r of part goes to
+// acc[(r / run) stride + r % run] -- runs of `run` rows that lie `stride` apart in acc (the Green's function's launch tiles of a few
+// frequencies times a part of the lattice vectors); run = nrows is the contiguous case, with no division.
 static __global__ __launch_bounds__(256) void k_group_rows(const double* __restrict__ part, const int G, const int64_t nrows, const double inv,
                                                            const int accumulate, double* __restrict__ acc) {
     __shared__ double red[4];
@@ -154,12 +156,15 @@ static __global__ __launch_bounds__(256) void k_group_rows(const double* __restr
     if (threadIdx.x == 0) acc[blockIdx.x] = accumulate ? acc[blockIdx.x] + t * inv : t * inv;
 }
 static __global__ __launch_bounds__(256) void k_group_rows_lanes(const double* __restrict__ part, const int G, const int64_t nrows,
-                                                                 const int accumulate, double* __restrict__ acc) {
+                                                                 const int64_t run, const int64_t stride, const int accumulate,
+                                                                 double* __restrict__ acc) {
     const int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (row >= nrows) return;
     double s = 0.0;
     for (int g = 0; g < G; ++g) s += part[(int64_t)g * nrows + row];
-    acc[row] = accumulate ? acc[row] + s : s;
+    const int64_t blk = run == nrows ? 0 : row / run;              // (uniform over the launch)
+    double* a = acc + blk * stride + (row - blk * run);
+    *a = accumulate ? *a + s : s;
 }
 
 static int kubo_rows_launch(tbk_ctx* ctx, const double* part, int gx, int64_t nrows, double* rows) {

@@ -29,6 +29,7 @@
 // atomics and no partition depends on the number of levels, fillings or lattice vectors: two calls give the same bits.
 #include <math.h>
 #include "tbk_occ.h"
+#include "tbk_mesh_phase.h"
 
 // ---------------------------------------------------------------- occupation
 // f and, where wanted, the entropy term s = -f ln f - (1 - f) ln(1 - f) of x = (E - mu) / kT (tbk_kubo.h's fermi_terms)
@@ -164,31 +165,6 @@ __global__ __launch_bounds__(64) void k_occ_edges(const double* __restrict__ par
 }
 
 // ---------------------------------------------------------------- density matrix
-struct OccMesh {
-    int N[3];   // the mesh, 1 beyond dim_k
-    int dk;
-};
-// e^{-2 pi i k.R} at point idx of the mesh: per axis the exact integer m = i_a R_a mod N_a, then sincospi(-2 m / N_a)
-__device__ __forceinline__ cd dm_phase(const OccMesh& M, const int64_t idx, const int32_t* __restrict__ R) {
-    int ii[3];
-    mesh_point(M.N, idx, ii);
-    cd ph{1.0, 0.0};
-    for (int d = 0; d < M.dk; ++d) {
-        int64_t mm = ((int64_t)ii[d] * (int64_t)R[d]) % M.N[d];
-        if (mm < 0) mm += M.N[d];
-        if (mm == 0) continue;
-        double sn, cs;
-        sincospi(-2.0 * ((double)mm / (double)M.N[d]), &sn, &cs);
-        ph = cmul_x(ph, cd{cs, sn});
-    }
-    return ph;
-}
-__device__ __forceinline__ cd dm_orb_phase(const ModelView& mv, const double* __restrict__ k, const int64_t ik, const int o) {
-    double kk[4] = {0.0, 0.0, 0.0, 0.0};
-    for (int d = 0; d < mv.dim_k; ++d) kk[d] = k[ik * mv.dim_k + d];
-    return expi2pi(kdot(kk, mv.orb[o]));
-}
-
 // f[b][ik] of a chunk
 __global__ __launch_bounds__(256) void k_dm_weights(const double* __restrict__ ev, const int64_t total, const double mu, const double kT,
                                                     double* __restrict__ fw) {
@@ -538,8 +514,8 @@ extern "C" int tbk_density_matrix_mesh(tbk_model* m, const int32_t* mesh, double
             }
             ProfScope ps(ctx, "dm_rows");
             const int64_t nrows = (int64_t)nr * nn * 2;
-            hipLaunchKernelGGL(k_group_rows_lanes, dim3(nblk(nrows)), dim3(256), 0, ctx->stream, (const double*)part, pl.G, nrows, first > 0 ? 1 : 0,
-                               (double*)(acc + (int64_t)r0 * nn));
+            hipLaunchKernelGGL(k_group_rows_lanes, dim3(nblk(nrows)), dim3(256), 0, ctx->stream, (const double*)part, pl.G, nrows, nrows, nrows,
+                               first > 0 ? 1 : 0, (double*)(acc + (int64_t)r0 * nn));
             TBK_HIP(hipGetLastError());
         }
         return TBK_OK;

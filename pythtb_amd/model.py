@@ -1219,6 +1219,24 @@ class tb_model(object):
             return res, (edges[0] if scalar else edges)
         return res
 
+    def _R_list_arg(self, R_list):
+        """(R, single) of the real-space calls: the checked lattice vectors as a contiguous int32 `(nR, dim_k)` array, 1 <= nR <=
+        4096 and |R_a| < 2**30 (None: R = 0); single: it was None or one `(dim_k,)` vector."""
+        dk = self._dim_k
+        Rf = np.zeros(dk) if R_list is None else np.array(R_list)
+        if Rf.dtype == object or not (np.issubdtype(Rf.dtype, np.integer) or np.issubdtype(Rf.dtype, np.floating)):
+            raise Exception("\n\nR_list must hold integers.")
+        single = Rf.ndim == 1
+        if single:
+            Rf = Rf.reshape(1, -1)
+        if Rf.ndim != 2 or Rf.shape[1] != dk or Rf.shape[0] < 1 or Rf.shape[0] > 4096:
+            raise Exception("\n\nR_list must have shape (nR, dim_k) with 1..4096 lattice vectors, or (dim_k,).")
+        if not np.all(np.isfinite(Rf)) or np.any(Rf != np.round(Rf)):
+            raise Exception("\n\nR_list must hold integers.")
+        if np.any(np.abs(Rf) >= 2 ** 30):
+            raise Exception("\n\nR_list: every component must be below 2**30 in magnitude.")
+        return np.ascontiguousarray(Rf, dtype=np.int32), single
+
     def density_matrix_mesh(self, mesh_size, fermi_level, kT=0.0, R_list=None):
         """Extension: the one-particle density matrix in real space, as a mean over `k_uniform_mesh(mesh_size)` (1-, 2- or 3-D,
         generated on the device): complex `(nR, nsta, nsta)`,
@@ -1245,29 +1263,208 @@ class tb_model(object):
             raise Exception("\n\nfermi_level must be one finite number.")
         if not np.isfinite(fermi_level):
             raise Exception("\n\nfermi_level must be finite.")
-        dk, n = self._dim_k, self._nsta
-        Rf = np.zeros(dk) if R_list is None else np.array(R_list)
-        if Rf.dtype == object or not (np.issubdtype(Rf.dtype, np.integer) or np.issubdtype(Rf.dtype, np.floating)):
-            raise Exception("\n\nR_list must hold integers.")
-        single = Rf.ndim == 1
-        if single:
-            Rf = Rf.reshape(1, -1)
-        if Rf.ndim != 2 or Rf.shape[1] != dk or Rf.shape[0] < 1 or Rf.shape[0] > 4096:
-            raise Exception("\n\nR_list must have shape (nR, dim_k) with 1..4096 lattice vectors, or (dim_k,).")
-        if not np.all(np.isfinite(Rf)) or np.any(Rf != np.round(Rf)):
-            raise Exception("\n\nR_list must hold integers.")
-        if np.any(np.abs(Rf) >= 2 ** 30):
-            raise Exception("\n\nR_list: every component must be below 2**30 in magnitude.")
-        nR = Rf.shape[0]
+        n = self._nsta
+        R, single = self._R_list_arg(R_list)
+        nR = R.shape[0]
         if nR * n * n > 2 ** 22:
             raise Exception("\n\nnR * nsta**2 must be at most 2**22: split R_list.")
-        R = np.ascontiguousarray(Rf, dtype=np.int32)
         out = np.zeros((nR, n, n), dtype=complex)
         _lib.check(_lib.lib.tbk_density_matrix_mesh(self._device_model(), _lib.iptr(mesh), fermi_level, kT, nR, _lib.iptr(R),
                                                     _lib.dptr(out.view(float))))
         if self._nspin == 2:
             out = out.reshape(nR, self._norb, 2, self._norb, 2)
         return out[0] if single else out
+
+    # ------------------------------------------------------------------ the lattice Green's function and local impurities (extensions)
+    def _gf_args(self, what, mesh_size, omega, eta):
+        """(mesh, N_k, omega, scalar, eta) of the Green's-function calls: dim_k 1, 2 or 3, the mesh of `_mesh_arg`, omega a scalar
+        or 1-D with 1..65536 finite values, eta one finite number > 0."""
+        if self._dim_k not in (1, 2, 3):
+            raise Exception("\n\n%s needs a model with dim_k 1, 2 or 3." % what)
+        mesh, nk = self._mesh_arg(mesh_size)
+        if nk >= 2 ** 31:
+            raise Exception("\n\n%s: the mesh must have fewer than 2**31 points." % what)
+        try:
+            w = np.array(omega, dtype=float)
+        except (TypeError, ValueError):
+            raise Exception("\n\nomega must be a scalar or a 1-D array of 1..65536 finite frequencies.")
+        scalar = w.ndim == 0
+        if scalar:
+            w = w.reshape(1)
+        if w.ndim != 1 or w.size < 1 or w.size > 65536:
+            raise Exception("\n\nomega must be a scalar or a 1-D array of 1..65536 finite frequencies.")
+        if not np.all(np.isfinite(w)):
+            raise Exception("\n\nomega must be finite.")
+        try:
+            eta = float(eta)
+        except (TypeError, ValueError):
+            raise Exception("\n\neta must be one finite number > 0.")
+        if not np.isfinite(eta) or not eta > 0.0:
+            raise Exception("\n\neta must be finite and > 0 (the retarded function).")
+        return mesh, nk, np.ascontiguousarray(w), scalar, eta
+
+    def _gf_states_arg(self, states):
+        """The selection of the Green's-function calls as int32 state indices, or None for all states: 1..32 distinct integers in
+        [-nsta, nsta), negative ones counted from the end."""
+        if states is None:
+            return None
+        st = np.asarray(states)
+        if st.ndim != 1 or st.size < 1 or st.size > 32 or not np.issubdtype(st.dtype, np.integer):
+            raise Exception("\n\nstates must be None or a list of 1..32 integer state indices.")
+        if st.min() < -self._nsta or st.max() >= self._nsta:
+            raise Exception("\n\nstates must be indices in [-nsta, nsta).")
+        st = np.where(st < 0, st + self._nsta, st)
+        if np.unique(st).size != st.size:
+            raise Exception("\n\nstates must be distinct.")
+        return np.ascontiguousarray(st, dtype=np.int32)
+
+    def _gf_impurity_args(self, mesh, sites, potential):
+        """(site states int32 (ns,), site lattice vectors int32 (ns, dim_k), V complex (ns, ns)) of the impurity calls."""
+        dk, n = self._dim_k, self._nsta
+        try:
+            pairs = [(s, np.array(R)) for s, R in sites]
+        except (TypeError, ValueError):
+            raise Exception("\n\nsites must be a list of 1..16 pairs (state index, R).")
+        if len(pairs) < 1 or len(pairs) > 16:
+            raise Exception("\n\nsites must be a list of 1..16 pairs (state index, R).")
+        st = np.zeros(len(pairs), dtype=np.int32)
+        Rs = np.zeros((len(pairs), dk), dtype=np.int32)
+        for a, (s, R) in enumerate(pairs):
+            if not _is_int(s) or s < -n or s >= n:
+                raise Exception("\n\nsites: the state index of site %d must be an integer in [-nsta, nsta)." % a)
+            if R.shape != (dk,) or R.dtype == object or not (np.issubdtype(R.dtype, np.integer) or np.issubdtype(R.dtype, np.floating)) \
+                    or not np.all(np.isfinite(R)) or np.any(R != np.round(R)) or np.any(np.abs(R) >= 2 ** 30):
+                raise Exception("\n\nsites: R of site %d must hold dim_k integers below 2**30 in magnitude." % a)
+            st[a] = s + n if s < 0 else s
+            Rs[a] = R
+        key = [(int(st[a]),) + tuple(int(x) for x in np.mod(Rs[a], mesh)) for a in range(len(pairs))]
+        if len(set(key)) != len(key):
+            raise Exception("\n\nsites: two sites coincide modulo the mesh (they are one site of its torus).")
+        ns = len(pairs)
+        try:
+            v = np.array(potential, dtype=complex)
+        except (TypeError, ValueError):
+            raise Exception("\n\npotential must be a Hermitian (ns, ns) matrix or ns real on-site shifts.")
+        if v.shape == (ns,):
+            if np.any(v.imag != 0.0):
+                raise Exception("\n\npotential: the on-site shifts must be real.")
+            v = np.diag(v)
+        if v.shape != (ns, ns):
+            raise Exception("\n\npotential must be a Hermitian (ns, ns) matrix or ns real on-site shifts.")
+        if not np.all(np.isfinite(v)):
+            raise Exception("\n\npotential must be finite.")
+        if np.max(np.abs(v - v.conj().T)) > 1e-12 * max(np.max(np.abs(v)), 0.0):
+            raise Exception("\n\npotential must be Hermitian.")
+        return st, np.ascontiguousarray(Rs), np.ascontiguousarray(v)
+
+    def green_function_mesh(self, mesh_size, omega, eta, R_list=None, states=None):
+        """Extension: the retarded real-space Green's function of the bulk crystal, resolved in energy, as a mean over
+        `k_uniform_mesh(mesh_size)` (1-, 2- or 3-D, generated on the device): complex `(nw, nR, nsta, nsta)`,
+
+            G_ij(R, w) = (1 / N_k) sum_k sum_n u_n,i(k) conj(u_n,j(k)) / (w + i eta - E_n(k)) e^{-2 pi i k.(R + tau_j - tau_i)}
+                       = <i,0| (w + i eta - H)^-1 |j,R>
+
+        with the eigenpairs of `solve_all`.  Index layout and phase convention are exactly those of `density_matrix_mesh` and of
+        `set_hop(amp, i, j, R)`; `density_matrix_mesh` is the w-integrated special case (its weight f(E_n) is 1 / (z - E_n) here).
+
+        G is EXACTLY the Green's function of the torus of the mesh: with H_T the Hamiltonian whose block from cell c to cell
+        c + R (mod mesh_size) is the hopping table t(R), `inv(z - H_T)[(0, i), (R, j)]` equals the formula above.  The
+        infinite-crystal limit needs eta above the level spacing of the mesh; below it G shows the discrete levels of the torus.
+        Degenerate levels need no care: G is a function of H.  conj(G_ij(R, w + i eta)) = G_ji(-R, w - i eta).
+
+        omega: a scalar (the w axis is dropped), or 1-D with 1..65536 finite values in any order, repeats allowed.  eta: one
+        finite number > 0.  R_list: as `density_matrix_mesh` -- `(nR, dim_k)` integers with |R_a| < 2**30, 1 <= nR <= 4096;
+        `(dim_k,)` alone drops the axis; None is R = 0.  states: None for all states, or 1..32 distinct state indices (negative
+        ones count from the end): the result is then the `(na, na)` block G_{s_a s_b} at a cost of nsta na^2 per point and
+        frequency instead of nsta^3 -- one site of a 512-state supercell is affordable.  Spinful models with states=None return
+        `(..., norb, 2, norb, 2)`.  nw * nR * na^2 <= 2**22.
+
+        The phase e^{-2 pi i k.R} is formed from exact integers: an R equal to a period of the mesh gives the bits of R = 0.  The
+        partition of the work depends on (mesh, nsta, dim_k) alone and every sum has a fixed order: two calls give the same
+        bits, and a frequency, an R or a selection gives the same bits alone and inside a longer omega or R_list.  The
+        eigenvectors never leave the device."""
+        mesh, nk, w, scalar, eta = self._gf_args("green_function_mesh", mesh_size, omega, eta)
+        R, single = self._R_list_arg(R_list)
+        sel = self._gf_states_arg(states)
+        n = self._nsta
+        na = n if sel is None else int(sel.size)
+        nw, nR = int(w.size), R.shape[0]
+        if nw * nR * na * na > 2 ** 22:
+            raise Exception("\n\nnw * nR * na^2 must be at most 2**22: split omega or R_list.")
+        out = np.zeros((nw, nR, na, na), dtype=complex)
+        _lib.check(_lib.lib.tbk_green_function_mesh(self._device_model(), _lib.iptr(mesh), nw, _lib.dptr(w), eta, nR, _lib.iptr(R),
+                                                    0 if sel is None else na, _lib.iptr(sel), _lib.dptr(out.view(float))))
+        if sel is None and self._nspin == 2:
+            out = out.reshape(nw, nR, self._norb, 2, self._norb, 2)
+        if single:
+            out = out[:, 0]
+        return out[0] if scalar else out
+
+    def impurity_t_matrix_mesh(self, mesh_size, omega, eta, sites, potential, return_det=False):
+        """Extension: the exact T-matrix of a local impurity in the bulk crystal (no supercell).  sites: a list of 1..16 pairs
+        `(state index, R)`, R holding dim_k integers; two sites that coincide modulo the mesh raise (they are one site of the
+        torus).  potential: a finite Hermitian complex `(ns, ns)` matrix V between the sites, or a 1-D real array of ns on-site
+        shifts.  With G of `green_function_mesh` on the same mesh,
+
+            g_ab(w) = G_{i_a i_b}(R_b - R_a, w)        T(w) = V (1 - g(w) V)^-1
+
+        Returns T, complex `(nw, ns, ns)` (`(ns, ns)` for a scalar omega); with return_det=True `(T, det)`, det = det(1 - g V),
+        complex `(nw,)`: its zeros in a gap are the bound states of the impurity.  The full Green's function with the impurity is
+        G + G T G.  The solve is an LU with partial pivoting per frequency on the device.  A singular 1 - g V (a pivot that is
+        exactly 0) raises an error that names the frequency; it is never a NaN result.  Bit-reproducible as `green_function_mesh`."""
+        mesh, nk, w, scalar, eta = self._gf_args("impurity_t_matrix_mesh", mesh_size, omega, eta)
+        st, Rs, v = self._gf_impurity_args(mesh, sites, potential)
+        nw, ns = int(w.size), int(st.size)
+        t = np.zeros((nw, ns, ns), dtype=complex)
+        det = np.zeros(nw, dtype=complex) if return_det else None
+        _lib.check(_lib.lib.tbk_impurity_t_matrix_mesh(self._device_model(), _lib.iptr(mesh), nw, _lib.dptr(w), eta, ns, _lib.iptr(st),
+                                                       _lib.iptr(Rs), _lib.dptr(v.view(float)), _lib.dptr(t.view(float)),
+                                                       None if det is None else _lib.dptr(det.view(float))))
+        if scalar:
+            return (t[0], det[0]) if return_det else t[0]
+        return (t, det) if return_det else t
+
+    def impurity_ldos_mesh(self, mesh_size, omega, eta, sites, potential, R_list=None, states=None):
+        """Extension: the local density of states around the impurity of `impurity_t_matrix_mesh`: `(ldos0, dldos)`,
+
+            ldos0[w, a]    = -(1 / pi) Im G_{s_a s_a}(0, w)                                         float (nw, na)
+            dldos[w, r, a] = -(1 / pi) Im sum_{bc} G_{s_a i_b}(R_b - R_r) T_bc G_{i_c s_a}(R_r - R_c)    float (nw, nR, na)
+
+        ldos0 is the bulk LDOS of state s_a (the same in every cell, Lorentzian-broadened by eta), dldos the change in the cell
+        R_r of R_list: the Friedel ripple, and over a grid of R a quasi-particle interference map.  R_list and states (the probe
+        states s_a; None: all states, which needs nsta <= 32) as `green_function_mesh`; a scalar omega, a single R or R_list=None
+        drop their axes.  The G blocks are computed into device scratch and contracted there; only the two real results come
+        back.  Internally the lattice vectors are the differences between probe cells and sites, reduced modulo the mesh (it
+        cannot tell them apart) and de-duplicated, nR_int of them, and the selection is the union of the probe and site states,
+        na_int of them.  Caps: nR_int <= 16384, nw * nR_int * na_int^2 <= 2**23 and nw * nR * na <= 2**24 -- a 64 x 64 map of R
+        around one site of a 2-state model at 16 frequencies fits in one call; beyond them the call raises (split omega or
+        R_list).  A singular 1 - g V raises as in `impurity_t_matrix_mesh`."""
+        mesh, nk, w, scalar, eta = self._gf_args("impurity_ldos_mesh", mesh_size, omega, eta)
+        st, Rs, v = self._gf_impurity_args(mesh, sites, potential)
+        R, single = self._R_list_arg(R_list)
+        sel = self._gf_states_arg(states)
+        n = self._nsta
+        if sel is None and n > 32:
+            raise Exception("\n\nstates=None means all states, which needs nsta <= 32: give states (1..32 state indices).")
+        na = n if sel is None else int(sel.size)
+        nw, nR, ns = int(w.size), R.shape[0], int(st.size)
+        # the internal problem, as the library forms it: differences reduced modulo the mesh, kept once
+        d = (Rs[None, :, :].astype(np.int64) - R[:, None, :].astype(np.int64)).reshape(-1, self._dim_k)
+        pd = (Rs[None, :, :].astype(np.int64) - Rs[:, None, :].astype(np.int64)).reshape(-1, self._dim_k)
+        nint = np.unique(np.mod(np.concatenate([np.zeros((1, self._dim_k), dtype=np.int64), d, -d, pd]), mesh), axis=0).shape[0]
+        naint = np.union1d(st, np.arange(n) if sel is None else sel).size
+        if nint > 16384 or nw * nint * naint * naint > 2 ** 23 or nw * nR * na > 2 ** 24:
+            raise Exception("\n\nimpurity_ldos_mesh: %d internal lattice vectors and %d internal states at %d frequencies are beyond "
+                            "the caps (nR_int <= 16384, nw * nR_int * na_int^2 <= 2**23, nw * nR * na <= 2**24): split omega or R_list."
+                            % (nint, naint, nw))
+        ldos0 = np.zeros((nw, na), dtype=float)
+        dldos = np.zeros((nw, nR, na), dtype=float)
+        _lib.check(_lib.lib.tbk_impurity_ldos_mesh(self._device_model(), _lib.iptr(mesh), nw, _lib.dptr(w), eta, ns, _lib.iptr(st),
+                                                   _lib.iptr(Rs), _lib.dptr(v.view(float)), nR, _lib.iptr(R), 0 if sel is None else na,
+                                                   _lib.iptr(sel), _lib.dptr(ldos0), _lib.dptr(dldos)))
+        if single:
+            dldos = dldos[:, 0]
+        return (ldos0[0], dldos[0]) if scalar else (ldos0, dldos)
 
     # ------------------------------------------------------------------ the linear tetrahedron method (extensions)
     def _tetra_mesh_arg(self, what, mesh_size):
