@@ -648,6 +648,27 @@ int tbk_impurity_ldos_mesh(tbk_model* model, const int32_t* mesh, int nomega, co
                            const int32_t* site_state, const int32_t* site_R, const double* potential, int nR, const int32_t* R, int nsel,
                            const int32_t* sel, double* ldos0, double* dldos);
 
+/* ---- band unfolding: a supercell's eigenstates on the Bloch sums of the primitive cell ----
+ * Called on the SUPERCELL model (nsta <= 2048, dim_k 1..3).  k_sc[nk][dim_k] is K = S k, the supercell's reduced k of the same Cartesian
+ * vector as the primitive k, solved as given (not reduced modulo 1).  group[nsta]: the group (primitive orbital x spin) state j is an
+ * image of, 0..ng-1, or -1 for none (never read into a sum); ng <= 64.  phase_k[nk][dim_k] (the primitive k) and delta[norb][dim_k]
+ * (the displacement of every supercell orbital from the nearest lattice image of its ideal site, primitive reduced coordinates) go
+ * together: both NULL means delta = 0 and no phase is formed.  inv_nc = 1 / N_c, N_c = |det S|.  With (E_b, u_b) the solver's eigenpairs:
+ *   W[b][g](k) = inv_nc | sum_{j in g} e^{2 pi i k.delta_j} u_b[j] |^2        (members in ascending state order, a fixed partition)
+ *   A[g](k, w) = sum_b W[b][g](k) (eta / pi) / ((w - E_b)^2 + eta^2)           (bands in index order)
+ * per_state != 0: per group (ngo = ng); else the sums over g (ngo = 1).
+ *
+ * tbk_unfold_bands_list: eval_out[nsta][nk] (as tbk_solve_list) and w_out[nsta][nk][ngo]; nsta nk ngo <= 2^24.
+ * tbk_unfold_spectral_list: out[nk][nomega][ngo] for omega[nomega], 1..65536 finite frequencies in any order, eta > 0;
+ *   nk nomega ngo <= 2^24 (the message says "split k_list or omega").
+ * The tiling is a function of (nsta, ng, nomega, nk) alone (pythtb_amd/csrc/tbk_unfold.h); no floating-point atomics: two calls give
+ * the same bits, a frequency the same bits alone and inside a longer list, and a k-point too wherever the solver takes the same route
+ * for both list lengths (the kernels here add no dependence on position or neighbours).  The eigenvectors never leave the device.     */
+int tbk_unfold_bands_list(tbk_model* model, const double* k_sc, int64_t nk, int ng, const int32_t* group, const double* phase_k,
+                          const double* delta, double inv_nc, int per_state, double* eval_out, double* w_out);
+int tbk_unfold_spectral_list(tbk_model* model, const double* k_sc, int64_t nk, int ng, const int32_t* group, const double* phase_k,
+                             const double* delta, double inv_nc, int nomega, const double* omega, double eta, int per_state, double* out);
+
 /* ---- multi-GPU: one process per GPU, k-points sharded, one gather ------
  * Thin RCCL wrappers (librccl is dlopen'ed on first use).  The 128-byte id is
  * created on rank 0 and distributed by the launcher (any out-of-band channel). */

@@ -1284,6 +1284,13 @@ class tb_model(object):
         mesh, nk = self._mesh_arg(mesh_size)
         if nk >= 2 ** 31:
             raise Exception("\n\n%s: the mesh must have fewer than 2**31 points." % what)
+        w, scalar, eta = self._omega_eta_arg(omega, eta)
+        return mesh, nk, w, scalar, eta
+
+    @staticmethod
+    def _omega_eta_arg(omega, eta):
+        """(omega as a contiguous 1-D float array, whether it was a scalar, eta): omega a scalar or 1-D with 1..65536 finite values,
+        eta one finite number > 0."""
         try:
             w = np.array(omega, dtype=float)
         except (TypeError, ValueError):
@@ -1301,7 +1308,7 @@ class tb_model(object):
             raise Exception("\n\neta must be one finite number > 0.")
         if not np.isfinite(eta) or not eta > 0.0:
             raise Exception("\n\neta must be finite and > 0 (the retarded function).")
-        return mesh, nk, np.ascontiguousarray(w), scalar, eta
+        return np.ascontiguousarray(w), scalar, eta
 
     def _gf_states_arg(self, states):
         """The selection of the Green's-function calls as int32 state indices, or None for all states: 1..32 distinct integers in
@@ -1465,6 +1472,184 @@ class tb_model(object):
         if single:
             dldos = dldos[:, 0]
         return (ldos0[0], dldos[0]) if scalar else (ldos0, dldos)
+
+    # ------------------------------------------------------------------ band unfolding (extensions)
+    def _unfold_args(self, what, k_list, sc_red_lat, prim_index, prim_orb, dense=True):
+        """The checked arguments of the unfolding calls, made on the supercell model: (k (nk, dim_k) primitive reduced, K = S_per k
+        the supercell's, group int32 (nsta,) with -1 for states that project on nothing, ng, the count of states per group (ng,),
+        delta (norb, dim_k) or None, N_c)."""
+        if self._dim_k not in (1, 2, 3):
+            raise Exception("\n\n%s needs a model with dim_k 1, 2 or 3." % what)
+        if dense and self._nsta > _lib.MAX_NSTA:
+            raise Exception("\n\n%s: the supercell has %d states, beyond the dense solver's %d: use kpm_unfolded_spectral."
+                            % (what, self._nsta, _lib.MAX_NSTA))
+        try:
+            k = np.array(k_list, dtype=float)
+        except (TypeError, ValueError):
+            raise Exception("\n\nk_list must be (nk, dim_k) k-points in the reduced coordinates of the primitive cell.")
+        if self._dim_k == 1 and k.ndim == 1:
+            k = k.reshape(-1, 1)
+        if k.ndim != 2 or k.shape[1] != self._dim_k or k.shape[0] < 1:
+            raise Exception("\n\nk_list must be (nk, dim_k) k-points in the reduced coordinates of the primitive cell.")
+        if not np.all(np.isfinite(k)):
+            raise Exception("\n\nk_list must be finite.")
+        S = np.array(sc_red_lat)                                   # the rules of make_supercell
+        if S.shape != (self._dim_r, self._dim_r):
+            raise Exception("\n\nDimension of sc_red_lat array must be dim_r*dim_r")
+        if S.dtype == object or not np.issubdtype(S.dtype, np.integer):
+            raise Exception("\n\nsc_red_lat array elements must be integers")
+        for i in range(self._dim_r):
+            for j in range(self._dim_r):
+                if i == j and i not in self._per and S[i, j] != 1:
+                    raise Exception("\n\nDiagonal elements of sc_red_lat for non-periodic directions must equal 1.")
+                if i != j and (i not in self._per or j not in self._per) and S[i, j] != 0:
+                    raise Exception("\n\nOff-diagonal elements of sc_red_lat for non-periodic directions must equal 0.")
+        det = np.linalg.det(S.astype(float))
+        if not det > 1.0E-6:
+            raise Exception("\n\nsc_red_lat must have a positive determinant (a right handed super-cell of non-zero volume).")
+        nc = int(round(det))
+        norb, nspin = self._norb, self._nspin
+        if prim_index is None:
+            if norb % nc != 0:
+                raise Exception("\n\nprim_index: the model has %d orbitals, not a multiple of the %d primitive cells of sc_red_lat "
+                                "(orbitals were removed or added): give prim_index, the primitive orbital of every orbital." % (norb, nc))
+            pi = np.arange(norb) % (norb // nc)
+        else:
+            pi = np.asarray(prim_index)
+            if pi.dtype == object or pi.ndim != 1 or pi.shape[0] != norb or not np.issubdtype(pi.dtype, np.integer):
+                raise Exception("\n\nprim_index must be None or %d integers (one per orbital): the primitive orbital, or -1." % norb)
+            if pi.min() < -1:
+                raise Exception("\n\nprim_index: entries must be >= -1 (-1: an orbital that projects on nothing).")
+            if pi.max() < 0:
+                raise Exception("\n\nprim_index: at least one orbital must belong to a primitive orbital.")
+            pi = pi.astype(np.int64)
+        n_prim = int(pi.max()) + 1
+        ng = n_prim * nspin
+        if ng > 64:
+            raise Exception("\n\nprim_index: %d primitive orbitals x %d spin components are ng = %d groups (at most 64)." % (n_prim, nspin, ng))
+        group = np.where(pi[:, None] >= 0, pi[:, None] * nspin + np.arange(nspin)[None, :], -1).reshape(-1)
+        group = np.ascontiguousarray(group, dtype=np.int32)
+        count = np.bincount(group[group >= 0], minlength=ng)
+        per = list(self._per)
+        delta = None
+        if prim_orb is not None:
+            try:
+                po = np.array(prim_orb, dtype=float)
+            except (TypeError, ValueError):
+                raise Exception("\n\nprim_orb must be None or a float array (n_prim, dim_r) = (%d, %d)." % (n_prim, self._dim_r))
+            if po.shape != (n_prim, self._dim_r):
+                raise Exception("\n\nprim_orb must be None or a float array (n_prim, dim_r) = (%d, %d)." % (n_prim, self._dim_r))
+            if not np.all(np.isfinite(po)):
+                raise Exception("\n\nprim_orb must be finite.")
+            d = (self._orb @ S.astype(float))[:, per] - po[np.maximum(pi, 0)][:, per]
+            d -= np.round(d)
+            d[pi < 0] = 0.0
+            delta = np.ascontiguousarray(d)
+        K = np.ascontiguousarray(k @ S[np.ix_(per, per)].astype(float).T)
+        return np.ascontiguousarray(k), K, group, ng, count, delta, nc
+
+    def unfolded_bands(self, k_list, sc_red_lat, prim_index=None, prim_orb=None, per_state=False):
+        """Extension: the bands of a supercell unfolded into the Brillouin zone of the primitive cell (the "effective band
+        structure").  The call is made ON THE SUPERCELL MODEL -- the result of `make_supercell(sc_red_lat)`, edited at will
+        (`set_onsite(mode="add")`, `remove_orb`, moved orbitals, added ones).  Returns `(evals, weights)`: `evals` float
+        `(nsta, nk)` as `solve_all` returns it, `weights` float `(nsta, nk)`, or `(nsta, nk, ng)` with per_state=True,
+
+            W_n,g(k) = (1 / N_c) | sum_{j in g} e^{2 pi i k.delta_j} u_n[j] |^2,      weights = sum_g W_n,g
+
+        the weight of eigenstate n of H_sc(K) on the normalised primitive Bloch sum |k,g> of group g.
+
+        k_list: `(nk, dim_k)` in the reduced coordinates of the PRIMITIVE cell.  sc_red_lat: the integer matrix S given to
+        `make_supercell` (same rules; det > 0), N_c = det S.  The supercell is solved at K = S k (the periodic block of S),
+        the same Cartesian vector, passed to the solver as is and not reduced modulo 1.  prim_index: for every supercell
+        orbital the primitive orbital it is an image of, or -1 for an adatom or interstitial that projects on nothing;
+        None is `arange(norb) % (norb // N_c)`, the order `make_supercell` produces (it raises when norb is no multiple of
+        N_c, as after `remove_orb`).  Spinful models: state (j, s) belongs to group g = prim_index[j] * 2 + s, ng = 2 n_prim.
+        prim_orb: None for an undistorted supercell (every delta_j = 0, no phase is formed), or the `(n_prim, dim_r)` orbital
+        positions of the primitive cell; delta_j = orb[j] S - prim_orb[prim_index[j]], minus its rounding, along the periodic
+        directions, is the displacement of orbital j from the nearest lattice image of its ideal site (so `to_home` does
+        not matter).  nsta <= 2048 (beyond: `kpm_unfolded_spectral`), ng <= 64, nsta * nk * ng <= 2**24.
+
+        sum_n W_n,g = (orbitals of group g) / N_c: 1 without vacancies.  With the identity supercell and
+        `prim_index = arange(norb)`, W_n,g = |u_n[g]|^2: orbital-projected ("fat") bands of any model.
+
+        Every sum has a fixed order and the partition of the work depends on (nsta, ng) alone: two calls give the same
+        bits, and the projection adds no dependence on a point's position, chunk or neighbours -- a k-point gives the same
+        bits alone and inside a longer list wherever the eigen-solver takes the same route for both (it picks its method
+        from nsta and the number of points of a launch, as for `solve_all`).  The eigenvectors never leave the device."""
+        k, K, group, ng, _, delta, nc = self._unfold_args("unfolded_bands", k_list, sc_red_lat, prim_index, prim_orb)
+        n, nk = self._nsta, k.shape[0]
+        ngo = ng if per_state else 1
+        if n * nk * ngo > 2 ** 24:
+            raise Exception("\n\nnsta * nk * ng must be at most 2**24: split k_list or omega.")
+        ev = np.empty((n, nk), dtype=float)
+        wt = np.empty((n, nk, ngo), dtype=float)
+        _lib.check(_lib.lib.tbk_unfold_bands_list(self._device_model(), _lib.dptr(K), nk, ng, _lib.iptr(group),
+                                                  None if delta is None else _lib.dptr(k), _lib.dptr(delta), 1.0 / nc,
+                                                  1 if per_state else 0, _lib.dptr(ev), _lib.dptr(wt)))
+        return ev, (wt if per_state else wt[:, :, 0])
+
+    def unfolded_spectral(self, k_list, omega, eta, sc_red_lat, prim_index=None, prim_orb=None, per_state=False):
+        """Extension: the spectral function of a supercell in the Brillouin zone of the primitive cell (the ARPES-like map),
+        float `(nk, nw)`, or `(nk, nw, ng)` with per_state=True,
+
+            A_g(k, w) = sum_n W_n,g(k) (eta / pi) / ((w - E_n)^2 + eta^2) = -(1 / pi) Im <k,g| (w + i eta - H_sc)^-1 |k,g>
+            A(k, w)   = sum_g A_g(k, w)
+
+        with the eigenpairs of H_sc(K = S k) and the weights of `unfolded_bands`, whose arguments k_list, sc_red_lat,
+        prim_index and prim_orb it shares; it is called on the supercell model.  For an unedited supercell A_g is the
+        spectral function of the primitive model, sum_m |u_m[g](k)|^2 L_eta(w - E_m(k)); k and k + any integer vector give the
+        same A.  omega: a scalar (the w axis is dropped), or 1-D with 1..65536 finite values in any order, repeats allowed.
+        eta: one finite number > 0.  nsta <= 2048, ng <= 64, nk * nw * ng <= 2**24 (split k_list or omega beyond).
+
+        The Lorentzian is formed once per (band, frequency) and feeds every group; bands are added in index order.  Two
+        calls give the same bits; a frequency gives the same bits alone and inside a longer list, in any place of it; a
+        k-point does as in `unfolded_bands` (wherever the eigen-solver takes the same route for both list lengths).  The
+        eigenvectors never leave the device: nk * nw * ng doubles come back instead of nk * nsta^2 complex components."""
+        k, K, group, ng, _, delta, nc = self._unfold_args("unfolded_spectral", k_list, sc_red_lat, prim_index, prim_orb)
+        w, scalar, eta = self._omega_eta_arg(omega, eta)
+        nk, nw = k.shape[0], int(w.size)
+        ngo = ng if per_state else 1
+        if nk * nw * ngo > 2 ** 24:
+            raise Exception("\n\nnk * nw * ng must be at most 2**24: split k_list or omega.")
+        out = np.empty((nk, nw, ngo), dtype=float)
+        _lib.check(_lib.lib.tbk_unfold_spectral_list(self._device_model(), _lib.dptr(K), nk, ng, _lib.iptr(group),
+                                                     None if delta is None else _lib.dptr(k), _lib.dptr(delta), 1.0 / nc, nw,
+                                                     _lib.dptr(w), eta, 1 if per_state else 0, _lib.dptr(out)))
+        if not per_state:
+            out = out[:, :, 0]
+        return out[:, 0] if scalar else out
+
+    def kpm_unfolded_spectral(self, k_list, energies, n_moments, sc_red_lat, prim_index=None, prim_orb=None, per_state=False,
+                              kernel="jackson", bounds=None):
+        """Extension: `unfolded_spectral` for supercells of any size (beyond the 2048 states of the dense solver) by the kernel
+        polynomial method, float `(nk, nE)` or `(nk, nE, ng)`: A_g(k, E) = <k,g| delta(E - H_sc(K)) |k,g> from `kpm_moments`
+        with the primitive Bloch sums as start vectors -- v_j = e^{-2 pi i k.delta_j} / sqrt(N_c) on the members of group g --
+        multiplied back by <v|v> and reconstructed by `kpm_reconstruct` (energies, kernel and bounds as there; the
+        resolution is that of the kernel, ~ pi a / n_moments for "jackson", not a Lorentzian of given eta).  Without
+        prim_orb the start vectors do not depend on k and one `kpm_moments` call covers the list; else one call per k-point.
+        k_list, sc_red_lat, prim_index, prim_orb as `unfolded_bands`.  Host glue over the sparse path: no dense matrix."""
+        k, K, group, ng, count, delta, nc = self._unfold_args("kpm_unfolded_spectral", k_list, sc_red_lat, prim_index, prim_orb,
+                                                              dense=False)
+        nk, n, nspin = k.shape[0], self._nsta, self._nspin
+        live = np.flatnonzero(count > 0)                           # (a group without members has A = 0 and no start vector)
+        member = (group[None, :] == live[:, None]).astype(float)   # (nlive, nsta)
+        norm = count[live] / float(nc)                              # <v|v>
+        e = np.asarray(energies, dtype=float)
+        if delta is None:
+            mu, bnd = self.kpm_moments(n_moments, K, vectors=(member / np.sqrt(nc)).astype(complex), bounds=bounds)
+        else:
+            mu, bnd = None, None
+            for q in range(nk):
+                ph = np.repeat(np.exp(-2.0j * np.pi * (delta @ k[q])), nspin)
+                mq, bnd = self.kpm_moments(n_moments, K[q:q + 1], vectors=np.ascontiguousarray(member * ph[None, :] / np.sqrt(nc)),
+                                           bounds=bounds)
+                if mu is None:
+                    mu = np.empty((nk,) + mq.shape[1:], dtype=float)
+                mu[q] = mq[0]
+        a = kpm_reconstruct(mu * norm[None, :, None], e, bnd, kernel)   # (nk, nlive, nE)
+        out = np.zeros((nk, e.size, ng), dtype=float)
+        out[:, :, live] = np.transpose(a, (0, 2, 1))
+        return out if per_state else out.sum(axis=2)
 
     # ------------------------------------------------------------------ the linear tetrahedron method (extensions)
     def _tetra_mesh_arg(self, what, mesh_size):
