@@ -669,6 +669,34 @@ int tbk_unfold_bands_list(tbk_model* model, const double* k_sc, int64_t nk, int 
 int tbk_unfold_spectral_list(tbk_model* model, const double* k_sc, int64_t nk, int ng, const int32_t* group, const double* phase_k,
                              const double* delta, double inv_nc, int nomega, const double* omega, double eta, int per_state, double* out);
 
+/* ---- real-time propagation under a uniform time-dependent field: currents and Floquet propagators ----
+ * Velocity gauge: the field is a rigid shift of every k-point, k -> k + kappa(t).  shift[nt + 1][dim_k] is kappa at the times
+ * t_j = j dt (reduced coordinates, finite), 1 <= nt <= 65536, dt finite and > 0, dim_k 1..3, nsta <= 2048.  H and d_a H are the
+ * convention-II matrices of tbk_gen_ham / tbk_gen_dham; (E, V) are the solver's eigenpairs.  One step j -> j + 1 is the exponential
+ * midpoint rule  psi <- V diag(e^{-i E dt}) V^+ psi  with (E, V) of H(k + (kappa_j + kappa_{j+1}) / 2): exactly unitary, second order in
+ * dt, independent of the solver's basis inside a degenerate group.
+ *
+ * tbk_propagate_mesh: on k_uniform_mesh(mesh), N_k < 2^31.  The carried states start as the eigenvectors of H(k + kappa_0): the bands
+ *   occ[nocc] (distinct, weight f = 1), or -- occ_or_null = NULL, nocc = 0 -- every band with the Fermi weight f_n of (mu, kT), the
+ *   conventions of tbk_thermodynamics_mesh (no spin factor, f = [E <= mu] at kT = 0); a state whose weight is exactly 0 is skipped.
+ *   At every t_j, j = 0 included, with rho(k) = sum_n f_n psi_n psi_n^+:
+ *     current[j][a] = (1 / N_k) sum_k tr d_a H(k + kappa_j) rho(k),     energy[j] = (1 / N_k) sum_k tr H(k + kappa_j) rho(k).
+ *   kpop_or_null[nsta][N_k] = p_n(k) = sum_m f_m |<u_n(k + kappa_nt)|psi_m>|^2 and pop_or_null[nsta] = its mesh mean, from one more
+ *   solve at the last time; inside a group of degenerate levels only the group's sum is defined (the solver chooses the basis).
+ *   The carried states -- N_k nprop nsta c128, nprop = nocc or nsta -- stay on the device for the whole call: at most 2^26 c128
+ *   (1 GiB); beyond, TBK_EINVAL whose message says "coarsen the mesh or select fewer bands".
+ *
+ * tbk_propagator_list: the same steps on the list k[nk][dim_k], started from the identity, no weights:
+ *   u_out[k][i][j] = <i| prod_j exp(-i H(k + kappa_mid,j) dt) |j>, c128 (later steps to the left); nk nsta^2 <= 2^26.
+ *
+ * nsta <= 32: one step kernel with the eigenvectors, phases and carried states of a group of points in LDS; beyond: 16 x 16 tiles, plain
+ * VALU.  Fixed-order sums, no floating-point atomics, a partition that depends on (mesh or nk, nsta, dim_k, nprop) alone and not on
+ * nt: two calls give the same bits, and nt' < nt steps on the leading nt' + 1 shifts give the bits of the first nt' + 1 entries.        */
+int tbk_propagate_mesh(tbk_model* model, const int32_t* mesh, int nt, const double* shift, double dt, int nocc,
+                       const int32_t* occ_or_null, double mu, double kT, double* current, double* energy, double* pop_or_null,
+                       double* kpop_or_null);
+int tbk_propagator_list(tbk_model* model, const double* k, int64_t nk, int nt, const double* shift, double dt, double* u_out);
+
 /* ---- multi-GPU: one process per GPU, k-points sharded, one gather ------
  * Thin RCCL wrappers (librccl is dlopen'ed on first use).  The 128-byte id is
  * created on rank 0 and distributed by the launcher (any out-of-band channel). */

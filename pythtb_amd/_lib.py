@@ -117,6 +117,8 @@ SIGNATURES = {
     "tbk_impurity_ldos_mesh": (_i, [_p, _ip, _i, _dp, C.c_double, _i, _ip, _ip, _dp, _i, _ip, _i, _ip, _dp, _dp]),
     "tbk_unfold_bands_list": (_i, [_p, _dp, _i64, _i, _ip, _dp, _dp, C.c_double, _i, _dp, _dp]),
     "tbk_unfold_spectral_list": (_i, [_p, _dp, _i64, _i, _ip, _dp, _dp, C.c_double, _i, _dp, C.c_double, _i, _dp]),
+    "tbk_propagate_mesh": (_i, [_p, _ip, _i, _dp, C.c_double, _i, _ip, C.c_double, C.c_double, _dp, _dp, _dp, _dp]),
+    "tbk_propagator_list": (_i, [_p, _dp, _i64, _i, _dp, C.c_double, _dp]),
     "tbk_orb_moment_list": (_i, [_p, _dp, _i64, _i, _i, _ip, _i, _dp]),
     "tbk_orb_mag_mesh": (_i, [_p, _ip, _i, _i, _ip, _i, _i, _dp, C.c_double, _dp]),
     "tbk_band_velocity_list": (_i, [_p, _dp, _i64, _i, _dp]),

@@ -2079,6 +2079,193 @@ class tb_model(object):
         vc = np.sqrt(np.linalg.det(a @ a.T))
         return np.einsum("ia,wij,jb->wab", a, out, a) / ((2.0 * np.pi) ** 2 * vc)
 
+    # ------------------------------------------------------------------ real-time propagation under a uniform field (extensions)
+    def _shift_dt_args(self, what, shift, dt):
+        """(shift as a contiguous float64 `(nt + 1, dim_k)` array, nt, dt) of the propagation calls: dim_k 1, 2 or 3, 1 <= nt <=
+        65536, every shift finite, dt finite and > 0."""
+        if self._dim_k not in (1, 2, 3):
+            raise Exception("\n\n%s needs a model with dim_k 1, 2 or 3." % what)
+        try:
+            kap = np.array(shift, dtype=float)
+        except (TypeError, ValueError):
+            raise Exception("\n\nshift must be a real array of shape (nt + 1, dim_k).")
+        if self._dim_k == 1 and kap.ndim == 1:
+            kap = kap.reshape(-1, 1)
+        if kap.ndim != 2 or kap.shape[1] != self._dim_k:
+            raise Exception("\n\nshift must have shape (nt + 1, dim_k): the shift of k at the times j * dt, j = 0 .. nt.")
+        if kap.shape[0] < 2 or kap.shape[0] > 65537:
+            raise Exception("\n\nshift must hold the shifts at nt + 1 times with 1 <= nt <= 65536.")
+        if not np.all(np.isfinite(kap)):
+            raise Exception("\n\nshift must be finite.")
+        try:
+            dt = float(dt)
+        except (TypeError, ValueError):
+            raise Exception("\n\ndt must be finite and > 0.")
+        if not np.isfinite(dt) or not dt > 0.0:
+            raise Exception("\n\ndt must be finite and > 0.")
+        return np.ascontiguousarray(kap), kap.shape[0] - 1, dt
+
+    _TD_STATE_CAP = 2 ** 26
+
+    def propagate_mesh(self, mesh_size, shift, dt, occ=None, fermi_level=None, kT=0.0, cartesian=False, return_populations=False,
+                       return_k_populations=False):
+        """Extension: the crystal in a uniform time-dependent field, propagated in real time on `k_uniform_mesh(mesh_size)` (1-, 2-
+        or 3-D, generated on the device): `(current (nt + 1, dim_k), energy (nt + 1,))` per cell, hbar = e = 1.
+
+        Velocity gauge: the field is a rigid shift of every k-point, k -> k + shift(t); `shift` `(nt + 1, dim_k)` holds it at the
+        times t_j = j * dt in reduced coordinates (kappa = -A(t) . a_i / 2 pi for a vector potential A and an electron of charge
+        -1; `laser_shift` builds common pulses).  H and dH/dk_a are the matrices of `_gen_ham` and `_gen_dham`.
+        Start: the eigenvectors of `solve_all` at k + shift[0] -- the bands `occ` (a NumPy index, as `berry_curvature` reads it),
+        each with weight 1, or every band with the Fermi weight f_n of (`fermi_level`, `kT`) in the conventions of
+        `thermodynamics_mesh` (no spin factor; f = [E <= mu] at kT = 0).  Exactly one of occ / fermi_level must be given.
+        States whose weight is exactly 0 are not carried.
+        Step j -> j + 1: psi <- V exp(-i E dt) V^+ psi with the eigenpairs of H(k + (shift[j] + shift[j + 1]) / 2), the exponential
+        midpoint rule: exactly unitary, second order in dt, independent of the solver's basis inside a degenerate group.
+        At every t_j, j = 0 included:
+            current[j, a] = (1 / N_k) sum_k sum_n f_n <psi_n| dH/dk_a (k + shift[j]) |psi_n>,    energy[j] = the same with H.
+        cartesian=True maps the current as `band_velocity` documents: J A / (2 pi), `(nt + 1, dim_r)`.  With shift advancing by a
+        reciprocal vector along axis a over the run, int J_b dt / (2 pi) of a filled band is its pumped charge.
+
+        return_populations / return_k_populations append pop `(nsta,)` and kpop `(nsta, N_k)`: p_n(k) = sum_m f_m
+        |<u_n(k + shift[-1])|psi_m>|^2 with the eigenvectors of `solve_all` at the last time, and its mesh mean.  Inside a group
+        of degenerate levels the eigenvectors are the solver's choice and only the group's sum is defined, as for `band_velocity`.
+
+        The states stay on the device for the whole call: N_k * nprop * nsta <= 2**26 (nprop = the bands of occ, or nsta).
+        Fixed-order sums: two calls give the same bits, and the leading nt' + 1 shifts alone give the bits of the first nt' + 1
+        entries."""
+        kap, nt, dt = self._shift_dt_args("propagate_mesh", shift, dt)
+        mesh, nk = self._mesh_arg(mesh_size)
+        if (occ is None) == (fermi_level is None):
+            raise Exception("\n\nGive exactly one of occ (a band set) and fermi_level (Fermi weights).")
+        if not isinstance(cartesian, (bool, np.bool_)):
+            raise Exception("\n\ncartesian must be True or False.")
+        n, dk = self._nsta, self._dim_k
+        sel, mu = None, 0.0
+        if occ is not None:
+            sel = np.atleast_1d(np.arange(n)[occ]).ravel()
+            if sel.size == 0:
+                raise Exception("\n\nocc selects no band.")
+            if np.unique(sel).size != sel.size:
+                raise Exception("\n\nocc lists a band twice.")
+            sel = np.ascontiguousarray(sel, dtype=np.int32)
+            kT = 0.0
+        else:
+            try:
+                mu = float(fermi_level)
+            except (TypeError, ValueError):
+                raise Exception("\n\nfermi_level must be one finite number.")
+            if not np.isfinite(mu):
+                raise Exception("\n\nfermi_level must be finite.")
+            try:
+                kT = float(kT)
+            except (TypeError, ValueError):
+                raise Exception("\n\nkT must be finite and >= 0.")
+            if not np.isfinite(kT) or not kT >= 0.0:
+                raise Exception("\n\nkT must be finite and >= 0.")
+        nprop = n if sel is None else int(sel.size)
+        if nk * nprop * n > self._TD_STATE_CAP:
+            raise Exception("\n\npropagate_mesh keeps N_k * nprop * nsta = %d complex numbers on the device (at most 2**26): "
+                            "coarsen the mesh or select fewer bands (occ)." % (nk * nprop * n))
+        cur = np.zeros((nt + 1, dk), dtype=float)
+        en = np.zeros(nt + 1, dtype=float)
+        want = bool(return_populations) or bool(return_k_populations)
+        pop = np.zeros(n, dtype=float) if want else None
+        kpop = np.zeros((n, nk), dtype=float) if want else None
+        _lib.check(_lib.lib.tbk_propagate_mesh(self._device_model(), _lib.iptr(mesh), nt, _lib.dptr(kap), dt,
+                                               0 if sel is None else len(sel), _lib.iptr(sel), mu, kT, _lib.dptr(cur), _lib.dptr(en),
+                                               _lib.dptr(pop), _lib.dptr(kpop)))
+        if cartesian:
+            cur = cur @ np.array(self._lat, dtype=float)[self._per] / (2.0 * np.pi)
+        out = (cur, en)
+        if return_populations:
+            out += (pop,)
+        if return_k_populations:
+            out += (kpop,)
+        return out
+
+    def floquet_propagator(self, k_list, shift, dt):
+        """Extension: the propagator of the steps of `propagate_mesh` at every k of `k_list` (reduced coordinates, as solve_all),
+        started from the identity: complex `(nk, nsta, nsta)`,
+
+            U(k) = prod_j exp(-i H(k + (shift[j] + shift[j + 1]) / 2) dt),   j = nt - 1 .. 0 from the left,   U[k, i, j] = <i|U|j>,
+
+        exactly unitary.  Spinful models return `(nk, norb, 2, norb, 2)`, as `_gen_ham` does.  nk * nsta**2 <= 2**26."""
+        kap, nt, dt = self._shift_dt_args("floquet_propagator", shift, dt)
+        try:
+            k = np.array(k_list, dtype=float)
+        except (TypeError, ValueError):
+            raise Exception("\n\nk_list must be a real array of shape (nk, dim_k).")
+        if self._dim_k == 1 and k.ndim == 1:
+            k = k.reshape(-1, 1)
+        if k.ndim != 2 or k.shape[1] != self._dim_k or k.shape[0] < 1 or not np.all(np.isfinite(k)):
+            raise Exception("\n\nk_list must have shape (nk, dim_k) with at least one k-point, all finite.")
+        k = np.ascontiguousarray(k)
+        nk, n = k.shape[0], self._nsta
+        if nk * n * n > self._TD_STATE_CAP:
+            raise Exception("\n\nfloquet_propagator keeps nk * nsta**2 = %d complex numbers on the device (at most 2**26): split k_list."
+                            % (nk * n * n))
+        out = np.zeros((nk, n, n), dtype=complex)
+        _lib.check(_lib.lib.tbk_propagator_list(self._device_model(), _lib.dptr(k), nk, nt, _lib.dptr(kap), dt, _lib.dptr(out.view(float))))
+        if self._nspin == 2:
+            out = out.reshape(nk, self._norb, 2, self._norb, 2)
+        return out
+
+    def floquet_bands(self, k_list, shift, dt):
+        """Extension: the quasi-energies of a periodically driven model, float `(nsta, nk)` (the layout of `solve_all`), ascending,
+
+            eps_n(k) = -arg(lambda_n) / T  in  (-pi / T, pi / T],   T = nt * dt,   lambda_n the eigenvalues of `floquet_propagator`.
+
+        The propagator is built on the device; the eigenvalues of the small unitary matrices are taken on the host with NumPy -- a
+        reconstruction step like `kpm_reconstruct`, not a device computation.  The quasi-energies mean something only if the
+        caller's shift is periodic over the window, shift(t + T) = shift(t).  In convention II a shift by a reciprocal vector
+        gives a unitarily equivalent H (conjugated by the orbital phases e^{2 pi i G.tau}), not an equal one: a window over which
+        shift advances by a reciprocal vector is periodic only up to that transformation."""
+        kap, nt, dt = self._shift_dt_args("floquet_bands", shift, dt)
+        u = self.floquet_propagator(k_list, kap, dt)
+        nk, n = u.shape[0], self._nsta
+        period = nt * dt
+        lam = np.linalg.eigvals(u.reshape(nk, n, n))
+        eps = -np.angle(lam) / period
+        eps = np.where(eps <= -np.pi / period, eps + 2.0 * np.pi / period, eps)     # (arg = +pi -> the upper edge)
+        return np.ascontiguousarray(np.sort(eps, axis=1).T)
+
+    def laser_shift(self, times, amplitude, omega, phase=0.0, envelope="sin2"):
+        """Extension, a host convenience: the shift kappa(t) `(len(times), dim_k)` of a laser pulse for `propagate_mesh` and the
+        Floquet calls,
+
+            kappa_a(t) = env(t) [Re(amplitude_a) cos(omega t + phase) + Im(amplitude_a) sin(omega t + phase)].
+
+        amplitude `(dim_k,)` in reduced coordinates: real for linear polarisation, complex for elliptic -- a (1, 1j) is the
+        circular pulse a (cos, sin).  envelope "flat": env = 1; "sin2": env = sin^2(pi (t - t_0) / (t_end - t_0)) over the span of
+        `times`, which vanishes with its derivative at both ends.  times: 1-D, at least two finite values (propagate_mesh wants
+        them equally spaced from 0: j * dt)."""
+        if self._dim_k not in (1, 2, 3):
+            raise Exception("\n\nlaser_shift needs a model with dim_k 1, 2 or 3.")
+        try:
+            t = np.array(times, dtype=float)
+            amp = np.array(amplitude, dtype=complex)
+            omega, phase = float(omega), float(phase)
+        except (TypeError, ValueError):
+            raise Exception("\n\nlaser_shift: times, amplitude, omega and phase must be numbers.")
+        if t.ndim != 1 or t.size < 2 or not np.all(np.isfinite(t)):
+            raise Exception("\n\ntimes must be a 1-D array of at least two finite values.")
+        if amp.ndim == 0 and self._dim_k == 1:
+            amp = amp.reshape(1)
+        if amp.shape != (self._dim_k,) or not np.all(np.isfinite(amp)):
+            raise Exception("\n\namplitude must be a finite (dim_k,) vector (complex for elliptic polarisation).")
+        if not np.isfinite(omega) or not np.isfinite(phase):
+            raise Exception("\n\nomega and phase must be finite.")
+        if envelope == "flat":
+            env = np.ones_like(t)
+        elif envelope == "sin2":
+            if not t[-1] > t[0]:
+                raise Exception("\n\ntimes must increase for the sin2 envelope.")
+            env = np.sin(np.pi * (t - t[0]) / (t[-1] - t[0])) ** 2
+        else:
+            raise Exception("\n\nenvelope must be 'sin2' or 'flat'.")
+        arg = omega * t + phase
+        return env[:, None] * (np.cos(arg)[:, None] * amp.real[None, :] + np.sin(arg)[:, None] * amp.imag[None, :])
+
     # ------------------------------------------------------------------ position operator
     def ignore_position_operator_offdiagonal(self):
         self._assume_position_operator_diagonal = True
