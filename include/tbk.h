@@ -96,6 +96,13 @@ int tbk_model_flatten_host(int dim_k, int norb, int nspin, const double* orb, co
                            int64_t nhop, const int32_t* hop_i, const int32_t* hop_j, const int32_t* hop_R,
                            const double* hop_amp, int64_t term_cap, int64_t* nterm, int32_t* term_slot,
                            int32_t* term_R, double* term_amp, int32_t* info);
+/* The same with pinned keys pin[npin][6] = {a, b, R[4]} in STATE indices: terms that keep their slot (and cell, and lattice-vector
+ * table entry) at amplitude zero; a pin on the diagonal (a == b) pins R and -R.  npin = 0 is tbk_model_flatten_host.  The mean-field
+ * driver uploads its private model this way.                                                                 */
+int tbk_model_flatten_host_pinned(int dim_k, int norb, int nspin, const double* orb, const double* onsite,
+                                  int64_t nhop, const int32_t* hop_i, const int32_t* hop_j, const int32_t* hop_R,
+                                  const double* hop_amp, int64_t npin, const int32_t* pin, int64_t term_cap, int64_t* nterm,
+                                  int32_t* term_slot, int32_t* term_R, double* term_amp, int32_t* info);
 int tbk_model_info(tbk_model* model, int* dim_k, int* nsta, int64_t* nterm);
 
 /* Host-only: continuity of Berry phases along the first index of a result array (berry_phase(contin=True), pythtb.py:2980-3036).
@@ -696,6 +703,32 @@ int tbk_propagate_mesh(tbk_model* model, const int32_t* mesh, int nt, const doub
                        const int32_t* occ_or_null, double mu, double kT, double* current, double* energy, double* pop_or_null,
                        double* kpop_or_null);
 int tbk_propagator_list(tbk_model* model, const double* k, int64_t nk, int nt, const double* shift, double dt, double* u_out);
+
+/* ---- self-consistent Hartree-Fock on a k mesh ----
+ * H_int = 1/2 sum_{a,b,R} V_ab(R) n_{a,0} n_{b,R} over STATE indices (orbital * nspin + spin), decoupled with D_ij(R) = <c+_{j,R} c_{i,0}>
+ * of tbk_density_matrix_mesh: the on-site energy of a gets sum V_ab(R) n_b (Hartree) and, with fock != 0, the entry (a, b, R) of the
+ * hopping table gets -V_ab(R) D_ab(R) and its mirror the conjugate.  The bare model comes as the tables of tbk_model_upload: the
+ * driver uploads a private copy with every field entry pinned and frees it at the end.
+ *   interaction  nint >= 1 entries: int_ab[nint][2], int_R[nint][dim_k], int_V[nint]; an entry is the bond AND its mirror (b, a, -R),
+ *                given once; (a, a, R = 0) is refused.  The lattice vectors of the result: R = 0, then the entries' in order of first
+ *                appearance, nR <= 4096, nR nsta^2 <= 2^22.
+ *   parameters   x[np]: the occupations of the states some V touches (ascending state), then with fock Re, Im of D_ab(R) of every
+ *                entry in list order; np <= 2^20.
+ *   filling      have_nel != 0: nel_or_mu electrons per cell (the rules of tbk_fermi_level_mesh); else the Fermi level itself.
+ *   start        start_mode 0: the field of the bare model at the same filling; 1: x_start[np].
+ *   mixing       0 < mixing <= 1; history 0 linear, 1..8 Anderson over that many pairs after as many linear steps; tol >= 0 on
+ *                max |x_out - x_in| (0: exactly max_iter iterations); 1 <= max_iter <= 65536; the host reads the residual every
+ *                check_every >= 1 iterations (one 8-byte copy) and nothing else until the end.
+ * Out: x_in[np] the field the last iteration solved in, x_out[np] the field it produced, mu_out[1], dens[nR][nsta][nsta] c128 = D of the
+ * last iteration, R_out[nR][dim_k], energies[5] = {E, S, E - kT S, band energy, N} per cell, res_hist[max_iter] and
+ * occ_hist[max_iter][nsta] (the first `iterations` rows are written), info[5] = {iterations, converged, nR, np, resident form}.
+ * Fixed-order sums, no floating-point atomics: two calls give the same bits, and max_iter = k gives the first k rows of a longer run. */
+int tbk_mean_field_mesh(tbk_ctx* ctx, int dim_k, int norb, int nspin, const double* orb, const double* onsite, int64_t nhop,
+                        const int32_t* hop_i, const int32_t* hop_j, const int32_t* hop_R, const double* hop_amp,
+                        const int32_t* mesh, int nint, const int32_t* int_ab, const int32_t* int_R, const double* int_V, int fock,
+                        int have_nel, double nel_or_mu, double kT, int start_mode, const double* x_start, double mixing,
+                        int history, double tol, int max_iter, int check_every, double* x_in, double* x_out, double* mu_out,
+                        double* dens, int32_t* R_out, double* energies, double* res_hist, double* occ_hist, int32_t* info);
 
 /* ---- multi-GPU: one process per GPU, k-points sharded, one gather ------
  * Thin RCCL wrappers (librccl is dlopen'ed on first use).  The 128-byte id is

@@ -42,6 +42,7 @@ SIGNATURES = {
     "tbk_one_phase_cont": (_i, [_dp, _i64, _i64, C.c_double, _dp, _i64]),
     "tbk_array_phases_cont": (_i, [_dp, _i64, _i, _i64, _dp, _dp, _i64]),
     "tbk_model_flatten_host": (_i, [_i, _i, _i, _dp, _dp, _i64, _ip, _ip, _ip, _dp, _i64, C.POINTER(C.c_int64), _ip, _ip, _dp, _ip]),
+    "tbk_model_flatten_host_pinned": (_i, [_i, _i, _i, _dp, _dp, _i64, _ip, _ip, _ip, _dp, _i64, _ip, _i64, C.POINTER(C.c_int64), _ip, _ip, _dp, _ip]),
     "tbk_ctx_create": (_i, [_i, _pp]),
     "tbk_ctx_destroy": (_i, [_p]),
     "tbk_ctx_sync": (_i, [_p]),
@@ -117,6 +118,8 @@ SIGNATURES = {
     "tbk_impurity_ldos_mesh": (_i, [_p, _ip, _i, _dp, C.c_double, _i, _ip, _ip, _dp, _i, _ip, _i, _ip, _dp, _dp]),
     "tbk_unfold_bands_list": (_i, [_p, _dp, _i64, _i, _ip, _dp, _dp, C.c_double, _i, _dp, _dp]),
     "tbk_unfold_spectral_list": (_i, [_p, _dp, _i64, _i, _ip, _dp, _dp, C.c_double, _i, _dp, C.c_double, _i, _dp]),
+    "tbk_mean_field_mesh": (_i, [_p, _i, _i, _i, _dp, _dp, _i64, _ip, _ip, _ip, _dp, _ip, _i, _ip, _ip, _dp, _i, _i, C.c_double, C.c_double,
+                                 _i, _dp, C.c_double, _i, C.c_double, _i, _i, _dp, _dp, _dp, _dp, _ip, _dp, _dp, _dp, _ip]),
     "tbk_propagate_mesh": (_i, [_p, _ip, _i, _dp, C.c_double, _i, _ip, C.c_double, C.c_double, _dp, _dp, _dp, _dp]),
     "tbk_propagator_list": (_i, [_p, _dp, _i64, _i, _dp, C.c_double, _dp]),
     "tbk_orb_moment_list": (_i, [_p, _dp, _i64, _i, _i, _ip, _i, _dp]),

@@ -1,0 +1,275 @@
+// Stand-alone host check of tbk_mf.h (no device call): built under AddressSanitizer + UBSan by `make -C pythtb_amd/csrc mf-check` and run
+// as an ordinary program.  It covers every argument rule of tbk_mean_field_mesh and the edge of every cap; the expansion of an
+// interaction list into parameters, pins, gather indices and the term -> parameter map for hand-worked cases (Hubbard U on a spinful
+// two-orbital cell; one nearest-neighbour V on a spinless cell with and without a hop on that bond; a bond and its mirror given
+// twice); the small Anderson solve against values worked out by hand (m = 1, 2, 8, a zero residual, a non-finite entry); and the
+// resident and two-pass workspace layouts, filled and read back under the sanitizer.  The pinned flatten itself lives in
+// tbk_core.hip, beside the flatten it extends, and is held by tests/test_mean_field.py through tbk_model_flatten_host_pinned.
+#include <cmath>
+#include <cstdarg>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <limits>
+#include <vector>
+#include "../tbk_mf.h"
+
+// what the headers' host functions take from the library (this program links no translation unit of it)
+static char g_err[512];
+void tbk_set_error(const char* fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(g_err, sizeof g_err, fmt, ap);
+    va_end(ap);
+}
+int tbk_ctx_scratch(tbk_ctx*, size_t, void**) { return TBK_EHIP; }
+int tbk_k_uniform_mesh_range_dev(tbk_ctx*, int, const int32_t*, int64_t, int64_t, double*) { return TBK_EHIP; }
+int tbk_solve_list_dev_checked(tbk_model*, const double*, int64_t, double*, double*) { return TBK_EHIP; }
+ProfScope::ProfScope(tbk_ctx* c, const char* n) : ctx(c), name(n) {}
+ProfScope::~ProfScope() {}
+
+#define EXPECT(cond)                                                      \
+    do {                                                                  \
+        if (!(cond)) return printf("line %d: %s (%s)\n", __LINE__, #cond, g_err), 1;  \
+    } while (0)
+
+struct Inter {
+    std::vector<int32_t> ab, R;
+    std::vector<double> V;
+    void add(int a, int b, std::vector<int> r, double v) {
+        ab.push_back(a), ab.push_back(b);
+        for (int x : r) R.push_back(x);
+        V.push_back(v);
+    }
+    MfArgs args() const {
+        MfArgs A;
+        A.nint = (int)V.size(), A.ab = ab.data(), A.R = R.data(), A.V = V.data();
+        A.nel = 1.0;
+        return A;
+    }
+};
+
+static int check_arguments() {
+    const int32_t mesh[3] = {4, 4, 4};
+    Inter I;
+    I.add(0, 1, {0, 0}, 1.0);
+    int64_t npts;
+    double target;
+    MfArgs A = I.args();
+    EXPECT(mf_check("t", 2, 2, mesh, A, npts, target) == TBK_OK && npts == 16 && target == 16.0);
+    EXPECT(mf_check("t", 0, 2, mesh, A, npts, target) == TBK_EINVAL);              // dim_k 1..3
+    EXPECT(mf_check("t", 4, 2, mesh, A, npts, target) == TBK_EINVAL);
+    EXPECT(mf_check("t", 2, 2049, mesh, A, npts, target) == TBK_EINVAL);           // nsta <= 2048
+#define BAD(stmt)                                                         \
+    do {                                                                  \
+        MfArgs B = A;                                                     \
+        stmt;                                                             \
+        EXPECT(mf_check("t", 2, 2, mesh, B, npts, target) == TBK_EINVAL); \
+    } while (0)
+#define GOOD(stmt)                                                        \
+    do {                                                                  \
+        MfArgs B = A;                                                     \
+        stmt;                                                             \
+        EXPECT(mf_check("t", 2, 2, mesh, B, npts, target) == TBK_OK);     \
+    } while (0)
+    BAD(B.nint = 0);
+    BAD(B.history = -1);
+    BAD(B.history = 9);
+    GOOD(B.history = 0);
+    GOOD(B.history = 8);
+    BAD(B.max_iter = 0);
+    BAD(B.max_iter = 65537);
+    GOOD(B.max_iter = 65536);
+    BAD(B.check_every = 0);
+    GOOD(B.check_every = 1 << 20);
+    BAD(B.mixing = 0.0);
+    BAD(B.mixing = 1.0000001);
+    BAD(B.mixing = std::numeric_limits<double>::quiet_NaN());
+    GOOD(B.mixing = 1.0);
+    BAD(B.tol = -1e-300);
+    BAD(B.tol = std::numeric_limits<double>::infinity());
+    GOOD(B.tol = 0.0);
+    BAD(B.kT = -1.0);
+    BAD(B.nel = 0.53);                                                             // 0.53 x 16 points: not an integer at kT = 0
+    BAD(B.nel = 2.0);                                                              // every level: nothing to select
+    GOOD((B.nel = 0.53, B.kT = 0.1));
+    BAD((B.nel = 2.0, B.kT = 0.1));
+    BAD((B.have_nel = 0, B.mu = std::numeric_limits<double>::infinity()));
+    GOOD((B.have_nel = 0, B.mu = -3.0));
+    Inter S;                                                                       // a self-interaction, an index, a long vector
+    S.add(1, 1, {0, 0}, 1.0);
+    MfArgs As = S.args();
+    EXPECT(mf_check("t", 2, 2, mesh, As, npts, target) == TBK_EINVAL && strstr(g_err, "self-interaction"));
+    Inter O;
+    O.add(0, 2, {0, 0}, 1.0);
+    MfArgs Ao = O.args();
+    EXPECT(mf_check("t", 2, 2, mesh, Ao, npts, target) == TBK_EINVAL);
+    Inter L;
+    L.add(0, 1, {1 << 30, 0}, 1.0);
+    MfArgs Al = L.args();
+    EXPECT(mf_check("t", 2, 2, mesh, Al, npts, target) == TBK_EINVAL);
+    Inter N;
+    N.add(0, 1, {0, 0}, std::numeric_limits<double>::quiet_NaN());
+    MfArgs An = N.args();
+    EXPECT(mf_check("t", 2, 2, mesh, An, npts, target) == TBK_EINVAL);
+    // the caps of the expansion: 4096 lattice vectors, nR nsta^2 <= 2^22
+    Inter M;
+    for (int r = 1; r <= 4096; ++r) M.add(0, 1, {r, 0}, 1.0);                      // with R = 0: 4097 vectors
+    MfProblem P;
+    EXPECT(mf_problem("t", 2, 2, M.args(), P) == TBK_EINVAL && strstr(g_err, "distinct lattice vectors"));
+    M.ab.resize(2 * 4095), M.R.resize(2 * 4095), M.V.resize(4095);
+    EXPECT(mf_problem("t", 2, 2, M.args(), P) == TBK_OK && P.nR == 4096);
+    Inter W;
+    W.add(0, 1, {1}, 1.0);
+    EXPECT(mf_problem("t", 1, 1449, W.args(), P) == TBK_EINVAL && strstr(g_err, "nR * nsta^2"));   // 2 x 1449^2 > 2^22
+    EXPECT(mf_problem("t", 1, 1448, W.args(), P) == TBK_OK);
+    return 0;
+}
+
+static int check_expansion() {
+    MfProblem P;
+    {   // Hubbard U on a spinful two-orbital cell: states (0 up, 0 down, 1 up, 1 down), entries (0, 1) and (2, 3) at R = 0
+        Inter I;
+        I.add(0, 1, {0, 0}, 3.0);
+        I.add(2, 3, {0, 0}, 2.0);
+        MfArgs A = I.args();
+        EXPECT(mf_problem("t", 2, 4, A, P) == TBK_OK);
+        EXPECT(P.nocc == 4 && P.np == 8 && P.nR == 1 && P.pin.size() == 6 * 6);
+        EXPECT(P.gidx[0] == 0 && P.gidx[1] == 2 * 5 && P.gidx[3] == 2 * 15 && P.gidx[4] == 2 * 1 && P.gidx[5] == 2 * 1 + 1 &&
+               P.gidx[6] == 2 * 11);
+        EXPECT(P.rowsum[0] == 3.0 && P.rowsum[3] == 2.0);
+        // the flattened model: on-site terms of the four states and the two spin-flip terms, slots of a 4-state model
+        // (0,0)=0 (0,1)=1 (1,1)=4 (2,2)=7 (2,3)=8 (3,3)=9; terms in slot order, one each
+        const int nslot = 10;
+        std::vector<int32_t> slot_ptr = {0, 1, 2, 2, 2, 3, 3, 3, 4, 5, 6};
+        std::vector<int32_t> R4(6 * 4, 0);
+        std::vector<double> amp2 = {0.1, 0, 0, 0, 0.1, 0, -0.1, 0, 0, 0, -0.1, 0};
+        std::vector<int32_t> rvec(4, 0);
+        MfMap M;
+        EXPECT(mf_map("t", P, nslot, slot_ptr, R4, amp2, 1, rvec, M) == TBK_OK);
+        EXPECT(M.term.size() == 6 && M.ptr.back() == 8);
+        // term 0 = eps of state 0: + 3 n_1 (parameter 1); term 1 = (0, 1): -3 Re (parameter 4), -3 Im (parameter 5)
+        EXPECT(M.ptr[1] == 1 && M.coef[0] == 3.0 && M.par[0] == 1 && M.part[0] == 0 && M.base[0] == 0.1);
+        EXPECT(M.ptr[2] == 3 && M.coef[1] == -3.0 && M.par[1] == 4 && M.part[1] == 0 && M.coef[2] == -3.0 && M.par[2] == 5 && M.part[2] == 1);
+        EXPECT(M.rblk[1] == 1 && M.rblk[4] == 8 && M.rblk[5] == 9);
+        EXPECT(M.coef[3] == 3.0 && M.par[3] == 0);                                 // eps of state 1: + 3 n_0
+    }
+    {   // one nearest-neighbour V on a spinless two-orbital cell, given from the upper orbital: (1, 0, R = +1) is stored as (0, 1, -1)
+        Inter I;
+        I.add(1, 0, {1}, 0.5);
+        EXPECT(mf_problem("t", 1, 2, I.args(), P) == TBK_OK);
+        EXPECT(P.nocc == 2 && P.np == 4 && P.nR == 2 && P.Rl[0] == 0 && P.Rl[1] == 1);
+        EXPECT(P.gidx[2] == 2 * (4 + 2) && P.gidx[3] == 2 * (4 + 2) + 1);          // D_10(R = 1): acc[1][1][0]
+        // (a) the model has a hop on that bond: terms eps_0 | (0,1,R=-1) | eps_1
+        std::vector<int32_t> slot_ptr = {0, 1, 2, 3};
+        std::vector<int32_t> R4 = {0, 0, 0, 0, -1, 0, 0, 0, 0, 0, 0, 0};
+        std::vector<double> amp2 = {0, 0, -1.0, 0, 0, 0};
+        std::vector<int32_t> rvec;
+        MfMap M;
+        EXPECT(mf_map("t", P, 3, slot_ptr, R4, amp2, 0, rvec, M) == TBK_OK);
+        EXPECT(M.term.size() == 3 && M.term[1] == 1 && M.base[2] == -1.0 && M.rblk[1] == -1);
+        // the stored term is the conjugate: -V Re, +V Im
+        EXPECT(M.coef[1] == -0.5 && M.par[1] == 2 && M.part[1] == 0 && M.coef[2] == 0.5 && M.par[2] == 3 && M.part[2] == 1);
+        // (b) without the pinned term the map refuses
+        std::vector<int32_t> sp2 = {0, 1, 1, 2};
+        std::vector<int32_t> R42(8, 0);
+        std::vector<double> a2(4, 0.0);
+        EXPECT(mf_map("t", P, 3, sp2, R42, a2, 0, rvec, M) == TBK_EINVAL);
+        // Hartree only: no bond parameters and no bond pin
+        MfArgs A = I.args();
+        A.fock = 0;
+        EXPECT(mf_problem("t", 1, 2, A, P) == TBK_OK && P.np == 2 && P.pin.size() == 12 && P.field.size() == 2);
+    }
+    {   // a bond and its mirror: refused; a bond on the diagonal gets both directions
+        Inter I;
+        I.add(0, 1, {1}, 0.5);
+        I.add(1, 0, {-1}, 0.5);
+        EXPECT(mf_problem("t", 1, 2, I.args(), P) == TBK_EINVAL && strstr(g_err, "given once"));
+        Inter J;
+        J.add(0, 0, {1}, 0.5);
+        J.add(0, 0, {-1}, 0.5);
+        EXPECT(mf_problem("t", 1, 1, J.args(), P) == TBK_EINVAL);
+        Inter K;
+        K.add(0, 0, {1}, 0.5);
+        EXPECT(mf_problem("t", 1, 1, K.args(), P) == TBK_OK && P.np == 3);
+        int nfock = 0;
+        for (const MfField& F : P.field) nfock += F.par >= 1;
+        EXPECT(nfock == 4 && P.field[0].coef == 0.5 && P.field[1].coef == 0.5);    // Hartree: 2 V n_0 in two halves
+    }
+    return 0;
+}
+
+static int check_anderson() {
+    double B[64], c[8], W[MF_AND_WORK];
+    memset(B, 0, sizeof B);
+    B[0] = 4.0;
+    EXPECT(mf_anderson(1, B, c, W) && fabs(c[0] - 1.0) < 1e-15);
+    B[0] = 1.0, B[9] = 4.0;                                                        // orthogonal residuals: c_j ~ 1 / |r_j|^2
+    EXPECT(mf_anderson(2, B, c, W) && fabs(c[0] - 0.8) < 1e-11 && fabs(c[1] - 0.2) < 1e-11);
+    B[0] = 1.0, B[1] = B[8] = -0.5, B[9] = 1.0;                                    // symmetric: halves
+    EXPECT(mf_anderson(2, B, c, W) && fabs(c[0] - 0.5) < 1e-12 && fabs(c[1] - 0.5) < 1e-12);
+    B[0] = 1.0, B[1] = B[8] = 1.0, B[9] = 1.0;                                     // the same residual twice: singular but for the
+    EXPECT(mf_anderson(2, B, c, W) && fabs(c[0] + c[1] - 1.0) < 1e-12);            // regularisation, which splits it evenly
+    EXPECT(fabs(c[0] - 0.5) < 1e-3);
+    B[0] = 0.0, B[1] = B[8] = 0.0, B[9] = 1.0;                                     // a zero residual: the linear step
+    EXPECT(!mf_anderson(2, B, c, W));
+    B[0] = std::numeric_limits<double>::quiet_NaN();
+    EXPECT(!mf_anderson(2, B, c, W));
+    memset(B, 0, sizeof B);
+    for (int j = 0; j < 8; ++j) B[9 * j] = 1.0;
+    EXPECT(mf_anderson(8, B, c, W));
+    for (int j = 0; j < 8; ++j) EXPECT(fabs(c[j] - 0.125) < 1e-12);
+    EXPECT(!mf_anderson(0, B, c, W) && !mf_anderson(9, B, c, W));
+    return 0;
+}
+
+static int check_layout(const char* tag, const MfPlan& p) {
+    size_t end = 256;
+    for (int i = 0; i < MfPlan::NBUF; ++i) {
+        if (p.off[i] % 256 || p.off[i] < end) return printf("%s: buffer %d at %zu (the previous one ends at %zu)\n", tag, i, p.off[i], end);
+        end = p.off[i + 1];
+    }
+    if (end != p.total) return printf("%s: the total\n", tag);
+    if (p.total > ((size_t)256 << 20)) return 0;
+    unsigned char* base = (unsigned char*)aligned_alloc(256, al256(p.total));
+    if (!base) return printf("%s: no host block\n", tag);
+    int bad = 0;
+    for (int i = 0; i < MfPlan::NBUF; ++i) memset(base + p.off[i], i + 1, p.off[i + 1] - p.off[i]);
+    for (int i = 0; i < MfPlan::NBUF && !bad; ++i)
+        for (size_t j = p.off[i]; j < p.off[i + 1]; j += 61)
+            if (base[j] != (unsigned char)(i + 1)) {
+                bad = printf("%s: buffer %d is overwritten\n", tag, i);
+                break;
+            }
+    free(base);
+    return bad;
+}
+static int check_plans() {
+    // 40 states on 1369 points: chunks of 1310 + 59; resident, and two-pass under a lowered cap
+    MfPlan a = mf_plan(40, 1, 1369, 2, 120, 4, 3, 80, 160, mf_resident_cap(-1));
+    EXPECT(a.resident && a.chunk == 1310 && a.nchunks == 2 && a.nlev == 40 * 1369 && a.vstride >= 1310 * 1600 && a.vstride % 16 == 0);
+    EXPECT(a.off[MfPlan::VEC + 1] - a.off[MfPlan::VEC] >= (size_t)2 * a.vstride * 16);
+    EXPECT(check_layout("resident", a) == 0);
+    MfPlan b = mf_plan(40, 1, 1369, 2, 120, 4, 3, 80, 160, mf_resident_cap(1));
+    EXPECT(!b.resident && b.chunk == a.chunk && b.nchunks == a.nchunks && b.G == a.G && b.dm.G == a.dm.G);   // the same partition
+    EXPECT(b.off[MfPlan::VEC + 1] - b.off[MfPlan::VEC] == al256((size_t)b.vstride * 16));
+    EXPECT(check_layout("two-pass", b) == 0);
+    // the cap itself: 2^26 c128 resident, one more point not
+    EXPECT(mf_plan(32, 2, 65536, 1, 32, 0, 1, 32, 32, mf_resident_cap(-1)).resident);
+    EXPECT(!mf_plan(32, 2, 65537, 1, 32, 0, 1, 32, 32, mf_resident_cap(-1)).resident);
+    EXPECT(mf_resident_cap(0) == kMfResidentMax && mf_resident_cap((long long)1 << 40) == kMfResidentMax && mf_resident_cap(5) == 5);
+    // no partition depends on history, max_iter or the number of parameters
+    MfPlan c = mf_plan(40, 1, 1369, 2, 7, 0, 500, 3, 5, mf_resident_cap(-1));
+    EXPECT(c.chunk == a.chunk && c.G == a.G && c.dm.G == a.dm.G && c.dm.P == a.dm.P && c.dm.RT == a.dm.RT);
+    EXPECT(check_layout("small", mf_plan(2, 2, 144, 3, 14, 8, 65536, 8, 20, mf_resident_cap(-1))) == 0);
+    return 0;
+}
+
+int main() {
+    int bad = check_arguments();
+    if (!bad) bad = check_expansion();
+    if (!bad) bad = check_anderson();
+    if (!bad) bad = check_plans();
+    printf(bad ? "mf_plan_check: FAILED\n" : "mf_plan_check: ok\n");
+    return bad ? 1 : 0;
+}

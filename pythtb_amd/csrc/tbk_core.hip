@@ -8,6 +8,7 @@
 #include <chrono>
 #include <map>
 #include <new>
+#include <set>
 #include "tbk_internal.h"
 #include <cmath>
 
@@ -98,6 +99,7 @@ static void knobs_parse() {
     geti("TBK_WILSON_FORM", k.wilson_form);
     geti("TBK_WILSON_MFMA", k.wilson_mfma);
     getl("TBK_WILSON_BATCH_BYTES", k.wilson_batch_bytes);
+    getl("TBK_MF_RESIDENT_MAX", k.mf_resident_max);
     if (const char* e = getenv("TBK_WILSON_ALPHA")) {
         k.wilson_alpha = atof(e);
         k.wilson_alpha_set = true;
@@ -549,7 +551,7 @@ namespace {
 struct FlatModel {
     int n = 0, nslot = 0, pmax = 0, nR = 0, nnz = 0;
     int64_t nterm = 0;
-    std::vector<int32_t> slot_ptr, R4;
+    std::vector<int32_t> slot_ptr, R4, rvec;
     std::vector<cd> amp;
     std::vector<unsigned char> host;
     size_t o_orb = 0, o_amp = 0, o_R = 0, o_ptr = 0, o_ab = 0, o_cell = 0, o_rvec = 0, o_rblk = 0, o_nz = 0, total = 0;
@@ -558,8 +560,9 @@ struct FlatModel {
 
 static int model_flatten(int dim_k, int norb, int nspin, const double* orb, const double* onsite, int64_t nhop,
                          const int32_t* hop_i, const int32_t* hop_j, const int32_t* hop_R, const double* hop_amp,
-                         FlatModel& F) {
+                         FlatModel& F, int64_t npin = 0, const int32_t* pin = nullptr) {
     TBK_REQUIRE(dim_k >= 0 && dim_k <= TBK_MAX_DIM, TBK_EINVAL, "tbk_model_upload: dim_k=%d", dim_k);
+    TBK_REQUIRE(npin == 0 || pin, TBK_EINVAL, "tbk_model_upload: null pin list");
     TBK_REQUIRE(nspin == 1 || nspin == 2, TBK_EINVAL, "tbk_model_upload: nspin=%d", nspin);
     TBK_REQUIRE(norb >= 1, TBK_EINVAL, "tbk_model_upload: norb=%d", norb);
     const int n = norb * nspin;
@@ -621,6 +624,28 @@ static int model_flatten(int dim_k, int norb, int nspin, const double* orb, cons
                 }
             }
     }
+    // pinned keys {a, b, R[4]} (state indices; tbk_mf.hip): terms that keep their place in every table at amplitude zero.  A pin adds
+    // nothing to an amplitude; one on the diagonal (a == b) pins both R and -R, as a hop there fills both
+    std::set<TermKey> pinned;
+    for (int64_t p = 0; p < npin; ++p) {
+        const int32_t* q = pin + 6 * p;
+        TBK_REQUIRE(q[0] >= 0 && q[0] < n && q[1] >= 0 && q[1] < n, TBK_EINVAL, "tbk_model_upload: pin %lld has a state index out of range",
+                    (long long)p);
+        int R[4] = {0, 0, 0, 0}, mR[4] = {0, 0, 0, 0};
+        for (int d = 0; d < dim_k; ++d) {
+            R[d] = q[2 + d];
+            mR[d] = -R[d];
+        }
+        for (int side = 0; side < (q[0] == q[1] ? 2 : 1); ++side) {
+            add(q[0], q[1], side ? mR : R, cd{0.0, 0.0});
+            TermKey key;
+            key.last = last;
+            const bool up = q[0] <= q[1];
+            key.slot = up ? slot_of(n, q[0], q[1]) : slot_of(n, q[1], q[0]);
+            for (int d = 0; d < 4; ++d) key.R[d] = (up ? 1 : -1) * (side ? mR[d] : R[d]);
+            pinned.insert(key);
+        }
+    }
     // CSR over slots (std::map iterates in slot-major order)
     const int nslot = n * (n + 1) / 2;
     std::vector<int32_t>& slot_ptr = F.slot_ptr;
@@ -631,7 +656,7 @@ static int model_flatten(int dim_k, int norb, int nspin, const double* orb, cons
     for (int a = 0; a < n; ++a)
         for (int b = a; b < n; ++b) slot_ab[slot_of(n, a, b)] = a | (b << 16);
     for (auto& kv : acc) {
-        if (kv.second.x == 0.0 && kv.second.y == 0.0) continue;
+        if (kv.second.x == 0.0 && kv.second.y == 0.0 && !(npin && pinned.count(kv.first))) continue;
         slot_ptr[kv.first.slot + 1]++;
         amp.push_back(kv.second);
         for (int d = 0; d < 4; ++d) R4.push_back(kv.first.R[d]);
@@ -657,7 +682,7 @@ static int model_flatten(int dim_k, int norb, int nspin, const double* orb, cons
     // slots -- one phase per R instead of one per term, and coalesced coefficient loads.  Built for
     // the register (n = 5..8) and wavefront (n <= 64) solvers when the blocks are reasonably full
     // (Wannier-type long-ranged tables, dense synthetic models).
-    std::vector<int32_t> rvec;
+    std::vector<int32_t>& rvec = F.rvec;
     std::vector<cd> rblock;
     int nR = 0;
     // the non-empty slots {a | b<<16, t0, t1, 0}: sparse models (ribbons, slabs) have ~3n of n^2/2
@@ -793,13 +818,12 @@ extern "C" int tbk_array_phases_cont(const double* arr, int64_t n0, int nb, int6
     return TBK_OK;
 }
 
-extern "C" int tbk_model_flatten_host(int dim_k, int norb, int nspin, const double* orb, const double* onsite, int64_t nhop,
-                                      const int32_t* hop_i, const int32_t* hop_j, const int32_t* hop_R, const double* hop_amp,
-                                      int64_t term_cap, int64_t* nterm, int32_t* term_slot, int32_t* term_R, double* term_amp,
-                                      int32_t* info) {
+static int flatten_host(int dim_k, int norb, int nspin, const double* orb, const double* onsite, int64_t nhop, const int32_t* hop_i,
+                        const int32_t* hop_j, const int32_t* hop_R, const double* hop_amp, int64_t npin, const int32_t* pin, int64_t term_cap,
+                        int64_t* nterm, int32_t* term_slot, int32_t* term_R, double* term_amp, int32_t* info) {
     TBK_REQUIRE(nterm, TBK_EINVAL, "tbk_model_flatten_host: null nterm");
     FlatModel F;
-    int rc = model_flatten(dim_k, norb, nspin, orb, onsite, nhop, hop_i, hop_j, hop_R, hop_amp, F);
+    int rc = model_flatten(dim_k, norb, nspin, orb, onsite, nhop, hop_i, hop_j, hop_R, hop_amp, F, npin, pin);
     if (rc) return rc;
     *nterm = F.nterm;
     if (info) {
@@ -819,6 +843,21 @@ extern "C" int tbk_model_flatten_host(int dim_k, int norb, int nspin, const doub
     }
     return TBK_OK;
 }
+extern "C" int tbk_model_flatten_host(int dim_k, int norb, int nspin, const double* orb, const double* onsite, int64_t nhop,
+                                      const int32_t* hop_i, const int32_t* hop_j, const int32_t* hop_R, const double* hop_amp,
+                                      int64_t term_cap, int64_t* nterm, int32_t* term_slot, int32_t* term_R, double* term_amp,
+                                      int32_t* info) {
+    return flatten_host(dim_k, norb, nspin, orb, onsite, nhop, hop_i, hop_j, hop_R, hop_amp, 0, nullptr, term_cap, nterm, term_slot, term_R,
+                        term_amp, info);
+}
+// ... with pinned keys pin[npin][6] = {a, b, R[4]} in state indices: terms that survive a zero amplitude (the mean-field driver's slots)
+extern "C" int tbk_model_flatten_host_pinned(int dim_k, int norb, int nspin, const double* orb, const double* onsite, int64_t nhop,
+                                             const int32_t* hop_i, const int32_t* hop_j, const int32_t* hop_R, const double* hop_amp,
+                                             int64_t npin, const int32_t* pin, int64_t term_cap, int64_t* nterm, int32_t* term_slot,
+                                             int32_t* term_R, double* term_amp, int32_t* info) {
+    return flatten_host(dim_k, norb, nspin, orb, onsite, nhop, hop_i, hop_j, hop_R, hop_amp, npin, pin, term_cap, nterm, term_slot, term_R,
+                        term_amp, info);
+}
 
 static int64_t g_model_uploads = 0;
 
@@ -826,11 +865,31 @@ extern "C" int tbk_model_upload(tbk_ctx* ctx, int dim_k, int norb, int nspin, co
                                 const double* onsite, int64_t nhop, const int32_t* hop_i,
                                 const int32_t* hop_j, const int32_t* hop_R, const double* hop_amp,
                                 tbk_model** out) {
+    return tbk_model_upload_pinned(ctx, dim_k, norb, nspin, orb, onsite, nhop, hop_i, hop_j, hop_R, hop_amp, 0, nullptr, out, nullptr);
+}
+// The same upload with pinned keys (tbk_model_flatten_host_pinned); `terms`, where wanted, takes the host's copy of the term list and the
+// places of term_amp and rblock in the blob, for a caller that edits amplitudes on the device (tbk_mf.hip).  No pins: the blob of
+// tbk_model_upload, byte for byte.
+int tbk_model_upload_pinned(tbk_ctx* ctx, int dim_k, int norb, int nspin, const double* orb, const double* onsite, int64_t nhop,
+                            const int32_t* hop_i, const int32_t* hop_j, const int32_t* hop_R, const double* hop_amp, int64_t npin,
+                            const int32_t* pin, tbk_model** out, TbkFlatTerms* terms) {
     TBK_REQUIRE(ctx && out, TBK_EINVAL, "tbk_model_upload: null ctx/out");
     FlatModel F;
     {
-        int rc = model_flatten(dim_k, norb, nspin, orb, onsite, nhop, hop_i, hop_j, hop_R, hop_amp, F);
+        int rc = model_flatten(dim_k, norb, nspin, orb, onsite, nhop, hop_i, hop_j, hop_R, hop_amp, F, npin, pin);
         if (rc) return rc;
+    }
+    if (terms) {
+        terms->n = F.n;
+        terms->nslot = F.nslot;
+        terms->nR = F.nR;
+        terms->nterm = F.nterm;
+        terms->slot_ptr = F.slot_ptr;
+        terms->R4 = F.R4;
+        terms->rvec = F.rvec;
+        terms->amp = F.amp;
+        terms->o_amp = F.o_amp;
+        terms->o_rblk = F.o_rblk;
     }
     const int n = F.n, nslot = F.nslot, pmax = F.pmax, nR = F.nR, nnz = F.nnz;
     const int64_t nterm = F.nterm;

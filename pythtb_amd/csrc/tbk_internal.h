@@ -116,6 +116,7 @@ struct TbkKnobs {
     double wilson_alpha = 0.0;  // TBK_WILSON_ALPHA  test hook: first Cayley angle
     bool wilson_alpha_set = false;
     long long big_batch = -1;   // TBK_BIG_BATCH     test hook: matrices per workspace batch
+    long long mf_resident_max = -1;   // TBK_MF_RESIDENT_MAX  tests: c128 of eigenvectors the mean-field driver keeps resident (default and cap 2^26); below N_k nsta^2 it takes the two-pass form
     int reg_lanes = 0;          // TBK_REG_LANES     (multilane build only)
     int reg_cells = 1;          // TBK_REG_CELLS     0: n = 5..8 meshes sum every lattice vector per point instead of the row's coefficient cells
     int reg_direct = 1;         // TBK_REG_DIRECT    0: n = 5..8 with eigenvectors by the register Jacobi kernel instead of the direct method
@@ -400,6 +401,20 @@ struct tbk_model {
     size_t blob_bytes = 0; // its size (small ones are parked in the context's pool when the model is freed)
     ModelView view{};
 };
+
+// tbk_core.hip: tbk_model_upload with pinned keys pin[npin][6] = {a, b, R[4]} (state indices) -- terms that keep their place in
+// term_amp, cell_ptr, rblock and nz at amplitude zero -- and, where wanted, the host's copy of the flattened term list with the
+// offsets of term_amp and rblock in the blob (tbk_mf.hip edits both on the device).  No pins: tbk_model_upload's blob.
+struct TbkFlatTerms {
+    int n = 0, nslot = 0, nR = 0;
+    int64_t nterm = 0;
+    std::vector<int32_t> slot_ptr, R4, rvec;   // [nslot + 1], [nterm][4], [nR][4]
+    std::vector<cd> amp;                       // [nterm]
+    size_t o_amp = 0, o_rblk = 0;
+};
+int tbk_model_upload_pinned(tbk_ctx* ctx, int dim_k, int norb, int nspin, const double* orb, const double* onsite, int64_t nhop,
+                            const int32_t* hop_i, const int32_t* hop_j, const int32_t* hop_R, const double* hop_amp, int64_t npin,
+                            const int32_t* pin, struct tbk_model** out, TbkFlatTerms* terms);
 
 // Device layout of a wf_array: BAND-MAJOR planes, data[band][point][comp] with
 // point = row-major mesh index.  (The reference / NumPy layout is

@@ -28,8 +28,7 @@
 // The phase e^{-2 pi i k.R} at mesh point (i_a / N_a) is formed from the exact integer (i_a R_a mod N_a).  Nothing uses floating-point
 // atomics and no partition depends on the number of levels, fillings or lattice vectors: two calls give the same bits.
 #include <math.h>
-#include "tbk_occ.h"
-#include "tbk_mesh_phase.h"
+#include "tbk_occ_dev.h"
 
 // ---------------------------------------------------------------- occupation
 // f and, where wanted, the entropy term s = -f ln f - (1 - f) ln(1 - f) of x = (E - mu) / kT (tbk_kubo.h's fermi_terms)
@@ -163,6 +162,28 @@ __global__ __launch_bounds__(64) void k_occ_edges(const double* __restrict__ par
     edges[2 * j] = lower;
     edges[2 * j + 1] = cnt > target[j] ? lower : nxt;
 }
+// The bracket of every filling: every finite double (nothing is occupied at -DBL_MAX and everything at DBL_MAX), and the first midpoint
+__global__ __launch_bounds__(64) void k_occ_arm(const int nfill, uint64_t* __restrict__ lo, uint64_t* __restrict__ hi, double* __restrict__ mu) {
+    const int j = blockIdx.x * 64 + threadIdx.x;
+    if (j >= nfill) return;
+    const uint64_t klo = occ_key(-DBL_MAX), khi = occ_key(DBL_MAX);
+    lo[j] = klo;
+    hi[j] = khi;
+    mu[j] = occ_unkey(klo + (khi - klo) / 2);
+}
+// The Fermi level of every filling, left in device memory: kT > 0 the double of the upper key, kT = 0 the midpoint of the edges
+// (+ 0.0: -0 becomes +0)
+__global__ __launch_bounds__(64) void k_occ_final(const int nfill, const int thermal, const uint64_t* __restrict__ hi,
+                                                  const double* __restrict__ edges, double* __restrict__ mu) {
+    const int j = blockIdx.x * 64 + threadIdx.x;
+    if (j >= nfill) return;
+    if (thermal) {
+        mu[j] = occ_unkey(hi[j]) + 0.0;
+        return;
+    }
+    const double e0 = edges[2 * j] + 0.0, e1 = edges[2 * j + 1] + 0.0;
+    mu[j] = 0.5 * (e0 + e1);
+}
 
 // ---------------------------------------------------------------- density matrix
 // f[b][ik] of a chunk
@@ -170,6 +191,12 @@ __global__ __launch_bounds__(256) void k_dm_weights(const double* __restrict__ e
                                                     double* __restrict__ fw) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i < total) fw[i] = occ_fermi(ev[i], mu, kT, nullptr);
+}
+// ... at the Fermi level the selection left in device memory (the mean-field driver: no round trip between the two stages)
+__global__ __launch_bounds__(256) void k_dm_weights_ptr(const double* __restrict__ ev, const int64_t total, const double* __restrict__ mu,
+                                                        const double kT, double* __restrict__ fw) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < total) fw[i] = occ_fermi(ev[i], mu[0], kT, nullptr);
 }
 
 // Up to 32 states.  Workgroup (k-group g, block of OCC_RB lattice vectors): batches of P points.  A batch's weights, orbital phases and
@@ -314,6 +341,81 @@ __global__ __launch_bounds__(256) void k_dm_tile(const ModelView mv, const doubl
             if (r < nrb) part[((int64_t)g * nr + rb0 + r) * n * n + (int64_t)i * n + j] = acc[r];
 }
 
+// ---------------------------------------------------------------- host side: the two resident stages (tbk_occ_dev.h)
+int occ_fermi_stage(tbk_ctx* ctx, const double* e_dev, int64_t nlev, int G, int nfill, double kT, const OccFermiBufs& B) {
+    const dim3 grid((unsigned)G), fgrid((unsigned)((nfill + 63) / 64));
+    hipLaunchKernelGGL(k_occ_arm, fgrid, dim3(64), 0, ctx->stream, nfill, B.lo, B.hi, B.mu);
+    TBK_HIP(hipGetLastError());
+    for (int step = 0; step < kOccSteps; ++step) {
+        {
+            ProfScope ps(ctx, "occ_count");
+            hipLaunchKernelGGL(k_occ_count<false>, grid, dim3(256), 0, ctx->stream, e_dev, nlev, G, (const double*)B.mu, nfill, kT, B.part);
+            TBK_HIP(hipGetLastError());
+        }
+        ProfScope ps(ctx, "occ_bisect");
+        hipLaunchKernelGGL(k_occ_bisect, dim3((unsigned)nfill), dim3(64), 0, ctx->stream, (const double*)B.part, G, B.target, B.lo, B.hi, B.mu);
+        TBK_HIP(hipGetLastError());
+    }
+    if (kT == 0.0) {                                                // hi is the level e_{c-1} itself; the next one above
+        {
+            ProfScope ps(ctx, "occ_next");
+            hipLaunchKernelGGL(k_occ_count<true>, grid, dim3(256), 0, ctx->stream, e_dev, nlev, G, (const double*)B.hi, nfill, 0.0, B.part);
+            TBK_HIP(hipGetLastError());
+        }
+        ProfScope ps(ctx, "occ_edges");
+        hipLaunchKernelGGL(k_occ_edges, dim3((unsigned)nfill), dim3(64), 0, ctx->stream, (const double*)B.part, G, B.target,
+                           (const uint64_t*)B.hi, B.edges);
+        TBK_HIP(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_occ_final, fgrid, dim3(64), 0, ctx->stream, nfill, kT > 0.0 ? 1 : 0, (const uint64_t*)B.hi, (const double*)B.edges,
+                       B.mu);
+    TBK_HIP(hipGetLastError());
+    return TBK_OK;
+}
+
+int occ_dm_stage(tbk_ctx* ctx, const ModelView& mv, const OccDmPlan& pl, const OccMesh& M, int64_t first, int64_t cnt, const double* kp,
+                 const double* ec, const cd* vc, const double* mu_dev, double mu, double kT, double* fw, const int32_t* R_dev, int nR,
+                 cd* part, cd* acc, int accumulate) {
+    const int n = mv.nsta, dk = mv.dim_k;
+    const int64_t nn = (int64_t)n * n;
+    {
+        ProfScope ps(ctx, "dm_weights");
+        if (mu_dev) hipLaunchKernelGGL(k_dm_weights_ptr, dim3(nblk(cnt * n)), dim3(256), 0, ctx->stream, ec, cnt * n, mu_dev, kT, fw);
+        else hipLaunchKernelGGL(k_dm_weights, dim3(nblk(cnt * n)), dim3(256), 0, ctx->stream, ec, cnt * n, mu, kT, fw);
+        TBK_HIP(hipGetLastError());
+    }
+    for (int r0 = 0; r0 < nR; r0 += pl.RT) {
+        const int nr = std::min(pl.RT, nR - r0);
+        const unsigned nrb = (unsigned)((nr + OCC_RB - 1) / OCC_RB);
+        const int32_t* Rp = R_dev + (int64_t)r0 * dk;
+        if (pl.lds) {
+            ProfScope ps(ctx, "dm_lds");
+            const dim3 grid((unsigned)pl.G, nrb);
+            if (pl.ES == 1)
+                hipLaunchKernelGGL(k_dm_lds<1>, grid, dim3(256), 0, ctx->stream, mv, kp, vc, (const double*)fw, cnt, first, M, pl.P, pl.G, Rp, nr,
+                                   part);
+            else if (pl.ES == 2)
+                hipLaunchKernelGGL(k_dm_lds<2>, grid, dim3(256), 0, ctx->stream, mv, kp, vc, (const double*)fw, cnt, first, M, pl.P, pl.G, Rp, nr,
+                                   part);
+            else
+                hipLaunchKernelGGL(k_dm_lds<4>, grid, dim3(256), 0, ctx->stream, mv, kp, vc, (const double*)fw, cnt, first, M, pl.P, pl.G, Rp, nr,
+                                   part);
+            TBK_HIP(hipGetLastError());
+        } else {
+            ProfScope ps(ctx, "dm_tile");
+            hipLaunchKernelGGL(k_dm_tile, dim3((unsigned)(pl.T * pl.T), (unsigned)pl.G, nrb), dim3(256), 0, ctx->stream, mv, kp, vc,
+                               (const double*)fw, cnt, first, M, pl.T, pl.G, Rp, nr, part);
+            TBK_HIP(hipGetLastError());
+        }
+        ProfScope ps(ctx, "dm_rows");
+        const int64_t nrows = (int64_t)nr * nn * 2;
+        hipLaunchKernelGGL(k_group_rows_lanes, dim3(nblk(nrows)), dim3(256), 0, ctx->stream, (const double*)part, pl.G, nrows, nrows, nrows,
+                           accumulate, (double*)(acc + (int64_t)r0 * nn));
+        TBK_HIP(hipGetLastError());
+    }
+    return TBK_OK;
+}
+
 // ---------------------------------------------------------------- host side
 extern "C" int tbk_thermodynamics_mesh(tbk_model* m, const int32_t* mesh, int nmu, const double* mu, double kT, double* out) {
     const char* fn = "tbk_thermodynamics_mesh";
@@ -403,47 +505,18 @@ extern "C" int tbk_fermi_level_mesh(tbk_model* m, const int32_t* mesh, int nfill
     uint64_t* hi_dev = (uint64_t*)(b + pl.off_hi);
     double* target_dev = (double*)(b + pl.off_target);
     double* edges_dev = (double*)(b + pl.off_edges);
-    // the bracket of every filling: every finite double.  Nothing is occupied at -DBL_MAX and everything at DBL_MAX
-    const uint64_t klo = occ_key(-DBL_MAX), khi = occ_key(DBL_MAX);
-    std::vector<uint64_t> lo((size_t)nfill, klo), hi((size_t)nfill, khi);
-    std::vector<double> mid((size_t)nfill, occ_unkey(klo + (khi - klo) / 2));
     const size_t fb = (size_t)nfill * sizeof(double);
-    TBK_HIP(hipMemcpyAsync(lo_dev, lo.data(), fb, hipMemcpyHostToDevice, ctx->stream));
-    TBK_HIP(hipMemcpyAsync(hi_dev, hi.data(), fb, hipMemcpyHostToDevice, ctx->stream));
-    TBK_HIP(hipMemcpyAsync(mu_dev, mid.data(), fb, hipMemcpyHostToDevice, ctx->stream));
     TBK_HIP(hipMemcpyAsync(target_dev, target.data(), fb, hipMemcpyHostToDevice, ctx->stream));
     rc = tbk_mesh_evals_dev(m, mesh, npts, k_dev, e_dev);               // ONE eigen-solve for every filling and every step
     if (rc) return rc;
-    const dim3 grid((unsigned)pl.G);
-    for (int step = 0; step < kOccSteps; ++step) {
-        {
-            ProfScope ps(ctx, "occ_count");
-            hipLaunchKernelGGL(k_occ_count<false>, grid, dim3(256), 0, ctx->stream, (const double*)e_dev, pl.nlev, pl.G,
-                               (const double*)mu_dev, nfill, kT, part);
-            TBK_HIP(hipGetLastError());
-        }
-        ProfScope ps(ctx, "occ_bisect");
-        hipLaunchKernelGGL(k_occ_bisect, dim3((unsigned)nfill), dim3(64), 0, ctx->stream, (const double*)part, pl.G,
-                           (const double*)target_dev, lo_dev, hi_dev, mu_dev);
-        TBK_HIP(hipGetLastError());
-    }
+    rc = occ_fermi_stage(ctx, e_dev, pl.nlev, pl.G, nfill, kT, OccFermiBufs{part, mu_dev, lo_dev, hi_dev, target_dev, edges_dev});
+    if (rc) return rc;
     if (kT > 0.0) {                                                 // the first double whose occupation reaches the target
+        std::vector<uint64_t> hi((size_t)nfill);
         TBK_HIP(hipMemcpyAsync(hi.data(), hi_dev, fb, hipMemcpyDeviceToHost, ctx->stream));
         TBK_HIP(hipStreamSynchronize(ctx->stream));
         for (int j = 0; j < nfill; ++j) mu_out[j] = occ_unkey(hi[j]) + 0.0;
         return TBK_OK;
-    }
-    {                                                               // kT = 0: hi is the level e_{c-1} itself; the next one above
-        ProfScope ps(ctx, "occ_next");
-        hipLaunchKernelGGL(k_occ_count<true>, grid, dim3(256), 0, ctx->stream, (const double*)e_dev, pl.nlev, pl.G,
-                           (const double*)hi_dev, nfill, 0.0, part);
-        TBK_HIP(hipGetLastError());
-    }
-    {
-        ProfScope ps(ctx, "occ_edges");
-        hipLaunchKernelGGL(k_occ_edges, dim3((unsigned)nfill), dim3(64), 0, ctx->stream, (const double*)part, pl.G,
-                           (const double*)target_dev, (const uint64_t*)hi_dev, edges_dev);
-        TBK_HIP(hipGetLastError());
     }
     std::vector<double> edges((size_t)2 * nfill);
     TBK_HIP(hipMemcpyAsync(edges.data(), edges_dev, 2 * fb, hipMemcpyDeviceToHost, ctx->stream));
@@ -482,43 +555,8 @@ extern "C" int tbk_density_matrix_mesh(tbk_model* m, const int32_t* mesh, double
     TBK_HIP(hipMemcpyAsync(R_dev, R, (size_t)nR * dk * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
     OccMesh M{{1, 1, 1}, dk};
     for (int d = 0; d < dk; ++d) M.N[d] = mesh[d];
-    const int64_t nn = (int64_t)n * n;
     rc = kubo_for_chunks(m, cw, nullptr, mesh, npts, [&](int64_t first, int64_t cnt, const double* kp, const double* ec, const cd* vc) -> int {
-        {
-            ProfScope ps(ctx, "dm_weights");
-            hipLaunchKernelGGL(k_dm_weights, dim3(nblk(cnt * n)), dim3(256), 0, ctx->stream, ec, cnt * n, mu, kT, fw);
-            TBK_HIP(hipGetLastError());
-        }
-        for (int r0 = 0; r0 < nR; r0 += pl.RT) {
-            const int nr = std::min(pl.RT, nR - r0);
-            const unsigned nrb = (unsigned)((nr + OCC_RB - 1) / OCC_RB);
-            const int32_t* Rp = R_dev + (int64_t)r0 * dk;
-            if (pl.lds) {
-                ProfScope ps(ctx, "dm_lds");
-                const dim3 grid((unsigned)pl.G, nrb);
-                if (pl.ES == 1)
-                    hipLaunchKernelGGL(k_dm_lds<1>, grid, dim3(256), 0, ctx->stream, m->view, kp, vc, (const double*)fw, cnt, first, M, pl.P, pl.G,
-                                       Rp, nr, part);
-                else if (pl.ES == 2)
-                    hipLaunchKernelGGL(k_dm_lds<2>, grid, dim3(256), 0, ctx->stream, m->view, kp, vc, (const double*)fw, cnt, first, M, pl.P, pl.G,
-                                       Rp, nr, part);
-                else
-                    hipLaunchKernelGGL(k_dm_lds<4>, grid, dim3(256), 0, ctx->stream, m->view, kp, vc, (const double*)fw, cnt, first, M, pl.P, pl.G,
-                                       Rp, nr, part);
-                TBK_HIP(hipGetLastError());
-            } else {
-                ProfScope ps(ctx, "dm_tile");
-                hipLaunchKernelGGL(k_dm_tile, dim3((unsigned)(pl.T * pl.T), (unsigned)pl.G, nrb), dim3(256), 0, ctx->stream, m->view, kp, vc,
-                                   (const double*)fw, cnt, first, M, pl.T, pl.G, Rp, nr, part);
-                TBK_HIP(hipGetLastError());
-            }
-            ProfScope ps(ctx, "dm_rows");
-            const int64_t nrows = (int64_t)nr * nn * 2;
-            hipLaunchKernelGGL(k_group_rows_lanes, dim3(nblk(nrows)), dim3(256), 0, ctx->stream, (const double*)part, pl.G, nrows, nrows, nrows,
-                               first > 0 ? 1 : 0, (double*)(acc + (int64_t)r0 * nn));
-            TBK_HIP(hipGetLastError());
-        }
-        return TBK_OK;
+        return occ_dm_stage(ctx, m->view, pl, M, first, cnt, kp, ec, vc, nullptr, mu, kT, fw, R_dev, nR, part, acc, first > 0 ? 1 : 0);
     });
     if (rc) return rc;
     const size_t nd = (size_t)pl.acc_cd * 2;

@@ -6,6 +6,7 @@ run unchanged; `_gen_ham`, `_sol_ham`, `solve_all` and `solve_one` execute on th
 MI355X through libtbk (no CPU path).  The model->model transforms live in
 transforms.py, the text report and the sketch plot in report.py / plotting.py.
 """
+import copy
 import ctypes as C
 
 import numpy as np
@@ -232,6 +233,13 @@ def _kpm_evolution_coefficients(z):
     c[1:] *= 2.0
     keep = np.nonzero(np.abs(c) > 1e-17)[0]
     return c[:keep[-1] + 1]
+
+
+class mean_field_result(object):
+    """What `tb_model.mean_field_mesh` returns: model, fermi_level, occupations, spin_density, density, R_list, energy, entropy,
+    free_energy, band_energy, n_electrons, residuals, history, iterations, converged, resident, field (the parameter vector the
+    last iteration produced; `_x` is the one it solved in, which `model` carries and a restart begins from)."""
+    pass
 
 
 class tb_model(object):
@@ -1274,6 +1282,229 @@ class tb_model(object):
         if self._nspin == 2:
             out = out.reshape(nR, self._norb, 2, self._norb, 2)
         return out[0] if single else out
+
+    # ------------------------------------------------------------------ self-consistent Hartree-Fock (extension)
+    def _mf_entries(self, interaction, U):
+        """The state-indexed interaction of `mean_field_mesh`: (ab (nint, 2) int32, R (nint, dim_k) int32, V (nint,) float).
+        Orbital entries act on total densities (all four spin pairs on a spinful model); U adds (o up, o down, R = 0)."""
+        ns, no, dk = self._nspin, self._norb, self._dim_k
+        ab, Rs, Vs = [], [], []
+        if interaction is None and U is None:
+            raise Exception("\n\nmean_field_mesh needs an interaction list, U, or both.")
+        for ent in (interaction if interaction is not None else []):
+            try:
+                V, i, j, R = ent
+                V = float(V)
+            except (TypeError, ValueError):
+                raise Exception("\n\ninteraction must be a list of (V, i, j, R) with real V.")
+            if not np.isfinite(V):
+                raise Exception("\n\ninteraction: V must be finite.")
+            if not (_is_int(i) and _is_int(j)) or i < 0 or i >= no or j < 0 or j >= no:
+                raise Exception("\n\ninteraction: orbital index out of scope.")
+            Rf = np.array(R)
+            if Rf.shape != (self._dim_r,) or Rf.dtype == object or np.any(Rf != np.round(Rf)):
+                raise Exception("\n\ninteraction: R must hold dim_r integers, as in set_hop.")
+            Rp = np.array(Rf, dtype=np.int64)[self._per]
+            if np.any(np.abs(Rp) >= 2 ** 30):
+                raise Exception("\n\ninteraction: every component of R must be below 2**30 in magnitude.")
+            if i == j and not np.any(Rp):
+                if ns == 2:
+                    raise Exception("\n\ninteraction: (i, i, R = 0) on a spinful model: that is U.")
+                raise Exception("\n\ninteraction: (i, i, R = 0) is a self-interaction.")
+            for s in range(ns):
+                for t in range(ns):
+                    ab.append((i * ns + s, j * ns + t))
+                    Rs.append(Rp)
+                    Vs.append(V)
+        if U is not None:
+            if ns != 2:
+                raise Exception("\n\nU needs a spinful model (nspin = 2).")
+            Uv = np.array(U, dtype=float)
+            if Uv.ndim == 0:
+                Uv = np.full(no, float(Uv))
+            if Uv.shape != (no,) or not np.all(np.isfinite(Uv)):
+                raise Exception("\n\nU must be a finite scalar or one value per orbital.")
+            for o in range(no):
+                ab.append((2 * o, 2 * o + 1))
+                Rs.append(np.zeros(dk, dtype=np.int64))
+                Vs.append(float(Uv[o]))
+        if not ab:
+            raise Exception("\n\nmean_field_mesh needs an interaction list, U, or both.")
+        seen = set()
+        for (a, b), R in zip(ab, Rs):
+            k1, k2 = (a, b) + tuple(int(x) for x in R), (b, a) + tuple(int(-x) for x in R)
+            if k1 in seen or k2 in seen:
+                raise Exception("\n\ninteraction: a bond is given once and means the symmetric pair; one was given twice.")
+            seen.add(k1)
+        return (np.ascontiguousarray(ab, dtype=np.int32), np.ascontiguousarray(np.array(Rs).reshape(len(ab), dk), dtype=np.int32),
+                np.ascontiguousarray(Vs, dtype=float))
+
+    def mean_field_mesh(self, mesh_size, interaction=None, n_electrons=None, fermi_level=None, kT=0.0, U=None, start=None, fock=True,
+                        mixing=0.5, history=4, tol=1e-10, max_iter=200, check_every=1):
+        """Extension: unrestricted Hartree-Fock for a density-density interaction, iterated to self-consistency on
+        `k_uniform_mesh(mesh_size)` with the whole loop on the device.
+
+            H_int = 1/2 sum_{a,b,R} V_ab(R) n_{a,0} n_{b,R}        (a, b states; V_ab(R) = V_ba(-R) real, V_aa(0) = 0)
+
+        With D_ij(R) = <c+_{j,R} c_{i,0}> of `density_matrix_mesh`: the on-site energy of state a gets sum_{b,R} V_ab(R) n_b
+        (Hartree) and, with fock=True, the entry (a, b, R) of the hopping table gets -V_ab(R) D_ab(R), its mirror the conjugate
+        (on the Hubbard pair this is the spin-flip element of the on-site block).  interaction: a list of (V, i, j, R) in
+        orbital indices and full-dimension R as in `set_hop`, a bond given once; on a spinful model it couples the total
+        densities.  U: scalar or one value per orbital, U n_up n_down (nspin = 2).  Exactly one of n_electrons (the rules of
+        `fermi_level_mesh`) and fermi_level.  start: None (the field of the non-interacting model at the same filling), an
+        array of occupations `(nsta,)` / `(norb, 2)`, the on-site spin densities `(norb, 2, 2)`, or an earlier result (restart).
+        mixing 0 < alpha <= 1; history 0: x <- x + alpha r; history m in 1..8: Anderson mixing over the last m (x, r) pairs after
+        m linear steps.  tol on max |r| (0: exactly max_iter iterations); the host looks at the residual every check_every
+        iterations and at nothing else.
+
+        Returns a `mean_field_result`: model (a copy of this model with the field of the last iteration added; this model is
+        not edited), fermi_level, occupations `(norb,)` / `(norb, 2)`, spin_density `(norb, 2, 2)` on spinful models,
+        density `(nR, nsta, nsta)` with R_list `(nR, dim_k)`, energy = <H_0> + <H_int> per cell in the Hartree-Fock state,
+        entropy, free_energy, residuals (one per iteration), history (the occupations after every iteration), iterations,
+        converged (False is not an exception).  `density` is D of the last iteration, i.e. of `model` at `fermi_level`.
+        Fixed-order sums: two calls give the same bits, and max_iter = k gives the first k history rows of a longer run."""
+        mesh, nk, kT = self._occ_args("mean_field_mesh", mesh_size, kT)
+        ns, no, dk, n = self._nspin, self._norb, self._dim_k, self._nsta
+        if n > 2048:
+            raise Exception("\n\nmean_field_mesh: at most 2048 states.")
+        if (n_electrons is None) == (fermi_level is None):
+            raise Exception("\n\nmean_field_mesh needs exactly one of n_electrons and fermi_level.")
+        try:
+            filling = float(n_electrons if n_electrons is not None else fermi_level)
+        except (TypeError, ValueError):
+            raise Exception("\n\nn_electrons / fermi_level must be one finite number.")
+        if not np.isfinite(filling):
+            raise Exception("\n\nn_electrons / fermi_level must be finite.")
+        if n_electrons is not None:
+            if kT > 0.0:
+                if not 0.0 < filling < n:
+                    raise Exception("\n\nn_electrons must lie in the open interval (0, %d) at kT > 0." % n)
+            else:
+                c = filling * nk
+                if abs(c - round(c)) > 1e-6:
+                    raise Exception("\n\nn_electrons times the %d mesh points must be an integer at kT = 0." % nk)
+                if round(c) < 1 or round(c) > n * nk - 1:
+                    raise Exception("\n\nn_electrons must select between 1 and %d of the %d levels at kT = 0." % (n * nk - 1, n * nk))
+        if not _is_int(history) or history < 0 or history > 8:
+            raise Exception("\n\nhistory must be an integer in 0..8.")
+        if not _is_int(max_iter) or max_iter < 1 or max_iter > 65536:
+            raise Exception("\n\nmax_iter must be an integer in 1..65536.")
+        if not _is_int(check_every) or check_every < 1:
+            raise Exception("\n\ncheck_every must be an integer >= 1.")
+        mixing, tol = float(mixing), float(tol)
+        if not 0.0 < mixing <= 1.0:
+            raise Exception("\n\nmixing must satisfy 0 < mixing <= 1.")
+        if not (np.isfinite(tol) and tol >= 0.0):
+            raise Exception("\n\ntol must be finite and >= 0.")
+        ab, Rs, Vs = self._mf_entries(interaction, U)
+        nint = len(Vs)
+        fock = bool(fock)
+        # the parameters, as include/tbk.h lays them out
+        touched = sorted(set(ab.reshape(-1).tolist()))
+        occ_par = {a: p for p, a in enumerate(touched)}
+        nocc = len(touched)
+        npar = nocc + (2 * nint if fock else 0)
+        Rl = [tuple([0] * dk)]
+        for R in Rs:
+            if tuple(int(x) for x in R) not in Rl:
+                Rl.append(tuple(int(x) for x in R))
+        nR = len(Rl)
+        if nR > 4096:
+            raise Exception("\n\nmean_field_mesh: at most 4096 distinct lattice vectors.")
+        if nR * n * n > 2 ** 22:
+            raise Exception("\n\nmean_field_mesh: nR * nsta**2 must be at most 2**22.")
+        if npar > 2 ** 20:
+            raise Exception("\n\nmean_field_mesh: at most 2**20 mean-field parameters.")
+        key = (ab.tobytes(), Rs.tobytes(), Vs.tobytes(), fock, n)
+        x0 = None
+        if isinstance(start, mean_field_result):
+            if start._key != key:
+                raise Exception("\n\nstart: the result belongs to another model size, interaction or fock setting.")
+            x0 = np.array(start._x, dtype=float)
+        elif start is not None:
+            st = np.array(start, dtype=complex)
+            x0 = np.zeros(npar)
+            if ns == 2 and st.shape == (no, 2, 2):
+                occ = np.real(np.einsum("oss->os", st)).reshape(n)
+                if fock:
+                    for e in range(nint):
+                        a, b = int(ab[e, 0]), int(ab[e, 1])
+                        if a // 2 == b // 2 and not np.any(Rs[e]):
+                            x0[nocc + 2 * e] = st[a // 2, a % 2, b % 2].real
+                            x0[nocc + 2 * e + 1] = st[a // 2, a % 2, b % 2].imag
+            elif st.size == n and st.shape in ((n,), (no, ns)):
+                occ = np.real(st).reshape(n)
+            else:
+                raise Exception("\n\nstart must be None, occupations of shape (nsta,) or (norb, nspin), spin densities (norb, 2, 2), "
+                                "or an earlier result.")
+            for a in touched:
+                x0[occ_par[a]] = occ[a]
+        if x0 is not None and not np.all(np.isfinite(x0)):
+            raise Exception("\n\nstart must be finite.")
+        orb_per, onsite, hop_i, hop_j, hop_R, hop_amp = self._flat_tables()
+        ctx = _lib.default_context()
+        x_in, x_out, mu = np.zeros(npar), np.zeros(npar), np.zeros(1)
+        dens = np.zeros((nR, n, n), dtype=complex)
+        R_out = np.zeros((nR, dk), dtype=np.int32)
+        energies = np.zeros(5)
+        res_hist, occ_hist = np.zeros(max_iter), np.zeros((max_iter, n))
+        info = np.zeros(5, dtype=np.int32)
+        _lib.check(_lib.lib.tbk_mean_field_mesh(
+            ctx.handle, dk, no, ns, _lib.dptr(orb_per), _lib.dptr(onsite.view(float)), len(hop_i), _lib.iptr(hop_i), _lib.iptr(hop_j),
+            _lib.iptr(hop_R.reshape(-1)) if hop_R.size else None, _lib.dptr(hop_amp.view(float)) if hop_amp.size else None,
+            _lib.iptr(mesh), nint, _lib.iptr(ab.reshape(-1)), _lib.iptr(Rs.reshape(-1)), _lib.dptr(Vs), int(fock),
+            int(n_electrons is not None), filling, kT, 0 if x0 is None else 1, None if x0 is None else _lib.dptr(x0), mixing,
+            int(history), tol, int(max_iter), int(check_every), _lib.dptr(x_in), _lib.dptr(x_out), _lib.dptr(mu),
+            _lib.dptr(dens.view(float)), _lib.iptr(R_out.reshape(-1)), _lib.dptr(energies), _lib.dptr(res_hist), _lib.dptr(occ_hist),
+            _lib.iptr(info)))
+        if int(info[2]) != nR or int(info[3]) != npar:
+            raise Exception("\n\nmean_field_mesh: the library laid out %d lattice vectors and %d parameters, not %d and %d."
+                            % (info[2], info[3], nR, npar))
+        its = int(info[0])
+        res = mean_field_result()
+        res.model = self._mf_model(ab, Rs, Vs, fock, occ_par, nocc, x_in)
+        res.fermi_level = float(mu[0])
+        d0 = dens[0]
+        occ = np.real(np.diagonal(d0)).copy()
+        res.occupations = occ.reshape(no, 2) if ns == 2 else occ
+        res.spin_density = np.array([d0[2 * o:2 * o + 2, 2 * o:2 * o + 2] for o in range(no)]) if ns == 2 else None
+        res.density, res.R_list = dens, R_out
+        res.energy, res.entropy, res.free_energy = float(energies[0]), float(energies[1]), float(energies[2])
+        res.band_energy, res.n_electrons = float(energies[3]), float(energies[4])
+        res.residuals = res_hist[:its].copy()
+        res.history = occ_hist[:its].reshape((its, no, 2) if ns == 2 else (its, n)).copy()
+        res.iterations, res.converged = its, bool(info[1])
+        res.resident = bool(info[4])
+        res.field, res._x, res._key = x_out, x_in, key
+        return res
+
+    def _mf_model(self, ab, Rs, Vs, fock, occ_par, nocc, x):
+        """A copy of this model with the mean field of the parameter vector x added through set_onsite / set_hop(mode="add")."""
+        ns, no, dk = self._nspin, self._norb, self._dim_k
+        m = copy.deepcopy(self)
+        site = np.zeros((no, ns, ns), dtype=complex)
+        hops = {}
+        for e in range(len(Vs)):
+            a, b, V = int(ab[e, 0]), int(ab[e, 1]), float(Vs[e])
+            site[a // ns, a % ns, a % ns] += V * x[occ_par[b]]
+            site[b // ns, b % ns, b % ns] += V * x[occ_par[a]]
+            if not fock:
+                continue
+            amp = -V * (x[nocc + 2 * e] + 1j * x[nocc + 2 * e + 1])
+            if a // ns == b // ns and not np.any(Rs[e]):           # the on-site spin-flip element
+                site[a // ns, a % ns, b % ns] += amp
+                site[a // ns, b % ns, a % ns] += np.conj(amp)
+                continue
+            blk = hops.setdefault((a // ns, b // ns) + tuple(int(r) for r in Rs[e]), np.zeros((ns, ns), dtype=complex))
+            blk[a % ns, b % ns] += amp
+        for o in range(no):
+            if np.any(site[o]):
+                m.set_onsite(site[o] if ns == 2 else float(site[o, 0, 0].real), o, mode="add")
+        for (i, j, *R), blk in hops.items():
+            Rf = np.zeros(self._dim_r, dtype=int)
+            Rf[self._per] = R
+            m.set_hop(blk if ns == 2 else complex(blk[0, 0]), i, j, Rf, mode="add", allow_conjugate_pair=True)
+        return m
 
     # ------------------------------------------------------------------ the lattice Green's function and local impurities (extensions)
     def _gf_args(self, what, mesh_size, omega, eta):
