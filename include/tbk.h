@@ -730,6 +730,32 @@ int tbk_mean_field_mesh(tbk_ctx* ctx, int dim_k, int norb, int nspin, const doub
                         int history, double tol, int max_iter, int check_every, double* x_in, double* x_out, double* mu_out,
                         double* dens, int32_t* R_out, double* energies, double* res_hist, double* occ_hist, int32_t* info);
 
+/* ---- projected and maximally localised Wannier functions on a k mesh ----
+ * nw <= 16 functions from the nb <= 32 bands `bands` (distinct, the same at every k) of k_uniform_mesh(mesh), dim_k 1..3, every
+ * N_a >= 3, nsta <= 2048, N_k nsta nw <= 2^26 (the rotated states stay on the device).
+ *   trial       function w is the sum of its terms term_ptr[w] .. term_ptr[w + 1]: amplitude term_amp[t] (c128) on state term_state[t]
+ *               of cell term_R[t][dim_k]; g~_w(k)[j] = sum amp e^{-2 pi i k.(R + tau_j)}, A(k) = V_bands(k)+ g~(k), U = A (A+ A)^-1/2.
+ *               TBK_EINVAL "trial functions are singular on the bands at k = ..." when the smallest singular value of A over the mesh
+ *               is below 1e-8.
+ *   b-vectors   nbv <= 6 steps bstep[nbv][dim_k] in {-1, 0, 1} (b = sum_a step_a beta_a / N_a; -b is implied), weights bw[nbv] > 0 with
+ *               2 sum_b w_b b b^T = 1, bgram[nbv][nbv] = b.b' in Cartesian coordinates.
+ *   descent     max_iter >= 0 steps of Marzari-Vanderbilt steepest descent at alpha = 1 (0: the projection alone); the host reads the
+ *               change of Omega every check_every iterations (one 8-byte copy) and stops when its modulus is below tol > 0.
+ *   model       t_mn(R) = (1 / N_k) sum_k e^{-2 pi i k.R} [U_tot+ E U_tot]_mn for the nR vectors R[nR][dim_k] (r_user != 0: a list of the
+ *               caller's, nR <= 4096; else at most the N_k vectors of the torus), in the index layout of the hopping table (amp, i, j, R).
+ * Out: hop[nR][nw][nw] c128; sums[21 + 16 * 6] = {Omega_I, Omega_OD, Omega_D, Omega, the nw spreads} from [0], the smallest singular
+ * value at [20], sum_k Im ln M_nn(k, b) as [nw][nbv] from [21] (r_n = -(2 / N_k) sum_b w_b b of it); hist[max_iter + 1]: Omega of the
+ * projection and after every iteration (the first iterations + 1 entries are written); functions_or_null[nR][nsta][nw] c128:
+ * w_n(R, j) = (1 / N_k) sum_k e^{2 pi i k.(R + tau_j)} u~_n(k)[j]; gauge_or_null[N_k][nb][nw] c128: U_tot; info[5] = {iterations, converged,
+ * points per workgroup of the rotation, items per workgroup of the overlaps, k-groups of the spread sums}.
+ * Fixed-order sums, no atomics, a partition that depends on (mesh, nsta, nb, nw, nbv) alone: two calls give the same bits, and
+ * max_iter = m gives the first m + 1 entries of the history of a longer run.                                                        */
+int tbk_wannier_mesh(tbk_model* model, const int32_t* mesh, int nb, const int32_t* bands, int nw, int64_t nterm,
+                     const int32_t* term_ptr, const int32_t* term_state, const int32_t* term_R, const double* term_amp, int nbv,
+                     const int32_t* bstep, const double* bw, const double* bgram, int max_iter, double tol, int check_every, int nR,
+                     int r_user, const int32_t* R, double* hop, double* sums, double* hist, double* functions_or_null,
+                     double* gauge_or_null, int32_t* info);
+
 /* ---- multi-GPU: one process per GPU, k-points sharded, one gather ------
  * Thin RCCL wrappers (librccl is dlopen'ed on first use).  The 128-byte id is
  * created on rank 0 and distributed by the launcher (any out-of-band channel). */

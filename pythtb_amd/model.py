@@ -242,6 +242,12 @@ class mean_field_result(object):
     pass
 
 
+class wannier_result(object):
+    """What `tb_model.wannier_mesh` returns: model, hoppings, R_list, centers, spreads, omega_i, omega_od, omega_d, omega, sv_min,
+    history, iterations, converged, b_vectors, b_weights, and on request functions and gauge."""
+    pass
+
+
 class tb_model(object):
     """Tight-binding model in reduced coordinates (reference: pythtb.py:29-184)."""
 
@@ -1504,6 +1510,273 @@ class tb_model(object):
             Rf = np.zeros(self._dim_r, dtype=int)
             Rf[self._per] = R
             m.set_hop(blk if ns == 2 else complex(blk[0, 0]), i, j, Rf, mode="add", allow_conjugate_pair=True)
+        return m
+
+    # ------------------------------------------------------------------ Wannier functions (extension)
+    def _wannier_bvectors(self, mesh):
+        """The b-vector star of `wannier_mesh` in closed form: (steps (nbv, dim_k) int32 in {-1, 0, 1}, weights (nbv,), b (nbv, dim_r)
+        Cartesian).  With S_ab = N_a N_b (a_a . a_b) / (2 pi)^2: the step +beta_a / N_a with weight S_aa / 2 - sum_{b != a} |S_ab| / 2,
+        and for every pair a < b with S_ab != 0 the diagonal beta_a / N_a + sign(S_ab) beta_b / N_b with weight |S_ab| / 2, so that
+        2 sum_b w_b b b^T is the identity on the span of the periodic lattice vectors (the mirror -b of every step is implied)."""
+        dk = self._dim_k
+        A = self._lat[self._per]                                   # (dim_k, dim_r)
+        gram = A @ A.T
+        N = np.array(mesh, dtype=float)
+        S = gram * np.outer(N, N) / (2.0 * np.pi) ** 2
+        rec = 2.0 * np.pi * np.linalg.solve(gram, A)               # beta_a, rows: beta_a . a_b = 2 pi delta_ab
+        steps, weights = [], []
+        for a in range(dk):
+            w = 0.5 * S[a, a] - 0.5 * sum(abs(S[a, b]) for b in range(dk) if b != a)
+            if not w > 0.0:
+                raise Exception("\n\nwannier_mesh: the mesh is too skewed for the closed-form b-vector star (the weight of the step "
+                                "along axis %d is %.6g); choose mesh sizes that make the steps beta_a / N_a more nearly orthogonal." % (a, w))
+            s = [0] * dk
+            s[a] = 1
+            steps.append(s)
+            weights.append(w)
+        for a in range(dk):
+            for b in range(a + 1, dk):
+                if S[a, b] != 0.0:
+                    s = [0] * dk
+                    s[a], s[b] = 1, (1 if S[a, b] > 0.0 else -1)
+                    steps.append(s)
+                    weights.append(0.5 * abs(S[a, b]))
+        steps = np.ascontiguousarray(steps, dtype=np.int32).reshape(len(weights), dk)
+        bcart = (steps / N[None, :]) @ rec
+        return steps, np.ascontiguousarray(weights, dtype=float), np.ascontiguousarray(bcart)
+
+    def _wannier_torus(self, mesh):
+        """One lattice vector per class of the torus of the mesh: R_a in -floor((N_a - 1) / 2) .. floor(N_a / 2), row-major."""
+        axes = [np.arange(-((int(n) - 1) // 2), int(n) // 2 + 1) for n in mesh]
+        grid = np.meshgrid(*axes, indexing="ij")
+        return np.ascontiguousarray(np.stack([g.reshape(-1) for g in grid], axis=1), dtype=np.int32)
+
+    def _wannier_args(self, mesh_size, trial, bands, max_iter, tol, check_every, R_list):
+        """The checked arguments of `wannier_mesh` in the layout of tbk_wannier_mesh."""
+        if self._dim_k not in (1, 2, 3):
+            raise Exception("\n\nwannier_mesh needs a model with dim_k 1, 2 or 3.")
+        if self._dim_r != self._dim_k:
+            raise Exception("\n\nwannier_mesh needs a model that is periodic in every direction (dim_k == dim_r).")
+        mesh, nk = self._mesh_arg(mesh_size)
+        if np.min(mesh) < 3:
+            raise Exception("\n\nwannier_mesh: every mesh size must be at least 3 (the steps +b and -b must reach different points).")
+        n, dk = self._nsta, self._dim_k
+        if n > 2048:
+            raise Exception("\n\nwannier_mesh: at most 2048 states.")
+        try:
+            sel = np.atleast_1d(np.array(bands)).ravel()
+        except Exception:
+            raise Exception("\n\nbands must be a list of band indices.")
+        if sel.size < 1 or not all(_is_int(b) for b in sel.tolist()):
+            raise Exception("\n\nbands must be a list of band indices.")
+        if sel.size > 32:
+            raise Exception("\n\nwannier_mesh: at most 32 bands.")
+        if np.min(sel) < 0 or np.max(sel) >= n:
+            raise Exception("\n\nbands: index out of range.")
+        if np.unique(sel).size != sel.size:
+            raise Exception("\n\nbands lists a band twice.")
+        sel = np.ascontiguousarray(sel, dtype=np.int32)
+        # the trial functions as term lists
+        terms = []
+        tr = trial
+        as_arr = None
+        try:
+            as_arr = np.array(tr)
+        except Exception:
+            as_arr = None
+        if as_arr is not None and as_arr.dtype != object and as_arr.ndim == 1 and as_arr.size >= 1 \
+                and all(_is_int(s) for s in as_arr.tolist()):
+            for s in as_arr.tolist():
+                terms.append([(1.0 + 0.0j, int(s), np.zeros(dk, dtype=np.int64))])
+        elif as_arr is not None and as_arr.dtype != object and as_arr.ndim == 2 and np.issubdtype(as_arr.dtype, np.number):
+            if as_arr.shape[0] != n or as_arr.shape[1] < 1:
+                raise Exception("\n\ntrial: a matrix of amplitudes must have shape (nsta, nw).")
+            mat = np.array(as_arr, dtype=complex)
+            if not np.all(np.isfinite(mat)):
+                raise Exception("\n\ntrial: amplitudes must be finite.")
+            for w in range(mat.shape[1]):
+                nz = np.nonzero(mat[:, w])[0]
+                if nz.size == 0:
+                    raise Exception("\n\ntrial: function %d is zero." % w)
+                terms.append([(complex(mat[j, w]), int(j), np.zeros(dk, dtype=np.int64)) for j in nz])
+        else:
+            try:
+                for fnc in tr:
+                    lst = []
+                    for amp, s, R in fnc:
+                        amp = complex(amp)
+                        Rf = np.array(R)
+                        if dk == 1 and Rf.ndim == 0:
+                            Rf = Rf.reshape(1)
+                        if Rf.shape != (self._dim_r,) or Rf.dtype == object or np.any(Rf != np.round(Rf)):
+                            raise Exception("\n\ntrial: R must hold dim_r integers, as in set_hop.")
+                        if not _is_int(s):
+                            raise Exception("\n\ntrial: a state index must be an integer.")
+                        lst.append((amp, int(s), np.array(Rf, dtype=np.int64)[self._per]))
+                    if not lst:
+                        raise Exception("\n\ntrial: a function without terms.")
+                    terms.append(lst)
+            except (TypeError, ValueError):
+                raise Exception("\n\ntrial must be a list of state indices, a complex (nsta, nw) matrix, or per function a list of "
+                                "(amp, state, R) terms.")
+        nw = len(terms)
+        if nw < 1:
+            raise Exception("\n\ntrial: at least one function.")
+        if nw > 16:
+            raise Exception("\n\nwannier_mesh: at most 16 trial functions.")
+        if nw > sel.size:
+            raise Exception("\n\nwannier_mesh: more trial functions (%d) than bands (%d)." % (nw, sel.size))
+        tptr, tstate, tR, tamp = [0], [], [], []
+        for lst in terms:
+            for amp, s, R in lst:
+                if s < 0 or s >= n:
+                    raise Exception("\n\ntrial: state index out of range.")
+                if not np.isfinite(amp):
+                    raise Exception("\n\ntrial: amplitudes must be finite.")
+                if np.any(np.abs(R) >= 2 ** 30):
+                    raise Exception("\n\ntrial: every component of R must be below 2**30 in magnitude.")
+                tstate.append(s)
+                tR.append(R)
+                tamp.append(amp)
+            tptr.append(len(tstate))
+        if nk * n * nw > 2 ** 26:
+            raise Exception("\n\nwannier_mesh: N_k * nsta * nw = %d complex numbers stay resident (at most 2**26): coarsen the mesh."
+                            % (nk * n * nw))
+        if not _is_int(max_iter) or max_iter < 0 or max_iter > 65536:
+            raise Exception("\n\nmax_iter must be an integer in 0..65536.")
+        if not _is_int(check_every) or check_every < 1:
+            raise Exception("\n\ncheck_every must be an integer >= 1.")
+        try:
+            tol = float(tol)
+        except (TypeError, ValueError):
+            raise Exception("\n\ntol must be finite and >= 0.")
+        if not (np.isfinite(tol) and tol >= 0.0):
+            raise Exception("\n\ntol must be finite and >= 0.")
+        if R_list is None:
+            R, r_user = self._wannier_torus(mesh), 0
+        else:
+            R, single = self._R_list_arg(R_list)
+            r_user = 1
+        if R.shape[0] * nw * nw > 2 ** 26:
+            raise Exception("\n\nwannier_mesh: nR * nw**2 must be at most 2**26: give an R_list.")
+        steps, weights, bcart = self._wannier_bvectors(mesh)
+        return dict(mesh=mesh, nk=nk, bands=sel, nw=nw, tptr=np.ascontiguousarray(tptr, dtype=np.int32),
+                    tstate=np.ascontiguousarray(tstate, dtype=np.int32),
+                    tR=np.ascontiguousarray(np.array(tR).reshape(len(tstate), dk), dtype=np.int32),
+                    tamp=np.ascontiguousarray(tamp, dtype=complex), max_iter=int(max_iter), tol=tol, check_every=int(check_every),
+                    R=R, r_user=r_user, steps=steps, weights=weights, bcart=bcart)
+
+    def wannier_mesh(self, mesh_size, trial, bands, max_iter=0, tol=0.0, check_every=10, R_list=None, return_functions=False,
+                     return_gauge=False):
+        """Extension: projected and maximally localised Wannier functions of the bands `bands` on `k_uniform_mesh(mesh_size)`
+        (1-, 2- or 3-D, every N_a >= 3), with the whole loop on the device.
+
+        trial: nw <= 16 functions as a list of state indices, a complex `(nsta, nw)` matrix of home-cell amplitudes, or per function
+        a list of `(amp, state, R)` terms with R as in `set_hop` (states of a spinful model are orbital * 2 + spin, the order of
+        `_gen_ham`).  bands: nw <= nb <= 32 distinct band indices, the same at every k.  With the cell-periodic eigenvectors of
+        `solve_all`: g~_n(k)[j] = sum amp e^{-2 pi i k.(R + tau_j)}, A = V_bands+ g~, U = A (A+ A)^-1/2 (Loewdin), u~ = V_bands U.  The
+        call raises when the smallest singular value of A over the mesh is below 1e-8 -- what the band of a Chern insulator does to
+        any trial function.  The overlaps M(k, b) = <u~(k)|u~(k + b)> run over the closed-form b-vector star of
+        `_wannier_bvectors`; centres, the spread Omega = Omega_I + Omega_OD + Omega_D and the steepest-descent step (alpha = 1)
+        are those of Marzari and Vanderbilt, PRB 56, 12847.  max_iter = 0 is the projection alone; otherwise up to max_iter
+        steps, the host reading the change of Omega every check_every steps and stopping when its modulus is below tol > 0.
+
+        Returns a `wannier_result`: model (an ordinary `tb_model` of nw orbitals at the centres with the hoppings
+        t_mn(R) = (1 / N_k) sum_k e^{-2 pi i k.R} [U_tot+ E U_tot]_mn; R over one representative per class of the torus of the
+        mesh, an entry at R_a = N_a / 2 of an even axis split in halves between +-N_a / 2, or over R_list, at most 4096
+        vectors), hoppings `(nR, nw, nw)` with R_list `(nR, dim_k)` (the raw table), centers `(nw, dim_r)` Cartesian, spreads
+        `(nw,)`, omega_i, omega_od, omega_d, omega, sv_min, history (Omega of the projection, then at every check), iterations,
+        converged, b_vectors `(nbv, dim_r)`, b_weights; with return_functions, functions `(nR, nsta, nw)`:
+        w_n(R, j) = (1 / N_k) sum_k e^{2 pi i k.(R + tau_j)} u~_n(k)[j]; with return_gauge, gauge `(N_k, nb, nw)`: U_tot.
+        Fixed-order sums: two calls give the same bits, and max_iter = m gives the first rows of the history of a longer run."""
+        a = self._wannier_args(mesh_size, trial, bands, max_iter, tol, check_every, R_list)
+        mesh, nk, nw, R = a["mesh"], a["nk"], a["nw"], a["R"]
+        n, dk, nb, nR, nbv = self._nsta, self._dim_k, a["bands"].size, a["R"].shape[0], a["weights"].size
+        if return_functions and nR * n * nw > 2 ** 26:
+            raise Exception("\n\nwannier_mesh: the functions take nR * nsta * nw complex numbers (at most 2**26): give an R_list.")
+        bgram = np.ascontiguousarray(a["bcart"] @ a["bcart"].T)
+        hop = np.zeros((nR, nw, nw), dtype=complex)
+        sums = np.zeros(21 + 16 * 6)
+        hist = np.zeros(a["max_iter"] + 1)
+        fns = np.zeros((nR, n, nw), dtype=complex) if return_functions else None
+        gauge = np.zeros((nk, nb, nw), dtype=complex) if return_gauge else None
+        info = np.zeros(5, dtype=np.int32)
+        _lib.check(_lib.lib.tbk_wannier_mesh(
+            self._device_model(), _lib.iptr(mesh), int(nb), _lib.iptr(a["bands"]), int(nw), len(a["tstate"]), _lib.iptr(a["tptr"]),
+            _lib.iptr(a["tstate"]), _lib.iptr(a["tR"].reshape(-1)), _lib.dptr(a["tamp"].view(float)), int(nbv),
+            _lib.iptr(a["steps"].reshape(-1)), _lib.dptr(a["weights"]), _lib.dptr(bgram.reshape(-1)), a["max_iter"], a["tol"],
+            a["check_every"], int(nR), int(a["r_user"]), _lib.iptr(R.reshape(-1)), _lib.dptr(hop.view(float)), _lib.dptr(sums),
+            _lib.dptr(hist), _lib.dptr(fns.view(float)) if return_functions else None,
+            _lib.dptr(gauge.view(float)) if return_gauge else None, _lib.iptr(info)))
+        its = int(info[0])
+        res = wannier_result()
+        res.omega_i, res.omega_od, res.omega_d, res.omega = (float(x) for x in sums[:4])
+        res.spreads = sums[4:4 + nw].copy()
+        res.sv_min = float(sums[20])
+        s1 = sums[21:21 + nw * nbv].reshape(nw, nbv)
+        res.centers = -(2.0 / nk) * (s1 * a["weights"][None, :]) @ a["bcart"]
+        rows = [0] + [it for it in range(1, its + 1) if it % a["check_every"] == 0 or it == its]
+        res.history = hist[rows].copy()
+        res.iterations, res.converged = its, bool(info[1])
+        res.b_vectors, res.b_weights = a["bcart"], a["weights"]
+        res.hoppings, res.R_list = hop, R
+        res.model = self._wannier_model(mesh, hop, R, res.centers, split=not a["r_user"])
+        if return_functions:
+            res.functions = fns
+        if return_gauge:
+            res.gauge = gauge
+        return res
+
+    def _wannier_model(self, mesh, hop, R, centers, split):
+        """The tb_model of the Wannier functions: nw orbitals at the centres (reduced coordinates), on-site terms the real diagonal
+        of t(0), every other entry of the table a hopping.  split: an entry at R_a = N_a / 2 of an even axis goes in halves to
+        +-N_a / 2, so that the table is Hermitian.  A pair (m, n, R) and its mirror (n, m, -R) are stored once, as their mean."""
+        nw, dk = hop.shape[1], self._dim_k
+        red = np.linalg.solve(self._lat.T, np.array(centers, dtype=float).T).T
+        m = tb_model(dk, self._dim_r, self._lat.copy(), red, per=list(self._per), nspin=1)
+        table = {}
+        for r in range(R.shape[0]):
+            Rv = [int(x) for x in R[r]]
+            images = [([], 1.0)]
+            for d in range(dk):
+                if split and mesh[d] % 2 == 0 and Rv[d] == mesh[d] // 2:
+                    images = [(pre + [s * Rv[d]], w * 0.5) for pre, w in images for s in (1, -1)]
+                else:
+                    images = [(pre + [Rv[d]], w) for pre, w in images]
+            for Ri, w in images:
+                key = tuple(Ri)
+                table[key] = table.get(key, 0.0) + w * hop[r]
+        zero = tuple([0] * dk)
+        if zero in table:
+            m.set_onsite([float(table[zero][i, i].real) for i in range(nw)])
+        hops = []
+        for key in sorted(table):
+            neg = tuple(-x for x in key)
+            if key < neg:
+                continue                                           # its mirror carries the pair
+            t = table[key]
+            tm = table.get(neg)
+            for i in range(nw):
+                for j in range(nw):
+                    if key == zero and i >= j:
+                        continue
+                    amp = t[i, j] if tm is None or key == zero else 0.5 * (t[i, j] + np.conj(tm[j, i]))
+                    if key == zero:
+                        amp = 0.5 * (t[i, j] + np.conj(t[j, i]))
+                    Rf = np.zeros(self._dim_r, dtype=int)
+                    Rf[self._per] = key
+                    hops.append([complex(amp), i, j, Rf])
+        for key in sorted(table):                                   # vectors whose mirror is not in a caller's list
+            neg = tuple(-x for x in key)
+            if key < neg and neg not in table:
+                t = table[key]
+                for i in range(nw):
+                    for j in range(nw):
+                        Rf = np.zeros(self._dim_r, dtype=int)
+                        Rf[self._per] = key
+                        hops.append([complex(t[i, j]), i, j, Rf])
+        m._hoppings.extend(hops)
+        m._tbk_epoch += 1
         return m
 
     # ------------------------------------------------------------------ the lattice Green's function and local impurities (extensions)
