@@ -2,7 +2,7 @@
 """Wall times of the Green's-function calls on one device: green_function_mesh for Haldane (n = 2) on a
 256 x 256 mesh, the w90 silicon model (n = 8) on 32 x 32 x 32 and the 4 x 4 Haldane supercell (n = 32) on 64 x 64, each at
 (nw = 256, R = 0), (nw = 16, 9 lattice vectors) and (nw = 1, the same 9 vectors); beside each the time of density_matrix_mesh on
-the same mesh and R list (its kernels are the ones the parent commit has: G at nw = 1 is the same walk with complex weights) and
+the same mesh and R list (both run the lattice sum of tbk_lat_dev.h: G at nw = 1 is the same walk with complex weights) and
 the ratio; then the 64 x 64 impurity LDOS map of Haldane 256 x 256 at 16 frequencies.
 
 Method: every call ends in a device synchronise (it downloads its result), so a host clock around calls is their time.  Each case

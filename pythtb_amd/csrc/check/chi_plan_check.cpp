@@ -7,21 +7,10 @@
 // the sanitizer, where the block is at most 512 MiB).  Then the argument checks: every rule of chi_check, one bad value at a time; and
 // what tbk_kubo.h shares between the mesh sweeps: the eigenvalue-only chunk workspace and the one mesh check.
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <limits>
 #include <vector>
 #include "../tbk_chi.h"
-
-// what the headers' host functions take from the library (this program links no translation unit of it)
-void tbk_set_error(const char*, ...) {}
-int tbk_ctx_scratch(tbk_ctx*, size_t, void**) { return TBK_EHIP; }
-int tbk_k_uniform_mesh_range_dev(tbk_ctx*, int, const int32_t*, int64_t, int64_t, double*) { return TBK_EHIP; }
-int tbk_solve_list_dev_checked(tbk_model*, const double*, int64_t, double*, double*) { return TBK_EHIP; }
-ProfScope::ProfScope(tbk_ctx* c, const char* n) : ctx(c), name(n) {}
-ProfScope::~ProfScope() {}
+#include "check_common.h"
 
 struct Case {
     int n, dk, mesh[3], nq, nw, flags;
@@ -122,16 +111,9 @@ static int check_case(const Case& c) {
     if ((int64_t)p.ntile * kPairTile < c.nw || (p.ntile > 0 && (int64_t)(p.ntile - 1) * kPairTile >= c.nw)) return printf("%s: tiles\n", tag);
     if (p.wide && p.chunk > 65535) return printf("%s: the chunk is beyond the z limit of k_chi_mprod's grid\n", tag);
     // the k-groups of a full chunk and of the last one cover the points once, in order
-    for (int64_t cnt : {p.chunk, npts - (p.nchunks - 1) * p.chunk}) {
-        int64_t at = 0;
-        for (int g = 0; g < p.G; ++g) {
-            const int64_t p0 = (int64_t)g * cnt / p.G, p1 = (int64_t)(g + 1) * cnt / p.G;
-            if (p0 != at || p1 < p0) return printf("%s: group %d of %lld points starts at %lld\n", tag, g, (long long)cnt, (long long)p0);
-            at = p1;
-        }
-        if (at != cnt) return printf("%s: the groups end at %lld of %lld points\n", tag, (long long)at, (long long)cnt);
+    if (check_groups(tag, p.G, npts, p.chunk, p.nchunks)) return 1;
+    for (int64_t cnt : {p.chunk, npts - (p.nchunks - 1) * p.chunk})
         if (p.lds && !p.dynamic && (cnt + p.P - 1) / p.P > p.gmax) return printf("%s: more workgroups than part holds\n", tag);
-    }
     // a q alone is worked through like the same q inside this list
     const ChiPlan one = chi_plan(c.n, c.dk, npts, 1, c.nw, c.flags);
     if (one.chunk != p.chunk || one.G != p.G || one.ntile != p.ntile || one.gmax != p.gmax || one.P != p.P || one.nrows != p.nrows ||

@@ -8,21 +8,10 @@
 // overlapping, the last one ending at the total (each is filled with its own index over a real host block and read back, under the
 // sanitizer, where the block is at most 512 MiB).  Then the argument checks: every rule of chim_check, one bad value at a time.
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <limits>
 #include <vector>
 #include "../tbk_chim.h"
-
-// what the headers' host functions take from the library (this program links no translation unit of it)
-void tbk_set_error(const char*, ...) {}
-int tbk_ctx_scratch(tbk_ctx*, size_t, void**) { return TBK_EHIP; }
-int tbk_k_uniform_mesh_range_dev(tbk_ctx*, int, const int32_t*, int64_t, int64_t, double*) { return TBK_EHIP; }
-int tbk_solve_list_dev_checked(tbk_model*, const double*, int64_t, double*, double*) { return TBK_EHIP; }
-ProfScope::ProfScope(tbk_ctx* c, const char* n) : ctx(c), name(n) {}
-ProfScope::~ProfScope() {}
+#include "check_common.h"
 
 struct Case {
     int n, dk, mesh[3], nq, nw, na, nvq;
@@ -139,15 +128,7 @@ static int check_case(const Case& c) {
     if (p.lane_rows != (p.nrows >= kChimLaneRows)) return printf("%s: the group sum\n", tag);
     // the launches of one lane per item stay inside a grid
     if (p.tables && ((int64_t)p.chunk * c.n * p.nab + 255) / 256 > 0x7fffffffLL) return printf("%s: the tables' grid\n", tag);
-    for (int64_t cnt : {p.chunk, npts - (p.nchunks - 1) * p.chunk}) {
-        int64_t at = 0;
-        for (int g = 0; g < p.G; ++g) {
-            const int64_t p0 = (int64_t)g * cnt / p.G, p1 = (int64_t)(g + 1) * cnt / p.G;
-            if (p0 != at || p1 < p0) return printf("%s: group %d of %lld points starts at %lld\n", tag, g, (long long)cnt, (long long)p0);
-            at = p1;
-        }
-        if (at != cnt) return printf("%s: the groups end at %lld of %lld points\n", tag, (long long)at, (long long)cnt);
-    }
+    if (check_groups(tag, p.G, npts, p.chunk, p.nchunks)) return 1;
     // a q alone is worked through like the same q inside this list
     const ChimPlan one = chim_plan(c.n, c.dk, npts, 1, c.nw, c.na, c.nvq ? 1 : 0);
     if (one.chunk != p.chunk || one.G != p.G || one.ntile != p.ntile || one.neb != p.neb || one.EB != p.EB || one.P != p.P ||

@@ -8,47 +8,13 @@
 // is filled with its own index over a real host block and read back, under the sanitizer, where the block is at most 512 MiB).
 // Then the internal problem of the impurity calls (the reduction modulo the mesh, the de-duplication, the index tables, the union
 // of the states) on cases small enough to enumerate, the 64 x 64 map the caps must admit, and the argument checks: every rule, one
-// bad value at a time.
+// bad value at a time.  It also replays the lane map of the lattice sum (tbk_lat.h: the functions k_lat_lds runs) for 1..32 states
+// and every selection length, under the density matrix's and the Green's function's block sizes.
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <limits>
 #include <vector>
 #include "../tbk_gf.h"
-
-// what the headers' host functions take from the library (this program links no translation unit of it)
-void tbk_set_error(const char*, ...) {}
-int tbk_ctx_scratch(tbk_ctx*, size_t, void**) { return TBK_EHIP; }
-int tbk_k_uniform_mesh_range_dev(tbk_ctx*, int, const int32_t*, int64_t, int64_t, double*) { return TBK_EHIP; }
-int tbk_solve_list_dev_checked(tbk_model*, const double*, int64_t, double*, double*) { return TBK_EHIP; }
-ProfScope::ProfScope(tbk_ctx* c, const char* n) : ctx(c), name(n) {}
-ProfScope::~ProfScope() {}
-
-// (offset, bytes) of the buffers of a scratch block in order: at multiples of 256, none overlapping, the last ending at the total
-static int check_buffers(const char* tag, const size_t (*buf)[2], int nb, size_t total) {
-    size_t end = 256;
-    for (int i = 0; i < nb; ++i) {
-        if (buf[i][0] % 256 || buf[i][0] < end)
-            return printf("%s: buffer %d at offset %zu (the previous one ends at %zu)\n", tag, i, buf[i][0], end);
-        end = buf[i][0] + buf[i][1];
-    }
-    if (end > total || total - end >= 256) return printf("%s: the last buffer ends at %zu, the total is %zu\n", tag, end, total);
-    if (total > ((size_t)512 << 20)) return 0;
-    unsigned char* base = (unsigned char*)aligned_alloc(256, al256(total));
-    if (!base) return printf("%s: no host block of %zu bytes\n", tag, total);
-    int bad = 0;
-    for (int i = 0; i < nb; ++i) memset(base + buf[i][0], i + 1, buf[i][1]);
-    for (int i = 0; i < nb && !bad; ++i)
-        for (size_t j = 0; j < buf[i][1]; j += 61)
-            if (base[buf[i][0] + j] != (unsigned char)(i + 1)) {
-                bad = printf("%s: buffer %d is overwritten at byte %zu\n", tag, i, j);
-                break;
-            }
-    free(base);
-    return bad;
-}
+#include "check_common.h"
 
 // ---------------------------------------------------------------- the plan
 struct Case {
@@ -130,15 +96,7 @@ static int check_case(const Case& c) {
             if (s != 1) return printf("%s: the launch tiles do not cover every (frequency, R) once\n", tag);
     }
     // the k-groups of a full chunk and of the last one cover the points once, in order
-    for (int64_t cnt : {p.chunk, npts - (p.nchunks - 1) * p.chunk}) {
-        int64_t at = 0;
-        for (int g = 0; g < p.G; ++g) {
-            const int64_t p0 = (int64_t)g * cnt / p.G, p1 = (int64_t)(g + 1) * cnt / p.G;
-            if (p0 != at || p1 < p0) return printf("%s: group %d of %lld points starts at %lld\n", tag, g, (long long)cnt, (long long)p0);
-            at = p1;
-        }
-        if (at != cnt) return printf("%s: the groups end at %lld of %lld points\n", tag, (long long)at, (long long)cnt);
-    }
+    if (check_groups(tag, p.G, npts, p.chunk, p.nchunks)) return 1;
     // a frequency, an R, a selection of one state alone is worked through with the same chunk, batch and groups
     const GfPlan one = gf_plan(c.n, c.dk, npts, 1, 1, 1, 0);
     if (one.chunk != p.chunk || one.P != p.P || one.G != p.G || one.cw.bytes() != p.cw.bytes()) return printf("%s: the plan depends on nw, nR or na\n", tag);
@@ -165,6 +123,54 @@ static int check_case(const Case& c) {
     };
     if (lay.tab_ints != (size_t)c.ns + (size_t)c.ns * c.ns + 2 * (size_t)c.nR * c.ns) return printf("%s: the tables\n", tag);
     return check_buffers(tag, buf, (int)(sizeof buf / sizeof buf[0]), p.total);
+}
+
+// ---------------------------------------------------------------- the lane map of k_lat_lds (tbk_lat.h), replayed
+// n states of which na are kept, WB x RB accumulators per entry, weights of wbytes: every share of every entry has one (lane, slot);
+// the shares cover the points of a full and of a ragged batch once; every LDS index the frame forms lies inside its array -- U
+// [OCC_LDS_CD], the weights [OCC_LDS_PN][WB], the orbital phases [OCC_LDS_PN], the lattice phases [64][RB], the selection -- and the
+// share buffer (256 c128, over U) fits
+static int check_lane_map(int n, int na, int WB, int RB, size_t wbytes, size_t lds_max) {
+    char tag[96];
+    snprintf(tag, sizeof tag, "lanes n=%d na=%d WB=%d RB=%d", n, na, WB, RB);
+    const int nab = na * na, ns = n * na, ES = lat_entries_per_lane(nab), P = lat_points(n);
+    const LatLane l0 = lat_lane(ES, nab, 0);
+    if (na > kGfSelMax || 256 * ES < nab || l0.Q < 1 || (ES == 1 && l0.Q * nab > 256) || 256 > OCC_LDS_CD) return printf("%s: ES=%d Q=%d\n", tag, ES, l0.Q);
+    const size_t lds = (size_t)OCC_LDS_CD * sizeof(cd) + (size_t)OCC_LDS_PN * (WB * wbytes + sizeof(cd)) + (size_t)64 * RB * sizeof(cd);
+    if (lds > lds_max) return printf("%s: %zu bytes of LDS\n", tag, lds);
+    if (P < 1 || P > 64 || P * ns > OCC_LDS_CD || P * n > OCC_LDS_PN || (P * n - 1) * WB + WB - 1 >= OCC_LDS_PN * WB || (P - 1) * RB + RB - 1 >= 64 * RB)
+        return printf("%s: a batch of %d points does not fit the LDS\n", tag, P);
+    for (int np : {P, std::max(1, P - 1), 1}) {
+        std::vector<int> own((size_t)nab * np, 0);                 // (entry, point) -> the lanes that take it
+        for (int t = 0; t < 256; ++t) {
+            const LatLane l = lat_lane(ES, nab, t);
+            if (l.Q != l0.Q || (ES == 1 && l.live && l.q * nab + l.el0 != t)) return printf("%s: lane %d\n", tag, t);
+            if (!l.live) continue;
+            for (int s = 0; s < ES; ++s) {
+                const int el = l.el0 + 256 * s;
+                if (el >= nab) continue;
+                int i, j;
+                lat_entry(el, na, i, j);
+                if (i < 0 || i >= na || j < 0 || j >= na || i * na + j != el) return printf("%s: entry %d is (%d, %d)\n", tag, el, i, j);
+                for (int p = l.q; p < np; p += l.Q) {
+                    if (p * ns + (n - 1) * na + std::max(i, j) >= OCC_LDS_CD) return printf("%s: lane %d reads beyond U\n", tag, t);
+                    ++own[(size_t)el * np + p];
+                }
+                if (l.Q > 1 && (l.q * nab + el >= 256 || t != l.q * nab + el)) return printf("%s: the share of lane %d\n", tag, t);
+            }
+        }
+        for (int o : own)
+            if (o != 1) return printf("%s: an (entry, point) of a batch of %d is taken %d times\n", tag, np, o);
+    }
+    return 0;
+}
+static int check_lane_maps() {
+    for (int n = 1; n <= 32; ++n) {
+        if (check_lane_map(n, n, 1, OCC_RB, sizeof(double), 32768)) return 1;     // the density matrix: a fifth of a CU's 160 KiB
+        for (int na = 1; na <= n; ++na)
+            if (check_lane_map(n, na, GF_WB, GF_RB, sizeof(cd), 65536 - kGfSelMax * sizeof(int))) return 1;
+    }
+    return 0;
 }
 
 // ---------------------------------------------------------------- the internal problem of the impurity calls
@@ -337,9 +343,10 @@ int main() {
         bad |= check_case(c) ? 1 : 0;
         ++cases;
     }
+    bad |= check_lane_maps() ? 1 : 0;
     bad |= check_impurity() ? 1 : 0;
     bad |= check_args() ? 1 : 0;
     if (bad) return printf("gf_plan_check: FAILED\n"), 1;
-    printf("gf_plan_check: %d plans, the internal problem of the impurity calls and the argument checks ok\n", cases);
+    printf("gf_plan_check: %d plans, the lane map of the lattice sum for 1..32 states, the internal problem of the impurity calls and the argument checks ok\n", cases);
     return 0;
 }

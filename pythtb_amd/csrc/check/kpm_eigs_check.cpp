@@ -11,23 +11,9 @@
 //      values those of the operator on the span.
 //   5. kpm_eigs_verdict: selection, order, saturation and the NaN residual.
 #include <complex>
-#include <cstdarg>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <vector>
 #include "../tbk_kpm_eigs.h"
-
-static char g_err[512];
-void tbk_set_error(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof g_err, fmt, ap);
-    va_end(ap);
-}
-int tbk_ctx_scratch(tbk_ctx*, size_t, void**) { return TBK_EHIP; }
-ProfScope::ProfScope(tbk_ctx* c, const char* n) : ctx(c), name(n) {}
-ProfScope::~ProfScope() {}
+#include "check_common.h"
 
 typedef std::complex<double> cplx;
 

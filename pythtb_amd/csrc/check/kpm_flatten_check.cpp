@@ -9,23 +9,11 @@
 // only record: every step 0 .. nsteps is reduced exactly once, into dots[step] and from the slot it was written to, and no slot is
 // written again before its reduction.
 #include <complex>
-#include <cstdarg>
-#include <cstdio>
-#include <cstdlib>
 #include <vector>
 #include "../tbk_kpm.h"
+#include "check_common.h"
 
 // what tbk_kpm.hip takes from tbk_core.hip (this program links the one translation unit alone)
-static char g_err[512];
-void tbk_set_error(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof g_err, fmt, ap);
-    va_end(ap);
-}
-int tbk_ctx_scratch(tbk_ctx*, size_t, void**) { return TBK_EHIP; }
-ProfScope::ProfScope(tbk_ctx* c, const char* n) : ctx(c), name(n) {}
-ProfScope::~ProfScope() {}
 
 typedef std::complex<double> cplx;
 

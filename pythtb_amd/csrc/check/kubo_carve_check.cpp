@@ -7,20 +7,11 @@
 // overlap (every buffer is filled with its own index and read back, under the sanitizer).  The lists below are copies of the
 // entries' registrations, written out by hand: the program checks the carver's arithmetic on lists of their shape, not the call
 // sites, and has to follow an entry whose list changes.  A ninth buffer must be refused (KuboCarve::full).
-#include <cstdarg>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <vector>
 #include "../tbk_kubo.h"
+#include "check_common.h"
 
 // what tbk_kubo.h's host functions take from tbk_core.hip (this program links no translation unit of the library)
-void tbk_set_error(const char*, ...) {}
-int tbk_ctx_scratch(tbk_ctx*, size_t, void**) { return TBK_EHIP; }
-int tbk_k_uniform_mesh_range_dev(tbk_ctx*, int, const int32_t*, int64_t, int64_t, double*) { return TBK_EHIP; }
-int tbk_solve_list_dev_checked(tbk_model*, const double*, int64_t, double*, double*) { return TBK_EHIP; }
-ProfScope::ProfScope(tbk_ctx* c, const char* n) : ctx(c), name(n) {}
-ProfScope::~ProfScope() {}
 
 static int g_lists = 0;
 

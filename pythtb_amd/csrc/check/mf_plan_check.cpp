@@ -6,27 +6,10 @@
 // resident and two-pass workspace layouts, filled and read back under the sanitizer.  The pinned flatten itself lives in
 // tbk_core.hip, beside the flatten it extends, and is held by tests/test_mean_field.py through tbk_model_flatten_host_pinned.
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <limits>
 #include <vector>
 #include "../tbk_mf.h"
-
-// what the headers' host functions take from the library (this program links no translation unit of it)
-static char g_err[512];
-void tbk_set_error(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof g_err, fmt, ap);
-    va_end(ap);
-}
-int tbk_ctx_scratch(tbk_ctx*, size_t, void**) { return TBK_EHIP; }
-int tbk_k_uniform_mesh_range_dev(tbk_ctx*, int, const int32_t*, int64_t, int64_t, double*) { return TBK_EHIP; }
-int tbk_solve_list_dev_checked(tbk_model*, const double*, int64_t, double*, double*) { return TBK_EHIP; }
-ProfScope::ProfScope(tbk_ctx* c, const char* n) : ctx(c), name(n) {}
-ProfScope::~ProfScope() {}
+#include "check_common.h"
 
 #define EXPECT(cond)                                                      \
     do {                                                                  \

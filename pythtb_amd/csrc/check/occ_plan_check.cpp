@@ -8,45 +8,10 @@
 // in order, none overlapping, the last one ending at the total; each is filled with its own index over a real host block and read
 // back, under the sanitizer, where the block is at most 512 MiB).  Then the argument checks: every rule, one bad value at a time.
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <limits>
 #include <vector>
 #include "../tbk_occ.h"
-
-// what the headers' host functions take from the library (this program links no translation unit of it)
-void tbk_set_error(const char*, ...) {}
-int tbk_ctx_scratch(tbk_ctx*, size_t, void**) { return TBK_EHIP; }
-int tbk_k_uniform_mesh_range_dev(tbk_ctx*, int, const int32_t*, int64_t, int64_t, double*) { return TBK_EHIP; }
-int tbk_solve_list_dev_checked(tbk_model*, const double*, int64_t, double*, double*) { return TBK_EHIP; }
-ProfScope::ProfScope(tbk_ctx* c, const char* n) : ctx(c), name(n) {}
-ProfScope::~ProfScope() {}
-
-// (offset, bytes) of the buffers of a scratch block in order: at multiples of 256, none overlapping, the last ending at the total
-static int check_buffers(const char* tag, const size_t (*buf)[2], int nb, size_t total) {
-    size_t end = 256;
-    for (int i = 0; i < nb; ++i) {
-        if (buf[i][0] % 256 || buf[i][0] < end)
-            return printf("%s: buffer %d at offset %zu (the previous one ends at %zu)\n", tag, i, buf[i][0], end);
-        end = buf[i][0] + buf[i][1];
-    }
-    if (end > total || total - end >= 256) return printf("%s: the last buffer ends at %zu, the total is %zu\n", tag, end, total);
-    if (total > ((size_t)512 << 20)) return 0;
-    unsigned char* base = (unsigned char*)aligned_alloc(256, al256(total));
-    if (!base) return printf("%s: no host block of %zu bytes\n", tag, total);
-    int bad = 0;
-    for (int i = 0; i < nb; ++i) memset(base + buf[i][0], i + 1, buf[i][1]);
-    for (int i = 0; i < nb && !bad; ++i)
-        for (size_t j = 0; j < buf[i][1]; j += 61)
-            if (base[buf[i][0] + j] != (unsigned char)(i + 1)) {
-                bad = printf("%s: buffer %d is overwritten at byte %zu\n", tag, i, j);
-                break;
-            }
-    free(base);
-    return bad;
-}
+#include "check_common.h"
 
 // ---------------------------------------------------------------- the key and the bisection on it
 static int check_key() {
@@ -128,17 +93,10 @@ static int check_dm_case(const Case& c) {
     } else {
         if (p.T != (c.n + 15) / 16 || (int64_t)p.T * p.T > 2147483647) return printf("%s: T=%d\n", tag, p.T);
     }
-    if ((p.RT + OCC_RB - 1) / OCC_RB > 65535 || p.G > 65535) return printf("%s: the grid\n", tag);
+    // the grid: the k-groups in x, the blocks of lattice vectors (times the tiles) in y
+    if ((int64_t)((p.RT + OCC_RB - 1) / OCC_RB) * (p.lds ? 1 : p.T * p.T) > 65535 || p.G > 65535) return printf("%s: the grid\n", tag);
     // the k-groups of a full chunk and of the last one cover the points once, in order
-    for (int64_t cnt : {p.chunk, npts - (p.nchunks - 1) * p.chunk}) {
-        int64_t at = 0;
-        for (int g = 0; g < p.G; ++g) {
-            const int64_t p0 = (int64_t)g * cnt / p.G, p1 = (int64_t)(g + 1) * cnt / p.G;
-            if (p0 != at || p1 < p0) return printf("%s: group %d of %lld points starts at %lld\n", tag, g, (long long)cnt, (long long)p0);
-            at = p1;
-        }
-        if (at != cnt) return printf("%s: the groups end at %lld of %lld points\n", tag, (long long)at, (long long)cnt);
-    }
+    if (check_groups(tag, p.G, npts, p.chunk, p.nchunks)) return 1;
     // an R alone is worked through like the same R inside this list
     const OccDmPlan one = occ_dm_plan(c.n, c.dk, npts, 1);
     if (one.chunk != p.chunk || one.P != p.P || one.ES != p.ES || one.T != p.T || one.G != p.G || one.RT != p.RT || one.cw.bytes() != p.cw.bytes())

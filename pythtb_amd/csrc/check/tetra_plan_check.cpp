@@ -8,45 +8,17 @@
 // independent of the number of energies); the layout of every scratch block (every buffer at a multiple of 256, in order, none
 // overlapping, the last one ending at the total).  Then the argument checks: every rule, one bad value at a time.
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <limits>
 #include <random>
 #include <vector>
 #include "../tbk_tetra.h"
+#include "check_common.h"
 
-// what the headers' host functions take from the library (this program links no translation unit of it)
-void tbk_set_error(const char*, ...) {}
-int tbk_ctx_scratch(tbk_ctx*, size_t, void**) { return TBK_EHIP; }
-int tbk_k_uniform_mesh_range_dev(tbk_ctx*, int, const int32_t*, int64_t, int64_t, double*) { return TBK_EHIP; }
-int tbk_solve_list_dev_checked(tbk_model*, const double*, int64_t, double*, double*) { return TBK_EHIP; }
-ProfScope::ProfScope(tbk_ctx* c, const char* n) : ctx(c), name(n) {}
-ProfScope::~ProfScope() {}
-
-// (offset, bytes) of the buffers of a scratch block in order: at multiples of 256, none overlapping, the last ending at the total
+// check_common.h's check of a scratch block over a list that grows with the form of the call; blocks up to 256 MiB are filled
 static int check_buffers(const char* tag, const std::vector<std::pair<size_t, size_t>>& buf, size_t total) {
-    size_t end = 256;
-    for (size_t i = 0; i < buf.size(); ++i) {
-        if (buf[i].first % 256 || buf[i].first < end)
-            return printf("%s: buffer %zu at offset %zu (the previous one ends at %zu)\n", tag, i, buf[i].first, end);
-        end = buf[i].first + buf[i].second;
-    }
-    if (end > total || total - end >= 256) return printf("%s: the last buffer ends at %zu, the total is %zu\n", tag, end, total);
-    if (total > ((size_t)256 << 20)) return 0;
-    unsigned char* base = (unsigned char*)aligned_alloc(256, al256(total));
-    if (!base) return printf("%s: no host block of %zu bytes\n", tag, total);
-    int bad = 0;
-    for (size_t i = 0; i < buf.size(); ++i) memset(base + buf[i].first, (int)i + 1, buf[i].second);
-    for (size_t i = 0; i < buf.size() && !bad; ++i)
-        for (size_t j = 0; j < buf[i].second; j += 61)
-            if (base[buf[i].first + j] != (unsigned char)(i + 1)) {
-                bad = printf("%s: buffer %zu is overwritten at byte %zu\n", tag, i, j);
-                break;
-            }
-    free(base);
-    return bad;
+    std::vector<size_t> flat;
+    for (const auto& b : buf) flat.insert(flat.end(), {b.first, b.second});
+    return check_buffers(tag, (const size_t(*)[2])flat.data(), (int)buf.size(), total, (size_t)256 << 20);
 }
 
 // ---------------------------------------------------------------- the cut of a cell

@@ -7,44 +7,10 @@
 // group -1 never) and the layout of the scratch block (every buffer at a multiple of 256, in order, none overlapping, filled and read
 // back under the sanitizer).  Then the group tables and the argument checks: every rule and the edges of the caps, one bad value at a time.
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <limits>
 #include <vector>
 #include "../tbk_unfold.h"
-
-// what the headers' host functions take from the library (this program links no translation unit of it)
-void tbk_set_error(const char*, ...) {}
-int tbk_ctx_scratch(tbk_ctx*, size_t, void**) { return TBK_EHIP; }
-int tbk_k_uniform_mesh_range_dev(tbk_ctx*, int, const int32_t*, int64_t, int64_t, double*) { return TBK_EHIP; }
-int tbk_solve_list_dev_checked(tbk_model*, const double*, int64_t, double*, double*) { return TBK_EHIP; }
-ProfScope::ProfScope(tbk_ctx* c, const char* n) : ctx(c), name(n) {}
-ProfScope::~ProfScope() {}
-
-static int check_buffers(const char* tag, const size_t (*buf)[2], int nb, size_t total) {
-    size_t end = 256;
-    for (int i = 0; i < nb; ++i) {
-        if (buf[i][0] % 256 || buf[i][0] < end)
-            return printf("%s: buffer %d at offset %zu (the previous one ends at %zu)\n", tag, i, buf[i][0], end);
-        end = buf[i][0] + buf[i][1];
-    }
-    if (end > total || total - end >= 256) return printf("%s: the last buffer ends at %zu, the total is %zu\n", tag, end, total);
-    if (total > ((size_t)512 << 20)) return 0;
-    unsigned char* base = (unsigned char*)aligned_alloc(256, al256(total));
-    if (!base) return printf("%s: no host block of %zu bytes\n", tag, total);
-    int bad = 0;
-    for (int i = 0; i < nb; ++i) memset(base + buf[i][0], i + 1, buf[i][1]);
-    for (int i = 0; i < nb && !bad; ++i)
-        for (size_t j = 0; j < buf[i][1]; j += 61)
-            if (base[buf[i][0] + j] != (unsigned char)(i + 1)) {
-                bad = printf("%s: buffer %d is overwritten at byte %zu\n", tag, i, j);
-                break;
-            }
-    free(base);
-    return bad;
-}
+#include "check_common.h"
 
 // the group of state j in the cases of the table: the order make_supercell produces, every 7th state an adatom where `holes`
 static std::vector<int32_t> groups_of(int n, int ng, bool holes) {

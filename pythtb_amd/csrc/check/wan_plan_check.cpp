@@ -5,27 +5,10 @@
 // back under the sanitizer; that no partition depends on max_iter; and the small Hermitian eigen-solver played by one lane: the
 // reconstruction Q diag(lam) Q+ and the orthonormality of Q for diagonal, degenerate, random and rank-one matrices of 1 .. 16 rows.
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <limits>
 #include <vector>
 #include "../tbk_wan.h"
-
-// what the headers' host functions take from the library (this program links no translation unit of it)
-static char g_err[512];
-void tbk_set_error(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof g_err, fmt, ap);
-    va_end(ap);
-}
-int tbk_ctx_scratch(tbk_ctx*, size_t, void**) { return TBK_EHIP; }
-int tbk_k_uniform_mesh_range_dev(tbk_ctx*, int, const int32_t*, int64_t, int64_t, double*) { return TBK_EHIP; }
-int tbk_solve_list_dev_checked(tbk_model*, const double*, int64_t, double*, double*) { return TBK_EHIP; }
-ProfScope::ProfScope(tbk_ctx* c, const char* n) : ctx(c), name(n) {}
-ProfScope::~ProfScope() {}
+#include "check_common.h"
 
 #define EXPECT(cond)                                                      \
     do {                                                                  \

@@ -32,13 +32,6 @@ static int gf_mesh_omega_check(const char* fn, int dk, int n, const int32_t* mes
     TBK_REQUIRE(omega, TBK_EINVAL, "%s: null omega", fn);
     return kubo_omega_check(fn, nw, omega, eta);
 }
-static int gf_R_check(const char* fn, int dk, int nR, const int32_t* R) {
-    TBK_REQUIRE(nR >= 1 && nR <= kOccRMax && R, TBK_EINVAL, "%s: nR=%d (1..%d lattice vectors)", fn, nR, kOccRMax);
-    for (int64_t j = 0; j < (int64_t)nR * dk; ++j)
-        TBK_REQUIRE(R[j] > -kOccRAbsMax && R[j] < kOccRAbsMax, TBK_EINVAL, "%s: lattice vector %lld has a component of 2^30 or more", fn,
-                    (long long)(j / dk));
-    return TBK_OK;
-}
 // nsel = 0 and sel = null: all states (na = n); else 1..kGfSelMax distinct indices in [0, n)
 static int gf_sel_check(const char* fn, int n, int nsel, const int32_t* sel, int& na) {
     if (!sel) {
@@ -57,7 +50,7 @@ static int gf_sel_check(const char* fn, int n, int nsel, const int32_t* sel, int
 static int gf_green_check(const char* fn, int dk, int n, const int32_t* mesh, int nw, const double* omega, double eta, int nR,
                           const int32_t* R, int nsel, const int32_t* sel, int64_t& npts, int& na) {
     int rc = gf_mesh_omega_check(fn, dk, n, mesh, nw, omega, eta, npts);
-    if (!rc) rc = gf_R_check(fn, dk, nR, R);
+    if (!rc) rc = lat_R_check(fn, dk, nR, R);
     if (!rc) rc = gf_sel_check(fn, n, nsel, sel, na);
     if (rc) return rc;
     TBK_REQUIRE((int64_t)nw * nR * na * na <= kGfOutCap, TBK_EINVAL, "%s: nw * nR * na^2 = %lld (at most %lld): split omega or R_list", fn,
@@ -178,14 +171,9 @@ static int gf_impurity_caps(const char* fn, const GfImpurity& g, int nw, int64_t
 }
 
 // ---------------------------------------------------------------- the plan
-struct GfPlan {
-    bool lds = false;
-    int64_t npts = 0, chunk = 0, nchunks = 0;
+// the partition of tbk_lat.h with na states kept and GF_WB x GF_RB (frequency, lattice vector) pairs per workgroup, and
+struct GfPlan : LatPart {
     int na = 0, nab = 0;    // selected states and entries of a block
-    int P = 0;              // points per batch of k_gf_lds (lds)
-    int ES = 0;             // entries per lane of k_gf_lds: 1 up to 256 entries, 2 up to 512, 4 up to 1024
-    int T = 0;              // 16 x 16 tiles per side of the tiled form
-    int G = 0;              // k-groups of a chunk: group g takes the points [g cnt / G, (g + 1) cnt / G) of a chunk of cnt
     int WT = 0, RT = 0;     // frequencies and lattice vectors per launch: part[G][WT][RT][nab] stays under kGfPartCap.  Every R where
                             // a frequency's partials fit, then as many frequencies as fit; else one block of frequencies and RT < nR
     int64_t part_cd = 0, acc_cd = 0;
@@ -196,19 +184,9 @@ struct GfPlan {
 };
 static GfPlan gf_plan(int n, int dk, int64_t npts, int nw, int nR, int na, size_t extra) {
     GfPlan p;
-    const int64_t nn = (int64_t)n * n, nab = (int64_t)na * na;
-    p.lds = n <= 32;
-    p.npts = npts;
+    const int64_t nab = (int64_t)na * na;
+    static_cast<LatPart&>(p) = lat_partition(n, na, npts, GF_WB * GF_RB, kGfPartCap, kGfGroupsMax);
     p.na = na, p.nab = (int)nab;
-    p.chunk = kubo_chunk_len(n, npts);
-    p.nchunks = (npts + p.chunk - 1) / p.chunk;
-    p.P = occ_lds_points(n);
-    p.ES = nab <= 256 ? 1 : (nab <= 512 ? 2 : 4);
-    p.T = (na + 15) / 16;
-    // a group walks about four batches (lds) or eight points (tiled); never more groups than points, nor than the cap on part allows
-    // for one block of frequencies and lattice vectors of the full matrix
-    const int64_t per = p.lds ? 4 * (int64_t)p.P : 8;
-    p.G = (int)std::max<int64_t>(1, std::min<int64_t>({(p.chunk + per - 1) / per, (int64_t)kGfGroupsMax, kGfPartCap / (nn * GF_WB * GF_RB)}));
     const int64_t one = (int64_t)p.G * nR * nab;                  // part of one frequency, every R
     if (one <= kGfPartCap) {
         int64_t wt = kGfPartCap / one;

@@ -11,24 +11,20 @@
 //   dldos[w][r][a] = -(1 / pi) Im sum_{bc} G_{s_a i_b}(R_b - R_r) T_bc G_{i_c s_a}(R_r - R_c)
 //
 // The mesh goes through tbk_kubo.h's chunks (solve with eigenvectors); per chunk and per launch tile of frequencies and lattice vectors
-//   n <= 32  k_gf_lds: a batch of P points in LDS -- the selected components of the eigenvectors, multiplied by the orbital phases
-//            e^{2 pi i k.tau_i} on the way in, and the weights 1 / (z - E_n) of GF_WB frequencies; a lane owns an entry (i, j) (and a
-//            share of the batch's points where na^2 < 256, or ES entries where na^2 > 256), forms P_ij(k, w) once per (point,
-//            frequency) -- one product w_n[i] conj(w_n[j]) per state, shared by the frequencies -- and adds P_ij e^{-2 pi i k.R} for
-//            GF_RB lattice vectors in registers
-//   n > 32   k_gf_tile: 16 x 16 tiles of the selected block of P(k, w), strips of 16 states through LDS, plain VALU
+// the lattice sum of tbk_lat_dev.h -- the walk of the density matrix -- under the weight policy GfWt below:
+//   n <= 32  k_lat_lds: the selected components of a batch's eigenvectors in LDS with the weights 1 / (z - E_n) of GF_WB frequencies; a
+//            lane forms P_ij(k, w) once per (point, frequency) -- one product w_n[i] conj(w_n[j]) per state, shared by the frequencies
+//            -- and adds P_ij e^{-2 pi i k.R} for GF_RB lattice vectors in registers
+//   n > 32   k_lat_tile: 16 x 16 tiles of the selected block of P(k, w), strips of 16 states through LDS, plain VALU
 //            both write part[g][w][R][i][j] for the k-group g of the chunk
 //   k_group_rows_lanes (tbk_kubo.h)  acc[w][R][i][j] (+)= sum_g part, the groups in index order, chunk after chunk in stream order;
 //            the rows of a launch tile of RT < nR lattice vectors are runs of acc, one per frequency
 // then k_gf_scale (acc / N_k), and for the impurity calls k_gf_tmatrix (a wavefront per frequency on tbk_small_solve.h's solver) and
-// k_gf_ldos (a lane per (frequency, probe cell, probe state)).  A selection costs n na^2 per point and frequency.  The phases are
-// those of tbk_mesh_phase.h, formed from exact integers.  A frequency or lattice vector beyond the last of a workgroup's block is
-// skipped by branches that are uniform over the workgroup: every entry goes through the same operations whatever stands beside it.
-// Nothing uses floating-point atomics and no partition depends on the frequencies, lattice vectors or selection: two calls give the
-// same bits.
+// k_gf_ldos (a lane per (frequency, probe cell, probe state)).  A selection costs n na^2 per point and frequency.  Nothing uses
+// floating-point atomics and no partition depends on the frequencies, lattice vectors or selection: two calls give the same bits.
 #include <math.h>
 #include "tbk_gf.h"
-#include "tbk_mesh_phase.h"
+#include "tbk_lat_dev.h"
 #include "tbk_small_solve.h"
 
 // 1 / (w + i eta - e)
@@ -40,226 +36,29 @@ __device__ __forceinline__ cd gf_weight(const double w, const double eta, const 
 // a conj(b), every operation spelled out
 __device__ __forceinline__ cd gf_outer(const cd a, const cd b) { return cd{fma(a.x, b.x, a.y * b.y), fma(a.y, b.x, -(a.x * b.y))}; }
 
-// Up to 32 states.  Workgroup (block of GF_WB frequencies and GF_RB lattice vectors: blockIdx.x; k-group g: blockIdx.y): batches of
-// P points.  A batch's weights, orbital phases and lattice phases are staged first, then the selected components of its eigenvectors
-// as W[p][b][a] = u_b[sel a] e^{2 pi i k.tau_{sel a}}.  Lane mapping as k_dm_lds: na^2 <= 256 -- lane t = q na^2 + (i na + j) takes
-// the points q, q + Q, ... of the batch (Q = 256 / na^2 shares, added in index order through LDS at the end); na^2 > 256 -- lane t
-// takes the entries t, t + 256, ... (ES of them).  Every lane of a wavefront reads the same state b at the same time, W_b[j] at
-// consecutive addresses, W_b[i] and the weights as broadcasts.
-template <int ES>
-__global__ __launch_bounds__(256) void k_gf_lds(const ModelView mv, const double* __restrict__ k, const cd* __restrict__ evec,
-                                                const double* __restrict__ ev, const int64_t nk, const int64_t first, const OccMesh M,
-                                                const int P, const int G, const int32_t* __restrict__ sel, const int na, const int all,
-                                                const double* __restrict__ omega, const int nw, const double eta,
-                                                const int32_t* __restrict__ R, const int nr, cd* __restrict__ part) {
-    __shared__ cd U[OCC_LDS_CD];
-    __shared__ cd gs[OCC_LDS_PN * GF_WB];
-    __shared__ cd eph[OCC_LDS_PN];
-    __shared__ cd phs[64 * GF_RB];
-    __shared__ int ssel[kGfSelMax];
-    const int n = mv.nsta, nab = na * na, ns = n * na, t = threadIdx.x;
-    const int nrb = (nr + GF_RB - 1) / GF_RB;
-    const int wb = blockIdx.x / nrb, w0 = wb * GF_WB, r0 = (blockIdx.x - wb * nrb) * GF_RB;
-    const int nwl = min(GF_WB, nw - w0), nrl = min(GF_RB, nr - r0);   // the block's own frequencies and lattice vectors
-    const int g = blockIdx.y;
-    const int64_t p0 = (int64_t)g * nk / G, p1 = (int64_t)(g + 1) * nk / G;
-    const int Q = ES == 1 ? max(1, 256 / nab) : 1;
-    const int q = ES == 1 ? t / nab : 0;
-    const int el0 = ES == 1 ? t - q * nab : t;
-    const bool live = ES > 1 || q < Q;
-    if (t < na) ssel[t] = sel[t];
-    double om[GF_WB];
-#pragma unroll
-    for (int w = 0; w < GF_WB; ++w) om[w] = omega[min(w0 + w, nw - 1)];
-    cd acc[ES][GF_WB][GF_RB];
-#pragma unroll
-    for (int s = 0; s < ES; ++s)
+// The weight policy of the lattice sum (tbk_lat_dev.h): the complex weights 1 / (z - E_n) of GF_WB frequencies per state, GF_RB lattice
+// vectors per workgroup, a selection of the states.  The product w_n[i] conj(w_n[j]) is formed once per state and shared by the
+// block's frequencies; no weight is skipped.
+struct GfWt {
+    static constexpr int WB = GF_WB, RB = GF_RB, NSEL = kGfSelMax;
+    static constexpr bool GROUP_X = false;   // (the blocks of a launch tile can outnumber the 65 535 of the y axis)
+    static constexpr const char* kLabel[3] = {"gf_lds", "gf_tile", "gf_rows"};
+    typedef cd W;
+    const double* omega;   // the launch tile's frequencies
+    double eta;
+    const int32_t* sel;    // [na], on the device
+    int na, all;           // all: sel = 0 .. n - 1 in order (k_lat_lds then loads through kubo_lds_load)
+    __device__ __forceinline__ double freq(const int w) const { return omega[w]; }
+    __device__ __forceinline__ cd weight(const double om, const double e) const { return gf_weight(om, eta, e); }
+    static __device__ __forceinline__ bool empty(const cd&) { return false; }
+    template <bool FULL>
+    static __device__ __forceinline__ void add(cd (&pij)[GF_WB], const cd a, const cd b, const cd* c, const int nwl) {
+        const cd x = gf_outer(a, b);
 #pragma unroll
         for (int w = 0; w < GF_WB; ++w)
-#pragma unroll
-            for (int r = 0; r < GF_RB; ++r) acc[s][w][r] = cd{0.0, 0.0};
-    __syncthreads();
-    for (int64_t b0 = p0; b0 < p1; b0 += P) {
-        const int np = (int)std::min<int64_t>(P, p1 - b0);
-        for (int e = t; e < np * n; e += 256) {
-            const int p = e / n, b = e - p * n;
-            const double eb = ev[(int64_t)b * nk + b0 + p];
-#pragma unroll
-            for (int w = 0; w < GF_WB; ++w)
-                if (w < nwl) gs[e * GF_WB + w] = gf_weight(om[w], eta, eb);
-        }
-        for (int e = t; e < np * na; e += 256) {
-            const int p = e / na, a = e - p * na;
-            eph[e] = dm_orb_phase(mv, k, b0 + p, ssel[a]);
-        }
-        for (int e = t; e < np * nrl; e += 256) {
-            const int p = e / nrl, r = e - p * nrl;
-            phs[p * GF_RB + r] = dm_phase(M, first + b0 + p, R + (int64_t)(r0 + r) * M.dk);
-        }
-        __syncthreads();
-        if (all) {                                                 // (sel = 0 .. n - 1, in order: the load of k_dm_lds)
-            kubo_lds_load(U, evec, nk, b0, np, n, ns, [&](const int e) {
-                const int p = e / ns, r = e - p * ns, i = r % n;
-                U[e] = cmul_x(U[e], eph[p * n + i]);
-            });
-        } else {
-            for (int e = t; e < np * ns; e += 256) {
-                const int p = e / ns, rr = e - p * ns, b = rr / na, a = rr - b * na;
-                U[e] = cmul_x(evec[((int64_t)b * nk + b0 + p) * n + ssel[a]], eph[p * na + a]);
-            }
-        }
-        __syncthreads();
-        if (live) {
-#pragma unroll
-            for (int s = 0; s < ES; ++s) {
-                const int el = el0 + 256 * s;
-                if (el >= nab) continue;
-                const int i = el / na, j = el - i * na;
-                for (int p = q; p < np; p += Q) {
-                    const cd* W = U + p * ns;
-                    const cd* gp = gs + p * n * GF_WB;
-                    cd pij[GF_WB];
-#pragma unroll
-                    for (int w = 0; w < GF_WB; ++w) pij[w] = cd{0.0, 0.0};
-                    if (nwl == GF_WB) {                            // (a full block: no test in the loop; the same operations)
-                        for (int b = 0; b < n; ++b) {
-                            const cd x = gf_outer(W[b * na + i], W[b * na + j]);   // w[i] conj(w[j]), once for the block's frequencies
-#pragma unroll
-                            for (int w = 0; w < GF_WB; ++w) cfma_x(pij[w], x, gp[b * GF_WB + w]);
-                        }
-                    } else {
-                        for (int b = 0; b < n; ++b) {
-                            const cd x = gf_outer(W[b * na + i], W[b * na + j]);
-#pragma unroll
-                            for (int w = 0; w < GF_WB; ++w)
-                                if (w < nwl) cfma_x(pij[w], x, gp[b * GF_WB + w]);
-                        }
-                    }
-#pragma unroll
-                    for (int w = 0; w < GF_WB; ++w)
-#pragma unroll
-                        for (int r = 0; r < GF_RB; ++r)
-                            if (w < nwl && r < nrl) cfma_x(acc[s][w][r], pij[w], phs[p * GF_RB + r]);
-                }
-            }
-        }
-        __syncthreads();                                           // (the batch is consumed)
+            if (FULL || w < nwl) cfma_x(pij[w], x, c[w]);
     }
-    if (ES == 1 && Q > 1) {                                        // the shares of the points, one (frequency, R) after the other
-        cd* buf = U;
-#pragma unroll
-        for (int w = 0; w < GF_WB; ++w)
-#pragma unroll
-            for (int r = 0; r < GF_RB; ++r) {
-                if (w >= nwl || r >= nrl) continue;                 // (uniform over the workgroup)
-                buf[t] = acc[0][w][r];
-                __syncthreads();
-                if (t < nab) {
-                    cd s = buf[t];
-                    for (int qq = 1; qq < Q; ++qq) s = cadd(s, buf[qq * nab + t]);
-                    part[(((int64_t)g * nw + w0 + w) * nr + r0 + r) * nab + t] = s;
-                }
-                __syncthreads();
-            }
-        return;
-    }
-#pragma unroll
-    for (int s = 0; s < ES; ++s) {
-        const int el = el0 + 256 * s;
-        if (!live || el >= nab) continue;
-#pragma unroll
-        for (int w = 0; w < GF_WB; ++w)
-#pragma unroll
-            for (int r = 0; r < GF_RB; ++r)
-                if (w < nwl && r < nrl) part[(((int64_t)g * nw + w0 + w) * nr + r0 + r) * nab + el] = acc[s][w][r];
-    }
-}
-
-// 33 .. 2048 states.  Workgroup (16 x 16 tile (ti, tj) of the selected block of P(k, w), block of GF_WB frequencies and GF_RB lattice
-// vectors: blockIdx.x; k-group g: blockIdx.y): lane (ty, tx) owns the entry (16 ti + ty, 16 tj + tx) of the selection.  Per point the
-// states go through LDS in strips of 16 (their selected components of the tile's rows and of its columns) with the strip's weights;
-// the orbital phases are applied to the finished P_ij.
-__global__ __launch_bounds__(256) void k_gf_tile(const ModelView mv, const double* __restrict__ k, const cd* __restrict__ evec,
-                                                 const double* __restrict__ ev, const int64_t nk, const int64_t first, const OccMesh M,
-                                                 const int T, const int G, const int32_t* __restrict__ sel, const int na,
-                                                 const double* __restrict__ omega, const int nw, const double eta,
-                                                 const int32_t* __restrict__ R, const int nr, cd* __restrict__ part) {
-    __shared__ cd As[16][16], Bs[16][16], eo[32], phs[GF_RB], gs[16][GF_WB];
-    __shared__ int so[32];
-    const int n = mv.nsta, t = threadIdx.x, tx = t & 15, ty = t >> 4;
-    const int tiles = T * T, blk = blockIdx.x / tiles, tile = blockIdx.x - blk * tiles;
-    const int ti = tile / T, tj = tile - ti * T;
-    const int nrb = (nr + GF_RB - 1) / GF_RB;
-    const int wb = blk / nrb, w0 = wb * GF_WB, r0 = (blk - wb * nrb) * GF_RB;
-    const int nwl = min(GF_WB, nw - w0), nrl = min(GF_RB, nr - r0);   // the block's own frequencies and lattice vectors
-    const int i = ti * 16 + ty, j = tj * 16 + tx;
-    const int g = blockIdx.y;
-    const int64_t p0 = (int64_t)g * nk / G, p1 = (int64_t)(g + 1) * nk / G;
-    if (t < 32) {
-        const int pos = t < 16 ? ti * 16 + t : tj * 16 + t - 16;
-        so[t] = pos < na ? sel[pos] : -1;
-    }
-    const double omt = omega[min(w0 + (t & (GF_WB - 1)), nw - 1)];  // (the frequency this lane stages the weights of)
-    cd acc[GF_WB][GF_RB];
-#pragma unroll
-    for (int w = 0; w < GF_WB; ++w)
-#pragma unroll
-        for (int r = 0; r < GF_RB; ++r) acc[w][r] = cd{0.0, 0.0};
-    __syncthreads();
-    for (int64_t ik = p0; ik < p1; ++ik) {
-        if (t < 32) {
-            eo[t] = so[t] >= 0 ? dm_orb_phase(mv, k, ik, so[t]) : cd{0.0, 0.0};
-        } else if (t < 32 + nrl) {
-            phs[t - 32] = dm_phase(M, first + ik, R + (int64_t)(r0 + t - 32) * M.dk);
-        }
-        cd pij[GF_WB];
-#pragma unroll
-        for (int w = 0; w < GF_WB; ++w) pij[w] = cd{0.0, 0.0};
-        for (int b0 = 0; b0 < n; b0 += 16) {
-            __syncthreads();                                       // (the previous strip is consumed; eo and phs are staged)
-            if (t < 16 * GF_WB) {
-                const int bb = t / GF_WB;
-                gs[bb][t & (GF_WB - 1)] = b0 + bb < n ? gf_weight(omt, eta, ev[(int64_t)(b0 + bb) * nk + ik]) : cd{0.0, 0.0};
-            }
-            const int b = b0 + ty;
-            const cd* u = evec + ((int64_t)(b < n ? b : 0) * nk + ik) * n;
-            As[ty][tx] = (b < n && so[tx] >= 0) ? u[so[tx]] : cd{0.0, 0.0};
-            Bs[ty][tx] = (b < n && so[16 + tx] >= 0) ? u[so[16 + tx]] : cd{0.0, 0.0};
-            __syncthreads();
-            if (nwl == GF_WB) {                                    // (a full block: no test in the loop; the same operations)
-#pragma unroll
-                for (int bb = 0; bb < 16; ++bb) {
-                    const cd x = gf_outer(As[bb][ty], Bs[bb][tx]);
-#pragma unroll
-                    for (int w = 0; w < GF_WB; ++w) cfma_x(pij[w], x, gs[bb][w]);
-                }
-            } else {
-#pragma unroll
-                for (int bb = 0; bb < 16; ++bb) {
-                    const cd x = gf_outer(As[bb][ty], Bs[bb][tx]);
-#pragma unroll
-                    for (int w = 0; w < GF_WB; ++w)
-                        if (w < nwl) cfma_x(pij[w], x, gs[bb][w]);
-                }
-            }
-        }
-#pragma unroll
-        for (int w = 0; w < GF_WB; ++w) {
-            if (w >= nwl) continue;
-            const cd pw = cmul_x(cmul_x(pij[w], eo[ty]), cconj(eo[16 + tx]));
-#pragma unroll
-            for (int r = 0; r < GF_RB; ++r)
-                if (r < nrl) cfma_x(acc[w][r], pw, phs[r]);
-        }
-        __syncthreads();                                           // (eo and phs are read)
-    }
-    if (i < na && j < na)
-#pragma unroll
-        for (int w = 0; w < GF_WB; ++w)
-#pragma unroll
-            for (int r = 0; r < GF_RB; ++r)
-                if (w < nwl && r < nrl) part[(((int64_t)g * nw + w0 + w) * nr + r0 + r) * na * na + (int64_t)i * na + j] = acc[w][r];
-}
+};
 
 // acc / N_k, one lane per double
 __global__ __launch_bounds__(256) void k_gf_scale(double* __restrict__ acc, const int64_t nd, const double nk) {
@@ -368,43 +167,17 @@ static int gf_run(tbk_model* m, const int32_t* mesh, const GfPlan& pl, unsigned 
     TBK_HIP(hipStreamSynchronize(ctx->stream));                     // (the host arrays may be the caller's temporaries)
     OccMesh M{{1, 1, 1}, dk};
     for (int d = 0; d < dk; ++d) M.N[d] = mesh[d];
-    int all = na == m->nsta ? 1 : 0;                               // every state in order: k_gf_lds loads through kubo_lds_load
+    int all = na == m->nsta ? 1 : 0;                               // every state in order
     for (int a = 0; a < na && all; ++a) all = sel[a] == a;
     int rc = kubo_for_chunks(m, cw, nullptr, mesh, npts, [&](int64_t first, int64_t cnt, const double* kp, const double* ec, const cd* vc) -> int {
-        for (int w0 = 0; w0 < nw; w0 += pl.WT) {
-            const int wt = std::min(pl.WT, nw - w0);
+        const LatChunk c{m->view, kp, vc, ec, cnt, first, M};
+        for (int w0 = 0; w0 < nw; w0 += pl.WT)
             for (int r0 = 0; r0 < nR; r0 += pl.RT) {
-                const int rt = std::min(pl.RT, nR - r0);
-                const int64_t nblk_wr = (int64_t)((wt + GF_WB - 1) / GF_WB) * ((rt + GF_RB - 1) / GF_RB);
-                const double* omp = om_dev + w0;
-                const int32_t* Rp = R_dev + (int64_t)r0 * dk;
-                if (pl.lds) {
-                    ProfScope ps(ctx, "gf_lds");
-                    const dim3 grid((unsigned)nblk_wr, (unsigned)pl.G);
-                    if (pl.ES == 1)
-                        hipLaunchKernelGGL(k_gf_lds<1>, grid, dim3(256), 0, ctx->stream, m->view, kp, vc, ec, cnt, first, M, pl.P, pl.G,
-                                           (const int32_t*)sel_dev, na, all, omp, wt, eta, Rp, rt, part);
-                    else if (pl.ES == 2)
-                        hipLaunchKernelGGL(k_gf_lds<2>, grid, dim3(256), 0, ctx->stream, m->view, kp, vc, ec, cnt, first, M, pl.P, pl.G,
-                                           (const int32_t*)sel_dev, na, all, omp, wt, eta, Rp, rt, part);
-                    else
-                        hipLaunchKernelGGL(k_gf_lds<4>, grid, dim3(256), 0, ctx->stream, m->view, kp, vc, ec, cnt, first, M, pl.P, pl.G,
-                                           (const int32_t*)sel_dev, na, all, omp, wt, eta, Rp, rt, part);
-                    TBK_HIP(hipGetLastError());
-                } else {
-                    ProfScope ps(ctx, "gf_tile");
-                    hipLaunchKernelGGL(k_gf_tile, dim3((unsigned)(nblk_wr * pl.T * pl.T), (unsigned)pl.G), dim3(256), 0, ctx->stream, m->view, kp,
-                                       vc, ec, cnt, first, M, pl.T, pl.G, (const int32_t*)sel_dev, na, omp, wt, eta, Rp, rt, part);
-                    TBK_HIP(hipGetLastError());
-                }
-                ProfScope ps(ctx, "gf_rows");
-                const int64_t nrow = (int64_t)rt * nab * 2;
-                const int64_t run = rt == nR ? wt * nrow : nrow;    // (every R: the tile is one run of acc)
-                hipLaunchKernelGGL(k_group_rows_lanes, dim3(nblk(wt * nrow)), dim3(256), 0, ctx->stream, (const double*)part, pl.G, wt * nrow,
-                                   run, (int64_t)nR * nab * 2, first > 0 ? 1 : 0, (double*)(acc + ((int64_t)w0 * nR + r0) * nab));
-                TBK_HIP(hipGetLastError());
+                const int rc = lat_launch(ctx, pl, c, GfWt{om_dev + w0, eta, sel_dev, na, all}, na, std::min(pl.WT, nw - w0),
+                                          R_dev + (int64_t)r0 * dk, std::min(pl.RT, nR - r0), nR, part, acc + ((int64_t)w0 * nR + r0) * nab,
+                                          first > 0 ? 1 : 0);
+                if (rc) return rc;
             }
-        }
         return TBK_OK;
     });
     if (rc) return rc;
@@ -454,7 +227,7 @@ static int gf_impurity(const char* fn, tbk_model* m, const int32_t* mesh, int no
     const bool want_ldos = ldos0 != nullptr;
     std::vector<int32_t> all;
     if (want_ldos) {
-        rc = gf_R_check(fn, dk, nprobe, Rp);
+        rc = lat_R_check(fn, dk, nprobe, Rp);
         int na_probe = 0;
         if (!rc) rc = gf_sel_check(fn, n, np, probe, na_probe);
         if (rc) return rc;

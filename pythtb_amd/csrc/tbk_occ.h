@@ -9,19 +9,15 @@
 // inside a longer list.
 #pragma once
 #include <cfloat>
-#include "tbk_kubo.h"
+#include "tbk_lat.h"
 
-#define OCC_LDS_CD 1408                                  // c128 of eigenvectors in LDS per workgroup of k_dm_lds (22 KiB of its 32)
-#define OCC_LDS_PN 256                                   // (point, state) pairs of a batch at most: their weights and orbital phases
 #define OCC_RB 4                                         // lattice vectors per workgroup of the density-matrix kernels
 static const int kOccFillMax = 64;                       // fillings of one tbk_fermi_level_mesh call
-static const int kOccRMax = 4096;                        // lattice vectors of one tbk_density_matrix_mesh call
 static const int64_t kOccOutCap = (int64_t)1 << 22;      // nR nsta^2 at most (64 MiB of c128)
 static const int64_t kOccPartCap = (int64_t)1 << 22;     // c128 of group partials per launch (64 MiB)
 static const int kOccGroupsMax = 512;                    // k-groups of a chunk of the density matrix
 static const int kOccScanGroupsMax = 1024;               // groups of a level scan
 static const int kOccSteps = 64;                         // bisection steps on the 64-bit key: the bracket ends on neighbouring doubles
-static const int32_t kOccRAbsMax = (int32_t)1 << 30;     // |R_a| below this
 
 // ---------------------------------------------------------------- the ordered key of a double
 // key(a) < key(b) exactly when a < b for finite doubles (-0 sorts just below +0): the bit pattern with the sign bit flipped for
@@ -88,12 +84,10 @@ static int occ_dm_check(const char* fn, int dk, int n, const int32_t* mesh, doub
     TBK_REQUIRE(std::isfinite(mu), TBK_EINVAL, "%s: the Fermi level must be finite", fn);
     rc = kubo_kt_check(fn, kT, false);
     if (rc) return rc;
-    TBK_REQUIRE(nR >= 1 && nR <= kOccRMax && R, TBK_EINVAL, "%s: nR=%d (1..%d lattice vectors)", fn, nR, kOccRMax);
+    rc = lat_R_check(fn, dk, nR, R);
+    if (rc) return rc;
     TBK_REQUIRE((int64_t)nR * n * n <= kOccOutCap, TBK_EINVAL, "%s: nR * nsta^2 = %lld (at most %lld)", fn, (long long)nR * n * n,
                 (long long)kOccOutCap);
-    for (int64_t j = 0; j < (int64_t)nR * dk; ++j)
-        TBK_REQUIRE(R[j] > -kOccRAbsMax && R[j] < kOccRAbsMax, TBK_EINVAL, "%s: lattice vector %lld has a component of 2^30 or more", fn,
-                    (long long)(j / dk));
     return TBK_OK;
 }
 
@@ -140,16 +134,8 @@ static OccScanPlan occ_scan_plan(int n, int dk, int64_t npts, int nmu, bool ther
 }
 
 // ---------------------------------------------------------------- the density matrix
-// points per batch of k_dm_lds: their eigenvectors in LDS, and at most OCC_LDS_PN (point, state) pairs
-static inline int occ_lds_points(int n) { return std::max(1, std::min({64, OCC_LDS_CD / (n * n), OCC_LDS_PN / n})); }
-
-struct OccDmPlan {
-    bool lds = false;
-    int64_t npts = 0, chunk = 0, nchunks = 0;
-    int P = 0;              // points per batch of k_dm_lds (lds)
-    int ES = 0;             // elements of P(k) per lane of k_dm_lds: 1 up to 16 states, 2 up to 22, 4 up to 32
-    int T = 0;              // 16 x 16 tiles per side of the tiled form (not lds)
-    int G = 0;              // k-groups of a chunk: group g takes the points [g cnt / G, (g + 1) cnt / G) of a chunk of cnt
+// the partition of tbk_lat.h with every state kept and OCC_RB lattice vectors per workgroup, and
+struct OccDmPlan : LatPart {
     int RT = 0;             // lattice vectors per launch: part[G][RT][n^2] stays under kOccPartCap
     int64_t part_cd = 0, acc_cd = 0;
     // the scratch block: 256 leading bytes, the R list (int32), acc[nR][n^2], part[G][RT][n^2], then the chunk workspace, whose first
@@ -160,16 +146,7 @@ struct OccDmPlan {
 static OccDmPlan occ_dm_plan(int n, int dk, int64_t npts, int nR) {
     OccDmPlan p;
     const int64_t nn = (int64_t)n * n;
-    p.lds = n <= 32;
-    p.npts = npts;
-    p.chunk = kubo_chunk_len(n, npts);
-    p.nchunks = (npts + p.chunk - 1) / p.chunk;
-    p.P = occ_lds_points(n);
-    p.ES = nn <= 256 ? 1 : (nn <= 512 ? 2 : 4);
-    p.T = (n + 15) / 16;
-    // a group walks about four batches (lds) or eight points (tiled); never more groups than points, nor than the cap on part allows
-    const int64_t per = p.lds ? 4 * (int64_t)p.P : 8;
-    p.G = (int)std::max<int64_t>(1, std::min<int64_t>({(p.chunk + per - 1) / per, (int64_t)kOccGroupsMax, kOccPartCap / (nn * OCC_RB)}));
+    static_cast<LatPart&>(p) = lat_partition(n, n, npts, OCC_RB, kOccPartCap, kOccGroupsMax);
     int64_t rt = std::max<int64_t>(1, kOccPartCap / (p.G * nn));
     if (rt >= OCC_RB) rt -= rt % OCC_RB;
     p.RT = (int)std::min<int64_t>(rt, kOccRMax);

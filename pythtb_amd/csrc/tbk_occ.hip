@@ -18,10 +18,11 @@
 //
 // tbk_density_matrix_mesh goes through the mesh in tbk_kubo.h's chunks (solve with eigenvectors), per chunk
 //   k_dm_weights   f[n][cnt], once per (point, state)
-//   n <= 32  k_dm_lds: a batch of P points' eigenvectors in LDS, multiplied by the orbital phases e^{2 pi i k.tau_i} on the way in; a lane
+// then the lattice sum of tbk_lat_dev.h under the weight policy DmWt below:
+//   n <= 32  k_lat_lds: a batch of P points' eigenvectors in LDS, multiplied by the orbital phases e^{2 pi i k.tau_i} on the way in; a lane
 //            owns an element (i, j) (and a share of the batch's points where n^2 < 256, or ES elements where n^2 > 256), forms
 //            P_ij(k) = sum_n f_n w_n[i] conj(w_n[j]) skipping f_n = 0, and adds P_ij e^{-2 pi i k.R} for OCC_RB lattice vectors in registers
-//   n > 32   k_dm_tile: 16 x 16 tiles of P(k), strips of 16 states through LDS, plain VALU
+//   n > 32   k_lat_tile: 16 x 16 tiles of P(k), strips of 16 states through LDS, plain VALU
 //            both write part[g][R][i][j] for the k-group g of the chunk
 //   k_group_rows_lanes (tbk_kubo.h)  acc[R][i][j] (+)= sum_g part[g][R][i][j], the groups in index order, chunk after chunk in
 //            stream order
@@ -199,147 +200,22 @@ __global__ __launch_bounds__(256) void k_dm_weights_ptr(const double* __restrict
     if (i < total) fw[i] = occ_fermi(ev[i], mu[0], kT, nullptr);
 }
 
-// Up to 32 states.  Workgroup (k-group g, block of OCC_RB lattice vectors): batches of P points.  A batch's weights, orbital phases and
-// lattice phases are staged first, then its eigenvectors come in through kubo_lds_load as w_n[i] = u_n[i] e^{2 pi i k.tau_i}.  Lane
-// mapping: n^2 <= 256 -- lane t = q n^2 + (i n + j) takes the points q, q + Q, ... of the batch (Q = 256 / n^2 shares, added in index
-// order through LDS at the end); n^2 > 256 -- lane t takes the elements t, t + 256, ... (ES of them).  Every lane of a wavefront reads
-// the same state b at the same time, w_b[j] at consecutive addresses and w_b[i] as a broadcast: no bank conflict at n = 16 or 32 (the
-// 16-way conflict of k_chi_pairs comes from lanes on different rows).
-template <int ES>
-__global__ __launch_bounds__(256) void k_dm_lds(const ModelView mv, const double* __restrict__ k, const cd* __restrict__ evec,
-                                                const double* __restrict__ fw, const int64_t nk, const int64_t first, const OccMesh M,
-                                                const int P, const int G, const int32_t* __restrict__ R, const int nr, cd* __restrict__ part) {
-    __shared__ cd U[OCC_LDS_CD];
-    __shared__ cd eph[OCC_LDS_PN];
-    __shared__ cd phs[64 * OCC_RB];
-    __shared__ double fs[OCC_LDS_PN];
-    const int n = mv.nsta, nn = n * n, t = threadIdx.x;
-    const int g = blockIdx.x, rb0 = blockIdx.y * OCC_RB, nrb = min(OCC_RB, nr - rb0);
-    const int64_t p0 = (int64_t)g * nk / G, p1 = (int64_t)(g + 1) * nk / G;
-    const int Q = ES == 1 ? max(1, 256 / nn) : 1;
-    const int q = ES == 1 ? t / nn : 0;
-    const int el0 = ES == 1 ? t - q * nn : t;
-    const bool live = ES > 1 || q < Q;
-    cd acc[ES][OCC_RB];
-#pragma unroll
-    for (int s = 0; s < ES; ++s)
-#pragma unroll
-        for (int r = 0; r < OCC_RB; ++r) acc[s][r] = cd{0.0, 0.0};
-    for (int64_t b0 = p0; b0 < p1; b0 += P) {
-        const int np = (int)std::min<int64_t>(P, p1 - b0);
-        for (int e = t; e < np * n; e += 256) {
-            const int p = e / n, b = e - p * n;
-            fs[e] = fw[(int64_t)b * nk + b0 + p];
-            eph[e] = dm_orb_phase(mv, k, b0 + p, b);
-        }
-        for (int e = t; e < np * nrb; e += 256) {
-            const int p = e / nrb, r = e - p * nrb;
-            phs[p * OCC_RB + r] = dm_phase(M, first + b0 + p, R + (int64_t)(rb0 + r) * M.dk);
-        }
-        __syncthreads();
-        kubo_lds_load(U, evec, nk, b0, np, n, nn, [&](const int e) {
-            const int p = e / nn, r = e - p * nn, i = r % n;
-            U[e] = cmul_x(U[e], eph[p * n + i]);
-        });
-        __syncthreads();
-        if (live) {
-#pragma unroll
-            for (int s = 0; s < ES; ++s) {
-                const int el = el0 + 256 * s;
-                if (el >= nn) continue;
-                const int i = el / n, j = el - i * n;
-                for (int p = q; p < np; p += Q) {
-                    const cd* W = U + p * nn;
-                    const double* fp = fs + p * n;
-                    cd pij{0.0, 0.0};
-                    for (int b = 0; b < n; ++b) {
-                        const double f = fp[b];
-                        if (f == 0.0) continue;                    // (kT = 0: the empty states)
-                        cfmac_x(pij, cscale(W[b * n + i], f), W[b * n + j]);   // += f w[i] conj(w[j])
-                    }
-#pragma unroll
-                    for (int r = 0; r < OCC_RB; ++r)
-                        if (r < nrb) cfma_x(acc[s][r], pij, phs[p * OCC_RB + r]);
-                }
-            }
-        }
-        __syncthreads();                                           // (the batch is consumed)
+// The weight policy of the lattice sum (tbk_lat_dev.h): a real weight f[b][ik] per state, one "frequency", OCC_RB lattice vectors per
+// workgroup, every state in order.  A state of weight 0 is skipped (kT = 0: the empty states), and in the tiled form the first strip
+// whose leading weight is 0 ends the point: the weights fall with the level.
+struct DmWt {
+    static constexpr int WB = 1, RB = OCC_RB, NSEL = 0;
+    static constexpr bool GROUP_X = true;   // (at most 1024 blocks of lattice vectors, or 4096 / G with their tiles: they fit y)
+    static constexpr const char* kLabel[3] = {"dm_lds", "dm_tile", "dm_rows"};
+    typedef double W;
+    __device__ __forceinline__ double freq(const int) const { return 0.0; }
+    __device__ __forceinline__ double weight(const double, const double f) const { return f; }
+    static __device__ __forceinline__ bool empty(const double f) { return f == 0.0; }
+    template <bool FULL>
+    static __device__ __forceinline__ void add(cd (&pij)[1], const cd a, const cd b, const double* f, const int) {
+        cfmac_x(pij[0], cscale(a, f[0]), b);                        // += f w[i] conj(w[j])
     }
-    if (ES == 1 && Q > 1) {
-        cd* buf = U;                                               // OCC_RB x 256 <= OCC_LDS_CD
-#pragma unroll
-        for (int r = 0; r < OCC_RB; ++r) buf[r * 256 + t] = acc[0][r];
-        __syncthreads();
-        if (t < nn)
-            for (int r = 0; r < nrb; ++r) {
-                cd s = buf[r * 256 + t];
-                for (int qq = 1; qq < Q; ++qq) s = cadd(s, buf[r * 256 + qq * nn + t]);
-                part[((int64_t)g * nr + rb0 + r) * nn + t] = s;
-            }
-        return;
-    }
-#pragma unroll
-    for (int s = 0; s < ES; ++s) {
-        const int el = el0 + 256 * s;
-        if (!live || el >= nn) continue;
-#pragma unroll
-        for (int r = 0; r < OCC_RB; ++r)
-            if (r < nrb) part[((int64_t)g * nr + rb0 + r) * nn + el] = acc[s][r];
-    }
-}
-
-// 33 .. 2048 states.  Workgroup (16 x 16 tile (ti, tj) of P(k), k-group g, block of OCC_RB lattice vectors): lane (ty, tx) owns the
-// element (16 ti + ty, 16 tj + tx).  Per point the states go through LDS in strips of 16 (their components of the tile's rows and of
-// its columns, both read along the components); the weights fall with the level, so the first strip whose leading weight is 0 ends the
-// point.  The orbital phases are applied to the finished P_ij.
-__global__ __launch_bounds__(256) void k_dm_tile(const ModelView mv, const double* __restrict__ k, const cd* __restrict__ evec,
-                                                 const double* __restrict__ fw, const int64_t nk, const int64_t first, const OccMesh M,
-                                                 const int T, const int G, const int32_t* __restrict__ R, const int nr, cd* __restrict__ part) {
-    __shared__ cd As[16][16], Bs[16][16], eo[32], phs[OCC_RB];
-    __shared__ double fs[16];
-    const int n = mv.nsta, t = threadIdx.x, tx = t & 15, ty = t >> 4;
-    const int ti = blockIdx.x / T, tj = blockIdx.x - ti * T;
-    const int i = ti * 16 + ty, j = tj * 16 + tx;
-    const int g = blockIdx.y, rb0 = blockIdx.z * OCC_RB, nrb = min(OCC_RB, nr - rb0);
-    const int64_t p0 = (int64_t)g * nk / G, p1 = (int64_t)(g + 1) * nk / G;
-    cd acc[OCC_RB];
-#pragma unroll
-    for (int r = 0; r < OCC_RB; ++r) acc[r] = cd{0.0, 0.0};
-    for (int64_t ik = p0; ik < p1; ++ik) {
-        if (t < 32) {
-            const int o = t < 16 ? ti * 16 + t : tj * 16 + t - 16;
-            eo[t] = o < n ? dm_orb_phase(mv, k, ik, o) : cd{0.0, 0.0};
-        } else if (t < 32 + nrb) {
-            phs[t - 32] = dm_phase(M, first + ik, R + (int64_t)(rb0 + t - 32) * M.dk);
-        }
-        cd pij{0.0, 0.0};
-        for (int b0 = 0; b0 < n; b0 += 16) {
-            __syncthreads();                                       // (the previous strip is consumed; eo and phs are staged)
-            if (t < 16) fs[t] = b0 + t < n ? fw[(int64_t)(b0 + t) * nk + ik] : 0.0;
-            const int b = b0 + ty;
-            const cd* u = evec + ((int64_t)(b < n ? b : 0) * nk + ik) * n;
-            As[ty][tx] = (b < n && ti * 16 + tx < n) ? u[ti * 16 + tx] : cd{0.0, 0.0};
-            Bs[ty][tx] = (b < n && tj * 16 + tx < n) ? u[tj * 16 + tx] : cd{0.0, 0.0};
-            __syncthreads();
-            if (fs[0] == 0.0) break;                               // (uniform: every later state is empty too)
-#pragma unroll
-            for (int bb = 0; bb < 16; ++bb) {
-                const double f = fs[bb];
-                if (f == 0.0) continue;
-                cfmac_x(pij, cscale(As[bb][ty], f), Bs[bb][tx]);
-            }
-        }
-        pij = cmul_x(cmul_x(pij, eo[ty]), cconj(eo[16 + tx]));
-#pragma unroll
-        for (int r = 0; r < OCC_RB; ++r)
-            if (r < nrb) cfma_x(acc[r], pij, phs[r]);
-        __syncthreads();                                           // (eo and phs are read)
-    }
-    if (i < n && j < n)
-#pragma unroll
-        for (int r = 0; r < OCC_RB; ++r)
-            if (r < nrb) part[((int64_t)g * nr + rb0 + r) * n * n + (int64_t)i * n + j] = acc[r];
-}
+};
 
 // ---------------------------------------------------------------- host side: the two resident stages (tbk_occ_dev.h)
 int occ_fermi_stage(tbk_ctx* ctx, const double* e_dev, int64_t nlev, int G, int nfill, double kT, const OccFermiBufs& B) {
@@ -384,34 +260,11 @@ int occ_dm_stage(tbk_ctx* ctx, const ModelView& mv, const OccDmPlan& pl, const O
         else hipLaunchKernelGGL(k_dm_weights, dim3(nblk(cnt * n)), dim3(256), 0, ctx->stream, ec, cnt * n, mu, kT, fw);
         TBK_HIP(hipGetLastError());
     }
+    const LatChunk c{mv, kp, vc, fw, cnt, first, M};
     for (int r0 = 0; r0 < nR; r0 += pl.RT) {
-        const int nr = std::min(pl.RT, nR - r0);
-        const unsigned nrb = (unsigned)((nr + OCC_RB - 1) / OCC_RB);
-        const int32_t* Rp = R_dev + (int64_t)r0 * dk;
-        if (pl.lds) {
-            ProfScope ps(ctx, "dm_lds");
-            const dim3 grid((unsigned)pl.G, nrb);
-            if (pl.ES == 1)
-                hipLaunchKernelGGL(k_dm_lds<1>, grid, dim3(256), 0, ctx->stream, mv, kp, vc, (const double*)fw, cnt, first, M, pl.P, pl.G, Rp, nr,
-                                   part);
-            else if (pl.ES == 2)
-                hipLaunchKernelGGL(k_dm_lds<2>, grid, dim3(256), 0, ctx->stream, mv, kp, vc, (const double*)fw, cnt, first, M, pl.P, pl.G, Rp, nr,
-                                   part);
-            else
-                hipLaunchKernelGGL(k_dm_lds<4>, grid, dim3(256), 0, ctx->stream, mv, kp, vc, (const double*)fw, cnt, first, M, pl.P, pl.G, Rp, nr,
-                                   part);
-            TBK_HIP(hipGetLastError());
-        } else {
-            ProfScope ps(ctx, "dm_tile");
-            hipLaunchKernelGGL(k_dm_tile, dim3((unsigned)(pl.T * pl.T), (unsigned)pl.G, nrb), dim3(256), 0, ctx->stream, mv, kp, vc,
-                               (const double*)fw, cnt, first, M, pl.T, pl.G, Rp, nr, part);
-            TBK_HIP(hipGetLastError());
-        }
-        ProfScope ps(ctx, "dm_rows");
-        const int64_t nrows = (int64_t)nr * nn * 2;
-        hipLaunchKernelGGL(k_group_rows_lanes, dim3(nblk(nrows)), dim3(256), 0, ctx->stream, (const double*)part, pl.G, nrows, nrows, nrows,
-                           accumulate, (double*)(acc + (int64_t)r0 * nn));
-        TBK_HIP(hipGetLastError());
+        const int rc = lat_launch(ctx, pl, c, DmWt{}, n, 1, R_dev + (int64_t)r0 * dk, std::min(pl.RT, nR - r0), nR, part,
+                                  acc + (int64_t)r0 * nn, accumulate);
+        if (rc) return rc;
     }
     return TBK_OK;
 }

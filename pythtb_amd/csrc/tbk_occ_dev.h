@@ -3,7 +3,7 @@
 // synchronise.
 #pragma once
 #include "tbk_occ.h"
-#include "tbk_mesh_phase.h"
+#include "tbk_lat_dev.h"
 
 // the buffers of the Fermi selection, all on the device: part[2 nfill G] doubles; mu, lo, hi, target [nfill]; edges [2 nfill]
 struct OccFermiBufs {
