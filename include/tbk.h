@@ -756,6 +756,33 @@ int tbk_wannier_mesh(tbk_model* model, const int32_t* mesh, int nb, const int32_
                      int r_user, const int32_t* R, double* hop, double* sums, double* hist, double* functions_or_null,
                      double* gauge_or_null, int32_t* info);
 
+/* ---- disentangled Wannier functions with energy windows on a k mesh ----
+ * tbk_wannier_mesh's arguments mean what they mean there; `bands` is the outermost candidate set, and the subspace of nw functions
+ * is chosen inside it after Souza, Marzari and Vanderbilt (PRB 65, 035109).  Beyond tbk_wannier_mesh's caps: the candidate states
+ * stay on the device, N_k nsta nb <= 2^26, and so do their overlaps, N_k nbv nb^2 <= 2^26.
+ *   window_or_null   (lo, hi): of the candidate bands only those with lo <= E_n(k) <= hi take part at k (null: all of them);
+ *                    TBK_EINVAL "... at k = ..." where fewer than nw do
+ *   frozen_or_null   (lo, hi): window bands inside it are kept in the subspace whole; TBK_EINVAL "... at k = ..." where more than nw are
+ *   dis_iter         0..65536 iterations (0: the projected subspace with the frozen states forced in); Z_in = dis_mixing Z_out +
+ *                    (1 - dis_mixing) Z_in, 0 < dis_mixing <= 1; the host reads the change of Omega_I every check_every iterations
+ *                    (one 8-byte copy) and stops when its modulus is below dis_tol > 0
+ * then the gauge U0 = U_dis A' (A'+ A')^-1/2 with A' = U_dis+ A (TBK_EINVAL "trial functions are singular ..." when the smallest
+ * singular value of A' over the mesh is below 1e-8) and tbk_wannier_mesh's spread, descent, model and functions.
+ * Out beyond tbk_wannier_mesh's (sums[20]: the smallest singular value of A'): dis_sums[2] = {the smallest singular value of the
+ * nb x nw projection over the mesh, the smallest gap over the mesh between the last selected and the first rejected eigenvalue of Z at
+ * the last iteration, infinity where nothing is rejected}; dis_hist[dis_iter + 1]: Omega_I of the starting subspace and after every
+ * iteration; n_window[N_k], n_frozen[N_k]; gauge_or_null[N_k][nb][nw]: U_tot, zero rows for bands outside the window;
+ * info[5] = {iterations, converged, dis_iterations, dis_converged, k-groups of the sums}.
+ * Fixed-order sums, no atomics, a partition that depends on (mesh, nsta, nb, nw, nbv) alone: two calls give the same bits, dis_iter = m
+ * gives the first m + 1 entries of dis_hist of a longer run, and with dis_iter fixed max_iter = m the first m + 1 entries of hist.   */
+int tbk_wannier_dis_mesh(tbk_model* model, const int32_t* mesh, int nb, const int32_t* bands, int nw, int64_t nterm,
+                         const int32_t* term_ptr, const int32_t* term_state, const int32_t* term_R, const double* term_amp, int nbv,
+                         const int32_t* bstep, const double* bw, const double* bgram, const double* window_or_null,
+                         const double* frozen_or_null, int dis_iter, double dis_mixing, double dis_tol, int max_iter, double tol,
+                         int check_every, int nR, int r_user, const int32_t* R, double* hop, double* sums, double* hist, double* dis_sums,
+                         double* dis_hist, int32_t* n_window, int32_t* n_frozen, double* functions_or_null, double* gauge_or_null,
+                         int32_t* info);
+
 /* ---- multi-GPU: one process per GPU, k-points sharded, one gather ------
  * Thin RCCL wrappers (librccl is dlopen'ed on first use).  The 128-byte id is
  * created on rank 0 and distributed by the launcher (any out-of-band channel). */

@@ -122,6 +122,8 @@ SIGNATURES = {
                                  _i, _dp, C.c_double, _i, C.c_double, _i, _i, _dp, _dp, _dp, _dp, _ip, _dp, _dp, _dp, _ip]),
     "tbk_wannier_mesh": (_i, [_p, _ip, _i, _ip, _i, _i64, _ip, _ip, _ip, _dp, _i, _ip, _dp, _dp, _i, C.c_double, _i, _i, _i, _ip, _dp, _dp, _dp,
                               _dp, _dp, _ip]),
+    "tbk_wannier_dis_mesh": (_i, [_p, _ip, _i, _ip, _i, _i64, _ip, _ip, _ip, _dp, _i, _ip, _dp, _dp, _dp, _dp, _i, C.c_double, C.c_double, _i,
+                                  C.c_double, _i, _i, _i, _ip, _dp, _dp, _dp, _dp, _dp, _ip, _ip, _dp, _dp, _ip]),
     "tbk_propagate_mesh": (_i, [_p, _ip, _i, _dp, C.c_double, _i, _ip, C.c_double, C.c_double, _dp, _dp, _dp, _dp]),
     "tbk_propagator_list": (_i, [_p, _dp, _i64, _i, _dp, C.c_double, _dp]),
     "tbk_orb_moment_list": (_i, [_p, _dp, _i64, _i, _i, _ip, _i, _dp]),

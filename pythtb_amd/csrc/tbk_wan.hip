@@ -568,64 +568,52 @@ int wan_step(const WanRun& S) {
     TBK_HIP(hipGetLastError());
     return TBK_OK;
 }
-}  // namespace
-
-extern "C" int tbk_wannier_mesh(tbk_model* m, const int32_t* mesh, int nb, const int32_t* bands, int nw, int64_t nterm,
-                                const int32_t* term_ptr, const int32_t* term_state, const int32_t* term_R, const double* term_amp, int nbv,
-                                const int32_t* bstep, const double* bw, const double* bgram, int max_iter, double tol, int check_every,
-                                int nR, int r_user, const int32_t* R, double* hop, double* sums, double* hist, double* functions_or_null,
-                                double* gauge_or_null, int32_t* info) {
-    const char* fn = "tbk_wannier_mesh";
-    TBK_REQUIRE(m && hop && sums && hist && info, TBK_EINVAL, "%s: null argument", fn);
-    const int dk = m->dim_k, n = m->nsta;
-    WanArgs A;
-    A.nb = nb, A.nw = nw, A.bands = bands, A.nterm = nterm, A.term_ptr = term_ptr, A.term_state = term_state, A.term_R = term_R;
-    A.term_amp = term_amp, A.nbv = nbv, A.bstep = bstep, A.bw = bw, A.bgram = bgram, A.max_iter = max_iter, A.tol = tol;
-    A.check_every = check_every, A.nR = nR, A.r_user = r_user, A.R = R, A.want_fn = functions_or_null ? 1 : 0;
-    int64_t npts;
-    int rc = wan_check(fn, dk, n, mesh, A, npts);
-    if (rc) return rc;
-    tbk_ctx* ctx = m->ctx;
-    TBK_HIP(hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-
-    WanRun S{};
-    S.ctx = ctx;
-    S.pl = wan_plan(n, dk, npts, mesh, nb, nw, nbv, nterm, max_iter, nR, A.want_fn);
-    S.M = WanMesh{{1, 1, 1}, dk};
-    for (int d = 0; d < dk; ++d) S.M.N[d] = mesh[d];
-    S.St.nbv = nbv;
-    for (int i = 0; i < WAN_BV_MAX; ++i) {
-        S.St.w[i] = i < nbv ? bw[i] : 0.0;
-        for (int d = 0; d < 3; ++d) S.St.s[i][d] = i < nbv && d < dk ? bstep[i * dk + d] : 0;
-    }
-    const WanPlan& p = S.pl;
-    struct Guard {
-        hipStream_t st;
-        void* blk = nullptr;
-        ~Guard() {
-            if (blk) {
-                hipStreamSynchronize(st);
-                hipFree(blk);
-            }
+// the workspace block: freed behind a synchronisation when the call returns, whichever way
+struct WanBlock {
+    hipStream_t st;
+    void* blk = nullptr;
+    ~WanBlock() {
+        if (blk) {
+            hipStreamSynchronize(st);
+            hipFree(blk);
         }
-    } guard{st};
-    {
-        hipError_t e = hipMalloc(&guard.blk, p.total);
+    }
+    int alloc(const char* fn, size_t bytes) {
+        hipError_t e = hipMalloc(&blk, bytes);
         if (e != hipSuccess) {
-            guard.blk = nullptr;
-            tbk_set_error("%s: hipMalloc(%zu) for the workspace: %s", fn, p.total, hipGetErrorString(e));
+            blk = nullptr;
+            tbk_set_error("%s: hipMalloc(%zu) for the workspace: %s", fn, bytes, hipGetErrorString(e));
             return TBK_ENOMEM;
         }
+        return TBK_OK;
     }
-    S.base = (unsigned char*)guard.blk;
-
-    // the small tables
+};
+WanRun wan_run(tbk_model* m, const int32_t* mesh, const WanPlan& pl, const WanArgs& A) {
+    WanRun S{};
+    const int dk = m->dim_k;
+    S.ctx = m->ctx;
+    S.pl = pl;
+    S.M = WanMesh{{1, 1, 1}, dk};
+    for (int d = 0; d < dk; ++d) S.M.N[d] = mesh[d];
+    S.St.nbv = A.nbv;
+    for (int i = 0; i < WAN_BV_MAX; ++i) {
+        S.St.w[i] = i < A.nbv ? A.bw[i] : 0.0;
+        for (int d = 0; d < 3; ++d) S.St.s[i][d] = i < A.nbv && d < dk ? A.bstep[i * dk + d] : 0;
+    }
+    return S;
+}
+// the small tables of a call, uploaded
+int wan_tables(const WanRun& S, tbk_model* m, const int32_t* mesh, const WanArgs& A) {
+    const WanPlan& p = S.pl;
+    hipStream_t st = S.ctx->stream;
+    const int dk = m->dim_k, n = m->nsta, nb = A.nb, nw = A.nw, nbv = A.nbv, nR = A.nR;
+    const int64_t nterm = A.nterm;
+    int rc;
     std::vector<int32_t> trv((size_t)nterm * 3, 0), rdev((size_t)nR * 3, 0);
     for (int64_t t = 0; t < nterm; ++t)
-        for (int d = 0; d < dk; ++d) trv[3 * t + d] = term_R[t * dk + d];
+        for (int d = 0; d < dk; ++d) trv[3 * t + d] = A.term_R[t * dk + d];
     for (int64_t r = 0; r < nR; ++r)
-        for (int d = 0; d < dk; ++d) rdev[3 * r + d] = R[r * dk + d];
+        for (int d = 0; d < dk; ++d) rdev[3 * r + d] = A.R[r * dk + d];
     std::vector<double4> orb((size_t)n);
     TBK_HIP(hipMemcpyAsync(orb.data(), m->view.orb, (size_t)n * sizeof(double4), hipMemcpyDeviceToHost, st));
     TBK_HIP(hipStreamSynchronize(st));
@@ -641,69 +629,50 @@ extern "C" int tbk_wannier_mesh(tbk_model* m, const int32_t* mesh, int nb, const
         if (bytes) TBK_HIP(hipMemcpyAsync(S.base + p.off[i], src, bytes, hipMemcpyHostToDevice, st));
         return TBK_OK;
     };
-    if ((rc = up(WanPlan::BANDS, bands, (size_t)nb * sizeof(int32_t)))) return rc;
-    if ((rc = up(WanPlan::TPTR, term_ptr, (size_t)(nw + 1) * sizeof(int32_t)))) return rc;
-    if ((rc = up(WanPlan::TSTATE, term_state, (size_t)nterm * sizeof(int32_t)))) return rc;
+    if ((rc = up(WanPlan::BANDS, A.bands, (size_t)nb * sizeof(int32_t)))) return rc;
+    if ((rc = up(WanPlan::TPTR, A.term_ptr, (size_t)(nw + 1) * sizeof(int32_t)))) return rc;
+    if ((rc = up(WanPlan::TSTATE, A.term_state, (size_t)nterm * sizeof(int32_t)))) return rc;
     if ((rc = up(WanPlan::TRV, trv.data(), trv.size() * sizeof(int32_t)))) return rc;
-    if ((rc = up(WanPlan::TAMP, term_amp, (size_t)nterm * sizeof(cd)))) return rc;
+    if ((rc = up(WanPlan::TAMP, A.term_amp, (size_t)nterm * sizeof(cd)))) return rc;
     if ((rc = up(WanPlan::PHASE, phase.data(), phase.size() * sizeof(cd)))) return rc;
-    if ((rc = up(WanPlan::BW, bw, (size_t)nbv * sizeof(double)))) return rc;
-    if ((rc = up(WanPlan::BGRAM, bgram, (size_t)nbv * nbv * sizeof(double)))) return rc;
+    if ((rc = up(WanPlan::BW, A.bw, (size_t)nbv * sizeof(double)))) return rc;
+    if ((rc = up(WanPlan::BGRAM, A.bgram, (size_t)nbv * nbv * sizeof(double)))) return rc;
     if ((rc = up(WanPlan::TW, tw.data(), tw.size() * sizeof(cd)))) return rc;
     if ((rc = up(WanPlan::RDEV, rdev.data(), rdev.size() * sizeof(int32_t)))) return rc;
     TBK_HIP(hipStreamSynchronize(st));                              // (the host vectors above go out of use)
-
-    // the solve, the projection and the rotation, chunk by chunk
-    KuboChunks cw = p.cw;
-    cw.base = S.base + p.off[WanPlan::CHUNKS];
-    rc = kubo_for_chunks(m, cw, nullptr, mesh, npts, [&](int64_t first, int64_t cnt, const double*, const double* ec, const cd* vc) -> int {
-        ProfScope ps(ctx, "wan_project");
-        hipLaunchKernelGGL(k_wan_project, dim3((unsigned)cnt), dim3(64), 0, st, m->view, S.M, first, cnt, vc, ec,
-                           (const int32_t*)S.buf<int32_t>(WanPlan::BANDS), nb, nw, (const int32_t*)S.buf<int32_t>(WanPlan::TPTR),
-                           (const int32_t*)S.buf<int32_t>(WanPlan::TSTATE), (const int32_t*)S.buf<int32_t>(WanPlan::TRV),
-                           (const cd*)S.buf<cd>(WanPlan::TAMP), S.buf<cd>(WanPlan::U0), S.buf<double>(WanPlan::EB), S.buf<double>(WanPlan::SVK));
-        hipLaunchKernelGGL(k_wan_rotate, dim3((unsigned)((cnt + p.P - 1) / p.P)), dim3(256), 0, st, n, first, cnt, p.P, vc,
-                           (const int32_t*)S.buf<int32_t>(WanPlan::BANDS), nb, nw, (const cd*)S.buf<cd>(WanPlan::U0), S.buf<cd>(WanPlan::UT));
-        TBK_HIP(hipGetLastError());
-        return TBK_OK;
-    });
-    if (rc) return rc;
-
-    // the smallest singular value of the projection over the mesh
-    {
-        std::vector<double> sv((size_t)npts);
-        TBK_HIP(hipMemcpyAsync(sv.data(), S.buf<double>(WanPlan::SVK), (size_t)npts * sizeof(double), hipMemcpyDeviceToHost, st));
-        TBK_HIP(hipStreamSynchronize(st));
-        int64_t at = 0;
-        for (int64_t k = 0; k < npts; ++k) {
-            TBK_REQUIRE(std::isfinite(sv[k]), TBK_ENOCONV, "%s: the projection at mesh point %lld is not finite", fn, (long long)k);
-            if (sv[k] < sv[at]) at = k;
-        }
-        sums[4 + WAN_NW_MAX] = sv[at];
-        if (sv[at] < kWanSvMin) {
-            int i[3] = {0, 0, 0};
-            int64_t idx = at;
-            for (int d = dk - 1; d >= 0; --d) i[d] = (int)(idx % mesh[d]), idx /= mesh[d];
-            char where[96];
-            int len = 0;
-            for (int d = 0; d < dk; ++d) len += snprintf(where + len, sizeof where - len, d ? ", %d/%d" : "%d/%d", i[d], mesh[d]);
-            tbk_set_error("%s: trial functions are singular on the bands at k = (%s): smallest singular value %.3g", fn, where, sv[at]);
-            return TBK_EINVAL;
-        }
+    return TBK_OK;
+}
+// the smallest singular value of the projection over the mesh, into sums[4 + WAN_NW_MAX]; below kWanSvMin the call ends here
+int wan_sv_check(const char* fn, const WanRun& S, int dk, const int32_t* mesh, double* sums) {
+    const int64_t npts = S.pl.npts;
+    hipStream_t st = S.ctx->stream;
+    std::vector<double> sv((size_t)npts);
+    TBK_HIP(hipMemcpyAsync(sv.data(), S.buf<double>(WanPlan::SVK), (size_t)npts * sizeof(double), hipMemcpyDeviceToHost, st));
+    TBK_HIP(hipStreamSynchronize(st));
+    int64_t at = 0;
+    for (int64_t k = 0; k < npts; ++k) {
+        TBK_REQUIRE(std::isfinite(sv[k]), TBK_ENOCONV, "%s: the projection at mesh point %lld is not finite", fn, (long long)k);
+        if (sv[k] < sv[at]) at = k;
     }
-
-    // the overlaps and the spread of the projection
-    {
-        ProfScope ps(ctx, "wan_overlap");
-        const int64_t nitems = npts * nbv;
-        hipLaunchKernelGGL(k_wan_overlap, dim3((unsigned)((nitems + p.Q - 1) / p.Q)), dim3(256), 0, st, S.M, S.St, n, nw, p.Q, nitems,
-                           (const cd*)S.buf<cd>(WanPlan::UT), (const cd*)S.buf<cd>(WanPlan::PHASE), S.buf<cd>(WanPlan::MOV));
-        hipLaunchKernelGGL(k_wan_identity, dim3(nblk(npts * nw * nw)), dim3(256), 0, st, npts, nw, S.buf<cd>(WanPlan::UACC));
-        TBK_HIP(hipGetLastError());
+    sums[4 + WAN_NW_MAX] = sv[at];
+    if (sv[at] < kWanSvMin) {
+        int i[3] = {0, 0, 0};
+        int64_t idx = at;
+        for (int d = dk - 1; d >= 0; --d) i[d] = (int)(idx % mesh[d]), idx /= mesh[d];
+        char where[96];
+        int len = 0;
+        for (int d = 0; d < dk; ++d) len += snprintf(where + len, sizeof where - len, d ? ", %d/%d" : "%d/%d", i[d], mesh[d]);
+        tbk_set_error("%s: trial functions are singular on the bands at k = (%s): smallest singular value %.3g", fn, where, sv[at]);
+        return TBK_EINVAL;
     }
+    return TBK_OK;
+}
+// the descent from the overlaps in MOV (U_acc the identity): the spread of the start, then up to max_iter steps
+int wan_descend(const char* fn, const WanRun& S, int max_iter, double tol, int check_every, int& iterations, int& converged) {
+    hipStream_t st = S.ctx->stream;
+    int rc;
     if ((rc = wan_spread(S, 0))) return rc;
-
-    int iterations = 0, converged = 0;
+    iterations = 0, converged = 0;
     for (int it = 1; it <= max_iter; ++it) {
         if ((rc = wan_step(S))) return rc;
         if ((rc = wan_spread(S, it))) return rc;
@@ -718,8 +687,17 @@ extern "C" int tbk_wannier_mesh(tbk_model* m, const int32_t* mesh, int nb, const
             break;
         }
     }
-
-    // the Wannier Hamiltonian, and on request the functions
+    return TBK_OK;
+}
+// the Wannier Hamiltonian, on request the functions, and the downloads
+int wan_finish(const WanRun& S, tbk_model* m, int nR, int iterations, double* hop, double* sums, double* hist, double* functions_or_null,
+               double* gauge_or_null) {
+    const WanPlan& p = S.pl;
+    tbk_ctx* ctx = S.ctx;
+    hipStream_t st = ctx->stream;
+    const int n = p.n, nb = p.nb, nw = p.nw, nbv = p.nbv;
+    const int64_t npts = p.npts;
+    int rc;
     {
         ProfScope ps(ctx, "wan_model");
         hipLaunchKernelGGL(k_wan_hw, dim3((unsigned)npts), dim3(64), 0, st, nb, nw, (const double*)S.buf<double>(WanPlan::EB), S.buf<cd>(WanPlan::U0),
@@ -743,6 +721,65 @@ extern "C" int tbk_wannier_mesh(tbk_model* m, const int32_t* mesh, int nb, const
     if (gauge_or_null)
         TBK_HIP(hipMemcpyAsync(gauge_or_null, S.buf<cd>(WanPlan::U0), (size_t)npts * nb * nw * sizeof(cd), hipMemcpyDeviceToHost, st));
     TBK_HIP(hipStreamSynchronize(st));
+    return TBK_OK;
+}
+}  // namespace
+
+extern "C" int tbk_wannier_mesh(tbk_model* m, const int32_t* mesh, int nb, const int32_t* bands, int nw, int64_t nterm,
+                                const int32_t* term_ptr, const int32_t* term_state, const int32_t* term_R, const double* term_amp, int nbv,
+                                const int32_t* bstep, const double* bw, const double* bgram, int max_iter, double tol, int check_every,
+                                int nR, int r_user, const int32_t* R, double* hop, double* sums, double* hist, double* functions_or_null,
+                                double* gauge_or_null, int32_t* info) {
+    const char* fn = "tbk_wannier_mesh";
+    TBK_REQUIRE(m && hop && sums && hist && info, TBK_EINVAL, "%s: null argument", fn);
+    const int dk = m->dim_k, n = m->nsta;
+    WanArgs A;
+    A.nb = nb, A.nw = nw, A.bands = bands, A.nterm = nterm, A.term_ptr = term_ptr, A.term_state = term_state, A.term_R = term_R;
+    A.term_amp = term_amp, A.nbv = nbv, A.bstep = bstep, A.bw = bw, A.bgram = bgram, A.max_iter = max_iter, A.tol = tol;
+    A.check_every = check_every, A.nR = nR, A.r_user = r_user, A.R = R, A.want_fn = functions_or_null ? 1 : 0;
+    int64_t npts;
+    int rc = wan_check(fn, dk, n, mesh, A, npts);
+    if (rc) return rc;
+    tbk_ctx* ctx = m->ctx;
+    TBK_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+
+    WanRun S = wan_run(m, mesh, wan_plan(n, dk, npts, mesh, nb, nw, nbv, nterm, max_iter, nR, A.want_fn), A);
+    const WanPlan& p = S.pl;
+    WanBlock guard{st};
+    if ((rc = guard.alloc(fn, p.total))) return rc;
+    S.base = (unsigned char*)guard.blk;
+    if ((rc = wan_tables(S, m, mesh, A))) return rc;
+
+    // the solve, the projection and the rotation, chunk by chunk
+    KuboChunks cw = p.cw;
+    cw.base = S.base + p.off[WanPlan::CHUNKS];
+    rc = kubo_for_chunks(m, cw, nullptr, mesh, npts, [&](int64_t first, int64_t cnt, const double*, const double* ec, const cd* vc) -> int {
+        ProfScope ps(ctx, "wan_project");
+        hipLaunchKernelGGL(k_wan_project, dim3((unsigned)cnt), dim3(64), 0, st, m->view, S.M, first, cnt, vc, ec,
+                           (const int32_t*)S.buf<int32_t>(WanPlan::BANDS), nb, nw, (const int32_t*)S.buf<int32_t>(WanPlan::TPTR),
+                           (const int32_t*)S.buf<int32_t>(WanPlan::TSTATE), (const int32_t*)S.buf<int32_t>(WanPlan::TRV),
+                           (const cd*)S.buf<cd>(WanPlan::TAMP), S.buf<cd>(WanPlan::U0), S.buf<double>(WanPlan::EB), S.buf<double>(WanPlan::SVK));
+        hipLaunchKernelGGL(k_wan_rotate, dim3((unsigned)((cnt + p.P - 1) / p.P)), dim3(256), 0, st, n, first, cnt, p.P, vc,
+                           (const int32_t*)S.buf<int32_t>(WanPlan::BANDS), nb, nw, (const cd*)S.buf<cd>(WanPlan::U0), S.buf<cd>(WanPlan::UT));
+        TBK_HIP(hipGetLastError());
+        return TBK_OK;
+    });
+    if (rc) return rc;
+    if ((rc = wan_sv_check(fn, S, dk, mesh, sums))) return rc;
+
+    // the overlaps, the spread of the projection and the descent
+    {
+        ProfScope ps(ctx, "wan_overlap");
+        const int64_t nitems = npts * nbv;
+        hipLaunchKernelGGL(k_wan_overlap, dim3((unsigned)((nitems + p.Q - 1) / p.Q)), dim3(256), 0, st, S.M, S.St, n, nw, p.Q, nitems,
+                           (const cd*)S.buf<cd>(WanPlan::UT), (const cd*)S.buf<cd>(WanPlan::PHASE), S.buf<cd>(WanPlan::MOV));
+        hipLaunchKernelGGL(k_wan_identity, dim3(nblk(npts * nw * nw)), dim3(256), 0, st, npts, nw, S.buf<cd>(WanPlan::UACC));
+        TBK_HIP(hipGetLastError());
+    }
+    int iterations = 0, converged = 0;
+    if ((rc = wan_descend(fn, S, max_iter, tol, check_every, iterations, converged))) return rc;
+    if ((rc = wan_finish(S, m, nR, iterations, hop, sums, hist, functions_or_null, gauge_or_null))) return rc;
     info[0] = iterations;
     info[1] = converged;
     info[2] = p.P;
@@ -750,3 +787,6 @@ extern "C" int tbk_wannier_mesh(tbk_model* m, const int32_t* mesh, int nb, const
     info[4] = p.G;
     return TBK_OK;
 }
+
+// the disentanglement entry shares this translation unit: it runs the spread, descent, model and Fourier kernels above unchanged
+#include "tbk_wdis.hip"

@@ -244,7 +244,8 @@ class mean_field_result(object):
 
 class wannier_result(object):
     """What `tb_model.wannier_mesh` returns: model, hoppings, R_list, centers, spreads, omega_i, omega_od, omega_d, omega, sv_min,
-    history, iterations, converged, b_vectors, b_weights, and on request functions and gauge."""
+    history, iterations, converged, b_vectors, b_weights, and on request functions and gauge.  `wannier_disentangle_mesh` adds
+    dis_history, dis_iterations, dis_converged, n_window, n_frozen, dis_gap_min and sv_min_projection."""
     pass
 
 
@@ -1513,11 +1514,15 @@ class tb_model(object):
         return m
 
     # ------------------------------------------------------------------ Wannier functions (extension)
-    def _wannier_bvectors(self, mesh):
-        """The b-vector star of `wannier_mesh` in closed form: (steps (nbv, dim_k) int32 in {-1, 0, 1}, weights (nbv,), b (nbv, dim_r)
+    def _wannier_bvectors(self, mesh, b_vectors="star"):
+        """b_vectors="shells": the shell search of `_wannier_shells`.  "star" (the default): the b-vector star of `wannier_mesh` in closed form: (steps (nbv, dim_k) int32 in {-1, 0, 1}, weights (nbv,), b (nbv, dim_r)
         Cartesian).  With S_ab = N_a N_b (a_a . a_b) / (2 pi)^2: the step +beta_a / N_a with weight S_aa / 2 - sum_{b != a} |S_ab| / 2,
         and for every pair a < b with S_ab != 0 the diagonal beta_a / N_a + sign(S_ab) beta_b / N_b with weight |S_ab| / 2, so that
         2 sum_b w_b b b^T is the identity on the span of the periodic lattice vectors (the mirror -b of every step is implied)."""
+        if not (isinstance(b_vectors, str) and b_vectors in ("star", "shells")):
+            raise Exception("\n\nb_vectors must be \"star\" or \"shells\".")
+        if b_vectors == "shells":
+            return self._wannier_shells(mesh)
         dk = self._dim_k
         A = self._lat[self._per]                                   # (dim_k, dim_r)
         gram = A @ A.T
@@ -1545,13 +1550,62 @@ class tb_model(object):
         bcart = (steps / N[None, :]) @ rec
         return steps, np.ascontiguousarray(weights, dtype=float), np.ascontiguousarray(bcart)
 
+    def _wannier_shells(self, mesh):
+        """The b-vector star by a search over shells, for lattices whose closed-form star has a vanishing weight (fcc, bcc).  The
+        candidates are the nonzero steps in {-1, 0, 1}^dim_k, one of every +-pair (the one whose first nonzero component is +1),
+        sorted by |b| and then by descending step tuple, grouped into shells by length (relative tolerance 1e-9).  Shells are added
+        shortest first, a shell that does not raise the rank of the system skipped; one weight per shell, by least squares on the
+        upper triangle of 2 sum_b w_b b b^T = 1; the first set with residual below 1e-12 and every weight positive is taken.  At
+        most 6 vectors (the kernels' cap).  Returns what `_wannier_bvectors` returns."""
+        dk = self._dim_k
+        A = self._lat[self._per]
+        N = np.array(mesh, dtype=float)
+        rec = 2.0 * np.pi * np.linalg.solve(A @ A.T, A)
+        cand = []
+        for idx in np.ndindex(*([3] * dk)):
+            s = [1 - i for i in idx]                               # descending tuples: (1, 1, 1) first
+            nz = [x for x in s if x != 0]
+            if nz and nz[0] == 1:
+                cand.append(s)
+        cand = np.array(cand, dtype=np.int32).reshape(-1, dk)
+        bc = (cand / N[None, :]) @ rec
+        ln = np.sqrt(np.sum(bc ** 2, axis=1))
+        order = np.argsort(ln, kind="stable")
+        shells = []
+        for i in order:
+            if shells and abs(ln[i] - ln[shells[-1][0]]) <= 1e-9 * ln[shells[-1][0]]:
+                shells[-1].append(int(i))
+            else:
+                shells.append([int(i)])
+        shells = [sorted(sh) for sh in shells]                     # inside a shell: the candidates' own order, not rounding's
+        iu = np.triu_indices(self._dim_r)
+        target = np.eye(self._dim_r)[iu]
+        cols, chosen = [], []
+        for sh in shells:
+            col = 2.0 * np.einsum("bi,bj->ij", bc[sh], bc[sh])[iu]
+            trial = cols + [col]
+            mat = np.array(trial).T
+            if np.linalg.matrix_rank(mat / np.linalg.norm(mat, axis=0)[None, :], tol=1e-9) < len(trial):
+                continue
+            if sum(len(c) for c in chosen) + len(sh) > 6:
+                break
+            cols, chosen = trial, chosen + [sh]
+            w = np.linalg.lstsq(mat, target, rcond=None)[0]
+            if np.max(np.abs(mat @ w - target)) < 1e-12 and np.all(w > 0.0):
+                pick = [i for c in chosen for i in c]
+                weights = np.concatenate([[w[j]] * len(c) for j, c in enumerate(chosen)])
+                return (np.ascontiguousarray(cand[pick], dtype=np.int32).reshape(len(pick), dk), np.ascontiguousarray(weights, dtype=float),
+                        np.ascontiguousarray(bc[pick]))
+        raise Exception("\n\nwannier_mesh: the mesh is too skewed: no b-vector star of positive weights was found within 6 vectors with "
+                        "steps in {-1, 0, 1}.")
+
     def _wannier_torus(self, mesh):
         """One lattice vector per class of the torus of the mesh: R_a in -floor((N_a - 1) / 2) .. floor(N_a / 2), row-major."""
         axes = [np.arange(-((int(n) - 1) // 2), int(n) // 2 + 1) for n in mesh]
         grid = np.meshgrid(*axes, indexing="ij")
         return np.ascontiguousarray(np.stack([g.reshape(-1) for g in grid], axis=1), dtype=np.int32)
 
-    def _wannier_args(self, mesh_size, trial, bands, max_iter, tol, check_every, R_list):
+    def _wannier_args(self, mesh_size, trial, bands, max_iter, tol, check_every, R_list, b_vectors="star"):
         """The checked arguments of `wannier_mesh` in the layout of tbk_wannier_mesh."""
         if self._dim_k not in (1, 2, 3):
             raise Exception("\n\nwannier_mesh needs a model with dim_k 1, 2 or 3.")
@@ -1659,7 +1713,7 @@ class tb_model(object):
             r_user = 1
         if R.shape[0] * nw * nw > 2 ** 26:
             raise Exception("\n\nwannier_mesh: nR * nw**2 must be at most 2**26: give an R_list.")
-        steps, weights, bcart = self._wannier_bvectors(mesh)
+        steps, weights, bcart = self._wannier_bvectors(mesh, b_vectors)
         return dict(mesh=mesh, nk=nk, bands=sel, nw=nw, tptr=np.ascontiguousarray(tptr, dtype=np.int32),
                     tstate=np.ascontiguousarray(tstate, dtype=np.int32),
                     tR=np.ascontiguousarray(np.array(tR).reshape(len(tstate), dk), dtype=np.int32),
@@ -1667,7 +1721,7 @@ class tb_model(object):
                     R=R, r_user=r_user, steps=steps, weights=weights, bcart=bcart)
 
     def wannier_mesh(self, mesh_size, trial, bands, max_iter=0, tol=0.0, check_every=10, R_list=None, return_functions=False,
-                     return_gauge=False):
+                     return_gauge=False, b_vectors="star"):
         """Extension: projected and maximally localised Wannier functions of the bands `bands` on `k_uniform_mesh(mesh_size)`
         (1-, 2- or 3-D, every N_a >= 3), with the whole loop on the device.
 
@@ -1688,8 +1742,9 @@ class tb_model(object):
         `(nw,)`, omega_i, omega_od, omega_d, omega, sv_min, history (Omega of the projection, then at every check), iterations,
         converged, b_vectors `(nbv, dim_r)`, b_weights; with return_functions, functions `(nR, nsta, nw)`:
         w_n(R, j) = (1 / N_k) sum_k e^{2 pi i k.(R + tau_j)} u~_n(k)[j]; with return_gauge, gauge `(N_k, nb, nw)`: U_tot.
+        b_vectors="shells" takes the star from the shell search of `_wannier_shells` (fcc, bcc) instead of the closed form.
         Fixed-order sums: two calls give the same bits, and max_iter = m gives the first rows of the history of a longer run."""
-        a = self._wannier_args(mesh_size, trial, bands, max_iter, tol, check_every, R_list)
+        a = self._wannier_args(mesh_size, trial, bands, max_iter, tol, check_every, R_list, b_vectors)
         mesh, nk, nw, R = a["mesh"], a["nk"], a["nw"], a["R"]
         n, dk, nb, nR, nbv = self._nsta, self._dim_k, a["bands"].size, a["R"].shape[0], a["weights"].size
         if return_functions and nR * n * nw > 2 ** 26:
@@ -1708,7 +1763,11 @@ class tb_model(object):
             a["check_every"], int(nR), int(a["r_user"]), _lib.iptr(R.reshape(-1)), _lib.dptr(hop.view(float)), _lib.dptr(sums),
             _lib.dptr(hist), _lib.dptr(fns.view(float)) if return_functions else None,
             _lib.dptr(gauge.view(float)) if return_gauge else None, _lib.iptr(info)))
-        its = int(info[0])
+        return self._wannier_result(a, int(info[0]), bool(info[1]), hop, sums, hist, fns, gauge)
+
+    def _wannier_result(self, a, its, converged, hop, sums, hist, fns, gauge):
+        """The `wannier_result` of a call from its checked arguments and what the device returned."""
+        mesh, nk, nw, R, nbv = a["mesh"], a["nk"], a["nw"], a["R"], a["weights"].size
         res = wannier_result()
         res.omega_i, res.omega_od, res.omega_d, res.omega = (float(x) for x in sums[:4])
         res.spreads = sums[4:4 + nw].copy()
@@ -1717,14 +1776,100 @@ class tb_model(object):
         res.centers = -(2.0 / nk) * (s1 * a["weights"][None, :]) @ a["bcart"]
         rows = [0] + [it for it in range(1, its + 1) if it % a["check_every"] == 0 or it == its]
         res.history = hist[rows].copy()
-        res.iterations, res.converged = its, bool(info[1])
+        res.iterations, res.converged = its, converged
         res.b_vectors, res.b_weights = a["bcart"], a["weights"]
         res.hoppings, res.R_list = hop, R
         res.model = self._wannier_model(mesh, hop, R, res.centers, split=not a["r_user"])
-        if return_functions:
+        if fns is not None:
             res.functions = fns
-        if return_gauge:
+        if gauge is not None:
             res.gauge = gauge
+        return res
+
+    def wannier_disentangle_mesh(self, mesh_size, trial, bands, window=None, frozen=None, dis_iter=200, dis_mixing=1.0, dis_tol=0.0,
+                                 max_iter=0, tol=0.0, check_every=10, R_list=None, return_functions=False, return_gauge=False,
+                                 b_vectors="star"):
+        """Extension: disentangled Wannier functions with energy windows (Souza, Marzari and Vanderbilt, PRB 65, 035109) on
+        `k_uniform_mesh(mesh_size)`, the whole loop on the device.  trial, bands, max_iter, tol, check_every, R_list,
+        return_functions, return_gauge and b_vectors mean what they mean in `wannier_mesh`; `bands` (nw <= nb <= 32, the same at
+        every k) is the outermost candidate set.
+
+        window=(lo, hi): of those bands only the ones with lo <= E_n(k) <= hi take part at k (None: all); the call raises, naming
+        the k, where fewer than nw do.  frozen=(lo, hi): window bands inside it are kept in the subspace whole; the call raises,
+        naming the k, where more than nw are.  The start is the projected subspace U = A (A+ A)^-1/2 (rows outside the window
+        zero) with the frozen states forced in: the frozen unit vectors, then the nw - n_frozen leading eigenvectors of U U+ on the
+        free indices (in the window, not frozen).  Iteration: Z(k) = sum_{+-b} w_b T T+, T = M0(k, b) U_dis(k + b) from the
+        previous iteration at every k, Z_in = dis_mixing Z + (1 - dis_mixing) Z_in, the leading eigenvectors of Z_in on the free
+        indices; dis_iter iterations (0..65536; 0: the start alone), the host reading the change of Omega_I every check_every
+        iterations and stopping when its modulus is below dis_tol > 0.  Then the gauge U0 = U_dis A' (A'+ A')^-1/2, A' = U_dis+ A,
+        and `wannier_mesh`'s spread, descent (max_iter), model and functions.  The frozen eigenvalues are eigenvalues of the
+        result model at every mesh point.
+
+        Returns `wannier_mesh`'s `wannier_result` (sv_min: the smallest singular value of A' over the mesh) with dis_history
+        (Omega_I of the start, then at every check), dis_iterations, dis_converged, n_window and n_frozen `(N_k,)`, dis_gap_min (the
+        smallest gap over k, at the last iteration, between the last selected and the first rejected eigenvalue of Z; inf where
+        nothing is rejected), sv_min_projection (of the nb x nw projection); gauge `(N_k, nb, nw)` has zero rows for bands outside
+        the window.  Beyond `wannier_mesh`'s caps: N_k * nsta * nb <= 2**26 and N_k * nbv * nb**2 <= 2**26 stay resident.
+        Fixed-order sums: two calls give the same bits, and a shorter dis_iter or max_iter gives the first rows of a longer run."""
+        def pair(x, name):
+            if x is None:
+                return None
+            try:
+                v = np.array(x, dtype=float).ravel()
+            except (TypeError, ValueError):
+                v = np.zeros(0)
+            if v.size != 2 or not np.all(np.isfinite(v)) or v[0] > v[1]:
+                raise Exception("\n\n%s must be None or a finite pair (lo, hi) with lo <= hi." % name)
+            return np.ascontiguousarray(v)
+        window, frozen = pair(window, "window"), pair(frozen, "frozen")
+        if not _is_int(dis_iter) or dis_iter < 0 or dis_iter > 65536:
+            raise Exception("\n\ndis_iter must be an integer in 0..65536.")
+        try:
+            dis_mixing, dis_tol = float(dis_mixing), float(dis_tol)
+        except (TypeError, ValueError):
+            raise Exception("\n\ndis_mixing and dis_tol must be numbers.")
+        if not (dis_mixing > 0.0 and dis_mixing <= 1.0):
+            raise Exception("\n\ndis_mixing must lie in (0, 1].")
+        if not (np.isfinite(dis_tol) and dis_tol >= 0.0):
+            raise Exception("\n\ndis_tol must be finite and >= 0.")
+        a = self._wannier_args(mesh_size, trial, bands, max_iter, tol, check_every, R_list, b_vectors)
+        mesh, nk, nw, R = a["mesh"], a["nk"], a["nw"], a["R"]
+        n, dk, nb, nR, nbv = self._nsta, self._dim_k, a["bands"].size, a["R"].shape[0], a["weights"].size
+        if nk * n * nb > 2 ** 26:
+            raise Exception("\n\nwannier_disentangle_mesh: N_k * nsta * nb = %d complex numbers of candidate states stay resident "
+                            "(at most 2**26): coarsen the mesh." % (nk * n * nb))
+        if nk * nbv * nb * nb > 2 ** 26:
+            raise Exception("\n\nwannier_disentangle_mesh: N_k * nbv * nb**2 = %d complex numbers of overlaps stay resident "
+                            "(at most 2**26): coarsen the mesh." % (nk * nbv * nb * nb))
+        if return_functions and nR * n * nw > 2 ** 26:
+            raise Exception("\n\nwannier_disentangle_mesh: the functions take nR * nsta * nw complex numbers (at most 2**26): give an R_list.")
+        bgram = np.ascontiguousarray(a["bcart"] @ a["bcart"].T)
+        hop = np.zeros((nR, nw, nw), dtype=complex)
+        sums = np.zeros(21 + 16 * 6)
+        hist = np.zeros(a["max_iter"] + 1)
+        dsums = np.zeros(2)
+        dhist = np.zeros(int(dis_iter) + 1)
+        nwin = np.zeros(nk, dtype=np.int32)
+        nfrz = np.zeros(nk, dtype=np.int32)
+        fns = np.zeros((nR, n, nw), dtype=complex) if return_functions else None
+        gauge = np.zeros((nk, nb, nw), dtype=complex) if return_gauge else None
+        info = np.zeros(5, dtype=np.int32)
+        _lib.check(_lib.lib.tbk_wannier_dis_mesh(
+            self._device_model(), _lib.iptr(mesh), int(nb), _lib.iptr(a["bands"]), int(nw), len(a["tstate"]), _lib.iptr(a["tptr"]),
+            _lib.iptr(a["tstate"]), _lib.iptr(a["tR"].reshape(-1)), _lib.dptr(a["tamp"].view(float)), int(nbv),
+            _lib.iptr(a["steps"].reshape(-1)), _lib.dptr(a["weights"]), _lib.dptr(bgram.reshape(-1)),
+            _lib.dptr(window) if window is not None else None, _lib.dptr(frozen) if frozen is not None else None, int(dis_iter),
+            dis_mixing, dis_tol, a["max_iter"], a["tol"], a["check_every"], int(nR), int(a["r_user"]), _lib.iptr(R.reshape(-1)),
+            _lib.dptr(hop.view(float)), _lib.dptr(sums), _lib.dptr(hist), _lib.dptr(dsums), _lib.dptr(dhist), _lib.iptr(nwin),
+            _lib.iptr(nfrz), _lib.dptr(fns.view(float)) if return_functions else None,
+            _lib.dptr(gauge.view(float)) if return_gauge else None, _lib.iptr(info)))
+        res = self._wannier_result(a, int(info[0]), bool(info[1]), hop, sums, hist, fns, gauge)
+        dits = int(info[2])
+        rows = [0] + [it for it in range(1, dits + 1) if it % a["check_every"] == 0 or it == dits]
+        res.dis_history = dhist[rows].copy()
+        res.dis_iterations, res.dis_converged = dits, bool(info[3])
+        res.n_window, res.n_frozen = nwin, nfrz
+        res.sv_min_projection, res.dis_gap_min = float(dsums[0]), float(dsums[1])
         return res
 
     def _wannier_model(self, mesh, hop, R, centers, split):
