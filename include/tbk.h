@@ -730,6 +730,35 @@ int tbk_mean_field_mesh(tbk_ctx* ctx, int dim_k, int norb, int nspin, const doub
                         int history, double tol, int max_iter, int check_every, double* x_in, double* x_out, double* mu_out,
                         double* dens, int32_t* R_out, double* energies, double* res_hist, double* occ_hist, int32_t* info);
 
+/* ---- selected entries of the density matrix, and self-consistent Bogoliubov-de Gennes superconductivity ----
+ * tbk_density_matrix_pairs_mesh: out[nt] c128 = D_{i_p j_p}(R_p) of tbk_density_matrix_mesh -- the same definition, phase, occupation
+ *   rule and chunks -- for nt = 1..2^20 triples ij[nt][2] (state indices), R[nt][dim_k] (|R_a| < 2^30), without forming any matrix:
+ *   what a self-consistency loop consumes.  The partition depends on (mesh, nsta, dim_k) alone, not on the list: two calls give the
+ *   same bits, and a triple gives the same bits alone and inside any list.
+ *
+ * tbk_bdg_mesh: H_int of tbk_mean_field_mesh, decoupled in the Hartree, Fock and pairing channels (each on or off) on the NAMBU model
+ *   of N = 2 nsta states, Psi = (c, c+): particle state a, hole state nsta + a at the same position, hole block -conj of the particle
+ *   block, Fermi level 0.  With D its density matrix: n_a = D_aa(0), <c+_{b,R} c_{a,0}> = D_ab(R), F_ab(R) = <c_{b,R} c_{a,0}> =
+ *   D_{a,nsta+b}(R); the pairing field of an entry (V, a, b, R) is Delta = V F_ab(R) on the hop (a -> nsta + b, R) and -Delta on
+ *   (b -> nsta + a, -R).  The tables (orb[N][dim_k], onsite[N] c128, hops over N spinless orbitals) are those of the bare Nambu model
+ *   without pairing: at Fermi level 0 with have_nel != 0, else at the given Fermi level nel_or_mu.
+ *   parameters   x[np]: the occupations of the states some V touches (ascending), with fock Re, Im of D_ab(R) per entry, with pairing
+ *                Re, Im of F_ab(R) per entry, with have_nel != 0 mu last; np <= 2^20.  x_start[np] is the first x_in.
+ *   filling      have_nel != 0: any 0 < nel_or_mu < nsta, and x_out[mu] = x_in[mu] + mu_step (n_electrons - N_out), mu_step > 0.
+ *   loop         mixing, history, tol, max_iter, check_every as in tbk_mean_field_mesh; nsta <= 1024, at most 4096 lattice vectors.
+ * Out: x_in[np], x_out[np] of the last iteration; energies[7] = {E = <H - mu N> + mu N, S, F = E - kT S, F - mu N, N_out, mu_in,
+ * min |E_n(k)| over the mesh} per cell; res_hist[max_iter], occ_hist[max_iter][nsta] (the first `iterations` rows are written);
+ * info[5] = {iterations, converged, nR, np, triples}.  Fixed-order sums, no floating-point atomics: two calls give the same bits, and
+ * max_iter = k gives the first k rows of a longer run.                                                                             */
+int tbk_density_matrix_pairs_mesh(tbk_model* model, const int32_t* mesh, double mu, double kT, int64_t nt, const int32_t* ij,
+                                  const int32_t* R, double* out);
+int tbk_bdg_mesh(tbk_ctx* ctx, int dim_k, int nsta, const double* orb, const double* onsite, int64_t nhop, const int32_t* hop_i,
+                 const int32_t* hop_j, const int32_t* hop_R, const double* hop_amp, const int32_t* mesh, int nint,
+                 const int32_t* int_ab, const int32_t* int_R, const double* int_V, int hartree, int fock, int pairing,
+                 int have_nel, double nel_or_mu, double kT, const double* x_start, double mu_step, double mixing, int history,
+                 double tol, int max_iter, int check_every, double* x_in, double* x_out, double* energies, double* res_hist,
+                 double* occ_hist, int32_t* info);
+
 /* ---- projected and maximally localised Wannier functions on a k mesh ----
  * nw <= 16 functions from the nb <= 32 bands `bands` (distinct, the same at every k) of k_uniform_mesh(mesh), dim_k 1..3, every
  * N_a >= 3, nsta <= 2048, N_k nsta nw <= 2^26 (the rotated states stay on the device).

@@ -120,6 +120,9 @@ SIGNATURES = {
     "tbk_unfold_spectral_list": (_i, [_p, _dp, _i64, _i, _ip, _dp, _dp, C.c_double, _i, _dp, C.c_double, _i, _dp]),
     "tbk_mean_field_mesh": (_i, [_p, _i, _i, _i, _dp, _dp, _i64, _ip, _ip, _ip, _dp, _ip, _i, _ip, _ip, _dp, _i, _i, C.c_double, C.c_double,
                                  _i, _dp, C.c_double, _i, C.c_double, _i, _i, _dp, _dp, _dp, _dp, _ip, _dp, _dp, _dp, _ip]),
+    "tbk_density_matrix_pairs_mesh": (_i, [_p, _ip, C.c_double, C.c_double, _i64, _ip, _ip, _dp]),
+    "tbk_bdg_mesh": (_i, [_p, _i, _i, _dp, _dp, _i64, _ip, _ip, _ip, _dp, _ip, _i, _ip, _ip, _dp, _i, _i, _i, _i, C.c_double, C.c_double, _dp,
+                          C.c_double, C.c_double, _i, C.c_double, _i, _i, _dp, _dp, _dp, _dp, _dp, _ip]),
     "tbk_wannier_mesh": (_i, [_p, _ip, _i, _ip, _i, _i64, _ip, _ip, _ip, _dp, _i, _ip, _dp, _dp, _i, C.c_double, _i, _i, _i, _ip, _dp, _dp, _dp,
                               _dp, _dp, _ip]),
     "tbk_wannier_dis_mesh": (_i, [_p, _ip, _i, _ip, _i, _i64, _ip, _ip, _ip, _dp, _i, _ip, _dp, _dp, _dp, _dp, _i, C.c_double, C.c_double, _i,

@@ -21,7 +21,7 @@
 // stream synchronisation, and the solver's status words with it.  No floating-point atomics; two calls give the same bits, and so do
 // the resident and the two-pass form (same chunks, same groups, same order).
 #include <math.h>
-#include "tbk_mf.h"
+#include "tbk_mf_dev.h"
 #include "tbk_occ_dev.h"
 
 // ---------------------------------------------------------------- kernels
@@ -197,31 +197,18 @@ int mf_loop(MfRun& S, const MfArgs& A, int start_mode, int* iterations, int* con
                            S.buf<double>(MfPlan::XIN));
         TBK_HIP(hipGetLastError());
     }
-    *iterations = 0;
-    *converged = 0;
-    for (int it = 0; it < A.max_iter; ++it) {
-        if ((rc = mf_pass(S))) return rc;
-        {
+    return mf_iterate(
+        ctx, "tbk_mean_field_mesh", S.n, A.max_iter, A.check_every, A.tol, S.buf<double>(MfPlan::RESH), [&]() { return mf_pass(S); },
+        [&](int it) -> int {
             ProfScope ps(ctx, "mf_mix");
             hipLaunchKernelGGL(k_mf_mix, dim3(1), dim3(256), 0, ctx->stream, S.np, it, A.history, A.mixing, S.n, (double)S.pl.npts,
                                (const double*)S.buf<cd>(MfPlan::ACC), S.buf<double>(MfPlan::XIN), (const double*)S.buf<double>(MfPlan::XOUT),
                                S.buf<double>(MfPlan::XPREV), S.buf<double>(MfPlan::RINGX), S.buf<double>(MfPlan::RINGR),
                                S.buf<double>(MfPlan::SMALL), S.buf<double>(MfPlan::RESH), S.buf<double>(MfPlan::OCCH));
             TBK_HIP(hipGetLastError());
-        }
-        *iterations = it + 1;
-        if ((it + 1) % A.check_every != 0 && it + 1 != A.max_iter) continue;
-        double res = 0.0;                                           // the check: one 8-byte copy behind a synchronisation
-        TBK_HIP(hipMemcpyAsync(&res, S.buf<double>(MfPlan::RESH) + it, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-        TBK_HIP(hipStreamSynchronize(ctx->stream));
-        if ((rc = tbk_eigh_check(ctx, S.n))) return rc;
-        TBK_REQUIRE(std::isfinite(res), TBK_ENOCONV, "tbk_mean_field_mesh: the residual of iteration %d is not finite", it + 1);
-        if (A.tol > 0.0 && res <= A.tol) {
-            *converged = 1;
-            break;
-        }
-    }
-    return TBK_OK;
+            return TBK_OK;
+        },
+        iterations, converged);
 }
 }  // namespace
 

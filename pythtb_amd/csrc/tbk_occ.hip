@@ -31,18 +31,7 @@
 #include <math.h>
 #include "tbk_occ_dev.h"
 
-// ---------------------------------------------------------------- occupation
-// f and, where wanted, the entropy term s = -f ln f - (1 - f) ln(1 - f) of x = (E - mu) / kT (tbk_kubo.h's fermi_terms)
-__device__ __forceinline__ double occ_fermi(const double e, const double mu, const double kT, double* s) {
-    if (kT == 0.0) {
-        if (s) *s = 0.0;
-        return e <= mu ? 1.0 : 0.0;
-    }
-    const FermiTerms ft = fermi_terms((e - mu) / kT);
-    if (s) *s = ft.entropy();
-    return ft.f();
-}
-
+// ---------------------------------------------------------------- occupation: occ_fermi (tbk_occ_dev.h)
 // the Fermi scan's source (k_kubo_fermi, the mesh as one row of N_k points): a level adds (1, E) to its bin
 struct OccEvSrc {
     const double* ev;   // [n][npts]

@@ -242,6 +242,14 @@ class mean_field_result(object):
     pass
 
 
+class bdg_result(object):
+    """What `tb_model.bdg_mesh` returns: model (the Nambu model), normal_model, fermi_level, n_electrons, occupations, pairing,
+    anomalous, gap, energy, entropy, free_energy, grand_potential, residuals, history, iterations, converged, field (the parameter
+    vector the last iteration produced; `_x` is the one it solved in, which `model` carries and a restart begins from), and on
+    request nambu_density and R_list."""
+    pass
+
+
 class wannier_result(object):
     """What `tb_model.wannier_mesh` returns: model, hoppings, R_list, centers, spreads, omega_i, omega_od, omega_d, omega, sv_min,
     history, iterations, converged, b_vectors, b_weights, and on request functions and gauge.  `wannier_disentangle_mesh` adds
@@ -1512,6 +1520,337 @@ class tb_model(object):
             Rf[self._per] = R
             m.set_hop(blk if ns == 2 else complex(blk[0, 0]), i, j, Rf, mode="add", allow_conjugate_pair=True)
         return m
+
+    # ------------------------------------------------------------------ Bogoliubov-de Gennes superconductivity (extension)
+    def _state_table(self):
+        """The state-level table {(a, b, R over the periodic directions): t_ab(R)}: on-site blocks at R = 0 and both directions of
+        every hop (a = orbital * nspin + spin)."""
+        ns, dk = self._nspin, self._dim_k
+        tab = {}
+        zero = (0,) * dk
+        for o in range(self._norb):
+            blk = np.array(self._site_energies[o], dtype=complex).reshape(ns, ns)
+            for s in range(ns):
+                for t in range(ns):
+                    if blk[s, t] != 0.0:
+                        tab[(o * ns + s, o * ns + t) + zero] = tab.get((o * ns + s, o * ns + t) + zero, 0.0) + complex(blk[s, t])
+        for hop in self._hoppings:
+            blk = np.array(hop[0], dtype=complex).reshape(ns, ns)
+            R = tuple(int(x) for x in np.array(hop[3], dtype=int)[self._per]) if dk > 0 else ()
+            mR = tuple(-x for x in R)
+            for s in range(ns):
+                for t in range(ns):
+                    a, b = hop[1] * ns + s, hop[2] * ns + t
+                    tab[(a, b) + R] = tab.get((a, b) + R, 0.0) + complex(blk[s, t])
+                    tab[(b, a) + mR] = tab.get((b, a) + mR, 0.0) + complex(np.conj(blk[s, t]))
+        return tab
+
+    def _pairing_arg(self, pairing):
+        """The checked pairing list of `nambu_model`: [(Delta, a, b, R over the periodic directions)]."""
+        n, dk = self._nsta, self._dim_k
+        out, seen = [], set()
+        for ent in (pairing if pairing is not None else []):
+            try:
+                D, a, b, R = ent
+                D = complex(D)
+            except (TypeError, ValueError):
+                raise Exception("\n\npairing must be a list of (Delta, a, b, R) with complex Delta.")
+            if not (np.isfinite(D.real) and np.isfinite(D.imag)):
+                raise Exception("\n\npairing: Delta must be finite.")
+            if not (_is_int(a) and _is_int(b)) or a < 0 or a >= n or b < 0 or b >= n:
+                raise Exception("\n\npairing: state index out of scope.")
+            Rf = np.array(R)
+            if Rf.shape != (self._dim_r,) or Rf.dtype == object or np.any(Rf != np.round(Rf)):
+                raise Exception("\n\npairing: R must hold dim_r integers, as in set_hop.")
+            Rp = tuple(int(x) for x in np.array(Rf, dtype=np.int64)[self._per]) if dk > 0 else ()
+            if any(abs(x) >= 2 ** 30 for x in Rp):
+                raise Exception("\n\npairing: every component of R must be below 2**30 in magnitude.")
+            if a == b and not any(Rp):
+                raise Exception("\n\npairing: (a, a, R = 0) vanishes by antisymmetry.")
+            k1, k2 = (int(a), int(b)) + Rp, (int(b), int(a)) + tuple(-x for x in Rp)
+            if k1 in seen or k2 in seen:
+                raise Exception("\n\npairing: an entry is given once and means the antisymmetric pair; one was given twice.")
+            seen.add(k1)
+            out.append((D, int(a), int(b), Rp))
+        return out
+
+    def nambu_model(self, fermi_level, pairing=None):
+        """Extension: the Bogoliubov-de Gennes (Nambu) model of this model, a new spinless `tb_model` with 2 nsta orbitals; this
+        model is not edited.  With Psi_k = (c_k, c+_{-k}) and H = 1/2 sum_k Psi+_k H_BdG(k) Psi_k + const,
+
+            H_BdG(k) = [[h(k) - mu, Delta(k)], [Delta(k)+, -h(-k)^T + mu]]
+
+        Particle orbital a is state a of this model (orbital * nspin + spin, the index of `density_matrix_mesh`) at that
+        orbital's position, hole orbital nsta + a sits at the same position.  With t_ab(R) the state-level hopping table: the
+        particle block is t with fermi_level subtracted on the diagonal; the hole block is the hop (a -> b, R) with amplitude
+        -conj(t_ab(R)) and the on-site energy -eps_a + fermi_level, which is -h(-k)^T with the orbital positions in the phases,
+        inversion symmetry or not.  pairing: a list of (Delta, a, b, R) -- complex Delta, state indices, full-dimension R as
+        in `set_hop` -- each meaning Delta c+_{a,0} c+_{b,R} + h.c.: the hop (a -> nsta + b, R) with amplitude Delta and its
+        antisymmetric mirror (b -> nsta + a, -R) with -Delta.  An entry and its mirror given twice is refused, and so is
+        (a, a, R = 0), which vanishes.  nsta <= 1024.
+
+        The density matrix of the result at Fermi level 0 holds every expectation value: n_a = D_aa(0), <c+_{b,R} c_{a,0}> =
+        D_ab(R), F_ab(R) = <c_{b,R} c_{a,0}> = D_{a,nsta+b}(R), and the hole block is delta - conj(D_ab(R)).  Every call that
+        takes a `tb_model` takes it: `berry_phase` of a topological superconductor, `cut_piece` for Majorana end states, the
+        quasi-particle DOS."""
+        n, dk = self._nsta, self._dim_k
+        if n > 1024:
+            raise Exception("\n\nnambu_model: at most 1024 states.")
+        try:
+            mu = float(fermi_level)
+        except (TypeError, ValueError):
+            raise Exception("\n\nfermi_level must be one finite number.")
+        if not np.isfinite(mu):
+            raise Exception("\n\nfermi_level must be finite.")
+        pair = self._pairing_arg(pairing)
+        zero = (0,) * dk
+        tab = {}
+        for key, amp in self._state_table().items():
+            a, b, R = key[0], key[1], key[2:]
+            tab[key] = tab.get(key, 0.0) + amp
+            hk = (n + a, n + b) + R
+            tab[hk] = tab.get(hk, 0.0) - np.conj(amp)
+        for a in range(n):
+            tab[(a, a) + zero] = tab.get((a, a) + zero, 0.0) - mu
+            tab[(n + a, n + a) + zero] = tab.get((n + a, n + a) + zero, 0.0) + mu
+        for D, a, b, R in pair:
+            mR = tuple(-x for x in R)
+            for key, amp in (((a, n + b) + R, D), ((b, n + a) + mR, -D), ((n + b, a) + mR, np.conj(D)), ((n + a, b) + R, -np.conj(D))):
+                tab[key] = tab.get(key, 0.0) + amp
+        return self._model_from_state_table(tab, 2)
+
+    def _model_from_state_table(self, tab, copies):
+        """A spinless tb_model with `copies` * nsta orbitals -- copy c of state a at the position of a's orbital -- from a
+        Hermitian state-level table {(a, b, R): amplitude}; exact zeros are dropped."""
+        dk, ns = self._dim_k, self._nspin
+        orb = np.tile(np.repeat(self._orb, ns, axis=0), (copies, 1))
+        m = tb_model(dk, self._dim_r, self._lat.copy(), orb, per=list(self._per), nspin=1)
+        N = orb.shape[0]
+        zero = (0,) * dk
+        ons = np.zeros(N)
+        for key in sorted(tab):
+            amp = complex(tab[key])
+            a, b, R = key[0], key[1], key[2:]
+            if a == b and R == zero:
+                ons[a] = amp.real
+                continue
+            if amp == 0.0 or (a, b) + R > (b, a) + tuple(-x for x in R):   # (the mirror is implied)
+                continue
+            entry = [amp, a, b]
+            if dk > 0:
+                Rf = np.zeros(self._dim_r, dtype=int)
+                Rf[self._per] = R
+                entry.append(Rf)
+            m._hoppings.append(entry)
+        m.set_onsite(list(ons))
+        m._tbk_epoch += 1
+        return m
+
+    def density_matrix_pairs_mesh(self, mesh_size, fermi_level, kT=0.0, pairs=None):
+        """Extension: selected entries of `density_matrix_mesh` -- the complex vector D_{i_p j_p}(R_p) for a list `pairs` of up to
+        2**20 triples (i, j, R): state indices and a lattice vector over the periodic directions (`(dim_k,)` integers,
+        |R_a| < 2**30; None is R = 0).  Definition, phase, occupation rule and chunking are those of `density_matrix_mesh`, but
+        no matrix is formed: a triple costs one weighted sum over the bands per k point, which is what a self-consistency loop
+        consumes (a handful of bond orders and occupations instead of nR nsta**2 entries).  Repeated triples are allowed.
+        Fixed-order sums and a partition that does not depend on the list: two calls give the same bits, and a triple gives
+        the same bits alone and inside any list."""
+        mesh, nk, kT = self._occ_args("density_matrix_pairs_mesh", mesh_size, kT)
+        try:
+            fermi_level = float(fermi_level)
+        except (TypeError, ValueError):
+            raise Exception("\n\nfermi_level must be one finite number.")
+        if not np.isfinite(fermi_level):
+            raise Exception("\n\nfermi_level must be finite.")
+        n, dk = self._nsta, self._dim_k
+        if pairs is None:
+            raise Exception("\n\ndensity_matrix_pairs_mesh needs a list of (i, j, R) triples.")
+        pairs = list(pairs)
+        if len(pairs) < 1 or len(pairs) > 2 ** 20:
+            raise Exception("\n\npairs must hold 1..2**20 triples (i, j, R).")
+        ij = np.zeros((len(pairs), 2), dtype=np.int32)
+        Rs = np.zeros((len(pairs), dk), dtype=np.int32)
+        for p, ent in enumerate(pairs):
+            try:
+                i, j, R = ent
+            except (TypeError, ValueError):
+                raise Exception("\n\npairs must hold triples (i, j, R).")
+            if not (_is_int(i) and _is_int(j)) or i < 0 or i >= n or j < 0 or j >= n:
+                raise Exception("\n\npairs: state index out of scope.")
+            Rf = np.zeros(dk) if R is None else np.array(R)
+            if Rf.shape != (dk,) or Rf.dtype == object or not np.all(np.isfinite(Rf.astype(float))) or np.any(Rf != np.round(Rf)):
+                raise Exception("\n\npairs: R must hold dim_k integers.")
+            if np.any(np.abs(Rf) >= 2 ** 30):
+                raise Exception("\n\npairs: every component of R must be below 2**30 in magnitude.")
+            ij[p] = (i, j)
+            Rs[p] = Rf
+        out = np.zeros(len(pairs), dtype=complex)
+        _lib.check(_lib.lib.tbk_density_matrix_pairs_mesh(self._device_model(), _lib.iptr(mesh), fermi_level, kT, len(pairs),
+                                                          _lib.iptr(ij.reshape(-1)), _lib.iptr(Rs.reshape(-1)), _lib.dptr(out.view(float))))
+        return out
+
+    def bdg_mesh(self, mesh_size, interaction=None, n_electrons=None, fermi_level=None, kT=0.0, U=None, hartree=True, fock=False,
+                 pairing=True, start=None, pairing_seed=0.1, mu_start=None, mu_step=1.0, mixing=0.5, history=4, tol=1e-10,
+                 max_iter=200, check_every=1, return_density=False):
+        """Extension: self-consistent Bogoliubov-de Gennes mean-field theory of the density-density interaction of
+        `mean_field_mesh` (the same `interaction` / `U`), iterated on `k_uniform_mesh(mesh_size)` with the whole loop on the
+        device.  An entry (V, a, b, R) -- the bond and its mirror -- is decoupled in up to three channels on the Nambu model of
+        `nambu_model`: hartree (the on-site energy of a gets sum V n_b), fock (the entry (a, b, R) gets -V D_ab(R)) and pairing
+        (Delta_ab(R) = V F_ab(R), F_ab(R) = <c_{b,R} c_{a,0}>, on the hop (a -> nsta + b, R) and -Delta on its mirror).
+
+        The unknown is the real vector x: the occupations of the touched states (ascending), Re and Im of D_ab(R) per entry
+        with fock, Re and Im of F_ab(R) per entry with pairing, and -- with n_electrons given -- mu last.  Exactly one of
+        n_electrons (any value in (0, nsta): N is continuous in a paired state) and fermi_level.  With n_electrons the chemical
+        potential is iterated with the field: x_out[mu] = x_in[mu] + mu_step (n_electrons - N_out).  start: None (occupations
+        n_electrons / nsta, or 1/2 at a given fermi_level; D = 0; every F = pairing_seed, since F = 0 is always a fixed point;
+        mu = mu_start, by default the mean bare on-site energy plus the mean Hartree shift of the start occupations), an array
+        of occupations `(nsta,)` / `(norb, nspin)`, or an earlier `bdg_result` (restart).  mixing, history, tol, max_iter and
+        check_every as in `mean_field_mesh`; for attractive interactions the mu update makes plain linear mixing unstable, use
+        history >= 1.
+
+        Returns a `bdg_result`: model (the Nambu `tb_model` of the last x_in: feed it to any other call), normal_model (this
+        model with the Hartree and Fock field, no mu), fermi_level, n_electrons, occupations, pairing (the list of
+        (Delta, a, b, R) `nambu_model` takes), anomalous (the F values), gap (min |E_n(k)| over the mesh), energy = <H - mu N> +
+        mu N, entropy, free_energy = energy - kT entropy, grand_potential = free_energy - mu N, residuals, history (the
+        occupations after every iteration), iterations, converged (False is not an exception), field (the x the last
+        iteration produced); with return_density=True nambu_density `(nR, 2 nsta, 2 nsta)` and R_list, the whole density
+        matrix of `model` at Fermi level 0 from one closing pass of `density_matrix_mesh`.  Fixed-order sums: two calls give
+        the same bits, and max_iter = k gives the first k history rows of a longer run."""
+        mesh, nk, kT = self._occ_args("bdg_mesh", mesh_size, kT)
+        ns, no, dk, n = self._nspin, self._norb, self._dim_k, self._nsta
+        if n > 1024:
+            raise Exception("\n\nbdg_mesh: at most 1024 states.")
+        if (n_electrons is None) == (fermi_level is None):
+            raise Exception("\n\nbdg_mesh needs exactly one of n_electrons and fermi_level.")
+        try:
+            filling = float(n_electrons if n_electrons is not None else fermi_level)
+        except (TypeError, ValueError):
+            raise Exception("\n\nn_electrons / fermi_level must be one finite number.")
+        if not np.isfinite(filling):
+            raise Exception("\n\nn_electrons / fermi_level must be finite.")
+        have_nel = n_electrons is not None
+        if have_nel and not 0.0 < filling < n:
+            raise Exception("\n\nn_electrons must lie in the open interval (0, %d)." % n)
+        if not _is_int(history) or history < 0 or history > 8:
+            raise Exception("\n\nhistory must be an integer in 0..8.")
+        if not _is_int(max_iter) or max_iter < 1 or max_iter > 65536:
+            raise Exception("\n\nmax_iter must be an integer in 1..65536.")
+        if not _is_int(check_every) or check_every < 1:
+            raise Exception("\n\ncheck_every must be an integer >= 1.")
+        mixing, tol, mu_step, seed = float(mixing), float(tol), float(mu_step), float(pairing_seed)
+        if not 0.0 < mixing <= 1.0:
+            raise Exception("\n\nmixing must satisfy 0 < mixing <= 1.")
+        if not (np.isfinite(tol) and tol >= 0.0):
+            raise Exception("\n\ntol must be finite and >= 0.")
+        if not (np.isfinite(mu_step) and mu_step > 0.0):
+            raise Exception("\n\nmu_step must be finite and > 0.")
+        if not np.isfinite(seed):
+            raise Exception("\n\npairing_seed must be finite.")
+        hartree, fock, pairing = bool(hartree), bool(fock), bool(pairing)
+        if not (hartree or fock or pairing):
+            raise Exception("\n\nbdg_mesh: every channel is switched off.")
+        try:
+            ab, Rs, Vs = self._mf_entries(interaction, U)
+        except Exception as err:
+            raise Exception(str(err).replace("mean_field_mesh", "bdg_mesh"))
+        nint = len(Vs)
+        touched = sorted(set(ab.reshape(-1).tolist()))
+        occ_par = {a: p for p, a in enumerate(touched)}
+        nocc = len(touched)
+        par_d = nocc if fock else -1
+        par_f = nocc + (2 * nint if fock else 0) if pairing else -1
+        npar = nocc + 2 * nint * (int(fock) + int(pairing)) + int(have_nel)
+        par_mu = npar - 1 if have_nel else -1
+        Rl = [tuple([0] * dk)]
+        for R in Rs:
+            if tuple(int(x) for x in R) not in Rl:
+                Rl.append(tuple(int(x) for x in R))
+        nR = len(Rl)
+        if nR > 4096:
+            raise Exception("\n\nbdg_mesh: at most 4096 distinct lattice vectors.")
+        if npar > 2 ** 20:
+            raise Exception("\n\nbdg_mesh: at most 2**20 mean-field parameters.")
+        if return_density and nR * 4 * n * n > 2 ** 22:
+            raise Exception("\n\nbdg_mesh: with return_density, nR * (2 nsta)**2 must be at most 2**22.")
+        key = (ab.tobytes(), Rs.tobytes(), Vs.tobytes(), hartree, fock, pairing, have_nel, n)
+        eps = np.array([np.real(np.array(self._site_energies[a // ns]).reshape(ns, ns)[a % ns, a % ns]) for a in range(n)])
+        if isinstance(start, bdg_result):
+            if start._key != key:
+                raise Exception("\n\nstart: the result belongs to another model size, interaction, channel or filling setting.")
+            x0 = np.array(start._x, dtype=float)
+        else:
+            if start is None:
+                occ = np.full(n, filling / n if have_nel else 0.5)
+            else:
+                st = np.array(start, dtype=float)
+                if not (st.size == n and st.shape in ((n,), (no, ns))):
+                    raise Exception("\n\nstart must be None, occupations of shape (nsta,) or (norb, nspin), or an earlier result.")
+                occ = st.reshape(n)
+            x0 = np.zeros(npar)
+            for a in touched:
+                x0[occ_par[a]] = occ[a]
+            if pairing:
+                x0[par_f:par_f + 2 * nint:2] = seed
+            if have_nel:
+                if mu_start is None:
+                    shift = np.zeros(n)
+                    if hartree:
+                        for e in range(nint):
+                            a, b = int(ab[e, 0]), int(ab[e, 1])
+                            shift[a] += Vs[e] * occ[b]
+                            shift[b] += Vs[e] * occ[a]
+                    x0[par_mu] = float(np.mean(eps) + np.mean(shift))
+                else:
+                    x0[par_mu] = float(mu_start)
+        if not np.all(np.isfinite(x0)):
+            raise Exception("\n\nstart must be finite.")
+        bare = self.nambu_model(0.0 if have_nel else filling)
+        orb_per, onsite, hop_i, hop_j, hop_R, hop_amp = bare._flat_tables()
+        ctx = _lib.default_context()
+        x_in, x_out = np.zeros(npar), np.zeros(npar)
+        energies = np.zeros(7)
+        res_hist, occ_hist = np.zeros(max_iter), np.zeros((max_iter, n))
+        info = np.zeros(5, dtype=np.int32)
+        _lib.check(_lib.lib.tbk_bdg_mesh(
+            ctx.handle, dk, n, _lib.dptr(orb_per), _lib.dptr(onsite.view(float)), len(hop_i), _lib.iptr(hop_i), _lib.iptr(hop_j),
+            _lib.iptr(hop_R.reshape(-1)) if hop_R.size else None, _lib.dptr(hop_amp.view(float)) if hop_amp.size else None,
+            _lib.iptr(mesh), nint, _lib.iptr(ab.reshape(-1)), _lib.iptr(Rs.reshape(-1)), _lib.dptr(Vs), int(hartree), int(fock),
+            int(pairing), int(have_nel), filling, kT, _lib.dptr(x0), mu_step, mixing, int(history), tol, int(max_iter),
+            int(check_every), _lib.dptr(x_in), _lib.dptr(x_out), _lib.dptr(energies), _lib.dptr(res_hist), _lib.dptr(occ_hist),
+            _lib.iptr(info)))
+        if int(info[2]) != nR or int(info[3]) != npar:
+            raise Exception("\n\nbdg_mesh: the library laid out %d lattice vectors and %d parameters, not %d and %d."
+                            % (info[2], info[3], nR, npar))
+        its = int(info[0])
+        res = bdg_result()
+        mu_in = float(energies[5])
+        y = x_in.copy()
+        if not hartree:
+            y[:nocc] = 0.0                                         # (_mf_model adds V n_b for every entry)
+        res.normal_model = self._mf_model(ab, Rs, Vs, fock, occ_par, nocc, y)
+        res.pairing, res.anomalous = [], np.zeros(0, dtype=complex)
+        if pairing:
+            F_in = x_in[par_f:par_f + 2 * nint:2] + 1j * x_in[par_f + 1:par_f + 2 * nint:2]
+            res.anomalous = x_out[par_f:par_f + 2 * nint:2] + 1j * x_out[par_f + 1:par_f + 2 * nint:2]
+            for e in range(nint):
+                Rf = np.zeros(self._dim_r, dtype=int)
+                Rf[self._per] = Rs[e]
+                res.pairing.append((complex(Vs[e] * F_in[e]), int(ab[e, 0]), int(ab[e, 1]), Rf))
+        res.model = res.normal_model.nambu_model(mu_in, res.pairing)
+        res.fermi_level, res.n_electrons = mu_in, float(energies[4])
+        occ = occ_hist[its - 1].copy()
+        res.occupations = occ.reshape(no, 2) if ns == 2 else occ
+        res.gap = float(energies[6])
+        res.energy, res.entropy, res.free_energy, res.grand_potential = (float(energies[0]), float(energies[1]), float(energies[2]),
+                                                                         float(energies[3]))
+        res.residuals = res_hist[:its].copy()
+        res.history = occ_hist[:its].reshape((its, no, 2) if ns == 2 else (its, n)).copy()
+        res.iterations, res.converged = its, bool(info[1])
+        res.field, res._x, res._key = x_out, x_in, key
+        res.nambu_density, res.R_list = None, None
+        if return_density:
+            res.R_list = np.ascontiguousarray(Rl, dtype=np.int32).reshape(nR, dk)
+            res.nambu_density = res.model.density_matrix_mesh(mesh_size, 0.0, kT, res.R_list)
+        return res
 
     # ------------------------------------------------------------------ Wannier functions (extension)
     def _wannier_bvectors(self, mesh, b_vectors="star"):
