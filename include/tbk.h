@@ -759,6 +759,46 @@ int tbk_bdg_mesh(tbk_ctx* ctx, int dim_k, int nsta, const double* orb, const dou
                  double tol, int max_iter, int check_every, double* x_in, double* x_out, double* energies, double* res_hist,
                  double* occ_hist, int32_t* info);
 
+/* ---- excitons: the Tamm-Dancoff Bethe-Salpeter operator, its dense states and its Haydock spectrum ----
+ * The bands are the model's own (for time-dependent Hartree-Fock: the model a converged tbk_mean_field_mesh produced), an insulator
+ * at kT = 0: the same number n_occ of levels at or below mu at every mesh point.  The interaction is the list of
+ * tbk_mean_field_mesh (a bond given once, state indices); E holds both directions of every bond, d_e = R + tau_b - tau_a.
+ * Transitions t = (k, v, c) over the mesh and the selected bands, X[k][v][c], Delta_t = E_c(k) - E_v(k):
+ *   H_ex = Delta + K^x - K^d,   (H_ex X)_vc(k) = Delta X_vc(k) + sum_a h_a conj(u_c[a]) u_v[a]
+ *                                                - sum_e V_e F_e e^{2 pi i k.d_e} conj(u_c[a]) u_v[b]
+ *   with T(k) = sum_vc X_vc(k) u_ck u_vk^+, F_e = (1/N) sum_k e^{-2 pi i k.d_e} T_ab(k), rho_b = (1/N) sum_k T_bb(k) and
+ *   h_a = sum_{e: a_e = a} V_e rho_{b_e}; `direct` = 0 drops K^d, `exchange` = 0 drops K^x.
+ *   bands        vsel / csel: nv / nc band indices (occupied / empty, 1..16 each); or null: the top nv occupied and the bottom nc
+ *                empty bands, 0 meaning all of them.  info[3] = {n_occ, nv, nc} as resolved.
+ *   dipoles      D^a_t = <u_c| dH/dk_a |u_v> / Delta_t (reduced k), S_ab = (1/N) <D^a|D^b>
+ * tbk_exciton_apply_mesh: out[nb][N_t] c128 = H_ex applied to vectors[nb][N_t] (nb = 1..16, of xnv x xnc bands per point, which must
+ *   be the selection's), gaps[N_t] = Delta_t; N_t <= 2^24 and N_k nsta (nv + nc) <= 2^26.
+ * tbk_exciton_states_mesh: N_t <= 2048 <= cap.  H_ex is formed by applying the operator to unit vectors in blocks of 16 and solved
+ *   by the dense solver: energies[N_t] ascending, dipoles[N_t][dim_k] c128 = <A^lambda|D^a>, sab[dim_k][dim_k] c128 = S_ab,
+ *   vectors[N_t][N_t] c128 (or null), scal[2] = {smallest, largest Delta_t}.
+ * tbk_exciton_spectrum_mesh: the Lanczos runs of a polarizability -- the full tensor (da = db = -1): one run from every D^a, then for
+ *   every pair a < b one from D^a + D^b and one from D^a + i D^b, dim_k^2 runs; one component: da == db one run, else D^da, D^db,
+ *   D^da + D^db, D^da + i D^db -- carried as one block through the same applications with alpha, beta, the three-term update and the
+ *   breakdown rule on the device: alpha[nrun][nsteps], beta[nrun][nsteps], norm2[nrun] = |start|^2, n_used[nrun] (a run whose beta
+ *   falls below 1e-10 max(largest |alpha| so far, largest Delta_t) ends there), sab, scal as above.
+ * tbk_exciton_reconstruct (host only): chi_ab(omega_w) = (1/N) <D^a| (H_ex - omega_w - i eta)^-1 |D^b> from those coefficients by
+ *   continued fractions: out[nw][dim_k][dim_k] c128 (da < 0) or out[nw].
+ * Fixed-order sums, no floating-point atomics, partitions that depend on (mesh, nv, nc) alone: two calls give the same bits, a vector
+ * gives the same bits alone and inside any block, and nsteps = k gives the first k coefficients of a longer run.                  */
+int tbk_exciton_apply_mesh(tbk_model* model, const int32_t* mesh, int nint, const int32_t* int_ab, const int32_t* int_R,
+                           const double* int_V, double mu, int nv, const int32_t* vsel, int nc, const int32_t* csel, int direct,
+                           int exchange, int nb, int xnv, int xnc, const double* vectors, double* out, double* gaps, int32_t* info);
+int tbk_exciton_states_mesh(tbk_model* model, const int32_t* mesh, int nint, const int32_t* int_ab, const int32_t* int_R,
+                            const double* int_V, double mu, int nv, const int32_t* vsel, int nc, const int32_t* csel, int direct,
+                            int exchange, int64_t cap, double* energies, double* dipoles, double* sab, double* vectors, double* scal,
+                            int32_t* info);
+int tbk_exciton_spectrum_mesh(tbk_model* model, const int32_t* mesh, int nint, const int32_t* int_ab, const int32_t* int_R,
+                              const double* int_V, double mu, int nv, const int32_t* vsel, int nc, const int32_t* csel, int direct,
+                              int exchange, int da, int db, int nsteps, double* alpha, double* beta, double* norm2, int32_t* n_used,
+                              double* sab, double* scal, int32_t* info);
+int tbk_exciton_reconstruct(int dim_k, int da, int db, int nsteps, const double* alpha, const double* beta, const double* norm2,
+                            const int32_t* n_used, int64_t npts, int nw, const double* omega, double eta, double* out);
+
 /* ---- projected and maximally localised Wannier functions on a k mesh ----
  * nw <= 16 functions from the nb <= 32 bands `bands` (distinct, the same at every k) of k_uniform_mesh(mesh), dim_k 1..3, every
  * N_a >= 3, nsta <= 2048, N_k nsta nw <= 2^26 (the rotated states stay on the device).

@@ -123,6 +123,11 @@ SIGNATURES = {
     "tbk_density_matrix_pairs_mesh": (_i, [_p, _ip, C.c_double, C.c_double, _i64, _ip, _ip, _dp]),
     "tbk_bdg_mesh": (_i, [_p, _i, _i, _dp, _dp, _i64, _ip, _ip, _ip, _dp, _ip, _i, _ip, _ip, _dp, _i, _i, _i, _i, C.c_double, C.c_double, _dp,
                           C.c_double, C.c_double, _i, C.c_double, _i, _i, _dp, _dp, _dp, _dp, _dp, _ip]),
+    "tbk_exciton_apply_mesh": (_i, [_p, _ip, _i, _ip, _ip, _dp, C.c_double, _i, _ip, _i, _ip, _i, _i, _i, _i, _i, _dp, _dp, _dp, _ip]),
+    "tbk_exciton_states_mesh": (_i, [_p, _ip, _i, _ip, _ip, _dp, C.c_double, _i, _ip, _i, _ip, _i, _i, _i64, _dp, _dp, _dp, _dp, _dp, _ip]),
+    "tbk_exciton_spectrum_mesh": (_i, [_p, _ip, _i, _ip, _ip, _dp, C.c_double, _i, _ip, _i, _ip, _i, _i, _i, _i, _i, _dp, _dp, _dp, _ip, _dp,
+                                       _dp, _ip]),
+    "tbk_exciton_reconstruct": (_i, [_i, _i, _i, _i, _dp, _dp, _dp, _ip, _i64, _i, _dp, C.c_double, _dp]),
     "tbk_wannier_mesh": (_i, [_p, _ip, _i, _ip, _i, _i64, _ip, _ip, _ip, _dp, _i, _ip, _dp, _dp, _i, C.c_double, _i, _i, _i, _ip, _dp, _dp, _dp,
                               _dp, _dp, _ip]),
     "tbk_wannier_dis_mesh": (_i, [_p, _ip, _i, _ip, _i, _i64, _ip, _ip, _ip, _dp, _i, _ip, _dp, _dp, _dp, _dp, _i, C.c_double, C.c_double, _i,

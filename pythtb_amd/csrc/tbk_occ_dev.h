@@ -49,3 +49,8 @@ int occ_pairs_stage(tbk_ctx* ctx, const ModelView& mv, const PdmPart& pl, const 
 // tbk_occ.hip: the thermal sums N, E, S of nmu Fermi levels over the resident levels, part[j][3][G] (the driver's final energies)
 __global__ __launch_bounds__(256) void k_occ_scan(const double* __restrict__ ev, const int64_t nlev, const int G, const double* __restrict__ mu,
                                                   const int nmu, const double kT, double* __restrict__ part);
+
+// tbk_pairs_dm.hip: acc[row] (+)= sum_g part[g][row], a wavefront per row (a double), the groups in a fixed order (the exciton
+// operator of tbk_bse.hip reduces its group partials with it)
+__global__ __launch_bounds__(256) void k_pairs_rows(const double* __restrict__ part, const int G, const int64_t nrows, const int accumulate,
+                                                    double* __restrict__ acc);

@@ -13,7 +13,7 @@ import numpy as np
 
 from . import _lib
 
-__all__ = ["tb_model", "kpm_reconstruct", "kpm_conductivity_reconstruct", "kpm_coefficients", "kpm_fermi_coefficients"]
+__all__ = ["tb_model", "exciton_reconstruct", "kpm_reconstruct", "kpm_conductivity_reconstruct", "kpm_coefficients", "kpm_fermi_coefficients"]
 
 
 def _is_int(a):
@@ -248,6 +248,65 @@ class bdg_result(object):
     vector the last iteration produced; `_x` is the one it solved in, which `model` carries and a restart begins from), and on
     request nambu_density and R_list."""
     pass
+
+
+class exciton_result(object):
+    """What `tb_model.exciton_states_mesh` returns: energies `(N_t,)` ascending, dipoles d^a_lambda `(N_t, dim_k)`, gap (the smallest
+    transition energy), binding = gap - energies[0], dipole_norm S_ab `(dim_k, dim_k)`, n_occ, valence and conduction (the selected
+    bands), mesh, and on request vectors `(N_t, *mesh, nv, nc)`."""
+
+    def polarizability(self, omega, eta, dirs=None):
+        """chi_ab(w) = (1/N) sum_lambda conj(d^a_lambda) d^b_lambda / (Omega_lambda - w - i eta), summed on the host:
+        `(nw, dim_k, dim_k)`, or `(nw,)` for dirs=(a, b).  omega and eta by the rules of `optical_conductivity_mesh`."""
+        w = _sweep_args(omega, eta, 0.0, 0.0)
+        dk = self.dipoles.shape[1]
+        res = 1.0 / (self.energies[None, :] - w[:, None] - 1j * float(eta))
+        if dirs is None:
+            return np.einsum("la,lb,wl->wab", np.conj(self.dipoles), self.dipoles, res) / self._nk
+        a, b = _exciton_dirs(dirs, dk)
+        return (res @ (np.conj(self.dipoles[:, a]) * self.dipoles[:, b])) / self._nk
+
+
+class exciton_coefficients(object):
+    """The Lanczos coefficients of `tb_model.exciton_spectrum_mesh`: alpha and beta `(n_runs, n_steps)`, norm2 `(n_runs,)` (the
+    squared norms of the start vectors), n_used `(n_runs,)`, runs (a list of (a, b, kind): kind 0 starts from D^a, 1 from
+    D^a + D^b, 2 from D^a + i D^b), dim_k, dirs, n_k.  `exciton_reconstruct` turns them into chi at any frequencies; whoever wants
+    Ritz values diagonalises the tridiagonal matrix of a run."""
+    pass
+
+
+class exciton_spectrum(object):
+    """What `tb_model.exciton_spectrum_mesh` returns: chi `(nw, dim_k, dim_k)` or `(nw,)`, dipole_norm, gap, n_used, and on request
+    coefficients (an `exciton_coefficients`)."""
+    pass
+
+
+def _exciton_dirs(dirs, dk):
+    dirs = list(dirs)
+    if len(dirs) != 2 or not all(_is_int(d) for d in dirs):
+        raise Exception("\n\ndirs must be two integer axes.")
+    if min(dirs) < 0 or max(dirs) >= dk:
+        raise Exception("\n\nDirection for the polarizability out of bounds.")
+    return int(dirs[0]), int(dirs[1])
+
+
+def exciton_reconstruct(coefficients, omega, eta):
+    """chi_ab(w) of `tb_model.exciton_spectrum_mesh` at other frequencies or another eta from its Lanczos coefficients: the
+    continued fractions of the runs and the polarisation algebra, on the host, no device call.  The same w gives the same bits
+    alone and inside a list."""
+    c = coefficients
+    if not isinstance(c, exciton_coefficients):
+        raise Exception("\n\nexciton_reconstruct needs the coefficients of exciton_spectrum_mesh.")
+    w = _sweep_args(omega, eta, 0.0, 0.0)
+    dk = c.dim_k
+    da, db = (-1, -1) if c.dirs is None else c.dirs
+    out = np.zeros((w.size, dk, dk) if da < 0 else (w.size,), dtype=complex)
+    alpha, beta = np.ascontiguousarray(c.alpha, dtype=float), np.ascontiguousarray(c.beta, dtype=float)
+    _lib.check(_lib.lib.tbk_exciton_reconstruct(dk, da, db, alpha.shape[1], _lib.dptr(alpha), _lib.dptr(beta),
+                                                _lib.dptr(np.ascontiguousarray(c.norm2, dtype=float)),
+                                                _lib.iptr(np.ascontiguousarray(c.n_used, dtype=np.int32)), int(c.n_k), int(w.size),
+                                                _lib.dptr(w), float(eta), _lib.dptr(out.view(float))))
+    return out
 
 
 class wannier_result(object):
@@ -1520,6 +1579,166 @@ class tb_model(object):
             Rf[self._per] = R
             m.set_hop(blk if ns == 2 else complex(blk[0, 0]), i, j, Rf, mode="add", allow_conjugate_pair=True)
         return m
+
+    # ------------------------------------------------------------------ excitons: Tamm-Dancoff BSE (extension)
+    def _exciton_args(self, what, mesh_size, interaction, U, fermi_level, valence, conduction):
+        """The checked arguments the three exciton calls share: (mesh, N_k, ab, Rs, Vs, mu, (nv, vsel), (nc, csel))."""
+        mesh, nk, _ = self._occ_args(what, mesh_size, 0.0)
+        if self._nsta > 2048:
+            raise Exception("\n\n%s: at most 2048 states." % what)
+        try:
+            mu = float(fermi_level)
+        except (TypeError, ValueError):
+            raise Exception("\n\nfermi_level must be one finite number.")
+        if not np.isfinite(mu):
+            raise Exception("\n\nfermi_level must be finite.")
+        ab, Rs, Vs = self._mf_entries(interaction, U)
+        sel = []
+        for name, arg, kind in (("valence", valence, "occupied"), ("conduction", conduction, "empty")):
+            if arg is None:
+                sel.append((0, None))
+            elif _is_int(arg):
+                if arg < 1:
+                    raise Exception("\n\n%s: no %s band selected." % (name, kind))
+                if arg > 16:
+                    raise Exception("\n\n%s: at most 16 bands." % name)
+                sel.append((int(arg), None))
+            else:
+                idx = list(arg)
+                if len(idx) < 1:
+                    raise Exception("\n\n%s: no %s band selected." % (name, kind))
+                if len(idx) > 16:
+                    raise Exception("\n\n%s: at most 16 bands." % name)
+                if not all(_is_int(b) for b in idx) or min(idx) < 0 or max(idx) >= self._nsta or len(set(idx)) != len(idx):
+                    raise Exception("\n\n%s must be an integer or a list of distinct band indices." % name)
+                sel.append((len(idx), np.ascontiguousarray(sorted(idx), dtype=np.int32)))
+        return mesh, nk, ab, Rs, Vs, mu, sel[0], sel[1]
+
+    def exciton_apply_mesh(self, mesh_size, interaction=None, U=None, fermi_level=0.0, valence=None, conduction=None, direct=True,
+                           exchange=True, vectors=None):
+        """Extension: the exciton Hamiltonian of the Tamm-Dancoff Bethe-Salpeter equation applied to vectors, without forming its
+        matrix.  The bands are this model's (`mean_field_mesh(...).model` for time-dependent Hartree-Fock; a bare model treats
+        its bands as quasi-particle energies and `interaction` as the screened interaction), an insulator at kT = 0: the same
+        number of levels at or below `fermi_level` at every point of `k_uniform_mesh(mesh_size)`.  interaction and U are those of
+        `mean_field_mesh`.  With transitions t = (k, v, c), Delta_t = E_c(k) - E_v(k), E both directions (a, b, R) of every bond,
+        d_e = R + tau_b - tau_a and N = N_k:
+
+            H_ex = Delta + K^x - K^d
+            K^d_tt' = (1/N) sum_e V_e e^{2 pi i (k-k').d_e} conj(u_ck[a]) u_c'k'[a] u_vk[b] conj(u_v'k'[b])   (direct, from Fock)
+            K^x_tt' = (1/N) sum_e V_e conj(u_ck[a]) u_vk[a] conj(u_v'k'[b]) u_c'k'[b]                        (exchange, from Hartree)
+
+        direct=False / exchange=False drops a term (the response of a fock=False mean field is direct=False).  States are
+        spin-orbitals; no spin-degeneracy factor.  valence / conduction: an int m (the top m occupied / bottom m empty bands), a
+        list of band indices, or None (all); at most 16 each.  vectors: `(nb, *mesh, nv, nc)` with nb in 1..16, or
+        `(*mesh, nv, nc)`, in the gauge of the eigenvectors `solve_all` returns.  Returns (H_ex X in the shape of vectors, gaps
+        `(*mesh, nv, nc)`).  One application is two sweeps over the selected eigenvectors, O(N_k) work.  Two calls give the same
+        bits, and a vector gives the same bits alone and inside any block.  Not covered: finite-momentum excitons (q != 0), the
+        non-TDA matrix, separate screened and bare interactions, kT > 0 and metals, several GPUs."""
+        what = "exciton_apply_mesh"
+        mesh, nk, ab, Rs, Vs, mu, (nv, vsel), (nc, csel) = self._exciton_args(what, mesh_size, interaction, U, fermi_level, valence,
+                                                                             conduction)
+        if vectors is None:
+            raise Exception("\n\nexciton_apply_mesh needs vectors of shape (nb, *mesh, nv, nc) or (*mesh, nv, nc).")
+        x = np.array(vectors, dtype=complex)
+        dk, ms = self._dim_k, tuple(int(v) for v in mesh)
+        single = x.ndim == dk + 2
+        if single:
+            x = x[None]
+        if x.ndim != dk + 3 or x.shape[1:dk + 1] != ms or not 1 <= x.shape[0] <= 16 or x.shape[-1] < 1 or x.shape[-2] < 1:
+            raise Exception("\n\nvectors must have shape (nb, *mesh, nv, nc) with nb in 1..16, or (*mesh, nv, nc).")
+        if not np.all(np.isfinite(x)):
+            raise Exception("\n\nvectors must be finite.")
+        x = np.ascontiguousarray(x)
+        out = np.zeros_like(x)
+        gaps = np.zeros(x.shape[1:])
+        info = np.zeros(3, dtype=np.int32)
+        _lib.check(_lib.lib.tbk_exciton_apply_mesh(
+            self._device_model(), _lib.iptr(mesh), len(Vs), _lib.iptr(ab.reshape(-1)), _lib.iptr(Rs.reshape(-1)), _lib.dptr(Vs), mu, nv,
+            _lib.iptr(vsel), nc, _lib.iptr(csel), int(bool(direct)), int(bool(exchange)), x.shape[0], x.shape[-2], x.shape[-1],
+            _lib.dptr(x.view(float)), _lib.dptr(out.view(float)), _lib.dptr(gaps), _lib.iptr(info)))
+        return (out[0] if single else out), gaps
+
+    def exciton_states_mesh(self, mesh_size, interaction=None, U=None, fermi_level=0.0, valence=None, conduction=None, direct=True,
+                            exchange=True, return_vectors=False):
+        """Extension: the exciton states of `exciton_apply_mesh`'s H_ex by the dense path, for N_t = N_k nv nc <= 2048: H_ex is
+        formed by applying the operator to unit vectors in blocks of 16 and diagonalised on the device.  Returns an
+        `exciton_result`: energies (ascending), dipoles d^a_lambda = <A^lambda|D^a> with D^a_t = <u_ck|dH/dk_a|u_vk> / Delta_t
+        (`_gen_dham`'s derivative, the length gauge), gap, binding = gap - energies[0], dipole_norm S_ab = (1/N) <D^a|D^b>, and with
+        return_vectors the eigenvectors `(N_t, *mesh, nv, nc)`; its `polarizability(omega, eta, dirs)` sums
+        chi_ab(w) = (1/N) sum_lambda conj(d^a) d^b / (Omega - w - i eta).  The resonant conductivity is -i w chi.  Not covered:
+        finite-momentum excitons, the non-TDA matrix, a Cartesian tensor, kT > 0 and metals; low-lying states beyond the dense
+        limit (the Lanczos coefficients of `exciton_spectrum_mesh` give Ritz values)."""
+        what = "exciton_states_mesh"
+        mesh, nk, ab, Rs, Vs, mu, (nv, vsel), (nc, csel) = self._exciton_args(what, mesh_size, interaction, U, fermi_level, valence,
+                                                                             conduction)
+        dk = self._dim_k
+        if nk > 2048:
+            raise Exception("\n\nexciton_states_mesh: at most 2048 transitions on the dense path; use exciton_spectrum_mesh.")
+        cap = min(2048, nk * min(16, self._nsta) ** 2)               # room for N_t, whatever the selection resolves to
+        energies, dip = np.zeros(cap), np.zeros((cap, dk), dtype=complex)
+        sab, scal, info = np.zeros((dk, dk), dtype=complex), np.zeros(2), np.zeros(3, dtype=np.int32)
+        vec = np.zeros(cap * cap, dtype=complex) if return_vectors else None
+        _lib.check(_lib.lib.tbk_exciton_states_mesh(
+            self._device_model(), _lib.iptr(mesh), len(Vs), _lib.iptr(ab.reshape(-1)), _lib.iptr(Rs.reshape(-1)), _lib.dptr(Vs), mu, nv,
+            _lib.iptr(vsel), nc, _lib.iptr(csel), int(bool(direct)), int(bool(exchange)), cap, _lib.dptr(energies),
+            _lib.dptr(dip.view(float)), _lib.dptr(sab.view(float)), None if vec is None else _lib.dptr(vec.view(float)),
+            _lib.dptr(scal), _lib.iptr(info)))
+        nocc, nv, nc = int(info[0]), int(info[1]), int(info[2])
+        nt = nk * nv * nc
+        res = exciton_result()
+        res.energies, res.dipoles = energies[:nt].copy(), dip[:nt].copy()
+        res.gap, res.binding, res.dipole_norm = float(scal[0]), float(scal[0] - energies[0]), sab
+        res.n_occ, res.mesh, res._nk = nocc, mesh.copy(), nk
+        res.valence = [int(b) for b in vsel] if vsel is not None else list(range(nocc - nv, nocc))
+        res.conduction = [int(b) for b in csel] if csel is not None else list(range(nocc, nocc + nc))
+        res.vectors = vec[:nt * nt].reshape((nt,) + tuple(int(v) for v in mesh) + (nv, nc)).copy() if return_vectors else None
+        return res
+
+    def exciton_spectrum_mesh(self, mesh_size, interaction=None, U=None, fermi_level=0.0, valence=None, conduction=None, direct=True,
+                              exchange=True, omega=None, eta=None, dirs=None, n_steps=256, return_coefficients=False):
+        """Extension: the polarizability chi_ab(w) = (1/N) <D^a| (H_ex - w - i eta)^-1 |D^b> of `exciton_apply_mesh`'s H_ex by the
+        Haydock recursion, for up to 2**24 transitions (the selected eigenvectors stay on the device: N_k nsta (nv + nc) <= 2**26).
+        Diagonal components are Lanczos runs started from D^a; an off-diagonal pair adds the runs from D^a + D^b and D^a + i D^b,
+        dim_k**2 runs for the tensor, all carried as one block through the same applications with the whole loop on the
+        device.  A run whose beta falls below 1e-10 of the largest |alpha| so far (at least the largest transition energy) has
+        exhausted its invariant subspace and ends there (n_used); it is not restarted.  The continued fraction is evaluated on the
+        host: `exciton_reconstruct(coefficients, omega, eta)` gives another frequency list for nothing.  omega, eta by the rules of
+        `optical_conductivity_mesh`; dirs=None -> `(nw, dim_k, dim_k)`, dirs=(a, b) -> `(nw,)`, bitwise the tensor's entry.
+        Returns an `exciton_spectrum` with chi, dipole_norm, gap, n_used and, on request, coefficients.  Two calls give the same
+        bits; n_steps = k gives the first k coefficients of a longer run.  Not covered: finite-momentum excitons, the non-TDA
+        matrix, a Cartesian tensor, kT > 0 and metals, several GPUs; eigenpairs come from the coefficients (Ritz values)."""
+        what = "exciton_spectrum_mesh"
+        mesh, nk, ab, Rs, Vs, mu, (nv, vsel), (nc, csel) = self._exciton_args(what, mesh_size, interaction, U, fermi_level, valence,
+                                                                             conduction)
+        if omega is None or eta is None:
+            raise Exception("\n\nexciton_spectrum_mesh needs omega and eta.")
+        w = _sweep_args(omega, eta, 0.0, 0.0)
+        dk = self._dim_k
+        da, db = (-1, -1) if dirs is None else _exciton_dirs(dirs, dk)
+        if not _is_int(n_steps) or n_steps < 1 or n_steps > 65536:
+            raise Exception("\n\nn_steps must be an integer in 1..65536.")
+        if da < 0:
+            runs = [(a, a, 0) for a in range(dk)] + [(a, b, kind) for a in range(dk) for b in range(a + 1, dk) for kind in (1, 2)]
+        elif da == db:
+            runs = [(da, da, 0)]
+        else:
+            runs = [(da, da, 0), (db, db, 0), (da, db, 1), (da, db, 2)]
+        nr = len(runs)
+        alpha, beta = np.zeros((nr, n_steps)), np.zeros((nr, n_steps))
+        norm2, n_used = np.zeros(nr), np.zeros(nr, dtype=np.int32)
+        sab, scal, info = np.zeros((dk, dk), dtype=complex), np.zeros(2), np.zeros(3, dtype=np.int32)
+        _lib.check(_lib.lib.tbk_exciton_spectrum_mesh(
+            self._device_model(), _lib.iptr(mesh), len(Vs), _lib.iptr(ab.reshape(-1)), _lib.iptr(Rs.reshape(-1)), _lib.dptr(Vs), mu, nv,
+            _lib.iptr(vsel), nc, _lib.iptr(csel), int(bool(direct)), int(bool(exchange)), da, db, int(n_steps), _lib.dptr(alpha),
+            _lib.dptr(beta), _lib.dptr(norm2), _lib.iptr(n_used), _lib.dptr(sab.view(float)), _lib.dptr(scal), _lib.iptr(info)))
+        co = exciton_coefficients()
+        co.alpha, co.beta, co.norm2, co.n_used, co.runs = alpha, beta, norm2, n_used, runs
+        co.dim_k, co.dirs, co.n_k = dk, (None if da < 0 else (da, db)), nk
+        res = exciton_spectrum()
+        res.chi = exciton_reconstruct(co, w, eta)
+        res.dipole_norm, res.gap, res.n_used = sab, float(scal[0]), n_used.copy()
+        res.coefficients = co if return_coefficients else None
+        return res
 
     # ------------------------------------------------------------------ Bogoliubov-de Gennes superconductivity (extension)
     def _state_table(self):
