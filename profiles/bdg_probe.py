@@ -73,7 +73,7 @@ def child(name, quick):
     res = run(2)[1]
     run(2)
     nambu = res.model
-    ab, Rs, _ = m._mf_entries(inter.get("interaction"), inter.get("U"))
+    ab, Rs, _ = m._mf_entries("bdg_mesh", inter.get("interaction"), inter.get("U"))
     Rl = np.unique(np.vstack([np.zeros((1, m._dim_k), dtype=np.int32), Rs]), axis=0)
     pairs = [(a, a, None) for a in range(n)] + [(int(a), n + int(b), R) for (a, b), R in zip(ab, Rs)]
 

@@ -70,7 +70,7 @@ def child(name, quick):
 
     nt, nc = NT[name], NC[name]
     run(2), run(2)
-    ab, Rs, _ = m._mf_entries(kw["interaction"], None)
+    ab, Rs, _ = m._mf_entries("exciton_spectrum_mesh", kw["interaction"], None)
     pairs = [(int(a), int(b), R) for (a, b), R in zip(ab, Rs)] + [(int(b), int(a), -R) for (a, b), R in zip(ab, Rs)]
     pairs += [(int(a), int(a), None) for a in sorted(set(ab.reshape(-1).tolist()))]
 

@@ -303,11 +303,12 @@ static int check_plans() {
     // the driver's workspace: 20 states (Nambu 40) on 1369 points, 23 triples, 11 parameters
     const BdgPlan b = bdg_plan(20, 2, 1369, 23, 11, 4, 6, 50, 90);
     EXPECT(b.pd.chunk == 1310 && b.pd.nchunks == 2 && b.nlev == 40 * 1369 && b.G == occ_scan_groups(40 * 1369));
-    size_t buf[BdgPlan::NBUF][2];
+    size_t buf[BdgPlan::NBUF + MfLoopBufs::NBUF][2];                                // the driver's own buffers, then the loop block
     for (int i = 0; i < BdgPlan::NBUF; ++i) buf[i][0] = b.off[i], buf[i][1] = b.off[i + 1] - b.off[i];
-    EXPECT(check_buffers("bdg", buf, BdgPlan::NBUF, b.total) == 0);
+    for (int i = 0; i < MfLoopBufs::NBUF; ++i) buf[BdgPlan::NBUF + i][0] = b.loop.off[i], buf[BdgPlan::NBUF + i][1] = b.loop.off[i + 1] - b.loop.off[i];
+    EXPECT(check_buffers("bdg", buf, BdgPlan::NBUF + MfLoopBufs::NBUF, b.total) == 0);
     EXPECT(b.off[BdgPlan::VEC + 1] - b.off[BdgPlan::VEC] == al256((size_t)1310 * 1600 * 16));   // ONE chunk of eigenvectors
-    EXPECT(b.off[BdgPlan::OCCH + 1] - b.off[BdgPlan::OCCH] == al256((size_t)6 * 20 * 8));
+    EXPECT(b.loop.off[MfLoopBufs::OCCH + 1] - b.loop.off[MfLoopBufs::OCCH] == al256((size_t)6 * 20 * 8));
     // no partition depends on history, max_iter or the parameters
     const BdgPlan c = bdg_plan(20, 2, 1369, 2000, 900, 0, 500, 3, 5);
     EXPECT(c.pd.G == b.pd.G && c.pd.chunk == b.pd.chunk && c.G == b.G && c.pd.TL == b.pd.TL);

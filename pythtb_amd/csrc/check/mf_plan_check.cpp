@@ -2,7 +2,9 @@
 // as an ordinary program.  It covers every argument rule of tbk_mean_field_mesh and the edge of every cap; the expansion of an
 // interaction list into parameters, pins, gather indices and the term -> parameter map for hand-worked cases (Hubbard U on a spinful
 // two-orbital cell; one nearest-neighbour V on a spinless cell with and without a hop on that bond; a bond and its mirror given
-// twice); the small Anderson solve against values worked out by hand (m = 1, 2, 8, a zero residual, a non-finite entry); and the
+// twice); the walk over the interaction list that the three drivers share (tbk_int.h: the repeated bond with the earlier index, the
+// lattice vectors in order of first appearance, the ascending touched states, dim_k = 1, 2, 3, 4096 and 4097 vectors); the small
+// Anderson solve against values worked out by hand (m = 1, 2, 8, a zero residual, a non-finite entry); and the loop block and the
 // resident and two-pass workspace layouts, filled and read back under the sanitizer.  The pinned flatten itself lives in
 // tbk_core.hip, beside the flatten it extends, and is held by tests/test_mean_field.py through tbk_model_flatten_host_pinned.
 #include <cmath>
@@ -206,20 +208,23 @@ static int check_anderson() {
     return 0;
 }
 
-static int check_layout(const char* tag, const MfPlan& p) {
-    size_t end = 256;
-    for (int i = 0; i < MfPlan::NBUF; ++i) {
-        if (p.off[i] % 256 || p.off[i] < end) return printf("%s: buffer %d at %zu (the previous one ends at %zu)\n", tag, i, p.off[i], end);
-        end = p.off[i + 1];
+// buffers [off[i], off[i + 1]) from `first` on: every one 256-aligned and behind the one before, the last ending at `total`; then filled
+// and read back under the sanitizer
+static int check_offsets(const char* tag, const std::vector<size_t>& off, size_t first, size_t total) {
+    const int nb = (int)off.size() - 1;
+    size_t end = first;
+    for (int i = 0; i < nb; ++i) {
+        if (off[i] % 256 || off[i] < end) return printf("%s: buffer %d at %zu (the previous one ends at %zu)\n", tag, i, off[i], end);
+        end = off[i + 1];
     }
-    if (end != p.total) return printf("%s: the total\n", tag);
-    if (p.total > ((size_t)256 << 20)) return 0;
-    unsigned char* base = (unsigned char*)aligned_alloc(256, al256(p.total));
+    if (end != total) return printf("%s: the total\n", tag);
+    if (total > ((size_t)256 << 20)) return 0;
+    unsigned char* base = (unsigned char*)aligned_alloc(256, al256(total));
     if (!base) return printf("%s: no host block\n", tag);
     int bad = 0;
-    for (int i = 0; i < MfPlan::NBUF; ++i) memset(base + p.off[i], i + 1, p.off[i + 1] - p.off[i]);
-    for (int i = 0; i < MfPlan::NBUF && !bad; ++i)
-        for (size_t j = p.off[i]; j < p.off[i + 1]; j += 61)
+    for (int i = 0; i < nb; ++i) memset(base + off[i], i + 1, off[i + 1] - off[i]);
+    for (int i = 0; i < nb && !bad; ++i)
+        for (size_t j = off[i]; j < off[i + 1]; j += 61)
             if (base[j] != (unsigned char)(i + 1)) {
                 bad = printf("%s: buffer %d is overwritten\n", tag, i);
                 break;
@@ -227,6 +232,98 @@ static int check_layout(const char* tag, const MfPlan& p) {
     free(base);
     return bad;
 }
+// the driver's own buffers, then the loop block behind them
+static int check_layout(const char* tag, const MfPlan& p) {
+    std::vector<size_t> off(p.off, p.off + MfPlan::NBUF);
+    off.insert(off.end(), p.loop.off, p.loop.off + MfLoopBufs::NBUF + 1);
+    if (p.loop.off[0] != p.off[MfPlan::NBUF]) return printf("%s: the loop block does not follow the driver's buffers\n", tag);
+    return check_offsets(tag, off, 256, p.total);
+}
+// the walk of tbk_int.h itself, as the three drivers call it
+static int check_walk() {
+    IntBonds B;
+    auto walk = [&](int dk, int n, const Inter& I) { return int_bonds("t", dk, n, (int)I.V.size(), I.ab.data(), I.R.data(), I.V.data(), B); };
+    for (int dk = 1; dk <= 3; ++dk) {
+        auto vec = [&](int r) {                                                    // r in the LAST component: a key cut short would miss it
+            std::vector<int> v((size_t)dk, 0);
+            v[dk - 1] = r;
+            return v;
+        };
+        // a bond and its mirror, in both orders, behind another bond: the refusal names the earlier entry
+        for (int order = 0; order < 2; ++order) {
+            Inter I;
+            I.add(0, 2, vec(0), 1.0);
+            I.add(order ? 1 : 0, order ? 0 : 1, vec(order ? -1 : 1), 0.5);
+            I.add(order ? 0 : 1, order ? 1 : 0, vec(order ? 1 : -1), 0.5);
+            EXPECT(walk(dk, 3, I) == TBK_EINVAL && strstr(g_err, "interaction 2 repeats the bond of interaction 1") && strstr(g_err, "given once"));
+            I.ab[4] = I.ab[2], I.ab[5] = I.ab[3], I.R[2 * dk + dk - 1] = I.R[dk + dk - 1];   // the same entry again
+            EXPECT(walk(dk, 3, I) == TBK_EINVAL && strstr(g_err, "interaction 2 repeats the bond of interaction 1"));
+            I.R[2 * dk + dk - 1] = 7;                                              // another vector: another bond
+            EXPECT(walk(dk, 3, I) == TBK_OK && B.nR == 3);
+        }
+        // the lattice vectors: R = 0 first, then in order of first appearance -- with R = 0 given first, in the middle, not at all
+        const int given[3][3] = {{0, 1, 2}, {2, 0, 1}, {3, -1, 3}}, Rl[3][3] = {{0, 1, 2}, {0, 2, 1}, {0, 3, -1}}, er[3][3] = {{0, 1, 2}, {1, 0, 2}, {1, 2, 1}};
+        for (int c = 0; c < 3; ++c) {
+            Inter I;
+            for (int e = 0; e < 3; ++e) I.add(e, e + 1, vec(given[c][e]), 1.0 + e);
+            EXPECT(walk(dk, 4, I) == TBK_OK && B.nR == 3 && B.Rl.size() == (size_t)3 * dk && B.ent_r.size() == 3);
+            for (int r = 0; r < 3; ++r) {
+                EXPECT(B.Rl[(size_t)r * dk + dk - 1] == Rl[c][r] && B.ent_r[r] == er[c][r]);
+                for (int d = 0; d + 1 < dk; ++d) EXPECT(B.Rl[(size_t)r * dk + d] == 0);
+            }
+            EXPECT(B.nocc == 4 && B.rowsum[0] == 1.0 && B.rowsum[1] == 3.0 && B.rowsum[2] == 5.0 && B.rowsum[3] == 3.0);
+        }
+        // the touched states, ascending, with gaps
+        Inter G;
+        G.add(7, 2, vec(0), 1.0);
+        G.add(5, 7, vec(1), -2.0);
+        EXPECT(walk(dk, 9, G) == TBK_OK && B.nocc == 3 && B.occ_par.size() == 9 && B.occ_par[2] == 0 && B.occ_par[5] == 1 && B.occ_par[7] == 2);
+        for (int a : {0, 1, 3, 4, 6, 8}) EXPECT(B.occ_par[a] == -1 && B.rowsum[a] == 0.0);
+        EXPECT(B.rowsum[7] == 3.0 && B.rowsum[2] == 1.0 && B.rowsum[5] == 2.0);
+        // one state, one entry: the bond to its own image, both directions in the row sum
+        Inter O;
+        O.add(0, 0, vec(1), -0.75);
+        EXPECT(walk(dk, 1, O) == TBK_OK && B.nocc == 1 && B.occ_par[0] == 0 && B.nR == 2 && B.ent_r[0] == 1 && B.rowsum[0] == 1.5);
+        // 4096 vectors and 4097: the walk counts them, the cap is the driver's (check_arguments)
+        Inter M;
+        for (int r = 1; r <= 4096; ++r) M.add(0, 1, vec(r), 1.0);
+        EXPECT(walk(dk, 2, M) == TBK_OK && B.nR == 4097 && B.ent_r[4095] == 4096 && B.Rl.size() == (size_t)4097 * dk);
+        MfProblem P;
+        EXPECT(mf_problem("t", dk, 2, M.args(), P) == TBK_EINVAL && strstr(g_err, "4097 distinct lattice vectors"));
+        M.ab.resize(2 * 4095), M.R.resize((size_t)dk * 4095), M.V.resize(4095);
+        EXPECT(walk(dk, 2, M) == TBK_OK && B.nR == 4096 && B.Rl[(size_t)4095 * dk + dk - 1] == 4095);
+        EXPECT(mf_problem("t", dk, 2, M.args(), P) == TBK_OK && P.nR == 4096);
+    }
+    return 0;
+}
+
+// the loop block alone: np = 1, no map (nft = 0), without and with the longest ring, behind an unaligned end
+static int check_loop_block() {
+    for (int history : {0, 8}) {
+        MfLoopBufs L;
+        const size_t end = mf_loop_bufs(L, 256 + 40, 1, history, 3, 0, 0, 5);
+        EXPECT(L.off[0] == 512);
+        EXPECT(check_offsets("loop", std::vector<size_t>(L.off, L.off + MfLoopBufs::NBUF + 1), 512, end) == 0);
+        auto size = [&](int i) { return L.off[i + 1] - L.off[i]; };
+        EXPECT(size(MfLoopBufs::XIN) == 256 && size(MfLoopBufs::XOUT) == 256 && size(MfLoopBufs::XPREV) == 256 && size(MfLoopBufs::GIDX) == 256);
+        EXPECT(size(MfLoopBufs::RINGX) == 256 && size(MfLoopBufs::RINGR) == 256 && size(MfLoopBufs::SMALL) == 1024);
+        EXPECT(size(MfLoopBufs::TBASE) == 0 && size(MfLoopBufs::TTERM) == 0 && size(MfLoopBufs::TRBLK) == 0 && size(MfLoopBufs::TPTR) == 256);
+        EXPECT(size(MfLoopBufs::CCOEF) == 0 && size(MfLoopBufs::CPAR) == 0 && size(MfLoopBufs::CPART) == 0);
+        EXPECT(size(MfLoopBufs::RESH) == 256 && size(MfLoopBufs::OCCH) == 256);
+    }
+    // the sizes of a larger one: 100 parameters, a ring of 8, 7 terms with 19 contributions, 11 iterations of 6 occupations
+    MfLoopBufs L;
+    const size_t end = mf_loop_bufs(L, 256, 100, 8, 11, 7, 19, 6);
+    EXPECT(check_offsets("loop", std::vector<size_t>(L.off, L.off + MfLoopBufs::NBUF + 1), 256, end) == 0);
+    auto size = [&](int i) { return L.off[i + 1] - L.off[i]; };
+    EXPECT(size(MfLoopBufs::XIN) == al256(800) && size(MfLoopBufs::RINGX) == al256(6400) && size(MfLoopBufs::RINGR) == al256(6400));
+    EXPECT(size(MfLoopBufs::GIDX) == al256(800) && size(MfLoopBufs::TBASE) == al256(112) && size(MfLoopBufs::TPTR) == al256(32));
+    EXPECT(size(MfLoopBufs::TTERM) == al256(28) && size(MfLoopBufs::TRBLK) == al256(56) && size(MfLoopBufs::CCOEF) == al256(152));
+    EXPECT(size(MfLoopBufs::CPAR) == al256(76) && size(MfLoopBufs::CPART) == al256(76) && size(MfLoopBufs::RESH) == al256(88));
+    EXPECT(size(MfLoopBufs::OCCH) == al256(528));
+    return 0;
+}
+
 static int check_plans() {
     // 40 states on 1369 points: chunks of 1310 + 59; resident, and two-pass under a lowered cap
     MfPlan a = mf_plan(40, 1, 1369, 2, 120, 4, 3, 80, 160, mf_resident_cap(-1));
@@ -251,7 +348,9 @@ static int check_plans() {
 int main() {
     int bad = check_arguments();
     if (!bad) bad = check_expansion();
+    if (!bad) bad = check_walk();
     if (!bad) bad = check_anderson();
+    if (!bad) bad = check_loop_block();
     if (!bad) bad = check_plans();
     printf(bad ? "mf_plan_check: FAILED\n" : "mf_plan_check: ok\n");
     return bad ? 1 : 0;

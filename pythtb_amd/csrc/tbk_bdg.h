@@ -36,14 +36,12 @@ static int bdg_check(const char* fn, int dk, int n, const int32_t* mesh, const B
 // with n_electrons given, mu last).  The triples of the Nambu density matrix: (a, a, 0) of EVERY state (N_out needs them all), then
 // (a, b, R) per entry with fock, then (a, n + b, R) per entry with pairing.  P is tbk_mf.h's problem of the NAMBU model (P.n = 2 n): its
 // pins and its field, through which mf_map builds the gather of k_mf_apply.
-struct BdgProblem {
-    int n = 0, dk = 0, nint = 0, nocc = 0, hartree = 0, fock = 0, pairing = 0, have_nel = 0, nR = 0;
+struct BdgProblem : IntBonds {                   // (the walk of tbk_int.h over the NORMAL model's states: occ_par[n], Rl)
+    int n = 0, dk = 0, nint = 0, hartree = 0, fock = 0, pairing = 0, have_nel = 0;
     int64_t np = 0, nt = 0;
     int par_d = -1, par_f = -1, par_mu = -1;     // the first parameter of the D block and of the F block, and mu (-1: absent)
-    std::vector<int> occ_par;                    // [n]
     std::vector<int32_t> tij, tR;                // [nt][2], [nt][dk]
     std::vector<int64_t> gidx;                   // [np - have_nel]: where x_out[p] sits in acc[nt] seen as doubles
-    std::vector<int32_t> Rl;                     // [nR][dk]: R = 0 first, then the entries' vectors in order of first appearance
     MfProblem P;
 };
 static int bdg_problem(const char* fn, int dk, int n, const BdgArgs& A, BdgProblem& B) {
@@ -53,29 +51,9 @@ static int bdg_problem(const char* fn, int dk, int n, const BdgArgs& A, BdgProbl
     TBK_REQUIRE(B.hartree || B.fock || B.pairing, TBK_EINVAL, "%s: every channel is switched off", fn);
     MfProblem& P = B.P;
     P.n = 2 * n, P.dk = dk, P.nint = A.nint, P.fock = B.fock;
-    B.occ_par.assign((size_t)n, -1);
-    std::map<std::array<int, 6>, int> seen;
-    std::map<std::array<int, 4>, int> rid;
-    rid[{0, 0, 0, 0}] = 0;
-    B.Rl.assign((size_t)dk, 0);
-    for (int e = 0; e < A.nint; ++e) {
-        const int a = A.ab[2 * e], b = A.ab[2 * e + 1];
-        std::array<int, 4> R{0, 0, 0, 0};
-        for (int d = 0; d < dk; ++d) R[d] = A.R[(int64_t)e * dk + d];
-        const std::array<int, 6> k1{a, b, R[0], R[1], R[2], R[3]}, k2{b, a, -R[0], -R[1], -R[2], -R[3]};
-        TBK_REQUIRE(!seen.count(k1) && !seen.count(k2), TBK_EINVAL, "%s: interaction %d repeats the bond of interaction %d (a bond is given once)",
-                    fn, e, seen.count(k1) ? seen[k1] : seen[k2]);
-        seen[k1] = e;
-        B.occ_par[a] = B.occ_par[b] = 0;
-        if (!rid.count(R)) {
-            rid.emplace(R, (int)rid.size());
-            for (int d = 0; d < dk; ++d) B.Rl.push_back(R[d]);
-        }
-    }
-    B.nR = (int)rid.size();
+    int rc = int_bonds(fn, dk, n, A.nint, A.ab, A.R, A.V, B);
+    if (rc) return rc;
     TBK_REQUIRE(B.nR <= kOccRMax, TBK_EINVAL, "%s: %d distinct lattice vectors (at most %d)", fn, B.nR, kOccRMax);
-    for (int a = 0; a < n; ++a)
-        if (B.occ_par[a] == 0) B.occ_par[a] = B.nocc++;
     B.np = B.nocc;
     if (B.fock) B.par_d = (int)B.np, B.np += 2 * (int64_t)A.nint;
     if (B.pairing) B.par_f = (int)B.np, B.np += 2 * (int64_t)A.nint;
@@ -112,30 +90,21 @@ static int bdg_problem(const char* fn, int dk, int n, const BdgArgs& A, BdgProbl
             const int mR[4] = {-R[0], -R[1], -R[2], -R[3]};
             if (ch == 0 && B.hartree) {
                 // the on-site energy of a gets V n_b and that of b gets V n_a; the hole block the negative
-                P.field.push_back(MfField{a, a, {0, 0, 0, 0}, V, B.occ_par[b], 0});
-                P.field.push_back(MfField{b, b, {0, 0, 0, 0}, V, B.occ_par[a], 0});
-                P.field.push_back(MfField{n + a, n + a, {0, 0, 0, 0}, -V, B.occ_par[b], 0});
-                P.field.push_back(MfField{n + b, n + b, {0, 0, 0, 0}, -V, B.occ_par[a], 0});
+                mf_field_hartree(P.field, a, b, V, B.occ_par[a], B.occ_par[b], 0, 1.0);
+                mf_field_hartree(P.field, a, b, V, B.occ_par[a], B.occ_par[b], n, -1.0);
             }
             if (ch == 1 && B.fock) {
                 const int pr = B.par_d + 2 * e, pi = pr + 1;
                 const int64_t t = triple(a, b, R);
                 B.gidx[pr] = 2 * t, B.gidx[pi] = 2 * t + 1;
                 pin(a, b, R, 1), pin(n + a, n + b, R, 1);
-                // particle: (a, b, R) gets -V D; hole: (n + a, n + b, R) gets +V conj(D).  Stored above the diagonal, (a > b) as
-                // (b, a, -R) conjugated; on the diagonal the slot also holds the mirror at -R with the conjugate (tbk_mf.h)
-                if (a <= b) {
-                    P.field.push_back(MfField{a, b, {R[0], R[1], R[2], R[3]}, -V, pr, 0});
-                    P.field.push_back(MfField{a, b, {R[0], R[1], R[2], R[3]}, -V, pi, 1});
-                    P.field.push_back(MfField{n + a, n + b, {R[0], R[1], R[2], R[3]}, V, pr, 0});
-                    P.field.push_back(MfField{n + a, n + b, {R[0], R[1], R[2], R[3]}, -V, pi, 1});
-                }
-                if (a >= b) {
-                    P.field.push_back(MfField{b, a, {mR[0], mR[1], mR[2], mR[3]}, -V, pr, 0});
-                    P.field.push_back(MfField{b, a, {mR[0], mR[1], mR[2], mR[3]}, V, pi, 1});
-                    P.field.push_back(MfField{n + b, n + a, {mR[0], mR[1], mR[2], mR[3]}, V, pr, 0});
-                    P.field.push_back(MfField{n + b, n + a, {mR[0], mR[1], mR[2], mR[3]}, V, pi, 1});
-                }
+                // particle: (a, b, R) gets -V D; hole: (n + a, n + b, R) gets +V conj(D); per stored direction (tbk_mf.h), particle
+                // before hole
+                for (int mirror = 0; mirror < 2; ++mirror)
+                    if (mirror ? a >= b : a <= b) {
+                        mf_field_fock(P.field, a, b, R, V, pr, 0, -1.0, -1.0, mirror);
+                        mf_field_fock(P.field, a, b, R, V, pr, n, 1.0, -1.0, mirror);
+                    }
             }
             if (ch == 2 && B.pairing) {
                 const int pr = B.par_f + 2 * e, pi = pr + 1;
@@ -159,9 +128,9 @@ struct BdgPlan {
     int64_t npts = 0, nlev = 0;
     int G = 0;                 // groups of the level scans (occ_scan_groups)
     PdmPart pd;
-    enum { K_ALL, LEV, EC, VEC, PART, ACC, TIJ, TR, SPART, GAPP, XIN, XOUT, XPREV, RINGX, RINGR, SMALL, GIDX, TBASE, TPTR, TTERM, TRBLK, CCOEF,
-           CPAR, CPART, RESH, OCCH, NBUF };
+    enum { K_ALL, LEV, EC, VEC, PART, ACC, TIJ, TR, SPART, GAPP, NBUF };
     size_t off[NBUF + 1];
+    MfLoopBufs loop;
     size_t total = 0;
 };
 static BdgPlan bdg_plan(int n, int dk, int64_t npts, int64_t nt, int64_t np, int history, int max_iter, int64_t nft, int64_t nnz) {
@@ -172,7 +141,6 @@ static BdgPlan bdg_plan(int n, int dk, int64_t npts, int64_t nt, int64_t np, int
     p.nlev = npts * N;
     p.G = occ_scan_groups(p.nlev);
     p.pd = pdm_partition(N, npts);
-    const int m = std::max(history, 1);
     size_t b[BdgPlan::NBUF];
     b[BdgPlan::K_ALL] = (size_t)npts * dk * D;
     b[BdgPlan::LEV] = (size_t)p.nlev * D;
@@ -184,20 +152,8 @@ static BdgPlan bdg_plan(int n, int dk, int64_t npts, int64_t nt, int64_t np, int
     b[BdgPlan::TR] = (size_t)nt * dk * sizeof(int32_t);
     b[BdgPlan::SPART] = (size_t)3 * p.G * D + 512;      // the final scan's partials, its three sums, and the level 0 it scans at
     b[BdgPlan::GAPP] = (size_t)p.G * D + 256;           // the partial minima of |E| and their minimum
-    b[BdgPlan::XIN] = b[BdgPlan::XOUT] = b[BdgPlan::XPREV] = (size_t)np * D;
-    b[BdgPlan::RINGX] = b[BdgPlan::RINGR] = (size_t)m * np * D;
-    b[BdgPlan::SMALL] = 1024;                           // the Gram matrix [8][8]
-    b[BdgPlan::GIDX] = (size_t)np * sizeof(int64_t);
-    b[BdgPlan::TBASE] = (size_t)nft * 2 * D;
-    b[BdgPlan::TPTR] = (size_t)(nft + 1) * sizeof(int32_t);
-    b[BdgPlan::TTERM] = (size_t)nft * sizeof(int32_t);
-    b[BdgPlan::TRBLK] = (size_t)nft * sizeof(int64_t);
-    b[BdgPlan::CCOEF] = (size_t)nnz * D;
-    b[BdgPlan::CPAR] = b[BdgPlan::CPART] = (size_t)nnz * sizeof(int32_t);
-    b[BdgPlan::RESH] = (size_t)max_iter * D;
-    b[BdgPlan::OCCH] = (size_t)max_iter * n * D;
     p.off[0] = 256;
     for (int i = 0; i < BdgPlan::NBUF; ++i) p.off[i + 1] = p.off[i] + al256(b[i]);
-    p.total = p.off[BdgPlan::NBUF];
+    p.total = mf_loop_bufs(p.loop, p.off[BdgPlan::NBUF], np, history, max_iter, nft, nnz, n);
     return p;
 }

@@ -61,55 +61,45 @@ __global__ __launch_bounds__(64) void k_bdg_gap_min(const double* __restrict__ p
 // ---------------------------------------------------------------- host side
 namespace {
 struct BdgRun {
-    tbk_ctx* ctx;
-    tbk_model* m;
+    MfFrame F;                 // the private Nambu model, the workspace and the loop's buffers (tbk_mf_dev.h)
     BdgPlan pl;
     OccMesh M;
-    unsigned char* base;
-    int n, dk, nft, pmu;
-    int64_t np, nt;
+    int n, dk, pmu;
+    int64_t nt;
     double kT, nel, mu_step;
-    cd *amp, *rblock;
     template <class T>
-    T* buf(int i) const { return (T*)(base + pl.off[i]); }
+    T* buf(int i) const { return (T*)(F.base + pl.off[i]); }
 };
 
 // x_in -> H[x_in] -> per chunk the eigenpairs and the selected entries of D at 0 -> x_out
 int bdg_pass(const BdgRun& S, int it) {
-    tbk_ctx* ctx = S.ctx;
-    if (S.nft > 0) {
-        ProfScope ps(ctx, "bdg_apply");
-        hipLaunchKernelGGL(k_mf_apply, dim3(nblk(S.nft)), dim3(256), 0, ctx->stream, S.nft, (const int32_t*)S.buf<int32_t>(BdgPlan::TPTR),
-                           (const int32_t*)S.buf<int32_t>(BdgPlan::TTERM), (const int64_t*)S.buf<int64_t>(BdgPlan::TRBLK),
-                           (const double*)S.buf<double>(BdgPlan::TBASE), (const double*)S.buf<double>(BdgPlan::CCOEF),
-                           (const int32_t*)S.buf<int32_t>(BdgPlan::CPAR), (const int32_t*)S.buf<int32_t>(BdgPlan::CPART),
-                           (const double*)S.buf<double>(BdgPlan::XIN), S.amp, S.rblock);
-        TBK_HIP(hipGetLastError());
-    }
+    tbk_ctx* ctx = S.F.ctx;
+    int rc = mf_launch_apply(S.F, "bdg_apply");
+    if (rc) return rc;
     const int N = 2 * S.n;
     double* ec = S.buf<double>(BdgPlan::EC);
     cd* vec = S.buf<cd>(BdgPlan::VEC);
     for (int64_t c = 0; c < S.pl.pd.nchunks; ++c) {
         const int64_t first = c * S.pl.pd.chunk, cnt = std::min<int64_t>(S.pl.pd.chunk, S.pl.npts - first);
         const double* kp = S.buf<double>(BdgPlan::K_ALL) + first * S.dk;
-        int rc = tbk_solve_list_dev(S.m, kp, cnt, ec, (double*)vec);
+        rc = tbk_solve_list_dev(S.F.m, kp, cnt, ec, (double*)vec);
         if (rc) return rc;
         TBK_HIP(hipMemcpyAsync(S.buf<double>(BdgPlan::LEV) + first * N, ec, (size_t)cnt * N * sizeof(double), hipMemcpyDeviceToDevice,
                                ctx->stream));
-        rc = occ_pairs_stage(ctx, S.m->view, S.pl.pd, S.M, first, cnt, kp, ec, vec, nullptr, 0.0, S.kT, S.buf<int32_t>(BdgPlan::TIJ),
+        rc = occ_pairs_stage(ctx, S.F.m->view, S.pl.pd, S.M, first, cnt, kp, ec, vec, nullptr, 0.0, S.kT, S.buf<int32_t>(BdgPlan::TIJ),
                              S.buf<int32_t>(BdgPlan::TR), S.nt, S.buf<cd>(BdgPlan::PART), S.buf<cd>(BdgPlan::ACC), c > 0 ? 1 : 0);
         if (rc) return rc;
     }
-    const int64_t ng = S.np - (S.pmu >= 0 ? 1 : 0);
+    const int64_t ng = S.F.np - (S.pmu >= 0 ? 1 : 0);
     ProfScope ps(ctx, "bdg_gather");
     if (ng > 0) {
-        hipLaunchKernelGGL(k_mf_gather, dim3(nblk(ng)), dim3(256), 0, ctx->stream, ng, (const int64_t*)S.buf<int64_t>(BdgPlan::GIDX),
-                           (const double*)S.buf<cd>(BdgPlan::ACC), (double)S.pl.npts, S.buf<double>(BdgPlan::XOUT));
+        hipLaunchKernelGGL(k_mf_gather, dim3(nblk(ng)), dim3(256), 0, ctx->stream, ng, (const int64_t*)S.F.lp<int64_t>(MfLoopBufs::GIDX),
+                           (const double*)S.buf<cd>(BdgPlan::ACC), (double)S.pl.npts, S.F.lp<double>(MfLoopBufs::XOUT));
         TBK_HIP(hipGetLastError());
     }
     hipLaunchKernelGGL(k_bdg_mu, dim3(1), dim3(256), 0, ctx->stream, S.n, (const double*)S.buf<cd>(BdgPlan::ACC), (double)S.pl.npts, it, S.pmu,
-                       S.nel, S.mu_step, (const double*)S.buf<double>(BdgPlan::XIN), S.buf<double>(BdgPlan::XOUT),
-                       S.buf<double>(BdgPlan::OCCH));
+                       S.nel, S.mu_step, (const double*)S.F.lp<double>(MfLoopBufs::XIN), S.F.lp<double>(MfLoopBufs::XOUT),
+                       S.F.lp<double>(MfLoopBufs::OCCH));
     TBK_HIP(hipGetLastError());
     return TBK_OK;
 }
@@ -137,99 +127,41 @@ extern "C" int tbk_bdg_mesh(tbk_ctx* ctx, int dim_k, int nsta, const double* orb
     for (int64_t p = 0; p < B.np; ++p) TBK_REQUIRE(std::isfinite(x_start[p]), TBK_EINVAL, "%s: the start field is not finite", fn);
     TBK_HIP(hipSetDevice(ctx->device));
 
-    // the private Nambu model (spinless, N orbitals; the caller's tables hold the bare model, with the Fermi level where it is given):
-    // every field entry pinned
-    tbk_model* pm = nullptr;
-    TbkFlatTerms T;
-    rc = tbk_model_upload_pinned(ctx, dim_k, N, 1, orb, onsite, nhop, hop_i, hop_j, hop_R, hop_amp, (int64_t)B.P.pin.size() / 6, B.P.pin.data(),
-                                 &pm, &T);
-    if (rc) return rc;
-    struct Guard {
-        tbk_model* m;
-        void* blk = nullptr;
-        ~Guard() {
-            if (blk) {
-                hipStreamSynchronize(m->ctx->stream);
-                hipFree(blk);
-            }
-            tbk_model_free(m);
-        }
-    } guard{pm};
-    std::vector<double> amp2((size_t)T.nterm * 2);
-    for (int64_t t = 0; t < T.nterm; ++t) amp2[2 * t] = T.amp[t].x, amp2[2 * t + 1] = T.amp[t].y;
-    MfMap map;
-    rc = mf_map(fn, B.P, T.nslot, T.slot_ptr, T.R4, amp2, T.nR, T.rvec, map);
-    if (rc) return rc;
-    const int64_t nft = (int64_t)map.term.size(), nnz = (int64_t)map.coef.size();
-
+    // the private Nambu model: spinless, N orbitals; the caller's tables hold the bare model, with the Fermi level where it is given
     BdgRun S{};
-    S.ctx = ctx, S.m = pm, S.n = n, S.dk = dk, S.nft = (int)nft, S.pmu = B.par_mu, S.np = B.np, S.nt = B.nt, S.kT = kT, S.nel = A.nel;
-    S.mu_step = mu_step;
-    S.pl = bdg_plan(n, dk, npts, B.nt, B.np, history, max_iter, nft, nnz);
+    S.n = n, S.dk = dk, S.pmu = B.par_mu, S.nt = B.nt, S.kT = kT, S.nel = A.nel, S.mu_step = mu_step;
     S.M = OccMesh{{1, 1, 1}, dk};
     for (int d = 0; d < dk; ++d) S.M.N[d] = mesh[d];
-    {
-        hipError_t e = hipMalloc(&guard.blk, S.pl.total);
-        if (e != hipSuccess) {
-            guard.blk = nullptr;
-            tbk_set_error("%s: hipMalloc(%zu) for the workspace: %s", fn, S.pl.total, hipGetErrorString(e));
-            return TBK_ENOMEM;
-        }
-    }
-    S.base = (unsigned char*)guard.blk;
-    S.amp = (cd*)((unsigned char*)pm->blob + T.o_amp);
-    S.rblock = (cd*)((unsigned char*)pm->blob + T.o_rblk);
-    hipStream_t st = ctx->stream;
-    auto up = [&](int i, const void* src, size_t bytes) -> int {
-        if (bytes) TBK_HIP(hipMemcpyAsync(S.base + S.pl.off[i], src, bytes, hipMemcpyHostToDevice, st));
-        return TBK_OK;
-    };
-    if ((rc = up(BdgPlan::TIJ, B.tij.data(), B.tij.size() * sizeof(int32_t)))) return rc;
-    if ((rc = up(BdgPlan::TR, B.tR.data(), B.tR.size() * sizeof(int32_t)))) return rc;
-    if ((rc = up(BdgPlan::GIDX, B.gidx.data(), B.gidx.size() * sizeof(int64_t)))) return rc;
-    if ((rc = up(BdgPlan::TBASE, map.base.data(), map.base.size() * sizeof(double)))) return rc;
-    if ((rc = up(BdgPlan::TPTR, map.ptr.data(), map.ptr.size() * sizeof(int32_t)))) return rc;
-    if ((rc = up(BdgPlan::TTERM, map.term.data(), map.term.size() * sizeof(int32_t)))) return rc;
-    if ((rc = up(BdgPlan::TRBLK, map.rblk.data(), map.rblk.size() * sizeof(int64_t)))) return rc;
-    if ((rc = up(BdgPlan::CCOEF, map.coef.data(), map.coef.size() * sizeof(double)))) return rc;
-    if ((rc = up(BdgPlan::CPAR, map.par.data(), map.par.size() * sizeof(int32_t)))) return rc;
-    if ((rc = up(BdgPlan::CPART, map.part.data(), map.part.size() * sizeof(int32_t)))) return rc;
-    if ((rc = up(BdgPlan::XIN, x_start, (size_t)B.np * sizeof(double)))) return rc;
-    TBK_HIP(hipMemsetAsync(S.buf<double>(BdgPlan::SMALL), 0, 1024, st));
-    TBK_HIP(hipMemsetAsync(S.buf<double>(BdgPlan::SPART), 0, al256((size_t)3 * S.pl.G * sizeof(double) + 512), st));
-    TBK_HIP(hipStreamSynchronize(st));                              // (the host vectors above go out of use)
-    rc = tbk_k_uniform_mesh_dev(ctx, dk, mesh, S.buf<double>(BdgPlan::K_ALL));
+    rc = mf_frame_open(S.F, ctx, fn, dim_k, N, 1, orb, onsite, nhop, hop_i, hop_j, hop_R, hop_amp, B.P, B.np,
+                       [&](MfFrame& F, int64_t nft, int64_t nnz) {
+                           S.pl = bdg_plan(n, dk, npts, B.nt, B.np, history, max_iter, nft, nnz);
+                           F.L = S.pl.loop, F.total = S.pl.total, F.k_all = S.pl.off[BdgPlan::K_ALL];
+                       });
     if (rc) return rc;
+    hipStream_t st = ctx->stream;
+    TBK_HIP(hipMemcpyAsync(S.buf<int32_t>(BdgPlan::TIJ), B.tij.data(), B.tij.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    TBK_HIP(hipMemcpyAsync(S.buf<int32_t>(BdgPlan::TR), B.tR.data(), B.tR.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    if ((rc = mf_frame_upload(S.F, B.gidx, x_start))) return rc;
+    // (SPART zeroed whole: behind the scan's partials and sums sits the level 0 it runs at)
+    if ((rc = mf_frame_start(S.F, dk, mesh, S.buf<double>(BdgPlan::SPART), al256((size_t)3 * S.pl.G * sizeof(double) + 512)))) return rc;
 
     int iterations = 0, converged = 0, cur = 0;
     rc = mf_iterate(
-        ctx, fn, N, max_iter, check_every, tol, S.buf<double>(BdgPlan::RESH), [&]() { return bdg_pass(S, cur); },
-        [&](int it) -> int {
+        ctx, fn, N, max_iter, check_every, tol, S.F.lp<double>(MfLoopBufs::RESH), [&]() { return bdg_pass(S, cur); },
+        [&](int it) {
             cur = it + 1;
-            ProfScope ps(ctx, "bdg_mix");
-            hipLaunchKernelGGL(k_mf_mix, dim3(1), dim3(256), 0, st, S.np, it, history, mixing, 0, (double)npts,
-                               (const double*)S.buf<cd>(BdgPlan::ACC), S.buf<double>(BdgPlan::XIN), (const double*)S.buf<double>(BdgPlan::XOUT),
-                               S.buf<double>(BdgPlan::XPREV), S.buf<double>(BdgPlan::RINGX), S.buf<double>(BdgPlan::RINGR),
-                               S.buf<double>(BdgPlan::SMALL), S.buf<double>(BdgPlan::RESH), S.buf<double>(BdgPlan::OCCH));
-            TBK_HIP(hipGetLastError());
-            return TBK_OK;
+            return mf_launch_mix(S.F, "bdg_mix", it, history, mixing, 0, (double)npts, S.buf<cd>(BdgPlan::ACC));   // (the row is k_bdg_mu's)
         },
         &iterations, &converged);
     if (rc) return rc;
 
     // once, from the last iteration's own levels: sum f E and S at the Fermi level 0 by the thermal scan of section 27, and min |E|
     double* spart = S.buf<double>(BdgPlan::SPART);
-    double* srows = spart + (size_t)3 * S.pl.G;
-    double* zero_dev = srows + 32;                                  // (the block was zeroed: the level the scan runs at)
+    double* zero_dev = spart + (size_t)3 * S.pl.G + 32;             // (the block was zeroed: the level the scan runs at)
     double* gpart = S.buf<double>(BdgPlan::GAPP);
     double* gmin = gpart + S.pl.G;
-    {
-        ProfScope ps(ctx, "bdg_scan");
-        hipLaunchKernelGGL(k_occ_scan, dim3(1, (unsigned)S.pl.G), dim3(256), 0, st, (const double*)S.buf<double>(BdgPlan::LEV), S.pl.nlev, S.pl.G,
-                           (const double*)zero_dev, 1, kT, spart);
-        TBK_HIP(hipGetLastError());
-    }
-    rc = kubo_rows_launch(ctx, spart, S.pl.G, 3, srows);
+    double sums[3], gap = 0.0, *srows;
+    rc = mf_frame_scan(S.F, "bdg_scan", S.buf<double>(BdgPlan::LEV), S.pl.nlev, S.pl.G, zero_dev, kT, spart, &srows);
     if (rc) return rc;
     {
         ProfScope ps(ctx, "bdg_gap");
@@ -238,42 +170,23 @@ extern "C" int tbk_bdg_mesh(tbk_ctx* ctx, int dim_k, int nsta, const double* orb
         hipLaunchKernelGGL(k_bdg_gap_min, dim3(1), dim3(64), 0, st, (const double*)gpart, S.pl.G, gmin);
         TBK_HIP(hipGetLastError());
     }
-    double sums[3], gap = 0.0;
     TBK_HIP(hipMemcpyAsync(sums, srows, sizeof sums, hipMemcpyDeviceToHost, st));
     TBK_HIP(hipMemcpyAsync(&gap, gmin, sizeof gap, hipMemcpyDeviceToHost, st));
-    TBK_HIP(hipMemcpyAsync(x_in, S.buf<double>(BdgPlan::XPREV), (size_t)B.np * sizeof(double), hipMemcpyDeviceToHost, st));
-    TBK_HIP(hipMemcpyAsync(x_out, S.buf<double>(BdgPlan::XOUT), (size_t)B.np * sizeof(double), hipMemcpyDeviceToHost, st));
-    TBK_HIP(hipMemcpyAsync(res_hist, S.buf<double>(BdgPlan::RESH), (size_t)iterations * sizeof(double), hipMemcpyDeviceToHost, st));
-    TBK_HIP(hipMemcpyAsync(occ_hist, S.buf<double>(BdgPlan::OCCH), (size_t)iterations * n * sizeof(double), hipMemcpyDeviceToHost, st));
+    if ((rc = mf_frame_download_x(S.F, x_in, x_out))) return rc;
+    if ((rc = mf_frame_download_hist(S.F, iterations, n, res_hist, occ_hist))) return rc;
     TBK_HIP(hipStreamSynchronize(st));
     const double nk = (double)npts;
-    // <H - mu N> = 1/2 (1 / N_k) sum f E + 1/2 sum_a (eps_a + d eps_a^in - mu_in) - sum_e V [n_a^in n_b^out + n_b^in n_a^out - n_a^out n_b^out
-    //   - 2 Re(conj(D^in) D^out) + |D^out|^2 + 2 Re(conj(F^in) F^out) - |F^out|^2], every term with its channel (tbk_bdg.h); the trace is that
-    // of the particle block's on-site energies in the field of x_in
+    // <H - mu N> = 1/2 (1 / N_k) sum f E + 1/2 sum_a (eps_a + d eps_a^in - mu_in) - E_dc (mf_edc, every bracket with its channel:
+    // tbk_bdg.h); the trace is that of the particle block's on-site energies in the field of x_in
     const double mu_in = have_nel ? x_in[B.par_mu] : nel_or_mu;
-    double tr = 0.0, edc = 0.0, nout = 0.0;
+    double tr = 0.0, nout = 0.0;
     for (int a = 0; a < n; ++a) {
         tr += onsite[2 * a];                                        // (bare; minus the given Fermi level where the tables carry it)
         nout += occ_hist[(size_t)(iterations - 1) * n + a];
     }
     if (have_nel) tr -= (double)n * mu_in;
-    for (int e = 0; e < nint; ++e) {
-        const int pa = B.occ_par[int_ab[2 * e]], pb = B.occ_par[int_ab[2 * e + 1]];
-        double t = 0.0;
-        if (B.hartree) {
-            tr += int_V[e] * (x_in[pa] + x_in[pb]);
-            t += x_in[pa] * x_out[pb] + x_in[pb] * x_out[pa] - x_out[pa] * x_out[pb];
-        }
-        if (B.fock) {
-            const int pr = B.par_d + 2 * e, pi = pr + 1;
-            t += -2.0 * (x_in[pr] * x_out[pr] + x_in[pi] * x_out[pi]) + x_out[pr] * x_out[pr] + x_out[pi] * x_out[pi];
-        }
-        if (B.pairing) {
-            const int pr = B.par_f + 2 * e, pi = pr + 1;
-            t += 2.0 * (x_in[pr] * x_out[pr] + x_in[pi] * x_out[pi]) - x_out[pr] * x_out[pr] - x_out[pi] * x_out[pi];
-        }
-        edc += int_V[e] * t;
-    }
+    for (int e = 0; B.hartree && e < nint; ++e) tr += int_V[e] * (x_in[B.occ_par[int_ab[2 * e]]] + x_in[B.occ_par[int_ab[2 * e + 1]]]);
+    const double edc = mf_edc(nint, int_ab, int_V, B.occ_par, B.hartree, B.par_d, B.par_f, x_in, x_out);
     const double omega = 0.5 * sums[1] / nk + 0.5 * tr - edc, ent = 0.5 * sums[2] / nk;
     energies[0] = omega + mu_in * nout;                             // E = <H - mu N> + mu N
     energies[1] = ent;

@@ -9,7 +9,6 @@
 // through with the same tiles, the same groups and the same order of operations whatever stands beside it.
 #pragma once
 #include <complex>
-#include <set>
 #include "tbk_mf.h"
 
 static const int kBseBandMax = 16;                          // selected valence bands, and conduction bands
@@ -116,25 +115,22 @@ struct BseProblem {
 static int bse_problem(const char* fn, int dk, int n, const BseArgs& A, BseProblem& P) {
     P = BseProblem();
     P.dk = dk, P.nint = A.nint, P.ne = 2 * A.nint;
-    std::set<std::array<int, 5>> seen;
-    std::set<int> touched;
+    IntBonds W;                                               // the walk of tbk_int.h: the repeated bond, the touched states
+    int rc = int_bonds(fn, dk, n, A.nint, A.ab, A.R, A.V, W);
+    if (rc) return rc;
     for (int e = 0; e < A.nint; ++e) {
         const int a = A.ab[2 * e], b = A.ab[2 * e + 1];
         int R[3] = {0, 0, 0};
         for (int d = 0; d < dk; ++d) R[d] = A.R[(int64_t)e * dk + d];
-        const std::array<int, 5> k1{a, b, R[0], R[1], R[2]}, k2{b, a, -R[0], -R[1], -R[2]};
-        TBK_REQUIRE(!seen.count(k1) && !seen.count(k2), TBK_EINVAL, "%s: interaction %d repeats an earlier bond (a bond is given once)", fn, e);
-        seen.insert(k1);
         P.ea.push_back(a), P.eb.push_back(b);
         P.ea.push_back(b), P.eb.push_back(a);
         for (int d = 0; d < 3; ++d) P.eR.push_back(R[d]);
         for (int d = 0; d < 3; ++d) P.eR.push_back(-R[d]);
         P.eV.push_back(A.V[e]), P.eV.push_back(A.V[e]);
-        touched.insert(a), touched.insert(b);
     }
-    (void)n;
     P.ned = A.direct ? P.ne : 0;
-    if (A.exchange) P.st.assign(touched.begin(), touched.end());
+    for (int a = 0; A.exchange && a < n; ++a)
+        if (W.occ_par[a] >= 0) P.st.push_back(a);
     P.nst = (int)P.st.size();
     P.np = P.ned + P.nst;
     TBK_REQUIRE(P.np <= kBseEntryMax, TBK_EINVAL, "%s: %d directed entries and touched states (at most %d)", fn, P.np, kBseEntryMax);

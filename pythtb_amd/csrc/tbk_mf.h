@@ -6,9 +6,7 @@
 //
 // Every partition is a function of (mesh, nsta, dim_k, the interaction's structure) alone.
 #pragma once
-#include <map>
-#include <array>
-#include "tbk_occ.h"
+#include "tbk_int.h"
 
 static const int64_t kMfParamMax = (int64_t)1 << 20;    // real parameters of the field
 static const int kMfHistMax = 8;                        // Anderson pairs kept
@@ -49,74 +47,51 @@ static int mf_check(const char* fn, int dk, int n, const int32_t* mesh, const Mf
         TBK_REQUIRE(std::isfinite(A.mu), TBK_EINVAL, "%s: the Fermi level must be finite", fn);
         target = 0.0;
     }
-    for (int e = 0; e < A.nint; ++e) {
-        const int a = A.ab[2 * e], b = A.ab[2 * e + 1];
-        TBK_REQUIRE(a >= 0 && a < n && b >= 0 && b < n, TBK_EINVAL, "%s: interaction %d has a state index out of range", fn, e);
-        TBK_REQUIRE(std::isfinite(A.V[e]), TBK_EINVAL, "%s: interaction %d is not finite", fn, e);
-        bool zero = true;
-        for (int d = 0; d < dk; ++d) {
-            const int32_t r = A.R[(int64_t)e * dk + d];
-            TBK_REQUIRE(r > -kOccRAbsMax && r < kOccRAbsMax, TBK_EINVAL, "%s: interaction %d has a lattice component of 2^30 or more", fn, e);
-            zero = zero && r == 0;
-        }
-        TBK_REQUIRE(!(a == b && zero), TBK_EINVAL, "%s: interaction %d couples state %d to itself (a self-interaction)", fn, e, a);
-    }
+    for (int e = 0; e < A.nint; ++e)
+        if ((rc = int_entry_check(fn, dk, n, e, A.ab, A.R, A.V))) return rc;
     return TBK_OK;
 }
 
 // ---------------------------------------------------------------- the parameters
 // x = (n_a of every state some V touches, ascending a; then, with Fock, Re and Im of D_ab(R) of every entry, in list order).
-// An entry (a, b, R) stands for the bond and its mirror (b, a, -R): given twice in either form it is refused.
+// The walk over the list is tbk_int.h's: occ_par[a] is the parameter of n_a.
 struct MfField {           // one contribution to a term of the private model: amp(key) += coef x[par] in its real (part 0) or imaginary part
     int a, b, R[4];        // the key in flatten order: a <= b (a > b is stored as (b, a, -R), conjugated: the sign of an imaginary coef)
     double coef;
     int par, part;
 };
-struct MfProblem {
-    int n = 0, dk = 0, nint = 0, nocc = 0, fock = 0, nR = 0;
+// The field entries of one (entry, channel, block); `off` shifts both states into the block (0: the particles; n: the holes of a
+// Nambu model, tbk_bdg.h).
+// Hartree: the on-site energy of a gets s V n_b and that of b gets s V n_a (a == b, R != 0: 2 V n_a, the bonds to R and to -R)
+static void mf_field_hartree(std::vector<MfField>& F, int a, int b, double V, int par_a, int par_b, int off, double s) {
+    F.push_back(MfField{off + a, off + a, {0, 0, 0, 0}, s * V, par_b, 0});
+    F.push_back(MfField{off + b, off + b, {0, 0, 0, 0}, s * V, par_a, 0});
+}
+// Fock: the entry (a, b, R) of the table gets (s_re Re + i s_im Im) V D_ab(R), D = x[pr] + i x[pr + 1]: -1, -1 on the particles
+// (-V D), +1, -1 on the holes (V conj(D)).  One stored direction per call: the slot (a, b, R) itself where a <= b, or (mirror) the
+// slot (b, a, -R) with the conjugate where a >= b -- on the diagonal (a == b) both, the slot also holds the mirror term at -R.
+static void mf_field_fock(std::vector<MfField>& F, int a, int b, const int* R, double V, int pr, int off, double s_re, double s_im, bool mirror) {
+    const int m = mirror ? -1 : 1;
+    const MfField f{off + (mirror ? b : a), off + (mirror ? a : b), {m * R[0], m * R[1], m * R[2], m * R[3]}, s_re * V, pr, 0};
+    F.push_back(f);
+    F.push_back(f);
+    F.back().coef = m * s_im * V, F.back().par = pr + 1, F.back().part = 1;
+}
+struct MfProblem : IntBonds {
+    int n = 0, dk = 0, nint = 0, fock = 0;
     int64_t np = 0;
-    std::vector<int> occ_par;            // [n]: the parameter of n_a, -1 where no V touches a
-    std::vector<int32_t> Rl;             // [nR][dk]: R = 0 first, then the entries' vectors in order of first appearance
-    std::vector<int> ent_r;              // [nint]: the index of an entry's R in Rl
     std::vector<int64_t> gidx;           // [np]: where x_out[p] sits in acc[nR][n][n] seen as doubles
     std::vector<int32_t> pin;            // [npin][6]
     std::vector<MfField> field;
-    std::vector<double> rowsum;          // [n]: sum_b,R |V_ab(R)| (both directions of every bond)
 };
 static int mf_problem(const char* fn, int dk, int n, const MfArgs& A, MfProblem& P) {
     P = MfProblem();
+    int rc = int_bonds(fn, dk, n, A.nint, A.ab, A.R, A.V, P);
+    if (rc) return rc;
     P.n = n, P.dk = dk, P.nint = A.nint, P.fock = A.fock ? 1 : 0;
-    P.occ_par.assign((size_t)n, -1);
-    P.rowsum.assign((size_t)n, 0.0);
-    std::map<std::array<int, 6>, int> seen;
-    std::map<std::array<int, 4>, int> rid;
-    rid[{0, 0, 0, 0}] = 0;
-    P.Rl.assign((size_t)dk, 0);
-    P.ent_r.resize((size_t)A.nint);
-    for (int e = 0; e < A.nint; ++e) {
-        const int a = A.ab[2 * e], b = A.ab[2 * e + 1];
-        std::array<int, 4> R{0, 0, 0, 0};
-        for (int d = 0; d < dk; ++d) R[d] = A.R[(int64_t)e * dk + d];
-        const std::array<int, 6> k1{a, b, R[0], R[1], R[2], R[3]}, k2{b, a, -R[0], -R[1], -R[2], -R[3]};
-        TBK_REQUIRE(!seen.count(k1) && !seen.count(k2), TBK_EINVAL, "%s: interaction %d repeats the bond of interaction %d (a bond is given once)",
-                    fn, e, seen.count(k1) ? seen[k1] : seen[k2]);
-        seen[k1] = e;
-        P.occ_par[a] = P.occ_par[b] = 0;
-        auto it = rid.find(R);
-        if (it == rid.end()) {
-            it = rid.emplace(R, (int)rid.size()).first;
-            for (int d = 0; d < dk; ++d) P.Rl.push_back(R[d]);
-        }
-        P.ent_r[e] = it->second;
-        P.rowsum[a] += fabs(A.V[e]);
-        P.rowsum[b] += fabs(A.V[e]);
-    }
-    P.nR = (int)rid.size();
     TBK_REQUIRE(P.nR <= kOccRMax, TBK_EINVAL, "%s: %d distinct lattice vectors (at most %d)", fn, P.nR, kOccRMax);
     TBK_REQUIRE((int64_t)P.nR * n * n <= kOccOutCap, TBK_EINVAL, "%s: nR * nsta^2 = %lld (at most %lld)", fn, (long long)P.nR * n * n,
                 (long long)kOccOutCap);
-    for (int a = 0; a < n; ++a)
-        if (P.occ_par[a] == 0) P.occ_par[a] = P.nocc++;
     P.np = (int64_t)P.nocc + (P.fock ? 2 * (int64_t)A.nint : 0);
     TBK_REQUIRE(P.np <= kMfParamMax, TBK_EINVAL, "%s: %lld parameters (at most 2^20)", fn, (long long)P.np);
     P.gidx.resize((size_t)P.np);
@@ -132,25 +107,15 @@ static int mf_problem(const char* fn, int dk, int n, const MfArgs& A, MfProblem&
         const double V = A.V[e];
         int R[4] = {0, 0, 0, 0};
         for (int d = 0; d < dk; ++d) R[d] = A.R[(int64_t)e * dk + d];
-        // Hartree: the on-site energy of a gets V n_b and that of b gets V n_a (a == b, R != 0: 2 V n_a, the bonds to R and to -R)
-        P.field.push_back(MfField{a, a, {0, 0, 0, 0}, V, P.occ_par[b], 0});
-        P.field.push_back(MfField{b, b, {0, 0, 0, 0}, V, P.occ_par[a], 0});
+        mf_field_hartree(P.field, a, b, V, P.occ_par[a], P.occ_par[b], 0, 1.0);
         if (!P.fock) continue;
         const int pr = P.nocc + 2 * e, pi = pr + 1;
         P.gidx[pr] = 2 * ((int64_t)P.ent_r[e] * nn + (int64_t)a * n + b);
         P.gidx[pi] = P.gidx[pr] + 1;
         const int32_t q[6] = {a, b, R[0], R[1], R[2], R[3]};
         P.pin.insert(P.pin.end(), q, q + 6);
-        // Fock: the entry (a, b, R) of the table gets -V D_ab(R); stored above the diagonal, so (a > b) as (b, a, -R) conjugated;
-        // on the diagonal (a == b) the slot also holds the mirror term at -R with the conjugate
-        if (a <= b) {
-            P.field.push_back(MfField{a, b, {R[0], R[1], R[2], R[3]}, -V, pr, 0});
-            P.field.push_back(MfField{a, b, {R[0], R[1], R[2], R[3]}, -V, pi, 1});
-        }
-        if (a >= b) {
-            P.field.push_back(MfField{b, a, {-R[0], -R[1], -R[2], -R[3]}, -V, pr, 0});
-            P.field.push_back(MfField{b, a, {-R[0], -R[1], -R[2], -R[3]}, V, pi, 1});
-        }
+        if (a <= b) mf_field_fock(P.field, a, b, R, V, pr, 0, -1.0, -1.0, false);
+        if (a >= b) mf_field_fock(P.field, a, b, R, V, pr, 0, -1.0, -1.0, true);
     }
     return TBK_OK;
 }
@@ -260,15 +225,42 @@ inline __host__ __device__ bool mf_anderson(const int cnt, const double* B, doub
 }
 
 // ---------------------------------------------------------------- the workspace
+// The loop's share of a driver's private device block, behind the driver's own buffers: the vectors and the ring of the mixing, the
+// gather indices, the term -> parameter map and the two history arrays (occ_cols occupations per iteration).  Returns its end.
+struct MfLoopBufs {
+    enum { XIN, XOUT, XPREV, RINGX, RINGR, SMALL, GIDX, TBASE, TPTR, TTERM, TRBLK, CCOEF, CPAR, CPART, RESH, OCCH, NBUF };
+    size_t off[NBUF + 1];
+};
+static size_t mf_loop_bufs(MfLoopBufs& L, size_t at, int64_t np, int history, int max_iter, int64_t nft, int64_t nnz, int occ_cols) {
+    const size_t D = sizeof(double);
+    const int m = std::max(history, 1);
+    size_t b[MfLoopBufs::NBUF];
+    b[MfLoopBufs::XIN] = b[MfLoopBufs::XOUT] = b[MfLoopBufs::XPREV] = (size_t)np * D;
+    b[MfLoopBufs::RINGX] = b[MfLoopBufs::RINGR] = (size_t)m * np * D;
+    b[MfLoopBufs::SMALL] = 1024;                        // the Gram matrix [8][8]
+    b[MfLoopBufs::GIDX] = (size_t)np * sizeof(int64_t);
+    b[MfLoopBufs::TBASE] = (size_t)nft * 2 * D;
+    b[MfLoopBufs::TPTR] = (size_t)(nft + 1) * sizeof(int32_t);
+    b[MfLoopBufs::TTERM] = (size_t)nft * sizeof(int32_t);
+    b[MfLoopBufs::TRBLK] = (size_t)nft * sizeof(int64_t);
+    b[MfLoopBufs::CCOEF] = (size_t)nnz * D;
+    b[MfLoopBufs::CPAR] = b[MfLoopBufs::CPART] = (size_t)nnz * sizeof(int32_t);
+    b[MfLoopBufs::RESH] = (size_t)max_iter * D;
+    b[MfLoopBufs::OCCH] = (size_t)max_iter * occ_cols * D;
+    L.off[0] = al256(at);
+    for (int i = 0; i < MfLoopBufs::NBUF; ++i) L.off[i + 1] = L.off[i] + al256(b[i]);
+    return L.off[MfLoopBufs::NBUF];
+}
+
 // One private device block.  resident: every chunk's eigenvectors stay (chunk c at c * vstride c128); else one chunk's worth.
 struct MfPlan {
     bool resident = false;
     int64_t npts = 0, chunk = 0, nchunks = 0, nlev = 0, vstride = 0;
     int G = 0;                 // groups of the level scans (occ_scan_groups)
     OccDmPlan dm;
-    enum { K_ALL, LEV, EC, VEC, FW, DPART, ACC, RDEV, FPART, FSMALL, SPART, XIN, XOUT, XPREV, RINGX, RINGR, SMALL, GIDX, TBASE, TPTR, TTERM, TRBLK,
-           CCOEF, CPAR, CPART, RESH, OCCH, NBUF };
+    enum { K_ALL, LEV, EC, VEC, FW, DPART, ACC, RDEV, FPART, FSMALL, SPART, NBUF };
     size_t off[NBUF + 1];
+    MfLoopBufs loop;
     size_t total = 0;
 };
 static inline int64_t mf_resident_cap(long long knob) {
@@ -286,7 +278,6 @@ static MfPlan mf_plan(int n, int dk, int64_t npts, int nR, int64_t np, int histo
     p.nchunks = p.dm.nchunks;
     p.resident = npts * nn <= resident_cap;
     p.vstride = (int64_t)(al256((size_t)p.chunk * nn * sizeof(cd)) / sizeof(cd));
-    const int m = std::max(history, 1);
     size_t b[MfPlan::NBUF];
     b[MfPlan::K_ALL] = (size_t)npts * dk * D;
     b[MfPlan::LEV] = (size_t)p.nlev * D;
@@ -299,20 +290,9 @@ static MfPlan mf_plan(int n, int dk, int64_t npts, int nR, int64_t np, int histo
     b[MfPlan::FPART] = (size_t)2 * p.G * D;
     b[MfPlan::FSMALL] = 2048;                           // mu, lo, hi, target, edges[2] of the one filling, 256 bytes apart
     b[MfPlan::SPART] = (size_t)3 * p.G * D + 256;       // the final scan's partials and its three sums
-    b[MfPlan::XIN] = b[MfPlan::XOUT] = b[MfPlan::XPREV] = (size_t)np * D;
-    b[MfPlan::RINGX] = b[MfPlan::RINGR] = (size_t)m * np * D;
-    b[MfPlan::SMALL] = 1024;                            // the Gram matrix [8][8]
-    b[MfPlan::GIDX] = (size_t)np * sizeof(int64_t);
-    b[MfPlan::TBASE] = (size_t)nft * 2 * D;
-    b[MfPlan::TPTR] = (size_t)(nft + 1) * sizeof(int32_t);
-    b[MfPlan::TTERM] = (size_t)nft * sizeof(int32_t);
-    b[MfPlan::TRBLK] = (size_t)nft * sizeof(int64_t);
-    b[MfPlan::CCOEF] = (size_t)nnz * D;
-    b[MfPlan::CPAR] = b[MfPlan::CPART] = (size_t)nnz * sizeof(int32_t);
-    b[MfPlan::RESH] = (size_t)max_iter * D;
-    b[MfPlan::OCCH] = (size_t)max_iter * n * D;
     p.off[0] = 256;
     for (int i = 0; i < MfPlan::NBUF; ++i) p.off[i + 1] = p.off[i] + al256(b[i]);
-    p.total = p.off[MfPlan::NBUF];
+    p.total = mf_loop_bufs(p.loop, p.off[MfPlan::NBUF], np, history, max_iter, nft, nnz, n);
     return p;
 }
+

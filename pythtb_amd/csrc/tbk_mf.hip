@@ -126,50 +126,38 @@ __global__ __launch_bounds__(256) void k_mf_mix(const int64_t np, const int it, 
 // ---------------------------------------------------------------- host side
 namespace {
 struct MfRun {
-    tbk_ctx* ctx;
-    tbk_model* m;
+    MfFrame F;                 // the private model, the workspace and the loop's buffers (tbk_mf_dev.h)
     MfPlan pl;
     OccMesh M;
-    unsigned char* base;
-    int n, dk, nR, nft, fixed_mu;
-    int64_t np;
-    double kT, mu;
-    cd *amp, *rblock;
+    int n, dk, nR, fixed_mu;
+    double kT;
     template <class T>
-    T* buf(int i) const { return (T*)(base + pl.off[i]); }
-    double* fsmall(int i) const { return (double*)(base + pl.off[MfPlan::FSMALL] + 256 * (size_t)i); }
+    T* buf(int i) const { return (T*)(F.base + pl.off[i]); }
+    double* fsmall(int i) const { return (double*)(F.base + pl.off[MfPlan::FSMALL] + 256 * (size_t)i); }
     double* mu_dev() const { return fsmall(0); }
 };
 
 int mf_solve_chunk(const MfRun& S, int64_t c, cd* vec) {
     const int64_t first = c * S.pl.chunk, cnt = std::min<int64_t>(S.pl.chunk, S.pl.npts - first);
     double* ec = S.buf<double>(MfPlan::EC);
-    int rc = tbk_solve_list_dev(S.m, S.buf<double>(MfPlan::K_ALL) + first * S.dk, cnt, ec, (double*)vec);
+    int rc = tbk_solve_list_dev(S.F.m, S.buf<double>(MfPlan::K_ALL) + first * S.dk, cnt, ec, (double*)vec);
     if (rc) return rc;
     TBK_HIP(hipMemcpyAsync(S.buf<double>(MfPlan::LEV) + first * S.n, ec, (size_t)cnt * S.n * sizeof(double), hipMemcpyDeviceToDevice,
-                           S.ctx->stream));
+                           S.F.ctx->stream));
     return TBK_OK;
 }
 int mf_dm_chunk(const MfRun& S, int64_t c, const cd* vec) {
     const int64_t first = c * S.pl.chunk, cnt = std::min<int64_t>(S.pl.chunk, S.pl.npts - first);
-    return occ_dm_stage(S.ctx, S.m->view, S.pl.dm, S.M, first, cnt, S.buf<double>(MfPlan::K_ALL) + first * S.dk,
+    return occ_dm_stage(S.F.ctx, S.F.m->view, S.pl.dm, S.M, first, cnt, S.buf<double>(MfPlan::K_ALL) + first * S.dk,
                         S.buf<double>(MfPlan::LEV) + first * S.n, vec, S.mu_dev(), 0.0, S.kT, S.buf<double>(MfPlan::FW),
                         S.buf<int32_t>(MfPlan::RDEV), S.nR, S.buf<cd>(MfPlan::DPART), S.buf<cd>(MfPlan::ACC), c > 0 ? 1 : 0);
 }
 // x_in -> H[x_in] -> the levels -> mu -> D -> x_out
 int mf_pass(const MfRun& S) {
-    tbk_ctx* ctx = S.ctx;
-    if (S.nft > 0) {
-        ProfScope ps(ctx, "mf_apply");
-        hipLaunchKernelGGL(k_mf_apply, dim3(nblk(S.nft)), dim3(256), 0, ctx->stream, S.nft, (const int32_t*)S.buf<int32_t>(MfPlan::TPTR),
-                           (const int32_t*)S.buf<int32_t>(MfPlan::TTERM), (const int64_t*)S.buf<int64_t>(MfPlan::TRBLK),
-                           (const double*)S.buf<double>(MfPlan::TBASE), (const double*)S.buf<double>(MfPlan::CCOEF),
-                           (const int32_t*)S.buf<int32_t>(MfPlan::CPAR), (const int32_t*)S.buf<int32_t>(MfPlan::CPART),
-                           (const double*)S.buf<double>(MfPlan::XIN), S.amp, S.rblock);
-        TBK_HIP(hipGetLastError());
-    }
+    tbk_ctx* ctx = S.F.ctx;
+    int rc = mf_launch_apply(S.F, "mf_apply");
+    if (rc) return rc;
     cd* vec = S.buf<cd>(MfPlan::VEC);
-    int rc;
     if (S.pl.resident || !S.fixed_mu)
         for (int64_t c = 0; c < S.pl.nchunks; ++c)
             if ((rc = mf_solve_chunk(S, c, vec + (S.pl.resident ? c * S.pl.vstride : 0)))) return rc;
@@ -182,32 +170,25 @@ int mf_pass(const MfRun& S) {
         if ((rc = mf_dm_chunk(S, c, vec + (S.pl.resident ? c * S.pl.vstride : 0)))) return rc;
     }
     ProfScope ps(ctx, "mf_gather");
-    hipLaunchKernelGGL(k_mf_gather, dim3(nblk(S.np)), dim3(256), 0, ctx->stream, S.np, (const int64_t*)S.buf<int64_t>(MfPlan::GIDX),
-                       (const double*)S.buf<cd>(MfPlan::ACC), (double)S.pl.npts, S.buf<double>(MfPlan::XOUT));
+    hipLaunchKernelGGL(k_mf_gather, dim3(nblk(S.F.np)), dim3(256), 0, ctx->stream, S.F.np, (const int64_t*)S.F.lp<int64_t>(MfLoopBufs::GIDX),
+                       (const double*)S.buf<cd>(MfPlan::ACC), (double)S.pl.npts, S.F.lp<double>(MfLoopBufs::XOUT));
     TBK_HIP(hipGetLastError());
     return TBK_OK;
 }
 int mf_loop(MfRun& S, const MfArgs& A, int start_mode, int* iterations, int* converged) {
-    tbk_ctx* ctx = S.ctx;
+    tbk_ctx* ctx = S.F.ctx;
+    const int64_t np = S.F.np;
     int rc;
     if (start_mode == 0) {                                         // the field of the bare model at the same filling: x = 0 goes in
-        TBK_HIP(hipMemsetAsync(S.buf<double>(MfPlan::XIN), 0, (size_t)S.np * sizeof(double), ctx->stream));
+        TBK_HIP(hipMemsetAsync(S.F.lp<double>(MfLoopBufs::XIN), 0, (size_t)np * sizeof(double), ctx->stream));
         if ((rc = mf_pass(S))) return rc;
-        hipLaunchKernelGGL(k_mf_copy, dim3(nblk(S.np)), dim3(256), 0, ctx->stream, S.np, (const double*)S.buf<double>(MfPlan::XOUT),
-                           S.buf<double>(MfPlan::XIN));
+        hipLaunchKernelGGL(k_mf_copy, dim3(nblk(np)), dim3(256), 0, ctx->stream, np, (const double*)S.F.lp<double>(MfLoopBufs::XOUT),
+                           S.F.lp<double>(MfLoopBufs::XIN));
         TBK_HIP(hipGetLastError());
     }
     return mf_iterate(
-        ctx, "tbk_mean_field_mesh", S.n, A.max_iter, A.check_every, A.tol, S.buf<double>(MfPlan::RESH), [&]() { return mf_pass(S); },
-        [&](int it) -> int {
-            ProfScope ps(ctx, "mf_mix");
-            hipLaunchKernelGGL(k_mf_mix, dim3(1), dim3(256), 0, ctx->stream, S.np, it, A.history, A.mixing, S.n, (double)S.pl.npts,
-                               (const double*)S.buf<cd>(MfPlan::ACC), S.buf<double>(MfPlan::XIN), (const double*)S.buf<double>(MfPlan::XOUT),
-                               S.buf<double>(MfPlan::XPREV), S.buf<double>(MfPlan::RINGX), S.buf<double>(MfPlan::RINGR),
-                               S.buf<double>(MfPlan::SMALL), S.buf<double>(MfPlan::RESH), S.buf<double>(MfPlan::OCCH));
-            TBK_HIP(hipGetLastError());
-            return TBK_OK;
-        },
+        ctx, "tbk_mean_field_mesh", S.n, A.max_iter, A.check_every, A.tol, S.F.lp<double>(MfLoopBufs::RESH), [&]() { return mf_pass(S); },
+        [&](int it) { return mf_launch_mix(S.F, "mf_mix", it, A.history, A.mixing, S.n, (double)S.pl.npts, S.buf<cd>(MfPlan::ACC)); },
         iterations, converged);
 }
 }  // namespace
@@ -240,109 +221,44 @@ extern "C" int tbk_mean_field_mesh(tbk_ctx* ctx, int dim_k, int norb, int nspin,
         for (int64_t p = 0; p < P.np; ++p) TBK_REQUIRE(std::isfinite(x_start[p]), TBK_EINVAL, "%s: the start field is not finite", fn);
     TBK_HIP(hipSetDevice(ctx->device));
 
-    // the private model: every field entry pinned; never the caller's cached handle
-    tbk_model* pm = nullptr;
-    TbkFlatTerms T;
-    rc = tbk_model_upload_pinned(ctx, dim_k, norb, nspin, orb, onsite, nhop, hop_i, hop_j, hop_R, hop_amp, (int64_t)P.pin.size() / 6,
-                                 P.pin.data(), &pm, &T);
-    if (rc) return rc;
-    struct Guard {
-        tbk_model* m;
-        void* blk = nullptr;
-        ~Guard() {
-            if (blk) {
-                hipStreamSynchronize(m->ctx->stream);
-                hipFree(blk);
-            }
-            tbk_model_free(m);
-        }
-    } guard{pm};
-    std::vector<double> amp2((size_t)T.nterm * 2);
-    for (int64_t t = 0; t < T.nterm; ++t) amp2[2 * t] = T.amp[t].x, amp2[2 * t + 1] = T.amp[t].y;
-    MfMap map;
-    rc = mf_map(fn, P, T.nslot, T.slot_ptr, T.R4, amp2, T.nR, T.rvec, map);
-    if (rc) return rc;
-    const int64_t nft = (int64_t)map.term.size(), nnz = (int64_t)map.coef.size();
-
     MfRun S{};
-    S.ctx = ctx, S.m = pm, S.n = n, S.dk = dk, S.nR = P.nR, S.nft = (int)nft, S.np = P.np, S.kT = kT, S.fixed_mu = have_nel ? 0 : 1;
-    S.pl = mf_plan(n, dk, npts, P.nR, P.np, history, max_iter, nft, nnz, mf_resident_cap(tbk_knobs().mf_resident_max));
+    S.n = n, S.dk = dk, S.nR = P.nR, S.kT = kT, S.fixed_mu = have_nel ? 0 : 1;
     S.M = OccMesh{{1, 1, 1}, dk};
     for (int d = 0; d < dk; ++d) S.M.N[d] = mesh[d];
-    {
-        hipError_t e = hipMalloc(&guard.blk, S.pl.total);
-        if (e != hipSuccess) {
-            guard.blk = nullptr;
-            tbk_set_error("%s: hipMalloc(%zu) for the workspace: %s", fn, S.pl.total, hipGetErrorString(e));
-            return TBK_ENOMEM;
-        }
-    }
-    S.base = (unsigned char*)guard.blk;
-    S.amp = (cd*)((unsigned char*)pm->blob + T.o_amp);
-    S.rblock = (cd*)((unsigned char*)pm->blob + T.o_rblk);
+    rc = mf_frame_open(S.F, ctx, fn, dim_k, norb, nspin, orb, onsite, nhop, hop_i, hop_j, hop_R, hop_amp, P, P.np,
+                       [&](MfFrame& F, int64_t nft, int64_t nnz) {
+                           S.pl = mf_plan(n, dk, npts, P.nR, P.np, history, max_iter, nft, nnz, mf_resident_cap(tbk_knobs().mf_resident_max));
+                           F.L = S.pl.loop, F.total = S.pl.total, F.k_all = S.pl.off[MfPlan::K_ALL];
+                       });
+    if (rc) return rc;
     hipStream_t st = ctx->stream;
-    auto up = [&](int i, const void* src, size_t bytes) -> int {
-        if (bytes) TBK_HIP(hipMemcpyAsync(S.base + S.pl.off[i], src, bytes, hipMemcpyHostToDevice, st));
-        return TBK_OK;
-    };
-    if ((rc = up(MfPlan::RDEV, P.Rl.data(), P.Rl.size() * sizeof(int32_t)))) return rc;
-    if ((rc = up(MfPlan::GIDX, P.gidx.data(), P.gidx.size() * sizeof(int64_t)))) return rc;
-    if ((rc = up(MfPlan::TBASE, map.base.data(), map.base.size() * sizeof(double)))) return rc;
-    if ((rc = up(MfPlan::TPTR, map.ptr.data(), map.ptr.size() * sizeof(int32_t)))) return rc;
-    if ((rc = up(MfPlan::TTERM, map.term.data(), map.term.size() * sizeof(int32_t)))) return rc;
-    if ((rc = up(MfPlan::TRBLK, map.rblk.data(), map.rblk.size() * sizeof(int64_t)))) return rc;
-    if ((rc = up(MfPlan::CCOEF, map.coef.data(), map.coef.size() * sizeof(double)))) return rc;
-    if ((rc = up(MfPlan::CPAR, map.par.data(), map.par.size() * sizeof(int32_t)))) return rc;
-    if ((rc = up(MfPlan::CPART, map.part.data(), map.part.size() * sizeof(int32_t)))) return rc;
-    if (start_mode == 1 && (rc = up(MfPlan::XIN, x_start, (size_t)P.np * sizeof(double)))) return rc;
+    TBK_HIP(hipMemcpyAsync(S.buf<int32_t>(MfPlan::RDEV), P.Rl.data(), P.Rl.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    if ((rc = mf_frame_upload(S.F, P.gidx, start_mode == 1 ? x_start : nullptr))) return rc;
     TBK_HIP(hipMemcpyAsync(S.fsmall(3), &target, sizeof(double), hipMemcpyHostToDevice, st));
     if (!have_nel) TBK_HIP(hipMemcpyAsync(S.mu_dev(), &A.mu, sizeof(double), hipMemcpyHostToDevice, st));
-    TBK_HIP(hipMemsetAsync(S.buf<double>(MfPlan::SMALL), 0, 1024, st));
-    TBK_HIP(hipStreamSynchronize(st));                              // (the host vectors above go out of use)
-    rc = tbk_k_uniform_mesh_dev(ctx, dk, mesh, S.buf<double>(MfPlan::K_ALL));
-    if (rc) return rc;
+    if ((rc = mf_frame_start(S.F, dk, mesh))) return rc;
 
     int iterations = 0, converged = 0;
     rc = mf_loop(S, A, start_mode, &iterations, &converged);
     if (rc) return rc;
 
     // the energies, once, from the last iteration's own levels and mu: N, E_band, S by the thermal scan of section 27
-    double* spart = S.buf<double>(MfPlan::SPART);
-    double* srows = spart + (size_t)3 * S.pl.G;
-    {
-        ProfScope ps(ctx, "mf_scan");
-        hipLaunchKernelGGL(k_occ_scan, dim3(1, (unsigned)S.pl.G), dim3(256), 0, st, (const double*)S.buf<double>(MfPlan::LEV), S.pl.nlev, S.pl.G,
-                           (const double*)S.mu_dev(), 1, kT, spart);
-        TBK_HIP(hipGetLastError());
-    }
-    rc = kubo_rows_launch(ctx, spart, S.pl.G, 3, srows);
+    double sums[3], *srows;
+    rc = mf_frame_scan(S.F, "mf_scan", S.buf<double>(MfPlan::LEV), S.pl.nlev, S.pl.G, S.mu_dev(), kT, S.buf<double>(MfPlan::SPART), &srows);
     if (rc) return rc;
-    double sums[3];
     TBK_HIP(hipMemcpyAsync(sums, srows, sizeof sums, hipMemcpyDeviceToHost, st));
     TBK_HIP(hipMemcpyAsync(mu_out, S.mu_dev(), sizeof(double), hipMemcpyDeviceToHost, st));
-    TBK_HIP(hipMemcpyAsync(x_in, S.buf<double>(MfPlan::XPREV), (size_t)P.np * sizeof(double), hipMemcpyDeviceToHost, st));
-    TBK_HIP(hipMemcpyAsync(x_out, S.buf<double>(MfPlan::XOUT), (size_t)P.np * sizeof(double), hipMemcpyDeviceToHost, st));
+    if ((rc = mf_frame_download_x(S.F, x_in, x_out))) return rc;
     const size_t nd = (size_t)P.nR * n * n * 2;
     TBK_HIP(hipMemcpyAsync(dens, S.buf<cd>(MfPlan::ACC), nd * sizeof(double), hipMemcpyDeviceToHost, st));
-    TBK_HIP(hipMemcpyAsync(res_hist, S.buf<double>(MfPlan::RESH), (size_t)iterations * sizeof(double), hipMemcpyDeviceToHost, st));
-    TBK_HIP(hipMemcpyAsync(occ_hist, S.buf<double>(MfPlan::OCCH), (size_t)iterations * n * sizeof(double), hipMemcpyDeviceToHost, st));
+    if ((rc = mf_frame_download_hist(S.F, iterations, n, res_hist, occ_hist))) return rc;
     TBK_HIP(hipStreamSynchronize(st));
     const double nk = (double)npts;
     for (size_t i = 0; i < nd; ++i) dens[i] /= nk;
     memcpy(R_out, P.Rl.data(), P.Rl.size() * sizeof(int32_t));
     // E = <H_0> + <H_int> in the Hartree-Fock state of the last iteration (density x_out in the field of x_in): the band energy
-    // minus E_dc = sum_e V [n_a^in n_b^out + n_b^in n_a^out - n_a^out n_b^out - 2 Re(conj(D^in) D^out) + |D^out|^2], which is
-    // 1/2 sum V [n n - |D|^2] at the fixed point
-    double edc = 0.0;
-    for (int e = 0; e < nint; ++e) {
-        const int pa = P.occ_par[int_ab[2 * e]], pb = P.occ_par[int_ab[2 * e + 1]];
-        double t = x_in[pa] * x_out[pb] + x_in[pb] * x_out[pa] - x_out[pa] * x_out[pb];
-        if (P.fock) {
-            const int pr = P.nocc + 2 * e, pi = pr + 1;
-            t += -2.0 * (x_in[pr] * x_out[pr] + x_in[pi] * x_out[pi]) + x_out[pr] * x_out[pr] + x_out[pi] * x_out[pi];
-        }
-        edc += int_V[e] * t;
-    }
+    // minus E_dc (mf_edc), which is 1/2 sum V [n n - |D|^2] at the fixed point
+    const double edc = mf_edc(nint, int_ab, int_V, P.occ_par, true, P.fock ? P.nocc : -1, -1, x_in, x_out);
     const double eband = sums[1] / nk, ent = sums[2] / nk;
     energies[0] = eband - edc;
     energies[1] = ent;

@@ -1358,13 +1358,14 @@ class tb_model(object):
         return out[0] if single else out
 
     # ------------------------------------------------------------------ self-consistent Hartree-Fock (extension)
-    def _mf_entries(self, interaction, U):
-        """The state-indexed interaction of `mean_field_mesh`: (ab (nint, 2) int32, R (nint, dim_k) int32, V (nint,) float).
-        Orbital entries act on total densities (all four spin pairs on a spinful model); U adds (o up, o down, R = 0)."""
+    def _mf_entries(self, what, interaction, U):
+        """The state-indexed interaction of `mean_field_mesh`, for the call `what`: (ab (nint, 2) int32, R (nint, dim_k) int32,
+        V (nint,) float).  Orbital entries act on total densities (all four spin pairs on a spinful model); U adds
+        (o up, o down, R = 0)."""
         ns, no, dk = self._nspin, self._norb, self._dim_k
         ab, Rs, Vs = [], [], []
         if interaction is None and U is None:
-            raise Exception("\n\nmean_field_mesh needs an interaction list, U, or both.")
+            raise Exception("\n\n%s needs an interaction list, U, or both." % what)
         for ent in (interaction if interaction is not None else []):
             try:
                 V, i, j, R = ent
@@ -1403,7 +1404,7 @@ class tb_model(object):
                 Rs.append(np.zeros(dk, dtype=np.int64))
                 Vs.append(float(Uv[o]))
         if not ab:
-            raise Exception("\n\nmean_field_mesh needs an interaction list, U, or both.")
+            raise Exception("\n\n%s needs an interaction list, U, or both." % what)
         seen = set()
         for (a, b), R in zip(ab, Rs):
             k1, k2 = (a, b) + tuple(int(x) for x in R), (b, a) + tuple(int(-x) for x in R)
@@ -1412,6 +1413,69 @@ class tb_model(object):
             seen.add(k1)
         return (np.ascontiguousarray(ab, dtype=np.int32), np.ascontiguousarray(np.array(Rs).reshape(len(ab), dk), dtype=np.int32),
                 np.ascontiguousarray(Vs, dtype=float))
+
+    def _scf_args(self, what, nsta_max, n_electrons, fermi_level, filling_rule, history, max_iter, check_every, mixing, tol):
+        """The argument checks `mean_field_mesh` and `bdg_mesh` share: (filling, mixing, tol) as floats.  The rule that ties
+        n_electrons to the mesh is the caller's: filling_rule(filling) raises where it is broken, and is asked where it always
+        was, behind the checks of the filling itself and before those of the loop."""
+        if self._nsta > nsta_max:
+            raise Exception("\n\n%s: at most %d states." % (what, nsta_max))
+        if (n_electrons is None) == (fermi_level is None):
+            raise Exception("\n\n%s needs exactly one of n_electrons and fermi_level." % what)
+        try:
+            filling = float(n_electrons if n_electrons is not None else fermi_level)
+        except (TypeError, ValueError):
+            raise Exception("\n\nn_electrons / fermi_level must be one finite number.")
+        if not np.isfinite(filling):
+            raise Exception("\n\nn_electrons / fermi_level must be finite.")
+        if n_electrons is not None:
+            filling_rule(filling)
+        if not _is_int(history) or history < 0 or history > 8:
+            raise Exception("\n\nhistory must be an integer in 0..8.")
+        if not _is_int(max_iter) or max_iter < 1 or max_iter > 65536:
+            raise Exception("\n\nmax_iter must be an integer in 1..65536.")
+        if not _is_int(check_every) or check_every < 1:
+            raise Exception("\n\ncheck_every must be an integer >= 1.")
+        mixing, tol = float(mixing), float(tol)
+        if not 0.0 < mixing <= 1.0:
+            raise Exception("\n\nmixing must satisfy 0 < mixing <= 1.")
+        if not (np.isfinite(tol) and tol >= 0.0):
+            raise Exception("\n\ntol must be finite and >= 0.")
+        return filling, mixing, tol
+
+    def _mf_layout(self, what, ab, Rs):
+        """The layout of the parameters as include/tbk.h has it: (touched states ascending, state -> parameter of its occupation,
+        their number, the distinct lattice vectors: R = 0 first, then in order of first appearance; at most 4096)."""
+        touched = sorted(set(ab.reshape(-1).tolist()))
+        occ_par = {a: p for p, a in enumerate(touched)}
+        Rl = [tuple([0] * self._dim_k)]
+        for R in Rs:
+            if tuple(int(x) for x in R) not in Rl:
+                Rl.append(tuple(int(x) for x in R))
+        if len(Rl) > 4096:
+            raise Exception("\n\n%s: at most 4096 distinct lattice vectors." % what)
+        return touched, occ_par, len(touched), Rl
+
+    @staticmethod
+    def _mf_table_args(tables, mesh, ab, Rs, Vs):
+        """The arguments tbk_mean_field_mesh and tbk_bdg_mesh take from orb to int_V: the flattened tables of the bare model, the mesh
+        and the state-indexed interaction."""
+        orb_per, onsite, hop_i, hop_j, hop_R, hop_amp = tables
+        return (_lib.dptr(orb_per), _lib.dptr(onsite.view(float)), len(hop_i), _lib.iptr(hop_i), _lib.iptr(hop_j),
+                _lib.iptr(hop_R.reshape(-1)) if hop_R.size else None, _lib.dptr(hop_amp.view(float)) if hop_amp.size else None,
+                _lib.iptr(mesh), len(Vs), _lib.iptr(ab.reshape(-1)), _lib.iptr(Rs.reshape(-1)), _lib.dptr(Vs))
+
+    def _scf_result(self, what, res, info, nR, res_hist, occ_hist, x_in, x_out, key):
+        """The fields every self-consistent result carries: residuals, history, iterations, converged, field, _x, _key."""
+        if int(info[2]) != nR or int(info[3]) != len(x_in):
+            raise Exception("\n\n%s: the library laid out %d lattice vectors and %d parameters, not %d and %d."
+                            % (what, info[2], info[3], nR, len(x_in)))
+        its, ns, no, n = int(info[0]), self._nspin, self._norb, self._nsta
+        res.residuals = res_hist[:its].copy()
+        res.history = occ_hist[:its].reshape((its, no, 2) if ns == 2 else (its, n)).copy()
+        res.iterations, res.converged = its, bool(info[1])
+        res.field, res._x, res._key = x_out, x_in, key
+        return its
 
     def mean_field_mesh(self, mesh_size, interaction=None, n_electrons=None, fermi_level=None, kT=0.0, U=None, start=None, fock=True,
                         mixing=0.5, history=4, tol=1e-10, max_iter=200, check_every=1):
@@ -1439,17 +1503,7 @@ class tb_model(object):
         Fixed-order sums: two calls give the same bits, and max_iter = k gives the first k history rows of a longer run."""
         mesh, nk, kT = self._occ_args("mean_field_mesh", mesh_size, kT)
         ns, no, dk, n = self._nspin, self._norb, self._dim_k, self._nsta
-        if n > 2048:
-            raise Exception("\n\nmean_field_mesh: at most 2048 states.")
-        if (n_electrons is None) == (fermi_level is None):
-            raise Exception("\n\nmean_field_mesh needs exactly one of n_electrons and fermi_level.")
-        try:
-            filling = float(n_electrons if n_electrons is not None else fermi_level)
-        except (TypeError, ValueError):
-            raise Exception("\n\nn_electrons / fermi_level must be one finite number.")
-        if not np.isfinite(filling):
-            raise Exception("\n\nn_electrons / fermi_level must be finite.")
-        if n_electrons is not None:
+        def filling_rule(filling):
             if kT > 0.0:
                 if not 0.0 < filling < n:
                     raise Exception("\n\nn_electrons must lie in the open interval (0, %d) at kT > 0." % n)
@@ -1459,32 +1513,15 @@ class tb_model(object):
                     raise Exception("\n\nn_electrons times the %d mesh points must be an integer at kT = 0." % nk)
                 if round(c) < 1 or round(c) > n * nk - 1:
                     raise Exception("\n\nn_electrons must select between 1 and %d of the %d levels at kT = 0." % (n * nk - 1, n * nk))
-        if not _is_int(history) or history < 0 or history > 8:
-            raise Exception("\n\nhistory must be an integer in 0..8.")
-        if not _is_int(max_iter) or max_iter < 1 or max_iter > 65536:
-            raise Exception("\n\nmax_iter must be an integer in 1..65536.")
-        if not _is_int(check_every) or check_every < 1:
-            raise Exception("\n\ncheck_every must be an integer >= 1.")
-        mixing, tol = float(mixing), float(tol)
-        if not 0.0 < mixing <= 1.0:
-            raise Exception("\n\nmixing must satisfy 0 < mixing <= 1.")
-        if not (np.isfinite(tol) and tol >= 0.0):
-            raise Exception("\n\ntol must be finite and >= 0.")
-        ab, Rs, Vs = self._mf_entries(interaction, U)
+
+        filling, mixing, tol = self._scf_args("mean_field_mesh", 2048, n_electrons, fermi_level, filling_rule, history, max_iter,
+                                              check_every, mixing, tol)
+        ab, Rs, Vs = self._mf_entries("mean_field_mesh", interaction, U)
         nint = len(Vs)
         fock = bool(fock)
-        # the parameters, as include/tbk.h lays them out
-        touched = sorted(set(ab.reshape(-1).tolist()))
-        occ_par = {a: p for p, a in enumerate(touched)}
-        nocc = len(touched)
+        touched, occ_par, nocc, Rl = self._mf_layout("mean_field_mesh", ab, Rs)
         npar = nocc + (2 * nint if fock else 0)
-        Rl = [tuple([0] * dk)]
-        for R in Rs:
-            if tuple(int(x) for x in R) not in Rl:
-                Rl.append(tuple(int(x) for x in R))
         nR = len(Rl)
-        if nR > 4096:
-            raise Exception("\n\nmean_field_mesh: at most 4096 distinct lattice vectors.")
         if nR * n * n > 2 ** 22:
             raise Exception("\n\nmean_field_mesh: nR * nsta**2 must be at most 2**22.")
         if npar > 2 ** 20:
@@ -1515,7 +1552,6 @@ class tb_model(object):
                 x0[occ_par[a]] = occ[a]
         if x0 is not None and not np.all(np.isfinite(x0)):
             raise Exception("\n\nstart must be finite.")
-        orb_per, onsite, hop_i, hop_j, hop_R, hop_amp = self._flat_tables()
         ctx = _lib.default_context()
         x_in, x_out, mu = np.zeros(npar), np.zeros(npar), np.zeros(1)
         dens = np.zeros((nR, n, n), dtype=complex)
@@ -1524,18 +1560,13 @@ class tb_model(object):
         res_hist, occ_hist = np.zeros(max_iter), np.zeros((max_iter, n))
         info = np.zeros(5, dtype=np.int32)
         _lib.check(_lib.lib.tbk_mean_field_mesh(
-            ctx.handle, dk, no, ns, _lib.dptr(orb_per), _lib.dptr(onsite.view(float)), len(hop_i), _lib.iptr(hop_i), _lib.iptr(hop_j),
-            _lib.iptr(hop_R.reshape(-1)) if hop_R.size else None, _lib.dptr(hop_amp.view(float)) if hop_amp.size else None,
-            _lib.iptr(mesh), nint, _lib.iptr(ab.reshape(-1)), _lib.iptr(Rs.reshape(-1)), _lib.dptr(Vs), int(fock),
+            ctx.handle, dk, no, ns, *self._mf_table_args(self._flat_tables(), mesh, ab, Rs, Vs), int(fock),
             int(n_electrons is not None), filling, kT, 0 if x0 is None else 1, None if x0 is None else _lib.dptr(x0), mixing,
             int(history), tol, int(max_iter), int(check_every), _lib.dptr(x_in), _lib.dptr(x_out), _lib.dptr(mu),
             _lib.dptr(dens.view(float)), _lib.iptr(R_out.reshape(-1)), _lib.dptr(energies), _lib.dptr(res_hist), _lib.dptr(occ_hist),
             _lib.iptr(info)))
-        if int(info[2]) != nR or int(info[3]) != npar:
-            raise Exception("\n\nmean_field_mesh: the library laid out %d lattice vectors and %d parameters, not %d and %d."
-                            % (info[2], info[3], nR, npar))
-        its = int(info[0])
         res = mean_field_result()
+        self._scf_result("mean_field_mesh", res, info, nR, res_hist, occ_hist, x_in, x_out, key)
         res.model = self._mf_model(ab, Rs, Vs, fock, occ_par, nocc, x_in)
         res.fermi_level = float(mu[0])
         d0 = dens[0]
@@ -1545,11 +1576,7 @@ class tb_model(object):
         res.density, res.R_list = dens, R_out
         res.energy, res.entropy, res.free_energy = float(energies[0]), float(energies[1]), float(energies[2])
         res.band_energy, res.n_electrons = float(energies[3]), float(energies[4])
-        res.residuals = res_hist[:its].copy()
-        res.history = occ_hist[:its].reshape((its, no, 2) if ns == 2 else (its, n)).copy()
-        res.iterations, res.converged = its, bool(info[1])
         res.resident = bool(info[4])
-        res.field, res._x, res._key = x_out, x_in, key
         return res
 
     def _mf_model(self, ab, Rs, Vs, fock, occ_par, nocc, x):
@@ -1592,7 +1619,7 @@ class tb_model(object):
             raise Exception("\n\nfermi_level must be one finite number.")
         if not np.isfinite(mu):
             raise Exception("\n\nfermi_level must be finite.")
-        ab, Rs, Vs = self._mf_entries(interaction, U)
+        ab, Rs, Vs = self._mf_entries(what, interaction, U)
         sel = []
         for name, arg, kind in (("valence", valence, "occupied"), ("conduction", conduction, "empty")):
             if arg is None:
@@ -1936,30 +1963,14 @@ class tb_model(object):
         the same bits, and max_iter = k gives the first k history rows of a longer run."""
         mesh, nk, kT = self._occ_args("bdg_mesh", mesh_size, kT)
         ns, no, dk, n = self._nspin, self._norb, self._dim_k, self._nsta
-        if n > 1024:
-            raise Exception("\n\nbdg_mesh: at most 1024 states.")
-        if (n_electrons is None) == (fermi_level is None):
-            raise Exception("\n\nbdg_mesh needs exactly one of n_electrons and fermi_level.")
-        try:
-            filling = float(n_electrons if n_electrons is not None else fermi_level)
-        except (TypeError, ValueError):
-            raise Exception("\n\nn_electrons / fermi_level must be one finite number.")
-        if not np.isfinite(filling):
-            raise Exception("\n\nn_electrons / fermi_level must be finite.")
+        def filling_rule(filling):
+            if not 0.0 < filling < n:
+                raise Exception("\n\nn_electrons must lie in the open interval (0, %d)." % n)
+
+        filling, mixing, tol = self._scf_args("bdg_mesh", 1024, n_electrons, fermi_level, filling_rule, history, max_iter, check_every,
+                                              mixing, tol)
         have_nel = n_electrons is not None
-        if have_nel and not 0.0 < filling < n:
-            raise Exception("\n\nn_electrons must lie in the open interval (0, %d)." % n)
-        if not _is_int(history) or history < 0 or history > 8:
-            raise Exception("\n\nhistory must be an integer in 0..8.")
-        if not _is_int(max_iter) or max_iter < 1 or max_iter > 65536:
-            raise Exception("\n\nmax_iter must be an integer in 1..65536.")
-        if not _is_int(check_every) or check_every < 1:
-            raise Exception("\n\ncheck_every must be an integer >= 1.")
-        mixing, tol, mu_step, seed = float(mixing), float(tol), float(mu_step), float(pairing_seed)
-        if not 0.0 < mixing <= 1.0:
-            raise Exception("\n\nmixing must satisfy 0 < mixing <= 1.")
-        if not (np.isfinite(tol) and tol >= 0.0):
-            raise Exception("\n\ntol must be finite and >= 0.")
+        mu_step, seed = float(mu_step), float(pairing_seed)
         if not (np.isfinite(mu_step) and mu_step > 0.0):
             raise Exception("\n\nmu_step must be finite and > 0.")
         if not np.isfinite(seed):
@@ -1967,25 +1978,14 @@ class tb_model(object):
         hartree, fock, pairing = bool(hartree), bool(fock), bool(pairing)
         if not (hartree or fock or pairing):
             raise Exception("\n\nbdg_mesh: every channel is switched off.")
-        try:
-            ab, Rs, Vs = self._mf_entries(interaction, U)
-        except Exception as err:
-            raise Exception(str(err).replace("mean_field_mesh", "bdg_mesh"))
+        ab, Rs, Vs = self._mf_entries("bdg_mesh", interaction, U)
         nint = len(Vs)
-        touched = sorted(set(ab.reshape(-1).tolist()))
-        occ_par = {a: p for p, a in enumerate(touched)}
-        nocc = len(touched)
+        touched, occ_par, nocc, Rl = self._mf_layout("bdg_mesh", ab, Rs)
         par_d = nocc if fock else -1
         par_f = nocc + (2 * nint if fock else 0) if pairing else -1
         npar = nocc + 2 * nint * (int(fock) + int(pairing)) + int(have_nel)
         par_mu = npar - 1 if have_nel else -1
-        Rl = [tuple([0] * dk)]
-        for R in Rs:
-            if tuple(int(x) for x in R) not in Rl:
-                Rl.append(tuple(int(x) for x in R))
         nR = len(Rl)
-        if nR > 4096:
-            raise Exception("\n\nbdg_mesh: at most 4096 distinct lattice vectors.")
         if npar > 2 ** 20:
             raise Exception("\n\nbdg_mesh: at most 2**20 mean-field parameters.")
         if return_density and nR * 4 * n * n > 2 ** 22:
@@ -2023,24 +2023,18 @@ class tb_model(object):
         if not np.all(np.isfinite(x0)):
             raise Exception("\n\nstart must be finite.")
         bare = self.nambu_model(0.0 if have_nel else filling)
-        orb_per, onsite, hop_i, hop_j, hop_R, hop_amp = bare._flat_tables()
         ctx = _lib.default_context()
         x_in, x_out = np.zeros(npar), np.zeros(npar)
         energies = np.zeros(7)
         res_hist, occ_hist = np.zeros(max_iter), np.zeros((max_iter, n))
         info = np.zeros(5, dtype=np.int32)
         _lib.check(_lib.lib.tbk_bdg_mesh(
-            ctx.handle, dk, n, _lib.dptr(orb_per), _lib.dptr(onsite.view(float)), len(hop_i), _lib.iptr(hop_i), _lib.iptr(hop_j),
-            _lib.iptr(hop_R.reshape(-1)) if hop_R.size else None, _lib.dptr(hop_amp.view(float)) if hop_amp.size else None,
-            _lib.iptr(mesh), nint, _lib.iptr(ab.reshape(-1)), _lib.iptr(Rs.reshape(-1)), _lib.dptr(Vs), int(hartree), int(fock),
+            ctx.handle, dk, n, *self._mf_table_args(bare._flat_tables(), mesh, ab, Rs, Vs), int(hartree), int(fock),
             int(pairing), int(have_nel), filling, kT, _lib.dptr(x0), mu_step, mixing, int(history), tol, int(max_iter),
             int(check_every), _lib.dptr(x_in), _lib.dptr(x_out), _lib.dptr(energies), _lib.dptr(res_hist), _lib.dptr(occ_hist),
             _lib.iptr(info)))
-        if int(info[2]) != nR or int(info[3]) != npar:
-            raise Exception("\n\nbdg_mesh: the library laid out %d lattice vectors and %d parameters, not %d and %d."
-                            % (info[2], info[3], nR, npar))
-        its = int(info[0])
         res = bdg_result()
+        its = self._scf_result("bdg_mesh", res, info, nR, res_hist, occ_hist, x_in, x_out, key)
         mu_in = float(energies[5])
         y = x_in.copy()
         if not hartree:
@@ -2061,10 +2055,6 @@ class tb_model(object):
         res.gap = float(energies[6])
         res.energy, res.entropy, res.free_energy, res.grand_potential = (float(energies[0]), float(energies[1]), float(energies[2]),
                                                                          float(energies[3]))
-        res.residuals = res_hist[:its].copy()
-        res.history = occ_hist[:its].reshape((its, no, 2) if ns == 2 else (its, n)).copy()
-        res.iterations, res.converged = its, bool(info[1])
-        res.field, res._x, res._key = x_out, x_in, key
         res.nambu_density, res.R_list = None, None
         if return_density:
             res.R_list = np.ascontiguousarray(Rl, dtype=np.int32).reshape(nR, dk)
